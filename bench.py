@@ -21,6 +21,10 @@ RetrievalDataset-style collate -> PremiseRetriever.predict_step, which gathers h
 single-state `retrieve()` calls, and the CPU baseline (the oracle on the host cores, bounded sample).
 
 Prints ONE JSON line on rank 0.
+
+`--dump-outputs DIR` also writes what the timed path computed in its last timed step - the query embeddings and the top-k
+scores, ids and counts a caller receives - as DIR/<name>.npy (float32 / float64; at N > 1 one set per rank, suffixed
+_rank<r>).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -437,6 +441,19 @@ def _cpu_model():
     return "unknown"
 
 
+def snapshot_outputs(q, scores, ids, counts) -> dict:
+    """Host copies of one step's results: query embeddings and top-k scores in float32, ids and counts in float64 (exact)."""
+    return {"query_embeddings": q.float().cpu().numpy(), "topk_scores": scores.float().cpu().numpy(),
+            "topk_ids": ids.cpu().numpy().astype(np.float64), "topk_counts": counts.cpu().numpy().astype(np.float64)}
+
+
+def dump_outputs(dirpath: str, arrays: dict, suffix: str = "") -> None:
+    os.makedirs(dirpath, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "--dump-outputs: more than 64 MB"
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), a)
+
+
 class _Leg:
     """``with _Leg(name, errors):`` - an auxiliary measurement whose failure must not cost the headline line: the exception
     is recorded under ``leg_errors[name]`` in the JSON and printed on stderr, and the run goes on."""
@@ -526,6 +543,8 @@ def run_c5(args):
             step(fp8)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
+        if fp8 and args.dump_outputs:  # the line's headline path (the e4m3 index); the bf16 leg below overwrites out_*
+            dump_outputs(args.dump_outputs, snapshot_outputs(q, out_s, out_i, out_c))
         _lib.profile_enable(True)
         for _ in range(args.steps):
             step(fp8)
@@ -675,7 +694,13 @@ def main():
     ap.add_argument("--headline-only", action="store_true",
                     help="skip the premise-encode and scan-only legs (used under rocprofv3 so that every launch of "
                          "the dominant kernel has the step's shape and the stats average is comparable)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's query embeddings and top-k scores / ids / counts as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.plumbing_only and args.dump_outputs:
+        ap.error("--plumbing-only computes nothing to dump")
     if args.config == "c5":
         return run_c5(args)
 
@@ -888,6 +913,9 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs:  # before the passes below overwrite the step's buffers; at N > 1 this rank's merged lists
+        res = snapshot_outputs(q_loc, f_s, f_i, f_c) if world > 1 else snapshot_outputs(q_loc, out_s, out_i, out_c)
+        dump_outputs(args.dump_outputs, res, f"_rank{rank}" if world > 1 else "")
     # second pass, instrumented: an event pair around every launch (rp_profile_*) for the per-kernel split
     _lib.profile_enable(True)
     for _ in range(args.steps):

@@ -24,16 +24,17 @@ _PARITY_MARGINS = {}
 
 @pytest.fixture(scope="session")
 def parity_margins():
-    """Filled by the end-to-end GPU parity tests (G5 / G7 / G9 and G5h / G7h / G9h); written to profiles/r06_parity_margins.json and
-    gpurun_out/parity_margins.json and printed in the terminal summary when the session ends."""
+    """Filled by the end-to-end GPU parity tests (G5 / G7 / G9 and G5h / G7h / G9h); printed in the terminal summary when the
+    session ends, and written as JSON to $RP_PARITY_MARGINS_OUT when that names a file (a plain test run writes nothing)."""
     return _PARITY_MARGINS
 
 
 def pytest_sessionfinish(session, exitstatus):
-    if _PARITY_MARGINS:
+    out = os.environ.get("RP_PARITY_MARGINS_OUT")
+    if _PARITY_MARGINS and out:
         from oracle.parity_margins import write_margins
 
-        write_margins(_PARITY_MARGINS, ROOT)
+        write_margins(_PARITY_MARGINS, out)
 
 
 def pytest_terminal_summary(terminalreporter):

@@ -15,8 +15,7 @@ grep '^{"metric"' $OUT/bench_full.log | tail -1 > $OUT/${R}_bench_unprofiled.jso
 timeout 900 python bench.py --config c5 --steps 5 > $OUT/c5.log 2>&1
 grep '^{"metric"' $OUT/c5.log | tail -1 > $OUT/${R}_c5_byt5base_1m_e4m3.json
 CASES=$R NBYTES=100 bash tools/latency_profile.sh > $OUT/${R}_b1_latency_kernel_stats.txt 2>&1
-timeout 2400 python -m pytest tests/ -x -q -m gpu > $OUT/pytest_gpu.log 2>&1
+RP_PARITY_MARGINS_OUT=$OUT/${R}_parity_margins.json timeout 2400 python -m pytest tests/ -x -q -m gpu > $OUT/pytest_gpu.log 2>&1
 tail -15 $OUT/pytest_gpu.log
-cp gpurun_out/parity_margins.json $OUT/${R}_parity_margins.json 2>/dev/null
 timeout 600 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; tail -3 $OUT/smoke.log
 head -c 1500 $OUT/${R}_bench_unprofiled.json; echo; head -c 600 $OUT/${R}_c5_byt5base_1m_e4m3.json; echo
