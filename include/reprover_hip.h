@@ -43,7 +43,7 @@ enum {
 enum { RP_DT_F32 = 0, RP_DT_BF16 = 1 };
 
 /* ABI / build identification; bumps when a signature changes. */
-int32_t rp_abi_version(void);   /* 6 */
+int32_t rp_abi_version(void);   /* 7 */
 /* Message of the last error returned on this thread ("" if none). */
 const char* rp_last_error(void);
 
@@ -443,6 +443,77 @@ RpStatus rp_dbg_dgrad(const void* A, const void* W, int32_t M, int32_t N, int32_
                       const float* aux1, void* out0, float* out1, int32_t variant, void* stream);
 /* Tuning knobs (integers), e.g. "gemm_variant"; returns RP_E_INVALID for unknown names. */
 RpStatus rp_set_option(const char* name, int32_t value);
+
+
+/* ---------------------------------------------------------------------------------------------
+ * Tactic generator: the T5 decoder of T5ForConditionalGeneration, one beam-search step at a time
+ *   (transformers modeling_t5.py T5Stack.forward as a decoder with a KV cache; generation/utils.py
+ *   _beam_search's top-2nb selection).  reprover_amd/generation.py drives it; DESIGN.md section 9.
+ * ------------------------------------------------------------------------------------------- */
+
+/* T5's unidirectional bucket (bidirectional=False) of rel = key position - query position (<= 0). */
+int32_t rp_relative_position_bucket_causal(int32_t rel, int32_t num_buckets, int32_t max_distance);
+
+/* The encoder's last_hidden_state (final RMSNorm applied) instead of the pooled embedding: same
+ * arguments and workspace as rp_encode_varlen; out = device bf16 [total_tokens, d_model]. */
+RpStatus rp_encode_hidden(RpEncoder* enc, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
+                          int32_t total_tokens, int32_t max_len, void* out_bf16, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+typedef struct RpT5DecoderLayerWeights {
+  const void* ln_self;   /* decoder.block.i.layer.0.layer_norm.weight          [d_model]         */
+  const void* q;         /* ...layer.0.SelfAttention.{q,k,v}.weight            [H*d_kv, d_model] */
+  const void* k;
+  const void* v;
+  const void* o;         /* ...layer.0.SelfAttention.o.weight                  [d_model, H*d_kv] */
+  const void* ln_cross;  /* ...layer.1.layer_norm.weight                       [d_model]         */
+  const void* cq;        /* ...layer.1.EncDecAttention.{q,k,v}.weight          [H*d_kv, d_model] */
+  const void* ck;
+  const void* cv;
+  const void* co;        /* ...layer.1.EncDecAttention.o.weight                [d_model, H*d_kv] */
+  const void* ln_ff;     /* ...layer.2.layer_norm.weight                       [d_model]         */
+  const void* wi_0;      /* ...layer.2.DenseReluDense.wi_0.weight              [d_ff, d_model]   */
+  const void* wi_1;
+  const void* wo;        /* ...layer.2.DenseReluDense.wo.weight                [d_model, d_ff]   */
+} RpT5DecoderLayerWeights;
+
+typedef struct RpT5DecoderWeights {
+  const void* embed;            /* shared.weight                               [vocab, d_model]  */
+  const void* rel_bias;         /* decoder.block.0 SelfAttention relative_attention_bias [buckets, H] */
+  const void* final_ln;         /* decoder.final_layer_norm.weight             [d_model]         */
+  const void* lm_head;          /* lm_head.weight (shared.weight when tied)    [vocab, d_model]  */
+  const RpT5DecoderLayerWeights* layers; /* host array, cfg->num_layers (= num_decoder_layers)   */
+  int32_t tie_word_embeddings;  /* 1: hidden * d_model^-0.5 before lm_head (HF's tied rescale)   */
+} RpT5DecoderWeights;
+
+typedef struct RpDecoder RpDecoder;
+
+/* cfg->num_layers is the number of DECODER layers.  Packs bf16 weights (synchronises once). */
+RpStatus rp_decoder_create(const RpT5Config* cfg, const RpT5DecoderWeights* weights, int32_t weight_dtype,
+                           RpDecoder** out);
+void     rp_decoder_destroy(RpDecoder* dec);
+/* Workspace of one generate call: cross K/V of a src_len source, the self-attention cache of
+ * max_len * num_beams rows per layer, activations of num_beams rows.  0 on bad arguments. */
+size_t   rp_decoder_workspace_bytes(const RpDecoder* dec, int32_t num_beams, int32_t max_len, int32_t src_len);
+/* Cross-attention K/V of every layer from the encoder states enc_bf16 [src_len, d_model] (one
+ * GEMM against the concatenated [layers*2*H*d_kv, d_model] weight), into the workspace. */
+RpStatus rp_decoder_cross_kv(RpDecoder* dec, const void* enc_bf16, int32_t src_len, int32_t num_beams,
+                             int32_t max_len, void* workspace, size_t workspace_bytes, void* stream);
+/* One decode step at position t for nb beams (same workspace as rp_decoder_cross_kv):
+ *   tokens    device int32 [nb], the beams' tokens at position t
+ *   ancestry  device int32 [nb, anc_stride]: cache row read by beam b at position p <= t; row
+ *             t*nb + b is the one this step writes for beam b (entries are clamped to the cache)
+ *   logprobs  device fp32 [nb, vocab]: log_softmax of the lm_head logits
+ * A row's output does not depend on the other rows of the launch. */
+RpStatus rp_decoder_step(RpDecoder* dec, const int32_t* tokens, const int32_t* ancestry, int32_t anc_stride,
+                         int32_t nb, int32_t t, int32_t max_len, int32_t src_len, float* logprobs,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* Top k (<= 128, <= nb*vocab) of logprobs[b, v] + running[b] over the flattened [nb*vocab], in
+ * descending order, ties to the lower flat index (torch.topk): score, token (v), parent (b).
+ * workspace: nb * min(k, vocab) * 8 bytes of device memory. */
+RpStatus rp_beam_select(const float* logprobs, const float* running, int32_t nb, int32_t vocab, int32_t k,
+                        float* scores, int32_t* tokens, int32_t* parents, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 #ifdef __cplusplus
 }

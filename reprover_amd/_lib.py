@@ -18,7 +18,7 @@ RP_OK = 0
 RP_DT_F32, RP_DT_BF16 = 0, 1
 RP_TOPK_AUTO, RP_TOPK_DENSE = 0, 1
 RP_EPI_STORE_BF16, RP_EPI_RESID, RP_EPI_GEGLU_BF16, RP_EPI_RESID8 = 0, 1, 2, 3
-ABI_VERSION = 6  # round 5 added exports, enum values and changed the workspace planes without a bump: 5 was skipped
+ABI_VERSION = 7  # 7: the tactic generator's decoder (rp_decoder_*, rp_beam_select, rp_encode_hidden); 5 was skipped
 KERNEL_CLASSES = ["embed", "rmsnorm", "gemm_qkv", "attention", "gemm_o", "gemm_wi", "gemm_wo", "pool", "scan",
                   "select", "scan_sample", "bwd_dgrad", "bwd_wgrad", "bwd_attention", "bwd_other", "optimizer", "collective"]
 
@@ -47,6 +47,22 @@ class RpT5Weights(C.Structure):
         ("rel_bias", C.c_void_p),
         ("final_ln", C.c_void_p),
         ("layers", C.POINTER(RpT5LayerWeights)),
+    ]
+
+
+class RpT5DecoderLayerWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("ln_self", "q", "k", "v", "o", "ln_cross", "cq", "ck", "cv", "co", "ln_ff",
+                                          "wi_0", "wi_1", "wo")]
+
+
+class RpT5DecoderWeights(C.Structure):
+    _fields_ = [
+        ("embed", C.c_void_p),
+        ("rel_bias", C.c_void_p),
+        ("final_ln", C.c_void_p),
+        ("lm_head", C.c_void_p),
+        ("layers", C.POINTER(RpT5DecoderLayerWeights)),
+        ("tie_word_embeddings", C.c_int32),
     ]
 
 
@@ -195,6 +211,28 @@ SIGNATURES = {
     "rp_dbg_attention": (
         C.c_int32,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+    ),
+    "rp_relative_position_bucket_causal": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "rp_encode_hidden": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+         C.c_void_p],
+    ),
+    "rp_decoder_create": (C.c_int32, [C.POINTER(RpT5Config), C.POINTER(RpT5DecoderWeights), C.c_int32,
+                                      C.POINTER(C.c_void_p)]),
+    "rp_decoder_destroy": (None, [C.c_void_p]),
+    "rp_decoder_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "rp_decoder_cross_kv": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
+    "rp_decoder_step": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+         C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "rp_beam_select": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_size_t, C.c_void_p],
     ),
     "rp_set_option": (C.c_int32, [C.c_char_p, C.c_int32]),
     "rp_profile_enable": (C.c_int32, [C.c_int32]),

@@ -1,0 +1,559 @@
+// libreprover_hip - the tactic generator's T5 decoder (include/reprover_hip.h).
+//
+// One beam-search step for nb <= 64 beams: per layer RMSNorm -> fused self QKV -> causal self-attention over the
+// ancestry-addressed cache -> o + residual -> RMSNorm -> cross q -> cross-attention over the source -> o + residual ->
+// gated-GELU FFN; then the final norm, lm_head and log_softmax.  Precision: bf16 weights and GEMM operands, fp32
+// accumulation, statistics, softmax and residual stream, fp32 log-probs.
+//
+// Every output element of every kernel here is computed by a reduction whose order depends only on the shapes (K, the
+// key count), never on which other rows share the launch or where the row sits in it: a row's log-probs are the same
+// bits batched or alone.
+#include <algorithm>
+#include <vector>
+
+#include "rp_util.h"
+
+using namespace rp;
+
+namespace {
+
+constexpr int DEC_MAX_BEAMS = 64;
+constexpr int DEC_MAX_KIT = 8;          // GEMM K <= 8 * 512 = 4096 (a wave holds its weight row in registers)
+constexpr int DEC_MAX_KEYS = 8192;      // attention keys per launch (fp32 scores in dynamic LDS: 32 KB)
+constexpr int DEC_SELECT_MAX_K = 128;   // 2 * DEC_MAX_BEAMS
+constexpr int DEC_SELECT_ROW = 512;     // the per-row sort covers vocab <= 512
+constexpr int DEC_MERGE = 8192;         // nb * min(k, vocab) candidates <= 64 * 128
+
+template <typename T>
+__global__ void dec_to_bf16_kernel(bf16_t* __restrict__ dst, const T* __restrict__ src, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = f2bf((float)src[i]);
+}
+template <>
+__global__ void dec_to_bf16_kernel<bf16_t>(bf16_t* __restrict__ dst, const bf16_t* __restrict__ src, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = src[i];
+}
+template <typename T>
+__global__ void dec_to_f32_kernel(float* __restrict__ dst, const T* __restrict__ src, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = (float)src[i];
+}
+template <>
+__global__ void dec_to_f32_kernel<bf16_t>(float* __restrict__ dst, const bf16_t* __restrict__ src, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = bf2f(src[i]);
+}
+
+__device__ __forceinline__ float wave_sum64(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max64(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// 256-thread block reductions in a fixed order (wave butterflies, then the four waves in index order)
+__device__ __forceinline__ float block_sum256(float v, float* red) {
+  v = wave_sum64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float block_max256(float v, float* red) {
+  v = wave_max64(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// x[b, :] = embed[tokens[b], :]   (fp32 residual stream)
+__global__ __launch_bounds__(256) void dec_embed_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ embed,
+                                                        float* __restrict__ x, int D, int V) {
+  const int b = blockIdx.x;
+  const int tok = min(max(tokens[b], 0), V - 1);
+  for (int c = threadIdx.x; c < D; c += 256) x[(size_t)b * D + c] = embed[(size_t)tok * D + c];
+}
+
+// out[b, :] = bf16(w * (x * rsqrt(mean(x^2) + eps)) * scale)   (T5LayerNorm; scale = d_model^-0.5 on a tied lm_head)
+__global__ __launch_bounds__(256) void dec_rmsnorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                          bf16_t* __restrict__ out, int D, float eps, float scale) {
+  __shared__ float red[4];
+  const float* row = x + (size_t)blockIdx.x * D;
+  float ss = 0.f;
+  for (int c = threadIdx.x; c < D; c += 256) ss = fmaf(row[c], row[c], ss);
+  ss = block_sum256(ss, red);
+  const float r = rsqrtf(ss / (float)D + eps);
+  for (int c = threadIdx.x; c < D; c += 256) out[(size_t)blockIdx.x * D + c] = f2bf(w[c] * (row[c] * r) * scale);
+}
+
+enum DecEpi { EPI_BF16 = 0, EPI_RESID = 1, EPI_F32 = 2, EPI_GEGLU = 3 };
+
+__device__ __forceinline__ float dot8(uint4 a, uint4 w, float acc) {
+  const uint32_t av[4] = {a.x, a.y, a.z, a.w}, wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    acc = fmaf(__uint_as_float(av[i] << 16), __uint_as_float(wv[i] << 16), acc);
+    acc = fmaf(__uint_as_float(av[i] & 0xffff0000u), __uint_as_float(wv[i] & 0xffff0000u), acc);
+  }
+  return acc;
+}
+__device__ __forceinline__ float gelu_tanh(float u) {
+  return 0.5f * u * (1.f + tanhf(0.7978845608028654f * (u + 0.044715f * u * u * u)));
+}
+
+// out[m, n] = sum_k A[m, k] W[n, k] for rows m in [m0, m0 + 64) of this workgroup row, one wave per output column n.  The
+// wave keeps its weight row (KIT x 512 elements) in registers and streams the A rows past it; lane l covers the 16-byte
+// pieces l, l + 64, ... of K, and the 64 lane sums are combined by one xor butterfly: the same chain for every (m, n).
+// EPI_GEGLU: column n reads W rows n (wi_0) and n + N (wi_1), out = gelu_new(a0) * a1.
+template <int KIT, int EPI>
+__global__ __launch_bounds__(256) void dec_gemm_kernel(const bf16_t* __restrict__ A, int lda, int M,
+                                                       const bf16_t* __restrict__ W, int N, int K,
+                                                       void* __restrict__ out, int ldo) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const int nk = K >> 3;  // 16-byte pieces per row
+  uint4 w0[KIT], w1[KIT];
+#pragma unroll
+  for (int i = 0; i < KIT; ++i) {
+    const int j = lane + 64 * i;
+    w0[i] = (j < nk) ? reinterpret_cast<const uint4*>(W + (size_t)n * K)[j] : make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (EPI == EPI_GEGLU)
+      w1[i] = (j < nk) ? reinterpret_cast<const uint4*>(W + (size_t)(n + N) * K)[j] : make_uint4(0u, 0u, 0u, 0u);
+  }
+  const int m1 = min(M, (int)(blockIdx.y + 1) * 64);
+  for (int m = blockIdx.y * 64; m < m1; ++m) {
+    const uint4* a = reinterpret_cast<const uint4*>(A + (size_t)m * lda);
+    float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < KIT; ++i) {
+      const int j = lane + 64 * i;
+      const uint4 av = (j < nk) ? a[j] : make_uint4(0u, 0u, 0u, 0u);
+      acc0 = dot8(av, w0[i], acc0);
+      if constexpr (EPI == EPI_GEGLU) acc1 = dot8(av, w1[i], acc1);
+    }
+    acc0 = wave_sum64(acc0);
+    if constexpr (EPI == EPI_GEGLU) acc1 = wave_sum64(acc1);
+    if (lane == 0) {
+      if constexpr (EPI == EPI_BF16) reinterpret_cast<bf16_t*>(out)[(size_t)m * ldo + n] = f2bf(acc0);
+      if constexpr (EPI == EPI_RESID) reinterpret_cast<float*>(out)[(size_t)m * ldo + n] += acc0;
+      if constexpr (EPI == EPI_F32) reinterpret_cast<float*>(out)[(size_t)m * ldo + n] = acc0;
+      if constexpr (EPI == EPI_GEGLU) reinterpret_cast<bf16_t*>(out)[(size_t)m * ldo + n] = f2bf(gelu_tanh(acc0) * acc1);
+    }
+  }
+}
+
+template <int EPI>
+RpStatus launch_dec_gemm(const bf16_t* A, int lda, int M, const bf16_t* W, int N, int K, void* out, int ldo,
+                         hipStream_t s) {
+  const int kit = (K / 8 + 63) / 64;
+  const dim3 grid((N + 3) / 4, (M + 63) / 64);
+#define DEC_GEMM_CASE(I) \
+  case I: hipLaunchKernelGGL((dec_gemm_kernel<I, EPI>), grid, dim3(256), 0, s, A, lda, M, W, N, K, out, ldo); break;
+  switch (kit) {
+    DEC_GEMM_CASE(1) DEC_GEMM_CASE(2) DEC_GEMM_CASE(3) DEC_GEMM_CASE(4)
+    DEC_GEMM_CASE(5) DEC_GEMM_CASE(6) DEC_GEMM_CASE(7) DEC_GEMM_CASE(8)
+    default: return fail(RP_E_UNSUPPORTED, "decoder GEMM K=%d > %d", K, DEC_MAX_KIT * 512);
+  }
+#undef DEC_GEMM_CASE
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// One (head, beam) per workgroup: softmax(q k^T + bias) v over `len` keys, d_kv = 64, fp32 scores in dynamic LDS.
+// Key p lives in row r(p) of kv (r = anc[b * astride + p] clamped to [0, rows), or p); K at column koff + 64 h, V at
+// voff + 64 h.  bias (self-attention): tab[h * nbias + min(len - 1 - p, nbias - 1)] (distance query - key).
+__global__ __launch_bounds__(256) void dec_attention_kernel(const bf16_t* __restrict__ q, int ldq,
+                                                            const bf16_t* __restrict__ kv, int ldkv, int koff, int voff,
+                                                            int rows, const int32_t* __restrict__ anc, int astride,
+                                                            const float* __restrict__ tab, int nbias, int len,
+                                                            bf16_t* __restrict__ out, int ldo) {
+  extern __shared__ float s_sc[];
+  __shared__ float s_q[64];
+  __shared__ float red[4];
+  __shared__ float s_part[4][64];
+  const int h = blockIdx.x, b = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < 64) s_q[tid] = bf2f(q[(size_t)b * ldq + h * 64 + tid]);
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int p = tid; p < len; p += 256) {
+    int r = anc ? anc[(size_t)b * astride + p] : p;
+    r = min(max(r, 0), rows - 1);
+    const uint4* kr = reinterpret_cast<const uint4*>(kv + (size_t)r * ldkv + koff + h * 64);
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint4 k8 = kr[i];
+      const uint32_t kw[4] = {k8.x, k8.y, k8.z, k8.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc = fmaf(s_q[8 * i + 2 * e], __uint_as_float(kw[e] << 16), acc);
+        acc = fmaf(s_q[8 * i + 2 * e + 1], __uint_as_float(kw[e] & 0xffff0000u), acc);
+      }
+    }
+    if (tab) acc += tab[(size_t)h * nbias + min(len - 1 - p, nbias - 1)];
+    s_sc[p] = acc;
+    mx = fmaxf(mx, acc);
+  }
+  mx = block_max256(mx, red);
+  float sum = 0.f;
+  for (int p = tid; p < len; p += 256) {
+    const float e = __expf(s_sc[p] - mx);
+    s_sc[p] = e;
+    sum += e;
+  }
+  sum = block_sum256(sum, red);  // (its leading barrier also publishes s_sc)
+  float acc = 0.f;
+  for (int p = wave; p < len; p += 4) {
+    int r = anc ? anc[(size_t)b * astride + p] : p;
+    r = min(max(r, 0), rows - 1);
+    acc = fmaf(s_sc[p], bf2f(kv[(size_t)r * ldkv + voff + h * 64 + lane]), acc);
+  }
+  s_part[wave][lane] = acc;
+  __syncthreads();
+  if (tid < 64) {
+    const float o = ((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) / sum;
+    out[(size_t)b * ldo + h * 64 + tid] = f2bf(o);
+  }
+}
+
+// cache row t * nb + b of layer l <- the k, v columns of qkv[b]
+__global__ __launch_bounds__(256) void dec_store_kv_kernel(const bf16_t* __restrict__ qkv, int inner,
+                                                           bf16_t* __restrict__ cache, int row0) {
+  const int b = blockIdx.x;
+  for (int c = threadIdx.x; c < 2 * inner; c += 256)
+    cache[(size_t)(row0 + b) * 2 * inner + c] = qkv[(size_t)b * 3 * inner + inner + c];
+}
+
+__global__ __launch_bounds__(256) void dec_log_softmax_kernel(float* __restrict__ x, int V) {
+  __shared__ float red[4];
+  float* row = x + (size_t)blockIdx.x * V;
+  float mx = -INFINITY;
+  for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, row[c]);
+  mx = block_max256(mx, red);
+  float s = 0.f;
+  for (int c = threadIdx.x; c < V; c += 256) s += __expf(row[c] - mx);
+  s = block_sum256(s, red);
+  const float ls = logf(s);
+  for (int c = threadIdx.x; c < V; c += 256) row[c] = (row[c] - mx) - ls;
+}
+
+// ---- beam selection ---------------------------------------------------------------------------------------------------
+// Keys sort descending: high 32 bits = the score made order-preserving as an unsigned integer, low 32 = ~flat index (a
+// lower index ranks higher on equal scores, torch.topk's order).
+__device__ __forceinline__ uint64_t sel_key(float v, uint32_t idx) {
+  uint32_t u = __float_as_uint(v);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((uint64_t)u << 32) | (uint64_t)(~idx);
+}
+__device__ __forceinline__ float key_score(uint64_t k) {
+  uint32_t u = (uint32_t)(k >> 32);
+  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  return __uint_as_float(u);
+}
+// bitonic sort, descending, of n (power of two) keys in LDS by the whole workgroup
+__device__ void bitonic_desc(uint64_t* s, int n) {
+  for (int size = 2; size <= n; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const bool desc = (i & size) == 0;
+          const uint64_t a = s[i], c = s[j];
+          if (desc ? (a < c) : (a > c)) {
+            s[i] = c;
+            s[j] = a;
+          }
+        }
+      }
+    }
+  __syncthreads();
+}
+
+// per beam row: the top kr keys of logprobs[b, :] + running[b]
+__global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restrict__ lp, const float* __restrict__ running,
+                                                            int V, int kr, uint64_t* __restrict__ cand) {
+  __shared__ uint64_t s[DEC_SELECT_ROW];
+  const int b = blockIdx.x;
+  const float rb = running[b];
+  for (int i = threadIdx.x; i < DEC_SELECT_ROW; i += 256)
+    s[i] = (i < V) ? sel_key(lp[(size_t)b * V + i] + rb, (uint32_t)(b * V + i)) : 0ull;
+  bitonic_desc(s, DEC_SELECT_ROW);
+  for (int i = threadIdx.x; i < kr; i += 256) cand[(size_t)b * kr + i] = s[i];
+}
+
+__global__ __launch_bounds__(1024) void beam_merge_kernel(const uint64_t* __restrict__ cand, int n, int V, int k,
+                                                          float* __restrict__ scores, int32_t* __restrict__ tokens,
+                                                          int32_t* __restrict__ parents) {
+  __shared__ uint64_t s[DEC_MERGE];
+  int np2 = 1;
+  while (np2 < n) np2 <<= 1;
+  for (int i = threadIdx.x; i < np2; i += 1024) s[i] = (i < n) ? cand[i] : 0ull;
+  bitonic_desc(s, np2);
+  for (int i = threadIdx.x; i < k; i += 1024) {
+    const uint32_t idx = ~(uint32_t)s[i];
+    scores[i] = key_score(s[i]);
+    tokens[i] = (int32_t)(idx % (uint32_t)V);
+    parents[i] = (int32_t)(idx / (uint32_t)V);
+  }
+}
+
+}  // namespace
+
+struct RpDecoder {
+  RpT5Config cfg;
+  int inner = 0, nbias = 0, tied = 0;
+  float* embed = nullptr;     // [V, D] fp32
+  float* final_ln = nullptr;  // [D]
+  bf16_t* lm_head = nullptr;  // [V, D]
+  bf16_t* cross_kv_w = nullptr;  // [L * 2 * inner, D]: layer l's k rows at 2 l inner, v rows at (2 l + 1) inner
+  float* bias_tab = nullptr;     // [H, nbias] by distance query - key (clamped)
+  struct Layer {
+    float *ln_self, *ln_cross, *ln_ff;
+    bf16_t *wqkv, *wo, *cq, *co, *wi, *wo2;
+  };
+  std::vector<Layer> layers;
+  std::vector<void*> allocs;
+};
+
+namespace {
+struct DecWs {
+  bf16_t* ckv;    // [S, L * 2 * inner]
+  bf16_t* cache;  // [L][max_len * nb, 2 * inner]
+  float* x;       // [nb, D]
+  bf16_t* h;      // [nb, D] + [nb, F]
+  bf16_t* qkv;    // [nb, 3 * inner]
+  bf16_t* att;    // [nb, inner]
+  size_t bytes;
+};
+DecWs dec_carve(const RpDecoder* d, int nb, int max_len, int S, char* base) {
+  const size_t D = d->cfg.d_model, F = d->cfg.d_ff, inner = d->inner, L = d->cfg.num_layers;
+  DecWs w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += align_up(bytes, 256);
+    return p;
+  };
+  w.ckv = (bf16_t*)take((size_t)S * L * 2 * inner * 2);
+  w.cache = (bf16_t*)take(L * (size_t)max_len * nb * 2 * inner * 2);
+  w.x = (float*)take((size_t)nb * D * 4);
+  w.h = (bf16_t*)take((size_t)nb * (D + F) * 2);  // the normed rows, then the FFN's inner rows
+  w.qkv = (bf16_t*)take((size_t)nb * 3 * inner * 2);
+  w.att = (bf16_t*)take((size_t)nb * inner * 2);
+  w.bytes = off;
+  return w;
+}
+
+template <typename T>
+RpStatus dec_pack(RpDecoder* d, const RpT5DecoderWeights* w) {
+  const RpT5Config& c = d->cfg;
+  const size_t D = c.d_model, F = c.d_ff, inner = d->inner, V = c.vocab_size, L = c.num_layers;
+  auto alloc = [&](size_t bytes, void** p) -> RpStatus {
+    RP_HIP(hipMalloc(p, bytes));
+    d->allocs.push_back(*p);
+    return RP_OK;
+  };
+  auto bf = [&](bf16_t* dst, const void* src, size_t n) {
+    hipLaunchKernelGGL((dec_to_bf16_kernel<T>), dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, 0, dst,
+                       (const T*)src, (int64_t)n);
+  };
+  auto f32 = [&](float* dst, const void* src, size_t n) {
+    hipLaunchKernelGGL((dec_to_f32_kernel<T>), dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, 0, dst,
+                       (const T*)src, (int64_t)n);
+  };
+  RpStatus st;
+  if ((st = alloc(V * D * 4, (void**)&d->embed))) return st;
+  f32(d->embed, w->embed, V * D);
+  if ((st = alloc(D * 4, (void**)&d->final_ln))) return st;
+  f32(d->final_ln, w->final_ln, D);
+  if ((st = alloc(V * D * 2, (void**)&d->lm_head))) return st;
+  bf(d->lm_head, w->lm_head, V * D);
+  if ((st = alloc(L * 2 * inner * D * 2, (void**)&d->cross_kv_w))) return st;
+  d->layers.resize(L);
+  for (size_t i = 0; i < L; ++i) {
+    const RpT5DecoderLayerWeights& s = w->layers[i];
+    RpDecoder::Layer& l = d->layers[i];
+    if ((st = alloc(D * 4, (void**)&l.ln_self)) || (st = alloc(D * 4, (void**)&l.ln_cross)) ||
+        (st = alloc(D * 4, (void**)&l.ln_ff)) || (st = alloc(3 * inner * D * 2, (void**)&l.wqkv)) ||
+        (st = alloc(D * inner * 2, (void**)&l.wo)) || (st = alloc(inner * D * 2, (void**)&l.cq)) ||
+        (st = alloc(D * inner * 2, (void**)&l.co)) || (st = alloc(2 * F * D * 2, (void**)&l.wi)) ||
+        (st = alloc(D * F * 2, (void**)&l.wo2)))
+      return st;
+    f32(l.ln_self, s.ln_self, D);
+    f32(l.ln_cross, s.ln_cross, D);
+    f32(l.ln_ff, s.ln_ff, D);
+    bf(l.wqkv, s.q, inner * D);
+    bf(l.wqkv + inner * D, s.k, inner * D);
+    bf(l.wqkv + 2 * inner * D, s.v, inner * D);
+    bf(l.wo, s.o, D * inner);
+    bf(l.cq, s.cq, inner * D);
+    bf(l.co, s.co, D * inner);
+    bf(d->cross_kv_w + (2 * i) * inner * D, s.ck, inner * D);
+    bf(d->cross_kv_w + (2 * i + 1) * inner * D, s.cv, inner * D);
+    bf(l.wi, s.wi_0, F * D);
+    bf(l.wi + F * D, s.wi_1, F * D);
+    bf(l.wo2, s.wo, D * F);
+    RP_CHECK_LAUNCH();
+  }
+  // relative-position bias by distance j = query - key in [0, nbias): beyond 2 * max_distance every bucket is the last
+  const int nbk = c.rel_num_buckets, H = c.num_heads;
+  d->nbias = 2 * c.rel_max_distance + 1;
+  std::vector<float> raw((size_t)nbk * H);
+  {
+    float* tmp;
+    RP_HIP(hipMalloc((void**)&tmp, raw.size() * 4));
+    hipLaunchKernelGGL((dec_to_f32_kernel<T>), dim3((nbk * H + 255) / 256), dim3(256), 0, 0, tmp, (const T*)w->rel_bias,
+                       (int64_t)nbk * H);
+    RP_HIP(hipMemcpy(raw.data(), tmp, raw.size() * 4, hipMemcpyDeviceToHost));
+    RP_HIP(hipFree(tmp));
+  }
+  std::vector<float> tab((size_t)H * d->nbias);
+  for (int j = 0; j < d->nbias; ++j) {
+    const int bk = rp_relative_position_bucket_causal(-j, nbk, c.rel_max_distance);
+    for (int h = 0; h < H; ++h) tab[(size_t)h * d->nbias + j] = raw[(size_t)bk * H + h];
+  }
+  if ((st = alloc(tab.size() * 4, (void**)&d->bias_tab))) return st;
+  RP_HIP(hipMemcpy(d->bias_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  RP_HIP(hipDeviceSynchronize());
+  return RP_OK;
+}
+}  // namespace
+
+// modeling_t5.py _relative_position_bucket, bidirectional=False: n = -min(rel, 0); exact below num_buckets / 2, then
+// logarithmic up to max_distance; float32 arithmetic as torch evaluates it.
+extern "C" int32_t rp_relative_position_bucket_causal(int32_t rel, int32_t num_buckets, int32_t max_distance) {
+  const int n = rel < 0 ? -rel : 0;
+  const int max_exact = num_buckets / 2;
+  if (n < max_exact) return n;
+  float ratio = (float)n / (float)max_exact;
+  float t = logf(ratio) / (float)log((double)max_distance / (double)max_exact) * (float)(num_buckets - max_exact);
+  int large = max_exact + (int)t;
+  return large > num_buckets - 1 ? num_buckets - 1 : large;
+}
+
+extern "C" RpStatus rp_decoder_create(const RpT5Config* cfg, const RpT5DecoderWeights* weights, int32_t weight_dtype,
+                                      RpDecoder** out) {
+  RP_REQUIRE(cfg && weights && out && weights->layers && weights->embed && weights->lm_head, "null argument");
+  if (cfg->d_kv != 64) return fail(RP_E_UNSUPPORTED, "d_kv=%d: the decoder kernels implement d_kv=64", cfg->d_kv);
+  if (cfg->num_layers < 1) return fail(RP_E_INVALID, "num_layers (decoder layers) = %d", cfg->num_layers);
+  if (cfg->d_model % 8 || cfg->d_ff % 8 || cfg->d_model > DEC_MAX_KIT * 512 || cfg->d_ff > DEC_MAX_KIT * 512)
+    return fail(RP_E_UNSUPPORTED, "d_model=%d / d_ff=%d: multiples of 8, at most %d", cfg->d_model, cfg->d_ff,
+                DEC_MAX_KIT * 512);
+  if (cfg->vocab_size < 1 || cfg->vocab_size > DEC_SELECT_ROW)
+    return fail(RP_E_UNSUPPORTED, "vocab_size=%d: the beam selection implements vocab <= %d", cfg->vocab_size,
+                DEC_SELECT_ROW);
+  RP_REQUIRE(cfg->rel_num_buckets >= 2 && cfg->rel_max_distance > cfg->rel_num_buckets / 2, "relative-position config");
+  RP_REQUIRE(weight_dtype == RP_DT_F32 || weight_dtype == RP_DT_BF16, "weight_dtype");
+  RpDecoder* d = new RpDecoder();
+  d->cfg = *cfg;
+  d->inner = cfg->num_heads * cfg->d_kv;
+  d->tied = weights->tie_word_embeddings ? 1 : 0;
+  RpStatus st = weight_dtype == RP_DT_F32 ? dec_pack<float>(d, weights) : dec_pack<bf16_t>(d, weights);
+  if (st != RP_OK) {
+    rp_decoder_destroy(d);
+    return st;
+  }
+  *out = d;
+  return RP_OK;
+}
+
+extern "C" void rp_decoder_destroy(RpDecoder* d) {
+  if (!d) return;
+  for (void* p : d->allocs) (void)hipFree(p);
+  delete d;
+}
+
+static RpStatus dec_check_shape(const RpDecoder* d, int nb, int max_len, int S) {
+  RP_REQUIRE(d, "null decoder");
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "num_beams=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(max_len >= 1 && max_len <= DEC_MAX_KEYS, "max_len=%d (1..%d)", max_len, DEC_MAX_KEYS);
+  RP_REQUIRE(S >= 1 && S <= DEC_MAX_KEYS, "src_len=%d (1..%d)", S, DEC_MAX_KEYS);
+  return RP_OK;
+}
+
+extern "C" size_t rp_decoder_workspace_bytes(const RpDecoder* d, int32_t nb, int32_t max_len, int32_t S) {
+  if (!d || nb < 1 || nb > DEC_MAX_BEAMS || max_len < 1 || max_len > DEC_MAX_KEYS || S < 1 || S > DEC_MAX_KEYS) return 0;
+  return dec_carve(d, nb, max_len, S, nullptr).bytes;
+}
+
+extern "C" RpStatus rp_decoder_cross_kv(RpDecoder* d, const void* enc, int32_t S, int32_t nb, int32_t max_len, void* ws,
+                                        size_t ws_bytes, void* stream_) {
+  RpStatus st = dec_check_shape(d, nb, max_len, S);
+  if (st) return st;
+  RP_REQUIRE(enc, "null encoder states");
+  const DecWs w = dec_carve(d, nb, max_len, S, (char*)ws);
+  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  const int D = d->cfg.d_model, NKV = d->cfg.num_layers * 2 * d->inner;
+  return launch_dec_gemm<EPI_BF16>((const bf16_t*)enc, D, S, d->cross_kv_w, NKV, D, w.ckv, NKV, (hipStream_t)stream_);
+}
+
+extern "C" RpStatus rp_decoder_step(RpDecoder* d, const int32_t* tokens, const int32_t* anc, int32_t astride, int32_t nb,
+                                    int32_t t, int32_t max_len, int32_t S, float* logprobs, void* ws, size_t ws_bytes,
+                                    void* stream_) {
+  RpStatus st = dec_check_shape(d, nb, max_len, S);
+  if (st) return st;
+  RP_REQUIRE(tokens && anc && logprobs, "null argument");
+  RP_REQUIRE(t >= 0 && t < max_len, "t=%d outside [0, max_len=%d)", t, max_len);
+  RP_REQUIRE(astride >= t + 1, "anc_stride=%d < t + 1 = %d", astride, t + 1);
+  const DecWs w = dec_carve(d, nb, max_len, S, (char*)ws);
+  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  hipStream_t s = (hipStream_t)stream_;
+  const RpT5Config& c = d->cfg;
+  const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
+  const float eps = c.layer_norm_eps;
+  const int rows = max_len * nb, ldckv = L * 2 * inner;
+  hipLaunchKernelGGL(dec_embed_kernel, dim3(nb), dim3(256), 0, s, tokens, d->embed, w.x, D, V);
+  for (int i = 0; i < L; ++i) {
+    const RpDecoder::Layer& l = d->layers[i];
+    bf16_t* cache = w.cache + (size_t)i * rows * 2 * inner;
+    // self-attention (modeling_t5.py T5LayerSelfAttention): x += o(attn(rmsnorm(x)))
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(nb), dim3(256), 0, s, w.x, l.ln_self, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, nb, l.wqkv, 3 * inner, D, w.qkv, 3 * inner, s))) return st;
+    hipLaunchKernelGGL(dec_store_kv_kernel, dim3(nb), dim3(256), 0, s, w.qkv, inner, cache, t * nb);
+    hipLaunchKernelGGL(dec_attention_kernel, dim3(H, nb), dim3(256), (t + 1) * sizeof(float), s, w.qkv, 3 * inner,
+                       cache, 2 * inner, 0, inner, rows, anc, astride, d->bias_tab, d->nbias, t + 1, w.att, inner);
+    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, nb, l.wo, D, inner, w.x, D, s))) return st;
+    // cross-attention (T5LayerCrossAttention): no position bias, all S source keys
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(nb), dim3(256), 0, s, w.x, l.ln_cross, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, nb, l.cq, inner, D, w.qkv, inner, s))) return st;
+    hipLaunchKernelGGL(dec_attention_kernel, dim3(H, nb), dim3(256), S * sizeof(float), s, w.qkv, inner, w.ckv, ldckv,
+                       2 * i * inner, (2 * i + 1) * inner, S, (const int32_t*)nullptr, 0, (const float*)nullptr, 1, S,
+                       w.att, inner);
+    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, nb, l.co, D, inner, w.x, D, s))) return st;
+    // gated-GELU FFN (T5LayerFF / T5DenseGatedActDense)
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(nb), dim3(256), 0, s, w.x, l.ln_ff, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_GEGLU>(w.h, D, nb, l.wi, F, D, w.h + (size_t)nb * D, F, s))) return st;
+    if ((st = launch_dec_gemm<EPI_RESID>(w.h + (size_t)nb * D, F, nb, l.wo2, D, F, w.x, D, s))) return st;
+  }
+  const float scale = d->tied ? 1.f / sqrtf((float)D) : 1.f;
+  hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(nb), dim3(256), 0, s, w.x, d->final_ln, w.h, D, eps, scale);
+  if ((st = launch_dec_gemm<EPI_F32>(w.h, D, nb, d->lm_head, V, D, logprobs, V, s))) return st;
+  hipLaunchKernelGGL(dec_log_softmax_kernel, dim3(nb), dim3(256), 0, s, logprobs, V);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_beam_select(const float* lp, const float* running, int32_t nb, int32_t V, int32_t k, float* scores,
+                                   int32_t* tokens, int32_t* parents, void* ws, size_t ws_bytes, void* stream_) {
+  RP_REQUIRE(lp && running && scores && tokens && parents, "null argument");
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "nb=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(V >= 1 && V <= DEC_SELECT_ROW, "vocab=%d (1..%d)", V, DEC_SELECT_ROW);
+  RP_REQUIRE(k >= 1 && k <= DEC_SELECT_MAX_K && k <= nb * V, "k=%d (1..min(%d, nb * vocab))", k, DEC_SELECT_MAX_K);
+  const int kr = std::min(k, V);  // a row contributes at most k candidates
+  const size_t need = (size_t)nb * kr * sizeof(uint64_t);
+  if (!ws || ws_bytes < need) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
+  hipStream_t s = (hipStream_t)stream_;
+  uint64_t* cand = (uint64_t*)ws;
+  hipLaunchKernelGGL(beam_row_topk_kernel, dim3(nb), dim3(256), 0, s, lp, running, V, kr, cand);
+  hipLaunchKernelGGL(beam_merge_kernel, dim3(1), dim3(1024), 0, s, cand, nb * kr, V, k, scores, tokens, parents);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}

@@ -99,7 +99,7 @@ void prof_end(hipStream_t stream) {
 
 using namespace rp;
 
-extern "C" int32_t rp_abi_version(void) { return 6; }
+extern "C" int32_t rp_abi_version(void) { return 7; }
 extern "C" const char* rp_last_error(void) { return g_last_error.c_str(); }
 
 extern "C" RpStatus rp_set_option(const char* name, int32_t value) {
@@ -411,10 +411,25 @@ extern "C" size_t rp_encoder_workspace_bytes(const RpEncoder* enc, int32_t total
   return carve(enc, total_tokens, batch, nullptr).bytes;
 }
 
+namespace {
+// last_hidden_state[t] = bf16(final_ln * (x[t] * rs[t])), x decoded from the 24-bit residual form (x24_decode2)
+__global__ __launch_bounds__(256) void hidden_out_kernel(const bf16_t* __restrict__ xb, const uint8_t* __restrict__ xlo,
+                                                         const float* __restrict__ rs, const float* __restrict__ w,
+                                                         bf16_t* __restrict__ out, int D) {
+  const size_t row = (size_t)blockIdx.x * D;
+  const float r = rs[blockIdx.x];
+  for (int c = threadIdx.x; c < D; c += 256) {
+    const uint32_t word = ((uint32_t)xb[row + c] << 16) | ((uint32_t)xlo[row + c] << 8);
+    out[row + c] = f2bf(w[c] * (__uint_as_float(word - 0x8000u) * r));
+  }
+}
+}  // namespace
+
 // The launch sequence of one encoder pass.  T / batch size the grids; when t_dev is given (rp_encode_padded) the
 // real token count is known on the device only: T is then an upper bound, kernels skip the rows beyond *t_dev.
 static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch, int32_t T,
-                            const int32_t* t_dev, void* out, int32_t out_dtype, const Workspace& w, hipStream_t stream) {
+                            const int32_t* t_dev, void* out, int32_t out_dtype, const Workspace& w, hipStream_t stream,
+                            bf16_t* hidden = nullptr) {
   const RpT5Config& c = e->cfg;
   const int D = c.d_model, F = c.d_ff, inner = e->inner, H = c.num_heads;
   const int Tp = (int)align_up((size_t)T, GEMM_M_ALIGN);
@@ -544,6 +559,12 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
     if (st) return st;
   }
   launch_rowscale(true);  // final RMSNorm statistic (the pooling pass reads rs per token row)
+  if (hidden) {  // rp_encode_hidden: last_hidden_state rows instead of the pool
+    hipLaunchKernelGGL(hidden_out_kernel, dim3(T), dim3(256), 0, stream, w.xb, reinterpret_cast<const uint8_t*>(w.xlo), w.rs,
+                       e->final_ln, hidden, D);
+    RP_CHECK_LAUNCH();
+    return RP_OK;
+  }
   {
     ProfScope ps(stream, RP_K_POOL);
     launch_pool_partial(dim3(T / pc + batch), stream, w.xb, w.xlo, w.rs, (const int4*)w.pwork, w.pool, D, pc, e->final_ln, out,
@@ -553,6 +574,17 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
   }
   RP_CHECK_LAUNCH();
   return RP_OK;
+}
+
+extern "C" RpStatus rp_encode_hidden(RpEncoder* e, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch, int32_t T,
+                                     int32_t max_len, void* out, void* workspace, size_t workspace_bytes, void* stream_) {
+  RP_REQUIRE(e && ids && cu_seqlens && out, "null argument");
+  RP_REQUIRE(batch > 0 && T > 0 && max_len > 0 && max_len <= T, "batch=%d total_tokens=%d max_len=%d", batch, T,
+             max_len);
+  Workspace w = carve(e, T, batch, (char*)workspace);
+  if (!workspace || workspace_bytes < w.bytes)
+    return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, w.bytes);
+  return encode_pass(e, ids, cu_seqlens, batch, T, nullptr, nullptr, RP_DT_BF16, w, (hipStream_t)stream_, (bf16_t*)out);
 }
 
 extern "C" RpStatus rp_encode_varlen(RpEncoder* e, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,

@@ -1,0 +1,214 @@
+"""HipT5Generator: T5ForConditionalGeneration.generate (beam search) on libreprover_hip.
+
+The encoder is ``HipT5Encoder`` (``rp_encode_hidden``: last_hidden_state instead of the pool); the decoder is
+``rp_decoder_*`` (one launch sequence per beam-search step); the beam bookkeeping is
+``reprover_amd.generation.beam_search`` with the device top-2nb selection ``rp_beam_select``.  PyTorch tensors are
+containers only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .encoder import HipT5Encoder, _require_gpu
+from .generation import BeamSearchOutput, beam_search
+
+_DEC_KEYS = {
+    "ln_self": "layer.0.layer_norm.weight",
+    "q": "layer.0.SelfAttention.q.weight",
+    "k": "layer.0.SelfAttention.k.weight",
+    "v": "layer.0.SelfAttention.v.weight",
+    "o": "layer.0.SelfAttention.o.weight",
+    "ln_cross": "layer.1.layer_norm.weight",
+    "cq": "layer.1.EncDecAttention.q.weight",
+    "ck": "layer.1.EncDecAttention.k.weight",
+    "cv": "layer.1.EncDecAttention.v.weight",
+    "co": "layer.1.EncDecAttention.o.weight",
+    "ln_ff": "layer.2.layer_norm.weight",
+    "wi_0": "layer.2.DenseReluDense.wi_0.weight",
+    "wi_1": "layer.2.DenseReluDense.wi_1.weight",
+    "wo": "layer.2.DenseReluDense.wo.weight",
+}
+
+
+def load_seq2seq_checkpoint(path: str) -> Tuple[Dict, Dict[str, torch.Tensor]]:
+    """(cfg, state dict) of a HuggingFace T5ForConditionalGeneration directory (config.json + model.safetensors or
+    pytorch_model.bin).  A decoder-only checkpoint raises ``ValueError``."""
+    if not os.path.isdir(path):
+        raise FileExistsError(f"Checkpoint {path} does not exist.")
+    with open(os.path.join(path, "config.json")) as fh:
+        hf = json.load(fh)
+    if not hf.get("is_encoder_decoder", hf.get("model_type") in ("t5", "mt5", "umt5")):
+        raise ValueError(f"{path} is not an encoder-decoder (T5ForConditionalGeneration) checkpoint; decoder-only "
+                         "generators (the reference's AutoModelForCausalLM fallback) are not implemented")
+    st = os.path.join(path, "model.safetensors")
+    if os.path.exists(st):
+        from safetensors.torch import load_file
+
+        sd = load_file(st)
+    else:
+        sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
+    if not any(k.startswith("decoder.block.") for k in sd):
+        raise ValueError(f"{path} holds no decoder.* weights: not a T5ForConditionalGeneration checkpoint")
+    cfg = dict(
+        vocab_size=hf["vocab_size"], d_model=hf["d_model"], d_kv=hf["d_kv"], num_heads=hf["num_heads"], d_ff=hf["d_ff"],
+        num_layers=hf["num_layers"], num_decoder_layers=hf.get("num_decoder_layers") or hf["num_layers"],
+        relative_attention_num_buckets=hf.get("relative_attention_num_buckets", 32),
+        relative_attention_max_distance=hf.get("relative_attention_max_distance", 128),
+        layer_norm_epsilon=hf.get("layer_norm_epsilon", 1e-6), feed_forward_proj=hf.get("feed_forward_proj", "relu"),
+        tie_word_embeddings=bool(hf.get("tie_word_embeddings", True)),
+        decoder_start_token_id=hf.get("decoder_start_token_id", 0), eos_token_id=hf.get("eos_token_id", 1),
+    )
+    return cfg, sd
+
+
+class HipT5Decoder:
+    """The decoder weights resident on one GPU + the per-step launch sequence."""
+
+    def __init__(self, cfg: Dict, sd: Dict[str, torch.Tensor], device):
+        if cfg.get("feed_forward_proj", "gated-gelu") != "gated-gelu":
+            raise _lib.HipLibraryError(f"feed_forward_proj={cfg.get('feed_forward_proj')!r} is not implemented")
+        self.device = _require_gpu(device)
+        self.cfg = dict(cfg)
+        self.V = cfg["vocab_size"]
+        L = cfg["num_decoder_layers"]
+        lib = _lib.load()
+        c = _lib.RpT5Config(cfg["vocab_size"], cfg["d_model"], cfg["d_kv"], cfg["num_heads"], cfg["d_ff"], L,
+                            cfg.get("relative_attention_num_buckets", 32), cfg.get("relative_attention_max_distance", 128),
+                            float(cfg.get("layer_norm_epsilon", 1e-6)))
+        tied = bool(cfg.get("tie_word_embeddings", False))
+        if not tied and "lm_head.weight" not in sd:
+            raise ValueError("untied checkpoint without lm_head.weight")
+        with torch.cuda.device(self.device):
+            keep = []
+
+            def dev(name: str) -> int:
+                t = sd[name].detach().to(device=self.device, dtype=torch.float32).contiguous()
+                keep.append(t)
+                return t.data_ptr()
+
+            layers = (_lib.RpT5DecoderLayerWeights * L)()
+            for i in range(L):
+                for fld, key in _DEC_KEYS.items():
+                    setattr(layers[i], fld, dev(f"decoder.block.{i}.{key}"))
+            w = _lib.RpT5DecoderWeights(
+                dev("shared.weight"), dev("decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"),
+                dev("decoder.final_layer_norm.weight"), dev("shared.weight" if tied else "lm_head.weight"), layers,
+                int(tied))
+            handle = C.c_void_p()
+            torch.cuda.synchronize(self.device)
+            _lib.check(lib.rp_decoder_create(C.byref(c), C.byref(w), _lib.RP_DT_F32, C.byref(handle)), "rp_decoder_create")
+            del keep
+        self._lib = lib
+        self._handle = handle
+        self._ws: Optional[torch.Tensor] = None
+        self._sel_ws: Optional[torch.Tensor] = None
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            try:
+                self._lib.rp_decoder_destroy(h)
+            except Exception:
+                pass
+            self._handle = None
+
+    def workspace_bytes(self, nb: int, max_len: int, src_len: int) -> int:
+        return int(self._lib.rp_decoder_workspace_bytes(self._handle, nb, max_len, src_len))
+
+    def start(self, enc_bf16: torch.Tensor, nb: int, max_len: int) -> None:
+        """Cross K/V of one source [S, d_model] bf16 for a search of ``nb`` beams and ``max_len`` positions."""
+        assert enc_bf16.dtype == torch.bfloat16 and enc_bf16.is_contiguous()
+        S = enc_bf16.shape[0]
+        n = self.workspace_bytes(nb, max_len, S)
+        if n == 0:
+            raise _lib.HipLibraryError(f"unsupported generate shape: num_beams={nb} max_len={max_len} src_len={S}")
+        if self._ws is None or self._ws.numel() < n:
+            self._ws = None
+            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self.nb, self.max_len, self.S = nb, max_len, S
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_cross_kv(self._handle, enc_bf16.data_ptr(), S, nb, max_len,
+                                                     self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
+                       "rp_decoder_cross_kv")
+
+    def step(self, tokens: torch.Tensor, ancestry: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """log-probs [nb, V] of one step (``beam_search``'s ``step``; ancestry int [nb, t + 1])."""
+        nb, T = ancestry.shape
+        tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
+        anc = ancestry.to(device=self.device, dtype=torch.int32).contiguous()
+        if out is None:
+            out = torch.empty((nb, self.V), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_step(self._handle, tok.data_ptr(), anc.data_ptr(), T, nb, T - 1, self.max_len,
+                                                 self.S, out.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                 _lib.current_stream()),
+                       "rp_decoder_step")
+        return out
+
+    def select(self, log_probs: torch.Tensor, running: torch.Tensor, k: int):
+        """Device top-k of log_probs + running[:, None] (``rp_beam_select``): (scores, tokens, parents)."""
+        nb, V = log_probs.shape
+        need = nb * min(k, V) * 8
+        if self._sel_ws is None or self._sel_ws.numel() < need:
+            self._sel_ws = torch.empty(max(need, 64 * 128 * 8), dtype=torch.uint8, device=self.device)
+        run = running.to(device=self.device, dtype=torch.float32).contiguous()
+        lp = log_probs.contiguous()
+        scores = torch.empty(k, dtype=torch.float32, device=self.device)
+        toks = torch.empty(k, dtype=torch.int32, device=self.device)
+        par = torch.empty(k, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_beam_select(lp.data_ptr(), run.data_ptr(), nb, V, k, scores.data_ptr(), toks.data_ptr(),
+                                                par.data_ptr(), self._sel_ws.data_ptr(), self._sel_ws.numel(),
+                                                _lib.current_stream()),
+                       "rp_beam_select")
+        return scores, toks, par
+
+
+class HipT5Generator:
+    """Encoder + decoder of one T5ForConditionalGeneration checkpoint on one GPU."""
+
+    def __init__(self, cfg: Dict, sd: Dict[str, torch.Tensor], device):
+        self.cfg = dict(cfg)
+        self.device = _require_gpu(device)
+        enc_sd = {k: v for k, v in sd.items() if k.startswith("encoder.") or k == "shared.weight"}
+        self.encoder = HipT5Encoder(cfg, enc_sd, self.device, keep_master_weights=False)
+        self.decoder = HipT5Decoder(cfg, sd, self.device)
+
+    @classmethod
+    def from_pretrained(cls, path: str, device) -> "HipT5Generator":
+        cfg, sd = load_seq2seq_checkpoint(path)
+        return cls(cfg, sd, device)
+
+    def encode_hidden(self, ids: np.ndarray) -> torch.Tensor:
+        """last_hidden_state [S, d_model] bf16 of one source (int ids including the final EOS)."""
+        ids = np.asarray(ids, dtype=np.int32)
+        S = int(ids.size)
+        enc = self.encoder
+        ids_d = torch.from_numpy(ids).to(self.device)
+        cu = torch.tensor([0, S], dtype=torch.int32, device=self.device)
+        out = torch.empty((S, self.cfg["d_model"]), dtype=torch.bfloat16, device=self.device)
+        n = enc._lib.rp_encoder_workspace_bytes(enc._handle, S, 1)
+        ws = enc._workspace(n)
+        with torch.cuda.device(self.device):
+            _lib.check(enc._lib.rp_encode_hidden(enc._handle, ids_d.data_ptr(), cu.data_ptr(), 1, S, S, out.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _lib.current_stream()),
+                       "rp_encode_hidden")
+        return out
+
+    def generate(self, ids: np.ndarray, num_beams: int, max_length: int, length_penalty: float = 1.0,
+                 trace: Optional[list] = None) -> BeamSearchOutput:
+        """``generate(input_ids, num_beams=n, num_return_sequences=n, length_penalty, max_length, early_stopping=False,
+        do_sample=False)`` for one source.  Reads the selected candidates back once per step (generation.py)."""
+        enc = self.encode_hidden(ids)
+        self.decoder.start(enc, num_beams, max_length)
+        return beam_search(self.decoder.step, num_beams, max_length, length_penalty,
+                           eos_token_id=self.cfg.get("eos_token_id", 1),
+                           decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),
+                           select=self.decoder.select, device=self.device, trace=trace)

@@ -1,0 +1,97 @@
+"""Tactic generators on libreprover_hip, mirroring prover/tactic_generator.py of the reference.
+
+``HuggingFaceGenerator`` loads a T5ForConditionalGeneration checkpoint directory into ``HipT5Generator`` (HIP encoder +
+decoder, beam search with HF's semantics, reprover_amd/generation.py); ``RetrievalAugmentedGenerator`` retrieves premises
+with ``PremiseRetriever`` and generates from the augmented state.  No ``transformers`` import at run time.
+"""
+from __future__ import annotations
+
+from typing import List, Tuple
+
+from ..common import Pos, format_augmented_state, remove_marks, zip_strict
+from ..decoder import HipT5Generator
+from ..retrieval.model import PremiseRetriever
+from ..tokenizer import ByT5Tokenizer, encode_one
+
+
+class TacticGenerator:
+    def initialize(self) -> None:
+        raise NotImplementedError
+
+    async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
+                       num_samples: int) -> List[Tuple[str, float]]:
+        raise NotImplementedError
+
+
+class HuggingFaceGenerator(TacticGenerator):
+    """Beam-search tactic generator (reference :169-243).  ``num_samples`` beams, ``num_samples`` returned sequences,
+    ``max_length=max_oup_seq_len`` (the decoder start token included), ``early_stopping=False``."""
+
+    def __init__(self, model_path: str, device, max_inp_seq_len: int, max_oup_seq_len: int, length_penalty: float,
+                 template: str = "%s"):
+        self.model_path = model_path
+        self.device = device
+        self.max_inp_seq_len = max_inp_seq_len
+        self.max_oup_seq_len = max_oup_seq_len
+        self.length_penalty = length_penalty
+        self.template = template
+
+    def initialize(self) -> None:
+        # A decoder-only checkpoint (the reference's AutoModelForCausalLM fallback) raises ValueError here.
+        self.generator = HipT5Generator.from_pretrained(self.model_path, self.device)
+        self.decoder_only = False
+        self.tokenizer = ByT5Tokenizer()
+
+    def generate_sync(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
+                      num_samples: int) -> List[Tuple[str, float]]:
+        state = self.template % state
+        ids = encode_one(state, self.max_inp_seq_len)  # tokenizer(state, max_length=..., truncation=True)
+        out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty)
+        raw_output_text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
+        raw_scores = out.sequences_scores.tolist()
+        output_text, output_score = [], []
+        for j in range(num_samples):  # :227-243
+            t = remove_marks(raw_output_text[j])
+            if t not in output_text:
+                output_text.append(t)
+                output_score.append(raw_scores[j])
+        return list(zip_strict(output_text, output_score))
+
+    async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
+                       num_samples: int) -> List[Tuple[str, float]]:
+        return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+
+
+class RetrievalAugmentedGenerator(TacticGenerator):
+    """Reference :246-298: retrieve, format the augmented state, generate."""
+
+    def __init__(self, gen_path: str, ret_path: str, indexed_corpus_path: str, device, max_inp_seq_len: int,
+                 max_oup_seq_len: int, length_penalty: float, max_num_retrieved: int) -> None:
+        self.gen_path = gen_path
+        self.ret_path = ret_path
+        self.indexed_corpus_path = indexed_corpus_path
+        self.device = device
+        self.max_inp_seq_len = max_inp_seq_len
+        self.max_oup_seq_len = max_oup_seq_len
+        self.length_penalty = length_penalty
+        self.max_num_retrieved = max_num_retrieved
+        self.hf_gen = HuggingFaceGenerator(gen_path, device, max_inp_seq_len, max_oup_seq_len, length_penalty)
+
+    def initialize(self) -> None:
+        self.hf_gen.initialize()
+        self.retriever = PremiseRetriever.load_hf(self.ret_path, self.max_inp_seq_len, self.device)
+        self.retriever.load_corpus(self.indexed_corpus_path)
+
+    def generate_sync(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
+                      num_samples: int) -> List[Tuple[str, float]]:
+        retrieved_premises, _ = self.retriever.retrieve(state, file_path, theorem_full_name, theorem_pos,
+                                                        self.max_num_retrieved)
+        aug_state = format_augmented_state(state, retrieved_premises, self.max_inp_seq_len)
+        return self.hf_gen.generate_sync(aug_state, file_path, theorem_full_name, theorem_pos, num_samples)
+
+    async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
+                       num_samples: int) -> List[Tuple[str, float]]:
+        return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+
+
+__all__ = ["TacticGenerator", "HuggingFaceGenerator", "RetrievalAugmentedGenerator"]

@@ -112,6 +112,57 @@ def synth_state_dict(cfg: Dict, seed: int = SEED, scale: str = "sharp") -> Dict[
     return sd
 
 
+SEQ2SEQ_CONFIGS: Dict[str, Dict] = {
+    # google/byt5-small as T5ForConditionalGeneration: 12 encoder + 4 decoder layers, untied lm_head (public config.json)
+    "byt5-small": dict(CONFIGS["byt5-small"], num_decoder_layers=4, tie_word_embeddings=False),
+    "tiny": dict(CONFIGS["tiny"], num_decoder_layers=2, tie_word_embeddings=False),
+    "tiny-tied": dict(CONFIGS["tiny"], num_decoder_layers=2, tie_word_embeddings=True),
+}
+
+
+def seq2seq_config(name: str) -> Dict:
+    return dict(SEQ2SEQ_CONFIGS[name])
+
+
+def synth_seq2seq_state_dict(cfg: Dict, seed: int = SEED, scale: str = "hf") -> Dict[str, torch.Tensor]:
+    """HF-keyed fp32 ``T5ForConditionalGeneration`` state dict: ``synth_state_dict``'s encoder (same bytes) plus the
+    decoder (``cfg["num_decoder_layers"]`` blocks: self-attention, cross-attention ``EncDecAttention``, gated-GELU FFN),
+    its own relative-position table, final norm and ``lm_head`` (absent when ``tie_word_embeddings``).  ``scale="hf"``:
+    HF's ``_init_weights`` standard deviations for every matrix (lm_head ~ N(0, 1)); layer-norm weights U(0.5, 1.5)."""
+    if scale != "hf":
+        raise ValueError(f"synth_seq2seq_state_dict implements scale='hf' only, got {scale!r}")
+    sd = synth_state_dict(cfg, seed, "hf")
+    D, dk, H, F, V = cfg["d_model"], cfg["d_kv"], cfg["num_heads"], cfg["d_ff"], cfg["vocab_size"]
+    inner = H * dk
+
+    def normal(name, shape, std):
+        n = int(np.prod(shape))
+        sd[name] = torch.from_numpy((_philox_normal(name, n, seed) * std).astype(np.float32).reshape(shape))
+
+    def ln(name):
+        sd[name] = torch.from_numpy((0.5 + _philox_uniform(name, D, seed)).astype(np.float32))
+
+    sd["decoder.embed_tokens.weight"] = sd["shared.weight"]
+    normal("decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight",
+           (cfg["relative_attention_num_buckets"], H), D**-0.5)
+    for i in range(cfg["num_decoder_layers"]):
+        p = f"decoder.block.{i}.layer."
+        for j, att in ((0, "SelfAttention"), (1, "EncDecAttention")):
+            ln(f"{p}{j}.layer_norm.weight")
+            normal(f"{p}{j}.{att}.q.weight", (inner, D), (D * dk) ** -0.5)
+            normal(f"{p}{j}.{att}.k.weight", (inner, D), D**-0.5)
+            normal(f"{p}{j}.{att}.v.weight", (inner, D), D**-0.5)
+            normal(f"{p}{j}.{att}.o.weight", (D, inner), inner**-0.5)
+        ln(p + "2.layer_norm.weight")
+        normal(p + "2.DenseReluDense.wi_0.weight", (F, D), D**-0.5)
+        normal(p + "2.DenseReluDense.wi_1.weight", (F, D), D**-0.5)
+        normal(p + "2.DenseReluDense.wo.weight", (D, F), F**-0.5)
+    ln("decoder.final_layer_norm.weight")
+    if not cfg.get("tie_word_embeddings", False):
+        normal("lm_head.weight", (V, D), 1.0)
+    return sd
+
+
 # ----------------------------------------------------------------------------------------------
 # Texts
 # ----------------------------------------------------------------------------------------------

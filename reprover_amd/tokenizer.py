@@ -100,3 +100,33 @@ class ByT5Tokenizer:
 
     def packed(self, texts: Sequence[str], max_length: int) -> Tuple[np.ndarray, np.ndarray]:
         return encode_packed(texts, max_length)
+
+
+def decode(ids, skip_special_tokens: bool = True) -> str:
+    """ByT5Tokenizer.decode (tokenization_byt5.py ``_convert_id_to_token`` / ``convert_tokens_to_string``): byte ids
+    (3..258) are ``id - 3``; with ``skip_special_tokens`` pad / eos / unk (0..2) and ``<extra_id_*>`` (259..383) are
+    dropped; the bytes are decoded as UTF-8 with ``errors="ignore"``."""
+    a = np.asarray(ids.tolist() if isinstance(ids, torch.Tensor) else ids, dtype=np.int64).reshape(-1)
+    if not skip_special_tokens:
+        out, buf = [], bytearray()
+        names = {PAD_TOKEN_ID: "<pad>", EOS_TOKEN_ID: "</s>", UNK_TOKEN_ID: "<unk>"}
+        for i in a.tolist():
+            if _OFFSET <= i < _EXTRA_BASE:
+                buf.append(i - _OFFSET)
+                continue
+            out.append(buf.decode("utf-8", errors="ignore"))
+            buf = bytearray()
+            out.append(names.get(i, f"<extra_id_{i - _EXTRA_BASE}>"))
+        out.append(buf.decode("utf-8", errors="ignore"))
+        return "".join(out)
+    keep = a[(a >= _OFFSET) & (a < _EXTRA_BASE)]
+    return (keep - _OFFSET).astype(np.uint8).tobytes().decode("utf-8", errors="ignore")
+
+
+def batch_decode(sequences, skip_special_tokens: bool = True) -> List[str]:
+    """``tokenizer.batch_decode(sequences, skip_special_tokens=...)`` over rows of ids."""
+    return [decode(s, skip_special_tokens) for s in sequences]
+
+
+ByT5Tokenizer.decode = staticmethod(decode)
+ByT5Tokenizer.batch_decode = staticmethod(batch_decode)
