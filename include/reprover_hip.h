@@ -483,7 +483,7 @@ typedef struct RpT5DecoderWeights {
   const void* final_ln;         /* decoder.final_layer_norm.weight             [d_model]         */
   const void* lm_head;          /* lm_head.weight (shared.weight when tied)    [vocab, d_model]  */
   const RpT5DecoderLayerWeights* layers; /* host array, cfg->num_layers (= num_decoder_layers)   */
-  int32_t tie_word_embeddings;  /* 1: hidden * d_model^-0.5 before lm_head (HF's tied rescale)   */
+  int32_t tie_word_embeddings;  /* 1: hidden * d_model^-0.5 before lm_head (HF's scale_decoder_outputs) */
 } RpT5DecoderWeights;
 
 typedef struct RpDecoder RpDecoder;

@@ -246,9 +246,11 @@ __global__ __launch_bounds__(256) void dec_log_softmax_kernel(float* __restrict_
 
 // ---- beam selection ---------------------------------------------------------------------------------------------------
 // Keys sort descending: high 32 bits = the score made order-preserving as an unsigned integer, low 32 = ~flat index (a
-// lower index ranks higher on equal scores, torch.topk's order).
+// lower index ranks higher on equal scores, torch.topk's order).  -0.0 is keyed as +0.0: the two compare equal, so the
+// index decides between them.  NaN scores are outside the contract.
 __device__ __forceinline__ uint64_t sel_key(float v, uint32_t idx) {
   uint32_t u = __float_as_uint(v);
+  if (u == 0x80000000u) u = 0u;
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
   return ((uint64_t)u << 32) | (uint64_t)(~idx);
 }

@@ -65,7 +65,24 @@ def load_seq2seq_checkpoint(path: str) -> Tuple[Dict, Dict[str, torch.Tensor]]:
         tie_word_embeddings=bool(hf.get("tie_word_embeddings", True)),
         decoder_start_token_id=hf.get("decoder_start_token_id", 0), eos_token_id=hf.get("eos_token_id", 1),
     )
+    # transformers 5 writes tie_word_embeddings=true for every T5 and keeps the d_model^-0.5 output rescale in
+    # scale_decoder_outputs; transformers 4 has no such key and rescales exactly when the embeddings are tied
+    cfg["scale_decoder_outputs"] = bool(hf.get("scale_decoder_outputs", cfg["tie_word_embeddings"]))
     return cfg, sd
+
+
+def lm_head_source(cfg: Dict, sd: Dict[str, torch.Tensor]) -> Tuple[str, bool]:
+    """(state-dict key of the lm_head, whether the final hidden state is scaled by d_model^-0.5 before it).  The head is
+    ``lm_head.weight`` whenever the checkpoint holds one, else ``shared.weight`` (a tied checkpoint saves only that); the
+    scale follows ``scale_decoder_outputs`` when the config has it, else ``tie_word_embeddings``."""
+    tied = bool(cfg.get("tie_word_embeddings", False))
+    if "lm_head.weight" in sd:
+        key = "lm_head.weight"
+    elif tied:
+        key = "shared.weight"
+    else:
+        raise ValueError("untied checkpoint without lm_head.weight")
+    return key, bool(cfg.get("scale_decoder_outputs", tied))
 
 
 class HipT5Decoder:
@@ -82,9 +99,7 @@ class HipT5Decoder:
         c = _lib.RpT5Config(cfg["vocab_size"], cfg["d_model"], cfg["d_kv"], cfg["num_heads"], cfg["d_ff"], L,
                             cfg.get("relative_attention_num_buckets", 32), cfg.get("relative_attention_max_distance", 128),
                             float(cfg.get("layer_norm_epsilon", 1e-6)))
-        tied = bool(cfg.get("tie_word_embeddings", False))
-        if not tied and "lm_head.weight" not in sd:
-            raise ValueError("untied checkpoint without lm_head.weight")
+        head, scaled = lm_head_source(cfg, sd)
         with torch.cuda.device(self.device):
             keep = []
 
@@ -99,8 +114,7 @@ class HipT5Decoder:
                     setattr(layers[i], fld, dev(f"decoder.block.{i}.{key}"))
             w = _lib.RpT5DecoderWeights(
                 dev("shared.weight"), dev("decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"),
-                dev("decoder.final_layer_norm.weight"), dev("shared.weight" if tied else "lm_head.weight"), layers,
-                int(tied))
+                dev("decoder.final_layer_norm.weight"), dev(head), layers, int(scaled))
             handle = C.c_void_p()
             torch.cuda.synchronize(self.device)
             _lib.check(lib.rp_decoder_create(C.byref(c), C.byref(w), _lib.RP_DT_F32, C.byref(handle)), "rp_decoder_create")
@@ -109,6 +123,18 @@ class HipT5Decoder:
         self._handle = handle
         self._ws: Optional[torch.Tensor] = None
         self._sel_ws: Optional[torch.Tensor] = None
+
+    @classmethod
+    def from_handle(cls, lib, handle, cfg: Optional[Dict], device) -> "HipT5Decoder":
+        """Wrap a decoder made by ``rp_decoder_create`` elsewhere (the wrapper owns it and destroys it).  With ``handle``
+        None and ``cfg`` None the object only serves ``select`` (``rp_beam_select`` needs no decoder)."""
+        self = cls.__new__(cls)
+        self._lib, self._handle, self.device = lib, handle, torch.device(device)
+        self.cfg = dict(cfg) if cfg else {}
+        self.V = self.cfg.get("vocab_size")
+        self._ws: Optional[torch.Tensor] = None
+        self._sel_ws: Optional[torch.Tensor] = None
+        return self
 
     def __del__(self):
         h = getattr(self, "_handle", None)

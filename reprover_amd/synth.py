@@ -127,13 +127,23 @@ def seq2seq_config(name: str) -> Dict:
 def synth_seq2seq_state_dict(cfg: Dict, seed: int = SEED, scale: str = "hf") -> Dict[str, torch.Tensor]:
     """HF-keyed fp32 ``T5ForConditionalGeneration`` state dict: ``synth_state_dict``'s encoder (same bytes) plus the
     decoder (``cfg["num_decoder_layers"]`` blocks: self-attention, cross-attention ``EncDecAttention``, gated-GELU FFN),
-    its own relative-position table, final norm and ``lm_head`` (absent when ``tie_word_embeddings``).  ``scale="hf"``:
-    HF's ``_init_weights`` standard deviations for every matrix (lm_head ~ N(0, 1)); layer-norm weights U(0.5, 1.5)."""
-    if scale != "hf":
-        raise ValueError(f"synth_seq2seq_state_dict implements scale='hf' only, got {scale!r}")
-    sd = synth_state_dict(cfg, seed, "hf")
+    its own relative-position table, final norm and ``lm_head`` (absent when ``tie_word_embeddings``).
+
+    * ``scale="hf"`` (default; G19 / G20): HF's ``_init_weights`` standard deviations for every matrix (lm_head ~ N(0, 1));
+      layer-norm weights U(0.5, 1.5).
+    * ``scale="sharp"`` (G21 and the decoder parity tests): ``synth_state_dict``'s sharp encoder, the decoder's self- and
+      cross-attention q 4x HF's scale and its relative-position table ~ N(0, 1), the same Philox normals otherwise, so
+      that self-attention is peaked and a wrong bias distance, a dropped key or a wrong ancestry row moves the log-probs.
+      The untied lm_head is tempered to N(0, (4 D^-½)²) (logits std ≈ 4 instead of ≈ sqrt(D)), so that a bf16 rounding
+      flip in the final hidden state moves a log-prob by hundredths of a nat, not by nats, at ByT5-small's width.
+    """
+    if scale not in SCALES:
+        raise ValueError(f"scale must be one of {SCALES}, got {scale!r}")
+    sd = synth_state_dict(cfg, seed, scale)
     D, dk, H, F, V = cfg["d_model"], cfg["d_kv"], cfg["num_heads"], cfg["d_ff"], cfg["vocab_size"]
     inner = H * dk
+    q_std = (D * dk) ** -0.5 if scale == "hf" else 0.5 * D**-0.5
+    table_std = D**-0.5 if scale == "hf" else 1.0
 
     def normal(name, shape, std):
         n = int(np.prod(shape))
@@ -144,12 +154,12 @@ def synth_seq2seq_state_dict(cfg: Dict, seed: int = SEED, scale: str = "hf") -> 
 
     sd["decoder.embed_tokens.weight"] = sd["shared.weight"]
     normal("decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight",
-           (cfg["relative_attention_num_buckets"], H), D**-0.5)
+           (cfg["relative_attention_num_buckets"], H), table_std)
     for i in range(cfg["num_decoder_layers"]):
         p = f"decoder.block.{i}.layer."
         for j, att in ((0, "SelfAttention"), (1, "EncDecAttention")):
             ln(f"{p}{j}.layer_norm.weight")
-            normal(f"{p}{j}.{att}.q.weight", (inner, D), (D * dk) ** -0.5)
+            normal(f"{p}{j}.{att}.q.weight", (inner, D), q_std)
             normal(f"{p}{j}.{att}.k.weight", (inner, D), D**-0.5)
             normal(f"{p}{j}.{att}.v.weight", (inner, D), D**-0.5)
             normal(f"{p}{j}.{att}.o.weight", (D, inner), inner**-0.5)
@@ -159,7 +169,7 @@ def synth_seq2seq_state_dict(cfg: Dict, seed: int = SEED, scale: str = "hf") -> 
         normal(p + "2.DenseReluDense.wo.weight", (D, F), F**-0.5)
     ln("decoder.final_layer_norm.weight")
     if not cfg.get("tie_word_embeddings", False):
-        normal("lm_head.weight", (V, D), 1.0)
+        normal("lm_head.weight", (V, D), 1.0 if scale == "hf" else 4 * D**-0.5)
     return sd
 
 

@@ -1,7 +1,7 @@
-"""Generate the tactic-generator fixtures G18 - G20 with HuggingFace transformers on CPU.
+"""Generate the tactic-generator fixtures G18 - G21 with HuggingFace transformers on CPU.
 
 Authoring container only; only the resulting data files are committed.  Usage:
-    python tests/golden/make_golden_generate.py [g18 g19 g20]   (default: all)
+    python tests/golden/make_golden_generate.py [g18 g19 g20 g21]   (default: all)
 
 G18  unidirectional relative-position buckets (T5Attention._relative_position_bucket(bidirectional=False)) over
      key - query in [-2200, 0], and ByT5Tokenizer.batch_decode(skip_special_tokens=True) cases.
@@ -9,6 +9,10 @@ G19  teacher-forced decoder log-probs of T5ForConditionalGeneration in fp32 and 
      and the ByT5-small-shaped synthetic seq2seq weights (synth.synth_seq2seq_state_dict, HF init scales).
 G20  generate(num_beams, num_return_sequences=num_beams, length_penalty, max_length, early_stopping=False,
      do_sample=False) in fp32 and bf16 over a grid, with the per-step top-2nb candidates of the fp32 run.
+G21  teacher-forced fp32 decoder log-probs for three tiny models: (a) the sharp family (synth_seq2seq_state_dict
+     scale="sharp") along a 520-position target, (b) tiny-tied at HF scale, (c) a transformers-5-style checkpoint:
+     lm_head = shared, scale_decoder_outputs=False.  Stored: the log-prob of the next target token at every position, and
+     full rows at a few positions (self-attention bucket edges, the 256-key boundaries of the attention kernel).
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ G20_EOS_BOOST = 1.6  # lm_head's EOS row scaled so that some grid points finish 
 G20_GRID = [(nb, lp, ml) for nb in (1, 4, 8, 64) for lp in (0.0, 1.0, -0.5) for ml in (6, 20)]
 
 
-def hf_model(cfg, sd, dtype=torch.float32):
+def hf_model(cfg, sd, dtype=torch.float32, scale_decoder_outputs=None):
     c = T5Config(vocab_size=cfg["vocab_size"], d_model=cfg["d_model"], d_kv=cfg["d_kv"], d_ff=cfg["d_ff"],
                  num_layers=cfg["num_layers"], num_decoder_layers=cfg["num_decoder_layers"], num_heads=cfg["num_heads"],
                  feed_forward_proj="gated-gelu", tie_word_embeddings=cfg["tie_word_embeddings"], dropout_rate=0.0,
@@ -50,7 +54,8 @@ def hf_model(cfg, sd, dtype=torch.float32):
     with torch.no_grad():
         m.shared.weight.copy_(sd["shared.weight"])
     assert m.encoder.embed_tokens.weight is m.shared.weight and m.decoder.embed_tokens.weight is m.shared.weight
-    m.config.scale_decoder_outputs = bool(cfg["tie_word_embeddings"])
+    m.config.scale_decoder_outputs = bool(cfg["tie_word_embeddings"] if scale_decoder_outputs is None
+                                          else scale_decoder_outputs)
     return m.to(dtype)
 
 
@@ -162,7 +167,40 @@ def g20():
     np.savez_compressed(os.path.join(OUT, "g20_generate.npz"), **arrays)
 
 
+# name -> (seq2seq config, weight scale, scale_decoder_outputs, source bytes, target positions, full-row positions)
+G21_MODELS = {
+    "a": ("tiny", "sharp", False, 300, 520,
+          [0, 1, 2, 15, 16, 17, 31, 32, 63, 64, 100, 127, 128, 129, 200, 255, 256, 257, 258, 300, 400, 510, 511, 519]),
+    "b": ("tiny-tied", "hf", True, 200, 160, [0, 15, 16, 17, 127, 128, 129, 159]),
+    "c": ("tiny-tied", "hf", False, 200, 160, [0, 15, 16, 17, 127, 128, 129, 159]),
+}
+
+
+def g21():
+    arrays, meta = {}, {}
+    for name, (cname, scale, sdo, n_src, T, rows) in G21_MODELS.items():
+        cfg = synth.seq2seq_config(cname)
+        sd = synth.synth_seq2seq_state_dict(cfg, scale=scale)
+        m = hf_model(cfg, sd, scale_decoder_outputs=sdo)
+        src, _ = source_ids(n_src, 210 + ord(name))
+        rng = np.random.default_rng(21 + ord(name))
+        tgt = np.concatenate([[0], rng.integers(3, 259, size=T)]).astype(np.int64)  # inputs tgt[:T], labels tgt[1:]
+        with torch.no_grad():
+            lp = torch.log_softmax(m(input_ids=torch.from_numpy(src)[None],
+                                     decoder_input_ids=torch.from_numpy(tgt[:T])[None]).logits[0].float(), -1)
+        arrays[f"{name}_src"] = src.astype(np.int32)
+        arrays[f"{name}_tgt"] = tgt.astype(np.int32)
+        arrays[f"{name}_lp_label"] = lp[torch.arange(T), torch.from_numpy(tgt[1:])].numpy().astype(np.float32)
+        arrays[f"{name}_rows"] = np.array(rows, dtype=np.int32)
+        arrays[f"{name}_lp_rows"] = lp[rows].numpy().astype(np.float32)
+        meta[name] = dict(config=cname, scale=scale, scale_decoder_outputs=sdo, source_bytes=n_src, positions=T)
+        print(f"g21 {name}: {cname} {scale} scale_decoder_outputs={sdo}, src {n_src}, positions {T}, "
+              f"label lp range [{float(arrays[f'{name}_lp_label'].min()):.2f}, {float(arrays[f'{name}_lp_label'].max()):.2f}]")
+    arrays["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
+    np.savez_compressed(os.path.join(OUT, "g21_decoder_long.npz"), **arrays)
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
-    for name in sys.argv[1:] or ["g18", "g19", "g20"]:
-        {"g18": g18, "g19": g19, "g20": g20}[name]()
+    for name in sys.argv[1:] or ["g18", "g19", "g20", "g21"]:
+        {"g18": g18, "g19": g19, "g20": g20, "g21": g21}[name]()
