@@ -515,6 +515,28 @@ RpStatus rp_beam_select(const float* logprobs, const float* running, int32_t nb,
                         float* scores, int32_t* tokens, int32_t* parents, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* Teacher-forced seq2seq forward (T5ForConditionalGeneration(input_ids, attention_mask, labels)) over
+ * `batch` (source, target) pairs packed varlen; DESIGN.md section 10.  src_cu / tgt_cu are HOST int32
+ * [batch + 1] prefix sums (start at 0): source b is rows src_cu[b] .. src_cu[b+1] of enc_bf16, target b
+ * positions tgt_cu[b] .. tgt_cu[b+1] of tokens / labels.  Every source and target holds at most 8192
+ * tokens; a pair may be empty (0 target tokens), a non-empty target needs a non-empty source.
+ *   enc_bf16        device bf16 [src_cu[batch], d_model]: rp_encode_hidden over the sources
+ *   tokens          device int32 [tgt_cu[batch]]: decoder input ids (labels shifted right, start token first)
+ *   labels          device int32 [tgt_cu[batch]]: target ids; < 0 (HF's -100) is ignored
+ *   label_logprobs  device fp32 [tgt_cu[batch]]: log p(label), 0 where ignored
+ *   loss_sum_count  device fp64 [2]: sum of -log p over the counted labels, their count (a fixed-order sum)
+ *   logprob_rows    NULL or device fp32 [tgt_cu[batch], vocab]: every position's log_softmax row
+ * labels >= vocab are outside the contract (the host layer rejects them); they come out as ignored.
+ * A pair's outputs do not depend on the other pairs of the launch.  It reads a second, interleaved copy
+ * of the FFN-in weights that rp_decoder_create packs (2 * layers * d_ff * d_model bf16 bytes).
+ * Workspace: rp_decoder_forward_workspace_bytes (0 on bad arguments, rp_last_error says why). */
+size_t   rp_decoder_forward_workspace_bytes(const RpDecoder* dec, const int32_t* src_cu, const int32_t* tgt_cu,
+                                            int32_t batch);
+RpStatus rp_decoder_forward(RpDecoder* dec, const void* enc_bf16, const int32_t* src_cu, const int32_t* tokens,
+                            const int32_t* labels, const int32_t* tgt_cu, int32_t batch, float* label_logprobs,
+                            double* loss_sum_count, float* logprob_rows, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

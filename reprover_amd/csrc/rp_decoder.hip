@@ -11,7 +11,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "rp_util.h"
+#include "rp_decoder_common.h"
 
 using namespace rp;
 
@@ -45,52 +45,6 @@ __global__ void dec_to_f32_kernel<bf16_t>(float* __restrict__ dst, const bf16_t*
     dst[i] = bf2f(src[i]);
 }
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max64(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// 256-thread block reductions in a fixed order (wave butterflies, then the four waves in index order)
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-  v = wave_sum64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ float block_max256(float v, float* red) {
-  v = wave_max64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-// x[b, :] = embed[tokens[b], :]   (fp32 residual stream)
-__global__ __launch_bounds__(256) void dec_embed_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ embed,
-                                                        float* __restrict__ x, int D, int V) {
-  const int b = blockIdx.x;
-  const int tok = min(max(tokens[b], 0), V - 1);
-  for (int c = threadIdx.x; c < D; c += 256) x[(size_t)b * D + c] = embed[(size_t)tok * D + c];
-}
-
-// out[b, :] = bf16(w * (x * rsqrt(mean(x^2) + eps)) * scale)   (T5LayerNorm; scale = d_model^-0.5 on a tied lm_head)
-__global__ __launch_bounds__(256) void dec_rmsnorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                          bf16_t* __restrict__ out, int D, float eps, float scale) {
-  __shared__ float red[4];
-  const float* row = x + (size_t)blockIdx.x * D;
-  float ss = 0.f;
-  for (int c = threadIdx.x; c < D; c += 256) ss = fmaf(row[c], row[c], ss);
-  ss = block_sum256(ss, red);
-  const float r = rsqrtf(ss / (float)D + eps);
-  for (int c = threadIdx.x; c < D; c += 256) out[(size_t)blockIdx.x * D + c] = f2bf(w[c] * (row[c] * r) * scale);
-}
-
 enum DecEpi { EPI_BF16 = 0, EPI_RESID = 1, EPI_F32 = 2, EPI_GEGLU = 3 };
 
 __device__ __forceinline__ float dot8(uint4 a, uint4 w, float acc) {
@@ -101,9 +55,6 @@ __device__ __forceinline__ float dot8(uint4 a, uint4 w, float acc) {
     acc = fmaf(__uint_as_float(av[i] & 0xffff0000u), __uint_as_float(wv[i] & 0xffff0000u), acc);
   }
   return acc;
-}
-__device__ __forceinline__ float gelu_tanh(float u) {
-  return 0.5f * u * (1.f + tanhf(0.7978845608028654f * (u + 0.044715f * u * u * u)));
 }
 
 // out[m, n] = sum_k A[m, k] W[n, k] for rows m in [m0, m0 + 64) of this workgroup row, one wave per output column n.  The
@@ -309,22 +260,6 @@ __global__ __launch_bounds__(1024) void beam_merge_kernel(const uint64_t* __rest
 
 }  // namespace
 
-struct RpDecoder {
-  RpT5Config cfg;
-  int inner = 0, nbias = 0, tied = 0;
-  float* embed = nullptr;     // [V, D] fp32
-  float* final_ln = nullptr;  // [D]
-  bf16_t* lm_head = nullptr;  // [V, D]
-  bf16_t* cross_kv_w = nullptr;  // [L * 2 * inner, D]: layer l's k rows at 2 l inner, v rows at (2 l + 1) inner
-  float* bias_tab = nullptr;     // [H, nbias] by distance query - key (clamped)
-  struct Layer {
-    float *ln_self, *ln_cross, *ln_ff;
-    bf16_t *wqkv, *wo, *cq, *co, *wi, *wo2;
-  };
-  std::vector<Layer> layers;
-  std::vector<void*> allocs;
-};
-
 namespace {
 struct DecWs {
   bf16_t* ckv;    // [S, L * 2 * inner]
@@ -403,6 +338,14 @@ RpStatus dec_pack(RpDecoder* d, const RpT5DecoderWeights* w) {
     bf(l.wi, s.wi_0, F * D);
     bf(l.wi + F * D, s.wi_1, F * D);
     bf(l.wo2, s.wo, D * F);
+    RP_CHECK_LAUNCH();
+  }
+  // the teacher-forced forward's FFN-in operand (rp_decoder_forward.hip): 2 L d_ff d_model bf16 bytes more
+  if (F % 32 == 0) {
+    if ((st = alloc(L * 2 * F * D * 2, (void**)&d->wi_il))) return st;
+    for (size_t i = 0; i < L; ++i)
+      hipLaunchKernelGGL(dec_interleave_kernel, dim3((unsigned)(2 * F)), dim3(256), 0, 0, d->wi_il + i * 2 * F * D,
+                         d->layers[i].wi, (int)F, (int)D);
     RP_CHECK_LAUNCH();
   }
   // relative-position bias by distance j = query - key in [0, nbias): beyond 2 * max_distance every bucket is the last

@@ -2,8 +2,9 @@
 
 The encoder is ``HipT5Encoder`` (``rp_encode_hidden``: last_hidden_state instead of the pool); the decoder is
 ``rp_decoder_*`` (one launch sequence per beam-search step); the beam bookkeeping is
-``reprover_amd.generation.beam_search`` with the device top-2nb selection ``rp_beam_select``.  PyTorch tensors are
-containers only.
+``reprover_amd.generation.beam_search`` with the device top-2nb selection ``rp_beam_select``.  The teacher-forced loss
+(``forward`` / ``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.
+PyTorch tensors are containers only.
 """
 from __future__ import annotations
 
@@ -17,7 +18,9 @@ import torch
 
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
-from .generation import BeamSearchOutput, beam_search
+from .generation import BeamSearchOutput, beam_search, greedy_search
+
+IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
 
 _DEC_KEYS = {
     "ln_self": "layer.0.layer_norm.weight",
@@ -83,6 +86,45 @@ def lm_head_source(cfg: Dict, sd: Dict[str, torch.Tensor]) -> Tuple[str, bool]:
     else:
         raise ValueError("untied checkpoint without lm_head.weight")
     return key, bool(cfg.get("scale_decoder_outputs", tied))
+
+
+def source_lengths(state_mask) -> np.ndarray:
+    """Per-row token counts of a right-padded 0/1 attention mask (what the tokenizer produces); anything else raises
+    ``ValueError``: the packed encoder reads the first ``n`` ids of a row."""
+    m = np.asarray(state_mask.cpu() if isinstance(state_mask, torch.Tensor) else state_mask).astype(np.int64)
+    if m.ndim != 2:
+        raise ValueError(f"state_mask must be [B, S], got shape {m.shape}")
+    if not np.isin(m, (0, 1)).all():
+        raise ValueError("state_mask must hold only 0 and 1")
+    n = m.sum(1)
+    if not (m == (np.arange(m.shape[1])[None] < n[:, None])).all():
+        raise ValueError("state_mask must be right-padded (ones, then zeros)")
+    return n
+
+
+def shift_and_segment(tactic_ids, decoder_start_token_id: int = 0, pad_token_id: int = 0):
+    """The decoder side of ``T5ForConditionalGeneration(labels=tactic_ids)`` as packed segments.
+
+    Row b's segment ends at its last non-ignored label (causality makes later positions irrelevant; a row with no
+    counted label is empty).  Inputs are HF's ``_shift_right(labels)``: the start token, then the labels shifted by one
+    with ``-100`` replaced by the pad id, so an interior ``-100`` is fed as 0 and excluded from the loss.
+    Returns (tokens int32 [sum T_b], labels int32 [sum T_b], cu int32 [B + 1])."""
+    y = np.asarray(tactic_ids.cpu() if isinstance(tactic_ids, torch.Tensor) else tactic_ids).astype(np.int64)
+    if y.ndim != 2:
+        raise ValueError(f"tactic_ids must be [B, T], got shape {y.shape}")
+    keep = y != IGNORE_INDEX
+    if (y[keep] < 0).any():
+        raise ValueError("tactic_ids holds negative ids other than -100")
+    lens = np.where(keep.any(1), y.shape[1] - np.argmax(keep[:, ::-1], axis=1), 0)
+    toks, labs = [], []
+    for b, n in enumerate(lens):
+        lab = y[b, :n]
+        inp = np.concatenate([[decoder_start_token_id], lab[:-1]]) if n else lab
+        toks.append(np.where(inp == IGNORE_INDEX, pad_token_id, inp))
+        labs.append(lab)
+    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    cat = (lambda a: np.concatenate(a).astype(np.int32)) if len(lens) else (lambda a: np.zeros(0, np.int32))
+    return cat(toks), cat(labs), cu
 
 
 class HipT5Decoder:
@@ -178,6 +220,38 @@ class HipT5Decoder:
                        "rp_decoder_step")
         return out
 
+    def forward(self, enc_bf16: torch.Tensor, src_cu: np.ndarray, tokens: np.ndarray, labels: np.ndarray,
+                tgt_cu: np.ndarray, rows: bool = False):
+        """Teacher-forced pass over packed pairs (``rp_decoder_forward``): enc_bf16 [sum S_b, d_model] device bf16,
+        host cu arrays, host int tokens / labels [sum T_b].  Returns (label log-probs [sum T_b] fp32 on the device,
+        (sum of -log p, count) as floats, the full log-prob rows [sum T_b, V] or None)."""
+        src_cu = np.ascontiguousarray(src_cu, dtype=np.int32)
+        tgt_cu = np.ascontiguousarray(tgt_cu, dtype=np.int32)
+        B = len(tgt_cu) - 1
+        T = int(tgt_cu[-1])
+        lib = self._lib
+        pc = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        n = int(lib.rp_decoder_forward_workspace_bytes(self._handle, pc(src_cu), pc(tgt_cu), B))
+        if n == 0:
+            raise _lib.HipLibraryError("rp_decoder_forward: " + lib.rp_last_error().decode(errors="replace"))
+        if getattr(self, "_fwd_ws", None) is None or self._fwd_ws.numel() < n:
+            self._fwd_ws = None
+            self._fwd_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
+        tok, lab = dev(tokens), dev(labels)
+        lp = torch.empty(T, dtype=torch.float32, device=self.device)
+        sc = torch.empty(2, dtype=torch.float64, device=self.device)
+        out_rows = torch.empty((T, self.V), dtype=torch.float32, device=self.device) if rows else None
+        with torch.cuda.device(self.device):
+            _lib.check(lib.rp_decoder_forward(self._handle, enc_bf16.data_ptr() if T else None, pc(src_cu),
+                                              tok.data_ptr() if T else None, lab.data_ptr() if T else None, pc(tgt_cu), B,
+                                              lp.data_ptr() if T else None, sc.data_ptr(),
+                                              out_rows.data_ptr() if (rows and T) else None, self._fwd_ws.data_ptr(),
+                                              self._fwd_ws.numel(), _lib.current_stream()),
+                       "rp_decoder_forward")
+        s, c = sc.cpu().tolist()
+        return lp, (s, c), out_rows
+
     def select(self, log_probs: torch.Tensor, running: torch.Tensor, k: int):
         """Device top-k of log_probs + running[:, None] (``rp_beam_select``): (scores, tokens, parents)."""
         nb, V = log_probs.shape
@@ -227,6 +301,67 @@ class HipT5Generator:
                                                  ws.data_ptr(), ws.numel(), _lib.current_stream()),
                        "rp_encode_hidden")
         return out
+
+    def encode_hidden_packed(self, ids: np.ndarray, cu: np.ndarray) -> torch.Tensor:
+        """last_hidden_state [sum S_b, d_model] bf16 of several sources packed varlen (``rp_encode_hidden``)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        cu = np.ascontiguousarray(cu, dtype=np.int32)
+        B, S = len(cu) - 1, int(cu[-1])
+        enc = self.encoder
+        out = torch.empty((S, self.cfg["d_model"]), dtype=torch.bfloat16, device=self.device)
+        if S == 0:
+            return out
+        ids_d = torch.from_numpy(ids).to(self.device)
+        cu_d = torch.from_numpy(cu).to(self.device)
+        max_len = int(np.diff(cu).max())
+        ws = enc._workspace(enc._lib.rp_encoder_workspace_bytes(enc._handle, S, B))
+        with torch.cuda.device(self.device):
+            _lib.check(enc._lib.rp_encode_hidden(enc._handle, ids_d.data_ptr(), cu_d.data_ptr(), B, S, max_len,
+                                                 out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream()),
+                       "rp_encode_hidden")
+        return out
+
+    def _teacher_forced(self, state_ids, state_mask, tactic_ids, rows: bool = False):
+        ids = np.asarray(state_ids.cpu() if isinstance(state_ids, torch.Tensor) else state_ids).astype(np.int64)
+        n_src = source_lengths(state_mask)
+        if ids.shape != tuple(state_mask.shape):
+            raise ValueError(f"state_ids {ids.shape} and state_mask {tuple(state_mask.shape)} disagree")
+        tokens, labels, tgt_cu = shift_and_segment(tactic_ids, self.cfg.get("decoder_start_token_id", 0), 0)
+        if len(tgt_cu) - 1 != len(n_src):
+            raise ValueError("state_ids and tactic_ids hold different batch sizes")
+        if (labels >= self.cfg["vocab_size"]).any():
+            raise ValueError(f"tactic_ids holds ids >= vocab_size={self.cfg['vocab_size']}")
+        if ((np.diff(tgt_cu) > 0) & (n_src == 0)).any():
+            raise ValueError("a pair with counted labels has an empty source")
+        src_cu = np.concatenate([[0], np.cumsum(n_src)]).astype(np.int32)
+        packed = np.concatenate([ids[b, :n] for b, n in enumerate(n_src)]) if len(n_src) else np.zeros(0)
+        enc = self.encode_hidden_packed(packed, src_cu) if int(tgt_cu[-1]) else None
+        lp, sc, lp_rows = self.decoder.forward(enc, src_cu, tokens, labels, tgt_cu, rows)
+        return lp, tgt_cu, sc, lp_rows
+
+    def forward(self, state_ids, state_mask, tactic_ids) -> float:
+        """``T5ForConditionalGeneration(input_ids, attention_mask, labels=tactic_ids).loss``: the mean of -log p over the
+        labels that are not -100 (NaN when there are none).  Padded int tensors as the reference's collate makes them."""
+        _, _, (s, c), _ = self._teacher_forced(state_ids, state_mask, tactic_ids)
+        return s / c if c else float("nan")
+
+    def label_log_probs(self, state_ids, state_mask, tactic_ids) -> torch.Tensor:
+        """Per-token log p(label) [B, T] fp32 (on the device), 0 where the label is -100."""
+        lp, tgt_cu, _, _ = self._teacher_forced(state_ids, state_mask, tactic_ids)
+        B, T = np.asarray(tactic_ids.shape if isinstance(tactic_ids, torch.Tensor) else np.shape(tactic_ids))
+        out = torch.zeros((int(B), int(T)), dtype=torch.float32, device=self.device)
+        for b in range(int(B)):
+            n = int(tgt_cu[b + 1] - tgt_cu[b])
+            out[b, :n] = lp[int(tgt_cu[b]) : int(tgt_cu[b]) + n]
+        return out
+
+    def greedy(self, ids: np.ndarray, max_length: int) -> BeamSearchOutput:
+        """``generate(input_ids, num_beams=1, max_length)``: HF's greedy search (argmax, ties to the lowest id), not a
+        one-beam beam search."""
+        enc = self.encode_hidden(ids)
+        self.decoder.start(enc, 1, max_length)
+        return greedy_search(self.decoder.step, max_length, eos_token_id=self.cfg.get("eos_token_id", 1),
+                             decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device)
 
     def generate(self, ids: np.ndarray, num_beams: int, max_length: int, length_penalty: float = 1.0,
                  trace: Optional[list] = None) -> BeamSearchOutput:

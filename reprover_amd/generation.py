@@ -129,3 +129,28 @@ def beam_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], num_
     beam_indices = beam_indices[:nret]
     max_generated = int(((beam_indices + 1).bool()).sum(dim=1).max())  # :3514-3517
     return BeamSearchOutput(sequences[:, : prompt_len + max_generated], beam_scores)
+
+
+def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], max_length: int, eos_token_id: int = 1,
+                  decoder_start_token_id: int = 0, device=None) -> BeamSearchOutput:
+    """``generate(num_beams=1, do_sample=False, max_length=L)``, which HF runs as greedy search (``_sample`` without
+    sampling), not as a one-beam beam search: the argmax token (ties to the lowest id) until EOS or ``max_length``
+    tokens including the start token.  After an EOS candidate a beam search keeps looking and may return a longer
+    sequence; greedy stops.  ``sequences_scores`` holds the sum of the chosen tokens' log-probs (HF reports none)."""
+    if max_length <= 1:
+        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+    seq = [int(decoder_start_token_id)]
+    total = 0.0
+    while len(seq) < max_length:
+        t = len(seq) - 1
+        tokens = torch.tensor([seq[-1]], dtype=torch.int64)
+        anc = torch.arange(t + 1, dtype=torch.int64)[None]
+        if device is not None:
+            tokens, anc = tokens.to(device), anc.to(device)
+        lp = step(tokens, anc)[0].float().cpu()
+        best = int(torch.nonzero(lp == lp.max())[0, 0])
+        total += float(lp[best])
+        seq.append(best)
+        if best == eos_token_id:
+            break
+    return BeamSearchOutput(torch.tensor([seq], dtype=torch.int64), torch.tensor([total], dtype=torch.float32))

@@ -1,0 +1,104 @@
+"""Time the teacher-forced seq2seq forward (rp_decoder_forward) at the reference's generator-validation shape.
+
+ByT5-small (synthetic weights), B pairs with sources of --src-bytes bytes and targets of each --tgt length.  Reports the
+encoder pass (rp_encode_hidden over the B sources) and the decoder side (cross K/V, layers, loss: one rp_decoder_forward)
+separately, the decoder side's GEMM FLOPs over its whole pass time (a lower bound of the GEMMs' own rate: the pass also
+holds attention, norms, the loss and the metadata copy), and the same pairs' per-token cost through the rp_decoder_step loop
+(a few pairs and positions only).  Prints one JSON object; --out also writes it.
+
+    python tools/seq2seq_bench.py [--batch 64] [--src-bytes 2300] [--tgt 64 512] [--iters 5] [--out FILE]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from reprover_amd import synth  # noqa: E402
+from reprover_amd.decoder import HipT5Generator, shift_and_segment  # noqa: E402
+
+
+def _time(fn, iters):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts))
+
+
+def _source(n, seed):
+    text = synth.synth_text(np.random.default_rng(seed), n + 8)
+    ids = np.frombuffer(text.encode("utf-8"), dtype=np.uint8).astype(np.int32)[: n - 1] + 3
+    return np.concatenate([ids, [1]]).astype(np.int32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--src-bytes", type=int, default=2300)
+    ap.add_argument("--tgt", type=int, nargs="+", default=[64, 512])
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--step-pairs", type=int, default=2)
+    ap.add_argument("--step-tokens", type=int, default=16)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    cfg = synth.seq2seq_config("byt5-small")
+    gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg, scale="sharp"), dev)
+    B, S = a.batch, a.src_bytes
+    srcs = [_source(S, 100 + b) for b in range(B)]
+    ids = np.concatenate(srcs)
+    src_cu = np.arange(B + 1, dtype=np.int32) * S
+    D, F, inner, V, L = cfg["d_model"], cfg["d_ff"], cfg["num_heads"] * cfg["d_kv"], cfg["vocab_size"], cfg["num_decoder_layers"]
+    enc_ms = _time(lambda: gen.encode_hidden_packed(ids, src_cu), a.iters)
+    enc = gen.encode_hidden_packed(ids, src_cu)
+    rng = np.random.default_rng(0)
+    result = dict(model="byt5-small (synthetic, sharp)", batch=B, source_bytes=S, encoder_ms=round(enc_ms, 3), targets={})
+    for T in a.tgt:
+        y = np.concatenate([rng.integers(3, 259, size=(B, T - 1)), np.ones((B, 1), np.int64)], 1)
+        tokens, labels, tgt_cu = shift_and_segment(y)
+        dec_ms = _time(lambda: gen.decoder.forward(enc, src_cu, tokens, labels, tgt_cu), a.iters)
+        Tt, St = B * T, B * S
+        layer_flop = 2 * Tt * D * (3 * inner + inner + inner + inner + 2 * F + F) * L + 2 * Tt * D * V
+        cross_flop = 2 * St * D * 2 * inner * L
+        attn_flop = 4 * L * cfg["num_heads"] * cfg["d_kv"] * B * (T * (T + 1) / 2 + T * S)
+        # the step loop: per-token cost of rp_decoder_step over the first tokens of a few pairs
+        n_tok = min(a.step_tokens, T)
+        t0 = time.perf_counter()
+        for b in range(a.step_pairs):
+            gen.decoder.start(enc[src_cu[b] : src_cu[b + 1]], 1, T)
+            for t in range(n_tok):
+                gen.decoder.step(torch.tensor([int(tokens[tgt_cu[b] + t])]), torch.arange(t + 1)[None])
+        torch.cuda.synchronize()
+        step_ms_per_token = (time.perf_counter() - t0) * 1e3 / (a.step_pairs * n_tok)
+        loop_ms = step_ms_per_token * Tt
+        result["targets"][str(T)] = dict(
+            decoder_ms=round(dec_ms, 3), decoder_vs_encoder=round(dec_ms / enc_ms, 4),
+            gemm_tflop=dict(layers_and_head=round(layer_flop / 1e12, 3), cross_kv=round(cross_flop / 1e12, 3)),
+            attention_tflop=round(attn_flop / 1e12, 3),
+            decoder_pass_gemm_tflops_per_s_lower_bound=round((layer_flop + cross_flop) / dec_ms / 1e9, 1),
+            step_loop_ms_per_token=round(step_ms_per_token, 4), step_loop_ms_estimated=round(loop_ms, 1),
+            speedup_vs_step_loop=round(loop_ms / dec_ms, 1))
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
