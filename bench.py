@@ -12,13 +12,19 @@ rank scans its shard for all N*256 queries, the per-shard top-k lists travel as 
 ([scores | ids | counts] per rank) and each rank merges the lists of its own queries straight from the receive buffer
 (two collectives per step in all: query embeddings, result block).  value = (N*256 queries) / max-over-ranks step time.
 
-The timed region is un-instrumented; a second pass of the same K steps with an event pair around every launch gives
-the per-kernel split the roofline objects are computed from.  Beside the headline value the line carries, at N = 1
-(SURVEY.md §8d): the same queries through the PRODUCT API from strings (`product_api_qps`: 16 eval batches of 64 states,
-RetrievalDataset-style collate -> PremiseRetriever.predict_step, which gathers host batches into 256-state GPU passes;
-`product_api` also holds the 4-batch figure and the figure with one pass per batch), premises/s at the fixed length tiers 128 / 512 /
-2048 and on the length mix, the wall time of a full 130,000-premise `reindex_corpus`, the wall latency of
-single-state `retrieve()` calls, and the CPU baseline (the oracle on the host cores, bounded sample).
+A plain run does only what the headline needs: set-up, the W warm-up steps, one untimed step that counts the collectives,
+the K timed steps (un-instrumented), `--dump-outputs`, the JSON line.  `--full` adds everything else the benchmark
+measures or checks: the device-built accessibility bits checked against the host-built ones (before the warm-up), then,
+after the timed region, a second pass of the same K steps with an event pair around every launch (the per-kernel split
+the roofline objects are computed from), `all_counts_eq_k`, the scan-only rates (bf16 and e4m3 index), the
+premise-encode throughput, the box calibration, and at N > 1 the sharded merge checked against an unsharded scan and the
+top-k stage timed with its collective (`topk_only`).  At N = 1 `--full` also carries: the per-rank scan
+call at the 1 / 2 / 4 / 8-GPU shard shapes, the same queries through the PRODUCT API from strings (`product_api_qps`: 16
+eval batches of 64 states, RetrievalDataset-style collate -> PremiseRetriever.predict_step, which gathers host batches
+into 256-state GPU passes; `product_api` also holds the 4-batch figure and the figure with one pass per batch),
+premises/s at the fixed length tiers 128 / 512 / 2048, the wall time of a full 130,000-premise `reindex_corpus`, the wall
+latency of single-state `retrieve()` calls, the training step and the CPU baseline (the oracle on the host cores,
+bounded sample).
 
 Prints ONE JSON line on rank 0.
 
@@ -675,7 +681,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run every other measurement and check of the benchmark (instrumented pass and "
+                         "roofline figures, scan-only and premise-encode rates, product API, length tiers, single-state "
+                         "latency, full re-index, training step, box calibration, CPU baseline; at N > 1 the sharded-merge "
+                         "check and topk_only).  Off by default: a plain run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the headline line.  Ignored by --config c5, which always runs all its legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--exchange", choices=("auto", "allgather", "alltoall"), default=os.environ.get("RP_BENCH_EXCHANGE", "auto"),
                     help="N > 1: how the per-shard top-k lists reach the rank that merges them: ONE packed all-gather "
                          "(north_star's form) or ONE all-to-all of per-destination slices (1 / N of the bytes: in this step a rank "
@@ -688,12 +700,14 @@ def main():
                          "N ranks, rendezvous, the one-builder-per-node barrier, shard bounds, one packed all-gather + one sliced "
                          "all-to-all of CPU blocks, the max-over-ranks clock - and print a line marked plumbing_only (no GPU, no "
                          "measurement; tests/test_dist_cpu.py drives it at N = 8 under gloo)")
-    ap.add_argument("--premise-sample", type=int, default=4096, help="premises in the encode-throughput leg")
-    ap.add_argument("--no-full-reindex", action="store_true", help="skip the 130,000-premise reindex_corpus leg (~20 s)")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the training-step leg")
+    ap.add_argument("--premise-sample", type=int, default=4096, help="with --full: premises in the encode-throughput leg")
+    ap.add_argument("--no-full-reindex", action="store_true",
+                    help="with --full: skip the 130,000-premise reindex_corpus leg (~20 s)")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: skip the training-step leg")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the premise-encode and scan-only legs (used under rocprofv3 so that every launch of "
-                         "the dominant kernel has the step's shape and the stats average is comparable)")
+                    help="with --full: skip the scan-only, premise-encode, product-API, length-tier, latency, re-index and "
+                         "training legs (used under rocprofv3 so that every launch of the dominant kernel has the step's shape "
+                         "and the stats average is comparable); a plain run runs none of them anyway")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write the last timed step's query embeddings and top-k scores / ids / counts as DIR/<name>.npy")
     args = ap.parse_args()
@@ -809,8 +823,10 @@ def main():
 
     build_masks()
     torch.cuda.synchronize()
-    assert np.array_equal(bits_d.cpu().numpy().view(np.uint32), bits_host), "device-built accessibility bits != host-built"
-    n_acc = np.array([int(corpus.accessible_mask(c.path, c.theorem_pos).sum()) for c in all_ctx[:8]])
+    n_acc = None
+    if args.full:
+        assert np.array_equal(bits_d.cpu().numpy().view(np.uint32), bits_host), "device-built accessibility bits != host-built"
+        n_acc = [int(corpus.accessible_mask(c.path, c.theorem_pos).sum()) for c in all_ctx[:8]]
 
     q_loc = torch.empty((B_STATES, D), dtype=torch.bfloat16, device=dev)
     q_all = torch.empty((BQ, D), dtype=torch.bfloat16, device=dev) if world > 1 else q_loc
@@ -916,6 +932,42 @@ def main():
     if args.dump_outputs:  # before the passes below overwrite the step's buffers; at N > 1 this rank's merged lists
         res = snapshot_outputs(q_loc, f_s, f_i, f_c) if world > 1 else snapshot_outputs(q_loc, out_s, out_i, out_c)
         dump_outputs(args.dump_outputs, res, f"_rank{rank}" if world > 1 else "")
+    ms_per_step = dt / args.steps * 1e3
+    qps = BQ * args.steps / dt
+
+    def headline_line(counts_ok=None, merged_ok=None):  # what a plain run prints; --full adds its legs to it
+        return {
+            "metric": "retrieve QPS@top-100 (state encode + masked similarity top-k), ByT5-small, 130k-premise corpus",
+            "value": qps,
+            "unit": "queries/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "bf16",
+            "data": "synthetic",
+            "full": args.full,
+            "config": {
+                "workload": "configs[1]: ByT5-small encode+retrieve, 130k premises, batch=256 states/GPU, top-100, bf16",
+                "n_premises": N, "n_files": N_FILES, "states_per_gpu": B_STATES, "k": TOP_K,
+                "state_tokens_per_gpu": T, "state_len_mix": "clip(round(LogNormal(ln 180, 0.9)), 16, 2048) bytes",
+                "index": "row-sharded %d-way, bf16 unit-norm random rows" % world,
+                "weights": "random-init ByT5-small (d_model 1472, 12 layers, 6 heads, d_ff 3584)",
+                "accessible_premises_first_queries": n_acc, "all_counts_eq_k": counts_ok, "sharded_merge_equals_single_gpu": merged_ok,
+                "collectives_per_step": collectives_per_step, "exchange": exchange_how if world > 1 else None,
+            },
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line()), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # second pass, instrumented: an event pair around every launch (rp_profile_*) for the per-kernel split
     _lib.profile_enable(True)
     for _ in range(args.steps):
@@ -1004,9 +1056,6 @@ def main():
         topk_only["path"] = ("per step: rp_sim_topk of all N*256 queries on this rank's shard -> the exchange -> "
                              "rp_topk_merge_strided of the rank's own 256 queries; qps = N*256 queries / max-over-ranks time; "
                              "exchange_us = collective + (all-to-all: three pack copies) + merge between HIP events")
-    ms_per_step = dt / args.steps * 1e3
-    qps = BQ * args.steps / dt
-
     # ---- per-kernel roofline figures from the HIP-event records of the timed region --------------
     Tp = (T + 255) // 256 * 256  # the engine pads the token dimension to the GEMM tile
     F_ = cfg["d_ff"]
@@ -1313,27 +1362,7 @@ def main():
             train["reference_conf_batch8"]["ms_per_step_without_dropout"] = train_step_leg(cfg, sd, dev, 8, dropout_rate=0.0)["ms_per_step"]
 
     result = {
-        "metric": "retrieve QPS@top-100 (state encode + masked similarity top-k), ByT5-small, 130k-premise corpus",
-        "value": qps,
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": "synthetic",
-        "config": {
-            "workload": "configs[1]: ByT5-small encode+retrieve, 130k premises, batch=256 states/GPU, top-100, bf16",
-            "n_premises": N, "n_files": N_FILES, "states_per_gpu": B_STATES, "k": TOP_K,
-            "state_tokens_per_gpu": T, "state_len_mix": "clip(round(LogNormal(ln 180, 0.9)), 16, 2048) bytes",
-            "index": "row-sharded %d-way, bf16 unit-norm random rows" % world,
-            "weights": "random-init ByT5-small (d_model 1472, 12 layers, 6 heads, d_ff 3584)",
-            "accessible_premises_first_queries": n_acc.tolist(), "all_counts_eq_k": counts_ok, "sharded_merge_equals_single_gpu": merged_ok,
-            "collectives_per_step": collectives_per_step, "exchange": exchange_how if world > 1 else None,
-        },
+        **headline_line(counts_ok, merged_ok),
         "premises_per_s": prem_per_s,
         "premises_per_s_incl_host_tokenisation": prem_per_s_host,
         "premise_tokens_per_s": prem_tok_per_s,

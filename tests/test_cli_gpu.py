@@ -249,7 +249,7 @@ def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it (the shape of the driver's scaling command when it does not
     wrap the script in torch.distributed.run) starts its two ranks itself.  Here both ranks share this box's one GPU and
     gather over gloo (a functional run of the N > 1 step, not a measurement): ONE JSON line, two collectives per step,
-    and the sharded search + merge equals the single-GPU answer."""
+    and (--full) the sharded search + merge equals the single-GPU answer."""
     import subprocess
     import sys
 
@@ -257,7 +257,7 @@ def test_bench_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(RP_BENCH_SHARE_GPU="1", RP_BENCH_BACKEND="gloo")
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--headline-only"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
+                          "--full", "--headline-only"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -278,12 +278,38 @@ def test_bench_launches_its_own_ranks():
     assert t["alltoall"]["collective_bytes_received_per_rank"] == blk // 2
     # ... and the step itself on the sliced exchange
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--headline-only", "--exchange", "alltoall"], env=env, capture_output=True, text=True, timeout=900,
+                          "--full", "--headline-only", "--exchange", "alltoall"], env=env, capture_output=True, text=True, timeout=900,
                          cwd=root)
     assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')][0])
     assert d["config"]["exchange"] == "alltoall" and d["config"]["collectives_per_step"] == 2
     assert d["config"]["sharded_merge_equals_single_gpu"] is True and d["config"]["all_counts_eq_k"] is True
+
+
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    """A plain `bench.py --gpus 1` times the steps, writes --dump-outputs and prints the headline line: none of the
+    measurements or checks that --full adds."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+    assert res.returncode == 0, (res.stdout[-1500:], res.stderr[-3000:])
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, res.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["unit"] == "queries/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 256 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    for key in ("roofline", "kernel_ms_per_step", "box_calibration", "cpu_baseline", "product_api", "train_step", "topk_only"):
+        assert key not in d, key
+    assert d["config"]["all_counts_eq_k"] is None and d["config"]["collectives_per_step"] == 0
+    counts = np.load(os.path.join(tmp_path, "topk_counts.npy"))
+    assert counts.shape == (256,) and (counts == 100).all()
+    assert np.load(os.path.join(tmp_path, "query_embeddings.npy")).shape == (256, 1472)
 
 
 def test_load_lightning_checkpoint_file(workdir, tmp_path):

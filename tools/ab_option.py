@@ -3,7 +3,7 @@ import contextlib, io, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 name, v = sys.argv[1], int(sys.argv[2])
-sys.argv = ['bench.py', '--headline-only', '--no-cpu-baseline', '--steps', '20', '--warmup', '3']
+sys.argv = ['bench.py', '--full', '--headline-only', '--no-cpu-baseline', '--steps', '20', '--warmup', '3']
 from reprover_amd import _lib
 _lib.check(_lib.load().rp_set_option(name.encode(), v), "rp_set_option")
 import bench

@@ -10,7 +10,7 @@ R=${ROUND:-r06}; OUT=gpurun_out/evidence_$R; mkdir -p $OUT
 ROUND=$R bash tools/profile_round.sh > $OUT/profile_round.log 2>&1
 cp gpurun_out/profiles_$R/* $OUT/ 2>/dev/null
 cp gpurun_out/profiles_$R/pmc_traffic.json profiles/pmc_traffic.json
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_full.log 2>&1
+timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_full.log 2>&1
 grep '^{"metric"' $OUT/bench_full.log | tail -1 > $OUT/${R}_bench_unprofiled.json
 timeout 900 python bench.py --config c5 --steps 5 > $OUT/c5.log 2>&1
 grep '^{"metric"' $OUT/c5.log | tail -1 > $OUT/${R}_c5_byt5base_1m_e4m3.json
