@@ -304,7 +304,10 @@ RpStatus rp_contrastive_mse_backward(const float* context_emb, const float* prem
  * weight decay, bias-corrected moments) of n fp32 parameters, in place:  param, exp_avg, exp_avg_sq device f32 [n],
  * 16-byte aligned;  step = 1, 2, ...;  lr = base rate x the schedule's factor for this step
  * (get_constant_schedule_with_warmup: min(1, (step - 1) / warmup_steps)).  torch defaults: betas (0.9, 0.999),
- * eps 1e-8, weight_decay 1e-2. */
+ * eps 1e-8, weight_decay 1e-2.  The update is AdamW for exactly the C floats it receives (beta2 = 0.999 arrives as
+ * 0.99900001287, and 1 - beta2, the bias corrections and 1 - lr * weight_decay are formed from that float); torch keeps
+ * the betas in double and rounds 1 - beta2 on its own, so its exp_avg_sq differs from this one by 1.3e-5 relative at the
+ * defaults - the bias correction absorbs it, the parameters agree to fp32 rounding (tests/test_step_ends_gpu.py). */
 RpStatus rp_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, int32_t step,
                        float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
 

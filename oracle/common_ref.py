@@ -222,6 +222,25 @@ def masked_topk(sims: np.ndarray, accessible: np.ndarray, k: int) -> Tuple[np.nd
     return ids, sc
 
 
+def merge_topk(scores: np.ndarray, ids: np.ndarray, counts: np.ndarray, k: int):
+    """The sharded search's merge (no reference counterpart: the reference replicates the index; this is the step that
+    makes R row shards answer as common.py:308-324 does on the whole): per query the union of the first
+    ``max(counts[r, b], 0)`` entries of every rank's list (scores / ids [R, B, k'], counts [R, B]; a negative count =
+    "this rank contributes nothing"), ordered (score descending, id ascending), cut to k.  Returns (ids int32 [B, k]
+    padded with -1, scores float32 [B, k] padded with -inf - the input bits, untouched -, count int32 [B] = min(k, total))."""
+    R, B, _ = scores.shape
+    out_i = np.full((B, k), -1, dtype=np.int32)
+    out_s = np.full((B, k), -np.inf, dtype=np.float32)
+    out_c = np.zeros(B, dtype=np.int32)
+    for b in range(B):
+        s = np.concatenate([scores[r, b, : max(int(counts[r, b]), 0)] for r in range(R)]).astype(np.float32)
+        i = np.concatenate([ids[r, b, : max(int(counts[r, b]), 0)] for r in range(R)]).astype(np.int64)
+        order = np.lexsort((i, -s.astype(np.float64)))[:k]  # last key is the primary one
+        n = order.size
+        out_i[b, :n], out_s[b, :n], out_c[b] = i[order], s[order], n
+    return out_i, out_s, out_c
+
+
 def format_augmented_state(s: str, premise_texts: Iterable[str], max_len: Optional[int], p_drop: float = 0.0) -> str:
     """common.py:357-378: prepend serialized premises (each followed by a blank line) while their
     total UTF-8 byte length fits in ``max_len - len(bytes(s))``; later premises end up *earlier* in

@@ -78,11 +78,26 @@ def warmup_factor(step_index: int, warmup_steps: int) -> float:
     return 1.0 if step_index >= warmup_steps else float(step_index) / float(max(1, warmup_steps))
 
 
+def grad_norm(grads) -> float:
+    """2-norm over every element of ``grads`` (one array or a sequence of arrays) in float64: the ``total_norm`` of
+    torch.nn.utils.clip_grad_norm_ (norm_type 2), what rp_grad_norm computes over the flat gradient buffer."""
+    arrs = [grads] if isinstance(grads, np.ndarray) else list(grads)
+    return float(np.sqrt(sum(float(np.dot(a.reshape(-1).astype(np.float64), a.reshape(-1).astype(np.float64))) for a in arrs)))
+
+
+def clip_coef(total_norm: float, max_norm: float) -> float:
+    """torch.nn.utils.clip_grad_norm_: the factor every gradient is multiplied by, min(1, max_norm / (total_norm + 1e-6))."""
+    return min(1.0, float(max_norm) / (float(total_norm) + 1e-6))
+
+
 def adamw_step(param: np.ndarray, grad: np.ndarray, m: np.ndarray, v: np.ndarray, t: int, lr: float,
-               betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
+               betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, clip=None):
     """One torch.optim.AdamW update (decoupled weight decay, bias-corrected moments), t = 1, 2, ...; returns the new
-    (param, m, v).  float64 inside so that the restatement is not the source of a mismatch."""
+    (param, m, v).  float64 inside so that the restatement is not the source of a mismatch.  ``clip`` = (total_norm,
+    max_norm): the gradient is first scaled as torch.nn.utils.clip_grad_norm_ does (clip_coef), in float64 too."""
     p, g = param.astype(np.float64), grad.astype(np.float64)
+    if clip is not None:
+        g = g * clip_coef(clip[0], clip[1])
     p = p * (1.0 - lr * weight_decay)
     m = betas[0] * m.astype(np.float64) + (1.0 - betas[0]) * g
     v = betas[1] * v.astype(np.float64) + (1.0 - betas[1]) * g * g
@@ -90,3 +105,29 @@ def adamw_step(param: np.ndarray, grad: np.ndarray, m: np.ndarray, v: np.ndarray
     denom = np.sqrt(v) / np.sqrt(1.0 - betas[1] ** t) + eps
     p = p - lr * m_hat / denom
     return p.astype(np.float32), m, v
+
+
+def adamw_step64(p: np.ndarray, grad: np.ndarray, m: np.ndarray, v: np.ndarray, t: int, lr: float,
+                 betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, clip=None):
+    """``adamw_step`` with the parameters carried in float64 from step to step as well (adamw_step rounds them to fp32
+    after every update, as the fixtures store them): the yardstick against which fp32 implementations are measured."""
+    g = grad.astype(np.float64)
+    if clip is not None:
+        g = g * clip_coef(clip[0], clip[1])
+    p = p.astype(np.float64) * (1.0 - lr * weight_decay)
+    m = betas[0] * m.astype(np.float64) + (1.0 - betas[0]) * g
+    v = betas[1] * v.astype(np.float64) + (1.0 - betas[1]) * g * g
+    denom = np.sqrt(v) / np.sqrt(1.0 - betas[1] ** t) + eps
+    return p - lr * (m / (1.0 - betas[0] ** t)) / denom, m, v
+
+
+def contrastive_mse(C: np.ndarray, P: np.ndarray, label: np.ndarray, similarity: np.ndarray = None):
+    """retrieval/model.py:133-139 and its autograd in float64: S = C P^T, loss = mean((S - label)^2),
+    dS = 2 (S - label) / (B P), dC = dS P, dP = dS^T C.  Returns (loss, S, dC, dP).  With ``similarity`` given, loss and
+    gradients are taken at THAT matrix (rp_contrastive_mse_backward is handed the forward's stored fp32 similarity)."""
+    C, P, label = (np.asarray(a, dtype=np.float64) for a in (C, P, label))
+    S = C @ P.T if similarity is None else np.asarray(similarity, dtype=np.float64)
+    diff = S - label
+    loss = float(np.mean(diff * diff))
+    dS = 2.0 * diff / diff.size
+    return loss, S, dS @ P, dS.T @ C

@@ -164,6 +164,100 @@ def topk_merge(scores, ids, counts):
     return out_i, out_s, out_c
 
 
+def topk_merge_strided(packed, R, Bt, k, q0, B, rank_stride=None):
+    """rp_topk_merge_strided over queries [q0, q0 + B) of ``packed``: a flat 4-byte-unit device buffer (int32) holding R
+    blocks [scores f32 [Bt, k] | ids i32 [Bt, k] | counts i32 [Bt]], block r at r * rank_stride (default Bt * (2 k + 1))."""
+    lib = _lib.load()
+    rank_stride = Bt * (2 * k + 1) if rank_stride is None else rank_stride
+    assert packed.dtype == torch.int32 and packed.numel() >= (R - 1) * rank_stride + Bt * (2 * k + 1)
+    assert 0 <= q0 and q0 + B <= Bt
+    out_s = torch.empty((B, k), dtype=torch.float32, device=packed.device)
+    out_i = torch.empty((B, k), dtype=torch.int32, device=packed.device)
+    out_c = torch.empty((B,), dtype=torch.int32, device=packed.device)
+    nbytes = lib.rp_topk_merge_workspace_bytes(R, B, k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
+    base = _lib.ptr(packed)
+    _lib.check(lib.rp_topk_merge_strided(base + 4 * q0 * k, base + 4 * (Bt * k + q0 * k), base + 4 * (2 * Bt * k + q0),
+                                         rank_stride, R, B, k, _lib.ptr(out_s), _lib.ptr(out_i), _lib.ptr(out_c),
+                                         _lib.ptr(ws), nbytes, _lib.current_stream()), "rp_topk_merge_strided")
+    torch.cuda.synchronize()
+    return out_i, out_s, out_c
+
+
+GUARD = 64  # floats behind every array handed to the optimizer-end kernels
+
+
+def guarded(n, fill, guard_value, device="cuda", dtype=torch.float32):
+    """(whole buffer [n + GUARD], view of its first n elements): the view is what a kernel is handed, the GUARD elements
+    behind it hold ``guard_value`` and must come back untouched (guard_intact) / unread."""
+    buf = torch.full((n + GUARD,), guard_value, dtype=dtype, device=device)
+    buf[:n] = fill
+    return buf, buf[:n]
+
+
+def guard_intact(buf, n, guard_value):
+    g = buf[n:]
+    want = torch.full_like(g, guard_value)
+    return bool(torch.equal(g.view(torch.int32), want.view(torch.int32)))  # bits: NaN guards compare too
+
+
+def grad_norm(g, n=None, scratch=None, sync=True):
+    """rp_grad_norm over the first n floats of g -> device f32 [1]."""
+    lib = _lib.load()
+    n = g.numel() if n is None else n
+    out = torch.full((1,), float("nan"), dtype=torch.float32, device=g.device)
+    scratch = torch.empty(1024, dtype=torch.float32, device=g.device) if scratch is None else scratch
+    _lib.check(lib.rp_grad_norm(_lib.ptr(g), n, _lib.ptr(out), _lib.ptr(scratch), _lib.current_stream()), "rp_grad_norm")
+    if sync:
+        torch.cuda.synchronize()
+    return out
+
+
+def adamw_step(p, g, m, v, step, lr, betas, eps, wd, total_norm=None, max_norm=0.0, clipped=True, n=None):
+    """rp_adamw_step_clipped (clipped=False: rp_adamw_step) in place; returns the status (no exception: the error tests
+    read it).  Launch only, no synchronisation."""
+    lib = _lib.load()
+    n = p.numel() if n is None else n
+    if clipped:
+        return lib.rp_adamw_step_clipped(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, step, lr, betas[0],
+                                         betas[1], eps, wd, _lib.ptr(total_norm), max_norm, _lib.current_stream())
+    return lib.rp_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, step, lr, betas[0], betas[1], eps,
+                             wd, _lib.current_stream())
+
+
+def contrastive_mse_raw(C, P, label, want_sim=True, ws_bytes=None, D=None):
+    """rp_contrastive_mse through the ABI -> (status, loss buffer, similarity buffer or None); both outputs are `guarded`
+    with NaN (loss: [1 + GUARD], similarity: [B * Pn + GUARD])."""
+    lib = _lib.load()
+    B, Pn = C.shape[0], P.shape[0]
+    D = C.shape[1] if D is None else D
+    need = lib.rp_contrastive_mse_workspace_bytes(B, Pn)
+    ws_bytes = need if ws_bytes is None else ws_bytes
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=C.device)
+    loss, _ = guarded(1, float("nan"), float("nan"))
+    sim = guarded(B * Pn, float("nan"), float("nan"))[0] if want_sim else None
+    st = lib.rp_contrastive_mse(_lib.ptr(C), _lib.ptr(P), _lib.ptr(label), B, Pn, D, _lib.ptr(loss), _lib.ptr(sim),
+                                _lib.ptr(ws), ws_bytes, _lib.current_stream())
+    torch.cuda.synchronize()
+    return st, loss, sim
+
+
+def contrastive_mse_backward_raw(C, P, S, label):
+    """rp_contrastive_mse_backward -> (status, d_ctx buffer [B * D + GUARD], d_prem buffer [Pn * D + GUARD]), NaN-guarded."""
+    lib = _lib.load()
+    (B, D), Pn = C.shape, P.shape[0]
+    dC = guarded(B * D, float("nan"), float("nan"))[0]
+    dP = guarded(Pn * D, float("nan"), float("nan"))[0]
+    st = lib.rp_contrastive_mse_backward(_lib.ptr(C), _lib.ptr(P), _lib.ptr(S), _lib.ptr(label), B, Pn, D, _lib.ptr(dC),
+                                         _lib.ptr(dP), _lib.current_stream())
+    torch.cuda.synchronize()
+    return st, dC, dP
+
+
+def last_error():
+    return _lib.load().rp_last_error().decode(errors="replace")
+
+
 from reprover_amd.synth import synth_masks  # noqa: E402,F401  (moved: bench.py --config c5 draws the same operands)
 
 
