@@ -518,6 +518,50 @@ RpStatus rp_beam_select(const float* logprobs, const float* running, int32_t nb,
                         float* scores, int32_t* tokens, int32_t* parents, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* Batched generation: one decode loop for the beams of n proof states ("Batched
+ * generation").  All states start together and sit at the same position t; a state that has finished
+ * is left out of the step's active list and costs nothing.  For every state the outputs are the bits
+ * that rp_decoder_cross_kv / rp_decoder_step / rp_beam_select give that state alone, whichever other
+ * states share the call and in whatever order.
+ * Caps: 1 <= n <= 32 states, n * num_beams <= 1024 rows (16 states of 64 beams), num_beams <= 64, max_len <= 8192, every source
+ * 1..8192 tokens, vocab <= 512.
+ *   src_cu  HOST int32 [n + 1] prefix sums (start at 0): source b is rows src_cu[b] .. src_cu[b+1] of
+ *           enc_bf16 [src_cu[n], d_model] (rp_encode_hidden over the packed sources)
+ * Workspace (each part rounded up to 256 bytes; L = decoder layers, inner = H * d_kv):
+ *   cross K/V   src_cu[n] * L * 2 * inner * 2 bytes
+ *   cache       n * L * max_len * num_beams * 2 * inner * 2 bytes: per state and layer
+ *               [max_len * num_beams, 2 * inner], row t * num_beams + b, as rp_decoder_step lays it out
+ *               (ByT5-small, 64 beams x 512 positions: ~200 MB per state)
+ *   activations n * num_beams * (4 d_model + 2 (d_model + d_ff) + 6 inner + 2 inner) bytes
+ * rp_decoder_batch_workspace_bytes returns 0 on bad arguments (rp_last_error says why). */
+size_t   rp_decoder_batch_workspace_bytes(const RpDecoder* dec, const int32_t* src_cu, int32_t n,
+                                          int32_t num_beams, int32_t max_len);
+/* Cross-attention K/V of every layer for all n sources in one GEMM over the src_cu[n] packed rows. */
+RpStatus rp_decoder_batch_cross_kv(RpDecoder* dec, const void* enc_bf16, const int32_t* src_cu, int32_t n,
+                                   int32_t num_beams, int32_t max_len, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+/* One decode step at position t for the n_active states still searching; row a * nb + b is beam b of the
+ * state in slot a:
+ *   active    HOST int32 [n_active]: distinct state indices in [0, n), the state each slot carries (host
+ *             memory, so that it is checked here: two slots naming one state would share cache rows)
+ *   tokens    device int32 [n_active * nb]
+ *   ancestry  device int32 [n_active * nb, anc_stride]: as rp_decoder_step, entries local to the state's
+ *             own cache (row t * nb + b is the one written for beam b; entries are clamped to that cache)
+ *   logprobs  device fp32 [n_active * nb, vocab]
+ * One launch per kernel of rp_decoder_step, over all rows; the attentions size their LDS for the longest
+ * key list of the call. */
+RpStatus rp_decoder_batch_step(RpDecoder* dec, const int32_t* src_cu, int32_t n, const int32_t* active,
+                               int32_t n_active, const int32_t* tokens, const int32_t* ancestry,
+                               int32_t anc_stride, int32_t nb, int32_t t, int32_t max_len, float* logprobs,
+                               void* workspace, size_t workspace_bytes, void* stream);
+/* rp_beam_select for n_active (<= 32) states in one launch pair: per state a, the top k of
+ * logprobs[a * nb + b, v] + running[a * nb + b] over its own [nb * vocab] block, in rp_beam_select's
+ * order; scores / tokens / parents are [n_active, k], parents local to the state.
+ * workspace: n_active * nb * min(k, vocab) * 8 bytes of device memory. */
+RpStatus rp_beam_select_batch(const float* logprobs, const float* running, int32_t n_active, int32_t nb,
+                              int32_t vocab, int32_t k, float* scores, int32_t* tokens, int32_t* parents,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Teacher-forced seq2seq forward (T5ForConditionalGeneration(input_ids, attention_mask, labels)) over
  * `batch` (source, target) pairs packed varlen; DESIGN.md section 10.  src_cu / tgt_cu are HOST int32
  * [batch + 1] prefix sums (start at 0): source b is rows src_cu[b] .. src_cu[b+1] of enc_bf16, target b

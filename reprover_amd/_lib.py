@@ -240,6 +240,19 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
          C.c_size_t, C.c_void_p],
     ),
+    "rp_decoder_batch_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "rp_decoder_batch_cross_kv": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rp_decoder_batch_step": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "rp_beam_select_batch": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
     "rp_set_option": (C.c_int32, [C.c_char_p, C.c_int32]),
     "rp_profile_enable": (C.c_int32, [C.c_int32]),
     "rp_profile_read": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

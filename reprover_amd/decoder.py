@@ -3,7 +3,9 @@
 The encoder is ``HipT5Encoder`` (``rp_encode_hidden``: last_hidden_state instead of the pool); the decoder is
 ``rp_decoder_*`` (one launch sequence per beam-search step); the beam bookkeeping is
 ``reprover_amd.generation.beam_search`` with the device top-2nb selection ``rp_beam_select``.  The teacher-forced loss
-(``forward`` / ``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.
+(``forward`` / ``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.  ``generate_many`` / ``greedy_many`` run
+the beams of several sources through one decode loop (``rp_decoder_batch_*``, ``rp_beam_select_batch``) and return, per
+source, the bits of ``generate`` / ``greedy``.
 PyTorch tensors are containers only.
 """
 from __future__ import annotations
@@ -18,7 +20,7 @@ import torch
 
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
-from .generation import BeamSearchOutput, beam_search, greedy_search
+from .generation import BeamSearchOutput, beam_search, beam_search_batch, greedy_search, greedy_search_batch
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
 
@@ -271,6 +273,79 @@ class HipT5Decoder:
         return scores, toks, par
 
 
+    @staticmethod
+    def max_states(nb: int) -> int:
+        """States one batched call takes at ``nb`` beams (include/reprover_hip.h: 32 states, 1024 rows)."""
+        return max(1, min(32, 1024 // max(1, int(nb))))
+
+    # -- batched generation (rp_decoder_batch_*): every state's rows are the bits of start / step / select alone --------
+    def start_many(self, enc_bf16: torch.Tensor, src_cu: np.ndarray, nb: int, max_len: int) -> None:
+        """Cross K/V of ``n`` sources packed varlen (enc_bf16 [sum S_b, d_model] bf16, host ``src_cu [n + 1]``) for a
+        search of ``nb`` beams and ``max_len`` positions per state, in one GEMM."""
+        assert enc_bf16.dtype == torch.bfloat16 and enc_bf16.is_contiguous()
+        cu = np.ascontiguousarray(src_cu, dtype=np.int32)
+        n = len(cu) - 1
+        if n < 1 or enc_bf16.shape[0] != int(cu[-1]):
+            raise _lib.HipLibraryError(f"start_many: {n} states, src_cu[-1]={int(cu[-1]) if len(cu) else None} for "
+                                       f"{enc_bf16.shape[0]} encoder rows")
+        need = int(self._lib.rp_decoder_batch_workspace_bytes(self._handle, cu.ctypes.data_as(C.c_void_p), n, nb, max_len))
+        if need == 0:
+            raise _lib.HipLibraryError("unsupported batched generate shape: "
+                                       + self._lib.rp_last_error().decode(errors="replace"))
+        if getattr(self, "_many_ws", None) is None or self._many_ws.numel() < need:
+            self._many_ws = None
+            self._many_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._many = (cu, n, nb, max_len)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_batch_cross_kv(self._handle, enc_bf16.data_ptr(), cu.ctypes.data_as(C.c_void_p),
+                                                           n, nb, max_len, self._many_ws.data_ptr(),
+                                                           self._many_ws.numel(), _lib.current_stream()),
+                       "rp_decoder_batch_cross_kv")
+
+    def step_many(self, active, tokens: torch.Tensor, ancestry: torch.Tensor,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """log-probs [n_active * nb, V] of one step for the states ``active`` (distinct indices into ``start_many``'s
+        sources): row ``a * nb + b`` is beam ``b`` of state ``active[a]`` (``beam_search_batch``'s ``step_many``)."""
+        cu, n, nb, max_len = self._many
+        act = np.ascontiguousarray(active, dtype=np.int32)
+        rows, T = ancestry.shape
+        if rows != len(act) * nb or tokens.numel() != rows:
+            raise _lib.HipLibraryError(f"step_many: {rows} ancestry rows, {tokens.numel()} tokens for {len(act)} states "
+                                       f"of {nb} beams")
+        tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
+        anc = ancestry.to(device=self.device, dtype=torch.int32).contiguous()
+        if out is None:
+            out = torch.empty((rows, self.V), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_batch_step(self._handle, cu.ctypes.data_as(C.c_void_p), n,
+                                                       act.ctypes.data_as(C.c_void_p), len(act), tok.data_ptr(),
+                                                       anc.data_ptr(), T, nb, T - 1, max_len, out.data_ptr(),
+                                                       self._many_ws.data_ptr(), self._many_ws.numel(),
+                                                       _lib.current_stream()),
+                       "rp_decoder_batch_step")
+        return out
+
+    def select_many(self, log_probs: torch.Tensor, running: torch.Tensor, nb: int, k: int):
+        """Per state the device top-k of its own ``[nb * V]`` block (``rp_beam_select_batch``): scores, tokens, parents,
+        each ``[n_active, k]``, parents local to the state."""
+        rows, V = log_probs.shape
+        na = rows // nb
+        need = rows * min(k, V) * 8
+        if getattr(self, "_sel_many_ws", None) is None or self._sel_many_ws.numel() < need:
+            self._sel_many_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        run = running.to(device=self.device, dtype=torch.float32).contiguous()
+        lp = log_probs.contiguous()
+        scores = torch.empty((na, k), dtype=torch.float32, device=self.device)
+        toks = torch.empty((na, k), dtype=torch.int32, device=self.device)
+        par = torch.empty((na, k), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_beam_select_batch(lp.data_ptr(), run.data_ptr(), na, nb, V, k, scores.data_ptr(),
+                                                      toks.data_ptr(), par.data_ptr(), self._sel_many_ws.data_ptr(),
+                                                      self._sel_many_ws.numel(), _lib.current_stream()),
+                       "rp_beam_select_batch")
+        return scores, toks, par
+
+
 class HipT5Generator:
     """Encoder + decoder of one T5ForConditionalGeneration checkpoint on one GPU."""
 
@@ -373,3 +448,31 @@ class HipT5Generator:
                            eos_token_id=self.cfg.get("eos_token_id", 1),
                            decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),
                            select=self.decoder.select, device=self.device, trace=trace)
+
+    def _start_many(self, sources, num_beams: int, max_length: int) -> int:
+        srcs = [np.asarray(x, dtype=np.int32).reshape(-1) for x in sources]
+        if not srcs:
+            raise ValueError("generate_many needs at least one source")
+        cu = np.concatenate([[0], np.cumsum([len(x) for x in srcs])]).astype(np.int32)
+        enc = self.encode_hidden_packed(np.concatenate(srcs), cu)
+        self.decoder.start_many(enc, cu, num_beams, max_length)
+        return len(srcs)
+
+    def greedy_many(self, sources, max_length: int) -> List[BeamSearchOutput]:
+        """``greedy`` for several sources through one decode loop: entry ``i`` is ``greedy(sources[i], max_length)`` bit
+        for bit, whichever other sources share the call."""
+        n = self._start_many(sources, 1, max_length)
+        return greedy_search_batch(self.decoder.step_many, n, max_length, eos_token_id=self.cfg.get("eos_token_id", 1),
+                                   decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device)
+
+    def generate_many(self, sources, num_beams: int, max_length: int, length_penalty: float = 1.0,
+                      traces: Optional[list] = None) -> List[BeamSearchOutput]:
+        """``generate`` for several sources at once: one packed encoder pass, one cross-K/V GEMM and one decode loop that
+        runs until the last state stops, with one readback per step.  Entry ``i`` equals ``generate(sources[i], ...)``
+        bit for bit (sequences, scores and, in ``traces[i]``, every step's selected triples), whichever other sources
+        share the call, in whatever order, and whenever they finish."""
+        n = self._start_many(sources, num_beams, max_length)
+        return beam_search_batch(self.decoder.step_many, n, num_beams, max_length, length_penalty,
+                                 eos_token_id=self.cfg.get("eos_token_id", 1),
+                                 decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),
+                                 select_many=self.decoder.select_many, device=self.device, traces=traces)

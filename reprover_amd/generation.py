@@ -23,7 +23,7 @@ bookkeeping below runs on the host.  At 64 beams that is one ~1.5 KB copy and on
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, Optional, Tuple
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
@@ -44,55 +44,54 @@ def topk_select(log_probs: torch.Tensor, running_scores: torch.Tensor, k: int):
     return vals, idx % V, torch.div(idx, V, rounding_mode="floor")
 
 
-def beam_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], num_beams: int, max_length: int,
-                length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
-                num_return_sequences: Optional[int] = None, select: Callable = topk_select,
-                device=None, trace: Optional[list] = None) -> BeamSearchOutput:
-    """Beam search over ``step`` (module docstring).  ``trace``, when a list, receives the per-step top-``2 nb``
-    candidates ``(scores, tokens, parents)`` as host tensors."""
-    nb = int(num_beams)
-    nret = nb if num_return_sequences is None else int(num_return_sequences)
-    assert 1 <= nret <= nb
-    prompt_len = 1  # the decoder prompt is the start token alone (utils.py:3266 decoder_prompt_len = cur_len)
-    cur_len = prompt_len
-    keep = 2 * nb  # beams_to_keep = max(2, 1 + n_eos_tokens) * num_beams with one EOS id (:3271)
-    fill = eos_token_id  # output_fill_value = pad_token_id (0, falsy) or eos_token_id[0] (:3294)
-    if max_length <= cur_len:
-        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+class _BeamState:
+    """The host bookkeeping of one source's beam search: ``inputs`` gives the step's tokens and ancestry table,
+    ``advance`` takes the step's top-``2 nb`` candidates (host tensors) and says whether the search is over.
+    ``beam_search`` drives one of these, ``beam_search_batch`` several in lockstep."""
 
-    running_seq = torch.full((nb, max_length), fill, dtype=torch.int64)
-    running_seq[:, 0] = decoder_start_token_id
-    sequences = running_seq.clone()
-    running_scores = torch.zeros(nb, dtype=torch.float32)
-    running_scores[1:] = NEG  # :3301 - only beam 0 is live at the first step
-    beam_scores = torch.full((nb,), NEG, dtype=torch.float32)
-    is_sent_finished = torch.zeros(nb, dtype=torch.bool)
-    heuristic_unsatisfied = True
-    running_bi = torch.full((nb, max_length - cur_len), -1, dtype=torch.int32)
-    beam_indices = running_bi.clone()
-    top_num_beam_mask = torch.cat([torch.ones(nb, dtype=torch.bool), torch.zeros(keep - nb, dtype=torch.bool)])
-    ancestry = torch.zeros((nb, 0), dtype=torch.int64)
-    running_scores_dev = running_scores.to(device) if device is not None else running_scores
+    def __init__(self, num_beams: int, max_length: int, length_penalty: float, eos_token_id: int,
+                 decoder_start_token_id: int, num_return_sequences: Optional[int]):
+        nb = self.nb = int(num_beams)
+        self.nret = nb if num_return_sequences is None else int(num_return_sequences)
+        assert 1 <= self.nret <= nb
+        self.prompt_len = 1  # the decoder prompt is the start token alone (utils.py:3266 decoder_prompt_len = cur_len)
+        self.cur_len = self.prompt_len
+        self.keep = 2 * nb  # beams_to_keep = max(2, 1 + n_eos_tokens) * num_beams with one EOS id (:3271)
+        fill = eos_token_id  # output_fill_value = pad_token_id (0, falsy) or eos_token_id[0] (:3294)
+        if max_length <= self.cur_len:
+            raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+        self.max_length, self.length_penalty, self.eos_token_id = max_length, length_penalty, eos_token_id
 
-    while True:
-        t = cur_len - 1  # position of the token fed this step
-        tokens = running_seq[:, t]
-        ancestry = torch.cat([ancestry, (t * nb + torch.arange(nb, dtype=torch.int64))[:, None]], dim=1)
-        if device is not None:
-            log_probs = step(tokens.to(device), ancestry.to(device))
-        else:
-            log_probs = step(tokens, ancestry)
-        # _get_top_k_continuations (:3077-3129)
-        vals, toks, parents = select(log_probs, running_scores_dev, keep)
-        vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
-        if trace is not None:
-            trace.append((vals.clone(), toks.clone(), parents.clone()))
+        self.running_seq = torch.full((nb, max_length), fill, dtype=torch.int64)
+        self.running_seq[:, 0] = decoder_start_token_id
+        self.sequences = self.running_seq.clone()
+        self.running_scores = torch.zeros(nb, dtype=torch.float32)
+        self.running_scores[1:] = NEG  # :3301 - only beam 0 is live at the first step
+        self.beam_scores = torch.full((nb,), NEG, dtype=torch.float32)
+        self.is_sent_finished = torch.zeros(nb, dtype=torch.bool)
+        self.heuristic_unsatisfied = True
+        self.running_bi = torch.full((nb, max_length - self.cur_len), -1, dtype=torch.int32)
+        self.beam_indices = self.running_bi.clone()
+        self.top_num_beam_mask = torch.cat([torch.ones(nb, dtype=torch.bool),
+                                            torch.zeros(self.keep - nb, dtype=torch.bool)])
+        self.ancestry = torch.zeros((nb, 0), dtype=torch.int64)
+
+    def inputs(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(tokens [nb], ancestry [nb, t + 1]) of the step at position ``t = cur_len - 1``."""
+        nb, t = self.nb, self.cur_len - 1
+        self.ancestry = torch.cat([self.ancestry, (t * nb + torch.arange(nb, dtype=torch.int64))[:, None]], dim=1)
+        return self.running_seq[:, t], self.ancestry
+
+    def advance(self, vals: torch.Tensor, toks: torch.Tensor, parents: torch.Tensor) -> bool:
+        """Take the selected candidates of this step; True when the search has stopped."""
+        nb, cur_len, prompt_len, length_penalty = self.nb, self.cur_len, self.prompt_len, self.length_penalty
+        running_seq, running_bi = self.running_seq, self.running_bi
         topk_seq = running_seq[parents].clone()
         topk_seq[:, cur_len] = toks
         topk_bi = running_bi[parents].clone()
         topk_bi[:, cur_len - prompt_len] = parents.to(torch.int32)
         # stopping criteria on topk_running_sequences[:, :cur_len + 1] (:3321-3327): MaxLength, then EOS
-        hits = (toks == eos_token_id) | torch.tensor(cur_len + 1 >= max_length)
+        hits = (toks == self.eos_token_id) | torch.tensor(cur_len + 1 >= self.max_length)
         # _get_running_beams_for_next_iteration (:3131-3151)
         run_lp = vals + hits.to(torch.float32) * NEG
         nxt = torch.topk(run_lp, k=nb)[1]
@@ -100,35 +99,106 @@ def beam_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], num_
         running_scores = run_lp[nxt]
         new_running_bi = topk_bi[nxt]
         # _update_finished_beams (:3153-3206)
-        just_finished = hits & top_num_beam_mask
+        just_finished = hits & self.top_num_beam_mask
         fin_lp = vals / ((cur_len + 1 - prompt_len) ** length_penalty)
-        fin_lp = fin_lp + (0.0 if heuristic_unsatisfied else NEG)
+        fin_lp = fin_lp + (0.0 if self.heuristic_unsatisfied else NEG)
         fin_lp = fin_lp + (~just_finished).to(torch.float32) * NEG
-        m_seq = torch.cat([sequences, topk_seq], 0)
-        m_scores = torch.cat([beam_scores, fin_lp], 0)
-        m_bi = torch.cat([beam_indices, topk_bi], 0)
-        m_fin = torch.cat([is_sent_finished, just_finished], 0)
+        m_seq = torch.cat([self.sequences, topk_seq], 0)
+        m_scores = torch.cat([self.beam_scores, fin_lp], 0)
+        m_bi = torch.cat([self.beam_indices, topk_bi], 0)
+        m_fin = torch.cat([self.is_sent_finished, just_finished], 0)
         sel = torch.topk(m_scores, k=nb)[1]
-        sequences, beam_scores, beam_indices, is_sent_finished = m_seq[sel], m_scores[sel], m_bi[sel], m_fin[sel]
+        self.sequences, self.beam_scores, self.beam_indices, self.is_sent_finished = (
+            m_seq[sel], m_scores[sel], m_bi[sel], m_fin[sel])
         # the cache reorder (:3478-3489) is a reorder of the ancestry table here
         src = parents[nxt]
-        ancestry = ancestry[src]
-        running_seq, running_bi = new_running_seq, new_running_bi
-        running_scores_dev = running_scores.to(device) if device is not None else running_scores
-        cur_len += 1
+        self.ancestry = self.ancestry[src]
+        self.running_seq, self.running_bi, self.running_scores = new_running_seq, new_running_bi, running_scores
+        self.cur_len = cur_len = cur_len + 1
         # _check_early_stop_heuristic (:3008-3053), early_stopping=False: best length = cur_len - prompt_len
         best_running = running_scores[0] / ((cur_len - prompt_len) ** length_penalty)
-        worst_finished = torch.where(is_sent_finished, beam_scores.min(), torch.tensor(NEG))
-        heuristic_unsatisfied = heuristic_unsatisfied and bool((best_running > worst_finished).any())
+        worst_finished = torch.where(self.is_sent_finished, self.beam_scores.min(), torch.tensor(NEG))
+        self.heuristic_unsatisfied = self.heuristic_unsatisfied and bool((best_running > worst_finished).any())
         # _beam_search_has_unfinished_sequences (:3055-3075), early_stopping=False
-        if not heuristic_unsatisfied or bool(hits.all()):
-            break
+        return not self.heuristic_unsatisfied or bool(hits.all())
 
-    sequences = sequences[:nret]
-    beam_scores = beam_scores[:nret]
-    beam_indices = beam_indices[:nret]
-    max_generated = int(((beam_indices + 1).bool()).sum(dim=1).max())  # :3514-3517
-    return BeamSearchOutput(sequences[:, : prompt_len + max_generated], beam_scores)
+    def result(self) -> BeamSearchOutput:
+        sequences = self.sequences[: self.nret]
+        beam_scores = self.beam_scores[: self.nret]
+        beam_indices = self.beam_indices[: self.nret]
+        max_generated = int(((beam_indices + 1).bool()).sum(dim=1).max())  # :3514-3517
+        return BeamSearchOutput(sequences[:, : self.prompt_len + max_generated], beam_scores)
+
+
+def beam_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], num_beams: int, max_length: int,
+                length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
+                num_return_sequences: Optional[int] = None, select: Callable = topk_select,
+                device=None, trace: Optional[list] = None) -> BeamSearchOutput:
+    """Beam search over ``step`` (module docstring).  ``trace``, when a list, receives the per-step top-``2 nb``
+    candidates ``(scores, tokens, parents)`` as host tensors."""
+    st = _BeamState(num_beams, max_length, length_penalty, eos_token_id, decoder_start_token_id, num_return_sequences)
+    while True:
+        tokens, ancestry = st.inputs()
+        running = st.running_scores
+        if device is not None:
+            tokens, ancestry, running = tokens.to(device), ancestry.to(device), running.to(device)
+        log_probs = step(tokens, ancestry)
+        # _get_top_k_continuations (:3077-3129)
+        vals, toks, parents = select(log_probs, running, st.keep)
+        vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
+        if trace is not None:
+            trace.append((vals.clone(), toks.clone(), parents.clone()))
+        if st.advance(vals, toks, parents):
+            break
+    return st.result()
+
+
+def topk_select_many(log_probs: torch.Tensor, running_scores: torch.Tensor, nb: int, k: int):
+    """``topk_select`` per state over ``[n_active * nb, vocab]`` rows: each output ``[n_active, k]``."""
+    outs = [topk_select(log_probs[a * nb : (a + 1) * nb], running_scores[a * nb : (a + 1) * nb], k)
+            for a in range(log_probs.shape[0] // nb)]
+    return tuple(torch.stack(x) for x in zip(*outs))
+
+
+def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_length: int, length_penalty: float = 1.0,
+                      eos_token_id: int = 1, decoder_start_token_id: int = 0,
+                      num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
+                      traces: Optional[list] = None) -> List[BeamSearchOutput]:
+    """``beam_search`` for ``num_states`` sources in lockstep: one ``step_many`` and one ``select_many`` per position,
+    one readback of the ``n_active x 2 nb`` triples.  Every state runs ``beam_search``'s bookkeeping unchanged and leaves
+    the active list at the step where the single-state loop would stop; the loop runs until the last one has.
+
+    - ``step_many(active, tokens, ancestry) -> log_probs``: ``active`` is the list of state indices still searching
+      (ascending); row ``a * nb + b`` of ``tokens [n_active * nb]`` / ``ancestry [n_active * nb, t + 1]`` is beam ``b``
+      of state ``active[a]``, ancestry entries local to that state's own cache.  Returns ``[n_active * nb, vocab]``.
+    - ``select_many(log_probs, running_scores, nb, k)``: per state the top ``k`` of its own ``[nb * vocab]`` block,
+      each output ``[n_active, k]``, parents local to the state.
+
+    ``traces``, when a list, receives one per-state list of ``(scores, tokens, parents)`` per step."""
+    states = [_BeamState(num_beams, max_length, length_penalty, eos_token_id, decoder_start_token_id,
+                         num_return_sequences) for _ in range(num_states)]
+    per_state = [[] for _ in states]
+    active = list(range(num_states))
+    nb = int(num_beams)
+    while active:
+        ins = [states[i].inputs() for i in active]
+        tokens = torch.cat([x[0] for x in ins])
+        ancestry = torch.cat([x[1] for x in ins])
+        running = torch.cat([states[i].running_scores for i in active])
+        if device is not None:
+            tokens, ancestry, running = tokens.to(device), ancestry.to(device), running.to(device)
+        log_probs = step_many(list(active), tokens, ancestry)
+        vals, toks, parents = select_many(log_probs, running, nb, 2 * nb)
+        vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
+        still = []
+        for a, i in enumerate(active):
+            per_state[i].append((vals[a].clone(), toks[a].clone(), parents[a].clone()))
+            if not states[i].advance(vals[a], toks[a], parents[a]):
+                still.append(i)
+        active = still
+    if traces is not None:
+        traces.extend(per_state)
+    return [st.result() for st in states]
 
 
 def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], max_length: int, eos_token_id: int = 1,
@@ -154,3 +224,34 @@ def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], ma
         if best == eos_token_id:
             break
     return BeamSearchOutput(torch.tensor([seq], dtype=torch.int64), torch.tensor([total], dtype=torch.float32))
+
+
+def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, eos_token_id: int = 1,
+                        decoder_start_token_id: int = 0, device=None) -> List[BeamSearchOutput]:
+    """``greedy_search`` for ``num_states`` sources in lockstep (one beam each): one ``step_many`` (as in
+    ``beam_search_batch``) and one readback of the active states' log-prob rows per position.  A state leaves the
+    active list at its EOS; the loop ends with the last one or at ``max_length``."""
+    if max_length <= 1:
+        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+    seqs = [[int(decoder_start_token_id)] for _ in range(num_states)]
+    totals = [0.0] * num_states
+    active = list(range(num_states))
+    t = 0
+    while active and t + 1 < max_length:
+        tokens = torch.tensor([seqs[i][-1] for i in active], dtype=torch.int64)
+        anc = torch.arange(t + 1, dtype=torch.int64)[None].repeat(len(active), 1)
+        if device is not None:
+            tokens, anc = tokens.to(device), anc.to(device)
+        lps = step_many(list(active), tokens, anc).float().cpu()
+        still = []
+        for a, i in enumerate(active):
+            lp = lps[a]
+            best = int(torch.nonzero(lp == lp.max())[0, 0])
+            totals[i] += float(lp[best])
+            seqs[i].append(best)
+            if best != eos_token_id:
+                still.append(i)
+        active = still
+        t += 1
+    return [BeamSearchOutput(torch.tensor([s], dtype=torch.int64), torch.tensor([tot], dtype=torch.float32))
+            for s, tot in zip(seqs, totals)]

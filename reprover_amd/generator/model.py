@@ -5,7 +5,8 @@ values (``epoch_metrics``: the loss as the mean over batches weighted by batch s
 
 Generation follows the reference's call: ``max_length=max_oup_seq_len``, ``num_return_sequences=num_beams``,
 ``early_stopping=False`` and no ``length_penalty`` argument, so HF's default 1.0 applies (not ``self.length_penalty``).
-With ``num_beams == 1`` HF runs greedy search, and so does this (``HipT5Generator.greedy``).  One state at a time.
+With ``num_beams == 1`` HF runs greedy search, and so does this (``HipT5Generator.greedy_many``).  A validation batch is one
+batched call (``generate_many``: one decode loop for all its states, the bits of one state at a time).
 """
 from __future__ import annotations
 
@@ -67,14 +68,16 @@ class RetrievalAugmentedGenerator:
         """num_beams decoded candidates per state (skip_special_tokens=True)."""
         ids = np.asarray(state_ids.cpu() if hasattr(state_ids, "cpu") else state_ids)
         n = np.asarray(state_mask.cpu() if hasattr(state_mask, "cpu") else state_mask).sum(1)
-        out = []
-        for b in range(ids.shape[0]):
-            src = ids[b, : int(n[b])]
+        srcs = [ids[b, : int(n[b])] for b in range(ids.shape[0])]
+        out: List[List[str]] = []
+        cap = self.generator.decoder.max_states(self.num_beams)  # the engine's cap on states per call
+        for i in range(0, len(srcs), cap):
+            chunk = srcs[i : i + cap]
             if self.num_beams == 1:
-                seqs = self.generator.greedy(src, self.max_oup_seq_len).sequences
+                res = self.generator.greedy_many(chunk, self.max_oup_seq_len)
             else:
-                seqs = self.generator.generate(src, self.num_beams, self.max_oup_seq_len, length_penalty=1.0).sequences
-            out.append(batch_decode(seqs.tolist(), skip_special_tokens=True))
+                res = self.generator.generate_many(chunk, self.num_beams, self.max_oup_seq_len, length_penalty=1.0)
+            out.extend(batch_decode(r.sequences.tolist(), skip_special_tokens=True) for r in res)
         return out
 
     def validation_step(self, batch: Dict[str, Any], _=None) -> Dict[str, float]:

@@ -61,6 +61,32 @@ class HuggingFaceGenerator(TacticGenerator):
                        num_samples: int) -> List[Tuple[str, float]]:
         return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
 
+    def batch_generate_sync(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
+                            theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:
+        """``generate_sync`` for several states through one decode loop (``HipT5Generator.generate_many``): entry ``i``
+        is ``generate_sync(states[i], ...)`` exactly, de-duplication order included."""
+        ids = [encode_one(self.template % s, self.max_inp_seq_len) for s in states]
+        results: List[List[Tuple[str, float]]] = []
+        cap = self.generator.decoder.max_states(num_samples)  # the engine's cap on states per call
+        for i in range(0, len(ids), cap):
+            outs = self.generator.generate_many(ids[i : i + cap], num_samples, self.max_oup_seq_len,
+                                                self.length_penalty)
+            for out in outs:
+                raw_output_text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
+                raw_scores = out.sequences_scores.tolist()
+                output_text, output_score = [], []
+                for j in range(num_samples):
+                    t = remove_marks(raw_output_text[j])
+                    if t not in output_text:
+                        output_text.append(t)
+                        output_score.append(raw_scores[j])
+                results.append(list(zip_strict(output_text, output_score)))
+        return results
+
+    async def batch_generate(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
+                             theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:
+        return self.batch_generate_sync(states, file_paths, theorem_full_names, theorem_poses, num_samples)
+
 
 class RetrievalAugmentedGenerator(TacticGenerator):
     """Reference :246-298: retrieve, format the augmented state, generate."""
@@ -92,6 +118,20 @@ class RetrievalAugmentedGenerator(TacticGenerator):
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
                        num_samples: int) -> List[Tuple[str, float]]:
         return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+
+    def batch_generate_sync(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
+                            theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:
+        """Retrieve per state (``retrieve``, as ``generate_sync``), format each augmented state, then one batched
+        generate."""
+        aug_states = []
+        for state, path, name, pos in zip_strict(states, file_paths, theorem_full_names, theorem_poses):
+            retrieved_premises, _ = self.retriever.retrieve(state, path, name, pos, self.max_num_retrieved)
+            aug_states.append(format_augmented_state(state, retrieved_premises, self.max_inp_seq_len))
+        return self.hf_gen.batch_generate_sync(aug_states, file_paths, theorem_full_names, theorem_poses, num_samples)
+
+    async def batch_generate(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
+                             theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:
+        return self.batch_generate_sync(states, file_paths, theorem_full_names, theorem_poses, num_samples)
 
 
 __all__ = ["TacticGenerator", "HuggingFaceGenerator", "RetrievalAugmentedGenerator"]

@@ -3,6 +3,14 @@
 max_length 512, length_penalty 0), and the decoder weight bytes per step against HBM bandwidth.  One JSON line.
 
     python tools/gen_bench.py [--out FILE]
+
+``--states B [B ...]``: batched generation instead.  For each B, ``generate_many`` over B distinct 2048-byte sources (64
+beams, max_length 512, length_penalty 0) against the loop of B ``generate`` calls, in one process, the two alternating;
+the same pair with the batched GEMM in its interleaved-row form (``dec_batch_gemm=0``; the default is the per-state kernel
+at a larger grid) at the largest B; and the validation shape (greedy, largest B).  Times, ratio (loop / batched), per-step milliseconds and kernel
+launches per step, as one JSON line.
+
+    python tools/gen_bench.py --states 1 4 8 [--reps 2] [--out FILE]
 """
 from __future__ import annotations
 
@@ -41,10 +49,90 @@ def step_us(gen, enc, nb, t, max_len, reps=20):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def _same(a, b):
+    return all(torch.equal(x.sequences, y.sequences) and torch.equal(x.sequences_scores, y.sequences_scores)
+               for x, y in zip(a, b))
+
+
+def states_bench(gen, cfg, states, reps, nb=64, max_len=512, src_bytes=2048):
+    from reprover_amd import _lib
+
+    lib = _lib.load()
+    rng = np.random.default_rng(0)
+    srcs = [np.concatenate([rng.integers(3, 259, size=src_bytes - 1), [1]]).astype(np.int32) for _ in range(max(states))]
+    L = cfg["num_decoder_layers"]
+    launches = 12 * L + 4  # per decode step: embed, 12 per layer, final norm, lm_head, log_softmax; + 2 for the selection
+    res = {"metric": "gen_batch_bench", "beams": nb, "max_length": max_len, "length_penalty": 0.0,
+           "config": f"byt5-small ({L} decoder layers), distinct sources of {src_bytes} bytes", "reps": reps, "states": {}}
+    gen.generate_many(srcs[:2], nb, 8, 0.0)  # warm-up: code objects of both paths and both GEMM forms
+    gen.generate(srcs[0], nb, 8, 0.0)
+    lib.rp_set_option(b"dec_batch_gemm", 0)
+    gen.generate_many(srcs[:2], nb, 8, 0.0)
+    lib.rp_set_option(b"dec_batch_gemm", 1)
+
+    def pair(B, greedy=False):
+        loop_ms, many_ms, steps_loop, steps_many, same = [], [], 0, 0, True
+        for _ in range(reps):
+            tr_loop = [[] for _ in range(B)]
+            if greedy:
+                ms, a = _timed(lambda: [gen.greedy(s, max_len) for s in srcs[:B]])
+                steps_loop = sum(o.sequences.shape[1] - 1 for o in a)
+            else:
+                ms, a = _timed(lambda: [gen.generate(s, nb, max_len, 0.0, trace=tr_loop[i]) for i, s in enumerate(srcs[:B])])
+                steps_loop = sum(len(t) for t in tr_loop)
+            loop_ms.append(ms)
+            tr = []
+            if greedy:
+                ms, b = _timed(lambda: gen.greedy_many(srcs[:B], max_len))
+                steps_many = max(o.sequences.shape[1] - 1 for o in b)
+            else:
+                ms, b = _timed(lambda: gen.generate_many(srcs[:B], nb, max_len, 0.0, traces=tr))
+                steps_many = max(len(t) for t in tr)
+            many_ms.append(ms)
+            same = same and _same(a, b)
+        lo, ma = min(loop_ms), min(many_ms)
+        sel = 0 if greedy else 2
+        return {"loop_ms": [round(x, 1) for x in loop_ms], "batched_ms": [round(x, 1) for x in many_ms],
+                "ratio_loop_over_batched": round(lo / ma, 3), "loop_steps": steps_loop, "batched_steps": steps_many,
+                "loop_ms_per_step": round(lo / steps_loop, 3), "batched_ms_per_step": round(ma / steps_many, 3),
+                "launches_per_step": {"loop": (launches + sel) * B, "batched": launches + sel},
+                "outputs_identical": same}
+
+    for B in states:
+        res["states"][str(B)] = pair(B)
+    B = max(states)
+    lib.rp_set_option(b"dec_batch_gemm", 0)
+    try:
+        res["interleaved_gemm_form"] = dict(pair(B), states=B)
+    finally:
+        lib.rp_set_option(b"dec_batch_gemm", 1)
+    res["greedy_validation_shape"] = dict(pair(B, greedy=True), states=B)
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--states", type=int, nargs="+", default=None, help="batched generation against the per-state loop")
+    ap.add_argument("--reps", type=int, default=2)
     args = ap.parse_args(argv)
+    if args.states:
+        cfg = synth.seq2seq_config("byt5-small")
+        gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
+        line = json.dumps(states_bench(gen, cfg, sorted(args.states), args.reps))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     cfg = synth.seq2seq_config("byt5-small")
     sd = synth.synth_seq2seq_state_dict(cfg)
     gen = HipT5Generator(cfg, sd, "cuda:0")
