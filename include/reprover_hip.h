@@ -518,11 +518,12 @@ RpStatus rp_beam_select(const float* logprobs, const float* running, int32_t nb,
                         float* scores, int32_t* tokens, int32_t* parents, void* workspace, size_t workspace_bytes,
                         void* stream);
 
-/* Batched generation: one decode loop for the beams of n proof states ("Batched
- * generation").  All states start together and sit at the same position t; a state that has finished
+/* Batched generation: one decode loop for the beams of n proof states ("One step,
+ * 1 - 32 states").  All states start together and sit at the same position t; a state that has finished
  * is left out of the step's active list and costs nothing.  For every state the outputs are the bits
  * that rp_decoder_cross_kv / rp_decoder_step / rp_beam_select give that state alone, whichever other
- * states share the call and in whatever order.
+ * states share the call and in whatever order: those three are the one-state calls of the functions
+ * below (n = 1, src_cu = {0, src_len}, active = {0}), one implementation.
  * Caps: 1 <= n <= 32 states, n * num_beams <= 1024 rows (16 states of 64 beams), num_beams <= 64, max_len <= 8192, every source
  * 1..8192 tokens, vocab <= 512.
  *   src_cu  HOST int32 [n + 1] prefix sums (start at 0): source b is rows src_cu[b] .. src_cu[b+1] of
@@ -548,7 +549,7 @@ RpStatus rp_decoder_batch_cross_kv(RpDecoder* dec, const void* enc_bf16, const i
  *   ancestry  device int32 [n_active * nb, anc_stride]: as rp_decoder_step, entries local to the state's
  *             own cache (row t * nb + b is the one written for beam b; entries are clamped to that cache)
  *   logprobs  device fp32 [n_active * nb, vocab]
- * One launch per kernel of rp_decoder_step, over all rows; the attentions size their LDS for the longest
+ * One launch per kernel over all rows (12 per layer + 4); the attentions size their LDS for the longest
  * key list of the call. */
 RpStatus rp_decoder_batch_step(RpDecoder* dec, const int32_t* src_cu, int32_t n, const int32_t* active,
                                int32_t n_active, const int32_t* tokens, const int32_t* ancestry,

@@ -1,9 +1,15 @@
 // libreprover_hip - the tactic generator's T5 decoder (include/reprover_hip.h).
 //
-// One beam-search step for nb <= 64 beams: per layer RMSNorm -> fused self QKV -> causal self-attention over the
-// ancestry-addressed cache -> o + residual -> RMSNorm -> cross q -> cross-attention over the source -> o + residual ->
-// gated-GELU FFN; then the final norm, lm_head and log_softmax.  Precision: bf16 weights and GEMM operands, fp32
-// accumulation, statistics, softmax and residual stream, fp32 log-probs.
+// One beam-search step for the nb <= 64 beams of each of 1..32 proof states: per layer RMSNorm -> fused self QKV ->
+// causal self-attention over the ancestry-addressed cache -> o + residual -> RMSNorm -> cross q -> cross-attention over
+// the source -> o + residual -> gated-GELU FFN; then the final norm, lm_head and log_softmax.  Precision: bf16 weights and
+// GEMM operands, fp32 accumulation, statistics, softmax and residual stream, fp32 log-probs.
+//
+// The rows of a step are the n_active * nb beams of the states that are still searching, packed slot by slot.  Embed,
+// RMSNorm, every projection, lm_head and log_softmax are row-wise and run over all rows in one launch each; the two
+// attentions run as one launch over (head, row), each row finding its state's cache, cross K/V and source length through
+// the slot table passed by value.  rp_decoder_step / rp_decoder_cross_kv / rp_beam_select are the one-state calls of
+// rp_decoder_batch_step / rp_decoder_batch_cross_kv / rp_beam_select_batch: there is one launch sequence.
 //
 // Every output element of every kernel here is computed by a reduction whose order depends only on the shapes (K, the
 // key count), never on which other rows share the launch or where the row sits in it: a row's log-probs are the same
@@ -16,6 +22,15 @@
 using namespace rp;
 
 namespace {
+
+constexpr int DEC_MAX_BEAMS = 64;
+constexpr int DEC_MAX_KIT = 8;          // GEMM K <= 8 * 512 = 4096 (a wave holds its weight row in registers)
+constexpr int DEC_MAX_KEYS = 8192;      // attention keys per launch (fp32 scores in dynamic LDS: 32 KB)
+constexpr int DEC_SELECT_MAX_K = 128;   // 2 * DEC_MAX_BEAMS
+constexpr int DEC_SELECT_ROW = 512;     // the per-row sort covers vocab <= 512
+constexpr int DEC_MERGE = 8192;         // nb * min(k, vocab) candidates <= 64 * 128
+constexpr int DEC_MAX_STATES = 32;      // states per call (a 32-bit mask checks the active list)
+constexpr int DEC_MAX_ROWS = 1024;      // states * nb: 16 states of 64 beams, 32 of 32 or fewer
 
 template <typename T>
 __global__ void dec_to_bf16_kernel(bf16_t* __restrict__ dst, const T* __restrict__ src, int64_t n) {
@@ -38,69 +53,261 @@ __global__ void dec_to_f32_kernel<bf16_t>(float* __restrict__ dst, const bf16_t*
     dst[i] = bf2f(src[i]);
 }
 
-// One (head, beam) per workgroup: dec_attention_row (rp_decoder_common.h) over the beam's q row, ancestry row and out row.
-__global__ __launch_bounds__(256) void dec_attention_kernel(const bf16_t* __restrict__ q, int ldq,
-                                                            const bf16_t* __restrict__ kv, int ldkv, int koff, int voff,
-                                                            int rows, const int32_t* __restrict__ anc, int astride,
-                                                            const float* __restrict__ tab, int nbias, int len,
-                                                            bf16_t* __restrict__ out, int ldo) {
-  extern __shared__ float s_sc[];
-  const int h = blockIdx.x, b = blockIdx.y;
-  dec_attention_row(s_sc, q + (size_t)b * ldq, kv, ldkv, koff, voff, rows, anc ? anc + (size_t)b * astride : nullptr, tab,
-                    nbias, len, out + (size_t)b * ldo, h);
+enum DecEpi { EPI_BF16 = 0, EPI_RESID = 1, EPI_F32 = 2, EPI_GEGLU = 3 };
+
+__device__ __forceinline__ float dot8(uint4 a, uint4 w, float acc) {
+  const uint32_t av[4] = {a.x, a.y, a.z, a.w}, wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    acc = fmaf(__uint_as_float(av[i] << 16), __uint_as_float(wv[i] << 16), acc);
+    acc = fmaf(__uint_as_float(av[i] & 0xffff0000u), __uint_as_float(wv[i] & 0xffff0000u), acc);
+  }
+  return acc;
 }
 
-// cache row t * nb + b of layer l <- the k, v columns of qkv[b]
+// out[m, n] = sum_k A[m, k] W[n, k] for rows m in [m0, m0 + 64) of this workgroup row, one wave per output column n.  The
+// wave keeps its weight row (KIT x 512 elements) in registers and streams the A rows past it; lane l covers the 16-byte
+// pieces l, l + 64, ... of K, and the 64 lane sums are combined by one xor butterfly: the same chain for every (m, n).
+// EPI_GEGLU: column n reads W rows n (wi_0) and n + N (wi_1), out = gelu_new(a0) * a1.
+template <int KIT, int EPI>
+__global__ __launch_bounds__(256) void dec_gemm_kernel(const bf16_t* __restrict__ A, int lda, int M,
+                                                       const bf16_t* __restrict__ W, int N, int K,
+                                                       void* __restrict__ out, int ldo) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const int nk = K >> 3;  // 16-byte pieces per row
+  uint4 w0[KIT], w1[KIT];
+#pragma unroll
+  for (int i = 0; i < KIT; ++i) {
+    const int j = lane + 64 * i;
+    w0[i] = (j < nk) ? reinterpret_cast<const uint4*>(W + (size_t)n * K)[j] : make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (EPI == EPI_GEGLU)
+      w1[i] = (j < nk) ? reinterpret_cast<const uint4*>(W + (size_t)(n + N) * K)[j] : make_uint4(0u, 0u, 0u, 0u);
+  }
+  const int m1 = min(M, (int)(blockIdx.y + 1) * 64);
+  for (int m = blockIdx.y * 64; m < m1; ++m) {
+    const uint4* a = reinterpret_cast<const uint4*>(A + (size_t)m * lda);
+    float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < KIT; ++i) {
+      const int j = lane + 64 * i;
+      const uint4 av = (j < nk) ? a[j] : make_uint4(0u, 0u, 0u, 0u);
+      acc0 = dot8(av, w0[i], acc0);
+      if constexpr (EPI == EPI_GEGLU) acc1 = dot8(av, w1[i], acc1);
+    }
+    acc0 = wave_sum64(acc0);
+    if constexpr (EPI == EPI_GEGLU) acc1 = wave_sum64(acc1);
+    if (lane == 0) {
+      if constexpr (EPI == EPI_BF16) reinterpret_cast<bf16_t*>(out)[(size_t)m * ldo + n] = f2bf(acc0);
+      if constexpr (EPI == EPI_RESID) reinterpret_cast<float*>(out)[(size_t)m * ldo + n] += acc0;
+      if constexpr (EPI == EPI_F32) reinterpret_cast<float*>(out)[(size_t)m * ldo + n] = acc0;
+      if constexpr (EPI == EPI_GEGLU) reinterpret_cast<bf16_t*>(out)[(size_t)m * ldo + n] = f2bf(gelu_tanh(acc0) * acc1);
+    }
+  }
+}
+
+template <int EPI>
+RpStatus launch_dec_gemm(const bf16_t* A, int lda, int M, const bf16_t* W, int N, int K, void* out, int ldo,
+                         hipStream_t s) {
+  const int kit = (K / 8 + 63) / 64;
+  const dim3 grid((N + 3) / 4, (M + 63) / 64);
+#define DEC_GEMM_CASE(I) \
+  case I: hipLaunchKernelGGL((dec_gemm_kernel<I, EPI>), grid, dim3(256), 0, s, A, lda, M, W, N, K, out, ldo); break;
+  switch (kit) {
+    DEC_GEMM_CASE(1) DEC_GEMM_CASE(2) DEC_GEMM_CASE(3) DEC_GEMM_CASE(4)
+    DEC_GEMM_CASE(5) DEC_GEMM_CASE(6) DEC_GEMM_CASE(7) DEC_GEMM_CASE(8)
+    default: return fail(RP_E_UNSUPPORTED, "decoder GEMM K=%d > %d", K, DEC_MAX_KIT * 512);
+  }
+#undef DEC_GEMM_CASE
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// per active slot: the state it carries and where that state's source sits in the packed cross K/V
+struct DecSlots {
+  int32_t state[DEC_MAX_STATES];
+  int32_t src_off[DEC_MAX_STATES];
+  int32_t src_len[DEC_MAX_STATES];
+};
+
+// One (head, row) of decoder attention: softmax(q k^T + bias) v over `len` keys, d_kv = 64, fp32 scores in s_sc (dynamic
+// LDS, >= len floats), by one 256-thread workgroup.  q / out point at the row's own q and output row, anc at its ancestry
+// row (or null).  Key p lives in row r(p) of kv (r = anc[p] clamped to [0, rows), or p); K at column koff + 64 h, V at
+// voff + 64 h.  bias (self-attention): tab[h * nbias + min(len - 1 - p, nbias - 1)] (distance query - key).  The
+// reductions (strided max / sum / PV loops, the 4-wave combine) depend on len alone.
+__device__ __forceinline__ void dec_attention_row(float* __restrict__ s_sc, const bf16_t* __restrict__ q,
+                                                  const bf16_t* __restrict__ kv, int ldkv, int koff, int voff, int rows,
+                                                  const int32_t* __restrict__ anc, const float* __restrict__ tab,
+                                                  int nbias, int len, bf16_t* __restrict__ out, int h) {
+  __shared__ float s_q[64];
+  __shared__ float red[4];
+  __shared__ float s_part[4][64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid < 64) s_q[tid] = bf2f(q[h * 64 + tid]);
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int p = tid; p < len; p += 256) {
+    int r = anc ? anc[p] : p;
+    r = min(max(r, 0), rows - 1);
+    const uint4* kr = reinterpret_cast<const uint4*>(kv + (size_t)r * ldkv + koff + h * 64);
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const uint4 k8 = kr[i];
+      const uint32_t kw[4] = {k8.x, k8.y, k8.z, k8.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        acc = fmaf(s_q[8 * i + 2 * e], __uint_as_float(kw[e] << 16), acc);
+        acc = fmaf(s_q[8 * i + 2 * e + 1], __uint_as_float(kw[e] & 0xffff0000u), acc);
+      }
+    }
+    if (tab) acc += tab[(size_t)h * nbias + min(len - 1 - p, nbias - 1)];
+    s_sc[p] = acc;
+    mx = fmaxf(mx, acc);
+  }
+  mx = block_max256(mx, red);
+  float sum = 0.f;
+  for (int p = tid; p < len; p += 256) {
+    const float e = __expf(s_sc[p] - mx);
+    s_sc[p] = e;
+    sum += e;
+  }
+  sum = block_sum256(sum, red);  // (its leading barrier also publishes s_sc)
+  float acc = 0.f;
+  for (int p = wave; p < len; p += 4) {
+    int r = anc ? anc[p] : p;
+    r = min(max(r, 0), rows - 1);
+    acc = fmaf(s_sc[p], bf2f(kv[(size_t)r * ldkv + voff + h * 64 + lane]), acc);
+  }
+  s_part[wave][lane] = acc;
+  __syncthreads();
+  if (tid < 64) {
+    const float o = ((s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid])) / sum;
+    out[h * 64 + tid] = f2bf(o);
+  }
+}
+
+// One (head, row) per workgroup, row = slot * nb + beam.  Self-attention (CROSS = false): the state's own cache of
+// `rows` = max_len * nb rows at kv + state * state_stride, keys through the row's ancestry entries (local to that cache),
+// len keys.  Cross-attention: the state's source rows of the packed cross K/V, all src_len keys, no bias.
+template <bool CROSS>
+__global__ __launch_bounds__(256) void dec_attention_kernel(const bf16_t* __restrict__ q, int ldq,
+                                                            const bf16_t* __restrict__ kv, int ldkv, int koff, int voff,
+                                                            int rows, size_t state_stride,
+                                                            const int32_t* __restrict__ anc, int astride,
+                                                            const float* __restrict__ tab, int nbias, int len, int nb,
+                                                            DecSlots slots, bf16_t* __restrict__ out, int ldo) {
+  extern __shared__ float s_sc[];
+  const int h = blockIdx.x, row = blockIdx.y;
+  const int slot = row / nb;
+  if constexpr (CROSS)
+    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)slots.src_off[slot] * ldkv, ldkv, koff, voff,
+                      slots.src_len[slot], nullptr, nullptr, 1, slots.src_len[slot], out + (size_t)row * ldo, h);
+  else
+    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)slots.state[slot] * state_stride, ldkv, koff, voff, rows,
+                      anc + (size_t)row * astride, tab, nbias, len, out + (size_t)row * ldo, h);
+}
+
+// cache row row0 + beam of the row's state <- the k, v columns of qkv[row]
 __global__ __launch_bounds__(256) void dec_store_kv_kernel(const bf16_t* __restrict__ qkv, int inner,
-                                                           bf16_t* __restrict__ cache, int row0) {
-  const int b = blockIdx.x;
-  for (int c = threadIdx.x; c < 2 * inner; c += 256)
-    cache[(size_t)(row0 + b) * 2 * inner + c] = qkv[(size_t)b * 3 * inner + inner + c];
+                                                           bf16_t* __restrict__ cache, size_t state_stride, int row0,
+                                                           int nb, DecSlots slots) {
+  const int row = blockIdx.x, slot = row / nb, b = row - slot * nb;
+  bf16_t* dst = cache + (size_t)slots.state[slot] * state_stride + (size_t)(row0 + b) * 2 * inner;
+  for (int c = threadIdx.x; c < 2 * inner; c += 256) dst[c] = qkv[(size_t)row * 3 * inner + inner + c];
+}
+
+__global__ __launch_bounds__(256) void dec_log_softmax_kernel(float* __restrict__ x, int V) {
+  __shared__ float red[4];
+  float* row = x + (size_t)blockIdx.x * V;
+  float mx = -INFINITY;
+  for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, row[c]);
+  mx = block_max256(mx, red);
+  float s = 0.f;
+  for (int c = threadIdx.x; c < V; c += 256) s += __expf(row[c] - mx);
+  s = block_sum256(s, red);
+  const float ls = logf(s);
+  for (int c = threadIdx.x; c < V; c += 256) row[c] = (row[c] - mx) - ls;
 }
 
 // ---- beam selection ---------------------------------------------------------------------------------------------------
-// per beam row: the top kr keys of logprobs[b, :] + running[b]
-__global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restrict__ lp, const float* __restrict__ running,
-                                                            int V, int kr, uint64_t* __restrict__ cand) {
-  __shared__ uint64_t s[DEC_SELECT_ROW];
-  const int b = blockIdx.x;
-  const float rb = running[b];
-  for (int i = threadIdx.x; i < DEC_SELECT_ROW; i += 256)
-    s[i] = (i < V) ? sel_key(lp[(size_t)b * V + i] + rb, (uint32_t)(b * V + i)) : 0ull;
-  bitonic_desc(s, DEC_SELECT_ROW);
-  for (int i = threadIdx.x; i < kr; i += 256) cand[(size_t)b * kr + i] = s[i];
+// Keys sort descending: high 32 bits = the score made order-preserving as an unsigned integer, low 32 = ~flat index (a
+// lower index ranks higher on equal scores, torch.topk's order).  -0.0 is keyed as +0.0: the two compare equal, so the
+// index decides between them.  NaN scores are outside the contract.
+__device__ __forceinline__ uint64_t sel_key(float v, uint32_t idx) {
+  uint32_t u = __float_as_uint(v);
+  if (u == 0x80000000u) u = 0u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((uint64_t)u << 32) | (uint64_t)(~idx);
+}
+__device__ __forceinline__ float key_score(uint64_t k) {
+  uint32_t u = (uint32_t)(k >> 32);
+  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  return __uint_as_float(u);
+}
+// bitonic sort, descending, of n (power of two) keys in LDS by the whole workgroup
+__device__ void bitonic_desc(uint64_t* s, int n) {
+  for (int size = 2; size <= n; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const bool desc = (i & size) == 0;
+          const uint64_t a = s[i], c = s[j];
+          if (desc ? (a < c) : (a > c)) {
+            s[i] = c;
+            s[j] = a;
+          }
+        }
+      }
+    }
+  __syncthreads();
 }
 
+// per beam row (row = slot * nb + b): the top kr keys of logprobs[row, :] + running[row], keyed by the flat index
+// b * V + i inside the state's own block
+__global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restrict__ lp, const float* __restrict__ running,
+                                                            int V, int kr, int nb, uint64_t* __restrict__ cand) {
+  __shared__ uint64_t s[DEC_SELECT_ROW];
+  const int row = blockIdx.x, b = row % nb;
+  const float rb = running[row];
+  for (int i = threadIdx.x; i < DEC_SELECT_ROW; i += 256)
+    s[i] = (i < V) ? sel_key(lp[(size_t)row * V + i] + rb, (uint32_t)(b * V + i)) : 0ull;
+  bitonic_desc(s, DEC_SELECT_ROW);
+  for (int i = threadIdx.x; i < kr; i += 256) cand[(size_t)row * kr + i] = s[i];
+}
+
+// per state: workgroup a sorts the state's n = nb * kr candidates and writes its k winners
 __global__ __launch_bounds__(1024) void beam_merge_kernel(const uint64_t* __restrict__ cand, int n, int V, int k,
                                                           float* __restrict__ scores, int32_t* __restrict__ tokens,
                                                           int32_t* __restrict__ parents) {
   __shared__ uint64_t s[DEC_MERGE];
+  const int a = blockIdx.x;
   int np2 = 1;
   while (np2 < n) np2 <<= 1;
-  for (int i = threadIdx.x; i < np2; i += 1024) s[i] = (i < n) ? cand[i] : 0ull;
+  for (int i = threadIdx.x; i < np2; i += 1024) s[i] = (i < n) ? cand[(size_t)a * n + i] : 0ull;
   bitonic_desc(s, np2);
   for (int i = threadIdx.x; i < k; i += 1024) {
     const uint32_t idx = ~(uint32_t)s[i];
-    scores[i] = key_score(s[i]);
-    tokens[i] = (int32_t)(idx % (uint32_t)V);
-    parents[i] = (int32_t)(idx / (uint32_t)V);
+    scores[(size_t)a * k + i] = key_score(s[i]);
+    tokens[(size_t)a * k + i] = (int32_t)(idx % (uint32_t)V);
+    parents[(size_t)a * k + i] = (int32_t)(idx / (uint32_t)V);
   }
 }
 
-}  // namespace
-
-namespace {
 struct DecWs {
-  bf16_t* ckv;    // [S, L * 2 * inner]
-  bf16_t* cache;  // [L][max_len * nb, 2 * inner]
-  float* x;       // [nb, D]
-  bf16_t* h;      // [nb, D] + [nb, F]
-  bf16_t* qkv;    // [nb, 3 * inner]
-  bf16_t* att;    // [nb, inner]
+  bf16_t* ckv;    // [sum S, L * 2 * inner]
+  bf16_t* cache;  // [n][L][max_len * nb, 2 * inner]
+  float* x;       // [n * nb, D]
+  bf16_t* h;      // [n * nb, D] then [n * nb, F]
+  bf16_t* qkv;    // [n * nb, 3 * inner]
+  bf16_t* att;    // [n * nb, inner]
   size_t bytes;
 };
-DecWs dec_carve(const RpDecoder* d, int nb, int max_len, int S, char* base) {
-  const size_t D = d->cfg.d_model, F = d->cfg.d_ff, inner = d->inner, L = d->cfg.num_layers;
+DecWs dec_carve(const RpDecoder* d, int n, int total_src, int nb, int max_len, char* base) {
+  const size_t D = d->cfg.d_model, F = d->cfg.d_ff, inner = d->inner, L = d->cfg.num_layers, M = (size_t)n * nb;
   DecWs w;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -108,12 +315,12 @@ DecWs dec_carve(const RpDecoder* d, int nb, int max_len, int S, char* base) {
     off += align_up(bytes, 256);
     return p;
   };
-  w.ckv = (bf16_t*)take((size_t)S * L * 2 * inner * 2);
-  w.cache = (bf16_t*)take(L * (size_t)max_len * nb * 2 * inner * 2);
-  w.x = (float*)take((size_t)nb * D * 4);
-  w.h = (bf16_t*)take((size_t)nb * (D + F) * 2);  // the normed rows, then the FFN's inner rows
-  w.qkv = (bf16_t*)take((size_t)nb * 3 * inner * 2);
-  w.att = (bf16_t*)take((size_t)nb * inner * 2);
+  w.ckv = (bf16_t*)take((size_t)total_src * L * 2 * inner * 2);
+  w.cache = (bf16_t*)take((size_t)n * L * max_len * nb * 2 * inner * 2);
+  w.x = (float*)take(M * D * 4);
+  w.h = (bf16_t*)take(M * (D + F) * 2);
+  w.qkv = (bf16_t*)take(M * 3 * inner * 2);
+  w.att = (bf16_t*)take(M * inner * 2);
   w.bytes = off;
   return w;
 }
@@ -199,6 +406,24 @@ RpStatus dec_pack(RpDecoder* d, const RpT5DecoderWeights* w) {
   RP_HIP(hipDeviceSynchronize());
   return RP_OK;
 }
+
+// the caps of a call; total_src = src_cu[n]
+RpStatus dec_check(const RpDecoder* d, const int32_t* src_cu, int n, int nb, int max_len, int& total_src) {
+  RP_REQUIRE(d, "null decoder");
+  RP_REQUIRE(src_cu, "null src_cu");
+  RP_REQUIRE(n >= 1 && n <= DEC_MAX_STATES, "states=%d (1..%d)", n, DEC_MAX_STATES);
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "num_beams=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(n * nb <= DEC_MAX_ROWS, "rows = states * num_beams = %d > %d", n * nb, DEC_MAX_ROWS);
+  RP_REQUIRE(max_len >= 1 && max_len <= DEC_MAX_KEYS, "max_len=%d (1..%d)", max_len, DEC_MAX_KEYS);
+  RP_REQUIRE(src_cu[0] == 0, "src_cu[0]=%d, not 0", src_cu[0]);
+  for (int b = 0; b < n; ++b) {
+    const int64_t S = (int64_t)src_cu[b + 1] - src_cu[b];
+    RP_REQUIRE(S >= 1 && S <= DEC_MAX_KEYS, "src_len of state %d = %lld (1..%d)", b, (long long)S, DEC_MAX_KEYS);
+  }
+  total_src = src_cu[n];
+  return RP_OK;
+}
+
 }  // namespace
 
 // modeling_t5.py _relative_position_bucket, bidirectional=False: n = -min(rel, 0); exact below num_buckets / 2, then
@@ -245,89 +470,129 @@ extern "C" void rp_decoder_destroy(RpDecoder* d) {
   delete d;
 }
 
-static RpStatus dec_check_shape(const RpDecoder* d, int nb, int max_len, int S) {
-  RP_REQUIRE(d, "null decoder");
-  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "num_beams=%d (1..%d)", nb, DEC_MAX_BEAMS);
-  RP_REQUIRE(max_len >= 1 && max_len <= DEC_MAX_KEYS, "max_len=%d (1..%d)", max_len, DEC_MAX_KEYS);
-  RP_REQUIRE(S >= 1 && S <= DEC_MAX_KEYS, "src_len=%d (1..%d)", S, DEC_MAX_KEYS);
-  return RP_OK;
+extern "C" size_t rp_decoder_batch_workspace_bytes(const RpDecoder* d, const int32_t* src_cu, int32_t n, int32_t nb,
+                                                   int32_t max_len) {
+  int total = 0;
+  if (dec_check(d, src_cu, n, nb, max_len, total) != RP_OK) return 0;
+  return dec_carve(d, n, total, nb, max_len, nullptr).bytes;
 }
 
-extern "C" size_t rp_decoder_workspace_bytes(const RpDecoder* d, int32_t nb, int32_t max_len, int32_t S) {
-  if (!d || nb < 1 || nb > DEC_MAX_BEAMS || max_len < 1 || max_len > DEC_MAX_KEYS || S < 1 || S > DEC_MAX_KEYS) return 0;
-  return dec_carve(d, nb, max_len, S, nullptr).bytes;
-}
-
-extern "C" RpStatus rp_decoder_cross_kv(RpDecoder* d, const void* enc, int32_t S, int32_t nb, int32_t max_len, void* ws,
-                                        size_t ws_bytes, void* stream_) {
-  RpStatus st = dec_check_shape(d, nb, max_len, S);
+extern "C" RpStatus rp_decoder_batch_cross_kv(RpDecoder* d, const void* enc, const int32_t* src_cu, int32_t n, int32_t nb,
+                                              int32_t max_len, void* ws, size_t ws_bytes, void* stream_) {
+  int total = 0;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
   if (st) return st;
   RP_REQUIRE(enc, "null encoder states");
-  const DecWs w = dec_carve(d, nb, max_len, S, (char*)ws);
+  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
   if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
   const int D = d->cfg.d_model, NKV = d->cfg.num_layers * 2 * d->inner;
-  return launch_dec_gemm<EPI_BF16>((const bf16_t*)enc, D, S, d->cross_kv_w, NKV, D, w.ckv, NKV, (hipStream_t)stream_);
+  return launch_dec_gemm<EPI_BF16>((const bf16_t*)enc, D, total, d->cross_kv_w, NKV, D, w.ckv, NKV, (hipStream_t)stream_);
 }
 
-extern "C" RpStatus rp_decoder_step(RpDecoder* d, const int32_t* tokens, const int32_t* anc, int32_t astride, int32_t nb,
-                                    int32_t t, int32_t max_len, int32_t S, float* logprobs, void* ws, size_t ws_bytes,
-                                    void* stream_) {
-  RpStatus st = dec_check_shape(d, nb, max_len, S);
+extern "C" RpStatus rp_decoder_batch_step(RpDecoder* d, const int32_t* src_cu, int32_t n, const int32_t* active,
+                                          int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
+                                          int32_t nb, int32_t t, int32_t max_len, float* logprobs, void* ws,
+                                          size_t ws_bytes, void* stream_) {
+  int total = 0;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
   if (st) return st;
-  RP_REQUIRE(tokens && anc && logprobs, "null argument");
+  RP_REQUIRE(active && tokens && anc && logprobs, "null argument");
+  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
   RP_REQUIRE(t >= 0 && t < max_len, "t=%d outside [0, max_len=%d)", t, max_len);
   RP_REQUIRE(astride >= t + 1, "anc_stride=%d < t + 1 = %d", astride, t + 1);
-  const DecWs w = dec_carve(d, nb, max_len, S, (char*)ws);
+  DecSlots slots = {};
+  uint32_t seen = 0;
+  int max_src = 0;
+  for (int a = 0; a < n_active; ++a) {
+    const int sidx = active[a];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share cache rows
+    seen |= 1u << sidx;
+    slots.state[a] = sidx;
+    slots.src_off[a] = src_cu[sidx];
+    slots.src_len[a] = src_cu[sidx + 1] - src_cu[sidx];
+    max_src = std::max(max_src, slots.src_len[a]);
+  }
+  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
   if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
   hipStream_t s = (hipStream_t)stream_;
   const RpT5Config& c = d->cfg;
   const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
   const float eps = c.layer_norm_eps;
-  const int rows = max_len * nb, ldckv = L * 2 * inner;
-  hipLaunchKernelGGL(dec_embed_kernel, dim3(nb), dim3(256), 0, s, tokens, d->embed, w.x, D, V);
+  const int M = n_active * nb, rows = max_len * nb, ldckv = L * 2 * inner;
+  const size_t layer_stride = (size_t)rows * 2 * inner, state_stride = (size_t)L * layer_stride;
+  bf16_t* ffn = w.h + (size_t)M * D;
+  hipLaunchKernelGGL(dec_embed_kernel, dim3(M), dim3(256), 0, s, tokens, d->embed, w.x, D, V);
   for (int i = 0; i < L; ++i) {
     const RpDecoder::Layer& l = d->layers[i];
-    bf16_t* cache = w.cache + (size_t)i * rows * 2 * inner;
+    bf16_t* cache = w.cache + (size_t)i * layer_stride;  // state 0's rows of layer i
     // self-attention (modeling_t5.py T5LayerSelfAttention): x += o(attn(rmsnorm(x)))
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(nb), dim3(256), 0, s, w.x, l.ln_self, w.h, D, eps, 1.f);
-    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, nb, l.wqkv, 3 * inner, D, w.qkv, 3 * inner, s))) return st;
-    hipLaunchKernelGGL(dec_store_kv_kernel, dim3(nb), dim3(256), 0, s, w.qkv, inner, cache, t * nb);
-    hipLaunchKernelGGL(dec_attention_kernel, dim3(H, nb), dim3(256), (t + 1) * sizeof(float), s, w.qkv, 3 * inner,
-                       cache, 2 * inner, 0, inner, rows, anc, astride, d->bias_tab, d->nbias, t + 1, w.att, inner);
-    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, nb, l.wo, D, inner, w.x, D, s))) return st;
-    // cross-attention (T5LayerCrossAttention): no position bias, all S source keys
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(nb), dim3(256), 0, s, w.x, l.ln_cross, w.h, D, eps, 1.f);
-    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, nb, l.cq, inner, D, w.qkv, inner, s))) return st;
-    hipLaunchKernelGGL(dec_attention_kernel, dim3(H, nb), dim3(256), S * sizeof(float), s, w.qkv, inner, w.ckv, ldckv,
-                       2 * i * inner, (2 * i + 1) * inner, S, (const int32_t*)nullptr, 0, (const float*)nullptr, 1, S,
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_self, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.wqkv, 3 * inner, D, w.qkv, 3 * inner, s))) return st;
+    hipLaunchKernelGGL(dec_store_kv_kernel, dim3(M), dim3(256), 0, s, w.qkv, inner, cache, state_stride, t * nb, nb, slots);
+    hipLaunchKernelGGL((dec_attention_kernel<false>), dim3(H, M), dim3(256), (t + 1) * sizeof(float), s, w.qkv, 3 * inner,
+                       cache, 2 * inner, 0, inner, rows, state_stride, anc, astride, d->bias_tab, d->nbias, t + 1, nb, slots,
                        w.att, inner);
-    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, nb, l.co, D, inner, w.x, D, s))) return st;
+    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.wo, D, inner, w.x, D, s))) return st;
+    // cross-attention (T5LayerCrossAttention): no position bias, all of the state's source keys
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_cross, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.cq, inner, D, w.qkv, inner, s))) return st;
+    hipLaunchKernelGGL((dec_attention_kernel<true>), dim3(H, M), dim3(256), max_src * sizeof(float), s, w.qkv, inner, w.ckv,
+                       ldckv, 2 * i * inner, (2 * i + 1) * inner, 0, (size_t)0, (const int32_t*)nullptr, 0,
+                       (const float*)nullptr, 1, 0, nb, slots, w.att, inner);
+    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.co, D, inner, w.x, D, s))) return st;
     // gated-GELU FFN (T5LayerFF / T5DenseGatedActDense)
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(nb), dim3(256), 0, s, w.x, l.ln_ff, w.h, D, eps, 1.f);
-    if ((st = launch_dec_gemm<EPI_GEGLU>(w.h, D, nb, l.wi, F, D, w.h + (size_t)nb * D, F, s))) return st;
-    if ((st = launch_dec_gemm<EPI_RESID>(w.h + (size_t)nb * D, F, nb, l.wo2, D, F, w.x, D, s))) return st;
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_ff, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_GEGLU>(w.h, D, M, l.wi, F, D, ffn, F, s))) return st;
+    if ((st = launch_dec_gemm<EPI_RESID>(ffn, F, M, l.wo2, D, F, w.x, D, s))) return st;
   }
   const float scale = d->tied ? 1.f / sqrtf((float)D) : 1.f;
-  hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(nb), dim3(256), 0, s, w.x, d->final_ln, w.h, D, eps, scale);
-  if ((st = launch_dec_gemm<EPI_F32>(w.h, D, nb, d->lm_head, V, D, logprobs, V, s))) return st;
-  hipLaunchKernelGGL(dec_log_softmax_kernel, dim3(nb), dim3(256), 0, s, logprobs, V);
+  hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, d->final_ln, w.h, D, eps, scale);
+  if ((st = launch_dec_gemm<EPI_F32>(w.h, D, M, d->lm_head, V, D, logprobs, V, s))) return st;
+  hipLaunchKernelGGL(dec_log_softmax_kernel, dim3(M), dim3(256), 0, s, logprobs, V);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
 
-extern "C" RpStatus rp_beam_select(const float* lp, const float* running, int32_t nb, int32_t V, int32_t k, float* scores,
-                                   int32_t* tokens, int32_t* parents, void* ws, size_t ws_bytes, void* stream_) {
+extern "C" RpStatus rp_beam_select_batch(const float* lp, const float* running, int32_t n_active, int32_t nb, int32_t V,
+                                         int32_t k, float* scores, int32_t* tokens, int32_t* parents, void* ws,
+                                         size_t ws_bytes, void* stream_) {
   RP_REQUIRE(lp && running && scores && tokens && parents, "null argument");
+  RP_REQUIRE(n_active >= 1 && n_active <= DEC_MAX_STATES, "states=%d (1..%d)", n_active, DEC_MAX_STATES);
   RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "nb=%d (1..%d)", nb, DEC_MAX_BEAMS);
   RP_REQUIRE(V >= 1 && V <= DEC_SELECT_ROW, "vocab=%d (1..%d)", V, DEC_SELECT_ROW);
   RP_REQUIRE(k >= 1 && k <= DEC_SELECT_MAX_K && k <= nb * V, "k=%d (1..min(%d, nb * vocab))", k, DEC_SELECT_MAX_K);
   const int kr = std::min(k, V);  // a row contributes at most k candidates
-  const size_t need = (size_t)nb * kr * sizeof(uint64_t);
+  const size_t need = (size_t)n_active * nb * kr * sizeof(uint64_t);
   if (!ws || ws_bytes < need) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, need);
   hipStream_t s = (hipStream_t)stream_;
   uint64_t* cand = (uint64_t*)ws;
-  hipLaunchKernelGGL(beam_row_topk_kernel, dim3(nb), dim3(256), 0, s, lp, running, V, kr, cand);
-  hipLaunchKernelGGL(beam_merge_kernel, dim3(1), dim3(1024), 0, s, cand, nb * kr, V, k, scores, tokens, parents);
+  hipLaunchKernelGGL(beam_row_topk_kernel, dim3(n_active * nb), dim3(256), 0, s, lp, running, V, kr, nb, cand);
+  hipLaunchKernelGGL(beam_merge_kernel, dim3(n_active), dim3(1024), 0, s, cand, nb * kr, V, k, scores, tokens, parents);
   RP_CHECK_LAUNCH();
   return RP_OK;
+}
+
+// ---- the per-state entry points: one state, its source at rows [0, S), alone in the active list --------------------------
+extern "C" size_t rp_decoder_workspace_bytes(const RpDecoder* d, int32_t nb, int32_t max_len, int32_t S) {
+  const int32_t cu[2] = {0, S};
+  return rp_decoder_batch_workspace_bytes(d, cu, 1, nb, max_len);
+}
+
+extern "C" RpStatus rp_decoder_cross_kv(RpDecoder* d, const void* enc, int32_t S, int32_t nb, int32_t max_len, void* ws,
+                                        size_t ws_bytes, void* stream) {
+  const int32_t cu[2] = {0, S};
+  return rp_decoder_batch_cross_kv(d, enc, cu, 1, nb, max_len, ws, ws_bytes, stream);
+}
+
+extern "C" RpStatus rp_decoder_step(RpDecoder* d, const int32_t* tokens, const int32_t* anc, int32_t astride, int32_t nb,
+                                    int32_t t, int32_t max_len, int32_t S, float* logprobs, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  const int32_t cu[2] = {0, S}, active = 0;
+  return rp_decoder_batch_step(d, cu, 1, &active, 1, tokens, anc, astride, nb, t, max_len, logprobs, ws, ws_bytes, stream);
+}
+
+extern "C" RpStatus rp_beam_select(const float* lp, const float* running, int32_t nb, int32_t V, int32_t k, float* scores,
+                                   int32_t* tokens, int32_t* parents, void* ws, size_t ws_bytes, void* stream) {
+  return rp_beam_select_batch(lp, running, 1, nb, V, k, scores, tokens, parents, ws, ws_bytes, stream);
 }

@@ -1,11 +1,11 @@
 """HipT5Generator: T5ForConditionalGeneration.generate (beam search) on libreprover_hip.
 
 The encoder is ``HipT5Encoder`` (``rp_encode_hidden``: last_hidden_state instead of the pool); the decoder is
-``rp_decoder_*`` (one launch sequence per beam-search step); the beam bookkeeping is
-``reprover_amd.generation.beam_search`` with the device top-2nb selection ``rp_beam_select``.  The teacher-forced loss
-(``forward`` / ``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.  ``generate_many`` / ``greedy_many`` run
-the beams of several sources through one decode loop (``rp_decoder_batch_*``, ``rp_beam_select_batch``) and return, per
-source, the bits of ``generate`` / ``greedy``.
+``rp_decoder_*`` (one launch sequence per beam-search step for 1..32 states); the beam bookkeeping
+is ``reprover_amd.generation.beam_search_batch`` with the device top-2nb selection ``rp_beam_select_batch``.
+``generate_many`` / ``greedy_many`` run the beams of several sources through that loop and return, per source, the bits
+of ``generate`` / ``greedy``, which are its one-state calls.  The teacher-forced loss (``forward`` /
+``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.
 PyTorch tensors are containers only.
 """
 from __future__ import annotations
@@ -23,6 +23,7 @@ from .encoder import HipT5Encoder, _require_gpu
 from .generation import BeamSearchOutput, beam_search, beam_search_batch, greedy_search, greedy_search_batch
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
+_STATE_0 = np.zeros(1, dtype=np.int32)  # the active list of a one-state step
 
 _DEC_KEYS = {
     "ln_self": "layer.0.layer_norm.weight",
@@ -189,38 +190,17 @@ class HipT5Decoder:
                 pass
             self._handle = None
 
+    # -- one state: the one-state calls of start_many / step_many / select_many below -------------------------------------
     def workspace_bytes(self, nb: int, max_len: int, src_len: int) -> int:
-        return int(self._lib.rp_decoder_workspace_bytes(self._handle, nb, max_len, src_len))
+        return self._many_workspace_bytes(np.array([0, src_len], dtype=np.int32), nb, max_len)
 
     def start(self, enc_bf16: torch.Tensor, nb: int, max_len: int) -> None:
         """Cross K/V of one source [S, d_model] bf16 for a search of ``nb`` beams and ``max_len`` positions."""
-        assert enc_bf16.dtype == torch.bfloat16 and enc_bf16.is_contiguous()
-        S = enc_bf16.shape[0]
-        n = self.workspace_bytes(nb, max_len, S)
-        if n == 0:
-            raise _lib.HipLibraryError(f"unsupported generate shape: num_beams={nb} max_len={max_len} src_len={S}")
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = None
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        self.nb, self.max_len, self.S = nb, max_len, S
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_decoder_cross_kv(self._handle, enc_bf16.data_ptr(), S, nb, max_len,
-                                                     self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
-                       "rp_decoder_cross_kv")
+        self.start_many(enc_bf16, np.array([0, enc_bf16.shape[0]], dtype=np.int32), nb, max_len)
 
     def step(self, tokens: torch.Tensor, ancestry: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """log-probs [nb, V] of one step (``beam_search``'s ``step``; ancestry int [nb, t + 1])."""
-        nb, T = ancestry.shape
-        tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
-        anc = ancestry.to(device=self.device, dtype=torch.int32).contiguous()
-        if out is None:
-            out = torch.empty((nb, self.V), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_decoder_step(self._handle, tok.data_ptr(), anc.data_ptr(), T, nb, T - 1, self.max_len,
-                                                 self.S, out.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                                 _lib.current_stream()),
-                       "rp_decoder_step")
-        return out
+        return self.step_many(_STATE_0, tokens, ancestry, out)
 
     def forward(self, enc_bf16: torch.Tensor, src_cu: np.ndarray, tokens: np.ndarray, labels: np.ndarray,
                 tgt_cu: np.ndarray, rows: bool = False):
@@ -255,30 +235,20 @@ class HipT5Decoder:
         return lp, (s, c), out_rows
 
     def select(self, log_probs: torch.Tensor, running: torch.Tensor, k: int):
-        """Device top-k of log_probs + running[:, None] (``rp_beam_select``): (scores, tokens, parents)."""
-        nb, V = log_probs.shape
-        need = nb * min(k, V) * 8
-        if self._sel_ws is None or self._sel_ws.numel() < need:
-            self._sel_ws = torch.empty(max(need, 64 * 128 * 8), dtype=torch.uint8, device=self.device)
-        run = running.to(device=self.device, dtype=torch.float32).contiguous()
-        lp = log_probs.contiguous()
-        scores = torch.empty(k, dtype=torch.float32, device=self.device)
-        toks = torch.empty(k, dtype=torch.int32, device=self.device)
-        par = torch.empty(k, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_beam_select(lp.data_ptr(), run.data_ptr(), nb, V, k, scores.data_ptr(), toks.data_ptr(),
-                                                par.data_ptr(), self._sel_ws.data_ptr(), self._sel_ws.numel(),
-                                                _lib.current_stream()),
-                       "rp_beam_select")
-        return scores, toks, par
-
+        """Device top-k of log_probs + running[:, None] (``rp_beam_select``): (scores, tokens, parents), each ``[k]``."""
+        scores, toks, par = self.select_many(log_probs, running, log_probs.shape[0], k)
+        return scores[0], toks[0], par[0]
 
     @staticmethod
     def max_states(nb: int) -> int:
         """States one batched call takes at ``nb`` beams (include/reprover_hip.h: 32 states, 1024 rows)."""
         return max(1, min(32, 1024 // max(1, int(nb))))
 
-    # -- batched generation (rp_decoder_batch_*): every state's rows are the bits of start / step / select alone --------
+    # -- 1..max_states states (rp_decoder_batch_*): a state's rows are the same bits alone or with others ----------------
+    def _many_workspace_bytes(self, cu: np.ndarray, nb: int, max_len: int) -> int:
+        return int(self._lib.rp_decoder_batch_workspace_bytes(self._handle, cu.ctypes.data_as(C.c_void_p), len(cu) - 1, nb,
+                                                              max_len))
+
     def start_many(self, enc_bf16: torch.Tensor, src_cu: np.ndarray, nb: int, max_len: int) -> None:
         """Cross K/V of ``n`` sources packed varlen (enc_bf16 [sum S_b, d_model] bf16, host ``src_cu [n + 1]``) for a
         search of ``nb`` beams and ``max_len`` positions per state, in one GEMM."""
@@ -288,18 +258,17 @@ class HipT5Decoder:
         if n < 1 or enc_bf16.shape[0] != int(cu[-1]):
             raise _lib.HipLibraryError(f"start_many: {n} states, src_cu[-1]={int(cu[-1]) if len(cu) else None} for "
                                        f"{enc_bf16.shape[0]} encoder rows")
-        need = int(self._lib.rp_decoder_batch_workspace_bytes(self._handle, cu.ctypes.data_as(C.c_void_p), n, nb, max_len))
+        need = self._many_workspace_bytes(cu, nb, max_len)
         if need == 0:
-            raise _lib.HipLibraryError("unsupported batched generate shape: "
-                                       + self._lib.rp_last_error().decode(errors="replace"))
-        if getattr(self, "_many_ws", None) is None or self._many_ws.numel() < need:
-            self._many_ws = None
-            self._many_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            raise _lib.HipLibraryError("unsupported generate shape: " + self._lib.rp_last_error().decode(errors="replace"))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         self._many = (cu, n, nb, max_len)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rp_decoder_batch_cross_kv(self._handle, enc_bf16.data_ptr(), cu.ctypes.data_as(C.c_void_p),
-                                                           n, nb, max_len, self._many_ws.data_ptr(),
-                                                           self._many_ws.numel(), _lib.current_stream()),
+                                                           n, nb, max_len, self._ws.data_ptr(), self._ws.numel(),
+                                                           _lib.current_stream()),
                        "rp_decoder_batch_cross_kv")
 
     def step_many(self, active, tokens: torch.Tensor, ancestry: torch.Tensor,
@@ -320,8 +289,7 @@ class HipT5Decoder:
             _lib.check(self._lib.rp_decoder_batch_step(self._handle, cu.ctypes.data_as(C.c_void_p), n,
                                                        act.ctypes.data_as(C.c_void_p), len(act), tok.data_ptr(),
                                                        anc.data_ptr(), T, nb, T - 1, max_len, out.data_ptr(),
-                                                       self._many_ws.data_ptr(), self._many_ws.numel(),
-                                                       _lib.current_stream()),
+                                                       self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
                        "rp_decoder_batch_step")
         return out
 
@@ -331,8 +299,8 @@ class HipT5Decoder:
         rows, V = log_probs.shape
         na = rows // nb
         need = rows * min(k, V) * 8
-        if getattr(self, "_sel_many_ws", None) is None or self._sel_many_ws.numel() < need:
-            self._sel_many_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self._sel_ws is None or self._sel_ws.numel() < need:
+            self._sel_ws = torch.empty(max(need, 64 * 128 * 8), dtype=torch.uint8, device=self.device)
         run = running.to(device=self.device, dtype=torch.float32).contiguous()
         lp = log_probs.contiguous()
         scores = torch.empty((na, k), dtype=torch.float32, device=self.device)
@@ -340,8 +308,8 @@ class HipT5Decoder:
         par = torch.empty((na, k), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rp_beam_select_batch(lp.data_ptr(), run.data_ptr(), na, nb, V, k, scores.data_ptr(),
-                                                      toks.data_ptr(), par.data_ptr(), self._sel_many_ws.data_ptr(),
-                                                      self._sel_many_ws.numel(), _lib.current_stream()),
+                                                      toks.data_ptr(), par.data_ptr(), self._sel_ws.data_ptr(),
+                                                      self._sel_ws.numel(), _lib.current_stream()),
                        "rp_beam_select_batch")
         return scores, toks, par
 

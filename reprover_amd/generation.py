@@ -19,6 +19,9 @@ The model enters through two callables:
 
 Host synchronisation: the ``2 nb`` selected triples are read back once per step (``.cpu()``) because the finished-beam
 bookkeeping below runs on the host.  At 64 beams that is one ~1.5 KB copy and one stream sync per step.
+
+There is one loop per search kind, over 1..n sources (``beam_search_batch``, ``greedy_search_batch``); ``beam_search`` and
+``greedy_search`` wrap their ``step`` / ``select`` into its ``_many`` protocol and run it with one source.
 """
 from __future__ import annotations
 
@@ -47,7 +50,7 @@ def topk_select(log_probs: torch.Tensor, running_scores: torch.Tensor, k: int):
 class _BeamState:
     """The host bookkeeping of one source's beam search: ``inputs`` gives the step's tokens and ancestry table,
     ``advance`` takes the step's top-``2 nb`` candidates (host tensors) and says whether the search is over.
-    ``beam_search`` drives one of these, ``beam_search_batch`` several in lockstep."""
+    ``beam_search_batch`` drives one per source in lockstep; ``beam_search`` is its one-source call."""
 
     def __init__(self, num_beams: int, max_length: int, length_penalty: float, eos_token_id: int,
                  decoder_start_token_id: int, num_return_sequences: Optional[int]):
@@ -134,23 +137,15 @@ def beam_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], num_
                 length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
                 num_return_sequences: Optional[int] = None, select: Callable = topk_select,
                 device=None, trace: Optional[list] = None) -> BeamSearchOutput:
-    """Beam search over ``step`` (module docstring).  ``trace``, when a list, receives the per-step top-``2 nb``
-    candidates ``(scores, tokens, parents)`` as host tensors."""
-    st = _BeamState(num_beams, max_length, length_penalty, eos_token_id, decoder_start_token_id, num_return_sequences)
-    while True:
-        tokens, ancestry = st.inputs()
-        running = st.running_scores
-        if device is not None:
-            tokens, ancestry, running = tokens.to(device), ancestry.to(device), running.to(device)
-        log_probs = step(tokens, ancestry)
-        # _get_top_k_continuations (:3077-3129)
-        vals, toks, parents = select(log_probs, running, st.keep)
-        vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
-        if trace is not None:
-            trace.append((vals.clone(), toks.clone(), parents.clone()))
-        if st.advance(vals, toks, parents):
-            break
-    return st.result()
+    """Beam search over ``step`` (module docstring): ``beam_search_batch`` with one state.  ``trace``, when a list,
+    receives the per-step top-``2 nb`` candidates ``(scores, tokens, parents)`` as host tensors."""
+    traces: Optional[list] = None if trace is None else []
+    out, = beam_search_batch(lambda active, tokens, ancestry: step(tokens, ancestry), 1, num_beams, max_length,
+                             length_penalty, eos_token_id, decoder_start_token_id, num_return_sequences,
+                             lambda lp, running, nb, k: tuple(x[None] for x in select(lp, running, k)), device, traces)
+    if trace is not None:
+        trace.extend(traces[0])
+    return out
 
 
 def topk_select_many(log_probs: torch.Tensor, running_scores: torch.Tensor, nb: int, k: int):
@@ -164,9 +159,9 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
                       eos_token_id: int = 1, decoder_start_token_id: int = 0,
                       num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
                       traces: Optional[list] = None) -> List[BeamSearchOutput]:
-    """``beam_search`` for ``num_states`` sources in lockstep: one ``step_many`` and one ``select_many`` per position,
-    one readback of the ``n_active x 2 nb`` triples.  Every state runs ``beam_search``'s bookkeeping unchanged and leaves
-    the active list at the step where the single-state loop would stop; the loop runs until the last one has.
+    """The search loop: ``num_states`` sources in lockstep, one ``step_many`` and one ``select_many`` per position, one
+    readback of the ``n_active x 2 nb`` triples.  Every state keeps its own bookkeeping (``_BeamState``) and leaves the
+    active list at the step where it would stop alone; the loop runs until the last one has.
 
     - ``step_many(active, tokens, ancestry) -> log_probs``: ``active`` is the list of state indices still searching
       (ascending); row ``a * nb + b`` of ``tokens [n_active * nb]`` / ``ancestry [n_active * nb, t + 1]`` is beam ``b``
@@ -192,7 +187,8 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
         vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
         still = []
         for a, i in enumerate(active):
-            per_state[i].append((vals[a].clone(), toks[a].clone(), parents[a].clone()))
+            if traces is not None:
+                per_state[i].append((vals[a].clone(), toks[a].clone(), parents[a].clone()))
             if not states[i].advance(vals[a], toks[a], parents[a]):
                 still.append(i)
         active = still
@@ -206,31 +202,17 @@ def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], ma
     """``generate(num_beams=1, do_sample=False, max_length=L)``, which HF runs as greedy search (``_sample`` without
     sampling), not as a one-beam beam search: the argmax token (ties to the lowest id) until EOS or ``max_length``
     tokens including the start token.  After an EOS candidate a beam search keeps looking and may return a longer
-    sequence; greedy stops.  ``sequences_scores`` holds the sum of the chosen tokens' log-probs (HF reports none)."""
-    if max_length <= 1:
-        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
-    seq = [int(decoder_start_token_id)]
-    total = 0.0
-    while len(seq) < max_length:
-        t = len(seq) - 1
-        tokens = torch.tensor([seq[-1]], dtype=torch.int64)
-        anc = torch.arange(t + 1, dtype=torch.int64)[None]
-        if device is not None:
-            tokens, anc = tokens.to(device), anc.to(device)
-        lp = step(tokens, anc)[0].float().cpu()
-        best = int(torch.nonzero(lp == lp.max())[0, 0])
-        total += float(lp[best])
-        seq.append(best)
-        if best == eos_token_id:
-            break
-    return BeamSearchOutput(torch.tensor([seq], dtype=torch.int64), torch.tensor([total], dtype=torch.float32))
+    sequence; greedy stops.  ``sequences_scores`` holds the sum of the chosen tokens' log-probs (HF reports none).
+    ``greedy_search_batch`` with one state."""
+    return greedy_search_batch(lambda active, tokens, ancestry: step(tokens, ancestry), 1, max_length, eos_token_id,
+                               decoder_start_token_id, device)[0]
 
 
 def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, eos_token_id: int = 1,
                         decoder_start_token_id: int = 0, device=None) -> List[BeamSearchOutput]:
-    """``greedy_search`` for ``num_states`` sources in lockstep (one beam each): one ``step_many`` (as in
-    ``beam_search_batch``) and one readback of the active states' log-prob rows per position.  A state leaves the
-    active list at its EOS; the loop ends with the last one or at ``max_length``."""
+    """The greedy loop (``greedy_search``'s semantics per source): ``num_states`` sources in lockstep, one beam each,
+    one ``step_many`` (as in ``beam_search_batch``) and one readback of the active states' log-prob rows per position.
+    A state leaves the active list at its EOS; the loop ends with the last one or at ``max_length``."""
     if max_length <= 1:
         raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
     seqs = [[int(decoder_start_token_id)] for _ in range(num_states)]

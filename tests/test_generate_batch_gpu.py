@@ -67,7 +67,7 @@ def _same_trace(got, want):
 @pytest.mark.parametrize("nb", [1, 4, 64])
 def test_step_many_rows_and_cross_kv_equal_the_per_state_step(tiny_gen, nb):
     """Sources of 1, 300 and 2048 bytes in one batch; the ancestry tables of seeded simulated searches (rows reordered
-    with repeats, one search per state); all states active, then strict subsets.  Both GEMM forms."""
+    with repeats, one search per state); all states active, then strict subsets."""
     z, cfg, sd, gen = tiny_gen
     dec = gen.decoder
     srcs = [source_ids(1, 0), np.asarray(z["src"], dtype=np.int32), source_ids(2048, 21)]
@@ -84,26 +84,20 @@ def test_step_many_rows_and_cross_kv_equal_the_per_state_step(tiny_gen, nb):
         dec.start(e, nb, T)
         ref_ckv.append(dec._ws[: e.shape[0] * nkv * 2].clone())
         ref.append([dec.step(tok, anc).clone() for _, tok, anc in runs[i]])
-    lib = _lib.load()
-    try:
-        for form in (0, 1):
-            _lib.check(lib.rp_set_option(b"dec_batch_gemm", form), "rp_set_option")
-            dec.start_many(enc, cu, nb, T)
-            got_ckv = dec._many_ws[: int(cu[-1]) * nkv * 2]
-            assert torch.equal(got_ckv, torch.cat(ref_ckv))  # one GEMM over all rows = rp_decoder_cross_kv per source
-            for t in range(T):
-                active = [0, 1, 2] if t < 4 else ([0, 2] if t < 7 else [1])
-                if t == 7:  # state 1 sat out steps 4-6: give it its rows for those positions (alone in the list)
-                    for tt in range(4, 7):
-                        one = dec.step_many([1], runs[1][tt][1], runs[1][tt][2])
-                        assert torch.equal(one, ref[1][tt])
-                tok = torch.cat([runs[i][t][1] for i in active])
-                anc = torch.cat([runs[i][t][2] for i in active])
-                lp = dec.step_many(active, tok, anc)
-                for a, i in enumerate(active):
-                    assert torch.equal(lp[a * nb : (a + 1) * nb], ref[i][t]), (form, t, i)
-    finally:
-        lib.rp_set_option(b"dec_batch_gemm", 1)  # the default
+    dec.start_many(enc, cu, nb, T)
+    got_ckv = dec._ws[: int(cu[-1]) * nkv * 2]
+    assert torch.equal(got_ckv, torch.cat(ref_ckv))  # one GEMM over all rows = rp_decoder_cross_kv per source
+    for t in range(T):
+        active = [0, 1, 2] if t < 4 else ([0, 2] if t < 7 else [1])
+        if t == 7:  # state 1 sat out steps 4-6: give it its rows for those positions (alone in the list)
+            for tt in range(4, 7):
+                one = dec.step_many([1], runs[1][tt][1], runs[1][tt][2])
+                assert torch.equal(one, ref[1][tt])
+        tok = torch.cat([runs[i][t][1] for i in active])
+        anc = torch.cat([runs[i][t][2] for i in active])
+        lp = dec.step_many(active, tok, anc)
+        for a, i in enumerate(active):
+            assert torch.equal(lp[a * nb : (a + 1) * nb], ref[i][t]), (t, i)
 
 
 def test_step_many_does_not_depend_on_slot_order(tiny_gen):
@@ -330,6 +324,59 @@ def test_prover_batch_generate_equals_generate_sync(gen_dir):
 
 
 # ---- ABI -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nb,S", [(1, 1), (3, 257), (64, 300)])
+def test_per_state_entry_points_are_the_one_state_batched_call(tiny_gen, nb, S):
+    """Through the C ABI: rp_decoder_cross_kv + rp_decoder_step on one zero-filled workspace, rp_decoder_batch_cross_kv +
+    rp_decoder_batch_step (n = 1, active = {0}) on another.  After every step the log-probs and the whole workspaces are
+    equal byte for byte, and rp_beam_select / rp_beam_select_batch(n_active = 1) pick the same candidates.  nb = 1 and 3:
+    the row / nb arithmetic and a merge that is no power of two; nb = 64 with k = 128 fills the merge; S = 257 crosses
+    one 256-thread trip of the attention loops."""
+    z, cfg, sd, gen = tiny_gen
+    lib = _lib.load()
+    h = gen.decoder._handle
+    C = _lib.C
+    T, V, k = 3, cfg["vocab_size"], 2 * nb
+    enc = gen.encode_hidden(source_ids(S, 70 + nb))
+    cu = np.array([0, S], dtype=np.int32)
+    act = np.zeros(1, dtype=np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    need = lib.rp_decoder_workspace_bytes(h, nb, T, S)
+    assert need > 0 and need == lib.rp_decoder_batch_workspace_bytes(h, p(cu), 1, nb, T)
+    ws1 = torch.zeros(need, dtype=torch.uint8, device=DEV)
+    ws2 = torch.zeros(need, dtype=torch.uint8, device=DEV)
+    _lib.check(lib.rp_decoder_cross_kv(h, enc.data_ptr(), S, nb, T, ws1.data_ptr(), need, None), "rp_decoder_cross_kv")
+    _lib.check(lib.rp_decoder_batch_cross_kv(h, enc.data_ptr(), p(cu), 1, nb, T, ws2.data_ptr(), need, None),
+               "rp_decoder_batch_cross_kv")
+    assert torch.equal(ws1, ws2)
+    sel_need = nb * min(k, V) * 8
+    sel_ws = torch.empty(sel_need, dtype=torch.uint8, device=DEV)
+    run = torch.randn(nb, generator=torch.Generator().manual_seed(nb)).to(DEV)
+    new = lambda dt: torch.empty(k, dtype=dt, device=DEV)  # noqa: E731
+    for t, tok, anc in simulated_search(nb, T, seed=80 + nb):
+        tok, anc = tok.to(DEV, torch.int32), anc.to(DEV, torch.int32).contiguous()
+        lp1 = torch.empty((nb, V), dtype=torch.float32, device=DEV)
+        lp2 = torch.empty_like(lp1)
+        _lib.check(lib.rp_decoder_step(h, tok.data_ptr(), anc.data_ptr(), t + 1, nb, t, T, S, lp1.data_ptr(),
+                                       ws1.data_ptr(), need, None), "rp_decoder_step")
+        _lib.check(lib.rp_decoder_batch_step(h, p(cu), 1, p(act), 1, tok.data_ptr(), anc.data_ptr(), t + 1, nb, t, T,
+                                             lp2.data_ptr(), ws2.data_ptr(), need, None), "rp_decoder_batch_step")
+        assert torch.equal(lp1.view(torch.int32), lp2.view(torch.int32)), t
+        assert torch.equal(ws1, ws2), t
+        s1, t1, p1, s2, t2, p2 = new(torch.float32), new(torch.int32), new(torch.int32), new(torch.float32), \
+            new(torch.int32), new(torch.int32)
+        # the two select workspace requirements are the same number: both take sel_need bytes and refuse one fewer
+        assert lib.rp_beam_select(lp1.data_ptr(), run.data_ptr(), nb, V, k, s1.data_ptr(), t1.data_ptr(), p1.data_ptr(),
+                                  sel_ws.data_ptr(), sel_need - 1, None) == -3
+        assert lib.rp_beam_select_batch(lp2.data_ptr(), run.data_ptr(), 1, nb, V, k, s2.data_ptr(), t2.data_ptr(),
+                                        p2.data_ptr(), sel_ws.data_ptr(), sel_need - 1, None) == -3
+        _lib.check(lib.rp_beam_select(lp1.data_ptr(), run.data_ptr(), nb, V, k, s1.data_ptr(), t1.data_ptr(),
+                                      p1.data_ptr(), sel_ws.data_ptr(), sel_need, None), "rp_beam_select")
+        _lib.check(lib.rp_beam_select_batch(lp2.data_ptr(), run.data_ptr(), 1, nb, V, k, s2.data_ptr(), t2.data_ptr(),
+                                            p2.data_ptr(), sel_ws.data_ptr(), sel_need, None), "rp_beam_select_batch")
+        assert torch.equal(s1.view(torch.int32), s2.view(torch.int32)) and torch.equal(t1, t2) and torch.equal(p1, p2)
+        assert torch.isfinite(lp1).all() and int(p1.max()) < nb  # a real step ran, not two empty buffers
+
+
 def test_batch_argument_errors_carry_messages(tiny_gen):
     z, cfg, sd, gen = tiny_gen
     lib = _lib.load()

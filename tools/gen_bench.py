@@ -6,9 +6,8 @@ max_length 512, length_penalty 0), and the decoder weight bytes per step against
 
 ``--states B [B ...]``: batched generation instead.  For each B, ``generate_many`` over B distinct 2048-byte sources (64
 beams, max_length 512, length_penalty 0) against the loop of B ``generate`` calls, in one process, the two alternating;
-the same pair with the batched GEMM in its interleaved-row form (``dec_batch_gemm=0``; the default is the per-state kernel
-at a larger grid) at the largest B; and the validation shape (greedy, largest B).  Times, ratio (loop / batched), per-step milliseconds and kernel
-launches per step, as one JSON line.
+and the validation shape (greedy, largest B).  Times, ratio (loop / batched), per-step milliseconds and kernel launches
+per step, as one JSON line.
 
     python tools/gen_bench.py --states 1 4 8 [--reps 2] [--out FILE]
 """
@@ -63,20 +62,14 @@ def _same(a, b):
 
 
 def states_bench(gen, cfg, states, reps, nb=64, max_len=512, src_bytes=2048):
-    from reprover_amd import _lib
-
-    lib = _lib.load()
     rng = np.random.default_rng(0)
     srcs = [np.concatenate([rng.integers(3, 259, size=src_bytes - 1), [1]]).astype(np.int32) for _ in range(max(states))]
     L = cfg["num_decoder_layers"]
     launches = 12 * L + 4  # per decode step: embed, 12 per layer, final norm, lm_head, log_softmax; + 2 for the selection
     res = {"metric": "gen_batch_bench", "beams": nb, "max_length": max_len, "length_penalty": 0.0,
            "config": f"byt5-small ({L} decoder layers), distinct sources of {src_bytes} bytes", "reps": reps, "states": {}}
-    gen.generate_many(srcs[:2], nb, 8, 0.0)  # warm-up: code objects of both paths and both GEMM forms
+    gen.generate_many(srcs[:2], nb, 8, 0.0)  # warm-up: code objects
     gen.generate(srcs[0], nb, 8, 0.0)
-    lib.rp_set_option(b"dec_batch_gemm", 0)
-    gen.generate_many(srcs[:2], nb, 8, 0.0)
-    lib.rp_set_option(b"dec_batch_gemm", 1)
 
     def pair(B, greedy=False):
         loop_ms, many_ms, steps_loop, steps_many, same = [], [], 0, 0, True
@@ -109,11 +102,6 @@ def states_bench(gen, cfg, states, reps, nb=64, max_len=512, src_bytes=2048):
     for B in states:
         res["states"][str(B)] = pair(B)
     B = max(states)
-    lib.rp_set_option(b"dec_batch_gemm", 0)
-    try:
-        res["interleaved_gemm_form"] = dict(pair(B), states=B)
-    finally:
-        lib.rp_set_option(b"dec_batch_gemm", 1)
     res["greedy_validation_shape"] = dict(pair(B, greedy=True), states=B)
     return res
 
