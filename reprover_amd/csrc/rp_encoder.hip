@@ -14,6 +14,8 @@
 //   ff   bf16 [Tp, F]        gelu_new(wi_0 h) * (wi_1 h)
 // Sequences are packed back to back (varlen): no padded token is ever computed except the
 // < 256 rows that round the last GEMM tile.  Device code: rp_encoder_kernels.h (shared with rp_train.hip).
+#include <limits.h>
+
 #include "rp_encoder_kernels.h"
 
 namespace rp {
@@ -23,9 +25,6 @@ thread_local std::string g_last_error;
 // ------------------------------------------------------------------------------------------
 // options
 // ------------------------------------------------------------------------------------------
-extern int g_scan_waves, g_scan_small_tiles;
-extern int g_scan_cfg, g_scan_impl, g_scan_filter_cfg, g_scan_sample_cfg, g_scan_stride, g_scan_no_epilogue, g_scan_impl_force_new,
-    g_scan_cap, g_train_dbg, g_train_wgrad_form;
 int g_gemm_group_m = 8;
 // Tile configuration per encoder GEMM (see launch_gemm()), measured at 65536 tokens (tools/gemm_bench.py,
 // profiles/).  20 / 26 = the software-pipelined 256 x 256 x 64 tile with 4 / 8 waves: the same main
@@ -34,17 +33,13 @@ int g_gemm_group_m = 8;
 // launches, three A/B pairs) and 2-5 % at 9-44 k tokens (tools/gemm_bench.py), so every big GEMM uses it now.  The K = H*64
 // attention-output projection is bound by the read-modify-write of x whatever the tiling: two small
 // blocks per CU overlap one block's epilogue with the other's main loop.
-int g_gemm_variant = 26;      // FFN-in (wi_0|wi_1 + gated GELU)
-int g_gemm_variant_qkv = 26;  // QKV
-int g_gemm_variant_wo = 26;   // FFN-out (+ residual)
-int g_gemm_variant_o = -1;    // attention output (+ residual); -1 = by pass size: two 128 x 128 blocks per CU, or - from 57 k
+constexpr int GEMM_VARIANT_BIG = 26, GEMM_VARIANT_O_BY_SIZE = -1;  // (gemm_variant_all = -1 restores these)
+int g_gemm_variant = GEMM_VARIANT_BIG;        // FFN-in (wi_0|wi_1 + gated GELU)
+int g_gemm_variant_qkv = GEMM_VARIANT_BIG;    // QKV
+int g_gemm_variant_wo = GEMM_VARIANT_BIG;     // FFN-out (+ residual)
+int g_gemm_variant_o = GEMM_VARIANT_O_BY_SIZE;  // attention output (+ residual); -1 = by pass size: two 128 x 128 blocks per CU, or - from 57 k
                               // tokens - the 8-wave 256 x 256 tile (A/B inside the 70 k-token step: 2.553 -> 2.470 ms per 12
                               // launches, three pairs; in isolation the two alternate below that size, tools/gemm_bench.py)
-int g_gemm_rs_lds = 0;      // 1: big tiles reduce the RMSNorm statistic in the consuming GEMM from slot rows DMA'd into LDS (RowScaleLds:
-                            // 24 launches per pass fewer, the same bits).  Round 5 A/B inside the 70 k-token step, two boxes: the
-                            // rowscale launches + a 4-byte global read per token in the epilogue are FASTER than the LDS form, by
-                            // 0.48 ms per step with every lane summing its tokens' slots (round 4's form: 92 LDS reads + adds per
-                            // lane and tile) and still by 0.12 ms with one thread per token summing once per tile (reduce())
 int g_gemm_small_pipe = 1;  // few-token passes: the 64 x 128 x 64 tile on the software-pipelined loop (variant 17) instead of the plain one (16)
 int g_gemm_helpers = 64;      // few-token launches: up to this many surplus workgroups prefetch the weight rows (0 = off)
 int g_gemm_persist = 9;   // persistent workgroups (gemm_tiles_persist) per projection: 1 QKV, 4 attention-out, 8 FFN-in, 16 FFN-out
@@ -52,8 +47,6 @@ int g_pool_chunk = 64;      // tokens per workgroup of the pooling pass (32 / 64
 int g_gemm_edge_layout = 1;  // big tiles: the last feature tile of 1152 / 1472 features on a wave grid over its valid features only
 int g_gemm_mixed = 20;  // full and half tiles in ONE launch (gemm_kernel_mixed) per projection: 1 QKV, 4 attention-out, 16 FFN-out
 int g_gemm_mixed_bwd = 1;  // the same for the training step's dgrad GEMMs whose tile count leaves a short last round (plan_mixed_loose)
-int g_gemm_tail_variant = 30;  // tile configuration of that tail round: 30 = 256 x 128 x 64 half tiles, 0 = 128 x 128 x 32 quarter tiles
-int g_gemm_tail_split = 1;  // big passes without a mixed launch: the last partial round of 256 x 256 tiles as one round of smaller tiles
 int g_debug_skip_ffn = 0;  // parity debugging: stop each block after the attention sub-layer
 int g_gemm_skinny = 1;
 int g_gemm_skinny_variant = 0;  // 15: few-token passes forced onto variant 15 (a test); 0: the measured table of pick_gemm_variant
@@ -102,49 +95,54 @@ using namespace rp;
 extern "C" int32_t rp_abi_version(void) { return 7; }
 extern "C" const char* rp_last_error(void) { return g_last_error.c_str(); }
 
+// One row per option: value in [lo, hi] (and, where `valid` is given, one of the values it names); BOOL stores value != 0.
+namespace {
+enum OptKind { OPT_PLAIN, OPT_BOOL };
+struct Option {
+  const char* name;
+  int* var;
+  int lo, hi;
+  OptKind kind;
+  bool (*valid)(int);
+};
+constexpr int ANY_LO = INT_MIN, ANY_HI = INT_MAX;
+const Option g_options[] = {
+    {"gemm_group_m", &g_gemm_group_m, 1, 64, OPT_PLAIN, nullptr},
+    {"gemm_variant", &g_gemm_variant, ANY_LO, ANY_HI, OPT_PLAIN, gemm_variant_known},
+    {"gemm_variant_qkv", &g_gemm_variant_qkv, ANY_LO, ANY_HI, OPT_PLAIN, gemm_variant_known},
+    {"gemm_variant_wo", &g_gemm_variant_wo, ANY_LO, ANY_HI, OPT_PLAIN, gemm_variant_known},
+    {"gemm_variant_o", &g_gemm_variant_o, ANY_LO, ANY_HI, OPT_PLAIN, gemm_variant_known},
+    {"debug_skip_ffn", &g_debug_skip_ffn, ANY_LO, ANY_HI, OPT_BOOL, nullptr},
+    {"gemm_skinny_variant", &g_gemm_skinny_variant, 0, 15, OPT_PLAIN, [](int v) { return v == 0 || v == 15; }},
+    {"gemm_small_pipe", &g_gemm_small_pipe, ANY_LO, ANY_HI, OPT_BOOL, nullptr},
+    {"pool_chunk", &g_pool_chunk, 32, 128, OPT_PLAIN, [](int v) { return v == 32 || v == 64 || v == 128; }},
+    {"gemm_persist", &g_gemm_persist, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+    {"gemm_edge_layout", &g_gemm_edge_layout, ANY_LO, ANY_HI, OPT_BOOL, nullptr},
+    {"gemm_mixed", &g_gemm_mixed, 0, 31, OPT_PLAIN, nullptr},  // bit mask
+    {"gemm_mixed_bwd", &g_gemm_mixed_bwd, ANY_LO, ANY_HI, OPT_BOOL, nullptr},
+    {"gemm_skinny", &g_gemm_skinny, ANY_LO, ANY_HI, OPT_BOOL, nullptr},
+    {"scan_cfg", &g_scan_cfg, 0, 1, OPT_PLAIN, nullptr},
+#ifdef RP_EXPERIMENTS  // knobs of measured-and-rejected alternatives and timing probes: probe builds only
+    {"scan_filter_cfg", &g_scan_filter_cfg, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+    {"scan_sample_cfg", &g_scan_sample_cfg, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+    {"scan_waves", &g_scan_waves, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+    {"scan_stride", &g_scan_stride, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+    {"train_dbg", &g_train_dbg, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+    {"scan_no_epilogue", &g_scan_no_epilogue, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+#endif
+    {"train_wgrad_form", &g_train_wgrad_form, 0, 3, OPT_PLAIN, nullptr},  // tests: bit mask of the weight-gradient launch forms (rp_train.hip)
+    {"scan_cap", &g_scan_cap, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},        // tests: forces the overflow -> dense contract
+    {"scan_force_new", &g_scan_impl_force_new, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+    {"scan_small_tiles", &g_scan_small_tiles, 0, 1, OPT_PLAIN, nullptr},  // tests: 0 = at most 32 queries on the 128-query tiles (must be the same bits)
+    {"scan_impl", &g_scan_impl, 0, 1, OPT_PLAIN, nullptr},
+};
+}  // namespace
+
 extern "C" RpStatus rp_set_option(const char* name, int32_t value) {
-  if (!strcmp(name, "gemm_group_m")) {
-    RP_REQUIRE(value >= 1 && value <= 64, "gemm_group_m out of range");
-    g_gemm_group_m = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_variant")) {
-    RP_REQUIRE(value >= 0 && value <= 30, "gemm_variant out of range");
-    g_gemm_variant = value;
-    return RP_OK;
-  }
   if (!strcmp(name, "gemm_variant_all")) {  // benches/tests: one configuration for every GEMM; -1 = defaults
-    RP_REQUIRE(value >= -1 && value <= 30, "gemm_variant_all out of range");
-    if (value < 0) {
-      g_gemm_variant = g_gemm_variant_qkv = g_gemm_variant_wo = 26;
-      g_gemm_variant_o = -1;
-    } else {
-      g_gemm_variant = g_gemm_variant_qkv = g_gemm_variant_wo = g_gemm_variant_o = value;
-    }
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_variant_qkv")) {
-    RP_REQUIRE(value >= 0 && value <= 30, "gemm_variant_qkv out of range");
-    g_gemm_variant_qkv = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_variant_wo")) {
-    RP_REQUIRE(value >= 0 && value <= 30, "gemm_variant_wo out of range");
-    g_gemm_variant_wo = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_variant_o")) {
-    RP_REQUIRE(value >= 0 && value <= 30, "gemm_variant_o out of range");
-    g_gemm_variant_o = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "debug_skip_ffn")) {
-    g_debug_skip_ffn = value != 0;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_skinny_variant")) {
-    RP_REQUIRE(value == 0 || value == 15, "gemm_skinny_variant must be 0 or 15");
-    g_gemm_skinny_variant = value;
+    RP_REQUIRE(value == -1 || gemm_variant_known(value), "gemm_variant_all: tile configuration %d is not in this build", value);
+    g_gemm_variant = g_gemm_variant_qkv = g_gemm_variant_wo = value < 0 ? GEMM_VARIANT_BIG : value;
+    g_gemm_variant_o = value < 0 ? GEMM_VARIANT_O_BY_SIZE : value;
     return RP_OK;
   }
   if (!strcmp(name, "gemm_helpers")) {
@@ -152,55 +150,7 @@ extern "C" RpStatus rp_set_option(const char* name, int32_t value) {
     g_gemm_helpers = value & ~7;
     return RP_OK;
   }
-  if (!strcmp(name, "gemm_small_pipe")) {
-    g_gemm_small_pipe = value != 0;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_rs_lds")) {
-    g_gemm_rs_lds = value != 0;
-    return RP_OK;
-  }
-  if (!strcmp(name, "pool_chunk")) {
-    RP_REQUIRE(value == 32 || value == 64 || value == 128, "pool_chunk must be 32, 64 or 128");
-    g_pool_chunk = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_persist")) {
-    g_gemm_persist = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_edge_layout")) {
-    g_gemm_edge_layout = value != 0;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_mixed")) {
-    RP_REQUIRE(value >= 0 && value <= 31, "gemm_mixed: bit mask 0..31");
-    g_gemm_mixed = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_mixed_bwd")) {
-    g_gemm_mixed_bwd = value != 0;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_tail_variant")) {
-    RP_REQUIRE(value == 0 || value == 30, "gemm_tail_variant: 0 or 30");
-    g_gemm_tail_variant = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_tail_split")) {
-    g_gemm_tail_split = value != 0;
-    return RP_OK;
-  }
-  if (!strcmp(name, "gemm_skinny")) {
-    g_gemm_skinny = value != 0;
-    return RP_OK;
-  }
-  if (!strcmp(name, "scan_cfg")) {
-    RP_REQUIRE(value >= 0 && value <= 1, "scan_cfg out of range");
-    g_scan_cfg = value;
-    return RP_OK;
-  }
-#ifdef RP_EXPERIMENTS  // knobs of measured-and-rejected alternatives and timing probes: probe builds only
+#ifdef RP_EXPERIMENTS
   if (!strncmp(name, "gemm_stagger_us_", 16)) {  // gemm_stagger_us_{qkv,o,wi,wo}
     const char* which = name + 16;
     const int cls = !strcmp(which, "qkv") ? RP_K_GEMM_QKV : !strcmp(which, "o") ? RP_K_GEMM_O
@@ -209,28 +159,12 @@ extern "C" RpStatus rp_set_option(const char* name, int32_t value) {
     g_gemm_stagger_us[cls] = value;
     return RP_OK;
   }
-  if (!strcmp(name, "scan_filter_cfg")) { g_scan_filter_cfg = value; return RP_OK; }
-  if (!strcmp(name, "scan_sample_cfg")) { g_scan_sample_cfg = value; return RP_OK; }
-  if (!strcmp(name, "scan_waves")) { g_scan_waves = value; return RP_OK; }
-  if (!strcmp(name, "scan_stride")) { g_scan_stride = value; return RP_OK; }
-  if (!strcmp(name, "train_dbg")) { g_train_dbg = value; return RP_OK; }
-  if (!strcmp(name, "scan_no_epilogue")) { g_scan_no_epilogue = value; return RP_OK; }
 #endif
-  if (!strcmp(name, "train_wgrad_form")) {  // tests: the weight-gradient launch forms of the training step (rp_train.hip)
-    RP_REQUIRE(value >= 0 && value <= 3, "train_wgrad_form: bit mask 0..3");
-    g_train_wgrad_form = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "scan_cap")) { g_scan_cap = value; return RP_OK; }  // tests: forces the overflow -> dense contract
-  if (!strcmp(name, "scan_force_new")) { g_scan_impl_force_new = value; return RP_OK; }
-  if (!strcmp(name, "scan_small_tiles")) {  // tests: 0 = at most 32 queries on the 128-query tiles (must be the same bits)
-    RP_REQUIRE(value >= 0 && value <= 1, "scan_small_tiles out of range");
-    g_scan_small_tiles = value;
-    return RP_OK;
-  }
-  if (!strcmp(name, "scan_impl")) {
-    RP_REQUIRE(value >= 0 && value <= 1, "scan_impl out of range");
-    g_scan_impl = value;
+  for (const Option& o : g_options) {
+    if (strcmp(name, o.name)) continue;
+    RP_REQUIRE(value >= o.lo && value <= o.hi, "%s out of range", o.name);
+    RP_REQUIRE(!o.valid || o.valid(value), "%s: %d is not one of its values in this build", o.name, value);
+    *o.var = o.kind == OPT_BOOL ? value != 0 : value;
     return RP_OK;
   }
   return fail(RP_E_INVALID, "unknown option %s", name);
@@ -438,50 +372,11 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
 
   const int np = (D + 63) / 64;
   // When both row-scaled projections run small tiles (passes of up to ~1000 tokens) their epilogues reduce the
-  // statistic themselves (RowScaleFromSlots): two launches fewer per layer.
+  // statistic themselves (RowScaleFromSlots): two launches fewer per layer.  Every other pass launches rowscale_kernel.
   const bool fused_rs = small_variant(pick_gemm_variant(RP_K_GEMM_QKV, Tp, 3 * inner, D, tv)) &&
                         small_variant(pick_gemm_variant(RP_K_GEMM_WI, Tp, 2 * F, D, tv));
   const RowScale rs{w.rs};
   const RowScaleFromSlots rs_slots{w.ssp, np, Tp, 1.f / (float)D, c.layer_norm_eps};
-  const RowScaleLds rs_lds{w.ssp, np, Tp, 1.f / (float)D, c.layer_norm_eps};
-  // big tiles: each of the two row-scaled projections reduces the statistic itself from LDS (no rowscale launch)
-  const bool lds_qkv = !fused_rs && g_gemm_rs_lds && np <= 32 && big_variant(pick_gemm_variant(RP_K_GEMM_QKV, Tp, 3 * inner, D, tv));
-  const bool lds_wi = !fused_rs && g_gemm_rs_lds && np <= 32 && big_variant(pick_gemm_variant(RP_K_GEMM_WI, Tp, 2 * F, D, tv));
-  // Tail of the FFN-out launch.  1644 tiles of 256 x 256 on 256 CUs are 6.42 rounds: the seventh runs 108 tiles
-  // while 148 CUs idle (70 k tokens).  Since round 5 the projection runs as a MIXED launch (gemm_kernel_mixed, option
-  // gemm_mixed: the token rows beyond the whole rounds are half tiles inside the same launch) and main_rows() returns Tp.
-  // With that option off this is rounds 3 - 4's form: the token rows that make whole rounds go to the big tiles in
-  // one launch, the rest (18 token tiles here) runs as ONE more round - of 256 x 128 half tiles (gemm_tail_variant 30,
-  // one per CU) or 128 x 128 quarter tiles (0, two per CU).  Same K-ascending chains per output element: not a bit
-  // changes.  Measured 9.28 -> 9.04 ms per step in round 3; the same split of the QKV projection (5.35 rounds) gained
-  // nothing (3.11 -> 3.14 ms: its short K loop leaves the tail round cheap already).
-  const int n_cus = device_cu_count();
-  auto main_rows = [&](int prof_class, int n_features, int K) -> int {
-    if (!g_gemm_tail_split || t_dev) return Tp;  // (token count known on the device only: one launch)
-    const int v = pick_gemm_variant(prof_class, Tp, n_features, K, tv);
-    if (v != 20 && v != 26) return Tp;
-    const int tiles_f = (n_features + 255) / 256, tiles_t = Tp / 256;
-    // The mixed launch carries its own half tiles - when launch_gemm_cfg actually takes it: the 8-wave 256 x 256
-    // configuration (26; the 4-wave form 20 has no edge layouts), at least two k-tiles, and a plan (plan_mixed, the SAME
-    // function and CU count launch_gemm_cfg uses).  Declined there, the tail split below still applies.
-    if (((g_gemm_mixed >> (prof_class - RP_K_GEMM_QKV)) & 1) && v == 26 && K >= 128 && plan_mixed(tiles_f, tiles_t, n_cus).full_rows)
-      return Tp;
-    int g = tiles_f, b = n_cus;  // gcd
-    while (b) {
-      const int t = g % b;
-      g = b;
-      b = t;
-    }
-    const int unit = n_cus / g;  // token tiles per whole number of rounds
-    const int t1 = tiles_t / unit * unit, rest = tiles_t - t1;
-    if (t1 == 0 || rest == 0) return Tp;
-    if (rest * tiles_f > (7 * n_cus) / 10) return Tp;                      // the last round is nearly full anyway
-    if (g_gemm_tail_variant == 30 ? rest * 2 * tiles_f > n_cus             // the half tiles (one per CU) ...
-                                  : rest * 2 * ((n_features + 127) / 128) > 2 * n_cus)  // ... the quarter tiles (two per CU)
-      return Tp;                                                           // would not fit one round
-    return t1 * 256;
-  };
-  const int wo_main = main_rows(RP_K_GEMM_WO, D, F);
   auto launch_rowscale = [&](bool needed_anyway = false) {
     if (fused_rs && !needed_anyway) return;
     ProfScope ps(stream, RP_K_RMSNORM);
@@ -489,8 +384,8 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
                        1.f / (float)D, c.layer_norm_eps);
   };
   // the first QKV projection's RMSNorm factor straight from the embedding kernel (the table carries every row's sum of
-  // squares) unless a consumer reads the statistic slots itself (few-token passes, the LDS form)
-  const bool embed_rs = !fused_rs && !lds_qkv;
+  // squares) unless the consumer reads the statistic slots itself (few-token passes)
+  const bool embed_rs = !fused_rs;
   {
     ProfScope ps(stream, RP_K_EMBED);
     // four token rows per wave, all their loads in flight before the first store (round 6, exp10: 66 -> 57 us at 70 k tokens;
@@ -519,13 +414,11 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
   for (int i = 0; i < c.num_layers; ++i) {
     const LayerPacked& L = e->layers[i];
     // attention sub-layer: qkv = rs * (xb Wqkv'^T)  ->  attention  ->  x += att Wo^T  (+ xb, ssp refreshed)
-    if (!lds_qkv && !(i == 0 && embed_rs)) launch_rowscale();
+    if (!(i == 0 && embed_rs)) launch_rowscale();
     st = fused_rs ? launch_gemm<true>(w.xb, D, Tp, L.wqkv, D, 3 * inner, D,
                                       EpiStoreBf16Slots{w.qkv, 3 * inner, 3 * inner, rs_slots}, stream, RP_K_GEMM_QKV, tv, t_dev)
-         : lds_qkv ? launch_gemm_big(w.xb, D, Tp, L.wqkv, D, 3 * inner, D,
-                                     EpiStoreBf16Lds{{w.qkv, 3 * inner, 3 * inner, rs_lds}}, stream, RP_K_GEMM_QKV, tv, t_dev)
-                   : launch_gemm(w.xb, D, Tp, L.wqkv, D, 3 * inner, D, EpiStoreBf16{w.qkv, 3 * inner, 3 * inner, rs}, stream,
-                                 RP_K_GEMM_QKV, tv, t_dev);
+                  : launch_gemm(w.xb, D, Tp, L.wqkv, D, 3 * inner, D, EpiStoreBf16{w.qkv, 3 * inner, 3 * inner, rs}, stream,
+                                RP_K_GEMM_QKV, tv, t_dev);
     if (st) return st;
     {
       ProfScope ps(stream, RP_K_ATTENTION);
@@ -536,27 +429,16 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
                           RP_K_GEMM_O, tv, t_dev)))
       return st;
     if (g_debug_skip_ffn) continue;
-    if (!lds_wi) launch_rowscale();
+    launch_rowscale();
     // feed-forward sub-layer: ff = gelu(rs * g) * (rs * u)  ->  x += ff Wo2^T  (+ xb, ssp refreshed)
     st = fused_rs ? launch_gemm<true>(w.xb, D, Tp, L.wi, D, 2 * F, D, EpiGegluBf16Slots{w.ff, F, 2 * F, rs_slots}, stream,
                                       RP_K_GEMM_WI, tv, t_dev)
-         : lds_wi ? launch_gemm_big(w.xb, D, Tp, L.wi, D, 2 * F, D, EpiGegluBf16Lds{{w.ff, F, 2 * F, rs_lds}}, stream,
-                                    RP_K_GEMM_WI, tv, t_dev)
                   : launch_gemm(w.xb, D, Tp, L.wi, D, 2 * F, D, EpiGegluBf16{w.ff, F, 2 * F, rs}, stream, RP_K_GEMM_WI, tv,
                                 t_dev);
     if (st) return st;
-    if (wo_main < Tp) {
-      const int r1 = wo_main;
-      st = launch_gemm(w.ff, F, r1, L.wo2, F, D, F, EpiResid8{w.xb, w.xlo, D, D, w.ssp, np, Tp}, stream, RP_K_GEMM_WO);
-      if (st) return st;
-      st = launch_gemm(w.ff + (size_t)r1 * F, F, Tp - r1, L.wo2, F, D, F,
-                       EpiResid8{w.xb + (size_t)r1 * D, (bf16_t*)((uint8_t*)w.xlo + (size_t)r1 * D), D, D, w.ssp + r1, np, Tp}, stream,
-                       RP_K_GEMM_WO, std::max(1, tv - r1), nullptr, g_gemm_tail_variant);
-    } else {
-      st = launch_gemm(w.ff, F, Tp, L.wo2, F, D, F, EpiResid8{w.xb, w.xlo, D, D, w.ssp, np, Tp}, stream, RP_K_GEMM_WO, tv,
-                       t_dev);
-    }
-    if (st) return st;
+    if ((st = launch_gemm(w.ff, F, Tp, L.wo2, F, D, F, EpiResid8{w.xb, w.xlo, D, D, w.ssp, np, Tp}, stream, RP_K_GEMM_WO, tv,
+                          t_dev)))
+      return st;
   }
   launch_rowscale(true);  // final RMSNorm statistic (the pooling pass reads rs per token row)
   if (hidden) {  // rp_encode_hidden: last_hidden_state rows instead of the pool

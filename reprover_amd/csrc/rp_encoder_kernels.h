@@ -12,9 +12,12 @@
 
 namespace rp {
 
-// tuning knobs (defined in rp_encoder.hip, set through rp_set_option)
-extern int g_gemm_group_m, g_gemm_variant, g_gemm_variant_qkv, g_gemm_variant_wo, g_gemm_variant_o, g_gemm_tail_split,
-    g_debug_skip_ffn, g_gemm_skinny, g_gemm_skinny_variant, g_gemm_rs_lds, g_gemm_small_pipe, g_gemm_helpers, g_gemm_persist, g_pool_chunk, g_gemm_edge_layout, g_gemm_tail_variant, g_gemm_mixed, g_gemm_mixed_bwd;
+// tuning knobs, set through rp_set_option (rp_encoder.hip); g_scan_* are defined in rp_retrieval.hip, g_train_* in rp_train.hip,
+// the others in rp_encoder.hip
+extern int g_gemm_group_m, g_gemm_variant, g_gemm_variant_qkv, g_gemm_variant_wo, g_gemm_variant_o, g_debug_skip_ffn, g_gemm_skinny,
+    g_gemm_skinny_variant, g_gemm_small_pipe, g_gemm_helpers, g_gemm_persist, g_pool_chunk, g_gemm_edge_layout, g_gemm_mixed,
+    g_gemm_mixed_bwd, g_scan_waves, g_scan_small_tiles, g_scan_cfg, g_scan_impl, g_scan_filter_cfg, g_scan_sample_cfg, g_scan_stride,
+    g_scan_no_epilogue, g_scan_impl_force_new, g_scan_cap, g_train_dbg, g_train_wgrad_form;
 extern int g_gemm_stagger_us[RP_K_COUNT];
 
 // ------------------------------------------------------------------------------------------
@@ -344,52 +347,8 @@ struct RowScaleFromSlots {
   }
 };
 
-// The big tiles (256 tokens per workgroup, gemm_tile_pipe) reduce the statistic in the consuming GEMM as well, without a
-// register cost in the main loop: the tile's slot rows - np x 256 floats, one 1-KiB LDS-DMA piece per slot - ride into
-// LDS behind the operand ring before the first operand DMA (the epilogue's prologue hook: in-order vmcnt has them
-// landed long before the epilogue), and the epilogue sums a token's np slots from LDS in index order: the bits
-// rowscale_kernel produces, 24 launches per pass fewer (6.7 us each + their boundaries at 70 k tokens).
-struct RowScaleLds {
-  static constexpr int EXTRA_LDS = 32 * 1024;  // np <= 32 slot rows of 256 floats
-  const float* ssp;  // [np, ld] slot-major partial sums of squares
-  int np, ld;
-  float inv_d, eps;
-  float* lds = nullptr;  // set by prologue()
-  int n0 = 0;
-  __device__ __forceinline__ void prologue(char* extra, int wave, int lane, int tok0) {
-    lds = reinterpret_cast<float*>(extra);
-    n0 = tok0;
-    const int nw = (int)blockDim.x >> 6;
-    for (int p = wave; p < np; p += nw)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(ssp + (size_t)p * ld + tok0 + lane * 4), (lds_ptr_t)(extra + p * 1024), 16,
-                                       0, 0);
-  }
-  // After the main loop (the rows have landed, every wave is past the barrier): ONE thread per token sums its np slots in
-  // index order - rowscale_kernel's chain, whose zero padding beyond np adds exactly nothing - and leaves rs in row 0.
-  // (Round 5: until then every lane summed the slots of its own four tokens in the epilogue, 8 x redundantly across the
-  // workgroup: 92 LDS reads + adds per lane, 0.5 ms per step.)  The caller puts a barrier behind it.
-  __device__ __forceinline__ void reduce(int tid) {
-    if (tid < 256) {
-      float* p = lds + tid;
-      float s = 0.f;
-#pragma unroll 4
-      for (int i = 0; i < np; ++i) s += p[i * 256];
-      p[0] = rsqrtf(s * inv_d + eps);
-    }
-  }
-  __device__ __forceinline__ float get(int token) const { return lds[token - n0]; }
-};
-// an epilogue whose row scale has a prologue of its own exposes it to gemm_tile_pipe
-template <class Base>
-struct WithRsPrologue : Base {
-  static constexpr int EXTRA_LDS = decltype(Base::rs)::EXTRA_LDS;
-  __device__ __forceinline__ void prologue(char* extra, int wave, int lane, int n0) { this->rs.prologue(extra, wave, lane, n0); }
-  __device__ __forceinline__ void reduce(int tid) { this->rs.reduce(tid); }
-};
-template <class E, class = void>
-struct epi_extra_lds : std::integral_constant<int, 0> {};
-template <class E>
-struct epi_extra_lds<E, std::void_t<decltype(E::EXTRA_LDS)>> : std::integral_constant<int, E::EXTRA_LDS> {};
+// (The big tiles reduced the statistic in the consuming GEMM too, from slot rows DMA'd into LDS behind the ring, until that form
+// lost its A/B against the rowscale launches: docs/HISTORY.md.)
 
 // rs[token] = rsqrt(sum_p ssp[p][token] / D + eps), slots summed in index order
 static __global__ __launch_bounds__(64) void rowscale_kernel(const float* __restrict__ ssp, float* __restrict__ rs, int rows,
@@ -671,8 +630,6 @@ typedef EpiStoreBf16T<RowScale> EpiStoreBf16;
 typedef EpiGegluBf16T<RowScale> EpiGegluBf16;
 typedef EpiStoreBf16T<RowScaleFromSlots> EpiStoreBf16Slots;
 typedef EpiGegluBf16T<RowScaleFromSlots> EpiGegluBf16Slots;
-typedef WithRsPrologue<EpiStoreBf16T<RowScaleLds>> EpiStoreBf16Lds;
-typedef WithRsPrologue<EpiGegluBf16T<RowScaleLds>> EpiGegluBf16Lds;
 
 // Weight prefetch by the CUs a few-token launch leaves idle.  A pass of one proof state runs 18 - 112 workgroups, each
 // streaming its 64 weight rows from HBM (a single-state retrieve() walks all 434 MB of weights: nothing is cached from
@@ -901,7 +858,7 @@ template <class E>
 struct epi_loose_mixed<E, std::void_t<decltype(E::loose_mixed)>> : std::true_type {};
 template <class C, class Epi>
 constexpr bool mixed_capable() {
-  return C::PIPE != 0 && C::FP8 == 0 && C::BM == 256 && C::BN == 256 && C::NWAVES == 8 && C::OCC == 0 && epi_extra_lds<Epi>::value == 0;
+  return C::PIPE != 0 && C::FP8 == 0 && C::BM == 256 && C::BN == 256 && C::NWAVES == 8 && C::OCC == 0;
 }
 
 // One workgroup per CU walking its share of the tiles (gemm_tiles_persist).  Workgroup b runs on XCD b % 8 (observed, speed
@@ -932,14 +889,6 @@ __global__ __launch_bounds__(C::THREADS) void gemm_kernel_persist(GemmOperand A,
   // full tiles: the epilogue's preferred wave grid when it names one (main_layout), else the configuration's own
   gemm_tiles_persist<C, edge_layouts<C, Epi>(), typename epi_main_layout<Epi, C>::type>(A, W, K, next_tile, epi, smem, edge_on != 0);
 }
-// an epilogue with metadata behind the ring (RowScaleLds) has 24 KiB for it in the persistent layout
-template <class Epi>
-static bool epi_fits_persist(const Epi& epi) {
-  if constexpr (epi_extra_lds<Epi>::value != 0)
-    return epi.rs.np * 1024 <= PERSIST_LDS_BYTES - PERSIST_META_OFF;
-  else
-    return true;
-}
 template <class C>
 constexpr bool persist_capable() {
   return C::PIPE != 0 && C::FP8 == 0 && C::KTAIL == 0 && C::NSTAGE == 2 && C::STAGE_BYTES == 64 * 1024 && C::NWAVES == 8 && C::OCC == 0;
@@ -960,11 +909,8 @@ static RpStatus launch_gemm_cfg(GemmOperand w, GemmOperand a, int K, Epi epi, hi
                                 int prof_class, int tokens_valid, const int32_t* t_dev) {
   auto kern = pick_gemm_kernel<C, Epi>();
   static_assert(C::OCC == 0 || (C::OCC == 2 && C::THREADS == 256), "OCC: two 4-wave workgroups per CU");
-  constexpr int LDS = (epi_extra_lds<Epi>::value ? C::RING_BYTES : C::LDS_BYTES) + epi_extra_lds<Epi>::value;
-  static_assert(epi_extra_lds<Epi>::value == 0 || (C::PIPE != 0 && C::RING_BYTES >= C::NWAVES * EPI_STAGE_BYTES),
-                "metadata behind the ring: pipelined tiles only");
   static LdsAttrOnce attr;
-  RP_HIP(attr.ensure((const void*)kern, LDS));
+  RP_HIP(attr.ensure((const void*)kern, C::LDS_BYTES));
   RP_REQUIRE(K % C::BK == 0 && a.rows % C::BN == 0, "gemm: K=%d must be a multiple of %d, M=%d of %d", K, C::BK,
              a.rows, C::BN);
   const int rows_needed = (tokens_valid > 0 && tokens_valid < a.rows) ? tokens_valid : a.rows;
@@ -1008,7 +954,7 @@ static RpStatus launch_gemm_cfg(GemmOperand w, GemmOperand a, int K, Epi epi, hi
     const int slots = n_cus & ~7;
     // (K >= two k-tiles: the persistent loop requests ring slot 1 unconditionally)
     if (prof_class >= RP_K_GEMM_QKV && prof_class <= RP_K_GEMM_WO && ((g_gemm_persist >> (prof_class - RP_K_GEMM_QKV)) & 1) &&
-        n_helpers == 0 && n_grid > slots && K >= 2 * C::BK && epi_fits_persist(epi)) {
+        n_helpers == 0 && n_grid > slots && K >= 2 * C::BK) {
       auto pk = gemm_kernel_persist<C, Epi>;
       static LdsAttrOnce pattr;
       RP_HIP(pattr.ensure((const void*)pk, PERSIST_LDS_BYTES));
@@ -1018,7 +964,7 @@ static RpStatus launch_gemm_cfg(GemmOperand w, GemmOperand a, int K, Epi epi, hi
       return RP_OK;
     }
   }
-  hipLaunchKernelGGL(kern, dim3(n_grid + n_helpers), dim3(C::THREADS), LDS, stream, w, a, K, tiles_f, tiles_t, group,
+  hipLaunchKernelGGL(kern, dim3(n_grid + n_helpers), dim3(C::THREADS), C::LDS_BYTES, stream, w, a, K, tiles_f, tiles_t, group,
                      stagger_ticks, t_dev, epi, n_helpers);
   RP_CHECK_LAUNCH();
   return RP_OK;
@@ -1063,18 +1009,27 @@ inline bool small_variant(int v) { return v == 0 || (v >= 15 && v <= 17); }
 //   26       pipelined 256 x 256 x 64, 8 waves          (the encoder's big GEMMs; the 4-wave form 20 - 128 x 128 per wave,
 //            accumulators in AGPRs - lost the in-step A/B of round 3 and left the sources in round 6, as did 12 = 64 x 256 x 32)
 //   27 / 28  (RP_EXPERIMENTS builds) pipelined 256 x 128 x 32 / 128 x 256 x 32 (features x tokens), 3 stages, 4 waves, TWO workgroups per CU
-//   30       pipelined 256 x 128 x 64, 8 waves          (the FFN-out projection's tail round: half tiles, one per CU)
+//   30       pipelined 256 x 128 x 64, 8 waves          (the half tile of gemm_kernel_mixed; on its own through the gemm_variant* options)
 //   9        plain 256 x 256 x 32, 3 stages             (K % 64 != 0)
 //   0        plain 128 x 128 x 32, 3 stages, 2 blocks/CU (attention-out; token counts not a multiple of 256)
 //   17       64 x 128 x 64, 4 stages, pipelined loop    (up to ~1024 tokens: single-state queries)
 //   16 / 15  the same on the plain loop / x 32, 7 stages (16: kept selectable; 15: K % 64 != 0)
 // SMALL_ONLY: the epilogue type exists for the small configurations only (pick_gemm_variant said so).
+// The ids with a `case` below in this build - what the gemm_variant* options accept and launch_gemm() runs:
+inline bool gemm_variant_known(int v) {
+#ifdef RP_EXPERIMENTS
+  if (v >= 27 && v <= 29) return true;
+#endif
+  return v == 0 || v == 9 || (v >= 15 && v <= 17) || v == 26 || v == 30;
+}
 template <bool SMALL_ONLY = false, class Epi>
 static RpStatus launch_gemm(const bf16_t* A, int lda, int M, const bf16_t* W, int ldw, int n_rows_w,
                             int K, Epi epi, hipStream_t stream, int prof_class, int tokens_valid = 0,
                             const int32_t* t_dev = nullptr, int force_variant = -1) {
   GemmOperand a{A, lda, M}, w{W, ldw, n_rows_w};
+  // (force_variant: the training step's dgrad GEMMs choose their tile themselves, rp_train.hip bwd_variant)
   const int v = force_variant >= 0 ? force_variant : pick_gemm_variant(prof_class, M, n_rows_w, K, tokens_valid);
+  RP_REQUIRE(gemm_variant_known(v), "tile configuration %d is not in this build", v);
   if constexpr (!SMALL_ONLY) {
     switch (v) {
       case 26: return launch_gemm_cfg<GemmCfg<256, 256, 64, 4, 2, 2, 1>>(w, a, K, epi, stream, prof_class, tokens_valid, t_dev);
@@ -1095,19 +1050,8 @@ static RpStatus launch_gemm(const bf16_t* A, int lda, int M, const bf16_t* W, in
     case 15: return launch_gemm_cfg<GemmCfg<64, 128, 32, 1, 4, 7>>(w, a, K, epi, stream, prof_class, tokens_valid, t_dev);
     case 16: return launch_gemm_cfg<GemmCfg<64, 128, 64, 1, 4, 4>>(w, a, K, epi, stream, prof_class, tokens_valid, t_dev);
     case 17: return launch_gemm_cfg<GemmCfg<64, 128, 64, 1, 4, 4, 1>>(w, a, K, epi, stream, prof_class, tokens_valid, t_dev);
-    default: return launch_gemm_cfg<GemmCfg<128, 128, 32, 2, 2, 3>>(w, a, K, epi, stream, prof_class, tokens_valid, t_dev);
+    default: return launch_gemm_cfg<GemmCfg<128, 128, 32, 2, 2, 3>>(w, a, K, epi, stream, prof_class, tokens_valid, t_dev);  // 0
   }
-}
-
-inline bool big_variant(int v) { return v == 26; }
-// epilogues that exist for the pipelined 256 x 256 tiles only (metadata behind the ring)
-template <class Epi>
-static RpStatus launch_gemm_big(const bf16_t* A, int lda, int M, const bf16_t* W, int ldw, int n_rows_w, int K, Epi epi,
-                                hipStream_t stream, int prof_class, int tokens_valid, const int32_t* t_dev) {
-  GemmOperand a{A, lda, M}, w{W, ldw, n_rows_w};
-  const int v = pick_gemm_variant(prof_class, M, n_rows_w, K, tokens_valid);
-  RP_REQUIRE(big_variant(v), "tile configuration %d has no LDS row-scale form", v);
-  return launch_gemm_cfg<GemmCfg<256, 256, 64, 4, 2, 2, 1>>(w, a, K, epi, stream, prof_class, tokens_valid, t_dev);
 }
 
 // ------------------------------------------------------------------------------------------

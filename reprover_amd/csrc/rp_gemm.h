@@ -121,8 +121,7 @@ struct has_prologue : std::false_type {};
 template <class E>
 struct has_prologue<E, std::void_t<decltype(&E::prologue)>> : std::true_type {};
 
-// ... and `void reduce(int tid)`: called once the main loop is over (the metadata has landed and every wave is past the
-// barrier), followed by a barrier - turns the metadata into what the epilogue reads.
+// (The similarity scan's second-generation filter brings its bounds and scales in this way, rp_retrieval.hip EpiSimFilter.)
 // An epilogue may ask for `template <int FN> void preload(int n_base, int lane)` (static constexpr bool preload_hook = true):
 // the persistent tile loop calls it in front of a tile's LAST k-tile - nothing of the wave's is in flight there - so that
 // per-token operands of the epilogue (the RMSNorm factors) are in registers when the epilogue starts instead of being
@@ -132,10 +131,6 @@ template <class E, class = void>
 struct has_preload : std::false_type {};
 template <class E>
 struct has_preload<E, std::enable_if_t<E::preload_hook>> : std::true_type {};
-template <class E, class = void>
-struct has_reduce : std::false_type {};
-template <class E>
-struct has_reduce<E, std::void_t<decltype(&E::reduce)>> : std::true_type {};
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
@@ -542,10 +537,6 @@ __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOp
   tile_body(kt, I0(), I0());  // (a half tile skips its upper k-steps inside the body: no second set of MFMA code)
   __syncthreads();
   RP_TS(2);
-  if constexpr (has_reduce<Epilogue>::value) {  // per-tile metadata -> what the epilogue reads (one pass, then visible to all)
-    epi.reduce(tid);
-    __syncthreads();
-  }
 
   epi.template run<FM, FN>(acc, tile_m * C::BM + wave_row * (FM * 32), tile_n * C::BN + wave_col * (FN * 32), lane,
                            smem + wave * EPI_STAGE_BYTES);
@@ -561,28 +552,28 @@ __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOp
 //   * the first k-tile of tile t+1 is requested BEFORE the epilogue of tile t and lands under it.  LDS (all 160 KiB):
 //       [0, 64 K)      ring slot 0 - free once the main loop is over: tile t+1's first k-tile goes there
 //       [64 K, 136 K)  the epilogue's per-wave staging areas (8 x 9 KiB; over ring slot 1, which is dead by then)
-//       [136 K, 160 K) per-tile metadata of an epilogue with a prologue() hook (<= 24 slot rows of 1 KiB)
-//     After the epilogue one raw barrier frees the staging area; the metadata and the second k-tile of tile t+1 are
-//     requested and the main loop starts on a k-tile that has already landed.
-// The queue of a wave at that point, oldest first: [slot 0 of t+1] [epilogue stores of t] [metadata] [slot 1 of t+1];
+//       [136 K, 160 K) unused (no epilogue that runs here has a prologue() hook); the launch still asks for the whole CU's LDS
+//     After the epilogue one raw barrier frees the staging area; the second k-tile of tile t+1 is requested and the main
+//     loop starts on a k-tile that has already landed.
+// The queue of a wave at that point, oldest first: [slot 0 of t+1] [epilogue stores of t] [slot 1 of t+1];
 // the first counted wait leaves only the youngest DPS operations outstanding, as in the one-tile form.
 // Every output element is the same K-ascending chain of MFMA steps: not a bit differs from gemm_tile_pipe.
 //
 // ORDERING ASSUMPTION.  `wait_vmcnt<DPS>` is read as "everything older than the youngest DPS vector-memory
-// operations of this wave has completed" across THREE kinds of operation in one queue: LDS-DMA loads (slot 0 of tile t+1),
-// the epilogue's global STORES, and the metadata DMA.  That holds on the gfx9 family this file is written for - gfx942 /
+// operations of this wave has completed" across TWO kinds of operation in one queue: LDS-DMA loads (slot 0 of tile t+1)
+// and the epilogue's global STORES.  That holds on the gfx9 family this file is written for - gfx942 /
 // gfx950 keep loads and stores on ONE vmcnt counter that retires in issue order (the ISA has no separate vscnt; gfx10+
 // split stores off into vscnt, where a store would no longer hold younger loads' count back and this wait would have to
 // become a load-only count).  The guard below refuses to compile the persistent form for anything else.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
 #error "gemm_tiles_persist relies on gfx942/gfx950 vmcnt semantics (loads and stores retire in order on one counter)"
 #endif
-constexpr int PERSIST_EPI_OFF = 64 * 1024, PERSIST_META_OFF = 136 * 1024, PERSIST_LDS_BYTES = 160 * 1024;
+constexpr int PERSIST_EPI_OFF = 64 * 1024, PERSIST_LDS_BYTES = 160 * 1024;
 template <class C, bool EDGE = false, class L0 = C, class Epilogue, class NextTile>
 __device__ __forceinline__ void gemm_tiles_persist(const GemmOperand A, const GemmOperand W, int K, NextTile next_tile,
                                                    Epilogue& epi, char* smem, bool edge_on = false) {
   static_assert(C::PIPE != 0 && C::FP8 == 0 && C::KTAIL == 0 && C::NSTAGE == 2 && C::STAGE_BYTES == 64 * 1024 &&
-                    C::NWAVES * EPI_STAGE_BYTES <= PERSIST_META_OFF - PERSIST_EPI_OFF,
+                    C::NWAVES * EPI_STAGE_BYTES <= PERSIST_LDS_BYTES - PERSIST_EPI_OFF,
                 "persistent form: the pipelined 256 x 256 x 64 bf16 tile");
   constexpr int BK = C::BK, KS = BK / 16, NSTAGE = 2, DPS = C::A_DMA + C::W_DMA;
   const int tid = threadIdx.x;
@@ -711,9 +702,8 @@ __device__ __forceinline__ void gemm_tiles_persist(const GemmOperand A, const Ge
       for (int j = 0; j < FN; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    if constexpr (has_prologue<Epilogue>::value) epi.prologue(smem + PERSIST_META_OFF, wave, lane, tile_n * C::BN);
     stage(1, 1);
-    wait_vmcnt<DPS>();  // everything older than slot 1's requests: slot 0 (and the last epilogue's stores, the metadata)
+    wait_vmcnt<DPS>();  // everything older than slot 1's requests: slot 0 (and the last epilogue's stores)
     __builtin_amdgcn_s_barrier();
     RP_PTS(p_t1);
     read_frags(smem, 0, 0);
@@ -729,7 +719,6 @@ __device__ __forceinline__ void gemm_tiles_persist(const GemmOperand A, const Ge
     tile_body(kt, I0(), I0());
     if constexpr (has_preload<Epilogue>::value) wait_vmcnt<0>();  // (landed under the k-tile; the next tile's requests come below)
     __syncthreads();  // every wave is done with the ring (nothing of this wave's is in flight here)
-    if constexpr (has_reduce<Epilogue>::value) epi.reduce(tid);  // (the barrier behind it: below, after the next tile's requests)
     RP_PTS(p_t2);
     int nm, nn;
     const bool more = next_tile(nm, nn);
@@ -739,10 +728,6 @@ __device__ __forceinline__ void gemm_tiles_persist(const GemmOperand A, const Ge
       stage(0, 0);  // lands under the epilogue
       tile_m = nm;
       tile_n = nn;
-    }
-    if constexpr (has_reduce<Epilogue>::value) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // the reduced metadata is visible to every wave (raw: the requests above stay in flight)
     }
     if constexpr (has_preload<Epilogue>::value)
       epi.template run<FM, FN, true>(acc, em, en, lane, smem + PERSIST_EPI_OFF + wave * EPI_STAGE_BYTES);
@@ -796,7 +781,7 @@ __device__ __forceinline__ void gemm_tiles_persist(const GemmOperand A, const Ge
     RP_PROBE_PERSIST_TILE_END(more);
     if (!more) break;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // the staging areas (over ring slot 1) and the metadata rows are free
+    __builtin_amdgcn_s_barrier();  // the staging areas (over ring slot 1) are free
   }
 }
 

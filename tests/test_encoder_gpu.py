@@ -182,15 +182,14 @@ def test_bf16_output_and_chunked_passes_agree(small, golden_dir):
 
 
 def test_big_pass_launch_forms_are_the_same_bits(small):
-    """Passes on the 256 x 256 tiles have four launch forms of the row-scaled projections: the RMSNorm statistic from a
-    rowscale launch per sub-layer (the default since round 5) or reduced inside the consuming GEMM (slot rows DMA'd into LDS
-    behind the operand ring, one thread per token summing them in index order: RowScaleLds), each with one workgroup per
-    tile or with persistent workgroups (gemm_tiles_persist: one per CU, the next tile's first k-tile requested under the
-    epilogue).  Round 5 added, on both forms: the last feature tile of 1152 / 1472 features on a wave grid over its valid
-    features only (`gemm_edge_layout`), the FFN-out / attention-out projections' half tiles inside the main launch
-    (`gemm_mixed`: gemm_kernel_mixed) or as a tail round of half / quarter tiles (`gemm_tail_variant` 30 / 0).  The same sums
-    in the same order, the same K-ascending MFMA chain per output element: the embeddings of a 70 k-token pass (more
-    tiles than CUs in every projection) must not differ by a bit between any two of them."""
+    """Passes on the 256 x 256 tiles have several launch forms per projection: one workgroup per tile or persistent
+    workgroups (`gemm_persist`, gemm_tiles_persist: one per CU, the next tile's first k-tile requested under the epilogue);
+    the last feature tile of 1152 / 1472 features on a wave grid over its valid features only (`gemm_edge_layout`); the
+    half tiles of the token rows beyond the whole rounds inside the main launch (`gemm_mixed`: gemm_kernel_mixed).  The same
+    sums in the same order, the same K-ascending MFMA chain per output element: the embeddings of a 70 k-token pass (more
+    tiles than CUs in every projection) must not differ by a bit between any two of them.
+    (The `gemm_rs_lds` and `gemm_tail_variant` columns left with their forms, docs/HISTORY.md section 14; every combination
+    of the three remaining columns that was listed is still here, none became a duplicate.)"""
     from reprover_amd import _lib
 
     lib = _lib.load()
@@ -201,20 +200,20 @@ def test_big_pass_launch_forms_are_the_same_bits(small):
     assert int(cu[-1]) > 65536  # 274 token tiles x >= 5 feature tiles: several tiles per persistent workgroup
     outs = []
     try:
-        #                rs_lds persist edge mixed tail
-        for forms in ((0, 9, 1, 20, 30),   # the defaults
-                      (0, 0, 0, 0, 0),     # round 4's launches: one workgroup per tile, every tile on the full wave grid, quarter-tile tail
-                      (1, 0, 1, 0, 30), (1, 29, 0, 0, 30), (0, 29, 1, 0, 0),
-                      (0, 0, 1, 21, 30),   # QKV, attention-out and FFN-out as mixed launches
-                      (0, 9, 1, 0, 30)):
-            for name, v in zip((b"gemm_rs_lds", b"gemm_persist", b"gemm_edge_layout", b"gemm_mixed", b"gemm_tail_variant"), forms):
+        #             persist edge mixed
+        for forms in ((9, 1, 20),   # the defaults
+                      (0, 0, 0),    # the independent baseline: one workgroup per tile, every tile on the full wave grid, no half tiles
+                      (0, 1, 0), (29, 0, 0), (29, 1, 0),
+                      (0, 1, 21),   # QKV, attention-out and FFN-out as mixed launches
+                      (9, 1, 0)):
+            for name, v in zip((b"gemm_persist", b"gemm_edge_layout", b"gemm_mixed"), forms):
                 _lib.check(lib.rp_set_option(name, v), "opt")
             out = torch.empty((len(texts), small.embedding_size), dtype=torch.float32, device="cuda:0")
             small.encoder.encode_packed(ids, cu, out)
             torch.cuda.synchronize()
             outs.append(out)
     finally:
-        for name, v in ((b"gemm_rs_lds", 0), (b"gemm_persist", 9), (b"gemm_edge_layout", 1), (b"gemm_mixed", 20), (b"gemm_tail_variant", 30)):
+        for name, v in ((b"gemm_persist", 9), (b"gemm_edge_layout", 1), (b"gemm_mixed", 20)):
             _lib.check(lib.rp_set_option(name, v), "opt")
     for o in outs[1:]:
         assert torch.equal(outs[0].view(torch.int32), o.view(torch.int32))
@@ -225,7 +224,8 @@ def test_big_pass_launch_forms_are_the_same_bits(small):
 def test_mixed_and_edge_forms_at_other_pass_sizes(small, n_states):
     """The mixed launch plans its half tiles from the token-tile count: 36 k tokens (142 token tiles: 128 whole-round tiles + 28 half
     rows, 21 handed out first) and 103 k (402 = 384 + 18 token tiles) beside the 70 k-token pass of the test above.  Shipped
-    forms vs one workgroup per tile on the full wave grid with no half tiles: the same bits."""
+    forms vs one workgroup per tile on the full wave grid with no half tiles: the same bits.  (The `gemm_tail_split` column
+    left with the tail round, docs/HISTORY.md: with `gemm_mixed` 0 the FFN-out projection is one launch of full tiles.)"""
     from reprover_amd import _lib
 
     lib = _lib.load()
@@ -235,12 +235,12 @@ def test_mixed_and_edge_forms_at_other_pass_sizes(small, n_states):
     ids, cu = small.tokenizer.packed(texts, small.max_seq_len)
     tiles = (int(cu[-1]) + 255) // 256
     assert tiles > 128 and 0 < tiles % 128 <= 21, tiles  # (a remainder the mixed plan takes)
-    names = (b"gemm_persist", b"gemm_edge_layout", b"gemm_mixed", b"gemm_tail_split")
+    names = (b"gemm_persist", b"gemm_edge_layout", b"gemm_mixed")
     outs = []
     old = small.encoder.max_tokens_per_pass
     small.encoder.max_tokens_per_pass = 1 << 20  # one pass whatever the size
     try:
-        for forms in ((9, 1, 20, 1), (0, 0, 0, 0)):
+        for forms in ((9, 1, 20), (0, 0, 0)):
             for name, v in zip(names, forms):
                 _lib.check(lib.rp_set_option(name, v), "opt")
             out = torch.empty((len(texts), small.embedding_size), dtype=torch.float32, device="cuda:0")
@@ -249,7 +249,7 @@ def test_mixed_and_edge_forms_at_other_pass_sizes(small, n_states):
             outs.append(out)
     finally:
         small.encoder.max_tokens_per_pass = old
-        for name, v in zip(names, (9, 1, 20, 1)):
+        for name, v in zip(names, (9, 1, 20)):
             _lib.check(lib.rp_set_option(name, v), "opt")
     assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
     assert torch.isfinite(outs[0]).all() and (outs[0].norm(dim=1) - 1).abs().max().item() < 1e-5
@@ -258,8 +258,9 @@ def test_mixed_and_edge_forms_at_other_pass_sizes(small, n_states):
 def test_launch_forms_are_the_same_bits_at_byt5_base_width():
     """The persistent / mixed / edge launch forms against one workgroup per tile at ByT5-BASE shapes: d_model
     1536 = 6 exact feature tiles (no edge tile; 24 statistic slots instead of 23), QKV 2304 = 9 tiles, FFN 2 x 3968 = 31
-    tiles - other tile counts per XCD range, other metadata sizes behind the ring than ByT5-small's.  Two layers keep
-    the test short; a 45 k-token pass gives every projection more tiles than CUs."""
+    tiles - other tile counts per XCD range than ByT5-small's.  Two layers keep the test short; a 45 k-token pass gives
+    every projection more tiles than CUs.  (`gemm_rs_lds` and `gemm_tail_split` left, docs/HISTORY.md section 14; the row
+    that differed from the baseline in `gemm_rs_lds` alone became its duplicate and was dropped.)"""
     from reprover_amd import _lib
 
     lib = _lib.load()
@@ -271,12 +272,12 @@ def test_launch_forms_are_the_same_bits_at_byt5_base_width():
     texts = [synth.synth_state(rng, int(n) - 1) for n in lens]
     ids, cu = model.tokenizer.packed(texts, model.max_seq_len)
     assert int(cu[-1]) > 36000
-    names = (b"gemm_rs_lds", b"gemm_persist", b"gemm_edge_layout", b"gemm_mixed", b"gemm_tail_split")
+    names = (b"gemm_persist", b"gemm_edge_layout", b"gemm_mixed")
     outs = []
     old = model.encoder.max_tokens_per_pass
     model.encoder.max_tokens_per_pass = 1 << 20
     try:
-        for forms in ((0, 9, 1, 20, 1), (0, 0, 0, 0, 0), (1, 29, 1, 21, 1), (1, 0, 0, 0, 1)):
+        for forms in ((9, 1, 20), (0, 0, 0), (29, 1, 21)):
             for name, v in zip(names, forms):
                 _lib.check(lib.rp_set_option(name, v), "opt")
             out = torch.empty((len(texts), model.embedding_size), dtype=torch.float32, device="cuda:0")
@@ -285,7 +286,7 @@ def test_launch_forms_are_the_same_bits_at_byt5_base_width():
             outs.append(out)
     finally:
         model.encoder.max_tokens_per_pass = old
-        for name, v in zip(names, (0, 9, 1, 20, 1)):
+        for name, v in zip(names, (9, 1, 20)):
             _lib.check(lib.rp_set_option(name, v), "opt")
     for o in outs[1:]:
         assert torch.equal(outs[0].view(torch.int32), o.view(torch.int32))

@@ -148,6 +148,66 @@ def test_c_abi_loads_and_exports_every_declared_symbol(hip_lib):
     assert hip_lib.rp_topk_merge_workspace_bytes(8, 256, 100) >= 8 * 256 * 100 * 8
 
 
+def test_retired_gemm_form_options_are_unknown(hip_lib):
+    """The LDS row-scale form and the FFN-out tail split left with their options (docs/HISTORY.md section 14)."""
+    for name in (b"gemm_rs_lds", b"gemm_tail_split", b"gemm_tail_variant"):
+        assert hip_lib.rp_set_option(name, 0) != 0
+        assert b"unknown option " + name in hip_lib.rp_last_error()
+
+
+GEMM_VARIANT_OPTIONS = (b"gemm_variant", b"gemm_variant_all", b"gemm_variant_qkv", b"gemm_variant_wo", b"gemm_variant_o")
+EXPERIMENT_BUILD = os.environ.get("RP_EXPERIMENTS") == "1"  # (reprover_amd/build.py: such a build also carries tiles 27 - 29)
+
+
+@pytest.mark.parametrize("name", GEMM_VARIANT_OPTIONS)
+def test_gemm_variant_options_take_only_tile_ids_of_this_build(hip_lib, name):
+    """Ids 12 and 20 left the sources in round 6 and ran the 128 x 128 x 32 tile under their own label until the options
+    started to reject every id launch_gemm() has no case for; -1 (the defaults) is a value of gemm_variant_all only."""
+    try:
+        for v in (0, 9, 15, 16, 17, 26, 30):
+            assert hip_lib.rp_set_option(name, v) == 0, (name, v, hip_lib.rp_last_error())
+        for v in (12, 20, 31) + (() if EXPERIMENT_BUILD else (27,)) + (() if name == b"gemm_variant_all" else (-1,)):
+            assert hip_lib.rp_set_option(name, v) != 0, (name, v)
+            assert name in hip_lib.rp_last_error() and str(v).encode() in hip_lib.rp_last_error()
+    finally:
+        assert hip_lib.rp_set_option(b"gemm_variant_all", -1) == 0
+
+
+def test_gemm_variant_all_minus_one_leaves_the_single_options_usable(hip_lib):
+    try:
+        assert hip_lib.rp_set_option(b"gemm_variant_all", 17) == 0
+        assert hip_lib.rp_set_option(b"gemm_variant_all", -1) == 0
+        assert hip_lib.rp_set_option(b"gemm_variant_qkv", 26) == 0
+        assert hip_lib.rp_set_option(b"gemm_variant_qkv", 12) != 0 and hip_lib.rp_set_option(b"gemm_variant_o", 30) == 0
+    finally:
+        assert hip_lib.rp_set_option(b"gemm_variant_all", -1) == 0
+
+
+# (name, default, values just outside what the option takes; None: it takes any value - the booleans store value != 0).
+# Written out here, not read from the C source: the table in rp_encoder.hip is what this list checks.
+OPTION_RANGES = [
+    (b"gemm_group_m", 8, (0, 65)), (b"gemm_skinny_variant", 0, (-1, 16, 9)), (b"gemm_helpers", 64, (-1, 249)),
+    (b"pool_chunk", 64, (31, 129, 96)), (b"gemm_mixed", 20, (-1, 32)), (b"scan_cfg", 0, (-1, 2)),
+    (b"train_wgrad_form", 0, (-1, 4)), (b"scan_small_tiles", 1, (-1, 2)), (b"scan_impl", 0, (-1, 2)),
+    (b"debug_skip_ffn", 0, None), (b"gemm_small_pipe", 1, None), (b"gemm_edge_layout", 1, None), (b"gemm_mixed_bwd", 1, None),
+    (b"gemm_skinny", 1, None), (b"gemm_persist", 9, None), (b"scan_cap", 0, None), (b"scan_force_new", 0, None),
+]
+
+
+@pytest.mark.parametrize("name,default,outside", OPTION_RANGES, ids=[o[0].decode() for o in OPTION_RANGES])
+def test_every_option_takes_its_default_and_rejects_values_outside_its_range(hip_lib, name, default, outside):
+    try:
+        assert hip_lib.rp_set_option(name, default) == 0, hip_lib.rp_last_error()
+        for v in outside if outside is not None else ():
+            assert hip_lib.rp_set_option(name, v) != 0, (name, v)
+            assert name in hip_lib.rp_last_error()
+        if outside is None:
+            for v in (-7, 2, 1 << 20):
+                assert hip_lib.rp_set_option(name, v) == 0, (name, v, hip_lib.rp_last_error())
+    finally:
+        assert hip_lib.rp_set_option(name, default) == 0
+
+
 def test_bucket_function_matches_hf(hip_lib, golden_dir):
     g = np.load(os.path.join(golden_dir, "g3_buckets.npz"))
     mine = np.array([hip_lib.rp_relative_position_bucket(int(r), 32, 128) for r in g["rel"]])

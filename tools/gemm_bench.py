@@ -7,7 +7,7 @@ if os.environ.get("LIB"):  # another build of the library (probe builds: tools/p
     _lib.LIB_PATH = os.path.abspath(os.environ["LIB"])
 lib = _lib.load()
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-variants = [int(v) for v in os.environ.get("VARIANTS", "26,20,9,0").split(",")]
+variants = [int(v) for v in os.environ.get("VARIANTS", "26,9,0").split(",")]
 groups = [int(v) for v in os.environ.get("GROUP_M", "8").split(",")]
 staggers = [int(v) for v in os.environ.get("STAGGER", "0").split(",")]
 persists = [int(v) for v in os.environ.get("PERSIST", "0").split(",")]  # gemm_persist masks (29 = every projection)  # gemm_stagger_us_* values (first-round spread)

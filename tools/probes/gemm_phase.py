@@ -2,7 +2,7 @@
 -DRP_PHASE_PROBE (here, on CPU) or loads it (on the GPU box) and prints per-phase times.
 
   python tools/probes/gemm_phase.py build        # here: cross-compile the probe library
-  VARIANTS=6,20 python tools/probes/gemm_phase.py   # on the GPU box
+  VARIANTS=26,9 python tools/probes/gemm_phase.py   # on the GPU box
 """
 import ctypes as C, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,7 +34,7 @@ for name in os.environ.get("ONLY", "wi,wo").split(","):
     out = (torch.zeros(2, M, N, dtype=torch.bfloat16, device=dev) if epi == _lib.RP_EPI_RESID else
            torch.empty(M, N // 2 if epi == _lib.RP_EPI_GEGLU_BF16 else N, dtype=torch.bfloat16, device=dev))
     persist = int(os.environ.get("PERSIST", "0"))
-    for v in [int(x) for x in os.environ.get("VARIANTS", "6,20").split(",")]:
+    for v in [int(x) for x in os.environ.get("VARIANTS", "26,9").split(",")]:
         _lib.check(lib.rp_set_option(b"gemm_variant_all", v), "opt")
         _lib.check(lib.rp_set_option(b"gemm_persist", persist), "opt")
         if persist:  # persistent workgroups keep SUMS per workgroup: read them around a batch of launches
