@@ -563,6 +563,39 @@ RpStatus rp_beam_select_batch(const float* logprobs, const float* running, int32
                               int32_t vocab, int32_t k, float* scores, int32_t* tokens, int32_t* parents,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* Sampled generation ("Sampling"): after rp_decoder_batch_step, one launch draws one
+ * token per row (row = slot * nb + sample, the step's layout) from logprobs [n_active * nb, vocab] and
+ * keeps the rows' books, so the host loop needs no readback.  HF's TemperatureLogitsWarper ->
+ * TopKLogitsWarper -> TopPLogitsWarper -> softmax -> multinomial, per row and in fp32:
+ *   1. s[v] = logprobs[v] / temperature
+ *   2. top-k (0 < top_k < vocab): drop s[v] < the k-th largest value; ties with it stay
+ *   3. top-p (top_p < 1), over e[v] = exp(s[v] - max) of what 2 kept: in ascending order of probability,
+ *      equal ones by descending id, drop every token whose inclusive cumulative mass is
+ *      <= (1 - top_p) * sum(e); the most probable token (the lowest id among equals) always stays
+ *   4. over the kept ids in ascending order, C(v) = inclusive prefix sum of e, Z = its total: the token
+ *      is the smallest kept v of non-zero mass with C(v) > u * Z, else the last kept v of non-zero mass
+ *   5. u = rp_sample_uniform(seeds[state], sample, t)
+ * Arrays indexed by state (not slot), all device memory, n = the states of the call:
+ *   seeds        uint32 [n]
+ *   seq          int32 [n, nb, max_len]: the token goes to position t + 1
+ *   cum_logprob  fp32  [n, nb]: += logprobs[token], the model's log-prob (untempered, unfiltered)
+ *   n_generated  int32 [n, nb]: += 1
+ *   finished     int32 [n, nb]: set when token == eos.  A row already finished writes pad to seq and
+ *                tokens_next and changes nothing else.
+ *   tokens_next  int32 [n_active * nb], by row: the next step's tokens
+ *   active       HOST int32 [n_active]: distinct states in [0, n), as rp_decoder_batch_step takes it
+ * RP_E_INVALID (nothing is launched): temperature <= 0 or not finite, top_p outside (0, 1], top_k < 0,
+ * vocab outside 1..512, nb outside 1..64, n outside 1..32, more than 1024 rows, t + 1 >= max_len. */
+RpStatus rp_sample_step(const float* logprobs, int32_t vocab, const int32_t* active, int32_t n_active, int32_t n,
+                        int32_t nb, const uint32_t* seeds, int32_t t, int32_t max_len, float temperature,
+                        int32_t top_k, float top_p, int32_t eos, int32_t pad, int32_t* seq, int32_t* tokens_next,
+                        float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream);
+/* The sampler's uniform in [0, 1), host only: (h >> 8) * 2^-24 with
+ *   h = fmix32(fmix32(seed ^ 0x53414D50) + sample * 0x85EBCA77 + position * 0x27D4EB2F)   (mod 2^32)
+ * fmix32 = murmur3's 32-bit finaliser (the training dropout's hash ends in it too).  seed is the state's,
+ * sample the row's index inside its state, position the step's t: nothing else enters. */
+float    rp_sample_uniform(uint32_t seed, uint32_t sample, uint32_t position);
+
 /* Teacher-forced seq2seq forward (T5ForConditionalGeneration(input_ids, attention_mask, labels)) over
  * `batch` (source, target) pairs packed varlen; DESIGN.md section 10.  src_cu / tgt_cu are HOST int32
  * [batch + 1] prefix sums (start at 0): source b is rows src_cu[b] .. src_cu[b+1] of enc_bf16, target b

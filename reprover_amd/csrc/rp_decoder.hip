@@ -297,6 +297,138 @@ __global__ __launch_bounds__(1024) void beam_merge_kernel(const uint64_t* __rest
   }
 }
 
+// ---- sampling ---------------------------------------------------------------------------------------------------------
+// The sampler's random number (include/reprover_hip.h, rp_sample_uniform): a counter-based hash of (the state's seed, the
+// sample's index inside its state, the position t), drop_hash's form with the seed finalised first so that neighbouring
+// seeds give unrelated streams.  Nothing else enters: not the row's slot in the launch, not the other states.
+constexpr uint32_t SAMPLE_SITE = 0x53414D50u;
+__host__ __device__ __forceinline__ float sample_uniform(uint32_t seed, uint32_t sample, uint32_t position) {
+  const uint32_t h = fmix32(fmix32(seed ^ SAMPLE_SITE) + sample * 0x85EBCA77u + position * 0x27D4EB2Fu);
+  return (float)(h >> 8) * 0x1p-24f;
+}
+
+// Inclusive prefix sums of a[0, 512) in place by 256 threads, in an order fixed by the index alone: thread i sums its pair
+// (2 i, 2 i + 1), a Hillis-Steele scan runs over the wave's 64 pair sums, the four wave totals are added in index order.
+// The caller has published a[]; the sums are published on return.
+__device__ __forceinline__ void block_scan512(float* a, float* red) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float x0 = a[2 * tid], x1 = x0 + a[2 * tid + 1];
+  float v = x1;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float up = __shfl_up(v, o, 64);
+    if (lane >= o) v += up;
+  }
+  float before = __shfl_up(v, 1, 64);
+  if (lane == 0) before = 0.f;
+  if (lane == 63) red[wave] = v;
+  __syncthreads();
+  for (int w = 0; w < wave; ++w) before += red[w];
+  a[2 * tid] = before + x0;
+  a[2 * tid + 1] = before + x1;
+  __syncthreads();
+}
+
+// One sampled token per row (row = slot * nb + sample) and the row's bookkeeping; one workgroup per row, vocab <= 512.
+// HF's TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> softmax -> multinomial with a stated order:
+//   s[v] = logprobs[v] / temperature, sorted descending with ties to the lower id (one bitonic sort serves both filters);
+//   top-k keeps s[v] >= the k-th largest (ties with it stay);
+//   top-p drops sorted position j > 0 when its tail mass sum_{i >= j} e_i <= drop_mass * sum_i e_i (e = exp(s - max) over
+//     what top-k kept; drop_mass = 1 - top_p; read from the far end this is HF's ascending cumulative sum, equal
+//     probabilities in descending id order);
+//   the draw walks the kept ids in ascending order: the smallest v of non-zero mass with C(v) > u Z (C = the inclusive
+//     prefix sum of e, Z its last value), else the last kept id of non-zero mass.
+// State arrays are indexed by (state, sample): a finished row writes pad and changes nothing else.
+__global__ __launch_bounds__(256) void sample_step_kernel(const float* __restrict__ lp, int V, int nb, DecSlots slots,
+                                                          const uint32_t* __restrict__ seeds, int t, int max_len,
+                                                          float temperature, int top_k, float drop_mass, int eos, int pad,
+                                                          int32_t* __restrict__ seq, int32_t* __restrict__ tokens_next,
+                                                          float* __restrict__ cum, int32_t* __restrict__ ngen,
+                                                          int32_t* __restrict__ finished) {
+  __shared__ uint64_t keys[DEC_SELECT_ROW];
+  __shared__ float sc[DEC_SELECT_ROW];  // tail masses by reversed sorted position, then masses / prefix sums by id
+  __shared__ float red[4];
+  __shared__ int s_first[4], s_last[4];
+  const int tid = threadIdx.x, row = blockIdx.x, slot = row / nb, b = row - slot * nb;
+  const int state = slots.state[slot];
+  const size_t idx = (size_t)state * nb + b;
+  int32_t* next = seq + idx * max_len + min(t + 1, max_len - 1);
+  if (finished[idx]) {  // the same value for the whole workgroup
+    if (tid == 0) {
+      *next = pad;
+      tokens_next[row] = pad;
+    }
+    return;
+  }
+  const float* r = lp + (size_t)row * V;
+  for (int i = tid; i < DEC_SELECT_ROW; i += 256) keys[i] = (i < V) ? sel_key(r[i] / temperature, (uint32_t)i) : 0ull;
+  bitonic_desc(keys, DEC_SELECT_ROW);  // the V keys of the row (all non-zero) come first
+  const float mx = key_score(keys[0]);
+  // top-k on the keys' order-preserving high words (s[v] >= the k-th largest); off: the row's smallest, all stay
+  const uint32_t thr = (uint32_t)(keys[(top_k > 0 && top_k < V) ? top_k - 1 : V - 1] >> 32);
+  float e[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int j = tid + 256 * c;
+    const float sj = key_score(keys[j]);
+    e[c] = (j < V && (uint32_t)(keys[j] >> 32) >= thr) ? expf(sj - mx) : 0.f;
+  }
+  if (drop_mass > 0.f) {
+    sc[DEC_SELECT_ROW - 1 - tid] = e[0];
+    sc[DEC_SELECT_ROW - 1 - (tid + 256)] = e[1];
+    __syncthreads();
+    block_scan512(sc, red);
+    const float cut = drop_mass * sc[DEC_SELECT_ROW - 1];
+    const float t0 = sc[DEC_SELECT_ROW - 1 - tid], t1 = sc[DEC_SELECT_ROW - 1 - (tid + 256)];
+    if (tid > 0 && t0 <= cut) e[0] = 0.f;  // sorted position 0, the most probable token, always stays
+    if (t1 <= cut) e[1] = 0.f;
+    __syncthreads();
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int j = tid + 256 * c;
+    if (j < V) sc[min(~(uint32_t)keys[j], (uint32_t)(V - 1))] = e[c];  // the ids of positions [0, V) are 0 .. V - 1
+    else sc[j] = 0.f;
+  }
+  __syncthreads();
+  const float w0 = sc[2 * tid], w1 = sc[2 * tid + 1];
+  block_scan512(sc, red);
+  const float target = sample_uniform(seeds[state], (uint32_t)b, (uint32_t)t) * sc[DEC_SELECT_ROW - 1];
+  // the smallest id whose prefix sum passes the target, and the largest id of non-zero mass (its stand-in when rounding
+  // leaves none): wave butterflies, then the four waves
+  int first = DEC_SELECT_ROW, last = -1;
+  if (w1 > 0.f) {
+    last = 2 * tid + 1;
+    if (sc[2 * tid + 1] > target) first = 2 * tid + 1;
+  }
+  if (w0 > 0.f) {
+    last = max(last, 2 * tid);
+    if (sc[2 * tid] > target) first = 2 * tid;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    first = min(first, __shfl_xor(first, o, 64));
+    last = max(last, __shfl_xor(last, o, 64));
+  }
+  if ((tid & 63) == 0) {
+    s_first[tid >> 6] = first;
+    s_last[tid >> 6] = last;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    first = min(min(s_first[0], s_first[1]), min(s_first[2], s_first[3]));
+    last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
+    int tok = first < DEC_SELECT_ROW ? first : last;
+    if (tok < 0) tok = (int)~(uint32_t)keys[0];  // no mass anywhere (NaN rows, outside the contract): the first key's id
+    tok = min(max(tok, 0), V - 1);
+    *next = tok;
+    tokens_next[row] = tok;
+    cum[idx] += r[tok];  // the model's log-prob: untempered, unfiltered
+    ngen[idx] += 1;
+    if (tok == eos) finished[idx] = 1;
+  }
+}
+
 struct DecWs {
   bf16_t* ckv;    // [sum S, L * 2 * inner]
   bf16_t* cache;  // [n][L][max_len * nb, 2 * inner]
@@ -569,6 +701,41 @@ extern "C" RpStatus rp_beam_select_batch(const float* lp, const float* running, 
   uint64_t* cand = (uint64_t*)ws;
   hipLaunchKernelGGL(beam_row_topk_kernel, dim3(n_active * nb), dim3(256), 0, s, lp, running, V, kr, nb, cand);
   hipLaunchKernelGGL(beam_merge_kernel, dim3(n_active), dim3(1024), 0, s, cand, nb * kr, V, k, scores, tokens, parents);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" float rp_sample_uniform(uint32_t seed, uint32_t sample, uint32_t position) {
+  return sample_uniform(seed, sample, position);
+}
+
+extern "C" RpStatus rp_sample_step(const float* lp, int32_t V, const int32_t* active, int32_t n_active, int32_t n,
+                                   int32_t nb, const uint32_t* seeds, int32_t t, int32_t max_len, float temperature,
+                                   int32_t top_k, float top_p, int32_t eos, int32_t pad, int32_t* seq, int32_t* tokens_next,
+                                   float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream_) {
+  RP_REQUIRE(lp && active && seeds && seq && tokens_next && cum_logprob && n_generated && finished, "null argument");
+  RP_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "temperature=%g, not a positive finite number", (double)temperature);
+  RP_REQUIRE(top_p > 0.f && top_p <= 1.f, "top_p=%g outside (0, 1]", (double)top_p);
+  RP_REQUIRE(top_k >= 0, "top_k=%d < 0", top_k);
+  RP_REQUIRE(V >= 1 && V <= DEC_SELECT_ROW, "vocab=%d (1..%d)", V, DEC_SELECT_ROW);
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "nb=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(n >= 1 && n <= DEC_MAX_STATES, "states=%d (1..%d)", n, DEC_MAX_STATES);
+  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
+  RP_REQUIRE(n_active * nb <= DEC_MAX_ROWS, "rows = active states * nb = %d > %d", n_active * nb, DEC_MAX_ROWS);
+  RP_REQUIRE(max_len >= 2 && t >= 0 && t + 1 < max_len, "t=%d: position t + 1 outside [1, max_len=%d)", t, max_len);
+  DecSlots slots = {};
+  uint32_t seen = 0;
+  for (int a = 0; a < n_active; ++a) {
+    const int sidx = active[a];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two rows would share a score
+    seen |= 1u << sidx;
+    slots.state[a] = sidx;
+  }
+  const float drop_mass = (float)(1.0 - (double)top_p);
+  hipLaunchKernelGGL(sample_step_kernel, dim3(n_active * nb), dim3(256), 0, (hipStream_t)stream_, lp, V, nb, slots, seeds,
+                     t, max_len, temperature, top_k, drop_mass, eos, pad, seq, tokens_next, cum_logprob, n_generated,
+                     finished);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }

@@ -84,13 +84,7 @@ struct Drop {
 // murmur3's 32-bit finaliser over a counter that is LINEAR in (row, column pair): walking a lane's elements along either
 // index is one add in front of it (the attention backward walks queries in one launch and keys in the other).
 __device__ __forceinline__ uint32_t drop_hash(uint32_t seed, uint32_t site, uint32_t row, uint32_t col2) {
-  uint32_t h = (seed ^ (site * 0x9E3779B1u)) + row * 0x85EBCA77u + col2 * 0x27D4EB2Fu;
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
+  return fmix32((seed ^ (site * 0x9E3779B1u)) + row * 0x85EBCA77u + col2 * 0x27D4EB2Fu);
 }
 // multipliers of columns col_even and col_even + 1 (col_even must be even)
 __device__ __forceinline__ void drop_mul2(const Drop& d, uint32_t site, uint32_t row, uint32_t col_even, float& m0, float& m1) {

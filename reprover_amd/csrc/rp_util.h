@@ -146,6 +146,17 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// murmur3's 32-bit finaliser: the last stage of the training dropout's hash (rp_encoder_kernels.h::drop_hash) and of the
+// sampler's uniform (rp_decoder.hip::sample_hash, which the host evaluates too)
+__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
 // monotone float <-> uint32 map (larger float = larger uint)
 __host__ __device__ __forceinline__ uint32_t f2ord(float f) {
 #ifdef __HIP_DEVICE_COMPILE__

@@ -20,7 +20,8 @@ import torch
 
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
-from .generation import BeamSearchOutput, beam_search, beam_search_batch, greedy_search, greedy_search_batch
+from .generation import (BeamSearchOutput, SampleState, beam_search, beam_search_batch, check_sampling, greedy_search,
+                         greedy_search_batch, sample_search_batch)
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
 _STATE_0 = np.zeros(1, dtype=np.int32)  # the active list of a one-state step
@@ -271,13 +272,17 @@ class HipT5Decoder:
                                                            _lib.current_stream()),
                        "rp_decoder_batch_cross_kv")
 
-    def step_many(self, active, tokens: torch.Tensor, ancestry: torch.Tensor,
-                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def step_many(self, active, tokens: torch.Tensor, ancestry: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  t: Optional[int] = None) -> torch.Tensor:
         """log-probs [n_active * nb, V] of one step for the states ``active`` (distinct indices into ``start_many``'s
-        sources): row ``a * nb + b`` is beam ``b`` of state ``active[a]`` (``beam_search_batch``'s ``step_many``)."""
+        sources): row ``a * nb + b`` is beam ``b`` of state ``active[a]`` (``beam_search_batch``'s ``step_many``).
+        The position is the table's last column; with ``t`` given it is ``t`` and ``ancestry`` a wider table of which
+        columns ``0..t`` are read (``sample_search_batch`` passes one table for the whole search)."""
         cu, n, nb, max_len = self._many
         act = np.ascontiguousarray(active, dtype=np.int32)
         rows, T = ancestry.shape
+        if t is not None and not 0 <= t < T:
+            raise _lib.HipLibraryError(f"step_many: t={t} outside the {T} columns of the ancestry table")
         if rows != len(act) * nb or tokens.numel() != rows:
             raise _lib.HipLibraryError(f"step_many: {rows} ancestry rows, {tokens.numel()} tokens for {len(act)} states "
                                        f"of {nb} beams")
@@ -288,10 +293,31 @@ class HipT5Decoder:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rp_decoder_batch_step(self._handle, cu.ctypes.data_as(C.c_void_p), n,
                                                        act.ctypes.data_as(C.c_void_p), len(act), tok.data_ptr(),
-                                                       anc.data_ptr(), T, nb, T - 1, max_len, out.data_ptr(),
+                                                       anc.data_ptr(), T, nb, T - 1 if t is None else t, max_len,
+                                                       out.data_ptr(),
                                                        self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
                        "rp_decoder_batch_step")
         return out
+
+    def sample_step(self, log_probs: torch.Tensor, active, t: int, state: SampleState, temperature: float = 1.0,
+                    top_k: int = 0, top_p: float = 1.0, eos_token_id: int = 1, pad_token_id: int = 0) -> None:
+        """One token per row of ``log_probs [n_active * nb, V]`` and the rows' books in ``state``, on the device
+        (``rp_sample_step``; ``sample_search_batch``'s ``sample_step``).  Nothing is read back."""
+        act = np.ascontiguousarray(active, dtype=np.int32)
+        n, nb, max_len = state.seq.shape
+        rows, V = log_probs.shape
+        if rows != len(act) * nb or state.tokens.numel() < rows:
+            raise _lib.HipLibraryError(f"sample_step: {rows} rows for {len(act)} states of {nb} samples")
+        for x in (log_probs, state.seeds, state.seq, state.cum_logprob, state.n_generated, state.finished, state.tokens):
+            assert x.is_cuda and x.is_contiguous(), "rp_sample_step takes contiguous device tensors"
+        assert log_probs.dtype == torch.float32
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_sample_step(log_probs.data_ptr(), V, act.ctypes.data_as(C.c_void_p), len(act), n, nb,
+                                                state.seeds.data_ptr(), t, max_len, temperature, top_k, top_p,
+                                                eos_token_id, pad_token_id, state.seq.data_ptr(), state.tokens.data_ptr(),
+                                                state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
+                                                state.finished.data_ptr(), _lib.current_stream()),
+                       "rp_sample_step")
 
     def select_many(self, log_probs: torch.Tensor, running: torch.Tensor, nb: int, k: int):
         """Per state the device top-k of its own ``[nb * V]`` block (``rp_beam_select_batch``): scores, tokens, parents,
@@ -444,3 +470,40 @@ class HipT5Generator:
                                  eos_token_id=self.cfg.get("eos_token_id", 1),
                                  decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),
                                  select_many=self.decoder.select_many, device=self.device, traces=traces)
+
+    def sample(self, ids: np.ndarray, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
+               top_p: float = 1.0, seed: int = 0, length_penalty: float = 0.0, sync_every: int = 16) -> BeamSearchOutput:
+        """``num_samples`` sampled continuations of one source (``sample_many`` with one state)."""
+        return self.sample_many([ids], num_samples, max_length, temperature, top_k, top_p, [seed], length_penalty,
+                                sync_every)[0]
+
+    def sample_many(self, sources, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
+                    top_p: float = 1.0, seeds=None, length_penalty: float = 0.0,
+                    sync_every: int = 16) -> List[BeamSearchOutput]:
+        """Temperature / top-k / top-p sampling (``generate(do_sample=True, num_return_sequences=num_samples)``'s warper
+        chain with a stated order and random number, DESIGN.md section 9 "Sampling") for several sources through one
+        decode loop with no per-step readback.  ``seeds[i]`` (default ``0..n-1``) is source ``i``'s 32-bit seed.  Entry
+        ``i`` equals ``sample(sources[i], ..., seed=seeds[i])`` bit for bit, tokens and scores, whichever states share
+        the call, in whatever order, for any ``sync_every``.  Rows come in sample order; ``sequences_scores`` is the
+        sum of the model's log-probs of the drawn tokens divided by ``n_generated ** length_penalty``."""
+        check_sampling(temperature, top_k, top_p)
+        if num_samples < 1 or max_length <= 1:
+            raise ValueError(f"num_samples={num_samples} (>= 1), max_length={max_length} (>= 2)")
+        if sync_every < 1:
+            raise ValueError(f"sync_every={sync_every} must be >= 1")
+        sources = list(sources)
+        seeds = list(range(len(sources))) if seeds is None else [int(x) for x in seeds]
+        if len(seeds) != len(sources):
+            raise ValueError(f"{len(seeds)} seeds for {len(sources)} sources")
+        if not sources or len(sources) > self.decoder.max_states(num_samples):
+            raise ValueError(f"sample_many takes 1..{self.decoder.max_states(num_samples)} sources at "
+                             f"{num_samples} samples, got {len(sources)}")
+        n = self._start_many(sources, num_samples, max_length)
+        eos = self.cfg.get("eos_token_id", 1)
+        dec = self.decoder
+        return sample_search_batch(
+            lambda active, tokens, ancestry, t: dec.step_many(active, tokens, ancestry, t=t),
+            lambda lp, active, t, state: dec.sample_step(lp, active, t, state, temperature, int(top_k), top_p, eos, 0),
+            n, num_samples, max_length, seeds, length_penalty, eos_token_id=eos,
+            decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
+            device=self.device)

@@ -20,13 +20,17 @@ The model enters through two callables:
 Host synchronisation: the ``2 nb`` selected triples are read back once per step (``.cpu()``) because the finished-beam
 bookkeeping below runs on the host.  At 64 beams that is one ~1.5 KB copy and one stream sync per step.
 
-There is one loop per search kind, over 1..n sources (``beam_search_batch``, ``greedy_search_batch``); ``beam_search`` and
-``greedy_search`` wrap their ``step`` / ``select`` into its ``_many`` protocol and run it with one source.
+There is one loop per search kind, over 1..n sources (``beam_search_batch``, ``greedy_search_batch``,
+``sample_search_batch``); ``beam_search``, ``greedy_search`` and ``sample_search`` wrap their callables into its ``_many``
+protocol and run it with one source.
+
+Sampling (``sample_search_batch``) keeps its whole state on the device and reads nothing back per step: rows never
+reorder, so the ancestry table is the identity, and the finished flags are read once every ``sync_every`` positions.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -237,3 +241,100 @@ def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, e
         t += 1
     return [BeamSearchOutput(torch.tensor([s], dtype=torch.int64), torch.tensor([tot], dtype=torch.float32))
             for s, tot in zip(seqs, totals)]
+
+
+@dataclass
+class SampleState:
+    """The per-row books of a sampled search, indexed by (state, sample); ``sample_step`` updates them in place."""
+    seeds: torch.Tensor        # int32 [n]: the states' 32-bit seeds (the bits of a uint32)
+    seq: torch.Tensor          # int32 [n, nb, max_length]: start token first, pad where nothing was written
+    cum_logprob: torch.Tensor  # fp32 [n, nb]: sum of the model's log-probs of the drawn tokens
+    n_generated: torch.Tensor  # int32 [n, nb]
+    finished: torch.Tensor     # int32 [n, nb]
+    tokens: torch.Tensor       # int32 [n * nb]: the next step's tokens by row (slot * nb + sample)
+
+
+def check_sampling(temperature: float, top_k: int, top_p: float) -> None:
+    """``ValueError`` for parameters outside the sampler's domain (``rp_sample_step``'s own rules)."""
+    if not (temperature > 0.0 and temperature < float("inf")):
+        raise ValueError(f"temperature={temperature} must be a positive finite number")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"top_k={top_k} must be an integer >= 0 (0 = off)")
+    if not (0.0 < top_p <= 1.0):
+        raise ValueError(f"top_p={top_p} must lie in (0, 1]")
+
+
+def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: int, num_samples: int, max_length: int,
+                        seeds: Sequence[int], length_penalty: float = 0.0, eos_token_id: int = 1,
+                        decoder_start_token_id: int = 0, pad_token_id: int = 0, sync_every: int = 16,
+                        device=None) -> List[BeamSearchOutput]:
+    """The sampling loop: ``num_states`` sources in lockstep with ``num_samples`` independent rows each; per position one
+    ``step_many`` and one ``sample_step``, nothing read back.  Every ``sync_every`` positions the finished flags are
+    read once and the states whose samples have all finished leave the active list; the loop ends when it is empty or
+    at ``max_length``.  A finished row of a state that is still active keeps being stepped (it is fed the pad token and
+    its outputs are ignored): that is the price of not looking every step, and it changes no result, because a row's
+    log-probs depend on no other row and its random numbers on (seed, sample, position) alone.  So entry ``i`` is the
+    same bits whichever states share the call, in whatever order, for any ``sync_every``.
+
+    - ``step_many(active, tokens, ancestry, t) -> log_probs``: as in ``beam_search_batch``, except that ``ancestry`` is
+      the first ``n_active * nb`` rows of one identity table built here once, ``[num_states * nb, max_length]`` with
+      entry ``[r, p] = p * nb + r % nb`` (row ``r`` keeps to its own cache rows), of which the step at position ``t``
+      reads columns ``0..t``; ``tokens`` is int32 ``[n_active * nb]``.
+    - ``sample_step(log_probs, active, t, state)``: draws one token per row and updates ``state`` (``SampleState``) as
+      ``rp_sample_step`` does: token to ``seq[.., t + 1]`` and ``tokens``, the model's log-prob added to ``cum_logprob``,
+      ``n_generated`` incremented, ``finished`` set at EOS; a finished row writes pad and nothing else.
+
+    Returns per state ``sequences [num_samples, out_len]`` (start token first, pad after EOS, trimmed to the state's
+    longest sample) in sample order and ``sequences_scores = cum_logprob / n_generated ** length_penalty`` (the
+    finished-beam formula; the default 0.0 gives the sum)."""
+    n, nb = int(num_states), int(num_samples)
+    if max_length <= 1:
+        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+    if len(seeds) != n:
+        raise ValueError(f"{len(seeds)} seeds for {n} states")
+    if nb < 1 or n < 1 or sync_every < 1:
+        raise ValueError(f"num_states={n}, num_samples={nb}, sync_every={sync_every} must all be >= 1")
+    seed_bits = torch.tensor([int(s) & 0xFFFFFFFF for s in seeds], dtype=torch.int64)
+    st = SampleState(
+        seeds=torch.where(seed_bits >= 2 ** 31, seed_bits - 2 ** 32, seed_bits).to(torch.int32),
+        seq=torch.full((n, nb, max_length), pad_token_id, dtype=torch.int32),
+        cum_logprob=torch.zeros((n, nb), dtype=torch.float32), n_generated=torch.zeros((n, nb), dtype=torch.int32),
+        finished=torch.zeros((n, nb), dtype=torch.int32),
+        tokens=torch.full((n * nb,), decoder_start_token_id, dtype=torch.int32))
+    st.seq[:, :, 0] = decoder_start_token_id
+    ancestry = (torch.arange(max_length, dtype=torch.int32)[None] * nb
+                + (torch.arange(n * nb, dtype=torch.int32) % nb)[:, None]).contiguous()
+    if device is not None:
+        for f in ("seeds", "seq", "cum_logprob", "n_generated", "finished", "tokens"):
+            setattr(st, f, getattr(st, f).to(device))
+        ancestry = ancestry.to(device)
+    active = list(range(n))
+    t = 0
+    while active and t + 1 < max_length:
+        rows = len(active) * nb
+        log_probs = step_many(list(active), st.tokens[:rows], ancestry[:rows], t)
+        sample_step(log_probs, list(active), t, st)
+        t += 1
+        if t % sync_every == 0 and t + 1 < max_length:
+            done = st.finished.bool().all(dim=1).cpu()  # the only host sync of the loop
+            still = [i for i in active if not bool(done[i])]
+            if still and len(still) != len(active):  # slots moved: the next step's tokens, by the new rows
+                idx = torch.tensor(still, dtype=torch.int64, device=st.seq.device)
+                st.tokens[: len(still) * nb] = st.seq[idx, :, t].reshape(-1)
+            active = still
+    seq, cum, ngen = st.seq.cpu().long(), st.cum_logprob.cpu(), st.n_generated.cpu()
+    outs = []
+    for i in range(n):
+        out_len = 1 + int(ngen[i].max())
+        scores = cum[i] / ngen[i].to(torch.float32) ** float(length_penalty)
+        outs.append(BeamSearchOutput(seq[i, :, :out_len].clone(), scores))
+    return outs
+
+
+def sample_search(step: Callable, sample_step: Callable, num_samples: int, max_length: int, seed: int = 0,
+                  length_penalty: float = 0.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
+                  pad_token_id: int = 0, sync_every: int = 16, device=None) -> BeamSearchOutput:
+    """``sample_search_batch`` with one state: ``step(tokens, ancestry, t)``, ``sample_step`` as there."""
+    return sample_search_batch(lambda active, tokens, ancestry, t: step(tokens, ancestry, t), sample_step, 1,
+                               num_samples, max_length, [seed], length_penalty, eos_token_id, decoder_start_token_id,
+                               pad_token_id, sync_every, device)[0]

@@ -10,6 +10,7 @@ from typing import List, Tuple
 
 from ..common import Pos, format_augmented_state, remove_marks, zip_strict
 from ..decoder import HipT5Generator
+from ..generation import check_sampling
 from ..retrieval.model import PremiseRetriever
 from ..tokenizer import ByT5Tokenizer, encode_one
 
@@ -25,16 +26,57 @@ class TacticGenerator:
 
 class HuggingFaceGenerator(TacticGenerator):
     """Beam-search tactic generator (reference :169-243).  ``num_samples`` beams, ``num_samples`` returned sequences,
-    ``max_length=max_oup_seq_len`` (the decoder start token included), ``early_stopping=False``."""
+    ``max_length=max_oup_seq_len`` (the decoder start token included), ``early_stopping=False``.
+
+    ``do_sample=True`` draws ``num_samples`` samples instead (temperature / top-k / top-p, ``HipT5Generator.sample_many``)
+    and returns them sorted by score, best first (a stable sort), de-duplicated keeping the first occurrence.  The seed
+    of a served state mixes ``seed`` with the number of states this object has served so far: repeated calls on one
+    state differ, and ``batch_generate_sync([a, b])`` equals ``generate_sync(a)`` then ``generate_sync(b)``."""
 
     def __init__(self, model_path: str, device, max_inp_seq_len: int, max_oup_seq_len: int, length_penalty: float,
-                 template: str = "%s"):
+                 template: str = "%s", do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
+                 top_p: float = 1.0, seed: int = 0):
         self.model_path = model_path
         self.device = device
         self.max_inp_seq_len = max_inp_seq_len
         self.max_oup_seq_len = max_oup_seq_len
         self.length_penalty = length_penalty
         self.template = template
+        check_sampling(temperature, top_k, top_p)
+        self.do_sample, self.temperature, self.top_k, self.top_p, self.seed = do_sample, temperature, top_k, top_p, seed
+        self.states_served = 0
+
+    def _next_seeds(self, n: int) -> List[int]:
+        """The 32-bit seeds of the next ``n`` served states (murmur3's finaliser over seed + golden-ratio steps)."""
+        out = []
+        for _ in range(n):
+            self.states_served += 1
+            h = (int(self.seed) + self.states_served * 0x9E3779B1) & 0xFFFFFFFF
+            h ^= h >> 16
+            h = (h * 0x85EBCA6B) & 0xFFFFFFFF
+            h ^= h >> 13
+            h = (h * 0xC2B2AE35) & 0xFFFFFFFF
+            out.append(h ^ (h >> 16))
+        return out
+
+    def _sampled(self, ids, num_samples: int) -> List[List[Tuple[str, float]]]:
+        results: List[List[Tuple[str, float]]] = []
+        cap = self.generator.decoder.max_states(num_samples)
+        for i in range(0, len(ids), cap):
+            chunk = ids[i : i + cap]
+            outs = self.generator.sample_many(chunk, num_samples, self.max_oup_seq_len, self.temperature, self.top_k,
+                                              self.top_p, self._next_seeds(len(chunk)), self.length_penalty)
+            for out in outs:
+                text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
+                scores = out.sequences_scores.tolist()
+                output_text, output_score = [], []
+                for j in sorted(range(len(scores)), key=lambda j: -scores[j]):  # sorted() is stable
+                    t = remove_marks(text[j])
+                    if t not in output_text:
+                        output_text.append(t)
+                        output_score.append(scores[j])
+                results.append(list(zip_strict(output_text, output_score)))
+        return results
 
     def initialize(self) -> None:
         # A decoder-only checkpoint (the reference's AutoModelForCausalLM fallback) raises ValueError here.
@@ -46,6 +88,8 @@ class HuggingFaceGenerator(TacticGenerator):
                       num_samples: int) -> List[Tuple[str, float]]:
         state = self.template % state
         ids = encode_one(state, self.max_inp_seq_len)  # tokenizer(state, max_length=..., truncation=True)
+        if self.do_sample:
+            return self._sampled([ids], num_samples)[0]
         out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty)
         raw_output_text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
         raw_scores = out.sequences_scores.tolist()
@@ -66,6 +110,8 @@ class HuggingFaceGenerator(TacticGenerator):
         """``generate_sync`` for several states through one decode loop (``HipT5Generator.generate_many``): entry ``i``
         is ``generate_sync(states[i], ...)`` exactly, de-duplication order included."""
         ids = [encode_one(self.template % s, self.max_inp_seq_len) for s in states]
+        if self.do_sample:
+            return self._sampled(ids, num_samples)
         results: List[List[Tuple[str, float]]] = []
         cap = self.generator.decoder.max_states(num_samples)  # the engine's cap on states per call
         for i in range(0, len(ids), cap):
@@ -92,7 +138,8 @@ class RetrievalAugmentedGenerator(TacticGenerator):
     """Reference :246-298: retrieve, format the augmented state, generate."""
 
     def __init__(self, gen_path: str, ret_path: str, indexed_corpus_path: str, device, max_inp_seq_len: int,
-                 max_oup_seq_len: int, length_penalty: float, max_num_retrieved: int) -> None:
+                 max_oup_seq_len: int, length_penalty: float, max_num_retrieved: int, do_sample: bool = False,
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
         self.gen_path = gen_path
         self.ret_path = ret_path
         self.indexed_corpus_path = indexed_corpus_path
@@ -101,7 +148,9 @@ class RetrievalAugmentedGenerator(TacticGenerator):
         self.max_oup_seq_len = max_oup_seq_len
         self.length_penalty = length_penalty
         self.max_num_retrieved = max_num_retrieved
-        self.hf_gen = HuggingFaceGenerator(gen_path, device, max_inp_seq_len, max_oup_seq_len, length_penalty)
+        self.hf_gen = HuggingFaceGenerator(gen_path, device, max_inp_seq_len, max_oup_seq_len, length_penalty,
+                                           do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                                           seed=seed)
 
     def initialize(self) -> None:
         self.hf_gen.initialize()

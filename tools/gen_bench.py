@@ -10,6 +10,12 @@ and the validation shape (greedy, largest B).  Times, ratio (loop / batched), pe
 per step, as one JSON line.
 
     python tools/gen_bench.py --states 1 4 8 [--reps 2] [--out FILE]
+
+``--sample``: the sampled call beside the beam-search prover call, in one process, the two alternating: 64 samples
+(temperature 1, top_k 0, top_p 0.95) against 64 beams, a 2048-byte source, max_length 512.  Whole-call and per-step
+milliseconds of both, as one JSON line.
+
+    python tools/gen_bench.py --sample [--reps 3] [--out FILE]
 """
 from __future__ import annotations
 
@@ -106,12 +112,47 @@ def states_bench(gen, cfg, states, reps, nb=64, max_len=512, src_bytes=2048):
     return res
 
 
+def sample_bench(gen, cfg, reps, nb=64, max_len=512, src_bytes=2048):
+    rng = np.random.default_rng(0)
+    src = np.concatenate([rng.integers(3, 259, size=src_bytes - 1), [1]]).astype(np.int32)
+    kw = dict(temperature=1.0, top_k=0, top_p=0.95)
+    gen.generate(src, nb, 8, 0.0)  # warm-up: code objects
+    gen.sample(src, nb, 8, **kw)
+    beam_ms, sample_ms, beam_steps, sample_steps = [], [], 0, 0
+    for r in range(reps):
+        steps = []
+        ms, _ = _timed(lambda: gen.generate(src, nb, max_len, 0.0, trace=steps))
+        beam_ms.append(ms)
+        beam_steps = len(steps)
+        ms, out = _timed(lambda: gen.sample(src, nb, max_len, seed=r, **kw))
+        sample_ms.append(ms)
+        sample_steps = out.sequences.shape[1] - 1  # an upper bound when every sample stops inside one sync interval
+    L = cfg["num_decoder_layers"]
+    return {"metric": "gen_sample_bench", "rows": nb, "max_length": max_len, "length_penalty": 0.0, "sampling": kw,
+            "sync_every": 16, "config": f"byt5-small ({L} decoder layers), source {src_bytes} bytes", "reps": reps,
+            "beam_ms": [round(x, 1) for x in beam_ms], "sample_ms": [round(x, 1) for x in sample_ms],
+            "beam_steps": beam_steps, "sample_steps": sample_steps,
+            "beam_ms_per_step": [round(x / beam_steps, 3) for x in beam_ms],
+            "sample_ms_per_step": [round(x / sample_steps, 3) for x in sample_ms],
+            "launches_per_step": {"beam": 12 * L + 4 + 2, "sample": 12 * L + 4 + 1}}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--states", type=int, nargs="+", default=None, help="batched generation against the per-state loop")
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--sample", action="store_true", help="the sampled call beside the beam-search prover call")
     args = ap.parse_args(argv)
+    if args.sample:
+        cfg = synth.seq2seq_config("byt5-small")
+        gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
+        line = json.dumps(sample_bench(gen, cfg, max(args.reps, 2)))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     if args.states:
         cfg = synth.seq2seq_config("byt5-small")
         gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
