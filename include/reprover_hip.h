@@ -618,6 +618,40 @@ RpStatus rp_decoder_forward(RpDecoder* dec, const void* enc_bf16, const int32_t*
                             double* loss_sum_count, float* logprob_rows, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* Gradients of the teacher-forced seq2seq loss (HF's: the mean of -log p over the counted labels) with respect to the
+ * decoder's parameters and to the encoder output; DESIGN.md section 11.  Arguments and bounds are rp_decoder_forward's;
+ * label_logprobs and loss_sum_count come out as rp_decoder_forward's bits.  Additionally vocab_size must be a multiple
+ * of 64 (RP_E_UNSUPPORTED otherwise).
+ *
+ * Flat gradient buffer (fp32): rp_decoder_grad_layout writes the rp_decoder_grad_tensors(dec) + 1 element offsets
+ * (last = total length incl. padding); every tensor starts at a multiple of 64 elements.  Order, HF shapes:
+ *   shared [V, D] | lm_head [V, D] (absent when the decoder was created with tie_word_embeddings: the head's gradient
+ *   is then added into shared) | rel_bias [buckets, H] | final_ln [D] | per layer: ln_self, q, k, v, o, ln_cross, cq,
+ *   ck, cv, co, ln_ff, wi_0, wi_1, wo
+ *   grads   device fp32 [layout total]: every element of every tensor is overwritten with d loss / d parameter; the
+ *           padding gaps are left untouched
+ *   d_enc   NULL or device fp32 [src_cu[batch], d_model]: d loss / d enc_bf16
+ *           (the layers' cross K | V terms are added one after another in the backward's order, last layer first)
+ * If no label is counted every gradient is 0 and the count comes back as 0.  No floating-point atomic touches device
+ * memory: two calls with the same arguments give the same bits; a pair's d_enc rows times the count do not depend on
+ * the other pairs of the call.
+ * Choices: the transposed bf16 weights of the input-gradient GEMMs are made per call, one at a time, in a workspace
+ * matrix of max(3 H d_kv d_model, 2 d_ff d_model, V d_model) bf16 (no second resident copy of the decoder); the gate /
+ * up pre-activations and the RMSNorm statistics are recomputed, everything else the backward reads is saved.
+ * Workspace, with Tp / Sp the target / source token totals rounded up to 128, I = H d_kv, L layers, all rounded to 256 B:
+ *   (3L+1) Tp D 6 + L (Tp (3I + 3I + F) 2 + Sp 2I 2 + 2 H Tp 4) + Tp V 6 + Tp D 10 + Tp F 16 + Tp 5I 2 + Sp 2I 2
+ *   + H Tp 4 + blocks H (2 max_distance + 1) 4 + transposed weight + Sp D 2 + the cu arrays and work lists
+ * (rp_decoder_loss_grad_workspace_bytes; 0 on bad arguments, rp_last_error says why).  Bad arguments return
+ * RP_E_INVALID / RP_E_UNSUPPORTED / RP_E_WORKSPACE and nothing is launched or written. */
+int32_t  rp_decoder_grad_tensors(const RpDecoder* dec);                  /* 3 (+ 1 untied) + 14 * layers */
+RpStatus rp_decoder_grad_layout(const RpDecoder* dec, int64_t* offsets /* [tensors + 1] */);
+size_t   rp_decoder_loss_grad_workspace_bytes(const RpDecoder* dec, const int32_t* src_cu, const int32_t* tgt_cu,
+                                              int32_t batch);
+RpStatus rp_decoder_loss_grad(RpDecoder* dec, const void* enc_bf16, const int32_t* src_cu, const int32_t* tokens,
+                              const int32_t* labels, const int32_t* tgt_cu, int32_t batch, float* label_logprobs,
+                              double* loss_sum_count, float* grads, float* d_enc, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,14 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
     ),
+    "rp_decoder_grad_tensors": (C.c_int32, [C.c_void_p]),
+    "rp_decoder_grad_layout": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "rp_decoder_loss_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "rp_decoder_loss_grad": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
     "rp_beam_select": (
         C.c_int32,
         [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

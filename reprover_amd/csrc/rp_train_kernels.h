@@ -844,7 +844,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(const bf16_t* __restri
 // dropout variants of the forward's memory-bound kernels (training only)
 // ------------------------------------------------------------------------------------------
 // embed_kernel + dropout on the embeddings (HF:725)
-__global__ __launch_bounds__(256) void embed_train_kernel(const int32_t* __restrict__ ids, const float* __restrict__ table,
+static __global__ __launch_bounds__(256) void embed_train_kernel(const int32_t* __restrict__ ids, const float* __restrict__ table,
                                                           bf16_t* __restrict__ xhi, bf16_t* __restrict__ xlo,
                                                           float* __restrict__ ssp, int np, int T, int Tp, int D, int vocab,
                                                           Drop drop) {
@@ -926,7 +926,7 @@ __global__ __launch_bounds__(256) void pool_partial_train_kernel(const bf16_t* _
 
 // dxm = bf16(mask * dx): the operand of the dgrad / wgrad GEMMs behind a residual-branch dropout (HF:140, 400) - the branch's
 // output gradient is the residual gradient times the branch's mask
-__global__ __launch_bounds__(256) void mask_dx_kernel(const bf16_t* __restrict__ dxhi, const bf16_t* __restrict__ dxlo,
+static __global__ __launch_bounds__(256) void mask_dx_kernel(const bf16_t* __restrict__ dxhi, const bf16_t* __restrict__ dxlo,
                                                       bf16_t* __restrict__ dxm, int rows, int D, Drop drop, uint32_t site) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -951,7 +951,7 @@ __global__ __launch_bounds__(256) void mask_dx_kernel(const bf16_t* __restrict__
 }
 
 // test entry: out[r, c] = 1 if element (site, row0 + r, col0 + c) is kept
-__global__ void dropout_mask_kernel(Drop drop, uint32_t site, uint32_t row0, uint32_t col0, int rows, int cols,
+static __global__ void dropout_mask_kernel(Drop drop, uint32_t site, uint32_t row0, uint32_t col0, int rows, int cols,
                                     uint8_t* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows * cols) return;
@@ -962,7 +962,7 @@ __global__ void dropout_mask_kernel(Drop drop, uint32_t site, uint32_t row0, uin
 // row-wise pieces
 // ------------------------------------------------------------------------------------------
 // rcoef[t] = rs[t]^2 * (sum_p rdp[p][t]) / D, slots summed in index order
-__global__ __launch_bounds__(64) void rowdot_finish_kernel(const float* __restrict__ rdp, int np, int ld,
+static __global__ __launch_bounds__(64) void rowdot_finish_kernel(const float* __restrict__ rdp, int np, int ld,
                                                            const float* __restrict__ rs, float inv_d,
                                                            float* __restrict__ rcoef, int rows) {
   const int t = blockIdx.x * 64 + threadIdx.x;
@@ -983,7 +983,7 @@ __global__ __launch_bounds__(64) void rowdot_finish_kernel(const float* __restri
 
 // qkv projection, behind the attention backward: dzs = rs * dqkv (in place), rcoef = rs^2 * sum_o dqkv_o qkv_o / D.
 // One wave per token row; rows >= T are zeroed (they are K rows of the wgrad that follows).
-__global__ __launch_bounds__(256) void qkv_scale_dot_kernel(bf16_t* __restrict__ dqkv, const bf16_t* __restrict__ qkv,
+static __global__ __launch_bounds__(256) void qkv_scale_dot_kernel(bf16_t* __restrict__ dqkv, const bf16_t* __restrict__ qkv,
                                                             const float* __restrict__ rs, float* __restrict__ rcoef,
                                                             int T, int rows, int width, float inv_d) {
   const int lane = threadIdx.x & 63;
@@ -1022,7 +1022,7 @@ __global__ __launch_bounds__(256) void qkv_scale_dot_kernel(bf16_t* __restrict__
 //                 dwf[b] = dm s / len (final_layer_norm.weight's gradient, summed over b afterwards)
 //   pool_bwd_tok: per token, dx_t = rs_t ds - x_t rs_t^3 (ds . x_t) / D   -> the two planes of the residual gradient
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pool_bwd_seq_kernel(const float* __restrict__ partial, const float* __restrict__ w,
+static __global__ __launch_bounds__(256) void pool_bwd_seq_kernel(const float* __restrict__ partial, const float* __restrict__ w,
                                                            const int32_t* __restrict__ cu, const float* __restrict__ de,
                                                            float* __restrict__ ds, float* __restrict__ dwf, int D) {
   __shared__ float red[2][4];
@@ -1157,7 +1157,7 @@ __global__ __launch_bounds__(256) void pool_bwd_tok_kernel(const bf16_t* __restr
 // grid = (vocab, ceil(D / 256)); the workgroup scans the pass's ids 256 at a time, ballots the matches and walks the set
 // bits in order (uniform control flow).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void embed_bwd_kernel(const int32_t* __restrict__ ids, int T, int vocab,
+static __global__ __launch_bounds__(256) void embed_bwd_kernel(const int32_t* __restrict__ ids, int T, int vocab,
                                                         const bf16_t* __restrict__ dxhi, const bf16_t* __restrict__ dxlo,
                                                         int D, float* __restrict__ dtable, Drop drop) {
   __shared__ unsigned long long masks[4];
@@ -1210,7 +1210,7 @@ struct UnfoldArgs {
 // grid = (ceil(C / 256), ceil(rows / 32)), 256 threads: a 32-row x 256-column tile, wave w takes rows 8 w .. 8 w + 7,
 // a lane 4 consecutive columns (16-byte accesses; every load of a row - the S partials, the master weight - is
 // independent of the others).  The norm-weight gradient's row-block partial is combined over the waves in wave order.
-__global__ __launch_bounds__(256) void unfold_kernel(UnfoldArgs a) {
+static __global__ __launch_bounds__(256) void unfold_kernel(UnfoldArgs a) {
   __shared__ float4 red[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 256 + lane * 4;
@@ -1267,7 +1267,7 @@ __global__ __launch_bounds__(256) void unfold_kernel(UnfoldArgs a) {
 // flight), then the sixteen wave sums pairwise in a fixed tree (deterministic).  Round 6: four waves per workgroup walked 56
 // rows each one load at a time - 9.5 us per launch, 25 launches per step.
 constexpr int COLSUM_WAVES = 16;
-__global__ __launch_bounds__(64 * COLSUM_WAVES) void colsum_kernel(const float* __restrict__ part, int rows, int C,
+static __global__ __launch_bounds__(64 * COLSUM_WAVES) void colsum_kernel(const float* __restrict__ part, int rows, int C,
                                                                    float* __restrict__ out) {
   __shared__ float red[COLSUM_WAVES][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1301,7 +1301,7 @@ __global__ __launch_bounds__(64 * COLSUM_WAVES) void colsum_kernel(const float* 
 
 // relative_attention_bias.weight's gradient: column sums of the workgroups' table rows, then offsets -> buckets
 // (HF:216-262 through `bucket_of`, computed on the host once).  One workgroup per head.
-__global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict__ dtab_part, int nrows, int H, int ntab,
+static __global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict__ dtab_part, int nrows, int H, int ntab,
                                                         const int32_t* __restrict__ bucket_of, int nbuckets,
                                                         float* __restrict__ d_rel_bias /* [buckets, H] */) {
   __shared__ float tabsum[ATT_TAB_MAX];
@@ -1327,7 +1327,7 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict_
 }
 
 // bias table [H, ntab] from relative_attention_bias.weight [buckets, H] (fp32 master), on the device
-__global__ void bias_table_kernel(const float* __restrict__ rel_bias, const int32_t* __restrict__ bucket_of, int H,
+static __global__ void bias_table_kernel(const float* __restrict__ rel_bias, const int32_t* __restrict__ bucket_of, int H,
                                   int ntab, float* __restrict__ tab) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= H * ntab) return;
@@ -1336,7 +1336,7 @@ __global__ void bias_table_kernel(const float* __restrict__ rel_bias, const int3
 }
 
 // bf16 [R, C] -> [C, R] (weight copies for the dgrad GEMMs, once per optimizer step)
-__global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __restrict__ in, int R, int C,
+static __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __restrict__ in, int R, int C,
                                                              bf16_t* __restrict__ out) {
   __shared__ bf16_t tile[64][66];
   const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
@@ -1367,7 +1367,7 @@ struct RepackMat {
 struct RepackArgs {
   RepackMat m[4];
 };
-__global__ __launch_bounds__(256) void repack_layer_kernel(RepackArgs a) {
+static __global__ __launch_bounds__(256) void repack_layer_kernel(RepackArgs a) {
   __shared__ bf16_t tile[64][68];
   int mi = 3;
   while (mi > 0 && (int)blockIdx.x < a.m[mi].tile0) --mi;
@@ -1409,7 +1409,7 @@ __global__ __launch_bounds__(256) void repack_layer_kernel(RepackArgs a) {
 }
 
 // sum of squares of n floats, deterministic: fixed grid of partials, then one workgroup
-__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, size_t n, float* __restrict__ part) {
+static __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, size_t n, float* __restrict__ part) {
   __shared__ float red[4];
   float s = 0.f;
   const size_t n4 = n >> 2;  // 16-byte pieces, four in flight per thread
@@ -1429,7 +1429,7 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-__global__ __launch_bounds__(256) void sumsq_finish_kernel(const float* __restrict__ part, int n, float* __restrict__ out_norm) {
+static __global__ __launch_bounds__(256) void sumsq_finish_kernel(const float* __restrict__ part, int n, float* __restrict__ out_norm) {
   __shared__ float red[256];
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) s += part[i];

@@ -235,6 +235,72 @@ class HipT5Decoder:
         s, c = sc.cpu().tolist()
         return lp, (s, c), out_rows
 
+    def grad_layout(self) -> Tuple[List[str], np.ndarray]:
+        """(HF state-dict names, element offsets [n + 1]) of ``rp_decoder_loss_grad``'s flat fp32 gradient buffer, in
+        buffer order.  A decoder created with the tied head has no ``lm_head.weight`` entry (``shared.weight`` carries
+        both gradients)."""
+        n = int(self._lib.rp_decoder_grad_tensors(self._handle))
+        off = np.zeros(n + 1, dtype=np.int64)
+        _lib.check(self._lib.rp_decoder_grad_layout(self._handle, off.ctypes.data_as(C.c_void_p)), "rp_decoder_grad_layout")
+        L = self.cfg["num_decoder_layers"]
+        names = ["shared.weight"]
+        if n == 4 + 14 * L:
+            names.append("lm_head.weight")
+        names += ["decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", "decoder.final_layer_norm.weight"]
+        for i in range(L):
+            names += [f"decoder.block.{i}.{key}" for key in _DEC_KEYS.values()]
+        assert len(names) == n, (len(names), n)
+        return names, off
+
+    def grad_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """HF shape of every tensor of ``grad_layout``."""
+        c = self.cfg
+        D, F, inner, V = c["d_model"], c["d_ff"], c["num_heads"] * c["d_kv"], c["vocab_size"]
+        sh = {"ln_self": (D,), "q": (inner, D), "k": (inner, D), "v": (inner, D), "o": (D, inner), "ln_cross": (D,),
+              "cq": (inner, D), "ck": (inner, D), "cv": (inner, D), "co": (D, inner), "ln_ff": (D,), "wi_0": (F, D),
+              "wi_1": (F, D), "wo": (D, F)}
+        out = {"shared.weight": (V, D), "lm_head.weight": (V, D), "decoder.final_layer_norm.weight": (D,),
+               "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight":
+                   (c.get("relative_attention_num_buckets", 32), c["num_heads"])}
+        for i in range(c["num_decoder_layers"]):
+            for fld, key in _DEC_KEYS.items():
+                out[f"decoder.block.{i}.{key}"] = sh[fld]
+        return out
+
+    def loss_grad(self, enc_bf16: torch.Tensor, src_cu: np.ndarray, tokens: np.ndarray, labels: np.ndarray,
+                  tgt_cu: np.ndarray, want_d_enc: bool = True, grads: Optional[torch.Tensor] = None):
+        """``rp_decoder_loss_grad`` over packed pairs (arguments as ``forward``).  Returns (label log-probs [sum T_b],
+        (sum of -log p, count), the flat fp32 gradient buffer of ``grad_layout``, d loss / d enc [sum S_b, d_model] fp32
+        or None).  ``grads``: a buffer to write into (its padding gaps are left as they are)."""
+        src_cu = np.ascontiguousarray(src_cu, dtype=np.int32)
+        tgt_cu = np.ascontiguousarray(tgt_cu, dtype=np.int32)
+        B = len(tgt_cu) - 1
+        T, S = int(tgt_cu[-1]), int(src_cu[-1])
+        lib = self._lib
+        pc = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        n = int(lib.rp_decoder_loss_grad_workspace_bytes(self._handle, pc(src_cu), pc(tgt_cu), B))
+        if n == 0:
+            raise _lib.HipLibraryError("rp_decoder_loss_grad: " + lib.rp_last_error().decode(errors="replace"))
+        if getattr(self, "_grad_ws", None) is None or self._grad_ws.numel() < n:
+            self._grad_ws = None
+            self._grad_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
+        tok, lab = dev(tokens), dev(labels)
+        lp = torch.empty(T, dtype=torch.float32, device=self.device)
+        sc = torch.empty(2, dtype=torch.float64, device=self.device)
+        if grads is None:
+            grads = torch.zeros(int(self.grad_layout()[1][-1]), dtype=torch.float32, device=self.device)
+        d_enc = torch.empty((S, self.cfg["d_model"]), dtype=torch.float32, device=self.device) if want_d_enc else None
+        with torch.cuda.device(self.device):
+            _lib.check(lib.rp_decoder_loss_grad(self._handle, enc_bf16.data_ptr() if T else None, pc(src_cu),
+                                                tok.data_ptr() if T else None, lab.data_ptr() if T else None, pc(tgt_cu),
+                                                B, lp.data_ptr() if T else None, sc.data_ptr(), grads.data_ptr(),
+                                                d_enc.data_ptr() if (want_d_enc and S) else None,
+                                                self._grad_ws.data_ptr(), self._grad_ws.numel(), _lib.current_stream()),
+                       "rp_decoder_loss_grad")
+        s, c = sc.cpu().tolist()
+        return lp, (s, c), grads, d_enc
+
     def select(self, log_probs: torch.Tensor, running: torch.Tensor, k: int):
         """Device top-k of log_probs + running[:, None] (``rp_beam_select``): (scores, tokens, parents), each ``[k]``."""
         scores, toks, par = self.select_many(log_probs, running, log_probs.shape[0], k)
@@ -390,7 +456,7 @@ class HipT5Generator:
                        "rp_encode_hidden")
         return out
 
-    def _teacher_forced(self, state_ids, state_mask, tactic_ids, rows: bool = False):
+    def _packed_pairs(self, state_ids, state_mask, tactic_ids):
         ids = np.asarray(state_ids.cpu() if isinstance(state_ids, torch.Tensor) else state_ids).astype(np.int64)
         n_src = source_lengths(state_mask)
         if ids.shape != tuple(state_mask.shape):
@@ -404,6 +470,27 @@ class HipT5Generator:
             raise ValueError("a pair with counted labels has an empty source")
         src_cu = np.concatenate([[0], np.cumsum(n_src)]).astype(np.int32)
         packed = np.concatenate([ids[b, :n] for b, n in enumerate(n_src)]) if len(n_src) else np.zeros(0)
+        return packed, src_cu, tokens, labels, tgt_cu
+
+    def loss_and_grads(self, state_ids, state_mask, tactic_ids):
+        """(loss, gradients, d_enc) of ``forward``'s loss (``rp_decoder_loss_grad``; no dropout).
+        ``gradients`` maps the HF state-dict names of the decoder's parameters (``shared.weight``, ``lm_head.weight``
+        when the head is untied, ``decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight``,
+        ``decoder.final_layer_norm.weight``, ``decoder.block.i.layer...``) to fp32 views of one flat device buffer;
+        ``d_enc`` is d loss / d encoder_last_hidden_state packed ``[sum S_b, d_model]`` fp32.  With no counted label the
+        loss is NaN and every gradient 0."""
+        packed, src_cu, tokens, labels, tgt_cu = self._packed_pairs(state_ids, state_mask, tactic_ids)
+        S = int(src_cu[-1])
+        enc = self.encode_hidden_packed(packed, src_cu) if S else torch.empty((0, self.cfg["d_model"]),
+                                                                              dtype=torch.bfloat16, device=self.device)
+        _, (s, c), flat, d_enc = self.decoder.loss_grad(enc, src_cu, tokens, labels, tgt_cu, want_d_enc=True)
+        names, off = self.decoder.grad_layout()
+        shapes = self.decoder.grad_shapes()
+        grads = {n: flat[int(off[i]) : int(off[i]) + int(np.prod(shapes[n]))].view(shapes[n]) for i, n in enumerate(names)}
+        return (s / c if c else float("nan")), grads, d_enc
+
+    def _teacher_forced(self, state_ids, state_mask, tactic_ids, rows: bool = False):
+        packed, src_cu, tokens, labels, tgt_cu = self._packed_pairs(state_ids, state_mask, tactic_ids)
         enc = self.encode_hidden_packed(packed, src_cu) if int(tgt_cu[-1]) else None
         lp, sc, lp_rows = self.decoder.forward(enc, src_cu, tokens, labels, tgt_cu, rows)
         return lp, tgt_cu, sc, lp_rows

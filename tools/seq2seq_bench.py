@@ -7,6 +7,11 @@ holds attention, norms, the loss and the metadata copy), and the same pairs' per
 (a few pairs and positions only).  Prints one JSON object; --out also writes it.
 
     python tools/seq2seq_bench.py [--batch 64] [--src-bytes 2300] [--tgt 64 512] [--iters 5] [--out FILE]
+
+--grad times the loss with its gradients (rp_decoder_loss_grad) instead: at the same shapes
+rp_decoder_forward and rp_decoder_loss_grad alternate in one process, and the result holds both medians and their ratio.
+
+    python tools/seq2seq_bench.py --grad --out profiles/seq2seq_grad_bench.json
 """
 from __future__ import annotations
 
@@ -46,6 +51,38 @@ def _source(n, seed):
     return np.concatenate([ids, [1]]).astype(np.int32)
 
 
+def _grad_leg(a, gen, enc, src_cu, rng):
+    B, S = a.batch, a.src_bytes
+    result = dict(metric="seq2seq_grad_bench", measured=True, model="byt5-small (synthetic, sharp)", batch=B, source_bytes=S,
+                  targets={})
+    grads = torch.zeros(int(gen.decoder.grad_layout()[1][-1]), dtype=torch.float32, device=enc.device)
+    for T in a.tgt:
+        y = np.concatenate([rng.integers(3, 259, size=(B, T - 1)), np.ones((B, 1), np.int64)], 1)
+        tokens, labels, tgt_cu = shift_and_segment(y)
+        fwd = lambda: gen.decoder.forward(enc, src_cu, tokens, labels, tgt_cu)  # noqa: E731
+        bwd = lambda: gen.decoder.loss_grad(enc, src_cu, tokens, labels, tgt_cu, True, grads)  # noqa: E731
+        fwd(), bwd()
+        torch.cuda.synchronize()
+        ts = {"f": [], "g": []}
+        for _ in range(a.iters):  # alternating: both see the same clocks and the same neighbours
+            for k, fn in (("f", fwd), ("g", bwd)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[k].append(e0.elapsed_time(e1))
+        f_ms, g_ms = float(np.median(ts["f"])), float(np.median(ts["g"]))
+        result["targets"][str(T)] = dict(forward_ms=round(f_ms, 3), loss_grad_ms=round(g_ms, 3),
+                                         ratio=round(g_ms / f_ms, 3), forward_ms_all=[round(x, 3) for x in ts["f"]],
+                                         loss_grad_ms_all=[round(x, 3) for x in ts["g"]])
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -55,6 +92,7 @@ def main():
     ap.add_argument("--step-pairs", type=int, default=2)
     ap.add_argument("--step-tokens", type=int, default=16)
     ap.add_argument("--out")
+    ap.add_argument("--grad", action="store_true", help="time rp_decoder_loss_grad against rp_decoder_forward")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = synth.seq2seq_config("byt5-small")
@@ -67,6 +105,8 @@ def main():
     enc_ms = _time(lambda: gen.encode_hidden_packed(ids, src_cu), a.iters)
     enc = gen.encode_hidden_packed(ids, src_cu)
     rng = np.random.default_rng(0)
+    if a.grad:
+        return _grad_leg(a, gen, enc, src_cu, rng)
     result = dict(model="byt5-small (synthetic, sharp)", batch=B, source_bytes=S, encoder_ms=round(enc_ms, 3), targets={})
     for T in a.tgt:
         y = np.concatenate([rng.integers(3, 259, size=(B, T - 1)), np.ones((B, 1), np.int64)], 1)
