@@ -1,9 +1,9 @@
 // libreprover_hip - gradients of the teacher-forced seq2seq loss with respect to the decoder's parameters and to the
 // encoder output (include/reprover_hip.h): rp_decoder_loss_grad.
 //
-// Forward part: rp_decoder_forward's launches (rp_decoder_forward_kernels.h: the same kernels in the same order with the
-// same arguments), except that every layer's activations go to slots of their own and the residual stream is copied
-// forward before each residual GEMM adds into it, so label_logprobs / loss_sum_count are rp_decoder_forward's bits.
+// Forward part: rp_decoder_forward's launch sequence itself (fwd_launch_layers, rp_decoder_forward_kernels.h), given a
+// buffer view in which every layer's activations have slots of their own; the sequence then copies the residual stream
+// forward before each residual GEMM adds into it.  label_logprobs / loss_sum_count are rp_decoder_forward's bits.
 // Saved per layer: the residual stream at the three sub-layer inputs (fp32), the three normed rows, qkv, the cross q,
 // the cross K | V, both attention outputs with their lse2, and the FFN inner rows.  Recomputed in the backward: the
 // RMSNorm statistic rsqrt(mean x^2 + eps) (from the saved stream, in the row kernel that needs it) and the gate / up
@@ -18,6 +18,8 @@
 // by the shapes, so two runs give the same bits, and d_enc rows of a pair do not depend on the other pairs except through
 // the 1 / count factor of the loss.
 #include <algorithm>
+#include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "rp_decoder_forward_kernels.h"
@@ -28,46 +30,33 @@ extern "C" int32_t rp_relative_position_bucket_causal(int32_t rel, int32_t num_b
 namespace {
 
 // ---- flat gradient layout ------------------------------------------------------------------------------------------------
+enum { G_LN_SELF, G_Q, G_K, G_V, G_O, G_LN_CROSS, G_CQ, G_CK, G_CV, G_CO, G_LN_FF, G_WI0, G_WI1, G_WO, G_PER_LAYER };
 struct GradLayout {
-  std::vector<int64_t> off;  // tensors + 1
-  int per_layer = 14, head = 0;
+  std::vector<int64_t> off;    // tensors + 1: every tensor starts at a multiple of 64 elements
+  std::vector<int64_t> elems;  // tensors: the real (unpadded) element counts
+  int head = 0;
   int64_t shared() const { return off[0]; }
   int64_t lm_head() const { return off[1]; }  // untied only
   int64_t rel_bias() const { return off[1 + head]; }
   int64_t final_ln() const { return off[2 + head]; }
-  int64_t layer(int i, int k) const { return off[3 + head + i * per_layer + k]; }
+  int64_t layer(int i, int k) const { return off[3 + head + i * G_PER_LAYER + k]; }
 };
-enum { G_LN_SELF, G_Q, G_K, G_V, G_O, G_LN_CROSS, G_CQ, G_CK, G_CV, G_CO, G_LN_FF, G_WI0, G_WI1, G_WO };
 GradLayout grad_layout(const RpDecoder* d) {
-  const int64_t D = d->cfg.d_model, F = d->cfg.d_ff, inner = d->inner, V = d->cfg.vocab_size;
+  const int64_t D = d->cfg.d_model, V = d->cfg.vocab_size, ID = (int64_t)d->inner * D, FD = (int64_t)d->cfg.d_ff * D;
+  const int64_t per_layer[G_PER_LAYER] = {D, ID, ID, ID, ID, D, ID, ID, ID, ID, D, FD, FD, FD};  // G_* order
   GradLayout l;
   l.head = d->tied ? 0 : 1;
-  int64_t o = 0;
+  l.off.push_back(0);
   auto add = [&](int64_t n) {
-    l.off.push_back(o);
-    o += (n + 63) / 64 * 64;
+    l.elems.push_back(n);
+    l.off.push_back(l.off.back() + (n + 63) / 64 * 64);
   };
   add(V * D);
   if (!d->tied) add(V * D);
   add((int64_t)d->cfg.rel_num_buckets * d->cfg.num_heads);
   add(D);
-  for (int i = 0; i < d->cfg.num_layers; ++i) {
-    add(D);
-    add(inner * D);
-    add(inner * D);
-    add(inner * D);
-    add(D * inner);
-    add(D);
-    add(inner * D);
-    add(inner * D);
-    add(inner * D);
-    add(D * inner);
-    add(D);
-    add(F * D);
-    add(F * D);
-    add(D * F);
-  }
-  l.off.push_back(o);
+  for (int i = 0; i < d->cfg.num_layers; ++i)
+    for (int64_t n : per_layer) add(n);
   return l;
 }
 
@@ -474,7 +463,17 @@ struct BwdWs {
   float *dx, *dh, *dff, *gu, *delta, *dtab_part;
   bf16_t *dyb, *dlog, *dgu, *datt, *dqkv, *dcq, *dkv, *wt, *encp;
   size_t sz_x, sz_qkv, sz_cq, sz_ckv, sz_ff, sz_lse, dtab_bytes;
+  int L, Tp;
   size_t bytes;
+  // layer i's slots: the stream and the normed rows move on by one slot per sub-layer, so x3 is layer i + 1's x0
+  FwdLayerBufs layer(int i) const {
+    float* x = xs + 3 * (size_t)i * sz_x;
+    bf16_t* h = hs + 3 * (size_t)i * sz_x;
+    const size_t n = i;
+    return {x, x + sz_x, x + 2 * sz_x, x + 3 * sz_x, h, h + sz_x, h + 2 * sz_x, qkv + n * sz_qkv, cq + n * sz_cq,
+            ckv + n * sz_ckv, att_s + n * sz_cq, att_c + n * sz_cq, ff + n * sz_ff, lse_s + n * sz_lse, lse_c + n * sz_lse, Tp};
+  }
+  FwdFinalBufs last() const { return {xs + 3 * (size_t)L * sz_x, hs + 3 * (size_t)L * sz_x, logits}; }
 };
 int bwd_src_work(int batch, int n_src) { return n_src / FA_Q + batch; }
 size_t bwd_max_weight(const RpDecoder* d) {
@@ -486,48 +485,45 @@ BwdWs bwd_carve(const RpDecoder* d, int batch, int n_src, int n_tgt, char* base)
   const size_t L = d->cfg.num_layers;
   const size_t Tp = align_up((size_t)std::max(n_tgt, 1), FWD_BN), Sp = align_up((size_t)std::max(n_src, 1), FWD_BN);
   BwdWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  };
-  w.meta = (int32_t*)take((size_t)(2 * (batch + 1) + 2 * fwd_max_work(batch, n_tgt) + 2 * bwd_src_work(batch, n_src) +
-                                   d->nbias) * 4);
+  Carver c{base};
+  w.L = (int)L;
+  w.Tp = (int)Tp;
+  w.meta = (int32_t*)c.take((size_t)(2 * (batch + 1) + 2 * fwd_max_work(batch, n_tgt) + 2 * bwd_src_work(batch, n_src) +
+                                     d->nbias) * 4);
   w.sz_x = Tp * D;
   w.sz_qkv = Tp * 3 * inner;
   w.sz_cq = Tp * inner;
   w.sz_ckv = Sp * 2 * inner;
   w.sz_ff = Tp * F;
   w.sz_lse = H * Tp;
-  w.xs = (float*)take((3 * L + 1) * w.sz_x * 4);
-  w.hs = (bf16_t*)take((3 * L + 1) * w.sz_x * 2);
-  w.qkv = (bf16_t*)take(L * w.sz_qkv * 2);
-  w.cq = (bf16_t*)take(L * w.sz_cq * 2);
-  w.ckv = (bf16_t*)take(L * w.sz_ckv * 2);
-  w.att_s = (bf16_t*)take(L * w.sz_cq * 2);
-  w.att_c = (bf16_t*)take(L * w.sz_cq * 2);
-  w.ff = (bf16_t*)take(L * w.sz_ff * 2);
-  w.lse_s = (float*)take(L * w.sz_lse * 4);
-  w.lse_c = (float*)take(L * w.sz_lse * 4);
-  w.logits = (float*)take(Tp * V * 4);
-  w.dx = (float*)take(Tp * D * 4);
-  w.dh = (float*)take(Tp * D * 4);
-  w.dyb = (bf16_t*)take(Tp * D * 2);
-  w.dlog = (bf16_t*)take(Tp * V * 2);
-  w.dff = (float*)take(Tp * F * 4);
-  w.gu = (float*)take(Tp * 2 * F * 4);
-  w.dgu = (bf16_t*)take(Tp * 2 * F * 2);
-  w.datt = (bf16_t*)take(Tp * inner * 2);
-  w.dqkv = (bf16_t*)take(Tp * 3 * inner * 2);
-  w.dcq = (bf16_t*)take(Tp * inner * 2);
-  w.dkv = (bf16_t*)take(Sp * 2 * inner * 2);
-  w.delta = (float*)take(H * Tp * 4);
+  w.xs = (float*)c.take((3 * L + 1) * w.sz_x * 4);
+  w.hs = (bf16_t*)c.take((3 * L + 1) * w.sz_x * 2);
+  w.qkv = (bf16_t*)c.take(L * w.sz_qkv * 2);
+  w.cq = (bf16_t*)c.take(L * w.sz_cq * 2);
+  w.ckv = (bf16_t*)c.take(L * w.sz_ckv * 2);
+  w.att_s = (bf16_t*)c.take(L * w.sz_cq * 2);
+  w.att_c = (bf16_t*)c.take(L * w.sz_cq * 2);
+  w.ff = (bf16_t*)c.take(L * w.sz_ff * 2);
+  w.lse_s = (float*)c.take(L * w.sz_lse * 4);
+  w.lse_c = (float*)c.take(L * w.sz_lse * 4);
+  w.logits = (float*)c.take(Tp * V * 4);
+  w.dx = (float*)c.take(Tp * D * 4);
+  w.dh = (float*)c.take(Tp * D * 4);
+  w.dyb = (bf16_t*)c.take(Tp * D * 2);
+  w.dlog = (bf16_t*)c.take(Tp * V * 2);
+  w.dff = (float*)c.take(Tp * F * 4);
+  w.gu = (float*)c.take(Tp * 2 * F * 4);
+  w.dgu = (bf16_t*)c.take(Tp * 2 * F * 2);
+  w.datt = (bf16_t*)c.take(Tp * inner * 2);
+  w.dqkv = (bf16_t*)c.take(Tp * 3 * inner * 2);
+  w.dcq = (bf16_t*)c.take(Tp * inner * 2);
+  w.dkv = (bf16_t*)c.take(Sp * 2 * inner * 2);
+  w.delta = (float*)c.take(H * Tp * 4);
   w.dtab_bytes = (size_t)fwd_max_work(batch, n_tgt) * H * d->nbias * 4;
-  w.dtab_part = (float*)take(w.dtab_bytes);
-  w.wt = (bf16_t*)take(bwd_max_weight(d) * 2);
-  w.encp = (bf16_t*)take(Sp * D * 2);
-  w.bytes = off;
+  w.dtab_part = (float*)c.take(w.dtab_bytes);
+  w.wt = (bf16_t*)c.take(bwd_max_weight(d) * 2);
+  w.encp = (bf16_t*)c.take(Sp * D * 2);
+  w.bytes = c.off;
   return w;
 }
 
@@ -539,30 +535,42 @@ RpStatus bwd_check_model(const RpDecoder* d) {
   return RP_OK;
 }
 
-using WgCfg = WgradCfg<128, 128, 2, 2, 2>;
-// dW[ny, nx] (fp32, row pitch nx) = Y[:rows_pad, :ny]^T X[:rows_pad, :nx]: one split, so K runs in ascending token order
-RpStatus bwd_wgrad(const bf16_t* Y, int ldy, int ny, const bf16_t* X, int ldx, int nx, int rows_pad, float* out,
-                   hipStream_t s) {
-  auto kern = wgrad_kernel<WgCfg>;
-  static LdsAttrOnce attr;
-  RP_HIP(attr.ensure((const void*)kern, WgCfg::LDS_BYTES));
-  const WgradProblem p{Y, ldy, ny, X, ldx, nx, (ny + WgCfg::BM - 1) / WgCfg::BM, (nx + WgCfg::BN - 1) / WgCfg::BN, out,
-                       nx, (size_t)ny * nx, WgradFinish{}};
-  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(WgCfg::THREADS), WgCfg::LDS_BYTES, s, p, WgradProblem{},
-                     p.tiles_m * p.tiles_n, rows_pad / 64, 1);
-  RP_CHECK_LAUNCH();
-  return RP_OK;
+// f(std::true_type) or f(std::false_type): the one place a run-time flag picks a template's ADD argument
+template <class F>
+auto with_bool(bool b, F f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
 }
-// out [C, R] = W [R, C]^T in the call's scratch matrix
-void bwd_transpose(const bf16_t* W, int R, int C, bf16_t* out, hipStream_t s) {
-  hipLaunchKernelGGL(transpose_bf16_kernel, dim3((C + 63) / 64, (R + 63) / 64), dim3(256), 0, s, W, R, C, out);
+
+// Backward of a projection  y = x W^T,  W [R, C] bf16, over n token rows (n_pad: rounded up to 128, the padding rows of dY
+// and X zero).  First one weight-gradient launch per slice of W's rows, in the order given: dW[row0 : row0 + rows] =
+// dY[:, row0 : row0 + rows]^T X  (wgrad_kernel, one split: K runs in ascending token order).  Then dX = dY W on the
+// forward's GEMM core: W is transposed into the scratch matrix wt immediately before the GEMM that reads it (every call
+// shares wt).
+struct WgradSlice {
+  int row0, rows;
+  float* dW;
+};
+enum DxKind { DX_NONE, DX_F32, DX_F32_ADD, DX_BF16 };
+RpStatus linear_bwd(const bf16_t* dY, const bf16_t* X, int n, int n_pad, const bf16_t* W, int R, int C,
+                    std::initializer_list<WgradSlice> slices, DxKind kind, void* dX, bf16_t* wt, hipStream_t s) {
+  RpStatus st;
+  for (const WgradSlice& sl : slices)
+    if ((st = launch_wgrad_cfg<WgradCfg<128, 128, 2, 2, 2>>(WgradOperands{dY + sl.row0, R, sl.rows, X, C, C, sl.dW}, nullptr,
+                                                           n_pad / 64, 1, s)))
+      return st;
+  if (kind == DX_NONE) return RP_OK;
+  hipLaunchKernelGGL(transpose_bf16_kernel, dim3((C + 63) / 64, (R + 63) / 64), dim3(256), 0, s, W, R, C, wt);
+  if (kind == DX_BF16) return fwd_gemm(dY, n, n_pad, wt, C, R, EpiDecBf16{(bf16_t*)dX, C, C, n}, s, RP_K_GEMM_O);
+  return with_bool(kind == DX_F32_ADD, [&](auto add) {
+    return fwd_gemm(dY, n, n_pad, wt, C, R, EpiDecF32<decltype(add)::value>{(float*)dX, C, C, n}, s, RP_K_GEMM_O);
+  });
 }
 
 }  // namespace
 
 extern "C" int32_t rp_decoder_grad_tensors(const RpDecoder* d) {
   if (!d) return 0;
-  return 3 + (d->tied ? 0 : 1) + 14 * d->cfg.num_layers;
+  return (int32_t)grad_layout(d).off.size() - 1;
 }
 
 extern "C" RpStatus rp_decoder_grad_layout(const RpDecoder* d, int64_t* offsets) {
@@ -597,38 +605,18 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
   const float eps = c.layer_norm_eps;
   const GradLayout lay = grad_layout(d);
-  const int n_tensors = (int)lay.off.size() - 1;
-  auto tensor_elems = [&](int k) -> size_t {  // real (unpadded) element count of tensor k
-    const size_t VD = (size_t)V * D, ID = (size_t)inner * D, FD = (size_t)F * D;
-    if (k == 0 || (k == 1 && lay.head)) return VD;
-    k -= 1 + lay.head;
-    if (k == 0) return (size_t)c.rel_num_buckets * H;
-    if (k == 1) return D;
-    switch ((k - 2) % 14) {
-      case G_LN_SELF: case G_LN_CROSS: case G_LN_FF: return D;
-      case G_WI0: case G_WI1: case G_WO: return FD;
-      default: return ID;
-    }
-  };
   if (d_enc && n_src) RP_HIP(hipMemsetAsync(d_enc, 0, (size_t)n_src * D * 4, s));
   if (n_tgt == 0) {  // no label at all: the loss is 0 / 0, every gradient 0
     const double zero[2] = {0.0, 0.0};
     RP_HIP(hipMemcpyWithStream(loss_sum_count, zero, sizeof zero, hipMemcpyHostToDevice, s));
-    for (int k = 0; k < n_tensors; ++k) RP_HIP(hipMemsetAsync(grads + lay.off[k], 0, tensor_elems(k) * 4, s));
+    for (size_t k = 0; k < lay.elems.size(); ++k) RP_HIP(hipMemsetAsync(grads + lay.off[k], 0, (size_t)lay.elems[k] * 4, s));
     return RP_OK;
   }
 
-  // metadata: the forward's (cu arrays, 128-query blocks of non-empty targets), then the 128-key blocks of the sources of
-  // non-empty targets (the cross dK | dV pass) and the bucket of every bias distance
-  std::vector<int32_t> meta(2 * (batch + 1));
-  std::copy(src_cu, src_cu + batch + 1, meta.begin());
-  std::copy(tgt_cu, tgt_cu + batch + 1, meta.begin() + batch + 1);
-  for (int b = 0; b < batch; ++b)
-    for (int q0 = 0; q0 < tgt_cu[b + 1] - tgt_cu[b]; q0 += FA_Q) {
-      meta.push_back(b);
-      meta.push_back(q0);
-    }
-  const int n_work = (int)(meta.size() - 2 * (batch + 1)) / 2;
+  // metadata: the forward's, then the 128-key blocks of the sources of non-empty targets (the cross dK | dV pass) and the
+  // bucket of every bias distance
+  std::vector<int32_t> meta;
+  const int n_work = fwd_build_meta(src_cu, tgt_cu, batch, meta);
   const size_t kwork_at = meta.size();
   for (int b = 0; b < batch; ++b) {
     if (tgt_cu[b + 1] == tgt_cu[b]) continue;
@@ -647,17 +635,20 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   const int2* d_kwork = reinterpret_cast<const int2*>(w.meta + kwork_at);
   const int32_t* d_bucket = w.meta + bucket_at;
 
-  const int Tp = (int)align_up(n_tgt, FWD_BN), Sp = (int)align_up(n_src, FWD_BN);
+  const int Tp = w.Tp, Sp = (int)align_up(n_src, FWD_BN);
+  std::vector<FwdLayerBufs> bufs(L);
+  for (int i = 0; i < L; ++i) bufs[i] = w.layer(i);
+  const FwdFinalBufs fin = w.last();
   // the wgrad GEMM reads whole 64-row tiles of both operands: their padding rows are zeroed once (no kernel writes them;
   // the cast / dlogits / geglu row kernels write their own); the source rows of pairs with an empty target keep dK | dV = 0
   auto zero_tail = [&](void* p, size_t rows, size_t rows_pad, size_t row_bytes) {
     return rows_pad > rows ? hipMemsetAsync((char*)p + rows * row_bytes, 0, (rows_pad - rows) * row_bytes, s) : hipSuccess;
   };
   for (int i = 0; i <= 3 * L; ++i) RP_HIP(zero_tail(w.hs + (size_t)i * w.sz_x, n_tgt, Tp, (size_t)D * 2));
-  for (int i = 0; i < L; ++i) {
-    RP_HIP(zero_tail(w.att_s + (size_t)i * w.sz_cq, n_tgt, Tp, (size_t)inner * 2));
-    RP_HIP(zero_tail(w.att_c + (size_t)i * w.sz_cq, n_tgt, Tp, (size_t)inner * 2));
-    RP_HIP(zero_tail(w.ff + (size_t)i * w.sz_ff, n_tgt, Tp, (size_t)F * 2));
+  for (const FwdLayerBufs& b : bufs) {
+    RP_HIP(zero_tail(b.att_s, n_tgt, Tp, (size_t)inner * 2));
+    RP_HIP(zero_tail(b.att_c, n_tgt, Tp, (size_t)inner * 2));
+    RP_HIP(zero_tail(b.ff, n_tgt, Tp, (size_t)F * 2));
   }
   RP_HIP(zero_tail(w.dqkv, n_tgt, Tp, (size_t)3 * inner * 2));
   RP_HIP(zero_tail(w.dcq, n_tgt, Tp, (size_t)inner * 2));
@@ -666,68 +657,20 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   RP_HIP(hipMemcpyAsync(w.encp, enc_bf16, (size_t)n_src * D * 2, hipMemcpyDeviceToDevice, s));
   RP_HIP(zero_tail(w.encp, n_src, Sp, (size_t)D * 2));
 
-  // ---- forward: rp_decoder_forward's launches on per-layer slots ------------------------------------------------------------
-  const dim3 att_grid(H * n_work);
-  auto xs = [&](int i) { return w.xs + (size_t)i * w.sz_x; };
-  auto hs = [&](int i) { return w.hs + (size_t)i * w.sz_x; };
-  auto next_x = [&](int i) {  // the stream moves on to slot i + 1: the residual GEMM adds into the copy
-    return hipMemcpyAsync(xs(i + 1), xs(i), (size_t)n_tgt * D * 4, hipMemcpyDeviceToDevice, s);
-  };
-  hipLaunchKernelGGL(dec_embed_kernel, dim3(n_tgt), dim3(256), 0, s, tokens, d->embed, xs(0), D, V);
-  for (int i = 0; i < L; ++i) {
-    const RpDecoder::Layer& l = d->layers[i];
-    bf16_t* qkv = w.qkv + (size_t)i * w.sz_qkv;
-    bf16_t* cq = w.cq + (size_t)i * w.sz_cq;
-    bf16_t* ckv = w.ckv + (size_t)i * w.sz_ckv;
-    bf16_t* att_s = w.att_s + (size_t)i * w.sz_cq;
-    bf16_t* att_c = w.att_c + (size_t)i * w.sz_cq;
-    bf16_t* ff = w.ff + (size_t)i * w.sz_ff;
-    float* lse_s = w.lse_s + (size_t)i * w.sz_lse;
-    float* lse_c = w.lse_c + (size_t)i * w.sz_lse;
-    const int k = 3 * i;
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(n_tgt), dim3(256), 0, s, xs(k), l.ln_self, hs(k), D, eps, 1.f);
-    if ((st = fwd_gemm(hs(k), n_tgt, Tp, l.wqkv, 3 * inner, D, EpiDecBf16{qkv, 3 * inner, 3 * inner, n_tgt}, s, RP_K_GEMM_QKV)))
-      return st;
-    hipLaunchKernelGGL(dec_flash_kernel<true>, att_grid, dim3(256), 0, s, qkv, 3 * inner, qkv, 3 * inner, inner, 2 * inner,
-                       d_tgt_cu, d_tgt_cu, d_work, d->bias_tab, d->nbias, att_s, inner, lse_s, Tp);
-    RP_HIP(next_x(k));
-    if ((st = fwd_gemm(att_s, n_tgt, Tp, l.wo, D, inner, EpiDecF32<true>{xs(k + 1), D, D, n_tgt}, s, RP_K_GEMM_O))) return st;
-    if ((st = fwd_gemm((const bf16_t*)enc_bf16, n_src, Sp, d->cross_kv_w + (size_t)2 * i * inner * D, 2 * inner, D,
-                       EpiDecBf16{ckv, 2 * inner, 2 * inner, n_src}, s, RP_K_GEMM_QKV)))
-      return st;
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(n_tgt), dim3(256), 0, s, xs(k + 1), l.ln_cross, hs(k + 1), D, eps, 1.f);
-    if ((st = fwd_gemm(hs(k + 1), n_tgt, Tp, l.cq, inner, D, EpiDecBf16{cq, inner, inner, n_tgt}, s, RP_K_GEMM_QKV))) return st;
-    hipLaunchKernelGGL(dec_flash_kernel<false>, att_grid, dim3(256), 0, s, cq, inner, ckv, 2 * inner, 0, inner, d_tgt_cu,
-                       d_src_cu, d_work, (const float*)nullptr, 1, att_c, inner, lse_c, Tp);
-    RP_HIP(next_x(k + 1));
-    if ((st = fwd_gemm(att_c, n_tgt, Tp, l.co, D, inner, EpiDecF32<true>{xs(k + 2), D, D, n_tgt}, s, RP_K_GEMM_O))) return st;
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(n_tgt), dim3(256), 0, s, xs(k + 2), l.ln_ff, hs(k + 2), D, eps, 1.f);
-    if ((st = fwd_gemm(hs(k + 2), n_tgt, Tp, d->wi_il + (size_t)i * 2 * F * D, 2 * F, D, EpiDecGeglu{ff, F, F, n_tgt}, s,
-                       RP_K_GEMM_WI)))
-      return st;
-    RP_HIP(next_x(k + 2));
-    if ((st = fwd_gemm(ff, n_tgt, Tp, l.wo2, D, F, EpiDecF32<true>{xs(k + 3), D, D, n_tgt}, s, RP_K_GEMM_WO))) return st;
-  }
-  const float scale = d->tied ? 1.f / sqrtf((float)D) : 1.f;
-  hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(n_tgt), dim3(256), 0, s, xs(3 * L), d->final_ln, hs(3 * L), D, eps, scale);
-  if ((st = fwd_gemm(hs(3 * L), n_tgt, Tp, d->lm_head, V, D, EpiDecF32<false>{w.logits, V, V, n_tgt}, s, RP_K_GEMM_O))) return st;
-  hipLaunchKernelGGL(fwd_loss_row_kernel, dim3(n_tgt), dim3(256), 0, s, w.logits, V, labels, label_logprobs, (float*)nullptr);
-  hipLaunchKernelGGL(fwd_loss_reduce_kernel, dim3(1), dim3(256), 0, s, label_logprobs, labels, n_tgt, V, loss_sum_count);
-  RP_CHECK_LAUNCH();
+  // ---- forward: the shared sequence on the per-layer slots ----------------------------------------------------------------
+  if ((st = fwd_launch_layers(d, enc_bf16, tokens, labels, batch, n_src, n_tgt, w.meta, n_work, bufs.data(), fin,
+                              label_logprobs, loss_sum_count, nullptr, s)))
+    return st;
 
   // ---- backward --------------------------------------------------------------------------------------------------------------
   auto G = [&](int64_t off) { return grads + off; };
-  // dX = dY W into an fp32 buffer: the forward's GEMM core on W^T
-  auto dgrad_f32 = [&](const bf16_t* dy, int n, int n_pad, const bf16_t* W, int R, int C, float* out, bool add) -> RpStatus {
-    bwd_transpose(W, R, C, w.wt, s);
-    if (add) return fwd_gemm(dy, n, n_pad, w.wt, C, R, EpiDecF32<true>{out, C, C, n}, s, RP_K_GEMM_O);
-    return fwd_gemm(dy, n, n_pad, w.wt, C, R, EpiDecF32<false>{out, C, C, n}, s, RP_K_GEMM_O);
-  };
-  auto norm_bwd = [&](int slot, const float* ln, float sc, bool add, float* dln) {
-    if (add)
-      hipLaunchKernelGGL(bwd_rmsnorm_kernel<true>, dim3(n_tgt), dim3(256), 0, s, xs(slot), ln, w.dh, w.dx, D, eps, sc);
-    else
-      hipLaunchKernelGGL(bwd_rmsnorm_kernel<false>, dim3(n_tgt), dim3(256), 0, s, xs(slot), ln, w.dh, w.dx, D, eps, sc);
+  auto lin = [&](const bf16_t* dY, const bf16_t* X, const bf16_t* W, int R, int C, std::initializer_list<WgradSlice> slices,
+                 DxKind kind, void* dX) { return linear_bwd(dY, X, n_tgt, Tp, W, R, C, slices, kind, dX, w.wt, s); };
+  // w.dh -> w.dx through the norm whose input rows were x; the rows' terms of d ln are summed into dln
+  auto norm_bwd = [&](const float* x, const float* ln, float sc, bool add, float* dln) {
+    with_bool(add, [&](auto a) {
+      hipLaunchKernelGGL(bwd_rmsnorm_kernel<decltype(a)::value>, dim3(n_tgt), dim3(256), 0, s, x, ln, w.dh, w.dx, D, eps, sc);
+    });
     hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, s, (const float*)w.dh, n_tgt, D, dln);
   };
   auto cast_dx = [&]() { hipLaunchKernelGGL(bwd_cast_kernel, dim3(Tp), dim3(256), 0, s, (const float*)w.dx, w.dyb, D, n_tgt); };
@@ -735,11 +678,11 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   // loss and head
   hipLaunchKernelGGL(bwd_dlogits_kernel, dim3(Tp), dim3(256), 0, s, (const float*)w.logits, V, n_tgt, labels,
                      (const double*)loss_sum_count, w.dlog);
-  float* g_head = G(d->tied ? lay.shared() : lay.lm_head());
-  if ((st = bwd_wgrad(w.dlog, V, V, hs(3 * L), D, D, Tp, g_head, s))) return st;
-  if ((st = dgrad_f32(w.dlog, n_tgt, Tp, d->lm_head, V, D, w.dh, false))) return st;
-  norm_bwd(3 * L, d->final_ln, scale, false, G(lay.final_ln()));
+  if ((st = lin(w.dlog, fin.h, d->lm_head, V, D, {{0, V, G(d->tied ? lay.shared() : lay.lm_head())}}, DX_F32, w.dh)))
+    return st;
+  norm_bwd(fin.x, d->final_ln, fwd_head_scale(d), false, G(lay.final_ln()));
 
+  const dim3 att_grid(H * n_work);
   FlashBwdArgs fa{};
   fa.q_cu = d_tgt_cu;
   fa.bias_tab = d->bias_tab;
@@ -750,80 +693,66 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   fa.dtab_part = w.dtab_part;
   for (int i = L - 1; i >= 0; --i) {
     const RpDecoder::Layer& l = d->layers[i];
-    const int k = 3 * i;
-    bf16_t* qkv = w.qkv + (size_t)i * w.sz_qkv;
-    bf16_t* cq = w.cq + (size_t)i * w.sz_cq;
-    bf16_t* ckv = w.ckv + (size_t)i * w.sz_ckv;
-    bf16_t* att_s = w.att_s + (size_t)i * w.sz_cq;
-    bf16_t* att_c = w.att_c + (size_t)i * w.sz_cq;
-    bf16_t* ff = w.ff + (size_t)i * w.sz_ff;
-    const bf16_t* ckv_w = d->cross_kv_w + (size_t)2 * i * inner * D;
+    const FwdLayerBufs& b = bufs[i];
+    auto Gl = [&](int k) { return G(lay.layer(i, k)); };
     // gated-GELU FFN
     cast_dx();
-    if ((st = bwd_wgrad(w.dyb, D, D, ff, F, F, Tp, G(lay.layer(i, G_WO)), s))) return st;
-    if ((st = dgrad_f32(w.dyb, n_tgt, Tp, l.wo2, D, F, w.dff, false))) return st;
-    if ((st = fwd_gemm(hs(k + 2), n_tgt, Tp, d->wi_il + (size_t)i * 2 * F * D, 2 * F, D,
-                       EpiDecF32<false>{w.gu, 2 * F, 2 * F, n_tgt}, s, RP_K_GEMM_WI)))
+    if ((st = lin(w.dyb, b.ff, l.wo2, D, F, {{0, D, Gl(G_WO)}}, DX_F32, w.dff))) return st;
+    if ((st = fwd_gemm(b.h2, n_tgt, Tp, d->wi_il + (size_t)i * 2 * F * D, 2 * F, D, EpiDecF32<false>{w.gu, 2 * F, 2 * F, n_tgt},
+                       s, RP_K_GEMM_WI)))
       return st;
     hipLaunchKernelGGL(bwd_geglu_kernel, dim3(Tp), dim3(256), 0, s, (const float*)w.gu, (const float*)w.dff, w.dgu, F, n_tgt);
-    if ((st = bwd_wgrad(w.dgu, 2 * F, F, hs(k + 2), D, D, Tp, G(lay.layer(i, G_WI0)), s))) return st;
-    if ((st = bwd_wgrad(w.dgu + F, 2 * F, F, hs(k + 2), D, D, Tp, G(lay.layer(i, G_WI1)), s))) return st;
-    if ((st = dgrad_f32(w.dgu, n_tgt, Tp, l.wi, 2 * F, D, w.dh, false))) return st;
-    norm_bwd(k + 2, l.ln_ff, 1.f, true, G(lay.layer(i, G_LN_FF)));
+    if ((st = lin(w.dgu, b.h2, l.wi, 2 * F, D, {{0, F, Gl(G_WI0)}, {F, F, Gl(G_WI1)}}, DX_F32, w.dh))) return st;
+    norm_bwd(b.x2, l.ln_ff, 1.f, true, Gl(G_LN_FF));
 
     // cross-attention
     cast_dx();
-    if ((st = bwd_wgrad(w.dyb, D, D, att_c, inner, inner, Tp, G(lay.layer(i, G_CO)), s))) return st;
-    bwd_transpose(l.co, D, inner, w.wt, s);
-    if ((st = fwd_gemm(w.dyb, n_tgt, Tp, w.wt, inner, D, EpiDecBf16{w.datt, inner, inner, n_tgt}, s, RP_K_GEMM_O))) return st;
-    fa.q = cq; fa.ldq = inner;
-    fa.kv = ckv; fa.ldkv = 2 * inner; fa.koff = 0; fa.voff = inner;
+    if ((st = lin(w.dyb, b.att_c, l.co, D, inner, {{0, D, Gl(G_CO)}}, DX_BF16, w.datt))) return st;
+    fa.q = b.cq; fa.ldq = inner;
+    fa.kv = b.ckv; fa.ldkv = 2 * inner; fa.koff = 0; fa.voff = inner;
     fa.k_cu = d_src_cu;
-    fa.o = att_c; fa.d_o = w.datt;
-    fa.lse2 = w.lse_c + (size_t)i * w.sz_lse;
+    fa.o = b.att_c; fa.d_o = w.datt;
+    fa.lse2 = b.lse_c;
     fa.dq = w.dcq; fa.lddq = inner;
     fa.dkv = w.dkv; fa.lddkv = 2 * inner; fa.dkoff = 0; fa.dvoff = inner;
     fa.work = d_work;
     hipLaunchKernelGGL((dec_flash_bwd_kernel<0, false>), att_grid, dim3(256), 0, s, fa);
     fa.work = d_kwork;
     if (n_kwork) hipLaunchKernelGGL((dec_flash_bwd_kernel<1, false>), dim3(H * n_kwork), dim3(256), 0, s, fa);
-    if ((st = bwd_wgrad(w.dcq, inner, inner, hs(k + 1), D, D, Tp, G(lay.layer(i, G_CQ)), s))) return st;
-    if ((st = bwd_wgrad(w.dkv, 2 * inner, inner, w.encp, D, D, Sp, G(lay.layer(i, G_CK)), s))) return st;
-    if ((st = bwd_wgrad(w.dkv + inner, 2 * inner, inner, w.encp, D, D, Sp, G(lay.layer(i, G_CV)), s))) return st;
-    if (d_enc && (st = dgrad_f32(w.dkv, n_src, Sp, ckv_w, 2 * inner, D, d_enc, true))) return st;
-    if ((st = dgrad_f32(w.dcq, n_tgt, Tp, l.cq, inner, D, w.dh, false))) return st;
-    norm_bwd(k + 1, l.ln_cross, 1.f, true, G(lay.layer(i, G_LN_CROSS)));
+    // the launch order of the two cross projections is kept: all three weight gradients, the K | V projection's dX (over
+    // the source rows, added into d_enc), then the q projection's dX
+    if ((st = lin(w.dcq, b.h1, l.cq, inner, D, {{0, inner, Gl(G_CQ)}}, DX_NONE, nullptr))) return st;
+    if ((st = linear_bwd(w.dkv, w.encp, n_src, Sp, d->cross_kv_w + (size_t)2 * i * inner * D, 2 * inner, D,
+                         {{0, inner, Gl(G_CK)}, {inner, inner, Gl(G_CV)}}, d_enc ? DX_F32_ADD : DX_NONE, d_enc, w.wt, s)))
+      return st;
+    if ((st = lin(w.dcq, b.h1, l.cq, inner, D, {}, DX_F32, w.dh))) return st;
+    norm_bwd(b.x1, l.ln_cross, 1.f, true, Gl(G_LN_CROSS));
 
     // self-attention
     cast_dx();
-    if ((st = bwd_wgrad(w.dyb, D, D, att_s, inner, inner, Tp, G(lay.layer(i, G_O)), s))) return st;
-    bwd_transpose(l.wo, D, inner, w.wt, s);
-    if ((st = fwd_gemm(w.dyb, n_tgt, Tp, w.wt, inner, D, EpiDecBf16{w.datt, inner, inner, n_tgt}, s, RP_K_GEMM_O))) return st;
-    fa.q = qkv; fa.ldq = 3 * inner;
-    fa.kv = qkv; fa.ldkv = 3 * inner; fa.koff = inner; fa.voff = 2 * inner;
+    if ((st = lin(w.dyb, b.att_s, l.wo, D, inner, {{0, D, Gl(G_O)}}, DX_BF16, w.datt))) return st;
+    fa.q = b.qkv; fa.ldq = 3 * inner;
+    fa.kv = b.qkv; fa.ldkv = 3 * inner; fa.koff = inner; fa.voff = 2 * inner;
     fa.k_cu = d_tgt_cu;
-    fa.o = att_s; fa.d_o = w.datt;
-    fa.lse2 = w.lse_s + (size_t)i * w.sz_lse;
+    fa.o = b.att_s; fa.d_o = w.datt;
+    fa.lse2 = b.lse_s;
     fa.dq = w.dqkv; fa.lddq = 3 * inner;
     fa.dkv = w.dqkv; fa.lddkv = 3 * inner; fa.dkoff = inner; fa.dvoff = 2 * inner;
     fa.work = d_work;
     hipLaunchKernelGGL((dec_flash_bwd_kernel<0, true>), att_grid, dim3(256), 0, s, fa);
     hipLaunchKernelGGL((dec_flash_bwd_kernel<1, true>), att_grid, dim3(256), 0, s, fa);
-    if ((st = bwd_wgrad(w.dqkv, 3 * inner, inner, hs(k), D, D, Tp, G(lay.layer(i, G_Q)), s))) return st;
-    if ((st = bwd_wgrad(w.dqkv + inner, 3 * inner, inner, hs(k), D, D, Tp, G(lay.layer(i, G_K)), s))) return st;
-    if ((st = bwd_wgrad(w.dqkv + 2 * inner, 3 * inner, inner, hs(k), D, D, Tp, G(lay.layer(i, G_V)), s))) return st;
-    if ((st = dgrad_f32(w.dqkv, n_tgt, Tp, l.wqkv, 3 * inner, D, w.dh, false))) return st;
-    norm_bwd(k, l.ln_self, 1.f, true, G(lay.layer(i, G_LN_SELF)));
+    if ((st = lin(w.dqkv, b.h0, l.wqkv, 3 * inner, D,
+                  {{0, inner, Gl(G_Q)}, {inner, inner, Gl(G_K)}, {2 * inner, inner, Gl(G_V)}}, DX_F32, w.dh)))
+      return st;
+    norm_bwd(b.x0, l.ln_self, 1.f, true, Gl(G_LN_SELF));
   }
   // the shared bias table (every layer added into the same partial rows) and the embedding
   hipLaunchKernelGGL(bias_grad_kernel, dim3(H), dim3(256), 0, s, (const float*)w.dtab_part, n_work, H, d->nbias, d_bucket,
                      c.rel_num_buckets, G(lay.rel_bias()));
-  if (d->tied)
-    hipLaunchKernelGGL(bwd_embed_kernel<true>, dim3(V, (D + 255) / 256), dim3(256), 0, s, tokens, n_tgt, V,
+  with_bool(d->tied, [&](auto add) {  // tied: the head's weight gradient is already there
+    hipLaunchKernelGGL(bwd_embed_kernel<decltype(add)::value>, dim3(V, (D + 255) / 256), dim3(256), 0, s, tokens, n_tgt, V,
                        (const float*)w.dx, D, G(lay.shared()));
-  else
-    hipLaunchKernelGGL(bwd_embed_kernel<false>, dim3(V, (D + 255) / 256), dim3(256), 0, s, tokens, n_tgt, V,
-                       (const float*)w.dx, D, G(lay.shared()));
+  });
   RP_CHECK_LAUNCH();
   return RP_OK;
 }

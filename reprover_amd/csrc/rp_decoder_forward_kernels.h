@@ -1,5 +1,6 @@
-// Device code and host helpers of the teacher-forced decoder forward, shared by rp_decoder_forward.hip (the loss) and
-// rp_decoder_backward.hip (the loss and its gradients, which re-run the same launches with per-layer activation slots).
+// Device code and host helpers of the teacher-forced decoder forward.  fwd_launch_layers below is the one launch sequence;
+// rp_decoder_forward.hip (the loss) runs it on one buffer per kind, rp_decoder_backward.hip (the loss and its gradients)
+// on per-layer activation slots: two fillings of FwdLayerBufs, the same launches.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -360,6 +361,18 @@ __global__ __launch_bounds__(256) void fwd_loss_reduce_kernel(const float* __res
   }
 }
 
+// ---- workspace and metadata ----------------------------------------------------------------------------------------------
+// Bump allocator over a caller's workspace, every buffer 256-byte aligned; base null: sizes only.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  char* take(size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += align_up(bytes, 256);
+    return p;
+  }
+};
+
 struct FwdWs {
   int32_t* meta;  // src_cu [B + 1], tgt_cu [B + 1], work entries (int2)
   float* x;       // [Tp, D] residual stream
@@ -376,22 +389,112 @@ FwdWs fwd_carve(const RpDecoder* d, int batch, int n_src, int n_tgt, char* base)
   const size_t D = d->cfg.d_model, F = d->cfg.d_ff, inner = d->inner, V = d->cfg.vocab_size;
   const size_t Tp = align_up((size_t)std::max(n_tgt, 1), FWD_BN), Sp = align_up((size_t)std::max(n_src, 1), FWD_BN);
   FwdWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  };
-  w.meta = (int32_t*)take((size_t)(2 * (batch + 1) + 2 * fwd_max_work(batch, n_tgt)) * 4);
-  w.x = (float*)take(Tp * D * 4);
-  w.h = (bf16_t*)take(Tp * D * 2);
-  w.ff = (bf16_t*)take(Tp * F * 2);
-  w.qkv = (bf16_t*)take(Tp * 3 * inner * 2);
-  w.att = (bf16_t*)take(Tp * inner * 2);
-  w.ckv = (bf16_t*)take(Sp * 2 * inner * 2);
-  w.logits = (float*)take(Tp * V * 4);
-  w.bytes = off;
+  Carver c{base};
+  w.meta = (int32_t*)c.take((size_t)(2 * (batch + 1) + 2 * fwd_max_work(batch, n_tgt)) * 4);
+  w.x = (float*)c.take(Tp * D * 4);
+  w.h = (bf16_t*)c.take(Tp * D * 2);
+  w.ff = (bf16_t*)c.take(Tp * F * 2);
+  w.qkv = (bf16_t*)c.take(Tp * 3 * inner * 2);
+  w.att = (bf16_t*)c.take(Tp * inner * 2);
+  w.ckv = (bf16_t*)c.take(Sp * 2 * inner * 2);
+  w.logits = (float*)c.take(Tp * V * 4);
+  w.bytes = c.off;
   return w;
+}
+
+// Host image of the metadata: src_cu [B + 1] | tgt_cu [B + 1] | the attention work list {pair, first query} (128-query
+// blocks of non-empty targets).  Returns the number of work entries; a caller may append lists of its own.
+int fwd_build_meta(const int32_t* src_cu, const int32_t* tgt_cu, int batch, std::vector<int32_t>& meta) {
+  meta.assign(src_cu, src_cu + batch + 1);
+  meta.insert(meta.end(), tgt_cu, tgt_cu + batch + 1);
+  for (int b = 0; b < batch; ++b)
+    for (int q0 = 0; q0 < tgt_cu[b + 1] - tgt_cu[b]; q0 += FA_Q) {
+      meta.push_back(b);
+      meta.push_back(q0);
+    }
+  return (int)(meta.size() - 2 * (batch + 1)) / 2;
+}
+
+// ---- the launch sequence ---------------------------------------------------------------------------------------------------
+// Where one layer's activations go.  x0 .. x3: the residual stream at the layer's input and after each of its three
+// sub-layers (x3 is the next layer's x0); h0 .. h2: the normed rows of the three sub-layers.  Pointers may coincide
+// wherever the later value may overwrite the earlier one (the loss alone: one buffer per kind).  lse (optional,
+// [H, lse_ld]): the attention rows' log-sum-exp, what a backward recomputes P from.
+struct FwdLayerBufs {
+  float *x0, *x1, *x2, *x3;
+  bf16_t *h0, *h1, *h2, *qkv, *cq, *ckv, *att_s, *att_c, *ff;
+  float *lse_s, *lse_c;
+  int lse_ld;
+};
+struct FwdFinalBufs {
+  float* x;  // the last layer's x3
+  bf16_t* h;
+  float* logits;
+};
+// scale of the final norm's rows: the tied head reads them times d_model^-1/2
+float fwd_head_scale(const RpDecoder* d) { return d->tied ? 1.f / sqrtf((float)d->cfg.d_model) : 1.f; }
+
+// The whole teacher-forced forward on the device copy `meta` of fwd_build_meta's image: embed, the layers, final norm,
+// lm_head, the rows' log-softmax + label gather and the fixed-order reduction of the loss.  Where a residual GEMM's
+// destination differs from the stream it adds to, the n_tgt * D floats are copied there just before that GEMM.
+RpStatus fwd_launch_layers(const RpDecoder* d, const void* enc_bf16, const int32_t* tokens, const int32_t* labels, int batch,
+                           int n_src, int n_tgt, const int32_t* meta, int n_work, const FwdLayerBufs* bufs,
+                           const FwdFinalBufs& fin, float* label_logprobs, double* loss_sum_count, float* logprob_rows,
+                           hipStream_t s) {
+  const RpT5Config& c = d->cfg;
+  const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
+  const float eps = c.layer_norm_eps;
+  const int32_t* d_src_cu = meta;
+  const int32_t* d_tgt_cu = meta + batch + 1;
+  const int2* d_work = reinterpret_cast<const int2*>(meta + 2 * (batch + 1));
+  const int Tp = (int)align_up(n_tgt, FWD_BN), Sp = (int)align_up(n_src, FWD_BN);
+  const dim3 att_grid(H * n_work);
+  RpStatus st;
+  auto norm = [&](const float* x, const float* ln, bf16_t* h, float scale) {
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(n_tgt), dim3(256), 0, s, x, ln, h, D, eps, scale);
+  };
+  auto move_stream = [&](float* to, const float* from) {
+    return to != from ? hipMemcpyAsync(to, from, (size_t)n_tgt * D * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
+  };
+  hipLaunchKernelGGL(dec_embed_kernel, dim3(n_tgt), dim3(256), 0, s, tokens, d->embed, L ? bufs[0].x0 : fin.x, D, V);
+  for (int i = 0; i < L; ++i) {
+    const RpDecoder::Layer& l = d->layers[i];
+    const FwdLayerBufs& b = bufs[i];
+    // self-attention: x += o(attn(rmsnorm(x))), causal inside each pair
+    norm(b.x0, l.ln_self, b.h0, 1.f);
+    if ((st = fwd_gemm(b.h0, n_tgt, Tp, l.wqkv, 3 * inner, D, EpiDecBf16{b.qkv, 3 * inner, 3 * inner, n_tgt}, s,
+                       RP_K_GEMM_QKV)))
+      return st;
+    hipLaunchKernelGGL(dec_flash_kernel<true>, att_grid, dim3(256), 0, s, b.qkv, 3 * inner, b.qkv, 3 * inner, inner,
+                       2 * inner, d_tgt_cu, d_tgt_cu, d_work, d->bias_tab, d->nbias, b.att_s, inner, b.lse_s, b.lse_ld);
+    RP_HIP(move_stream(b.x1, b.x0));
+    if ((st = fwd_gemm(b.att_s, n_tgt, Tp, l.wo, D, inner, EpiDecF32<true>{b.x1, D, D, n_tgt}, s, RP_K_GEMM_O))) return st;
+    // cross-attention: the pair's queries over its own source's K / V (this layer's, from one GEMM over all sources)
+    if ((st = fwd_gemm((const bf16_t*)enc_bf16, n_src, Sp, d->cross_kv_w + (size_t)2 * i * inner * D, 2 * inner, D,
+                       EpiDecBf16{b.ckv, 2 * inner, 2 * inner, n_src}, s, RP_K_GEMM_QKV)))
+      return st;
+    norm(b.x1, l.ln_cross, b.h1, 1.f);
+    if ((st = fwd_gemm(b.h1, n_tgt, Tp, l.cq, inner, D, EpiDecBf16{b.cq, inner, inner, n_tgt}, s, RP_K_GEMM_QKV)))
+      return st;
+    hipLaunchKernelGGL(dec_flash_kernel<false>, att_grid, dim3(256), 0, s, b.cq, inner, b.ckv, 2 * inner, 0, inner,
+                       d_tgt_cu, d_src_cu, d_work, (const float*)nullptr, 1, b.att_c, inner, b.lse_c, b.lse_ld);
+    RP_HIP(move_stream(b.x2, b.x1));
+    if ((st = fwd_gemm(b.att_c, n_tgt, Tp, l.co, D, inner, EpiDecF32<true>{b.x2, D, D, n_tgt}, s, RP_K_GEMM_O))) return st;
+    // gated-GELU FFN
+    norm(b.x2, l.ln_ff, b.h2, 1.f);
+    if ((st = fwd_gemm(b.h2, n_tgt, Tp, d->wi_il + (size_t)i * 2 * F * D, 2 * F, D, EpiDecGeglu{b.ff, F, F, n_tgt}, s,
+                       RP_K_GEMM_WI)))
+      return st;
+    RP_HIP(move_stream(b.x3, b.x2));
+    if ((st = fwd_gemm(b.ff, n_tgt, Tp, l.wo2, D, F, EpiDecF32<true>{b.x3, D, D, n_tgt}, s, RP_K_GEMM_WO))) return st;
+  }
+  norm(fin.x, d->final_ln, fin.h, fwd_head_scale(d));
+  if ((st = fwd_gemm(fin.h, n_tgt, Tp, d->lm_head, V, D, EpiDecF32<false>{fin.logits, V, V, n_tgt}, s, RP_K_GEMM_O)))
+    return st;
+  hipLaunchKernelGGL(fwd_loss_row_kernel, dim3(n_tgt), dim3(256), 0, s, fin.logits, V, labels, label_logprobs, logprob_rows);
+  hipLaunchKernelGGL(fwd_loss_reduce_kernel, dim3(1), dim3(256), 0, s, label_logprobs, labels, n_tgt, V, loss_sum_count);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
 }
 
 RpStatus fwd_check_model(const RpDecoder* d) {

@@ -216,34 +216,6 @@ int bwd_variant(int n_rows_w, int K, int Tp) {
   return tiles >= 192 ? 26 : 0;
 }
 
-// One product of a wgrad launch: dW[ny, nx] (fp32, ldc = nx) = Y[:Tp, :ny]^T X[:Tp, :nx], `splits` partial matrices at
-// out + s * ny * nx
-struct WgradOperands {
-  const bf16_t* Y;
-  int ldy, ny;
-  const bf16_t* X;
-  int ldx, nx;
-  float* out;
-  WgradFinish fin = WgradFinish{};  // first product of a split-free launch only
-};
-template <class C>
-RpStatus launch_wgrad_cfg(const WgradOperands& a, const WgradOperands* b, int nk, int splits, hipStream_t stream) {
-  auto kern = wgrad_kernel<C>;
-  static LdsAttrOnce attr;
-  RP_HIP(attr.ensure((const void*)kern, C::LDS_BYTES));
-  auto problem = [](const WgradOperands& o) {
-    return WgradProblem{o.Y, o.ldy, o.ny, o.X, o.ldx, o.nx, (o.ny + C::BM - 1) / C::BM, (o.nx + C::BN - 1) / C::BN,
-                        o.out, o.nx, (size_t)o.ny * o.nx, o.fin};
-  };
-  const WgradProblem p0 = problem(a), p1 = b ? problem(*b) : WgradProblem{};
-  RP_REQUIRE(!a.fin.geglu || (splits == 1 && a.ny % 64 == 0), "a finishing wgrad epilogue needs a split-free launch");
-  const int blocks0 = splits * p0.tiles_m * p0.tiles_n, blocks1 = b ? splits * p1.tiles_m * p1.tiles_n : 0;
-  ProfScope ps(stream, RP_K_BWD_WGRAD);
-  hipLaunchKernelGGL(kern, dim3(blocks0 + blocks1), dim3(C::THREADS), C::LDS_BYTES, stream, p0, p1, blocks0, nk, splits);
-  RP_CHECK_LAUNCH();
-  return RP_OK;
-}
-
 RpStatus launch_wgrad(const bf16_t* Y, int ldy, int ny, const bf16_t* X, int ldx, int nx, int Tp, int splits, float* out,
                       hipStream_t stream, int force_cfg = -1) {
   RP_REQUIRE(Tp % 64 == 0 && ny % 8 == 0 && nx % 8 == 0 && ny >= 8 && nx >= 8, "wgrad: Tp=%d ny=%d nx=%d", Tp, ny, nx);

@@ -131,6 +131,10 @@ def shift_and_segment(tactic_ids, decoder_start_token_id: int = 0, pad_token_id:
     return cat(toks), cat(labs), cu
 
 
+def _pc(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
 class HipT5Decoder:
     """The decoder weights resident on one GPU + the per-step launch sequence."""
 
@@ -203,34 +207,39 @@ class HipT5Decoder:
         """log-probs [nb, V] of one step (``beam_search``'s ``step``; ancestry int [nb, t + 1])."""
         return self.step_many(_STATE_0, tokens, ancestry, out)
 
+    def _teacher_forced_args(self, entry: str, src_cu, tokens, labels, tgt_cu):
+        """What ``rp_decoder_forward`` and ``rp_decoder_loss_grad`` share: int32 cu arrays, (B, T, S), the device tokens /
+        labels, the lp / sc outputs, and the entry's own workspace, kept between calls and grown to
+        ``<entry>_workspace_bytes``."""
+        src_cu = np.ascontiguousarray(src_cu, dtype=np.int32)
+        tgt_cu = np.ascontiguousarray(tgt_cu, dtype=np.int32)
+        B, T, S = len(tgt_cu) - 1, int(tgt_cu[-1]), int(src_cu[-1])
+        n = int(getattr(self._lib, entry + "_workspace_bytes")(self._handle, _pc(src_cu), _pc(tgt_cu), B))
+        if n == 0:
+            raise _lib.HipLibraryError(f"{entry}: " + self._lib.rp_last_error().decode(errors="replace"))
+        kept = self.__dict__.setdefault("_teacher_forced_ws", {})
+        if kept.get(entry) is None or kept[entry].numel() < n:
+            kept[entry] = None  # (released before the larger one is taken)
+            kept[entry] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
+        tok, lab = dev(tokens), dev(labels)
+        lp = torch.empty(T, dtype=torch.float32, device=self.device)
+        sc = torch.empty(2, dtype=torch.float64, device=self.device)
+        return kept[entry], src_cu, tgt_cu, B, T, S, tok, lab, lp, sc
+
     def forward(self, enc_bf16: torch.Tensor, src_cu: np.ndarray, tokens: np.ndarray, labels: np.ndarray,
                 tgt_cu: np.ndarray, rows: bool = False):
         """Teacher-forced pass over packed pairs (``rp_decoder_forward``): enc_bf16 [sum S_b, d_model] device bf16,
         host cu arrays, host int tokens / labels [sum T_b].  Returns (label log-probs [sum T_b] fp32 on the device,
         (sum of -log p, count) as floats, the full log-prob rows [sum T_b, V] or None)."""
-        src_cu = np.ascontiguousarray(src_cu, dtype=np.int32)
-        tgt_cu = np.ascontiguousarray(tgt_cu, dtype=np.int32)
-        B = len(tgt_cu) - 1
-        T = int(tgt_cu[-1])
-        lib = self._lib
-        pc = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        n = int(lib.rp_decoder_forward_workspace_bytes(self._handle, pc(src_cu), pc(tgt_cu), B))
-        if n == 0:
-            raise _lib.HipLibraryError("rp_decoder_forward: " + lib.rp_last_error().decode(errors="replace"))
-        if getattr(self, "_fwd_ws", None) is None or self._fwd_ws.numel() < n:
-            self._fwd_ws = None
-            self._fwd_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
-        tok, lab = dev(tokens), dev(labels)
-        lp = torch.empty(T, dtype=torch.float32, device=self.device)
-        sc = torch.empty(2, dtype=torch.float64, device=self.device)
+        ws, src_cu, tgt_cu, B, T, _, tok, lab, lp, sc = self._teacher_forced_args("rp_decoder_forward", src_cu, tokens,
+                                                                                  labels, tgt_cu)
+        ptr = lambda t: t.data_ptr() if T else None  # noqa: E731  (no target token: the entry point takes nulls)
         out_rows = torch.empty((T, self.V), dtype=torch.float32, device=self.device) if rows else None
         with torch.cuda.device(self.device):
-            _lib.check(lib.rp_decoder_forward(self._handle, enc_bf16.data_ptr() if T else None, pc(src_cu),
-                                              tok.data_ptr() if T else None, lab.data_ptr() if T else None, pc(tgt_cu), B,
-                                              lp.data_ptr() if T else None, sc.data_ptr(),
-                                              out_rows.data_ptr() if (rows and T) else None, self._fwd_ws.data_ptr(),
-                                              self._fwd_ws.numel(), _lib.current_stream()),
+            _lib.check(self._lib.rp_decoder_forward(self._handle, ptr(enc_bf16), _pc(src_cu), ptr(tok), ptr(lab),
+                                                    _pc(tgt_cu), B, ptr(lp), sc.data_ptr(), ptr(out_rows) if rows else None,
+                                                    ws.data_ptr(), ws.numel(), _lib.current_stream()),
                        "rp_decoder_forward")
         s, c = sc.cpu().tolist()
         return lp, (s, c), out_rows
@@ -272,31 +281,18 @@ class HipT5Decoder:
         """``rp_decoder_loss_grad`` over packed pairs (arguments as ``forward``).  Returns (label log-probs [sum T_b],
         (sum of -log p, count), the flat fp32 gradient buffer of ``grad_layout``, d loss / d enc [sum S_b, d_model] fp32
         or None).  ``grads``: a buffer to write into (its padding gaps are left as they are)."""
-        src_cu = np.ascontiguousarray(src_cu, dtype=np.int32)
-        tgt_cu = np.ascontiguousarray(tgt_cu, dtype=np.int32)
-        B = len(tgt_cu) - 1
-        T, S = int(tgt_cu[-1]), int(src_cu[-1])
-        lib = self._lib
-        pc = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        n = int(lib.rp_decoder_loss_grad_workspace_bytes(self._handle, pc(src_cu), pc(tgt_cu), B))
-        if n == 0:
-            raise _lib.HipLibraryError("rp_decoder_loss_grad: " + lib.rp_last_error().decode(errors="replace"))
-        if getattr(self, "_grad_ws", None) is None or self._grad_ws.numel() < n:
-            self._grad_ws = None
-            self._grad_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)  # noqa: E731
-        tok, lab = dev(tokens), dev(labels)
-        lp = torch.empty(T, dtype=torch.float32, device=self.device)
-        sc = torch.empty(2, dtype=torch.float64, device=self.device)
+        ws, src_cu, tgt_cu, B, T, S, tok, lab, lp, sc = self._teacher_forced_args("rp_decoder_loss_grad", src_cu, tokens,
+                                                                                  labels, tgt_cu)
+        ptr = lambda t: t.data_ptr() if T else None  # noqa: E731
         if grads is None:
             grads = torch.zeros(int(self.grad_layout()[1][-1]), dtype=torch.float32, device=self.device)
         d_enc = torch.empty((S, self.cfg["d_model"]), dtype=torch.float32, device=self.device) if want_d_enc else None
         with torch.cuda.device(self.device):
-            _lib.check(lib.rp_decoder_loss_grad(self._handle, enc_bf16.data_ptr() if T else None, pc(src_cu),
-                                                tok.data_ptr() if T else None, lab.data_ptr() if T else None, pc(tgt_cu),
-                                                B, lp.data_ptr() if T else None, sc.data_ptr(), grads.data_ptr(),
-                                                d_enc.data_ptr() if (want_d_enc and S) else None,
-                                                self._grad_ws.data_ptr(), self._grad_ws.numel(), _lib.current_stream()),
+            _lib.check(self._lib.rp_decoder_loss_grad(self._handle, ptr(enc_bf16), _pc(src_cu), ptr(tok), ptr(lab),
+                                                      _pc(tgt_cu), B, ptr(lp), sc.data_ptr(), grads.data_ptr(),
+                                                      d_enc.data_ptr() if (want_d_enc and S) else None,
+                                                      ws.data_ptr(), ws.numel(),
+                                                      _lib.current_stream()),
                        "rp_decoder_loss_grad")
         s, c = sc.cpu().tolist()
         return lp, (s, c), grads, d_enc

@@ -136,10 +136,13 @@ def test_grad_layout_matches_the_state_dict(name):
 
 
 def test_forward_bits_determinism_gaps_and_null_d_enc():
+    # the forward's bits on every cached case: two layers (slot stride), a 129- and a 260-token target (a second 128-query
+    # block, Tp > n_tgt), an empty target beside non-empty ones, tied and untied heads, d_model 1472 (no multiple of 128)
+    for name in ("tiny", "tiny-tied", "byt5-width"):
+        _, dec, _, _, out, _, _ = _case(name)
+        lp, sc, _ = dec.forward(*out["args"])
+        assert torch.equal(lp, out["lp"]) and sc == out["sc"], name
     cfg, dec, encs, y, out, _, _ = _case("tiny")
-    enc, src_cu, tokens, labels, tgt_cu = out["args"]
-    lp, sc, _ = dec.forward(enc, src_cu, tokens, labels, tgt_cu)
-    assert torch.equal(lp, out["lp"]) and sc == out["sc"]
     names, off = dec.grad_layout()
     shapes = dec.grad_shapes()
     assert all(o % 64 == 0 for o in off)
