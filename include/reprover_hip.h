@@ -19,6 +19,13 @@
  *   - launches are asynchronous on `stream`; no call synchronises the device unless documented.
  *   - no hidden allocations after rp_encoder_create(); scratch comes from caller workspaces sized
  *     by the matching *_workspace_bytes() function.
+ *   - a workspace's contents on entry are arbitrary: no call reads a workspace byte that the same call has not written
+ *     (the two documented hand-overs aside: rp_train_backward reads what rp_train_forward left, the decoder steps
+ *     read the cross K/V and the cache rows that earlier calls wrote).  workspace_bytes smaller than the matching
+ *     *_workspace_bytes() returns RP_E_WORKSPACE and nothing is launched or written.
+ *   - nothing outside [workspace, workspace + workspace_bytes) and the documented outputs is written, and nothing
+ *     outside the documented extent of an input is read.  Where an output is written only in part (the padding gaps
+ *     of the flat gradient buffers), its description says so.
  */
 #ifndef REPROVER_HIP_H
 #define REPROVER_HIP_H
@@ -147,7 +154,8 @@ int32_t  rp_relative_position_bucket(int32_t relative_position, int32_t num_buck
 enum { RP_TOPK_AUTO = 0, RP_TOPK_DENSE = 1 /* force the single-pass dense path */ };
 
 /* D = the embedding width for BOTH entry points (the e4m3 one plans with half the 2-byte units per row; its plan can
- * only differ by taking the first-generation filter kernel, which needs no more workspace than this returns). */
+ * only differ by taking the first-generation filter kernel, which needs no more workspace than this returns; it
+ * still asks for this size, so that one rule - workspace_bytes >= what this returns - holds for all four calls). */
 size_t   rp_sim_topk_workspace_bytes(int32_t B, int32_t N, int32_t D, int32_t k, int32_t flags);
 
 /*   Q            device bf16 [B, D]   query embeddings (unit norm)

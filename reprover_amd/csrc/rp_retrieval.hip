@@ -1190,8 +1190,11 @@ static RpStatus sim_topk_impl(const void* Q, const void* E, const float* q_scale
   hipStream_t stream = (hipStream_t)stream_;
   const int D2 = fp8 ? D / 2 : D;  // row length in 2-byte units
   const SimPlan p = plan_sim(B, N, D2, k, flags, fp8);
-  if (!workspace || workspace_bytes < p.bytes)
-    return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, p.bytes);
+  // one size for both operand types, the documented one: the e4m3 plan may need less (the first-generation filter has no
+  // private runs), and a workspace between the two sizes used to be accepted by the e4m3 entry points alone
+  const size_t need = fp8 ? std::max(p.bytes, plan_sim(B, N, D, k, flags).bytes) : p.bytes;
+  if (!workspace || workspace_bytes < need)
+    return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, need);
   char* ws = (char*)workspace;
   uint64_t* dense = (uint64_t*)(ws + p.off_dense);
   uint64_t* cand = (uint64_t*)(ws + p.off_cand);

@@ -292,3 +292,181 @@ def check_topk_against_scores(ids, scores, counts, S, acc, k, tol):
 
 
 from oracle.parity_margins import gap_rule_ids  # noqa: E402,F401  (one definition, shared with smoke())
+
+
+# ---- workspace hygiene: guarded arenas, poisoned workspaces, bit-exact comparison across fills -----------------------------
+# (device-agnostic: tests/test_hygiene_harness_cpu.py runs it on CPU tensors against a toy entry point)
+RP_E_WORKSPACE = -3
+GUARD_BYTE = 0xA5              # what an untouched guard holds
+OUTPUT_BYTE = 0x5A             # what an output holds before a call (elements a call leaves alone keep it)
+WS_FILLS = (0x00, 0xFF, 0x7F)  # zero pages; NaN / -1 / 255; large finite values whose squares overflow
+MIN_GUARD = 1 << 20
+
+
+def guard_bytes(d_ff=0):
+    """Bytes of each guard: at least 1 MiB, and 256 rows of the widest row an entry point stores for the model (the fp32
+    gate | up row, 2 * d_ff * 4 bytes), so that one whole 256-row tile stored past a buffer lands in the guard."""
+    return max(MIN_GUARD, 256 * 2 * int(d_ff) * 4)
+
+
+class Arena:
+    """One uint8 allocation [lead guard | payload | tail guard]; the payload starts at a multiple of 256 bytes and the
+    tail guard at the payload's last byte + 1.  ``init``: the payload's content before every call - a byte value or a
+    tensor whose bytes open the payload (the rest is OUTPUT_BYTE).  ``compare=False``: an output whose content is outside
+    the determinism contract (guarded, not compared)."""
+
+    def __init__(self, name, nbytes, guard, device, init=OUTPUT_BYTE, dtype=torch.uint8, compare=True):
+        self.name, self.nbytes, self.dtype, self.compare = name, int(nbytes), dtype, compare
+        self.raw = torch.empty(2 * guard + 256 + self.nbytes, dtype=torch.uint8, device=device)
+        self.off = guard + (-(self.raw.data_ptr() + guard)) % 256
+        self.lead_byte = self.tail_byte = GUARD_BYTE
+        self.raw.fill_(GUARD_BYTE)
+        self._init = init if isinstance(init, int) else init.detach().contiguous().view(-1).view(torch.uint8).clone()
+        assert isinstance(init, int) or self._init.numel() <= self.nbytes
+        self.reset()
+
+    @classmethod
+    def of(cls, name, tensor, guard, device=None, compare=True):
+        """An arena that holds ``tensor``'s bytes (an input, or an output with a meaningful content on entry)."""
+        t = tensor.detach().contiguous()
+        return cls(name, t.numel() * t.element_size(), guard, device if device is not None else t.device, init=t,
+                   dtype=t.dtype, compare=compare)
+
+    @property
+    def ptr(self):
+        return self.raw.data_ptr() + self.off
+
+    def payload(self):
+        return self.raw[self.off : self.off + self.nbytes]
+
+    def view(self, *shape, dtype=None):
+        """The payload's first elements as a typed tensor of ``shape`` (default: all of it, flat)."""
+        dtype = self.dtype if dtype is None else dtype
+        size = torch.empty((), dtype=dtype).element_size()
+        n = int(np.prod(shape)) if shape else self.nbytes // size
+        return self.payload()[: n * size].view(dtype).view(*(shape or (n,)))
+
+    def at(self, byte_offset, nbytes):
+        """Pointer arithmetic: ``nbytes`` bytes at payload + byte_offset, inside the payload or not (the self-test's toy
+        entry point plants its out-of-range accesses through this)."""
+        return self.raw[self.off + byte_offset : self.off + byte_offset + nbytes]
+
+    def fill(self, byte):
+        self.payload().fill_(byte)
+
+    def reset(self):
+        if isinstance(self._init, int):
+            self.fill(self._init)
+        else:
+            self.fill(OUTPUT_BYTE)
+            self.payload()[: self._init.numel()].copy_(self._init)
+
+    def at_rest(self):
+        """True when the payload holds exactly what reset() leaves (nothing was written)."""
+        keep = self.payload().clone()
+        self.reset()
+        same = torch.equal(keep, self.payload())
+        self.payload().copy_(keep)
+        return same
+
+    def set_tail(self, byte):
+        self.tail_byte = byte
+        self.raw[self.off + self.nbytes :].fill_(byte)
+
+    def broken_guards(self):
+        """The guards that no longer hold their byte pattern, by name ("lead" / "tail"): a bitwise check."""
+        bad = []
+        if not bool((self.raw[: self.off] == self.lead_byte).all()):
+            bad.append("lead")
+        if not bool((self.raw[self.off + self.nbytes :] == self.tail_byte).all()):
+            bad.append("tail")
+        return bad
+
+
+def _first_difference(arena, a, b):
+    size = torch.empty((), dtype=arena.dtype).element_size()
+    i = int(torch.nonzero(a != b)[0])
+    return f"first differing element {i // size} (byte {i}) of {arena.nbytes // size}"
+
+
+def hygiene_findings(call, workspace, outputs, inputs=(), fills=WS_FILLS, undersized=True, results=None):
+    """Run ``call(workspace_bytes) -> status`` under every workspace fill and input-tail fill and return what went wrong,
+    one line per finding (an empty list: the call is clean).  ``workspace`` (an Arena, None, or a list of Arenas for a
+    sequence of calls with a workspace each: workspace_bytes then speaks of the first), ``outputs`` and ``inputs``
+    (Arenas) are what the call's pointers refer to; outputs and inputs are put back to their initial content before every
+    run.  ``results`` (a dict) receives the outputs of the zero-filled run by name, as flat tensors of the arena's dtype.
+    Findings, by the words they start with:
+      status             a run did not return RP_OK
+      guard NAME lead    bytes in front of NAME's payload changed (a store before the buffer, an index of -1)
+      guard NAME tail    bytes behind NAME's payload changed (a store past the buffer)
+      not reproducible   two runs on a zero-filled workspace differ (nothing else can be concluded then)
+      stale workspace    an output depends on what the workspace held on entry (a read before the call's own write)
+      input tail         an output depends on the bytes behind an input (a read past its end)
+      undersized         workspace_bytes - 1 is not refused with RP_E_WORKSPACE, or the refused call wrote something"""
+    spaces = [] if workspace is None else list(workspace) if isinstance(workspace, (list, tuple)) else [workspace]
+    workspace = spaces[0] if spaces else None
+    everything = spaces + list(outputs) + list(inputs)
+    on_gpu = any(a.raw.is_cuda for a in everything)
+    findings = []
+
+    def guards(when):
+        for a in everything:
+            for side in a.broken_guards():
+                line = f"guard {a.name} {side}: changed during {when}"
+                if line not in findings:
+                    findings.append(line)
+                (a.raw[: a.off] if side == "lead" else a.raw[a.off + a.nbytes :]).fill_(
+                    a.lead_byte if side == "lead" else a.tail_byte)  # re-arm: later runs report their own
+
+    def run(fill, tail, when, ws_bytes=None):
+        for a in list(outputs) + list(inputs):
+            a.reset()
+        for a in inputs:
+            a.set_tail(tail)
+        for w in spaces:
+            w.fill(fill)
+        st = call((workspace.nbytes if workspace is not None else 0) if ws_bytes is None else ws_bytes)
+        if on_gpu:
+            torch.cuda.synchronize()
+        guards(when)
+        return st, [a.payload().clone() for a in outputs]
+
+    def compare(kind, base, got, when):
+        for a, x, y in zip(outputs, base, got):
+            if a.compare and not torch.equal(x, y):  # bytes: NaNs compare too
+                findings.append(f"{kind}: output {a.name} differs {when}: {_first_difference(a, x, y)}")
+
+    st, base = run(0x00, GUARD_BYTE, "the zero-filled run")
+    if st != 0:
+        return findings + [f"status {st} from the zero-filled run: {last_error() if on_gpu else ''}"]
+    if results is not None:
+        results.update({a.name: x.view(a.dtype) for a, x in zip(outputs, base)})
+    st, again = run(0x00, GUARD_BYTE, "the repeated zero-filled run")
+    compare("not reproducible", base, again, "between two zero-filled runs")
+    if st != 0 or any(f.startswith("not reproducible") for f in findings):
+        return findings
+    for fill in fills:
+        if fill == 0x00 or workspace is None:
+            continue
+        st, got = run(fill, GUARD_BYTE, f"the run with the workspace filled with 0x{fill:02X}")
+        if st != 0:
+            findings.append(f"status {st} with the workspace filled with 0x{fill:02X}")
+        compare("stale workspace", base, got, f"with the workspace filled with 0x{fill:02X}")
+    if inputs:
+        for tail in (0x00, 0xFF):
+            st, got = run(0x00, tail, f"the run with the input tails filled with 0x{tail:02X}")
+            if st != 0:
+                findings.append(f"status {st} with the input tails filled with 0x{tail:02X}")
+            compare("input tail", base, got, f"with the bytes behind the inputs set to 0x{tail:02X}")
+        for a in inputs:
+            a.set_tail(GUARD_BYTE)
+    if undersized and workspace is not None and workspace.nbytes > 0:
+        st, _ = run(GUARD_BYTE, GUARD_BYTE, "the undersized call", ws_bytes=workspace.nbytes - 1)
+        if st != RP_E_WORKSPACE:
+            findings.append(f"undersized: workspace_bytes - 1 returned {st}, not RP_E_WORKSPACE")
+        for a in outputs:
+            if not a.at_rest():
+                findings.append(f"undersized: the refused call wrote to output {a.name}")
+        if not all(bool((w.payload() == GUARD_BYTE).all()) for w in spaces):
+            findings.append("undersized: the refused call wrote to a workspace")
+    return findings
