@@ -360,6 +360,26 @@ RpStatus rp_train_forward(RpTrainer* tr, const int32_t* ids, const int32_t* cu_s
 RpStatus rp_train_backward(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens,
                            int32_t batch, int32_t total_tokens, const float* d_emb, float* grads,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* The same forward and backward with last_hidden_state as the hand-over instead of the pooled embedding: the encoder half
+ * of the seq2seq loss's gradient (generation/model.py:117-121 through T5ForConditionalGeneration; the decoder half is
+ * rp_decoder_loss_grad, whose d_enc is this pair's d_hidden).  The layer loops are the pooled pair's; only the head differs
+ * (the final RMSNorm alone).  Same workspace (rp_train_workspace_bytes), same determinism.
+ * rp_train_forward_hidden: the trainer's forward up to and including the final RMSNorm.  out_hidden: device bf16
+ * [total_tokens, d_model] = bf16(final_ln * (x * rs)), fp32 arithmetic and one rounding; the activations stay in `workspace`
+ * for rp_train_backward_hidden.  cu_seqlens is read back once before anything is launched (the one synchronisation of
+ * `stream` in this pair): it must run 0 .. total_tokens and an empty sequence is RP_E_INVALID.
+ * rp_train_backward_hidden: d_hidden: device f32 [total_tokens, d_model] = d loss / d out_hidden, unrounded (e.g.
+ * rp_decoder_loss_grad's d_enc); grads: the trainer's flat layout, every element overwritten, gaps untouched; ids and
+ * cu_seqlens are the forward's (not checked again).
+ * Both return RP_E_INVALID while rp_trainer_set_dropout holds p > 0 (the decoder has no dropout: a half-dropped model is
+ * neither the reference's training mode nor its eval mode), for a null pointer and for batch <= 0; RP_E_WORKSPACE for a
+ * workspace one byte short.  Nothing is launched or written then. */
+RpStatus rp_train_forward_hidden(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
+                                 int32_t total_tokens, void* out_hidden_bf16, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+RpStatus rp_train_backward_hidden(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens,
+                                  int32_t batch, int32_t total_tokens, const float* d_hidden, float* grads,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 /* out_norm[0] (device) = ||grads||_2 over n floats (Lightning's gradient_clip_val, confs/cli_lean4_random.yaml:19, clips
  * on it); scratch: 1024 device floats.  Pair with rp_adamw_step_clipped. */
 RpStatus rp_grad_norm(const float* grads, int64_t n, float* out_norm, float* scratch, void* stream);
@@ -381,7 +401,10 @@ enum {
   RP_K_BWD_DGRAD = 11 /* dY W GEMMs (+ fused GELU / RMSNorm backward) */, RP_K_BWD_WGRAD = 12 /* dY^T X GEMMs */,
   RP_K_BWD_ATTENTION = 13, RP_K_BWD_OTHER = 14 /* pooling, embedding, row statistics, gradient finishing */,
   RP_K_OPTIMIZER = 15 /* AdamW, gradient norm, weight re-packing */,
-  RP_K_COLLECTIVE = 16 /* the all-gather of rp_comm_allgather / rp_allgather_topk */, RP_K_COUNT = 17
+  RP_K_COLLECTIVE = 16 /* the all-gather of rp_comm_allgather / rp_allgather_topk */,
+  RP_K_HIDDEN_HEAD = 17 /* rp_train_forward_hidden's final-norm rows */,
+  RP_K_BWD_HIDDEN_HEAD = 18 /* rp_train_backward_hidden's final-norm backward (the row pass) */,
+  RP_K_COUNT = 19
 };
 RpStatus rp_profile_enable(int32_t on);   /* on != 0: start collecting (clears previous records) */
 /* Synchronises the recorded events; total_ms = sum of launch durations, launches = their number. */

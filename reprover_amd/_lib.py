@@ -21,6 +21,9 @@ RP_EPI_STORE_BF16, RP_EPI_RESID, RP_EPI_GEGLU_BF16, RP_EPI_RESID8 = 0, 1, 2, 3
 ABI_VERSION = 7  # 7: the tactic generator's decoder (rp_decoder_*, rp_beam_select, rp_encode_hidden); 5 was skipped
 KERNEL_CLASSES = ["embed", "rmsnorm", "gemm_qkv", "attention", "gemm_o", "gemm_wi", "gemm_wo", "pool", "scan",
                   "select", "scan_sample", "bwd_dgrad", "bwd_wgrad", "bwd_attention", "bwd_other", "optimizer", "collective"]
+# the classes behind them in the enum: the two head kernels of rp_train_forward_hidden / rp_train_backward_hidden, read with
+# profile_read(heads=True) (the plain call keeps the retriever's report as it was)
+HEAD_KERNEL_CLASSES = ["hidden_head", "bwd_hidden_head"]
 
 
 class RpT5Config(C.Structure):
@@ -183,6 +186,15 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
          C.c_size_t, C.c_void_p],
     ),
+    "rp_train_forward_hidden": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    ),
+    "rp_train_backward_hidden": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_size_t, C.c_void_p],
+    ),
     "rp_grad_norm": (C.c_int32, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rp_dbg_wgrad": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rp_dbg_wgrad_pair": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -330,11 +342,12 @@ def profile_enable(on: bool) -> None:
     check(load().rp_profile_enable(1 if on else 0), "rp_profile_enable")
 
 
-def profile_read() -> dict:
-    """{kernel class: (total_ms, launches)} of the launches recorded since profile_enable(True)."""
+def profile_read(heads: bool = False) -> dict:
+    """{kernel class: (total_ms, launches)} of the launches recorded since profile_enable(True); ``heads`` adds
+    HEAD_KERNEL_CLASSES."""
     lib = load()
     out = {}
-    for i, name in enumerate(KERNEL_CLASSES):
+    for i, name in enumerate(KERNEL_CLASSES + (HEAD_KERNEL_CLASSES if heads else [])):
         ms, n = C.c_double(), C.c_int64()
         check(lib.rp_profile_read(i, C.byref(ms), C.byref(n)), "rp_profile_read")
         out[name] = (ms.value, n.value)

@@ -17,6 +17,9 @@
 // Dropout: T5's dropout (0.1 in the reference's training) at HF's six sites, counter-based (rp_trainer_set_dropout): the
 // backward regenerates the forward's masks.  p = 0 is the deterministic step fixtures G11 / G12 pin; either way the step is
 // bit-reproducible run to run for a given seed.
+// The same layer loops serve two hand-overs: the pooled embedding (rp_train_forward / rp_train_backward, the retriever) and
+// last_hidden_state (rp_train_forward_hidden / rp_train_backward_hidden: the encoder half of the seq2seq loss's gradient,
+// generation/model.py:117-121; without dropout).  Only the head around the final RMSNorm differs.
 #include "rp_train_kernels.h"
 
 using namespace rp;
@@ -98,7 +101,7 @@ struct TrainWs {
   int4 *work, *pwork;
   // backward scratch
   bf16_t *dxhi, *dxlo, *dzs, *datt, *dqkv, *dxm;
-  float *delta, *rdp, *rcoef, *wpart, *dtab_part, *dln_part, *ds_seq, *dwf_seq, *norm_part;
+  float *delta, *rdp, *rcoef, *wpart, *dtab_part, *dln_part, *ds_seq, *dwf_seq, *norm_part, *dhead_part;
   size_t wpart_bytes;
   size_t bytes;
 };
@@ -205,6 +208,9 @@ TrainWs carve_train(const RpTrainer* tr, int T, int batch, char* base) {
   w.ds_seq = (float*)take((size_t)batch * D * 4);
   w.dwf_seq = (float*)take((size_t)batch * D * 4);
   w.norm_part = (float*)take(1024 * 4);
+  // rp_train_backward_hidden's partial rows of d final_ln, one per HIDDEN_BWD_ROWS token rows (last: the regions above are
+  // where they were before this one existed)
+  w.dhead_part = (float*)take(Tp / HIDDEN_BWD_ROWS * D * 4);
   w.bytes = off;
   return w;
 }
@@ -238,8 +244,10 @@ RpStatus run_unfold(const UnfoldArgs& a, hipStream_t stream) {
 }
 
 // ---- forward with saved activations -----------------------------------------------------------------------
-RpStatus train_forward(RpTrainer* tr, const int32_t* ids, const int32_t* cu, int batch, int T, float* out_emb,
-                       const TrainWs& w, hipStream_t stream) {
+// The shared body of rp_train_forward and rp_train_forward_hidden: embedding, every layer, the final RMSNorm's row
+// statistic.  Leaves the final residual stream in xa[L] + xlo and rs_final; the entry point's head follows.
+RpStatus forward_layers(RpTrainer* tr, const int32_t* ids, const int32_t* cu, int batch, int T, const TrainWs& w,
+                        hipStream_t stream) {
   RpEncoder* e = tr->enc;
   const RpT5Config& c = e->cfg;
   const int D = c.d_model, F = c.d_ff, inner = e->inner, H = c.num_heads, L = c.num_layers;
@@ -300,6 +308,15 @@ RpStatus train_forward(RpTrainer* tr, const int32_t* ids, const int32_t* cu, int
       return st;
   }
   rowscale(w.rs_final);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// head of rp_train_forward: final RMSNorm + mean pooling + normalisation -> out_emb [batch, D]
+RpStatus pool_head(RpTrainer* tr, const int32_t* cu, int batch, int T, float* out_emb, const TrainWs& w, hipStream_t stream) {
+  RpEncoder* e = tr->enc;
+  const int D = e->cfg.d_model, L = e->cfg.num_layers;
+  const Drop drop = tr->drop;
   {
     ProfScope ps(stream, RP_K_POOL);
     const dim3 pg(T / POOL_CHUNK + batch);
@@ -319,9 +336,81 @@ RpStatus train_forward(RpTrainer* tr, const int32_t* ids, const int32_t* cu, int
   return RP_OK;
 }
 
+// head of rp_train_forward_hidden: the final RMSNorm's rows, last_hidden_state [T, D] bf16
+RpStatus hidden_head(RpTrainer* tr, int T, bf16_t* out_hidden, const TrainWs& w, hipStream_t stream) {
+  RpEncoder* e = tr->enc;
+  const int D = e->cfg.d_model, L = e->cfg.num_layers;
+  ProfScope ps(stream, RP_K_HIDDEN_HEAD);
+  hipLaunchKernelGGL(hidden_head_kernel, dim3((T + HIDDEN_ROWS - 1) / HIDDEN_ROWS), dim3(256), 0, stream, (const bf16_t*)w.xa[L],
+                     (const bf16_t*)w.xlo, (const float*)w.rs_final, (const float*)e->final_ln, out_hidden, T, D);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
 // ---- backward ---------------------------------------------------------------------------------------------
-RpStatus train_backward(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu, int batch, int T,
-                        const float* d_emb, float* grads, const TrainWs& w, hipStream_t stream) {
+// The residual gradient starts as zero planes (rows T .. Tp stay zero: they are K rows of the wgrad GEMMs) and the
+// bias-table partials as zeros; then the entry point's head writes d loss / d x of the final residual stream and
+// final_layer_norm.weight's gradient, and backward_layers does the rest.
+RpStatus backward_zero(RpTrainer* tr, int batch, int T, const TrainWs& w, hipStream_t stream) {
+  const RpT5Config& c = tr->enc->cfg;
+  const int Tp = (int)align_up((size_t)T, GEMM_M_ALIGN);
+  const size_t att_rows = (size_t)(T / ATT_Q + batch), ntab = 2 * tr->enc->maxd + 1;
+  RP_HIP(hipMemsetAsync(w.dxhi, 0, (size_t)Tp * c.d_model * 2, stream));
+  RP_HIP(hipMemsetAsync(w.dxlo, 0, (size_t)Tp * c.d_model * 2, stream));
+  RP_HIP(hipMemsetAsync(w.dtab_part, 0, att_rows * c.num_heads * ntab * 4, stream));
+  return RP_OK;
+}
+
+// head of rp_train_backward: normalisation + mean pooling + final RMSNorm, from d loss / d embedding [batch, D]
+RpStatus pool_bwd_head(RpTrainer* tr, const int32_t* cu, int batch, int T, const float* d_emb, float* grads, const TrainWs& w,
+                       hipStream_t stream) {
+  RpEncoder* e = tr->enc;
+  const int D = e->cfg.d_model, L = e->cfg.num_layers;
+  const float inv_d = 1.f / (float)D;
+  const Drop drop = tr->drop;
+  ProfScope ps(stream, RP_K_BWD_OTHER);
+  hipLaunchKernelGGL(pool_bwd_seq_kernel, dim3(batch), dim3(256), 0, stream, (const float*)w.pool, (const float*)e->final_ln, cu,
+                     d_emb, w.ds_seq, w.dwf_seq, D);
+  hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)w.dwf_seq, batch, D,
+                     grads + tr->lay.final_ln());
+  const dim3 pg(T / POOL_CHUNK + batch);
+  if (D <= 3 * 512)
+    hipLaunchKernelGGL(pool_bwd_tok_kernel<3>, pg, dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
+                       (const float*)w.rs_final, (const int4*)w.pwork, (const float*)w.ds_seq, w.dxhi, w.dxlo, D, inv_d, drop);
+  else
+    hipLaunchKernelGGL(pool_bwd_tok_kernel<4>, pg, dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
+                       (const float*)w.rs_final, (const int4*)w.pwork, (const float*)w.ds_seq, w.dxhi, w.dxlo, D, inv_d, drop);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// head of rp_train_backward_hidden: the final RMSNorm alone, from d loss / d last_hidden_state [T, D] fp32.  The partial
+// rows of final_layer_norm.weight's gradient, one per workgroup, go through dhead_part to colsum_kernel.
+RpStatus hidden_bwd_head(RpTrainer* tr, int T, const float* d_hidden, float* grads, const TrainWs& w, hipStream_t stream) {
+  RpEncoder* e = tr->enc;
+  const int D = e->cfg.d_model, L = e->cfg.num_layers;
+  const float inv_d = 1.f / (float)D;
+  const int nblk = (T + HIDDEN_BWD_ROWS - 1) / HIDDEN_BWD_ROWS;
+  {
+    ProfScope ps(stream, RP_K_BWD_HIDDEN_HEAD);
+    if (D <= 3 * 512)
+      hipLaunchKernelGGL(hidden_head_bwd_kernel<3>, dim3(nblk), dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
+                         (const float*)w.rs_final, (const float*)e->final_ln, d_hidden, w.dxhi, w.dxlo, w.dhead_part, T, D, inv_d);
+    else
+      hipLaunchKernelGGL(hidden_head_bwd_kernel<4>, dim3(nblk), dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
+                         (const float*)w.rs_final, (const float*)e->final_ln, d_hidden, w.dxhi, w.dxlo, w.dhead_part, T, D, inv_d);
+  }
+  ProfScope ps(stream, RP_K_BWD_OTHER);
+  hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)w.dhead_part, nblk, D,
+                     grads + tr->lay.final_ln());
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// The shared body of rp_train_backward and rp_train_backward_hidden: from the residual gradient of the final stream
+// (dxhi + dxlo) through every layer to the embedding scatter and the bias table.
+RpStatus backward_layers(RpTrainer* tr, const float* params, const int32_t* ids, int batch, int T, float* grads,
+                         const TrainWs& w, hipStream_t stream) {
   RpEncoder* e = tr->enc;
   const RpT5Config& c = e->cfg;
   const Layout& lay = tr->lay;
@@ -351,27 +440,6 @@ RpStatus train_backward(RpTrainer* tr, const float* params, const int32_t* ids, 
     return launch_gemm(A, K, Tp, Wt, K, D, K, EpiRmsBwdResid{w.dxhi, w.dxlo, D, D, x_saved, w.rcoef}, stream, RP_K_BWD_DGRAD, 0,
                        nullptr, bwd_variant(D, K, Tp));
   };
-  RP_HIP(hipMemsetAsync(w.dxhi, 0, (size_t)Tp * D * 2, stream));
-  RP_HIP(hipMemsetAsync(w.dxlo, 0, (size_t)Tp * D * 2, stream));
-  RP_HIP(hipMemsetAsync(w.dtab_part, 0, (size_t)att_grid.y * H * ntab * 4, stream));
-
-  // pooling + final RMSNorm
-  {
-    ProfScope ps(stream, RP_K_BWD_OTHER);
-    hipLaunchKernelGGL(pool_bwd_seq_kernel, dim3(batch), dim3(256), 0, stream, (const float*)w.pool, (const float*)e->final_ln, cu,
-                       d_emb, w.ds_seq, w.dwf_seq, D);
-    hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)w.dwf_seq, batch, D,
-                       grads + lay.final_ln());
-    const dim3 pg(T / POOL_CHUNK + batch);
-    if (D <= 3 * 512)
-      hipLaunchKernelGGL(pool_bwd_tok_kernel<3>, pg, dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
-                         (const float*)w.rs_final, (const int4*)w.pwork, (const float*)w.ds_seq, w.dxhi, w.dxlo, D, inv_d, drop);
-    else
-      hipLaunchKernelGGL(pool_bwd_tok_kernel<4>, pg, dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
-                         (const float*)w.rs_final, (const int4*)w.pwork, (const float*)w.ds_seq, w.dxhi, w.dxlo, D, inv_d, drop);
-    RP_CHECK_LAUNCH();
-  }
-
   mask_first(DROP_SITE_LAYER0 + 8u * (uint32_t)(L - 1) + 3);
   for (int i = L - 1; i >= 0; --i) {
     const LayerT& Lt = tr->lt[i];
@@ -663,25 +731,82 @@ extern "C" size_t rp_train_workspace_bytes(const RpTrainer* tr, int32_t total_to
   return carve_train(tr, total_tokens, batch, nullptr).bytes;
 }
 
+// argument checks and the workspace carve shared by the four forward / backward entry points
+static RpStatus train_entry(RpTrainer* tr, int32_t batch, int32_t T, void* workspace, size_t workspace_bytes, TrainWs* w) {
+  RP_REQUIRE(batch > 0 && T > 0, "batch=%d total_tokens=%d", batch, T);
+  *w = carve_train(tr, T, batch, (char*)workspace);
+  if (!workspace || workspace_bytes < w->bytes)
+    return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, w->bytes);
+  return RP_OK;
+}
+// the hidden entry points run without dropout only: the decoder behind them has none, and a half-dropped model is neither
+// the reference's training mode nor its eval mode
+static RpStatus hidden_entry(const RpTrainer* tr, const char* what) {
+  RP_REQUIRE(!tr->drop.thresh, "%s: dropout is set (rp_trainer_set_dropout p > 0); the hidden entry points take p = 0 only", what);
+  RP_REQUIRE(tr->enc->cfg.d_model <= 4 * 512, "%s: d_model=%d > 2048", what, tr->enc->cfg.d_model);
+  return RP_OK;
+}
+
 extern "C" RpStatus rp_train_forward(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch, int32_t T,
                                      float* out_emb, void* workspace, size_t workspace_bytes, void* stream_) {
   RP_REQUIRE(tr && ids && cu_seqlens && out_emb, "null argument");
-  RP_REQUIRE(batch > 0 && T > 0, "batch=%d total_tokens=%d", batch, T);
-  TrainWs w = carve_train(tr, T, batch, (char*)workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, w.bytes);
-  return train_forward(tr, ids, cu_seqlens, batch, T, out_emb, w, (hipStream_t)stream_);
+  TrainWs w;
+  RpStatus st;
+  if ((st = train_entry(tr, batch, T, workspace, workspace_bytes, &w))) return st;
+  if ((st = forward_layers(tr, ids, cu_seqlens, batch, T, w, (hipStream_t)stream_))) return st;
+  return pool_head(tr, cu_seqlens, batch, T, out_emb, w, (hipStream_t)stream_);
 }
 
 extern "C" RpStatus rp_train_backward(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens,
                                       int32_t batch, int32_t T, const float* d_emb, float* grads, void* workspace,
                                       size_t workspace_bytes, void* stream_) {
   RP_REQUIRE(tr && params && ids && cu_seqlens && d_emb && grads, "null argument");
-  RP_REQUIRE(batch > 0 && T > 0, "batch=%d total_tokens=%d", batch, T);
-  TrainWs w = carve_train(tr, T, batch, (char*)workspace);
-  if (!workspace || workspace_bytes < w.bytes)
-    return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, w.bytes);
-  return train_backward(tr, params, ids, cu_seqlens, batch, T, d_emb, grads, w, (hipStream_t)stream_);
+  TrainWs w;
+  RpStatus st;
+  if ((st = train_entry(tr, batch, T, workspace, workspace_bytes, &w))) return st;
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((st = backward_zero(tr, batch, T, w, stream))) return st;
+  if ((st = pool_bwd_head(tr, cu_seqlens, batch, T, d_emb, grads, w, stream))) return st;
+  return backward_layers(tr, params, ids, batch, T, grads, w, stream);
+}
+
+// The sequence lengths are read on the device only (worklist_kernel); an empty sequence is refused here, where the pooled
+// pair divides by its length.  cu_seqlens is a device array: one small copy, made before anything is launched.
+static RpStatus check_no_empty_sequence(const int32_t* cu_dev, int32_t batch, int32_t T, hipStream_t stream) {
+  std::vector<int32_t> cu((size_t)batch + 1);
+  RP_HIP(hipMemcpyAsync(cu.data(), cu_dev, cu.size() * 4, hipMemcpyDeviceToHost, stream));
+  RP_HIP(hipStreamSynchronize(stream));
+  RP_REQUIRE(cu[0] == 0 && cu[batch] == T, "cu_seqlens runs %d .. %d for total_tokens=%d", cu[0], cu[batch], T);
+  for (int b = 0; b < batch; ++b) RP_REQUIRE(cu[b + 1] > cu[b], "sequence %d is empty (cu_seqlens %d, %d)", b, cu[b], cu[b + 1]);
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_train_forward_hidden(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
+                                            int32_t T, void* out_hidden_bf16, void* workspace, size_t workspace_bytes,
+                                            void* stream_) {
+  RP_REQUIRE(tr && ids && cu_seqlens && out_hidden_bf16, "null argument");
+  TrainWs w;
+  RpStatus st;
+  if ((st = hidden_entry(tr, "rp_train_forward_hidden"))) return st;
+  if ((st = train_entry(tr, batch, T, workspace, workspace_bytes, &w))) return st;
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((st = check_no_empty_sequence(cu_seqlens, batch, T, stream))) return st;
+  if ((st = forward_layers(tr, ids, cu_seqlens, batch, T, w, stream))) return st;
+  return hidden_head(tr, T, (bf16_t*)out_hidden_bf16, w, stream);
+}
+
+extern "C" RpStatus rp_train_backward_hidden(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens,
+                                             int32_t batch, int32_t T, const float* d_hidden, float* grads, void* workspace,
+                                             size_t workspace_bytes, void* stream_) {
+  RP_REQUIRE(tr && params && ids && cu_seqlens && d_hidden && grads, "null argument");
+  TrainWs w;
+  RpStatus st;
+  if ((st = hidden_entry(tr, "rp_train_backward_hidden"))) return st;
+  if ((st = train_entry(tr, batch, T, workspace, workspace_bytes, &w))) return st;
+  hipStream_t stream = (hipStream_t)stream_;
+  if ((st = backward_zero(tr, batch, T, w, stream))) return st;
+  if ((st = hidden_bwd_head(tr, T, d_hidden, grads, w, stream))) return st;
+  return backward_layers(tr, params, ids, batch, T, grads, w, stream);
 }
 
 // ||g||_2 of n floats -> out_norm[0] (device), deterministic; scratch = 1024 floats

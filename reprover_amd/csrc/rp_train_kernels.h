@@ -1181,6 +1181,153 @@ __global__ __launch_bounds__(256) void pool_bwd_tok_kernel(const bf16_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------
+// the last_hidden_state head (rp_train_forward_hidden / rp_train_backward_hidden): the final RMSNorm alone, no pooling
+//   forward:  out[t] = bf16(w * (x_t * rs_t))                                 (fp32, one rounding)
+//   backward: dx_t = w rs_t dh_t - x_t rs_t^3 (dh_t w . x_t) / D   -> the two planes of the residual gradient
+//             d w  = sum_t dh_t x_t rs_t : per-workgroup partial rows in fixed row order, summed by colsum_kernel
+// Both are HBM-bound row passes (x = hi + lo as everywhere in the trainer), 16-byte accesses, one wave per token row with
+// two rows' loads in flight, as embed_kernel / pool_bwd_tok_kernel.
+// ------------------------------------------------------------------------------------------
+constexpr int HIDDEN_ROWS = 8;  // token rows per workgroup of the forward head: two per wave
+static __global__ __launch_bounds__(256) void hidden_head_kernel(const bf16_t* __restrict__ xhi, const bf16_t* __restrict__ xlo,
+                                                          const float* __restrict__ rs, const float* __restrict__ w,
+                                                          bf16_t* __restrict__ out, int T, int D) {
+  const int lane = threadIdx.x & 63;
+  const int r0 = blockIdx.x * HIDDEN_ROWS + 2 * (threadIdx.x >> 6);
+  if (r0 >= T) return;
+  const int r1 = min(r0 + 1, T - 1);  // an odd tail: the second row's loads are clamped to row T - 1, its stores skipped
+  const bool two = r0 + 1 < T;
+  const uint4* h0 = reinterpret_cast<const uint4*>(xhi + (size_t)r0 * D);
+  const uint4* l0 = reinterpret_cast<const uint4*>(xlo + (size_t)r0 * D);
+  const uint4* h1 = reinterpret_cast<const uint4*>(xhi + (size_t)r1 * D);
+  const uint4* l1 = reinterpret_cast<const uint4*>(xlo + (size_t)r1 * D);
+  uint4* o0 = reinterpret_cast<uint4*>(out + (size_t)r0 * D);
+  uint4* o1 = reinterpret_cast<uint4*>(out + (size_t)r1 * D);
+  const float s0 = rs[r0], s1 = rs[r1];
+  for (int c = lane; c < (D >> 3); c += 64) {
+    const uint4 vh0 = h0[c], vl0 = l0[c], vh1 = h1[c], vl1 = l1[c];
+    const float4 wa = *reinterpret_cast<const float4*>(w + c * 8), wb = *reinterpret_cast<const float4*>(w + c * 8 + 4);
+    const float wv[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+    const uint32_t hw0[4] = {vh0.x, vh0.y, vh0.z, vh0.w}, lw0[4] = {vl0.x, vl0.y, vl0.z, vl0.w};
+    const uint32_t hw1[4] = {vh1.x, vh1.y, vh1.z, vh1.w}, lw1[4] = {vl1.x, vl1.y, vl1.z, vl1.w};
+    uint32_t a[4], b[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float x00 = __uint_as_float(hw0[e] << 16) + __uint_as_float(lw0[e] << 16);
+      const float x01 = __uint_as_float(hw0[e] & 0xffff0000u) + __uint_as_float(lw0[e] & 0xffff0000u);
+      const float x10 = __uint_as_float(hw1[e] << 16) + __uint_as_float(lw1[e] << 16);
+      const float x11 = __uint_as_float(hw1[e] & 0xffff0000u) + __uint_as_float(lw1[e] & 0xffff0000u);
+      a[e] = pack_bf2(wv[2 * e] * (x00 * s0), wv[2 * e + 1] * (x01 * s0));
+      b[e] = pack_bf2(wv[2 * e] * (x10 * s1), wv[2 * e + 1] * (x11 * s1));
+    }
+    o0[c] = make_uint4(a[0], a[1], a[2], a[3]);
+    if (two) o1[c] = make_uint4(b[0], b[1], b[2], b[3]);
+  }
+}
+
+// grid = ceil(T / HIDDEN_BWD_ROWS) workgroups of HIDDEN_BWD_ROWS token rows (every workgroup has at least one row and
+// writes its partial row of d w whole); wave v takes rows 2 v, 2 v + 1, then + 8, ... in order, the four waves' sums are
+// combined in wave order.  Rows T .. Tp of the planes are not touched (the caller zeroed them).
+// 32 rows: 575 workgroups at the reference's training batch (18.4 k tokens), two per CU by registers; the partial rows add
+// 1 / 48 to the pass's traffic.
+constexpr int HIDDEN_BWD_ROWS = 32;
+template <int NV>
+__global__ __launch_bounds__(256) void hidden_head_bwd_kernel(const bf16_t* __restrict__ xhi, const bf16_t* __restrict__ xlo,
+                                                              const float* __restrict__ rs, const float* __restrict__ w,
+                                                              const float* __restrict__ dh, bf16_t* __restrict__ dxhi,
+                                                              bf16_t* __restrict__ dxlo, float* __restrict__ dw_part, int T,
+                                                              int D, float inv_d) {
+  __shared__ float red[4][NV * 64 * 8];
+  const int t0 = blockIdx.x * HIDDEN_BWD_ROWS, t1 = min(T, t0 + HIDDEN_BWD_ROWS);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nv = D >> 3;
+  float wv[NV][8], acc[NV][8];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int col = min(lane + 64 * i, nv - 1);
+    const float4 a = *reinterpret_cast<const float4*>(w + col * 8), b = *reinterpret_cast<const float4*>(w + col * 8 + 4);
+    wv[i][0] = a.x; wv[i][1] = a.y; wv[i][2] = a.z; wv[i][3] = a.w;
+    wv[i][4] = b.x; wv[i][5] = b.y; wv[i][6] = b.z; wv[i][7] = b.w;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[i][e] = 0.f;
+  }
+  for (int tb = t0 + 2 * wave; tb < t1; tb += 8) {
+    uint4 vh[2][NV], vl[2][NV];
+    float4 ga[2][NV], gb[2][NV];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {  // both rows' loads are requested before either row is reduced
+      const int t = min(tb + q, t1 - 1);
+      const uint4* sh = reinterpret_cast<const uint4*>(xhi + (size_t)t * D);
+      const uint4* sl = reinterpret_cast<const uint4*>(xlo + (size_t)t * D);
+      const float4* sg = reinterpret_cast<const float4*>(dh + (size_t)t * D);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int col = min(lane + 64 * i, nv - 1);
+        vh[q][i] = sh[col];
+        vl[q][i] = sl[col];
+        ga[q][i] = sg[2 * col];
+        gb[q][i] = sg[2 * col + 1];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int t = tb + q;
+      if (t >= t1) break;
+      const float r = rs[t];
+      float xv[NV][8], gw[NV][8];  // gw = dh * w
+      float dot = 0.f;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const bool live = lane + 64 * i < nv;
+        const uint32_t hw[4] = {vh[q][i].x, vh[q][i].y, vh[q][i].z, vh[q][i].w}, lw[4] = {vl[q][i].x, vl[q][i].y, vl[q][i].z, vl[q][i].w};
+        const float g[8] = {ga[q][i].x, ga[q][i].y, ga[q][i].z, ga[q][i].w, gb[q][i].x, gb[q][i].y, gb[q][i].z, gb[q][i].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          xv[i][2 * e] = __uint_as_float(hw[e] << 16) + __uint_as_float(lw[e] << 16);
+          xv[i][2 * e + 1] = __uint_as_float(hw[e] & 0xffff0000u) + __uint_as_float(lw[e] & 0xffff0000u);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          gw[i][e] = g[e] * wv[i][e];
+          if (live) {
+            dot = __builtin_fmaf(gw[i][e], xv[i][e], dot);
+            acc[i][e] = __builtin_fmaf(g[e], xv[i][e] * r, acc[i][e]);
+          }
+        }
+      }
+      dot = wave_sum(dot);
+      const float k = r * r * r * dot * inv_d;
+      uint4* dh_ = reinterpret_cast<uint4*>(dxhi + (size_t)t * D);
+      uint4* dl_ = reinterpret_cast<uint4*>(dxlo + (size_t)t * D);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        if (lane + 64 * i >= nv) continue;
+        uint4 oh, ol;
+        float ss = 0.f;
+        auto v = [&](int e) { return __builtin_fmaf(r, gw[i][e], -k * xv[i][e]); };
+        hilo_update2(0u, 0u, v(0), v(1), oh.x, ol.x, ss);
+        hilo_update2(0u, 0u, v(2), v(3), oh.y, ol.y, ss);
+        hilo_update2(0u, 0u, v(4), v(5), oh.z, ol.z, ss);
+        hilo_update2(0u, 0u, v(6), v(7), oh.w, ol.w, ss);
+        dh_[lane + 64 * i] = oh;
+        dl_[lane + 64 * i] = ol;
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int col = lane + 64 * i;
+    if (col < nv) {
+      *reinterpret_cast<float4*>(&red[wave][col * 8]) = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+      *reinterpret_cast<float4*>(&red[wave][col * 8 + 4]) = make_float4(acc[i][4], acc[i][5], acc[i][6], acc[i][7]);
+    }
+  }
+  __syncthreads();
+  float* dst = dw_part + (size_t)blockIdx.x * D;
+  for (int col = threadIdx.x; col < D; col += 256) dst[col] = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
+}
+
+// ------------------------------------------------------------------------------------------
 // embedding backward:  d table[v] = sum over the tokens t with ids[t] == v, in token order, of dx[t]  (no float atomics).
 // grid = (vocab, ceil(D / 256)); the workgroup scans the pass's ids 256 at a time, ballots the matches and walks the set
 // bits in order (uniform control flow).

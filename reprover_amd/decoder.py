@@ -402,6 +402,26 @@ class HipT5Decoder:
         return scores, toks, par
 
 
+def packed_pairs(cfg: Dict, state_ids, state_mask, tactic_ids):
+    """The reference's padded (state_ids, state_mask, tactic_ids) batch as packed pairs: (source ids [sum S_b], src_cu,
+    decoder input tokens, labels, tgt_cu), the form the encoder passes and ``rp_decoder_forward`` /
+    ``rp_decoder_loss_grad`` take."""
+    ids = np.asarray(state_ids.cpu() if isinstance(state_ids, torch.Tensor) else state_ids).astype(np.int64)
+    n_src = source_lengths(state_mask)
+    if ids.shape != tuple(state_mask.shape):
+        raise ValueError(f"state_ids {ids.shape} and state_mask {tuple(state_mask.shape)} disagree")
+    tokens, labels, tgt_cu = shift_and_segment(tactic_ids, cfg.get("decoder_start_token_id", 0), 0)
+    if len(tgt_cu) - 1 != len(n_src):
+        raise ValueError("state_ids and tactic_ids hold different batch sizes")
+    if (labels >= cfg["vocab_size"]).any():
+        raise ValueError(f"tactic_ids holds ids >= vocab_size={cfg['vocab_size']}")
+    if ((np.diff(tgt_cu) > 0) & (n_src == 0)).any():
+        raise ValueError("a pair with counted labels has an empty source")
+    src_cu = np.concatenate([[0], np.cumsum(n_src)]).astype(np.int32)
+    packed = np.concatenate([ids[b, :n] for b, n in enumerate(n_src)]) if len(n_src) else np.zeros(0)
+    return packed, src_cu, tokens, labels, tgt_cu
+
+
 class HipT5Generator:
     """Encoder + decoder of one T5ForConditionalGeneration checkpoint on one GPU."""
 
@@ -452,22 +472,6 @@ class HipT5Generator:
                        "rp_encode_hidden")
         return out
 
-    def _packed_pairs(self, state_ids, state_mask, tactic_ids):
-        ids = np.asarray(state_ids.cpu() if isinstance(state_ids, torch.Tensor) else state_ids).astype(np.int64)
-        n_src = source_lengths(state_mask)
-        if ids.shape != tuple(state_mask.shape):
-            raise ValueError(f"state_ids {ids.shape} and state_mask {tuple(state_mask.shape)} disagree")
-        tokens, labels, tgt_cu = shift_and_segment(tactic_ids, self.cfg.get("decoder_start_token_id", 0), 0)
-        if len(tgt_cu) - 1 != len(n_src):
-            raise ValueError("state_ids and tactic_ids hold different batch sizes")
-        if (labels >= self.cfg["vocab_size"]).any():
-            raise ValueError(f"tactic_ids holds ids >= vocab_size={self.cfg['vocab_size']}")
-        if ((np.diff(tgt_cu) > 0) & (n_src == 0)).any():
-            raise ValueError("a pair with counted labels has an empty source")
-        src_cu = np.concatenate([[0], np.cumsum(n_src)]).astype(np.int32)
-        packed = np.concatenate([ids[b, :n] for b, n in enumerate(n_src)]) if len(n_src) else np.zeros(0)
-        return packed, src_cu, tokens, labels, tgt_cu
-
     def loss_and_grads(self, state_ids, state_mask, tactic_ids):
         """(loss, gradients, d_enc) of ``forward``'s loss (``rp_decoder_loss_grad``; no dropout).
         ``gradients`` maps the HF state-dict names of the decoder's parameters (``shared.weight``, ``lm_head.weight``
@@ -475,7 +479,7 @@ class HipT5Generator:
         ``decoder.final_layer_norm.weight``, ``decoder.block.i.layer...``) to fp32 views of one flat device buffer;
         ``d_enc`` is d loss / d encoder_last_hidden_state packed ``[sum S_b, d_model]`` fp32.  With no counted label the
         loss is NaN and every gradient 0."""
-        packed, src_cu, tokens, labels, tgt_cu = self._packed_pairs(state_ids, state_mask, tactic_ids)
+        packed, src_cu, tokens, labels, tgt_cu = packed_pairs(self.cfg, state_ids, state_mask, tactic_ids)
         S = int(src_cu[-1])
         enc = self.encode_hidden_packed(packed, src_cu) if S else torch.empty((0, self.cfg["d_model"]),
                                                                               dtype=torch.bfloat16, device=self.device)
@@ -486,7 +490,7 @@ class HipT5Generator:
         return (s / c if c else float("nan")), grads, d_enc
 
     def _teacher_forced(self, state_ids, state_mask, tactic_ids, rows: bool = False):
-        packed, src_cu, tokens, labels, tgt_cu = self._packed_pairs(state_ids, state_mask, tactic_ids)
+        packed, src_cu, tokens, labels, tgt_cu = packed_pairs(self.cfg, state_ids, state_mask, tactic_ids)
         enc = self.encode_hidden_packed(packed, src_cu) if int(tgt_cu[-1]) else None
         lp, sc, lp_rows = self.decoder.forward(enc, src_cu, tokens, labels, tgt_cu, rows)
         return lp, tgt_cu, sc, lp_rows
@@ -590,3 +594,46 @@ class HipT5Generator:
             n, num_samples, max_length, seeds, length_penalty, eos_token_id=eos,
             decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
             device=self.device)
+
+
+class HipSeq2SeqGradients:
+    """d loss / d every parameter of a T5ForConditionalGeneration for the reference's ``training_step`` loss
+    (``generation/model.py:117-121``), in one deterministic pass without dropout:
+    ``HipT5Trainer.forward_hidden`` (the encoder with saved activations) -> ``HipT5Decoder.loss_grad`` (the loss, the
+    decoder's gradients and d_enc) -> ``HipT5Trainer.backward_hidden`` (the encoder's gradients from d_enc).
+
+    Holds the encoder's fp32 masters (``self.trainer``) and the decoder (``self.decoder``).  No optimizer, no weight
+    reload and no ``fit`` here: those layers go on top of this gradient."""
+
+    def __init__(self, cfg: Dict, sd: Dict[str, torch.Tensor], device):
+        from .train import HipT5Trainer
+
+        self.cfg = dict(cfg)
+        self.device = _require_gpu(device)
+        enc_sd = {k: v for k, v in sd.items() if k.startswith("encoder.") or k == "shared.weight"}
+        self.trainer = HipT5Trainer(cfg, enc_sd, self.device, dropout_rate=0.0)
+        self.decoder = HipT5Decoder(cfg, sd, self.device)
+        self.last_d_enc: Optional[torch.Tensor] = None
+
+    def loss_and_grads(self, state_ids, state_mask, tactic_ids):
+        """(loss, grads) for padded int batches as the reference's collate makes them.  ``grads`` maps every parameter
+        name of the HF model (``shared.weight``, every ``encoder.*`` and ``decoder.*`` weight, ``lm_head.weight`` when the
+        head is untied) to an fp32 device tensor of HF's shape.  ``shared.weight`` is the encoder's embedding gradient +
+        the decoder's ``shared`` entry (which holds the tied head's), added on the device in that order; the other
+        ``encoder.*`` entries are views of the trainer's flat gradient buffer, which the next call overwrites.  ``loss``
+        is ``rp_decoder_loss_grad``'s on the trainer's hidden rows; with no counted label it is NaN and every gradient 0.
+        A pair with an empty source raises ``ValueError`` (the trainer takes at least one token per sequence).  d_enc of
+        the call is kept in ``last_d_enc``."""
+        packed, src_cu, tokens, labels, tgt_cu = packed_pairs(self.cfg, state_ids, state_mask, tactic_ids)
+        if len(src_cu) < 2 or int(np.diff(src_cu).min()) <= 0:
+            raise ValueError("every pair needs a source of at least one token")
+        hidden = self.trainer.forward_hidden(packed, src_cu)
+        _, (s, c), flat, d_enc = self.decoder.loss_grad(hidden, src_cu, tokens, labels, tgt_cu, want_d_enc=True)
+        self.trainer.backward_hidden(d_enc)
+        self.last_d_enc = d_enc
+        names, off = self.decoder.grad_layout()
+        shapes = self.decoder.grad_shapes()
+        grads = {n: flat[int(off[i]) : int(off[i]) + int(np.prod(shapes[n]))].view(shapes[n]) for i, n in enumerate(names)}
+        for name, g in self.trainer.named_gradients():
+            grads[name] = torch.add(g, grads[name]) if name == "shared.weight" else g
+        return (s / c if c else float("nan")), grads

@@ -263,6 +263,43 @@ class HipT5Trainer:
                                                    self._ws.numel(), _lib.current_stream()), "rp_train_backward")
         return self.grads
 
+    def forward_hidden(self, ids: np.ndarray, cu: np.ndarray) -> torch.Tensor:
+        """last_hidden_state [total_tokens, d_model] bf16 of the packed sequences (``rp_train_forward_hidden``: the same
+        layers as ``forward``, the final RMSNorm's rows instead of the pooled embedding); the activations stay in the
+        workspace for ``backward_hidden``.  Without dropout only."""
+        if self.dropout_rate > 0:
+            raise ValueError(f"forward_hidden runs without dropout (dropout_rate={self.dropout_rate}): the decoder behind "
+                             "it has none")
+        batch, T = len(cu) - 1, int(cu[-1])
+        if batch <= 0 or T <= 0 or len(ids) != T or int(np.diff(cu).min()) <= 0:
+            raise ValueError("forward_hidden needs at least one token per sequence")
+        _lib.check(self._lib.rp_trainer_set_dropout(self._handle, 0.0, 0), "rp_trainer_set_dropout")
+        with torch.cuda.device(self.device):
+            ids_d = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(self.device)
+            cu_d = torch.from_numpy(np.ascontiguousarray(cu, dtype=np.int32)).to(self.device)
+            ws = self._workspace(self._lib.rp_train_workspace_bytes(self._handle, T, batch))
+            out = torch.empty((T, self.cfg["d_model"]), dtype=torch.bfloat16, device=self.device)
+            _lib.check(self._lib.rp_train_forward_hidden(self._handle, _lib.ptr(ids_d), _lib.ptr(cu_d), batch, T,
+                                                         _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
+                       "rp_train_forward_hidden")
+        self._pass = (ids_d, cu_d, batch, T)
+        return out
+
+    def backward_hidden(self, d_hidden: torch.Tensor) -> torch.Tensor:
+        """d loss / d every parameter (the flat gradient buffer, overwritten) from d loss / d last_hidden_state
+        [total_tokens, d_model] fp32 (``rp_decoder_loss_grad``'s d_enc); follows ``forward_hidden``."""
+        if self.dropout_rate > 0:
+            raise ValueError(f"backward_hidden runs without dropout (dropout_rate={self.dropout_rate})")
+        assert self._pass is not None, "backward_hidden() follows forward_hidden()"
+        ids_d, cu_d, batch, T = self._pass
+        assert d_hidden.shape == (T, self.cfg["d_model"]) and d_hidden.dtype == torch.float32 and d_hidden.is_contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_train_backward_hidden(self._handle, _lib.ptr(self.params), _lib.ptr(ids_d), _lib.ptr(cu_d),
+                                                          batch, T, _lib.ptr(d_hidden), _lib.ptr(self.grads),
+                                                          _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
+                       "rp_train_backward_hidden")
+        return self.grads
+
     def current_lr(self) -> float:
         return self.lr * warmup_factor(self.steps, self.warmup_steps)
 

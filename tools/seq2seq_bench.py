@@ -12,6 +12,13 @@ holds attention, norms, the loss and the metadata copy), and the same pairs' per
 rp_decoder_forward and rp_decoder_loss_grad alternate in one process, and the result holds both medians and their ratio.
 
     python tools/seq2seq_bench.py --grad --out profiles/seq2seq_grad_bench.json
+
+--full-grad times the whole model's gradient (HipSeq2SeqGradients) at the reference's training
+batch (generation/confs/cli_lean4_random.yaml: batch 8, 2300-byte sources, 512-label targets): the full call and the
+decoder-only HipT5Generator.loss_and_grads alternate in one process; a separate profiled pass (rp_profile_read) gives the two
+head kernels' times, turned into bytes/s from the bytes their shapes need.  No threshold: figures only.
+
+    python tools/seq2seq_bench.py --full-grad --out profiles/seq2seq_full_grad_bench.json
 """
 from __future__ import annotations
 
@@ -28,7 +35,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from reprover_amd import synth  # noqa: E402
-from reprover_amd.decoder import HipT5Generator, shift_and_segment  # noqa: E402
+from reprover_amd import _lib  # noqa: E402
+from reprover_amd.decoder import HipSeq2SeqGradients, HipT5Generator, shift_and_segment  # noqa: E402
+
+HBM_PEAK = 8.0e12       # MI355X HBM3E, bytes/s (spec)
+HBM_MEASURED = 6.29e12  # a float4 copy on the same part: the achievable ceiling
 
 
 def _time(fn, iters):
@@ -83,6 +94,58 @@ def _grad_leg(a, gen, enc, src_cu, rng):
             fh.write(line + "\n")
 
 
+def _full_grad_leg(a, dev):
+    B, S, T = 8, 2300, 512
+    cfg = synth.seq2seq_config("byt5-small")
+    sd = synth.synth_seq2seq_state_dict(cfg, scale="hf")
+    full, dec_only = HipSeq2SeqGradients(cfg, sd, dev), HipT5Generator(cfg, sd, dev)
+    rng = np.random.default_rng(0)
+    ids = np.stack([_source(S, 100 + b) for b in range(B)]).astype(np.int64)
+    mask = np.ones_like(ids)
+    y = np.concatenate([rng.integers(3, 259, size=(B, T - 1)), np.ones((B, 1), np.int64)], 1)
+    legs = (("full", lambda: full.loss_and_grads(ids, mask, y)), ("decoder_only", lambda: dec_only.loss_and_grads(ids, mask, y)))
+    for _ in range(2):  # warm-up of every shape the timed window uses
+        for _, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k, _ in legs}
+    for _ in range(a.iters):  # alternating: both see the same clocks and the same neighbours
+        for k, fn in legs:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()  # ends in a device-to-host copy of the loss sums: host clock around synchronised work
+            torch.cuda.synchronize()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    f_ms, d_ms = float(np.median(ts["full"])), float(np.median(ts["decoder_only"]))
+    # the encoder's share: the full call's forward_hidden + backward_hidden against the decoder-only call's inference pass
+    _lib.profile_enable(True)
+    legs[0][1]()
+    torch.cuda.synchronize()
+    prof = _lib.profile_read(heads=True)
+    _lib.profile_enable(False)
+    Tn, D = B * S, cfg["d_model"]
+    heads = {}
+    for name, nbytes in (("hidden_head", Tn * D * (2 + 2 + 2)), ("bwd_hidden_head", Tn * D * (2 + 2 + 4 + 2 + 2))):
+        ms, n = prof[name]
+        rate = nbytes / (ms * 1e-3) if ms > 0 else float("nan")
+        heads[name] = dict(ms=round(ms, 4), launches=int(n), bytes=int(nbytes), tb_per_s=round(rate / 1e12, 3),
+                           of_hbm_peak=round(rate / HBM_PEAK, 3), of_measured_copy_rate=round(rate / HBM_MEASURED, 3))
+    result = dict(metric="seq2seq_full_grad_bench", measured=True, model="byt5-small (synthetic, hf)", batch=B, source_bytes=S,
+                  target_labels=T, source_tokens=Tn, iters=a.iters, full_ms=round(f_ms, 3), decoder_only_ms=round(d_ms, 3),
+                  encoder_backward_share=round((f_ms - d_ms) / f_ms, 4), full_ms_per_1k_source_tokens=round(f_ms / Tn * 1e3, 3),
+                  full_ms_all=[round(x, 3) for x in ts["full"]], decoder_only_ms_all=[round(x, 3) for x in ts["decoder_only"]],
+                  head_kernels=heads,
+                  profiled_pass_ms_by_class={k: round(v[0], 3) for k, v in prof.items() if v[1]},
+                  note="full = trainer forward with saved activations + decoder loss_grad + encoder backward + the shared sum; "
+                       "decoder_only = inference encoder pass + decoder loss_grad; encoder_backward_share = what the full call "
+                       "adds over it; head kernel rates = bytes their shapes need (both planes, d_hidden, outputs) / profiled time")
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -93,8 +156,11 @@ def main():
     ap.add_argument("--step-tokens", type=int, default=16)
     ap.add_argument("--out")
     ap.add_argument("--grad", action="store_true", help="time rp_decoder_loss_grad against rp_decoder_forward")
+    ap.add_argument("--full-grad", action="store_true", help="time HipSeq2SeqGradients against the decoder-only gradients")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.full_grad:
+        return _full_grad_leg(a, dev)
     cfg = synth.seq2seq_config("byt5-small")
     gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg, scale="sharp"), dev)
     B, S = a.batch, a.src_bytes
