@@ -683,6 +683,17 @@ RpStatus rp_decoder_loss_grad(RpDecoder* dec, const void* enc_bf16, const int32_
                               double* loss_sum_count, float* grads, float* d_enc, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* Refresh every resident copy of the decoder's weights from fp32 masters (after an optimizer step); DESIGN.md section 14.
+ *   params  device fp32 [layout total], 16-byte aligned, in exactly rp_decoder_grad_layout's order and offsets (with the
+ *           tied head, lm_head is taken from shared)
+ * Afterwards the fp32 embedding and norm vectors, the bf16 operands (lm_head, the fused self QKV, o, cross q / o, the
+ * cross K | V concatenation of all layers, wi_0 | wi_1, wo), the interleaved FFN-in copy and the expanded bias table hold
+ * the bits rp_decoder_create(..., RP_DT_F32, ...) packs from the same values: every element is rounded once, from the
+ * master.  One grid-stride launch over a device-resident descriptor table built at create; launch-only (no allocation,
+ * host copy or synchronisation), everything on `stream`.  Profile class RP_K_OPTIMIZER.  A null dec or params returns
+ * RP_E_INVALID and nothing is launched. */
+RpStatus rp_decoder_load_params(RpDecoder* dec, const float* params, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

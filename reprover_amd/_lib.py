@@ -249,6 +249,7 @@ SIGNATURES = {
     ),
     "rp_decoder_grad_tensors": (C.c_int32, [C.c_void_p]),
     "rp_decoder_grad_layout": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "rp_decoder_load_params": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rp_decoder_loss_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "rp_decoder_loss_grad": (
         C.c_int32,

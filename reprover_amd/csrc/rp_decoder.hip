@@ -429,6 +429,66 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restric
   }
 }
 
+// ---- rp_decoder_load_params: every resident copy refreshed from one flat fp32 buffer -------------------------------------
+// One table entry per (source tensor, resident copy): n source elements at params + src go to dst (and, for RL_BF16_IL,
+// row-permuted to dst2 as well).  The table is cut into chunks of RL_CHUNK elements, chunk0 = the entry's first chunk; a
+// workgroup finds the entry of its chunk by a binary search over chunk0, so small and large tensors share one grid evenly
+// and no entry depends on another (each reads the fp32 master and rounds each element once).
+enum { RL_F32 = 0, RL_BF16 = 1, RL_BF16_IL = 2, RL_BIAS = 3 };
+constexpr int RL_CHUNK = 8192;      // elements: 256 threads x 4 rounds x 8 elements (32 B read, 16 B written per thread)
+constexpr int RL_MAX_BLOCKS = 2048;  // 8 workgroups per CU; the rest is grid-strided
+struct DecReloadEntry {
+  int64_t src;   // element offset into params (a multiple of 64)
+  int64_t n;     // elements; a multiple of 8 except for RL_BIAS (dst elements: H * nbias)
+  void* dst;
+  void* dst2;    // RL_BF16_IL: wi_il's layer base
+  int32_t chunk0, kind;
+  int32_t cols;  // RL_BF16_IL: d_model; RL_BIAS: nbias
+  int32_t aux;   // RL_BF16_IL: 0 (wi_0: the gate rows) or 32 (wi_1: the up rows); RL_BIAS: H
+};
+
+__global__ __launch_bounds__(256) void dec_reload_kernel(const DecReloadEntry* __restrict__ tab, int n_entries, int n_chunks,
+                                                         const float* __restrict__ params,
+                                                         const int32_t* __restrict__ bucket) {
+  for (int ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
+    int lo = 0, hi = n_entries - 1;  // the last entry with chunk0 <= ch (block-uniform)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (tab[mid].chunk0 <= ch) lo = mid;
+      else hi = mid - 1;
+    }
+    const DecReloadEntry e = tab[lo];
+    const int64_t base = (int64_t)(ch - e.chunk0) * RL_CHUNK;
+    const float* __restrict__ src = params + e.src;
+    if (e.kind == RL_BIAS) {  // dst[h, j] = rel_bias[bucket[j], h]: a gather, no arithmetic
+      const int64_t end = base + RL_CHUNK < e.n ? base + RL_CHUNK : e.n;
+      for (int64_t i = base + threadIdx.x; i < end; i += 256) {
+        const int h = (int)(i / e.cols), j = (int)(i - (int64_t)h * e.cols);
+        reinterpret_cast<float*>(e.dst)[i] = src[(int64_t)bucket[j] * e.aux + h];
+      }
+      continue;
+    }
+#pragma unroll
+    for (int it = 0; it < RL_CHUNK / 2048; ++it) {
+      const int64_t i = base + (int64_t)(it * 256 + threadIdx.x) * 8;
+      if (i >= e.n) break;
+      const float4 a = *reinterpret_cast<const float4*>(src + i), b = *reinterpret_cast<const float4*>(src + i + 4);
+      if (e.kind == RL_F32) {
+        *reinterpret_cast<float4*>(reinterpret_cast<float*>(e.dst) + i) = a;
+        *reinterpret_cast<float4*>(reinterpret_cast<float*>(e.dst) + i + 4) = b;
+        continue;
+      }
+      const uint4 v = make_uint4(pack_bf2(a.x, a.y), pack_bf2(a.z, a.w), pack_bf2(b.x, b.y), pack_bf2(b.z, b.w));
+      *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(e.dst) + i) = v;
+      if (e.kind == RL_BF16_IL) {  // dec_interleave_kernel's row map, from the source side (cols % 8 == 0: one row)
+        const int64_t r = i / e.cols, c = i - r * e.cols;
+        const int64_t row = (r >> 5) * 64 + (r & 31) + e.aux;
+        *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(e.dst2) + row * e.cols + c) = v;
+      }
+    }
+  }
+}
+
 struct DecWs {
   bf16_t* ckv;    // [sum S, L * 2 * inner]
   bf16_t* cache;  // [n][L][max_len * nb, 2 * inner]
@@ -539,6 +599,63 @@ RpStatus dec_pack(RpDecoder* d, const RpT5DecoderWeights* w) {
   return RP_OK;
 }
 
+// the descriptor table of rp_decoder_load_params and the bias table's bucket index, made once (dec_pack has run)
+RpStatus dec_reload_table(RpDecoder* d) {
+  const RpT5Config& c = d->cfg;
+  const int64_t D = c.d_model, F = c.d_ff, ID = (int64_t)d->inner * D, V = c.vocab_size;
+  const int L = c.num_layers, H = c.num_heads;
+  std::vector<int64_t> off((size_t)rp_decoder_grad_tensors(d) + 1);
+  RpStatus st = rp_decoder_grad_layout(d, off.data());
+  if (st) return st;
+  std::vector<DecReloadEntry> tab;
+  int64_t chunks = 0;
+  auto add = [&](int kind, int64_t src, int64_t n, void* dst, void* dst2 = nullptr, int cols = 0, int aux = 0) {
+    tab.push_back(DecReloadEntry{src, n, dst, dst2, (int32_t)chunks, kind, cols, aux});
+    chunks += (n + RL_CHUNK - 1) / RL_CHUNK;
+  };
+  int t = 0;  // the layout's tensor index, in rp_decoder_grad_layout's order
+  add(RL_F32, off[t], V * D, d->embed);
+  if (d->tied) add(RL_BF16, off[t], V * D, d->lm_head);
+  ++t;
+  if (!d->tied) add(RL_BF16, off[t++], V * D, d->lm_head);
+  add(RL_BIAS, off[t++], (int64_t)H * d->nbias, d->bias_tab, nullptr, d->nbias, H);
+  add(RL_F32, off[t++], D, d->final_ln);
+  for (int i = 0; i < L; ++i) {
+    const RpDecoder::Layer& l = d->layers[i];
+    bf16_t* ckv = d->cross_kv_w + (size_t)2 * i * ID;
+    bf16_t* il = d->wi_il ? d->wi_il + (size_t)i * 2 * F * D : nullptr;
+    const int wi_kind = il ? RL_BF16_IL : RL_BF16;
+    add(RL_F32, off[t++], D, l.ln_self);
+    add(RL_BF16, off[t++], ID, l.wqkv);
+    add(RL_BF16, off[t++], ID, l.wqkv + ID);
+    add(RL_BF16, off[t++], ID, l.wqkv + 2 * ID);
+    add(RL_BF16, off[t++], ID, l.wo);
+    add(RL_F32, off[t++], D, l.ln_cross);
+    add(RL_BF16, off[t++], ID, l.cq);
+    add(RL_BF16, off[t++], ID, ckv);
+    add(RL_BF16, off[t++], ID, ckv + ID);
+    add(RL_BF16, off[t++], ID, l.co);
+    add(RL_F32, off[t++], D, l.ln_ff);
+    add(wi_kind, off[t++], F * D, l.wi, il, (int)D, 0);
+    add(wi_kind, off[t++], F * D, l.wi + F * D, il, (int)D, 32);
+    add(RL_BF16, off[t++], F * D, l.wo2);
+  }
+  if (t + 1 != (int)off.size() || chunks > INT32_MAX) return fail(RP_E_INVALID, "decoder reload table: %d tensors", t);
+  for (const DecReloadEntry& e : tab)  // the vector path moves 8 elements at a time (d_model and d_ff are multiples of 8)
+    if (e.kind != RL_BIAS && (e.n % 8 || e.src % 8)) return fail(RP_E_UNSUPPORTED, "decoder reload: tensor of %lld elements", (long long)e.n);
+  std::vector<int32_t> bk((size_t)d->nbias);
+  for (int j = 0; j < d->nbias; ++j) bk[j] = rp_relative_position_bucket_causal(-j, c.rel_num_buckets, c.rel_max_distance);
+  RP_HIP(hipMalloc((void**)&d->bias_bucket, bk.size() * 4));
+  d->allocs.push_back(d->bias_bucket);
+  RP_HIP(hipMalloc(&d->reload_tab, tab.size() * sizeof(DecReloadEntry)));
+  d->allocs.push_back(d->reload_tab);
+  RP_HIP(hipMemcpy(d->bias_bucket, bk.data(), bk.size() * 4, hipMemcpyHostToDevice));
+  RP_HIP(hipMemcpy(d->reload_tab, tab.data(), tab.size() * sizeof(DecReloadEntry), hipMemcpyHostToDevice));
+  d->reload_entries = (int)tab.size();
+  d->reload_chunks = (int)chunks;
+  return RP_OK;
+}
+
 // the caps of a call; total_src = src_cu[n]
 RpStatus dec_check(const RpDecoder* d, const int32_t* src_cu, int n, int nb, int max_len, int& total_src) {
   RP_REQUIRE(d, "null decoder");
@@ -588,11 +705,27 @@ extern "C" RpStatus rp_decoder_create(const RpT5Config* cfg, const RpT5DecoderWe
   d->inner = cfg->num_heads * cfg->d_kv;
   d->tied = weights->tie_word_embeddings ? 1 : 0;
   RpStatus st = weight_dtype == RP_DT_F32 ? dec_pack<float>(d, weights) : dec_pack<bf16_t>(d, weights);
+  if (st == RP_OK) st = dec_reload_table(d);
   if (st != RP_OK) {
     rp_decoder_destroy(d);
     return st;
   }
   *out = d;
+  return RP_OK;
+}
+
+// Refresh every resident copy of the weights (dec_pack's: the fp32 tables, the bf16 operands, the cross K/V
+// concatenation, the interleaved FFN-in copy, the expanded bias table) from the fp32 masters in rp_decoder_grad_layout's
+// order: one grid-stride launch over the descriptor table.  Launch-only.
+extern "C" RpStatus rp_decoder_load_params(RpDecoder* d, const float* params, void* stream_) {
+  RP_REQUIRE(d && params, "null argument");
+  RP_REQUIRE(((uintptr_t)params & 15) == 0, "params is not 16-byte aligned");
+  hipStream_t stream = (hipStream_t)stream_;
+  ProfScope ps(stream, RP_K_OPTIMIZER);
+  hipLaunchKernelGGL(dec_reload_kernel, dim3(std::min(d->reload_chunks, RL_MAX_BLOCKS)), dim3(256), 0, stream,
+                     (const DecReloadEntry*)d->reload_tab, d->reload_entries, d->reload_chunks, params,
+                     (const int32_t*)d->bias_bucket);
+  RP_CHECK_LAUNCH();
   return RP_OK;
 }
 

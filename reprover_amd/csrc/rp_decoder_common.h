@@ -85,5 +85,10 @@ struct RpDecoder {
   // rp_decoder_forward's FFN-in operand (packed at create time): per layer [wi_0; wi_1] re-ordered into 64-row blocks of
   // 32 gate rows then the same 32 up rows, [L][2 * d_ff, d_model] bf16
   bf16_t* wi_il = nullptr;
+  // rp_decoder_load_params (rp_decoder.hip): the device-resident descriptor table of every resident copy above, built once
+  // at create, and the distance -> bucket index of bias_tab's columns (nbias int32)
+  void* reload_tab = nullptr;
+  int32_t* bias_bucket = nullptr;
+  int reload_entries = 0, reload_chunks = 0;
   std::vector<void*> allocs;
 };

@@ -135,6 +135,33 @@ def _pc(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+REL_BIAS_KEY_DEC = "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"
+
+
+def decoder_grad_names(cfg: Dict, tied: bool) -> List[str]:
+    """HF state-dict names of the decoder's flat layout (``rp_decoder_grad_layout``), in buffer order; ``tied``: the
+    decoder was created with the tied head and has no ``lm_head.weight`` slot."""
+    names = ["shared.weight"] + ([] if tied else ["lm_head.weight"]) + [REL_BIAS_KEY_DEC, "decoder.final_layer_norm.weight"]
+    for i in range(cfg["num_decoder_layers"]):
+        names += [f"decoder.block.{i}.{key}" for key in _DEC_KEYS.values()]
+    return names
+
+
+def decoder_grad_shapes(cfg: Dict) -> Dict[str, Tuple[int, ...]]:
+    """HF shape of every tensor ``decoder_grad_names`` can name."""
+    c = cfg
+    D, F, inner, V = c["d_model"], c["d_ff"], c["num_heads"] * c["d_kv"], c["vocab_size"]
+    sh = {"ln_self": (D,), "q": (inner, D), "k": (inner, D), "v": (inner, D), "o": (D, inner), "ln_cross": (D,),
+          "cq": (inner, D), "ck": (inner, D), "cv": (inner, D), "co": (D, inner), "ln_ff": (D,), "wi_0": (F, D),
+          "wi_1": (F, D), "wo": (D, F)}
+    out = {"shared.weight": (V, D), "lm_head.weight": (V, D), "decoder.final_layer_norm.weight": (D,),
+           REL_BIAS_KEY_DEC: (c.get("relative_attention_num_buckets", 32), c["num_heads"])}
+    for i in range(c["num_decoder_layers"]):
+        for fld, key in _DEC_KEYS.items():
+            out[f"decoder.block.{i}.{key}"] = sh[fld]
+    return out
+
+
 class HipT5Decoder:
     """The decoder weights resident on one GPU + the per-step launch sequence."""
 
@@ -251,30 +278,23 @@ class HipT5Decoder:
         n = int(self._lib.rp_decoder_grad_tensors(self._handle))
         off = np.zeros(n + 1, dtype=np.int64)
         _lib.check(self._lib.rp_decoder_grad_layout(self._handle, off.ctypes.data_as(C.c_void_p)), "rp_decoder_grad_layout")
-        L = self.cfg["num_decoder_layers"]
-        names = ["shared.weight"]
-        if n == 4 + 14 * L:
-            names.append("lm_head.weight")
-        names += ["decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", "decoder.final_layer_norm.weight"]
-        for i in range(L):
-            names += [f"decoder.block.{i}.{key}" for key in _DEC_KEYS.values()]
+        names = decoder_grad_names(self.cfg, tied=n != 4 + 14 * self.cfg["num_decoder_layers"])
         assert len(names) == n, (len(names), n)
         return names, off
 
     def grad_shapes(self) -> Dict[str, Tuple[int, ...]]:
         """HF shape of every tensor of ``grad_layout``."""
-        c = self.cfg
-        D, F, inner, V = c["d_model"], c["d_ff"], c["num_heads"] * c["d_kv"], c["vocab_size"]
-        sh = {"ln_self": (D,), "q": (inner, D), "k": (inner, D), "v": (inner, D), "o": (D, inner), "ln_cross": (D,),
-              "cq": (inner, D), "ck": (inner, D), "cv": (inner, D), "co": (D, inner), "ln_ff": (D,), "wi_0": (F, D),
-              "wi_1": (F, D), "wo": (D, F)}
-        out = {"shared.weight": (V, D), "lm_head.weight": (V, D), "decoder.final_layer_norm.weight": (D,),
-               "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight":
-                   (c.get("relative_attention_num_buckets", 32), c["num_heads"])}
-        for i in range(c["num_decoder_layers"]):
-            for fld, key in _DEC_KEYS.items():
-                out[f"decoder.block.{i}.{key}"] = sh[fld]
-        return out
+        return decoder_grad_shapes(self.cfg)
+
+    def load_params(self, flat: torch.Tensor) -> None:
+        """Refresh every resident copy of the weights from fp32 masters in ``grad_layout``'s flat form
+        (``rp_decoder_load_params``: one launch on the current stream, nothing else)."""
+        assert flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous()
+        if flat.numel() != int(self.grad_layout()[1][-1]):
+            raise ValueError(f"load_params: {flat.numel()} floats for a layout of {int(self.grad_layout()[1][-1])}")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_load_params(self._handle, flat.data_ptr(), _lib.current_stream()),
+                       "rp_decoder_load_params")
 
     def loss_grad(self, enc_bf16: torch.Tensor, src_cu: np.ndarray, tokens: np.ndarray, labels: np.ndarray,
                   tgt_cu: np.ndarray, want_d_enc: bool = True, grads: Optional[torch.Tensor] = None):
@@ -436,6 +456,15 @@ class HipT5Generator:
     def from_pretrained(cls, path: str, device) -> "HipT5Generator":
         cfg, sd = load_seq2seq_checkpoint(path)
         return cls(cfg, sd, device)
+
+    @classmethod
+    def from_parts(cls, cfg: Dict, encoder: HipT5Encoder, decoder: "HipT5Decoder", device) -> "HipT5Generator":
+        """A generator over engines that live elsewhere (``HipSeq2SeqTrainer.generator``: the trainer's inference
+        encoder and its decoder): no second copy of any weight; whoever refreshes those engines refreshes this."""
+        self = cls.__new__(cls)
+        self.cfg, self.device = dict(cfg), _require_gpu(device)
+        self.encoder, self.decoder = encoder, decoder
+        return self
 
     def encode_hidden(self, ids: np.ndarray) -> torch.Tensor:
         """last_hidden_state [S, d_model] bf16 of one source (int ids including the final EOS)."""
@@ -615,6 +644,9 @@ class HipSeq2SeqGradients:
         self.decoder = HipT5Decoder(cfg, sd, self.device)
         self.last_d_enc: Optional[torch.Tensor] = None
 
+    # the decoder's flat gradient buffer: None = a fresh zeroed one per call; HipSeq2SeqTrainer keeps one for its optimizer
+    dec_grads: Optional[torch.Tensor] = None
+
     def loss_and_grads(self, state_ids, state_mask, tactic_ids):
         """(loss, grads) for padded int batches as the reference's collate makes them.  ``grads`` maps every parameter
         name of the HF model (``shared.weight``, every ``encoder.*`` and ``decoder.*`` weight, ``lm_head.weight`` when the
@@ -628,7 +660,8 @@ class HipSeq2SeqGradients:
         if len(src_cu) < 2 or int(np.diff(src_cu).min()) <= 0:
             raise ValueError("every pair needs a source of at least one token")
         hidden = self.trainer.forward_hidden(packed, src_cu)
-        _, (s, c), flat, d_enc = self.decoder.loss_grad(hidden, src_cu, tokens, labels, tgt_cu, want_d_enc=True)
+        _, (s, c), flat, d_enc = self.decoder.loss_grad(hidden, src_cu, tokens, labels, tgt_cu, want_d_enc=True,
+                                                        grads=self.dec_grads)
         self.trainer.backward_hidden(d_enc)
         self.last_d_enc = d_enc
         names, off = self.decoder.grad_layout()

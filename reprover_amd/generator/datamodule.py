@@ -86,6 +86,11 @@ def load_preds(preds_path: str) -> Dict:
     return preds
 
 
+def epoch_seed(base_seed: int, epoch: int) -> int:
+    """The seed of one epoch's shuffle and premise drops: the retriever's (``retrieval/main.py::_epoch_seed``)."""
+    return (int(base_seed) * 1_000_003 + 7919 * int(epoch) + 12345) % (2 ** 63)
+
+
 class GeneratorDataModule:
     def __init__(self, data_path: str, model_name: str, batch_size: int, eval_batch_size: int, max_inp_seq_len: int,
                  max_oup_seq_len: int, p_drop: float, num_workers: int = 0, corpus_path: Optional[str] = None,
@@ -100,6 +105,8 @@ class GeneratorDataModule:
         self.num_workers = num_workers
         self.tokenizer = tokenizer or ByT5Tokenizer()  # ByT5's byte tokenizer: model_name needs no download
         self.preds = None if preds_path is None else load_preds(preds_path)
+        self.ds_train: Optional[GeneratorDataset] = None
+        self.ds_val: Optional[GeneratorDataset] = None
 
     def setup(self, stage: Optional[str] = None) -> None:
         args = (self.corpus, self.preds, self.max_inp_seq_len, self.max_oup_seq_len, self.p_drop, self.tokenizer)
@@ -107,6 +114,24 @@ class GeneratorDataModule:
             self.ds_train = GeneratorDataset(os.path.join(self.data_path, "train.json"), *args, is_train=True)
         if stage in (None, "fit", "validate"):
             self.ds_val = GeneratorDataset(os.path.join(self.data_path, "val.json"), *args, is_train=False)
+
+    def train_dataloader(self, skip: int = 0, seed: Optional[int] = None, epoch: int = 0) -> Iterator[Dict[str, Any]]:
+        """One epoch of the train split as the reference's DataLoader yields it (generation/datamodule.py:184-193:
+        ``shuffle=True, drop_last=True``), examples fetched with ``is_train=True`` so that ``p_drop`` applies.  The order
+        and the premise drops draw from ``random``; with ``seed`` given it is seeded first with ``epoch_seed(seed, epoch)``
+        (the caller's stream is its own to restore).  ``skip``: the first ``skip`` batches are consumed at the index level,
+        their examples fetched (the draws advance as in an uninterrupted epoch) but neither collated nor yielded."""
+        import random
+
+        if seed is not None:
+            random.seed(epoch_seed(seed, epoch))
+        ds = self.ds_train
+        order = list(range(len(ds)))
+        random.shuffle(order)
+        for n, i in enumerate(range(0, len(order) - self.batch_size + 1, self.batch_size)):
+            examples = [ds[j] for j in order[i : i + self.batch_size]]
+            if n >= skip:
+                yield ds.collate(examples)
 
     def val_dataloader(self) -> Iterator[Dict[str, Any]]:
         """Batches of ``eval_batch_size`` in order, the last one short (shuffle=False, drop_last=False)."""

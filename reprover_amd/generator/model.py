@@ -57,12 +57,38 @@ class RetrievalAugmentedGenerator:
         self.max_inp_seq_len, self.max_oup_seq_len = max_inp_seq_len, max_oup_seq_len
         self.ret_ckpt_path = ret_ckpt_path  # (the retriever only serves Pass@1 through the prover: not run here)
         self.tokenizer = ByT5Tokenizer()
+        self.model_name, self.device = model_name, device
+        self.train_engine = None  # HipSeq2SeqTrainer, once configure_optimizers has run
         self.generator = HipT5Generator.from_pretrained(model_name, device)
         self.topk_accuracies = {k: TopkAccuracy(k) for k in range(1, num_beams + 1)}
         self._loss_sum, self._loss_n = 0.0, 0
 
     def forward(self, state_ids, state_mask, tactic_ids) -> float:
         return self.generator.forward(state_ids, state_mask, tactic_ids)
+
+    def configure_optimizers(self, weight_decay: float = 1e-2, gradient_clip_val: Optional[float] = None):
+        """generation/model.py:134-146 (``get_optimizers``: AdamW under a constant schedule after ``warmup_steps``): builds
+        the ``HipSeq2SeqTrainer`` from the checkpoint with this model's ``lr`` and ``warmup_steps`` and re-points
+        ``self.generator`` at its inference view; the inference-only copies made by the constructor are released.
+        ``weight_decay``: 1e-2 is ``torch.optim.AdamW``'s default."""
+        from ..decoder import load_seq2seq_checkpoint
+        from ..seq2seq_train import HipSeq2SeqTrainer
+
+        cfg, sd = load_seq2seq_checkpoint(self.model_name)
+        self.generator = None  # (released before the training buffers are taken)
+        self.train_engine = HipSeq2SeqTrainer(cfg, sd, self.device, lr=self.lr, warmup_steps=self.warmup_steps,
+                                              weight_decay=weight_decay, gradient_clip_val=gradient_clip_val)
+        self.generator = self.train_engine.generator()
+        return self.train_engine
+
+    def training_step(self, batch: Dict[str, Any], batch_idx: int = 0) -> float:
+        """generation/model.py:117-132: the loss of the batch (``loss_train``), and here also the update it leads to (the
+        optimizer and the scheduler are the engine's: gradients, AdamW, re-packing of the compute copies)."""
+        if self.train_engine is None:
+            raise RuntimeError("training_step needs configure_optimizers() first")
+        loss, _ = self.train_engine.loss_and_grads(batch["state_ids"], batch["state_mask"], batch["tactic_ids"])
+        self.train_engine.optimizer_step()
+        return float(loss)
 
     def generate_batch(self, state_ids, state_mask) -> List[List[str]]:
         """num_beams decoded candidates per state (skip_special_tokens=True)."""

@@ -19,6 +19,14 @@ decoder-only HipT5Generator.loss_and_grads alternate in one process; a separate 
 head kernels' times, turned into bytes/s from the bytes their shapes need.  No threshold: figures only.
 
     python tools/seq2seq_bench.py --full-grad --out profiles/seq2seq_full_grad_bench.json
+
+--step times the whole training step (HipSeq2SeqTrainer: the same gradient, then AdamW over both halves and the re-packing
+of every compute copy) at the same batch: the full step and the --full-grad call alternate in one
+process, median of --iters (9), host clock around synchronised calls.  Separate profiled passes (rp_profile_read) give the
+RP_K_OPTIMIZER class of one step and rp_decoder_load_params alone, the latter turned into bytes/s from the bytes its table
+moves.  No threshold: figures only.
+
+    python tools/seq2seq_bench.py --step --iters 9 --out profiles/seq2seq_train_bench.json
 """
 from __future__ import annotations
 
@@ -146,6 +154,108 @@ def _full_grad_leg(a, dev):
             fh.write(line + "\n")
 
 
+def reload_bytes(cfg, tied):
+    """bytes rp_decoder_load_params reads + writes: 4 B read per master element and table entry, 2 B written per bf16 copy
+    (4 B for the FFN-in tensors, which have a second, interleaved copy), 4 B per fp32 copy"""
+    D, F, V, L, H = cfg["d_model"], cfg["d_ff"], cfg["vocab_size"], cfg["num_decoder_layers"], cfg["num_heads"]
+    ID = H * cfg["d_kv"] * D
+    nbias = 2 * cfg.get("relative_attention_max_distance", 128) + 1
+    il = 2 if F % 32 == 0 else 0
+    total = V * D * (4 + 4) + V * D * (4 + 2) + H * nbias * (4 + 4 + 4) + D * 8
+    total += L * (3 * D * 8 + 8 * ID * 6 + 2 * F * D * (6 + il) + F * D * 6)
+    return total
+
+
+def _step_leg(a, dev):
+    from reprover_amd.seq2seq_train import HipSeq2SeqTrainer
+
+    B, S, T = 8, 2300, 512
+    cfg = synth.seq2seq_config("byt5-small")
+    sd = synth.synth_seq2seq_state_dict(cfg, scale="hf")
+    trainer = HipSeq2SeqTrainer(cfg, sd, dev, lr=5e-4, warmup_steps=2000)  # the reference's generator config
+    grad_only = HipSeq2SeqGradients(cfg, sd, dev)
+    rng = np.random.default_rng(0)
+    ids = np.stack([_source(S, 100 + b) for b in range(B)]).astype(np.int64)
+    mask = np.ones_like(ids)
+    y = np.concatenate([rng.integers(3, 259, size=(B, T - 1)), np.ones((B, 1), np.int64)], 1)
+
+    def step():
+        trainer.loss_and_grads(ids, mask, y)
+        trainer.optimizer_step()
+
+    legs = (("step", step), ("full_grad", lambda: grad_only.loss_and_grads(ids, mask, y)))
+    for _ in range(2):  # warm-up of every shape the timed window uses
+        for _, fn in legs:
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k, _ in legs}
+    for _ in range(a.iters):  # alternating: both see the same clocks and the same neighbours
+        for k, fn in legs:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    s_ms, g_ms = float(np.median(ts["step"])), float(np.median(ts["full_grad"]))
+    # the optimizer end alone, unprofiled: device events around back-to-back calls
+    def events(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    reload_ms = events(lambda: trainer.decoder.load_params(trainer.dec_params), 20)
+    opt_ms = events(trainer.optimizer_step, 5)
+    # profiled passes (events around every launch group: slower host, kernel classes apart)
+    _lib.profile_enable(True)
+    step()
+    torch.cuda.synchronize()
+    prof = _lib.profile_read(heads=True)
+    _lib.profile_enable(False)
+    _lib.profile_enable(True)
+    for _ in range(10):
+        trainer.decoder.load_params(trainer.dec_params)
+    torch.cuda.synchronize()
+    rl_ms, rl_n = _lib.profile_read()["optimizer"]
+    _lib.profile_enable(False)
+    nbytes = reload_bytes(cfg, trainer.tied)
+
+    def rate(ms):
+        r = nbytes / (ms * 1e-3) if ms > 0 else float("nan")
+        return dict(ms=round(ms, 4), tb_per_s=round(r / 1e12, 3), of_hbm_peak=round(r / HBM_PEAK, 3),
+                    of_measured_copy_rate=round(r / HBM_MEASURED, 3))
+
+    n_enc, n_dec = trainer.trainer.params.numel(), trainer.dec_params.numel()
+    opt_class_ms, opt_class_n = prof["optimizer"]
+    result = dict(metric="seq2seq_train_bench", measured=True, model="byt5-small (synthetic, hf)", batch=B, source_bytes=S,
+                  target_labels=T, iters=a.iters, step_ms=round(s_ms, 3), full_grad_ms=round(g_ms, 3),
+                  step_over_full_grad=round(s_ms / g_ms, 4), step_ms_all=[round(x, 3) for x in ts["step"]],
+                  full_grad_ms_all=[round(x, 3) for x in ts["full_grad"]],
+                  optimizer_step_ms_back_to_back=round(opt_ms, 4),
+                  optimizer_and_reload_share_of_step=round(opt_ms / s_ms, 4),
+                  profiled_step_optimizer_class=dict(ms=round(opt_class_ms, 4), launch_groups=int(opt_class_n)),
+                  profiled_step_ms_by_class={k: round(v[0], 3) for k, v in prof.items() if v[1]},
+                  decoder_reload=dict(bytes=int(nbytes), table_elements=int(n_dec), back_to_back=rate(reload_ms),
+                                      profiled=rate(rl_ms / max(rl_n, 1)), profiled_launches=int(rl_n)),
+                  parameters=dict(encoder_flat=int(n_enc), decoder_flat=int(n_dec)),
+                  note="step = HipSeq2SeqTrainer.loss_and_grads + optimizer_step (shared-gradient sum, AdamW over both flat "
+                       "buffers, copy of the embedding master, rp_trainer_load_params, rp_decoder_load_params); full_grad = "
+                       "HipSeq2SeqGradients.loss_and_grads, the protocol of profiles/seq2seq_full_grad_bench.json; "
+                       "optimizer_step_ms_back_to_back = device events around 5 consecutive optimizer steps; decoder_reload "
+                       "rates = bytes its table moves (4 B read per element, 2 B written per bf16 copy, 4 B per fp32 copy) / "
+                       "time; one box, one run")
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -157,8 +267,11 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--grad", action="store_true", help="time rp_decoder_loss_grad against rp_decoder_forward")
     ap.add_argument("--full-grad", action="store_true", help="time HipSeq2SeqGradients against the decoder-only gradients")
+    ap.add_argument("--step", action="store_true", help="time the whole training step against the --full-grad call")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.step:
+        return _step_leg(a, dev)
     if a.full_grad:
         return _full_grad_leg(a, dev)
     cfg = synth.seq2seq_config("byt5-small")
