@@ -475,6 +475,34 @@ RpStatus rp_dbg_dropout_mask(float p, uint32_t seed, uint32_t site, uint32_t row
                              int32_t cols, uint8_t* out, void* stream);
 RpStatus rp_dbg_dgrad(const void* A, const void* W, int32_t M, int32_t N, int32_t K, int32_t mode, const void* aux0,
                       const float* aux1, void* out0, float* out1, int32_t variant, void* stream);
+/* The seq2seq training path's kernels in isolation (tests/test_decoder_kernels_gpu.py; test-only).
+ * Each runs the launch functions rp_decoder_loss_grad / rp_train_*_hidden run; scratch is allocated inside, every call
+ * synchronises, and no output is zeroed first (rows a kernel does not write keep what the caller put there).
+ *   rp_dbg_decoder_attention: dec_flash_kernel, then dec_flash_bwd_kernel<0>, <1> and (causal) bias_grad_kernel, inner = H * 64,
+ *     Tp / Sp = the query / key row totals rounded up to 128.  q_cu / k_cu / bucket_of are HOST arrays, the rest device.
+ *       causal != 0: q = the fused bf16 [Tp, 3 inner] (q | k | v), kv / k_cu / dkv unused (k_cu = q_cu), dq = the fused
+ *                    gradient bf16 [Tp, 3 inner] (dq | dk | dv); bias_tab f32 [H, nbias]; bucket_of int32 [nbias] in
+ *                    [0, nbuckets): dtab f32 [nbuckets, H] = the table gradient folded through it (identity: raw).
+ *       causal == 0: q bf16 [Tp, inner], kv bf16 [Sp, 2 inner] (k | v), dq bf16 [Tp, inner], dkv bf16 [Sp, 2 inner]; key
+ *                    blocks of pairs with no query are not launched; the table arguments are unused.
+ *     d_o bf16 [Tp, inner]; out bf16 [Tp, inner]; lse2, delta f32 [H, Tp].
+ *   rp_dbg_decoder_rows: mode 0 bwd_dlogits_kernel (a = logits f32 [rows_pad, n], ia = labels [n_tok], b = loss_sum_count
+ *     f64 [2]; o0 bf16 [rows_pad, n]); 1 bwd_cast_kernel (a f32 [rows_pad, n]; o0 bf16); 2 bwd_rmsnorm_kernel<flag> +
+ *     colsum_kernel (a = x f32 [n_tok, n], b = ln f32 [n], o0 = dh f32 in / row terms of d ln out, o1 = dx f32 (flag: added
+ *     to), o2 = d ln f32 [n]; eps, scale); 3 bwd_geglu_kernel (a = gate | up f32 [rows_pad, 2 n] interleaved by 32, b = dff
+ *     f32 [rows_pad, n]; o0 bf16 [rows_pad, 2 n] = dg | du); 4 bwd_embed_kernel<flag> (ia = ids [n_tok], a = dx f32
+ *     [n_tok, n]; o0 f32 [vocab, n], flag: added to).  Launch only (stream-ordered).
+ *   rp_dbg_hidden_head: hidden_head_kernel, then hidden_head_bwd_kernel + colsum_kernel: xhi / xlo bf16 [T, D], rs f32 [T],
+ *     ln f32 [D], d_hidden f32 [T, D]; out_hidden, dxhi, dxlo bf16 [T, D], dln f32 [D].  D % 8 == 0, D <= 2048. */
+RpStatus rp_dbg_decoder_attention(int32_t causal, const void* q, const void* kv, const void* d_o, const int32_t* q_cu,
+                                  const int32_t* k_cu, int32_t batch, int32_t num_heads, const float* bias_tab, int32_t nbias,
+                                  const int32_t* bucket_of, int32_t nbuckets, void* out, float* lse2, float* delta, void* dq,
+                                  void* dkv, float* dtab, void* stream);
+RpStatus rp_dbg_decoder_rows(int32_t mode, const void* a, const void* b, const int32_t* ia, int32_t n_tok, int32_t rows_pad,
+                             int32_t n, int32_t vocab, int32_t flag, float eps, float scale, void* o0, void* o1, void* o2,
+                             void* stream);
+RpStatus rp_dbg_hidden_head(const void* xhi, const void* xlo, const float* rs, const float* ln, const float* d_hidden,
+                            int32_t T, int32_t D, void* out_hidden, void* dxhi, void* dxlo, float* dln, void* stream);
 /* Tuning knobs (integers), e.g. "gemm_variant"; returns RP_E_INVALID for unknown names. */
 RpStatus rp_set_option(const char* name, int32_t value);
 

@@ -209,6 +209,22 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
          C.c_void_p, C.c_int32, C.c_void_p],
     ),
+    # the seq2seq training path's kernels in isolation (test-only: tests/test_decoder_kernels_gpu.py)
+    "rp_dbg_decoder_attention": (
+        C.c_int32,
+        [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "rp_dbg_decoder_rows": (
+        C.c_int32,
+        [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "rp_dbg_hidden_head": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p],
+    ),
     "rp_dbg_gemm": (
         C.c_int32,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],

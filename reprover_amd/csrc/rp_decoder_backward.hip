@@ -541,6 +541,64 @@ auto with_bool(bool b, F f) {
   return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
+// ---- launches on raw pointers (rp_decoder_loss_grad and the rp_dbg_decoder_* test entries run these) --------------------------
+// the 128-key blocks {pair, first key} of the sources of non-empty targets, appended to meta; returns their number
+int bwd_build_kwork(const int32_t* src_cu, const int32_t* tgt_cu, int batch, std::vector<int32_t>& meta) {
+  const size_t at = meta.size();
+  for (int b = 0; b < batch; ++b) {
+    if (tgt_cu[b + 1] == tgt_cu[b]) continue;
+    for (int k0 = 0; k0 < src_cu[b + 1] - src_cu[b]; k0 += FA_Q) {
+      meta.push_back(b);
+      meta.push_back(k0);
+    }
+  }
+  return (int)(meta.size() - at) / 2;
+}
+void launch_dlogits(const float* logits, int V, int n_tok, int rows_pad, const int32_t* labels, const double* sum_count,
+                    bf16_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(bwd_dlogits_kernel, dim3(rows_pad), dim3(256), 0, s, logits, V, n_tok, labels, sum_count, out);
+}
+void launch_cast(const float* in, bf16_t* out, int D, int n_tok, int rows_pad, hipStream_t s) {
+  hipLaunchKernelGGL(bwd_cast_kernel, dim3(rows_pad), dim3(256), 0, s, in, out, D, n_tok);
+}
+void launch_geglu_bwd(const float* gu, const float* dff, bf16_t* dgu, int F, int n_tok, int rows_pad, hipStream_t s) {
+  hipLaunchKernelGGL(bwd_geglu_kernel, dim3(rows_pad), dim3(256), 0, s, gu, dff, dgu, F, n_tok);
+}
+// dh -> dx through the norm whose input rows were x; the rows' terms of d ln are summed into dln
+void launch_norm_bwd(const float* x, const float* ln, float* dh, float* dx, int n_tok, int D, float eps, float sc, bool add,
+                     float* dln, hipStream_t s) {
+  with_bool(add, [&](auto a) {
+    hipLaunchKernelGGL(bwd_rmsnorm_kernel<decltype(a)::value>, dim3(n_tok), dim3(256), 0, s, x, ln, dh, dx, D, eps, sc);
+  });
+  hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, s, (const float*)dh, n_tok, D, dln);
+}
+void launch_embed_bwd(bool add_, const int32_t* ids, int T, int V, const float* dx, int D, float* dtable, hipStream_t s) {
+  with_bool(add_, [&](auto add) {
+    hipLaunchKernelGGL(bwd_embed_kernel<decltype(add)::value>, dim3(V, (D + 255) / 256), dim3(256), 0, s, ids, T, V, dx, D,
+                       dtable);
+  });
+}
+// both passes of the attention backward: dQ (+ delta, + the table partials when causal) over the query blocks, then
+// dK | dV over the key blocks (causal: the query blocks again)
+void launch_flash_bwd(bool causal, FlashBwdArgs fa, int H, const int2* qwork, int n_qwork, const int2* kwork, int n_kwork,
+                      hipStream_t s) {
+  fa.work = qwork;
+  if (causal)
+    hipLaunchKernelGGL((dec_flash_bwd_kernel<0, true>), dim3(H * n_qwork), dim3(256), 0, s, fa);
+  else
+    hipLaunchKernelGGL((dec_flash_bwd_kernel<0, false>), dim3(H * n_qwork), dim3(256), 0, s, fa);
+  fa.work = kwork;
+  if (!n_kwork) return;
+  if (causal)
+    hipLaunchKernelGGL((dec_flash_bwd_kernel<1, true>), dim3(H * n_kwork), dim3(256), 0, s, fa);
+  else
+    hipLaunchKernelGGL((dec_flash_bwd_kernel<1, false>), dim3(H * n_kwork), dim3(256), 0, s, fa);
+}
+void launch_bias_grad(const float* dtab_part, int n_work, int H, int nbias, const int32_t* bucket_of, int nbuckets,
+                      float* d_rel_bias, hipStream_t s) {
+  hipLaunchKernelGGL(bias_grad_kernel, dim3(H), dim3(256), 0, s, dtab_part, n_work, H, nbias, bucket_of, nbuckets, d_rel_bias);
+}
+
 // Backward of a projection  y = x W^T,  W [R, C] bf16, over n token rows (n_pad: rounded up to 128, the padding rows of dY
 // and X zero).  First one weight-gradient launch per slice of W's rows, in the order given: dW[row0 : row0 + rows] =
 // dY[:, row0 : row0 + rows]^T X  (wgrad_kernel, one split: K runs in ascending token order).  Then dX = dY W on the
@@ -618,14 +676,7 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   std::vector<int32_t> meta;
   const int n_work = fwd_build_meta(src_cu, tgt_cu, batch, meta);
   const size_t kwork_at = meta.size();
-  for (int b = 0; b < batch; ++b) {
-    if (tgt_cu[b + 1] == tgt_cu[b]) continue;
-    for (int k0 = 0; k0 < src_cu[b + 1] - src_cu[b]; k0 += FA_Q) {
-      meta.push_back(b);
-      meta.push_back(k0);
-    }
-  }
-  const int n_kwork = (int)(meta.size() - kwork_at) / 2;
+  const int n_kwork = bwd_build_kwork(src_cu, tgt_cu, batch, meta);
   const size_t bucket_at = meta.size();
   for (int j = 0; j < d->nbias; ++j) meta.push_back(rp_relative_position_bucket_causal(-j, c.rel_num_buckets, c.rel_max_distance));
   RP_HIP(hipMemcpyWithStream(w.meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s));
@@ -666,23 +717,18 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   auto G = [&](int64_t off) { return grads + off; };
   auto lin = [&](const bf16_t* dY, const bf16_t* X, const bf16_t* W, int R, int C, std::initializer_list<WgradSlice> slices,
                  DxKind kind, void* dX) { return linear_bwd(dY, X, n_tgt, Tp, W, R, C, slices, kind, dX, w.wt, s); };
-  // w.dh -> w.dx through the norm whose input rows were x; the rows' terms of d ln are summed into dln
+  // w.dh -> w.dx through the norm whose input rows were x
   auto norm_bwd = [&](const float* x, const float* ln, float sc, bool add, float* dln) {
-    with_bool(add, [&](auto a) {
-      hipLaunchKernelGGL(bwd_rmsnorm_kernel<decltype(a)::value>, dim3(n_tgt), dim3(256), 0, s, x, ln, w.dh, w.dx, D, eps, sc);
-    });
-    hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, s, (const float*)w.dh, n_tgt, D, dln);
+    launch_norm_bwd(x, ln, w.dh, w.dx, n_tgt, D, eps, sc, add, dln, s);
   };
-  auto cast_dx = [&]() { hipLaunchKernelGGL(bwd_cast_kernel, dim3(Tp), dim3(256), 0, s, (const float*)w.dx, w.dyb, D, n_tgt); };
+  auto cast_dx = [&]() { launch_cast(w.dx, w.dyb, D, n_tgt, Tp, s); };
 
   // loss and head
-  hipLaunchKernelGGL(bwd_dlogits_kernel, dim3(Tp), dim3(256), 0, s, (const float*)w.logits, V, n_tgt, labels,
-                     (const double*)loss_sum_count, w.dlog);
+  launch_dlogits(w.logits, V, n_tgt, Tp, labels, loss_sum_count, w.dlog, s);
   if ((st = lin(w.dlog, fin.h, d->lm_head, V, D, {{0, V, G(d->tied ? lay.shared() : lay.lm_head())}}, DX_F32, w.dh)))
     return st;
   norm_bwd(fin.x, d->final_ln, fwd_head_scale(d), false, G(lay.final_ln()));
 
-  const dim3 att_grid(H * n_work);
   FlashBwdArgs fa{};
   fa.q_cu = d_tgt_cu;
   fa.bias_tab = d->bias_tab;
@@ -701,7 +747,7 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
     if ((st = fwd_gemm(b.h2, n_tgt, Tp, d->wi_il + (size_t)i * 2 * F * D, 2 * F, D, EpiDecF32<false>{w.gu, 2 * F, 2 * F, n_tgt},
                        s, RP_K_GEMM_WI)))
       return st;
-    hipLaunchKernelGGL(bwd_geglu_kernel, dim3(Tp), dim3(256), 0, s, (const float*)w.gu, (const float*)w.dff, w.dgu, F, n_tgt);
+    launch_geglu_bwd(w.gu, w.dff, w.dgu, F, n_tgt, Tp, s);
     if ((st = lin(w.dgu, b.h2, l.wi, 2 * F, D, {{0, F, Gl(G_WI0)}, {F, F, Gl(G_WI1)}}, DX_F32, w.dh))) return st;
     norm_bwd(b.x2, l.ln_ff, 1.f, true, Gl(G_LN_FF));
 
@@ -715,10 +761,7 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
     fa.lse2 = b.lse_c;
     fa.dq = w.dcq; fa.lddq = inner;
     fa.dkv = w.dkv; fa.lddkv = 2 * inner; fa.dkoff = 0; fa.dvoff = inner;
-    fa.work = d_work;
-    hipLaunchKernelGGL((dec_flash_bwd_kernel<0, false>), att_grid, dim3(256), 0, s, fa);
-    fa.work = d_kwork;
-    if (n_kwork) hipLaunchKernelGGL((dec_flash_bwd_kernel<1, false>), dim3(H * n_kwork), dim3(256), 0, s, fa);
+    launch_flash_bwd(false, fa, H, d_work, n_work, d_kwork, n_kwork, s);
     // the launch order of the two cross projections is kept: all three weight gradients, the K | V projection's dX (over
     // the source rows, added into d_enc), then the q projection's dX
     if ((st = lin(w.dcq, b.h1, l.cq, inner, D, {{0, inner, Gl(G_CQ)}}, DX_NONE, nullptr))) return st;
@@ -738,21 +781,139 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
     fa.lse2 = b.lse_s;
     fa.dq = w.dqkv; fa.lddq = 3 * inner;
     fa.dkv = w.dqkv; fa.lddkv = 3 * inner; fa.dkoff = inner; fa.dvoff = 2 * inner;
-    fa.work = d_work;
-    hipLaunchKernelGGL((dec_flash_bwd_kernel<0, true>), att_grid, dim3(256), 0, s, fa);
-    hipLaunchKernelGGL((dec_flash_bwd_kernel<1, true>), att_grid, dim3(256), 0, s, fa);
+    launch_flash_bwd(true, fa, H, d_work, n_work, d_work, n_work, s);
     if ((st = lin(w.dqkv, b.h0, l.wqkv, 3 * inner, D,
                   {{0, inner, Gl(G_Q)}, {inner, inner, Gl(G_K)}, {2 * inner, inner, Gl(G_V)}}, DX_F32, w.dh)))
       return st;
     norm_bwd(b.x0, l.ln_self, 1.f, true, Gl(G_LN_SELF));
   }
   // the shared bias table (every layer added into the same partial rows) and the embedding
-  hipLaunchKernelGGL(bias_grad_kernel, dim3(H), dim3(256), 0, s, (const float*)w.dtab_part, n_work, H, d->nbias, d_bucket,
-                     c.rel_num_buckets, G(lay.rel_bias()));
-  with_bool(d->tied, [&](auto add) {  // tied: the head's weight gradient is already there
-    hipLaunchKernelGGL(bwd_embed_kernel<decltype(add)::value>, dim3(V, (D + 255) / 256), dim3(256), 0, s, tokens, n_tgt, V,
-                       (const float*)w.dx, D, G(lay.shared()));
-  });
+  launch_bias_grad(w.dtab_part, n_work, H, d->nbias, d_bucket, c.rel_num_buckets, G(lay.rel_bias()), s);
+  launch_embed_bwd(d->tied, tokens, n_tgt, V, w.dx, D, G(lay.shared()), s);  // tied: the head's weight gradient is already there
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// ---- kernel-level test entry points (include/reprover_hip.h: tests/test_decoder_kernels_gpu.py) -----------------------------
+// The attention kernels alone on caller-supplied operands in the product's layouts, through the product's work lists and
+// launch functions.  Scratch (metadata, table partials) is allocated here; no output is zeroed.
+extern "C" RpStatus rp_dbg_decoder_attention(int32_t causal, const void* q, const void* kv, const void* d_o,
+                                             const int32_t* q_cu, const int32_t* k_cu, int32_t batch, int32_t H,
+                                             const float* bias_tab, int32_t nbias, const int32_t* bucket_of, int32_t nbuckets,
+                                             void* out, float* lse2, float* delta, void* dq, void* dkv, float* dtab,
+                                             void* stream_) {
+  RP_REQUIRE(q && d_o && q_cu && out && lse2 && delta && dq, "null argument");
+  RP_REQUIRE(H >= 1 && H <= 64, "H=%d", H);
+  if (causal) {
+    RP_REQUIRE(bias_tab && bucket_of && dtab && nbias >= 1 && nbias <= FA_TAB_MAX && nbuckets >= 1, "causal: table arguments");
+    for (int i = 0; i < nbias; ++i) RP_REQUIRE(bucket_of[i] >= 0 && bucket_of[i] < nbuckets, "bucket_of[%d]=%d", i, bucket_of[i]);
+    k_cu = q_cu;
+  } else {
+    RP_REQUIRE(kv && k_cu && dkv, "cross: null argument");
+  }
+  int n_src = 0, n_tgt = 0;
+  RpStatus st = fwd_check_cu(k_cu, q_cu, batch, n_src, n_tgt);
+  if (st) return st;
+  RP_REQUIRE(n_tgt > 0, "no query row");
+  hipStream_t s = (hipStream_t)stream_;
+  const int inner = H * 64, Tp = (int)align_up(n_tgt, FWD_BN);
+  std::vector<int32_t> meta;
+  const int n_work = fwd_build_meta(k_cu, q_cu, batch, meta);
+  const size_t kwork_at = meta.size();
+  const int n_kwork = causal ? n_work : bwd_build_kwork(k_cu, q_cu, batch, meta);
+  const size_t bucket_at = meta.size();
+  if (causal) meta.insert(meta.end(), bucket_of, bucket_of + nbias);
+  int32_t* d_meta = nullptr;
+  float* part = nullptr;
+  const size_t part_bytes = causal ? (size_t)n_work * H * nbias * 4 : 0;
+  RP_HIP(hipMalloc((void**)&d_meta, meta.size() * 4));
+  if (part_bytes && hipMalloc((void**)&part, part_bytes) != hipSuccess) {
+    (void)hipFree(d_meta);
+    return fail(RP_E_HIP, "hipMalloc of the table partials failed");
+  }
+  auto done = [&](RpStatus r) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(d_meta);
+    if (part) (void)hipFree(part);
+    return r;
+  };
+  if (hipMemcpyAsync(d_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+      (part && hipMemsetAsync(part, 0, part_bytes, s) != hipSuccess))
+    return done(fail(RP_E_HIP, "metadata upload failed"));
+  const int32_t* d_src_cu = d_meta;
+  const int32_t* d_tgt_cu = d_meta + batch + 1;
+  const int2* d_work = reinterpret_cast<const int2*>(d_meta + 2 * (batch + 1));
+  const int2* d_kwork = causal ? d_work : reinterpret_cast<const int2*>(d_meta + kwork_at);
+  FlashBwdArgs fa{};
+  fa.q_cu = d_tgt_cu;
+  fa.bias_tab = bias_tab;
+  fa.nbias = causal ? nbias : 1;
+  fa.ldo = inner;
+  fa.delta = delta;
+  fa.ld_stat = Tp;
+  fa.dtab_part = part;
+  fa.o = (const bf16_t*)out;
+  fa.d_o = (const bf16_t*)d_o;
+  fa.lse2 = lse2;
+  fa.q = (const bf16_t*)q;
+  if (causal) {
+    fa.ldq = 3 * inner;
+    fa.kv = (const bf16_t*)q; fa.ldkv = 3 * inner; fa.koff = inner; fa.voff = 2 * inner;
+    fa.k_cu = d_tgt_cu;
+    fa.dq = (bf16_t*)dq; fa.lddq = 3 * inner;
+    fa.dkv = (bf16_t*)dq; fa.lddkv = 3 * inner; fa.dkoff = inner; fa.dvoff = 2 * inner;
+  } else {
+    fa.ldq = inner;
+    fa.kv = (const bf16_t*)kv; fa.ldkv = 2 * inner; fa.koff = 0; fa.voff = inner;
+    fa.k_cu = d_src_cu;
+    fa.dq = (bf16_t*)dq; fa.lddq = inner;
+    fa.dkv = (bf16_t*)dkv; fa.lddkv = 2 * inner; fa.dkoff = 0; fa.dvoff = inner;
+  }
+  launch_dec_flash(causal != 0, fa.q, fa.ldq, fa.kv, fa.ldkv, fa.koff, fa.voff, fa.q_cu, fa.k_cu, d_work, n_work, H, bias_tab,
+                   fa.nbias, (bf16_t*)out, inner, lse2, Tp, s);
+  launch_flash_bwd(causal != 0, fa, H, d_work, n_work, d_kwork, n_kwork, s);
+  if (causal) launch_bias_grad(part, n_work, H, nbias, d_meta + bucket_at, nbuckets, dtab, s);
+  const hipError_t le = hipGetLastError();
+  if (le != hipSuccess) return done(fail(RP_E_HIP, "decoder attention launch failed: %s", hipGetErrorString(le)));
+  return done(RP_OK);
+}
+
+// The row kernels of the decoder backward, one per mode, through the product's launch functions:
+//   0 dlogits   a = logits f32 [rows_pad, n], ia = labels [n_tok], b = loss_sum_count f64 [2]; o0 = bf16 [rows_pad, n]
+//   1 cast      a = f32 [rows_pad, n]; o0 = bf16 [rows_pad, n]
+//   2 rmsnorm   a = x f32 [n_tok, n], b = ln f32 [n], o0 = dh f32 [n_tok, n] (in: dh, out: the rows' terms of d ln),
+//               o1 = dx f32 [n_tok, n] (flag: added to), o2 = d ln f32 [n]; eps, scale
+//   3 geglu     a = gate | up f32 [rows_pad, 2 n] (interleaved by 32), b = dff f32 [rows_pad, n]; o0 = bf16 [rows_pad, 2 n]
+//   4 embed     ia = ids [n_tok], a = dx f32 [n_tok, n]; o0 = table gradient f32 [vocab, n] (flag: added to)
+extern "C" RpStatus rp_dbg_decoder_rows(int32_t mode, const void* a, const void* b, const int32_t* ia, int32_t n_tok,
+                                        int32_t rows_pad, int32_t n, int32_t vocab, int32_t flag, float eps, float scale,
+                                        void* o0, void* o1, void* o2, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  RP_REQUIRE(a && o0 && n >= 1 && n_tok >= 0, "bad argument");
+  switch (mode) {
+    case 0:
+      RP_REQUIRE(b && ia && n <= FWD_MAX_VOCAB && rows_pad >= n_tok && rows_pad >= 1, "dlogits: bad argument");
+      launch_dlogits((const float*)a, n, n_tok, rows_pad, ia, (const double*)b, (bf16_t*)o0, s);
+      break;
+    case 1:
+      RP_REQUIRE(rows_pad >= n_tok && rows_pad >= 1, "cast: bad argument");
+      launch_cast((const float*)a, (bf16_t*)o0, n, n_tok, rows_pad, s);
+      break;
+    case 2:
+      RP_REQUIRE(b && o1 && o2 && n_tok >= 1, "rmsnorm: bad argument");
+      launch_norm_bwd((const float*)a, (const float*)b, (float*)o0, (float*)o1, n_tok, n, eps, scale, flag != 0, (float*)o2, s);
+      break;
+    case 3:
+      RP_REQUIRE(b && n % 64 == 0 && rows_pad >= n_tok && rows_pad >= 1, "geglu: bad argument");
+      launch_geglu_bwd((const float*)a, (const float*)b, (bf16_t*)o0, n, n_tok, rows_pad, s);
+      break;
+    case 4:
+      RP_REQUIRE(ia && vocab >= 1 && n_tok >= 1, "embed: bad argument");
+      launch_embed_bwd(flag != 0, ia, n_tok, vocab, (const float*)a, n, (float*)o0, s);
+      break;
+    default:
+      return fail(RP_E_INVALID, "mode=%d", mode);
+  }
   RP_CHECK_LAUNCH();
   return RP_OK;
 }

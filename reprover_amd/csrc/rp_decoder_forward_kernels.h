@@ -307,6 +307,20 @@ __global__ __launch_bounds__(256) void dec_flash_kernel(const bf16_t* __restrict
   }
 }
 
+// One forward attention launch over the work list {pair, first query}: the causal form reads q | k | v at koff / voff of
+// one fused buffer (k_cu = q_cu) and the bias table, the cross form reads no table.
+inline void launch_dec_flash(bool causal, const bf16_t* q, int ldq, const bf16_t* kv, int ldkv, int koff, int voff,
+                             const int32_t* q_cu, const int32_t* k_cu, const int2* work, int n_work, int H,
+                             const float* bias_tab, int nbias, bf16_t* out, int ldo, float* lse2, int lse_ld, hipStream_t s) {
+  const dim3 att_grid(H * n_work);
+  if (causal)
+    hipLaunchKernelGGL(dec_flash_kernel<true>, att_grid, dim3(256), 0, s, q, ldq, kv, ldkv, koff, voff, q_cu, k_cu, work,
+                       bias_tab, nbias, out, ldo, lse2, lse_ld);
+  else
+    hipLaunchKernelGGL(dec_flash_kernel<false>, att_grid, dim3(256), 0, s, q, ldq, kv, ldkv, koff, voff, q_cu, k_cu, work,
+                       (const float*)nullptr, 1, out, ldo, lse2, lse_ld);
+}
+
 // ---- loss ---------------------------------------------------------------------------------------------------------------
 // One workgroup per target row: log_softmax over V <= 512 in fp32 (the decode step's arithmetic: max, sum of __expf,
 // (x - max) - log(sum)); lp[row] = the label's log-prob, 0 when the label is ignored (< 0, HF's -100) or out of range.
@@ -448,7 +462,6 @@ RpStatus fwd_launch_layers(const RpDecoder* d, const void* enc_bf16, const int32
   const int32_t* d_tgt_cu = meta + batch + 1;
   const int2* d_work = reinterpret_cast<const int2*>(meta + 2 * (batch + 1));
   const int Tp = (int)align_up(n_tgt, FWD_BN), Sp = (int)align_up(n_src, FWD_BN);
-  const dim3 att_grid(H * n_work);
   RpStatus st;
   auto norm = [&](const float* x, const float* ln, bf16_t* h, float scale) {
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(n_tgt), dim3(256), 0, s, x, ln, h, D, eps, scale);
@@ -465,8 +478,8 @@ RpStatus fwd_launch_layers(const RpDecoder* d, const void* enc_bf16, const int32
     if ((st = fwd_gemm(b.h0, n_tgt, Tp, l.wqkv, 3 * inner, D, EpiDecBf16{b.qkv, 3 * inner, 3 * inner, n_tgt}, s,
                        RP_K_GEMM_QKV)))
       return st;
-    hipLaunchKernelGGL(dec_flash_kernel<true>, att_grid, dim3(256), 0, s, b.qkv, 3 * inner, b.qkv, 3 * inner, inner,
-                       2 * inner, d_tgt_cu, d_tgt_cu, d_work, d->bias_tab, d->nbias, b.att_s, inner, b.lse_s, b.lse_ld);
+    launch_dec_flash(true, b.qkv, 3 * inner, b.qkv, 3 * inner, inner, 2 * inner, d_tgt_cu, d_tgt_cu, d_work, n_work, H,
+                     d->bias_tab, d->nbias, b.att_s, inner, b.lse_s, b.lse_ld, s);
     RP_HIP(move_stream(b.x1, b.x0));
     if ((st = fwd_gemm(b.att_s, n_tgt, Tp, l.wo, D, inner, EpiDecF32<true>{b.x1, D, D, n_tgt}, s, RP_K_GEMM_O))) return st;
     // cross-attention: the pair's queries over its own source's K / V (this layer's, from one GEMM over all sources)
@@ -476,8 +489,8 @@ RpStatus fwd_launch_layers(const RpDecoder* d, const void* enc_bf16, const int32
     norm(b.x1, l.ln_cross, b.h1, 1.f);
     if ((st = fwd_gemm(b.h1, n_tgt, Tp, l.cq, inner, D, EpiDecBf16{b.cq, inner, inner, n_tgt}, s, RP_K_GEMM_QKV)))
       return st;
-    hipLaunchKernelGGL(dec_flash_kernel<false>, att_grid, dim3(256), 0, s, b.cq, inner, b.ckv, 2 * inner, 0, inner,
-                       d_tgt_cu, d_src_cu, d_work, (const float*)nullptr, 1, b.att_c, inner, b.lse_c, b.lse_ld);
+    launch_dec_flash(false, b.cq, inner, b.ckv, 2 * inner, 0, inner, d_tgt_cu, d_src_cu, d_work, n_work, H, nullptr, 1,
+                     b.att_c, inner, b.lse_c, b.lse_ld, s);
     RP_HIP(move_stream(b.x2, b.x1));
     if ((st = fwd_gemm(b.att_c, n_tgt, Tp, l.co, D, inner, EpiDecF32<true>{b.x2, D, D, n_tgt}, s, RP_K_GEMM_O))) return st;
     // gated-GELU FFN

@@ -336,15 +336,20 @@ RpStatus pool_head(RpTrainer* tr, const int32_t* cu, int batch, int T, float* ou
   return RP_OK;
 }
 
-// head of rp_train_forward_hidden: the final RMSNorm's rows, last_hidden_state [T, D] bf16
-RpStatus hidden_head(RpTrainer* tr, int T, bf16_t* out_hidden, const TrainWs& w, hipStream_t stream) {
-  RpEncoder* e = tr->enc;
-  const int D = e->cfg.d_model, L = e->cfg.num_layers;
+// head of rp_train_forward_hidden: the final RMSNorm's rows, last_hidden_state [T, D] bf16 (on raw pointers: the trainer
+// and the rp_dbg_hidden_head test entry both launch through here)
+RpStatus launch_hidden_head(const bf16_t* xhi, const bf16_t* xlo, const float* rs, const float* ln, bf16_t* out_hidden, int T,
+                            int D, hipStream_t stream) {
   ProfScope ps(stream, RP_K_HIDDEN_HEAD);
-  hipLaunchKernelGGL(hidden_head_kernel, dim3((T + HIDDEN_ROWS - 1) / HIDDEN_ROWS), dim3(256), 0, stream, (const bf16_t*)w.xa[L],
-                     (const bf16_t*)w.xlo, (const float*)w.rs_final, (const float*)e->final_ln, out_hidden, T, D);
+  hipLaunchKernelGGL(hidden_head_kernel, dim3((T + HIDDEN_ROWS - 1) / HIDDEN_ROWS), dim3(256), 0, stream, xhi, xlo, rs, ln,
+                     out_hidden, T, D);
   RP_CHECK_LAUNCH();
   return RP_OK;
+}
+RpStatus hidden_head(RpTrainer* tr, int T, bf16_t* out_hidden, const TrainWs& w, hipStream_t stream) {
+  RpEncoder* e = tr->enc;
+  return launch_hidden_head((const bf16_t*)w.xa[e->cfg.num_layers], (const bf16_t*)w.xlo, (const float*)w.rs_final,
+                            (const float*)e->final_ln, out_hidden, T, e->cfg.d_model, stream);
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------
@@ -386,25 +391,30 @@ RpStatus pool_bwd_head(RpTrainer* tr, const int32_t* cu, int batch, int T, const
 
 // head of rp_train_backward_hidden: the final RMSNorm alone, from d loss / d last_hidden_state [T, D] fp32.  The partial
 // rows of final_layer_norm.weight's gradient, one per workgroup, go through dhead_part to colsum_kernel.
-RpStatus hidden_bwd_head(RpTrainer* tr, int T, const float* d_hidden, float* grads, const TrainWs& w, hipStream_t stream) {
-  RpEncoder* e = tr->enc;
-  const int D = e->cfg.d_model, L = e->cfg.num_layers;
+// (on raw pointers, as launch_hidden_head; dhead_part: ceil(T / HIDDEN_BWD_ROWS) rows of D floats)
+RpStatus launch_hidden_bwd_head(const bf16_t* xhi, const bf16_t* xlo, const float* rs, const float* ln, const float* d_hidden,
+                                bf16_t* dxhi, bf16_t* dxlo, float* dhead_part, float* dln, int T, int D, hipStream_t stream) {
   const float inv_d = 1.f / (float)D;
   const int nblk = (T + HIDDEN_BWD_ROWS - 1) / HIDDEN_BWD_ROWS;
   {
     ProfScope ps(stream, RP_K_BWD_HIDDEN_HEAD);
     if (D <= 3 * 512)
-      hipLaunchKernelGGL(hidden_head_bwd_kernel<3>, dim3(nblk), dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
-                         (const float*)w.rs_final, (const float*)e->final_ln, d_hidden, w.dxhi, w.dxlo, w.dhead_part, T, D, inv_d);
+      hipLaunchKernelGGL(hidden_head_bwd_kernel<3>, dim3(nblk), dim3(256), 0, stream, xhi, xlo, rs, ln, d_hidden, dxhi, dxlo,
+                         dhead_part, T, D, inv_d);
     else
-      hipLaunchKernelGGL(hidden_head_bwd_kernel<4>, dim3(nblk), dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
-                         (const float*)w.rs_final, (const float*)e->final_ln, d_hidden, w.dxhi, w.dxlo, w.dhead_part, T, D, inv_d);
+      hipLaunchKernelGGL(hidden_head_bwd_kernel<4>, dim3(nblk), dim3(256), 0, stream, xhi, xlo, rs, ln, d_hidden, dxhi, dxlo,
+                         dhead_part, T, D, inv_d);
   }
   ProfScope ps(stream, RP_K_BWD_OTHER);
-  hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)w.dhead_part, nblk, D,
-                     grads + tr->lay.final_ln());
+  hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)dhead_part, nblk, D, dln);
   RP_CHECK_LAUNCH();
   return RP_OK;
+}
+RpStatus hidden_bwd_head(RpTrainer* tr, int T, const float* d_hidden, float* grads, const TrainWs& w, hipStream_t stream) {
+  RpEncoder* e = tr->enc;
+  return launch_hidden_bwd_head((const bf16_t*)w.xa[e->cfg.num_layers], (const bf16_t*)w.xlo, (const float*)w.rs_final,
+                                (const float*)e->final_ln, d_hidden, w.dxhi, w.dxlo, w.dhead_part, grads + tr->lay.final_ln(), T,
+                                e->cfg.d_model, stream);
 }
 
 // The shared body of rp_train_backward and rp_train_backward_hidden: from the residual gradient of the final stream
@@ -880,6 +890,25 @@ extern "C" RpStatus rp_dbg_attention_bwd(const void* qkv, const void* att, const
   (void)hipFree(bk);
   if (le != hipSuccess) return fail(RP_E_HIP, "attention backward launch failed: %s", hipGetErrorString(le));
   return RP_OK;
+}
+
+// The last_hidden_state head alone: the forward, then the backward with its colsum, on caller-supplied planes (rows T .. Tp of
+// dxhi / dxlo are the caller's); the partial rows of d ln are allocated here.
+extern "C" RpStatus rp_dbg_hidden_head(const void* xhi, const void* xlo, const float* rs, const float* ln, const float* d_hidden,
+                                       int32_t T, int32_t D, void* out_hidden, void* dxhi, void* dxlo, float* dln,
+                                       void* stream_) {
+  RP_REQUIRE(xhi && xlo && rs && ln && d_hidden && out_hidden && dxhi && dxlo && dln, "null argument");
+  RP_REQUIRE(T >= 1 && D >= 8 && D % 8 == 0 && D <= 4 * 512, "T=%d, D=%d", T, D);
+  hipStream_t stream = (hipStream_t)stream_;
+  float* part = nullptr;
+  RP_HIP(hipMalloc((void**)&part, (size_t)((T + HIDDEN_BWD_ROWS - 1) / HIDDEN_BWD_ROWS) * D * 4));
+  RpStatus st = launch_hidden_head((const bf16_t*)xhi, (const bf16_t*)xlo, rs, ln, (bf16_t*)out_hidden, T, D, stream);
+  if (st == RP_OK)
+    st = launch_hidden_bwd_head((const bf16_t*)xhi, (const bf16_t*)xlo, rs, ln, d_hidden, (bf16_t*)dxhi, (bf16_t*)dxlo, part, dln,
+                                T, D, stream);
+  (void)hipStreamSynchronize(stream);
+  (void)hipFree(part);
+  return st;
 }
 
 // dgrad epilogues in isolation.  mode 0: EpiGegluBwd (A = dx [M, K], W = Wo2^T [F, K]; aux0 = gu [M, 2F] bf16, aux1 = rs [M];
