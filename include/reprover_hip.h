@@ -371,15 +371,26 @@ RpStatus rp_train_backward(RpTrainer* tr, const float* params, const int32_t* id
  * rp_train_backward_hidden: d_hidden: device f32 [total_tokens, d_model] = d loss / d out_hidden, unrounded (e.g.
  * rp_decoder_loss_grad's d_enc); grads: the trainer's flat layout, every element overwritten, gaps untouched; ids and
  * cu_seqlens are the forward's (not checked again).
- * Both return RP_E_INVALID while rp_trainer_set_dropout holds p > 0 (the decoder has no dropout: a half-dropped model is
- * neither the reference's training mode nor its eval mode), for a null pointer and for batch <= 0; RP_E_WORKSPACE for a
- * workspace one byte short.  Nothing is launched or written then. */
+ * Both return RP_E_INVALID while rp_trainer_set_dropout holds p > 0 (what follows them must drop too: a half-dropped
+ * model is neither the reference's training mode nor its eval mode), for a null pointer and for batch <= 0;
+ * RP_E_WORKSPACE for a workspace one byte short.  Nothing is launched or written then.
+ * rp_train_forward_hidden_dropout / rp_train_backward_hidden_dropout: the same pair, same arguments, honouring
+ * rp_trainer_set_dropout: the layer loops drop at HF's sites as rp_train_forward does, and the final site
+ * (RP_DROP_SITE_FINAL) masks out_hidden = bf16(mask * final_ln * (x * rs)) and, in the backward, d_hidden before anything
+ * else.  The decoder half is then rp_decoder_loss_grad_dropout with the same (p, seed).  With dropout unset they give the
+ * plain pair's bits. */
 RpStatus rp_train_forward_hidden(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
                                  int32_t total_tokens, void* out_hidden_bf16, void* workspace, size_t workspace_bytes,
                                  void* stream);
 RpStatus rp_train_backward_hidden(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens,
                                   int32_t batch, int32_t total_tokens, const float* d_hidden, float* grads,
                                   void* workspace, size_t workspace_bytes, void* stream);
+RpStatus rp_train_forward_hidden_dropout(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
+                                         int32_t total_tokens, void* out_hidden_bf16, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+RpStatus rp_train_backward_hidden_dropout(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens,
+                                          int32_t batch, int32_t total_tokens, const float* d_hidden, float* grads,
+                                          void* workspace, size_t workspace_bytes, void* stream);
 /* out_norm[0] (device) = ||grads||_2 over n floats (Lightning's gradient_clip_val, confs/cli_lean4_random.yaml:19, clips
  * on it); scratch: 1024 device floats.  Pair with rp_adamw_step_clipped. */
 RpStatus rp_grad_norm(const float* grads, int64_t n, float* out_norm, float* scratch, void* stream);
@@ -469,8 +480,15 @@ RpStatus rp_dbg_attention_bwd(const void* qkv, const void* att, const void* datt
 /* out u8 [rows, cols]: 1 where element (site, row0 + r, col0 + c) is kept.  Sites: 0 embeddings, 1 final norm output,
  * 16 + 8 i + {0 attention probabilities (row = the query's packed token index, col = (head << 20) | key offset in its
  * sequence), 1 attention residual branch, 2 gated product inside the FFN, 3 FFN residual branch} (row = packed token
- * index, col = feature).  Element (site, row, col) is kept iff the 16-bit field (col & 1) of hash(seed, site, row, col >> 1)
- * is >= round(p * 65536): one hash per column pair (rp_encoder_kernels.h::drop_mul2). */
+ * index, col = feature).  The decoder's sites (rp_decoder_loss_grad_dropout; rows are packed TARGET token indices): 2
+ * embeddings, 3 final norm output, 0x4000 + 8 i + {0 self-attention probabilities, 1 self-attention residual branch, 2
+ * cross-attention probabilities (key offset inside the pair's source), 3 cross-attention residual branch, 4 gated product
+ * inside the FFN, 5 FFN residual branch}.  Element (site, row, col) is kept iff the 16-bit field (col & 1) of
+ * hash(seed, site, row, col >> 1) is >= round(p * 65536): one hash per column pair (rp_encoder_kernels.h::drop_mul2). */
+enum {
+  RP_DROP_SITE_EMBED = 0, RP_DROP_SITE_FINAL = 1, RP_DROP_SITE_LAYER0 = 16, /* encoder layer i: 16 + 8 i + {0 .. 3} */
+  RP_DROP_SITE_DEC_EMBED = 2, RP_DROP_SITE_DEC_FINAL = 3, RP_DROP_SITE_DEC_LAYER0 = 0x4000 /* decoder layer i: + 8 i + {0 .. 5} */
+};
 RpStatus rp_dbg_dropout_mask(float p, uint32_t seed, uint32_t site, uint32_t row0, uint32_t col0, int32_t rows,
                              int32_t cols, uint8_t* out, void* stream);
 RpStatus rp_dbg_dgrad(const void* A, const void* W, int32_t M, int32_t N, int32_t K, int32_t mode, const void* aux0,
@@ -486,6 +504,8 @@ RpStatus rp_dbg_dgrad(const void* A, const void* W, int32_t M, int32_t N, int32_
  *       causal == 0: q bf16 [Tp, inner], kv bf16 [Sp, 2 inner] (k | v), dq bf16 [Tp, inner], dkv bf16 [Sp, 2 inner]; key
  *                    blocks of pairs with no query are not launched; the table arguments are unused.
  *     d_o bf16 [Tp, inner]; out bf16 [Tp, inner]; lse2, delta f32 [H, Tp].
+ *   rp_dbg_decoder_attention_dropout: the same with the probabilities dropped at (p, seed, site) - the dropout forms of the
+ *     three kernels through the same launch functions; p = 0 gives rp_dbg_decoder_attention's bits.  lse2 is the undropped one.
  *   rp_dbg_decoder_rows: mode 0 bwd_dlogits_kernel (a = logits f32 [rows_pad, n], ia = labels [n_tok], b = loss_sum_count
  *     f64 [2]; o0 bf16 [rows_pad, n]); 1 bwd_cast_kernel (a f32 [rows_pad, n]; o0 bf16); 2 bwd_rmsnorm_kernel<flag> +
  *     colsum_kernel (a = x f32 [n_tok, n], b = ln f32 [n], o0 = dh f32 in / row terms of d ln out, o1 = dx f32 (flag: added
@@ -498,6 +518,16 @@ RpStatus rp_dbg_decoder_attention(int32_t causal, const void* q, const void* kv,
                                   const int32_t* k_cu, int32_t batch, int32_t num_heads, const float* bias_tab, int32_t nbias,
                                   const int32_t* bucket_of, int32_t nbuckets, void* out, float* lse2, float* delta, void* dq,
                                   void* dkv, float* dtab, void* stream);
+RpStatus rp_dbg_decoder_attention_dropout(int32_t causal, const void* q, const void* kv, const void* d_o, const int32_t* q_cu,
+                                          const int32_t* k_cu, int32_t batch, int32_t num_heads, const float* bias_tab,
+                                          int32_t nbias, const int32_t* bucket_of, int32_t nbuckets, float p, uint32_t seed,
+                                          uint32_t site, void* out, float* lse2, float* delta, void* dq, void* dkv,
+                                          float* dtab, void* stream);
+/* The decoder's embedding site alone, fp32 end to end (device pointers): x f32 [n_tok, n] = mask * embed[ids] and dtable f32
+ * [vocab, n] = per-id sum of mask * dx, mask = (RP_DROP_SITE_DEC_EMBED, row = token, column = feature).  On a table of ones
+ * x is the multiplier itself: exactly 0 or fp32 1 / (1 - p).  Launch only. */
+RpStatus rp_dbg_decoder_embed_dropout(const int32_t* ids, int32_t n_tok, const float* embed, int32_t vocab, int32_t n, float p,
+                                      uint32_t seed, const float* dx, float* x, float* dtable, void* stream);
 RpStatus rp_dbg_decoder_rows(int32_t mode, const void* a, const void* b, const int32_t* ia, int32_t n_tok, int32_t rows_pad,
                              int32_t n, int32_t vocab, int32_t flag, float eps, float scale, void* o0, void* o1, void* o2,
                              void* stream);
@@ -710,6 +740,21 @@ RpStatus rp_decoder_loss_grad(RpDecoder* dec, const void* enc_bf16, const int32_
                               const int32_t* labels, const int32_t* tgt_cu, int32_t batch, float* label_logprobs,
                               double* loss_sum_count, float* grads, float* d_enc, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* rp_decoder_loss_grad in T5's training mode: dropout with probability p in [0, 1) at HF's decoder
+ * sites - the embeddings, both attentions' probabilities, the three residual branches and the gated product of every layer,
+ * the final norm's output (the RP_DROP_SITE_DEC_* sites of rp_dbg_dropout_mask above).  Counter-based masks from `seed`:
+ * the backward regenerates them, nothing is stored, the same (inputs, p, seed) give the same bits.  Each mask multiplies the
+ * fp32 value before its rounding; the probabilities are masked after the row sum (the normaliser is the undropped one).
+ * label_logprobs / loss_sum_count are the DROPPED model's.  d_enc carries no mask of its own: the encoder's final site
+ * belongs to rp_train_backward_hidden_dropout; hand both halves the same seed (the site numbers are disjoint).
+ * p = 0 gives rp_decoder_loss_grad's bits.  The workspace function returns rp_decoder_loss_grad_workspace_bytes' size: the
+ * masked bf16 gradient of a residual branch is written by the cast that precedes the branch either way. */
+size_t   rp_decoder_loss_grad_dropout_workspace_bytes(const RpDecoder* dec, const int32_t* src_cu, const int32_t* tgt_cu,
+                                                      int32_t batch);
+RpStatus rp_decoder_loss_grad_dropout(RpDecoder* dec, const void* enc_bf16, const int32_t* src_cu, const int32_t* tokens,
+                                      const int32_t* labels, const int32_t* tgt_cu, int32_t batch, float p, uint32_t seed,
+                                      float* label_logprobs, double* loss_sum_count, float* grads, float* d_enc,
+                                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* Refresh every resident copy of the decoder's weights from fp32 masters (after an optimizer step); DESIGN.md section 14.
  *   params  device fp32 [layout total], 16-byte aligned, in exactly rp_decoder_grad_layout's order and offsets (with the

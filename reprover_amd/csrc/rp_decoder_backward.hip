@@ -92,16 +92,27 @@ __global__ __launch_bounds__(256) void bwd_cast_kernel(const float* __restrict__
   const int t = blockIdx.x;
   for (int c = threadIdx.x; c < D; c += 256) out[(size_t)t * D + c] = f2bf(t < n_tok ? in[(size_t)t * D + c] : 0.f);
 }
+// out = bf16(mask * in): what the branch behind a residual dropout reads as its dY (dgrad and wgrad); the stream's own
+// gradient `in` passes the residual unmasked
+__global__ __launch_bounds__(256) void bwd_cast_drop_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, int D,
+                                                            int n_tok, Drop drop, uint32_t site) {
+  const int t = blockIdx.x;
+  for (int c = threadIdx.x; c < D; c += 256)
+    out[(size_t)t * D + c] = f2bf(t < n_tok ? drop_mul(drop, site, (uint32_t)t, (uint32_t)c) * in[(size_t)t * D + c] : 0.f);
+}
 
 // T5 RMSNorm backward of h = scale * w * x * rs, rs = rsqrt(mean(x^2) + eps), one workgroup per token:
 //   dx (+)= scale * (w * rs * dh - x * rs^3 * mean(dh * w * x));   dh <- scale * dh * x * rs   (the row's term of d w,
 // summed over the tokens by colsum_kernel afterwards).  ADD = 0 writes dx (the final norm opens the backward).
-template <bool ADD>
+// DROP (the final norm under dropout): the rows were h = mask * (...), so dh is read times the regenerated mask.
+template <bool ADD, bool DROP = false>
 __global__ __launch_bounds__(256) void bwd_rmsnorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                           float* __restrict__ dh, float* __restrict__ dx, int D, float eps,
-                                                          float scale) {
+                                                          float scale, Drop drop = Drop{0u, 0u, 1.f}) {
   __shared__ float red[4];
   const size_t base = (size_t)blockIdx.x * D;
+  if constexpr (DROP)
+    for (int c = threadIdx.x; c < D; c += 256) dh[base + c] *= drop_mul(drop, DROP_SITE_DEC_FINAL, blockIdx.x, (uint32_t)c);
   float ss = 0.f, dot = 0.f;
   for (int c = threadIdx.x; c < D; c += 256) {
     const float xv = x[base + c];
@@ -123,14 +134,19 @@ __global__ __launch_bounds__(256) void bwd_rmsnorm_kernel(const float* __restric
 // Backward of ff = gelu_new(g) * u:  dg = dff * u * gelu_new'(g), du = dff * gelu_new(g), written bf16 as [dg (F) | du (F)]
 // per token (wi_0's rows then wi_1's: the order of the plain FFN-in weight).  gu is the recomputed fp32 pre-activation
 // pair in the interleaved order of RpDecoder::wi_il (64-column blocks: 32 gate, the same 32 up).  Padding rows get 0.
+// DROP: the forward stored ff = mask * gelu_new(g) * u (HF:110), so dff is read times the regenerated mask.
+template <bool DROP>
 __global__ __launch_bounds__(256) void bwd_geglu_kernel(const float* __restrict__ gu, const float* __restrict__ dff,
-                                                        bf16_t* __restrict__ dgu, int F, int n_tok) {
+                                                        bf16_t* __restrict__ dgu, int F, int n_tok, Drop drop,
+                                                        uint32_t drop_site) {
   const int t = blockIdx.x;
   for (int f = threadIdx.x; f < F; f += 256) {
     float dg = 0.f, du = 0.f;
     if (t < n_tok) {
       const size_t gi = (size_t)t * 2 * F + 64 * (f >> 5) + (f & 31);
-      const float g = gu[gi], u = gu[gi + 32], d = dff[(size_t)t * F + f];
+      const float g = gu[gi], u = gu[gi + 32];
+      float d = dff[(size_t)t * F + f];
+      if constexpr (DROP) d *= drop_mul(drop, drop_site, (uint32_t)t, (uint32_t)f);
       const float c0 = 0.7978845608028654f, c1 = 0.044715f;
       const float th = tanhf(c0 * (g + c1 * g * g * g));
       const float dgelu = 0.5f * (1.f + th) + 0.5f * g * (1.f - th * th) * c0 * (1.f + 3.f * c1 * g * g);
@@ -144,9 +160,11 @@ __global__ __launch_bounds__(256) void bwd_geglu_kernel(const float* __restrict_
 
 // d embed[v] (+)= sum over the tokens t with clamp(tokens[t]) == v, in token order, of dx[t] (embed_bwd_kernel's pattern on
 // the fp32 stream gradient: one owner per vocabulary row, no atomics).  ADD: the tied head's weight gradient is there.
-template <bool ADD>
+// DROP: the forward's rows were mask * embed[id] (HF:725), so each dx row is read times the regenerated mask.
+template <bool ADD, bool DROP = false>
 __global__ __launch_bounds__(256) void bwd_embed_kernel(const int32_t* __restrict__ ids, int T, int vocab,
-                                                        const float* __restrict__ dx, int D, float* __restrict__ dtable) {
+                                                        const float* __restrict__ dx, int D, float* __restrict__ dtable,
+                                                        Drop drop = Drop{0u, 0u, 1.f}) {
   __shared__ unsigned long long masks[4];
   const int v = blockIdx.x, col = blockIdx.y * 256 + threadIdx.x;
   const int wave = threadIdx.x >> 6;
@@ -163,7 +181,13 @@ __global__ __launch_bounds__(256) void bwd_embed_kernel(const int32_t* __restric
       while (mm) {
         const int bit = __builtin_ctzll(mm);
         mm &= mm - 1;
-        if (col < D) acc += dx[(size_t)(base + w * 64 + bit) * D + col];
+        if (col < D) {
+          const int t = base + w * 64 + bit;
+          if constexpr (DROP)
+            acc += dx[(size_t)t * D + col] * drop_mul(drop, DROP_SITE_DEC_EMBED, (uint32_t)t, (uint32_t)col);
+          else
+            acc += dx[(size_t)t * D + col];
+        }
       }
     }
     __syncthreads();
@@ -186,6 +210,9 @@ __global__ __launch_bounds__(256) void bwd_embed_kernel(const int32_t* __restric
 // Two passes, no atomics on HBM.  CAUSAL (self-attention, k_cu = q_cu): keys j <= i; MODE 0 stops at the key tile of the
 // block's last query, MODE 1 starts at the query tile of the block's first key.  P and dS are rounded to bf16 for the
 // second MFMAs.
+// DROP (the forward masked P before P V, mask M of dec_flash_kernel's elements): dV = (P M)^T dO, dP = M (dO V^T),
+// dS = P (dP - delta); delta = rowsum(dO O) is unchanged because O was built from P M.  MODE 0 walks keys (two column
+// pairs per four rows), MODE 1 walks queries (the lane's key picks the 16-bit field): the hash counter is linear in both.
 struct FlashBwdArgs {
   const bf16_t* q;
   int ldq;
@@ -205,9 +232,11 @@ struct FlashBwdArgs {
   bf16_t* dkv;  // MODE 1 [*, lddkv]: dK at column dkoff, dV at dvoff
   int lddkv, dkoff, dvoff;
   float* dtab_part;  // MODE 0, CAUSAL: [entries, H, nbias]
+  Drop drop = {0u, 0u, 1.f};  // thresh 0: no dropout
+  uint32_t drop_site = 0;
 };
 
-template <int MODE, bool CAUSAL>
+template <int MODE, bool CAUSAL, bool DROP>
 __global__ __launch_bounds__(256, 2) void dec_flash_bwd_kernel(FlashBwdArgs a) {
   constexpr bool TAB = MODE == 0 && CAUSAL;
   constexpr int WTAB = TAB ? 4 * FA_TAB_MAX * 4 : 0;
@@ -359,6 +388,18 @@ __global__ __launch_bounds__(256, 2) void dec_flash_bwd_kernel(FlashBwdArgs a) {
           lse_m[0] = lv.x; lse_m[1] = lv.y; lse_m[2] = lv.z; lse_m[3] = lv.w;
           del_m[0] = dv.x; del_m[1] = dv.y; del_m[2] = dv.z; del_m[3] = dv.w;
         }
+        float dmul[4];
+        if constexpr (DROP) {
+          const int jg = c0 + 8 * g + 4 * hi;  // even: the lane's four streamed indices are jg .. jg + 3
+          const uint32_t hcol = (uint32_t)h << 20;
+          if (MODE == 0) {  // streamed keys: two column pairs of the query's row
+            drop_mul2(a.drop, a.drop_site, (uint32_t)(qs + ni), hcol | (uint32_t)jg, dmul[0], dmul[1]);
+            drop_mul2(a.drop, a.drop_site, (uint32_t)(qs + ni), hcol | (uint32_t)(jg + 2), dmul[2], dmul[3]);
+          } else {  // streamed queries: the lane's key picks the field, the row advances
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dmul[e] = drop_mul(a.drop, a.drop_site, (uint32_t)(qs + jg + e), hcol | (uint32_t)ni);
+          }
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * g + e;
@@ -370,8 +411,13 @@ __global__ __launch_bounds__(256, 2) void dec_flash_bwd_kernel(FlashBwdArgs a) {
           const float del = (MODE == 0) ? delta_n : del_m[e];
           float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[mb][r] + bias, LOG2E, -lse));
           if (!live) p = 0.f;
-          const float ds = live ? p * (dp[mb][r] - del) : 0.f;
-          s[mb][r] = p;
+          float pm = p, dpv = dp[mb][r];
+          if constexpr (DROP) {
+            pm *= dmul[e];
+            dpv *= dmul[e];
+          }
+          const float ds = live ? p * (dpv - del) : 0.f;
+          s[mb][r] = pm;
           dp[mb][r] = ds;
           if (TAB) {
             const int kr = 8 * g + 4 * hi + e;
@@ -558,41 +604,61 @@ void launch_dlogits(const float* logits, int V, int n_tok, int rows_pad, const i
                     bf16_t* out, hipStream_t s) {
   hipLaunchKernelGGL(bwd_dlogits_kernel, dim3(rows_pad), dim3(256), 0, s, logits, V, n_tok, labels, sum_count, out);
 }
-void launch_cast(const float* in, bf16_t* out, int D, int n_tok, int rows_pad, hipStream_t s) {
-  hipLaunchKernelGGL(bwd_cast_kernel, dim3(rows_pad), dim3(256), 0, s, in, out, D, n_tok);
+const Drop NO_DROP = {0u, 0u, 1.f};
+// (site: the residual-branch site whose mask the cast applies; ignored without dropout)
+void launch_cast(const float* in, bf16_t* out, int D, int n_tok, int rows_pad, hipStream_t s, const Drop& drop = NO_DROP,
+                 uint32_t site = 0u) {
+  if (drop.thresh)
+    hipLaunchKernelGGL(bwd_cast_drop_kernel, dim3(rows_pad), dim3(256), 0, s, in, out, D, n_tok, drop, site);
+  else
+    hipLaunchKernelGGL(bwd_cast_kernel, dim3(rows_pad), dim3(256), 0, s, in, out, D, n_tok);
 }
-void launch_geglu_bwd(const float* gu, const float* dff, bf16_t* dgu, int F, int n_tok, int rows_pad, hipStream_t s) {
-  hipLaunchKernelGGL(bwd_geglu_kernel, dim3(rows_pad), dim3(256), 0, s, gu, dff, dgu, F, n_tok);
-}
-// dh -> dx through the norm whose input rows were x; the rows' terms of d ln are summed into dln
-void launch_norm_bwd(const float* x, const float* ln, float* dh, float* dx, int n_tok, int D, float eps, float sc, bool add,
-                     float* dln, hipStream_t s) {
-  with_bool(add, [&](auto a) {
-    hipLaunchKernelGGL(bwd_rmsnorm_kernel<decltype(a)::value>, dim3(n_tok), dim3(256), 0, s, x, ln, dh, dx, D, eps, sc);
+void launch_geglu_bwd(const float* gu, const float* dff, bf16_t* dgu, int F, int n_tok, int rows_pad, hipStream_t s,
+                      const Drop& drop = NO_DROP, uint32_t site = 0u) {
+  with_bool(drop.thresh != 0, [&](auto dr) {
+    hipLaunchKernelGGL(bwd_geglu_kernel<decltype(dr)::value>, dim3(rows_pad), dim3(256), 0, s, gu, dff, dgu, F, n_tok, drop,
+                       site);
   });
+}
+// dh -> dx through the norm whose input rows were x; the rows' terms of d ln are summed into dln.  drop (the final norm
+// alone, which writes dx): its rows were masked at DROP_SITE_DEC_FINAL.
+void launch_norm_bwd(const float* x, const float* ln, float* dh, float* dx, int n_tok, int D, float eps, float sc, bool add,
+                     float* dln, hipStream_t s, const Drop& drop = NO_DROP) {
+  if (drop.thresh && !add)
+    hipLaunchKernelGGL((bwd_rmsnorm_kernel<false, true>), dim3(n_tok), dim3(256), 0, s, x, ln, dh, dx, D, eps, sc, drop);
+  else
+    with_bool(add, [&](auto a) {
+      hipLaunchKernelGGL((bwd_rmsnorm_kernel<decltype(a)::value, false>), dim3(n_tok), dim3(256), 0, s, x, ln, dh, dx, D, eps,
+                         sc, NO_DROP);
+    });
   hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, s, (const float*)dh, n_tok, D, dln);
 }
-void launch_embed_bwd(bool add_, const int32_t* ids, int T, int V, const float* dx, int D, float* dtable, hipStream_t s) {
+void launch_embed_bwd(bool add_, const int32_t* ids, int T, int V, const float* dx, int D, float* dtable, hipStream_t s,
+                      const Drop& drop = NO_DROP) {
   with_bool(add_, [&](auto add) {
-    hipLaunchKernelGGL(bwd_embed_kernel<decltype(add)::value>, dim3(V, (D + 255) / 256), dim3(256), 0, s, ids, T, V, dx, D,
-                       dtable);
+    with_bool(drop.thresh != 0, [&](auto dr) {
+      hipLaunchKernelGGL((bwd_embed_kernel<decltype(add)::value, decltype(dr)::value>), dim3(V, (D + 255) / 256), dim3(256), 0,
+                         s, ids, T, V, dx, D, dtable, drop);
+    });
   });
 }
 // both passes of the attention backward: dQ (+ delta, + the table partials when causal) over the query blocks, then
 // dK | dV over the key blocks (causal: the query blocks again)
 void launch_flash_bwd(bool causal, FlashBwdArgs fa, int H, const int2* qwork, int n_qwork, const int2* kwork, int n_kwork,
                       hipStream_t s) {
+  auto launch = [&](auto mode, int n) {
+    constexpr int M = decltype(mode)::value;
+    with_bool(causal, [&](auto c) {
+      with_bool(fa.drop.thresh != 0, [&](auto dr) {
+        hipLaunchKernelGGL((dec_flash_bwd_kernel<M, decltype(c)::value, decltype(dr)::value>), dim3(H * n), dim3(256), 0, s, fa);
+      });
+    });
+  };
   fa.work = qwork;
-  if (causal)
-    hipLaunchKernelGGL((dec_flash_bwd_kernel<0, true>), dim3(H * n_qwork), dim3(256), 0, s, fa);
-  else
-    hipLaunchKernelGGL((dec_flash_bwd_kernel<0, false>), dim3(H * n_qwork), dim3(256), 0, s, fa);
+  launch(std::integral_constant<int, 0>{}, n_qwork);
   fa.work = kwork;
   if (!n_kwork) return;
-  if (causal)
-    hipLaunchKernelGGL((dec_flash_bwd_kernel<1, true>), dim3(H * n_kwork), dim3(256), 0, s, fa);
-  else
-    hipLaunchKernelGGL((dec_flash_bwd_kernel<1, false>), dim3(H * n_kwork), dim3(256), 0, s, fa);
+  launch(std::integral_constant<int, 1>{}, n_kwork);
 }
 void launch_bias_grad(const float* dtab_part, int n_work, int H, int nbias, const int32_t* bucket_of, int nbuckets,
                       float* d_rel_bias, hipStream_t s) {
@@ -645,10 +711,18 @@ extern "C" size_t rp_decoder_loss_grad_workspace_bytes(const RpDecoder* d, const
   return bwd_carve(d, batch, n_src, n_tgt, nullptr).bytes;
 }
 
-extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, const int32_t* src_cu, const int32_t* tokens,
-                                         const int32_t* labels, const int32_t* tgt_cu, int32_t batch,
-                                         float* label_logprobs, double* loss_sum_count, float* grads, float* d_enc,
-                                         void* ws, size_t ws_bytes, void* stream_) {
+// The dropout form needs no buffer of its own: the branch behind a residual mask reads bf16(mask * dx), and the fp32 stream
+// gradient is cast into the bf16 operand buffer (dyb) in front of every branch anyway - the mask rides on that cast.
+extern "C" size_t rp_decoder_loss_grad_dropout_workspace_bytes(const RpDecoder* d, const int32_t* src_cu, const int32_t* tgt_cu,
+                                                               int32_t batch) {
+  return rp_decoder_loss_grad_workspace_bytes(d, src_cu, tgt_cu, batch);
+}
+
+// rp_decoder_loss_grad (drop.thresh == 0) and rp_decoder_loss_grad_dropout: one body, the launches differ only where a mask
+// is applied
+static RpStatus loss_grad(RpDecoder* d, const void* enc_bf16, const int32_t* src_cu, const int32_t* tokens,
+                          const int32_t* labels, const int32_t* tgt_cu, int32_t batch, const Drop& drop, float* label_logprobs,
+                          double* loss_sum_count, float* grads, float* d_enc, void* ws, size_t ws_bytes, void* stream_) {
   RpStatus st = bwd_check_model(d);
   if (st) return st;
   int n_src = 0, n_tgt = 0;
@@ -710,7 +784,7 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
 
   // ---- forward: the shared sequence on the per-layer slots ----------------------------------------------------------------
   if ((st = fwd_launch_layers(d, enc_bf16, tokens, labels, batch, n_src, n_tgt, w.meta, n_work, bufs.data(), fin,
-                              label_logprobs, loss_sum_count, nullptr, s)))
+                              label_logprobs, loss_sum_count, nullptr, s, drop)))
     return st;
 
   // ---- backward --------------------------------------------------------------------------------------------------------------
@@ -719,9 +793,10 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
                  DxKind kind, void* dX) { return linear_bwd(dY, X, n_tgt, Tp, W, R, C, slices, kind, dX, w.wt, s); };
   // w.dh -> w.dx through the norm whose input rows were x
   auto norm_bwd = [&](const float* x, const float* ln, float sc, bool add, float* dln) {
-    launch_norm_bwd(x, ln, w.dh, w.dx, n_tgt, D, eps, sc, add, dln, s);
+    launch_norm_bwd(x, ln, w.dh, w.dx, n_tgt, D, eps, sc, add, dln, s, add ? NO_DROP : drop);
   };
-  auto cast_dx = [&]() { launch_cast(w.dx, w.dyb, D, n_tgt, Tp, s); };
+  // dyb = bf16([mask *] dx): the dY of the residual branch that was dropped at `site`
+  auto cast_dx = [&](uint32_t site) { launch_cast(w.dx, w.dyb, D, n_tgt, Tp, s, drop, site); };
 
   // loss and head
   launch_dlogits(w.logits, V, n_tgt, Tp, labels, loss_sum_count, w.dlog, s);
@@ -737,22 +812,24 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   fa.delta = w.delta;
   fa.ld_stat = Tp;
   fa.dtab_part = w.dtab_part;
+  fa.drop = drop;
   for (int i = L - 1; i >= 0; --i) {
     const RpDecoder::Layer& l = d->layers[i];
     const FwdLayerBufs& b = bufs[i];
+    const uint32_t site = DROP_SITE_DEC_LAYER0 + 8u * (uint32_t)i;  // + {0 .. 5}, as in fwd_launch_layers
     auto Gl = [&](int k) { return G(lay.layer(i, k)); };
     // gated-GELU FFN
-    cast_dx();
+    cast_dx(site + 5);
     if ((st = lin(w.dyb, b.ff, l.wo2, D, F, {{0, D, Gl(G_WO)}}, DX_F32, w.dff))) return st;
     if ((st = fwd_gemm(b.h2, n_tgt, Tp, d->wi_il + (size_t)i * 2 * F * D, 2 * F, D, EpiDecF32<false>{w.gu, 2 * F, 2 * F, n_tgt},
                        s, RP_K_GEMM_WI)))
       return st;
-    launch_geglu_bwd(w.gu, w.dff, w.dgu, F, n_tgt, Tp, s);
+    launch_geglu_bwd(w.gu, w.dff, w.dgu, F, n_tgt, Tp, s, drop, site + 4);
     if ((st = lin(w.dgu, b.h2, l.wi, 2 * F, D, {{0, F, Gl(G_WI0)}, {F, F, Gl(G_WI1)}}, DX_F32, w.dh))) return st;
     norm_bwd(b.x2, l.ln_ff, 1.f, true, Gl(G_LN_FF));
 
     // cross-attention
-    cast_dx();
+    cast_dx(site + 3);
     if ((st = lin(w.dyb, b.att_c, l.co, D, inner, {{0, D, Gl(G_CO)}}, DX_BF16, w.datt))) return st;
     fa.q = b.cq; fa.ldq = inner;
     fa.kv = b.ckv; fa.ldkv = 2 * inner; fa.koff = 0; fa.voff = inner;
@@ -761,6 +838,7 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
     fa.lse2 = b.lse_c;
     fa.dq = w.dcq; fa.lddq = inner;
     fa.dkv = w.dkv; fa.lddkv = 2 * inner; fa.dkoff = 0; fa.dvoff = inner;
+    fa.drop_site = site + 2;
     launch_flash_bwd(false, fa, H, d_work, n_work, d_kwork, n_kwork, s);
     // the launch order of the two cross projections is kept: all three weight gradients, the K | V projection's dX (over
     // the source rows, added into d_enc), then the q projection's dX
@@ -772,7 +850,7 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
     norm_bwd(b.x1, l.ln_cross, 1.f, true, Gl(G_LN_CROSS));
 
     // self-attention
-    cast_dx();
+    cast_dx(site + 1);
     if ((st = lin(w.dyb, b.att_s, l.wo, D, inner, {{0, D, Gl(G_O)}}, DX_BF16, w.datt))) return st;
     fa.q = b.qkv; fa.ldq = 3 * inner;
     fa.kv = b.qkv; fa.ldkv = 3 * inner; fa.koff = inner; fa.voff = 2 * inner;
@@ -781,6 +859,7 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
     fa.lse2 = b.lse_s;
     fa.dq = w.dqkv; fa.lddq = 3 * inner;
     fa.dkv = w.dqkv; fa.lddkv = 3 * inner; fa.dkoff = inner; fa.dvoff = 2 * inner;
+    fa.drop_site = site;
     launch_flash_bwd(true, fa, H, d_work, n_work, d_work, n_work, s);
     if ((st = lin(w.dqkv, b.h0, l.wqkv, 3 * inner, D,
                   {{0, inner, Gl(G_Q)}, {inner, inner, Gl(G_K)}, {2 * inner, inner, Gl(G_V)}}, DX_F32, w.dh)))
@@ -789,19 +868,35 @@ extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, con
   }
   // the shared bias table (every layer added into the same partial rows) and the embedding
   launch_bias_grad(w.dtab_part, n_work, H, d->nbias, d_bucket, c.rel_num_buckets, G(lay.rel_bias()), s);
-  launch_embed_bwd(d->tied, tokens, n_tgt, V, w.dx, D, G(lay.shared()), s);  // tied: the head's weight gradient is already there
+  launch_embed_bwd(d->tied, tokens, n_tgt, V, w.dx, D, G(lay.shared()), s, drop);  // tied: the head's weight gradient is already there
   RP_CHECK_LAUNCH();
   return RP_OK;
+}
+
+extern "C" RpStatus rp_decoder_loss_grad(RpDecoder* d, const void* enc_bf16, const int32_t* src_cu, const int32_t* tokens,
+                                         const int32_t* labels, const int32_t* tgt_cu, int32_t batch,
+                                         float* label_logprobs, double* loss_sum_count, float* grads, float* d_enc,
+                                         void* ws, size_t ws_bytes, void* stream_) {
+  return loss_grad(d, enc_bf16, src_cu, tokens, labels, tgt_cu, batch, NO_DROP, label_logprobs, loss_sum_count, grads, d_enc, ws,
+                   ws_bytes, stream_);
+}
+
+extern "C" RpStatus rp_decoder_loss_grad_dropout(RpDecoder* d, const void* enc_bf16, const int32_t* src_cu, const int32_t* tokens,
+                                                 const int32_t* labels, const int32_t* tgt_cu, int32_t batch, float p,
+                                                 uint32_t seed, float* label_logprobs, double* loss_sum_count, float* grads,
+                                                 float* d_enc, void* ws, size_t ws_bytes, void* stream_) {
+  RP_REQUIRE(p >= 0.f && p < 1.f, "dropout probability %g", (double)p);
+  return loss_grad(d, enc_bf16, src_cu, tokens, labels, tgt_cu, batch, make_drop(p, seed), label_logprobs, loss_sum_count, grads,
+                   d_enc, ws, ws_bytes, stream_);
 }
 
 // ---- kernel-level test entry points (include/reprover_hip.h: tests/test_decoder_kernels_gpu.py) -----------------------------
 // The attention kernels alone on caller-supplied operands in the product's layouts, through the product's work lists and
 // launch functions.  Scratch (metadata, table partials) is allocated here; no output is zeroed.
-extern "C" RpStatus rp_dbg_decoder_attention(int32_t causal, const void* q, const void* kv, const void* d_o,
-                                             const int32_t* q_cu, const int32_t* k_cu, int32_t batch, int32_t H,
-                                             const float* bias_tab, int32_t nbias, const int32_t* bucket_of, int32_t nbuckets,
-                                             void* out, float* lse2, float* delta, void* dq, void* dkv, float* dtab,
-                                             void* stream_) {
+static RpStatus dbg_attention(int32_t causal, const void* q, const void* kv, const void* d_o, const int32_t* q_cu,
+                              const int32_t* k_cu, int32_t batch, int32_t H, const float* bias_tab, int32_t nbias,
+                              const int32_t* bucket_of, int32_t nbuckets, const Drop& drop, uint32_t drop_site, void* out,
+                              float* lse2, float* delta, void* dq, void* dkv, float* dtab, void* stream_) {
   RP_REQUIRE(q && d_o && q_cu && out && lse2 && delta && dq, "null argument");
   RP_REQUIRE(H >= 1 && H <= 64, "H=%d", H);
   if (causal) {
@@ -852,6 +947,8 @@ extern "C" RpStatus rp_dbg_decoder_attention(int32_t causal, const void* q, cons
   fa.delta = delta;
   fa.ld_stat = Tp;
   fa.dtab_part = part;
+  fa.drop = drop;
+  fa.drop_site = drop_site;
   fa.o = (const bf16_t*)out;
   fa.d_o = (const bf16_t*)d_o;
   fa.lse2 = lse2;
@@ -870,12 +967,48 @@ extern "C" RpStatus rp_dbg_decoder_attention(int32_t causal, const void* q, cons
     fa.dkv = (bf16_t*)dkv; fa.lddkv = 2 * inner; fa.dkoff = 0; fa.dvoff = inner;
   }
   launch_dec_flash(causal != 0, fa.q, fa.ldq, fa.kv, fa.ldkv, fa.koff, fa.voff, fa.q_cu, fa.k_cu, d_work, n_work, H, bias_tab,
-                   fa.nbias, (bf16_t*)out, inner, lse2, Tp, s);
+                   fa.nbias, (bf16_t*)out, inner, lse2, Tp, s, drop, drop_site);
   launch_flash_bwd(causal != 0, fa, H, d_work, n_work, d_kwork, n_kwork, s);
   if (causal) launch_bias_grad(part, n_work, H, nbias, d_meta + bucket_at, nbuckets, dtab, s);
   const hipError_t le = hipGetLastError();
   if (le != hipSuccess) return done(fail(RP_E_HIP, "decoder attention launch failed: %s", hipGetErrorString(le)));
   return done(RP_OK);
+}
+
+extern "C" RpStatus rp_dbg_decoder_attention(int32_t causal, const void* q, const void* kv, const void* d_o,
+                                             const int32_t* q_cu, const int32_t* k_cu, int32_t batch, int32_t H,
+                                             const float* bias_tab, int32_t nbias, const int32_t* bucket_of, int32_t nbuckets,
+                                             void* out, float* lse2, float* delta, void* dq, void* dkv, float* dtab,
+                                             void* stream_) {
+  return dbg_attention(causal, q, kv, d_o, q_cu, k_cu, batch, H, bias_tab, nbias, bucket_of, nbuckets, NO_DROP, 0u, out, lse2,
+                       delta, dq, dkv, dtab, stream_);
+}
+
+// rp_dbg_decoder_attention with the probabilities dropped at (p, seed, site): the same launch functions in their dropout form
+extern "C" RpStatus rp_dbg_decoder_attention_dropout(int32_t causal, const void* q, const void* kv, const void* d_o,
+                                                     const int32_t* q_cu, const int32_t* k_cu, int32_t batch, int32_t H,
+                                                     const float* bias_tab, int32_t nbias, const int32_t* bucket_of,
+                                                     int32_t nbuckets, float p, uint32_t seed, uint32_t site, void* out,
+                                                     float* lse2, float* delta, void* dq, void* dkv, float* dtab,
+                                                     void* stream_) {
+  RP_REQUIRE(p >= 0.f && p < 1.f, "dropout probability %g", (double)p);
+  return dbg_attention(causal, q, kv, d_o, q_cu, k_cu, batch, H, bias_tab, nbias, bucket_of, nbuckets, make_drop(p, seed), site,
+                       out, lse2, delta, dq, dkv, dtab, stream_);
+}
+
+// The embedding site's two kernels alone, both fp32 end to end: x [n_tok, n] = mask * embed[ids] (dec_embed_drop_kernel) and
+// dtable [vocab, n] = the per-id sum of mask * dx (bwd_embed_kernel<false, true>), the mask of (DROP_SITE_DEC_EMBED, row =
+// token, column = feature).  On a table of ones x IS the multiplier: exactly 0 or fp32 1 / (1 - p).
+extern "C" RpStatus rp_dbg_decoder_embed_dropout(const int32_t* ids, int32_t n_tok, const float* embed, int32_t vocab, int32_t n,
+                                                 float p, uint32_t seed, const float* dx, float* x, float* dtable, void* stream_) {
+  RP_REQUIRE(ids && embed && dx && x && dtable && n_tok >= 1 && vocab >= 1 && n >= 1, "bad argument");
+  RP_REQUIRE(p > 0.f && p < 1.f, "dropout probability %g", (double)p);
+  hipStream_t s = (hipStream_t)stream_;
+  const Drop drop = make_drop(p, seed);
+  hipLaunchKernelGGL(dec_embed_drop_kernel, dim3(n_tok), dim3(256), 0, s, ids, embed, x, n, vocab, drop);
+  launch_embed_bwd(false, ids, n_tok, vocab, dx, n, dtable, s, drop);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
 }
 
 // The row kernels of the decoder backward, one per mode, through the product's launch functions:

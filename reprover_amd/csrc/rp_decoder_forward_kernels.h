@@ -3,6 +3,7 @@
 // on per-layer activation slots: two fillings of FwdLayerBufs, the same launches.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "rp_decoder_common.h"
@@ -44,10 +45,26 @@ struct EpiDecBf16 {  // out[token, feature] = bf16(acc)
     }
   }
 };
-template <bool ADD>
-struct EpiDecF32 {  // out[token, feature] (+)= acc: the fp32 residual stream (ADD) or the lm_head logits
+// Training dropout of an epilogue (rp_decoder_loss_grad_dropout): the mask of (site, row = token, column = feature)
+// multiplies the fp32 accumulator before anything is rounded or added.  The <.., false> forms hold no such member.
+struct DropSite {
+  Drop d;
+  uint32_t site;
+};
+struct NoDropSite {};
+template <bool DROP>
+using DropSiteIf = typename std::conditional<DROP, DropSite, NoDropSite>::type;
+// multipliers of a lane's four consecutive features f .. f + 3 (f a multiple of 4) of token t
+__device__ __forceinline__ void drop_mul4(const DropSite& ds, int t, int f, float (&m)[4]) {
+  drop_mul2(ds.d, ds.site, (uint32_t)t, (uint32_t)f, m[0], m[1]);
+  drop_mul2(ds.d, ds.site, (uint32_t)t, (uint32_t)f + 2u, m[2], m[3]);
+}
+
+template <bool ADD, bool DROP = false>
+struct EpiDecF32 {  // out[token, feature] (+)= [mask *] acc: the fp32 residual stream (ADD) or the lm_head logits
   float* out;
   int ldo, n_feat, n_tok;
+  [[no_unique_address]] DropSiteIf<DROP> drop;  // DROP: HF's dropout on the sub-layer's output before the add (:400, :431, :140)
   template <int FM, int FN>
   __device__ __forceinline__ void run(f32x16 (&acc)[FM][FN], int m_base, int n_base, int lane, char*) {
     const int hi = lane >> 5, cl = lane & 31;
@@ -62,6 +79,12 @@ struct EpiDecF32 {  // out[token, feature] (+)= acc: the fp32 residual stream (A
           const int f = m_base + 32 * i + 8 * g + 4 * hi;
           if (f >= n_feat) continue;
           float* p = out + (size_t)t * ldo + f;
+          if constexpr (DROP) {
+            float m[4];
+            drop_mul4(drop, t, f, m);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] *= m[e];
+          }
           if ((ldo & 3) == 0 && f + 4 <= n_feat) {  // 16-byte aligned and inside the row: one vector access
             float4 v = make_float4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
             if constexpr (ADD) {
@@ -79,10 +102,13 @@ struct EpiDecF32 {  // out[token, feature] (+)= acc: the fp32 residual stream (A
   }
 };
 // FFN-in on the interleaved weight (RpDecoder::wi_il): row fragment 2 k is the gate (wi_0) and 2 k + 1 the up (wi_1)
-// projection of the same 32 features (m_base is a multiple of 64): out = bf16(gelu_new(a0) * a1), the decode step's form.
+// projection of the same 32 features (m_base is a multiple of 64): out = bf16([mask *] gelu_new(a0) * a1), the decode
+// step's form; DROP: HF's dropout inside the gated FFN (:110).
+template <bool DROP = false>
 struct EpiDecGeglu {
   bf16_t* out;
   int ldo, n_feat, n_tok;
+  [[no_unique_address]] DropSiteIf<DROP> drop;
   template <int FM, int FN>
   __device__ __forceinline__ void run(f32x16 (&acc)[FM][FN], int m_base, int n_base, int lane, char*) {
     static_assert(FM % 2 == 0, "gate and up fragments in pairs");
@@ -100,6 +126,12 @@ struct EpiDecGeglu {
           float r[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) r[e] = gelu_tanh(acc[i][j][4 * g + e]) * acc[i + 1][j][4 * g + e];
+          if constexpr (DROP) {
+            float m[4];
+            drop_mul4(drop, t, f, m);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] *= m[e];
+          }
           uint2 v;
           v.x = pack_bf2(r[0], r[1]);
           v.y = pack_bf2(r[2], r[3]);
@@ -130,13 +162,16 @@ RpStatus fwd_gemm(const bf16_t* act, int n_tok, int n_tok_pad, const bf16_t* W, 
 constexpr int FA_Q = 128, FA_KV = 64, FA_TAB_MAX = 1024;
 constexpr int FA_K_BYTES = 64 * 128, FA_V_BYTES = 64 * 128, FA_STAGE = FA_K_BYTES + FA_V_BYTES;
 
-template <bool CAUSAL>
+// DROP (training, rp_decoder_loss_grad_dropout): HF's dropout on the probabilities (:168).  P is masked after the row sum
+// and before the PV MFMA, so the normaliser and lse2 are the undropped ones; mask element = (drop_site, row = the query's
+// packed index q_cu[b] + i, column = (head << 20) | j).  A lane's keys r, r + 1 (r even) are neighbours, one hash each.
+template <bool CAUSAL, bool DROP>
 __global__ __launch_bounds__(256) void dec_flash_kernel(const bf16_t* __restrict__ q, int ldq, const bf16_t* __restrict__ kv,
                                                         int ldkv, int koff, int voff, const int32_t* __restrict__ q_cu,
                                                         const int32_t* __restrict__ k_cu, const int2* __restrict__ work,
                                                         const float* __restrict__ bias_tab, int nbias,
                                                         bf16_t* __restrict__ out, int ldo, float* __restrict__ lse2,
-                                                        int lse_ld) {
+                                                        int lse_ld, Drop drop, uint32_t drop_site) {
   __shared__ __attribute__((aligned(16))) char smem[2 * FA_STAGE + FA_TAB_MAX * 4];
   float* tab = reinterpret_cast<float*>(smem + 2 * FA_STAGE);
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, cl = lane & 31;
@@ -265,6 +300,20 @@ __global__ __launch_bounds__(256) void dec_flash_kernel(const bf16_t* __restrict
     }
     l_run += psum;
     m_run = m_new;
+    if constexpr (DROP) {
+      const uint32_t row = (uint32_t)(qs + qi), col0 = ((uint32_t)h << 20) | (uint32_t)k0;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb) {
+        if (kb == 1 && !two) break;
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          float m0, m1;
+          drop_mul2(drop, drop_site, row, col0 + (uint32_t)(kb * 32 + mfma32_row(r, hi)), m0, m1);
+          s[kb][r] *= m0;
+          s[kb][r + 1] *= m1;
+        }
+      }
+    }
     // O^T += V^T P^T over four 16-key slabs (P rounded to bf16: DESIGN.md section 10, rounding point R_P)
 #pragma unroll
     for (int sl = 0; sl < 4; ++sl) {
@@ -308,17 +357,45 @@ __global__ __launch_bounds__(256) void dec_flash_kernel(const bf16_t* __restrict
 }
 
 // One forward attention launch over the work list {pair, first query}: the causal form reads q | k | v at koff / voff of
-// one fused buffer (k_cu = q_cu) and the bias table, the cross form reads no table.
+// one fused buffer (k_cu = q_cu) and the bias table, the cross form reads no table.  drop.thresh != 0: the dropout form.
 inline void launch_dec_flash(bool causal, const bf16_t* q, int ldq, const bf16_t* kv, int ldkv, int koff, int voff,
                              const int32_t* q_cu, const int32_t* k_cu, const int2* work, int n_work, int H,
-                             const float* bias_tab, int nbias, bf16_t* out, int ldo, float* lse2, int lse_ld, hipStream_t s) {
+                             const float* bias_tab, int nbias, bf16_t* out, int ldo, float* lse2, int lse_ld, hipStream_t s,
+                             const Drop& drop = Drop{0u, 0u, 1.f}, uint32_t drop_site = 0u) {
   const dim3 att_grid(H * n_work);
+  auto launch = [&](auto kernel, const float* tab, int nb) {
+    hipLaunchKernelGGL(kernel, att_grid, dim3(256), 0, s, q, ldq, kv, ldkv, koff, voff, q_cu, k_cu, work, tab, nb, out, ldo,
+                       lse2, lse_ld, drop, drop_site);
+  };
   if (causal)
-    hipLaunchKernelGGL(dec_flash_kernel<true>, att_grid, dim3(256), 0, s, q, ldq, kv, ldkv, koff, voff, q_cu, k_cu, work,
-                       bias_tab, nbias, out, ldo, lse2, lse_ld);
+    drop.thresh ? launch(dec_flash_kernel<true, true>, bias_tab, nbias) : launch(dec_flash_kernel<true, false>, bias_tab, nbias);
   else
-    hipLaunchKernelGGL(dec_flash_kernel<false>, att_grid, dim3(256), 0, s, q, ldq, kv, ldkv, koff, voff, q_cu, k_cu, work,
-                       (const float*)nullptr, 1, out, ldo, lse2, lse_ld);
+    drop.thresh ? launch(dec_flash_kernel<false, true>, nullptr, 1) : launch(dec_flash_kernel<false, false>, nullptr, 1);
+}
+
+// ---- row kernels of the dropout form ---------------------------------------------------------------------------------------
+// dec_embed_kernel with HF's dropout on the embeddings (:725): x[t, :] = mask * embed[tokens[t], :]
+__global__ __launch_bounds__(256) void dec_embed_drop_kernel(const int32_t* __restrict__ tokens, const float* __restrict__ embed,
+                                                             float* __restrict__ x, int D, int V, Drop drop) {
+  const int b = blockIdx.x;
+  const int tok = min(max(tokens[b], 0), V - 1);
+  for (int c = threadIdx.x; c < D; c += 256)
+    x[(size_t)b * D + c] = embed[(size_t)tok * D + c] * drop_mul(drop, DROP_SITE_DEC_EMBED, (uint32_t)b, (uint32_t)c);
+}
+// dec_rmsnorm_kernel with HF's dropout after the final norm (:745): the mask multiplies the fp32 value, one rounding (the
+// tied head's d_model^-1/2 in `scale` commutes with it)
+__global__ __launch_bounds__(256) void dec_rmsnorm_drop_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                               bf16_t* __restrict__ out, int D, float eps, float scale,
+                                                               Drop drop) {
+  __shared__ float red[4];
+  const float* row = x + (size_t)blockIdx.x * D;
+  float ss = 0.f;
+  for (int c = threadIdx.x; c < D; c += 256) ss = fmaf(row[c], row[c], ss);
+  ss = block_sum256(ss, red);
+  const float r = rsqrtf(ss / (float)D + eps);
+  for (int c = threadIdx.x; c < D; c += 256)
+    out[(size_t)blockIdx.x * D + c] =
+        f2bf(drop_mul(drop, DROP_SITE_DEC_FINAL, blockIdx.x, (uint32_t)c) * (w[c] * (row[c] * r) * scale));
 }
 
 // ---- loss ---------------------------------------------------------------------------------------------------------------
@@ -451,10 +528,11 @@ float fwd_head_scale(const RpDecoder* d) { return d->tied ? 1.f / sqrtf((float)d
 // The whole teacher-forced forward on the device copy `meta` of fwd_build_meta's image: embed, the layers, final norm,
 // lm_head, the rows' log-softmax + label gather and the fixed-order reduction of the loss.  Where a residual GEMM's
 // destination differs from the stream it adds to, the n_tgt * D floats are copied there just before that GEMM.
+// drop (thresh 0 = off: the launches and kernels of the loss alone): the training dropout at HF's decoder sites.
 RpStatus fwd_launch_layers(const RpDecoder* d, const void* enc_bf16, const int32_t* tokens, const int32_t* labels, int batch,
                            int n_src, int n_tgt, const int32_t* meta, int n_work, const FwdLayerBufs* bufs,
                            const FwdFinalBufs& fin, float* label_logprobs, double* loss_sum_count, float* logprob_rows,
-                           hipStream_t s) {
+                           hipStream_t s, const Drop& drop = Drop{0u, 0u, 1.f}) {
   const RpT5Config& c = d->cfg;
   const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
   const float eps = c.layer_norm_eps;
@@ -469,19 +547,32 @@ RpStatus fwd_launch_layers(const RpDecoder* d, const void* enc_bf16, const int32
   auto move_stream = [&](float* to, const float* from) {
     return to != from ? hipMemcpyAsync(to, from, (size_t)n_tgt * D * 4, hipMemcpyDeviceToDevice, s) : hipSuccess;
   };
-  hipLaunchKernelGGL(dec_embed_kernel, dim3(n_tgt), dim3(256), 0, s, tokens, d->embed, L ? bufs[0].x0 : fin.x, D, V);
+  // x += [mask *] act W^T  and  ff = bf16([mask *] gelu(gate) * up): the residual and gated-GELU GEMMs in either form
+  auto resid_gemm = [&](const bf16_t* act, const bf16_t* W, int K, float* x, uint32_t site, int prof_class) {
+    return drop.thresh ? fwd_gemm(act, n_tgt, Tp, W, D, K, EpiDecF32<true, true>{x, D, D, n_tgt, {drop, site}}, s, prof_class)
+                       : fwd_gemm(act, n_tgt, Tp, W, D, K, EpiDecF32<true>{x, D, D, n_tgt}, s, prof_class);
+  };
+  auto geglu_gemm = [&](const bf16_t* act, const bf16_t* W, bf16_t* ff, uint32_t site) {
+    return drop.thresh ? fwd_gemm(act, n_tgt, Tp, W, 2 * F, D, EpiDecGeglu<true>{ff, F, F, n_tgt, {drop, site}}, s, RP_K_GEMM_WI)
+                       : fwd_gemm(act, n_tgt, Tp, W, 2 * F, D, EpiDecGeglu<>{ff, F, F, n_tgt}, s, RP_K_GEMM_WI);
+  };
+  if (drop.thresh)
+    hipLaunchKernelGGL(dec_embed_drop_kernel, dim3(n_tgt), dim3(256), 0, s, tokens, d->embed, L ? bufs[0].x0 : fin.x, D, V, drop);
+  else
+    hipLaunchKernelGGL(dec_embed_kernel, dim3(n_tgt), dim3(256), 0, s, tokens, d->embed, L ? bufs[0].x0 : fin.x, D, V);
   for (int i = 0; i < L; ++i) {
     const RpDecoder::Layer& l = d->layers[i];
     const FwdLayerBufs& b = bufs[i];
+    const uint32_t site = DROP_SITE_DEC_LAYER0 + 8u * (uint32_t)i;  // + {0 .. 5}: rp_encoder_kernels.h
     // self-attention: x += o(attn(rmsnorm(x))), causal inside each pair
     norm(b.x0, l.ln_self, b.h0, 1.f);
     if ((st = fwd_gemm(b.h0, n_tgt, Tp, l.wqkv, 3 * inner, D, EpiDecBf16{b.qkv, 3 * inner, 3 * inner, n_tgt}, s,
                        RP_K_GEMM_QKV)))
       return st;
     launch_dec_flash(true, b.qkv, 3 * inner, b.qkv, 3 * inner, inner, 2 * inner, d_tgt_cu, d_tgt_cu, d_work, n_work, H,
-                     d->bias_tab, d->nbias, b.att_s, inner, b.lse_s, b.lse_ld, s);
+                     d->bias_tab, d->nbias, b.att_s, inner, b.lse_s, b.lse_ld, s, drop, site);
     RP_HIP(move_stream(b.x1, b.x0));
-    if ((st = fwd_gemm(b.att_s, n_tgt, Tp, l.wo, D, inner, EpiDecF32<true>{b.x1, D, D, n_tgt}, s, RP_K_GEMM_O))) return st;
+    if ((st = resid_gemm(b.att_s, l.wo, inner, b.x1, site + 1, RP_K_GEMM_O))) return st;
     // cross-attention: the pair's queries over its own source's K / V (this layer's, from one GEMM over all sources)
     if ((st = fwd_gemm((const bf16_t*)enc_bf16, n_src, Sp, d->cross_kv_w + (size_t)2 * i * inner * D, 2 * inner, D,
                        EpiDecBf16{b.ckv, 2 * inner, 2 * inner, n_src}, s, RP_K_GEMM_QKV)))
@@ -490,18 +581,20 @@ RpStatus fwd_launch_layers(const RpDecoder* d, const void* enc_bf16, const int32
     if ((st = fwd_gemm(b.h1, n_tgt, Tp, l.cq, inner, D, EpiDecBf16{b.cq, inner, inner, n_tgt}, s, RP_K_GEMM_QKV)))
       return st;
     launch_dec_flash(false, b.cq, inner, b.ckv, 2 * inner, 0, inner, d_tgt_cu, d_src_cu, d_work, n_work, H, nullptr, 1,
-                     b.att_c, inner, b.lse_c, b.lse_ld, s);
+                     b.att_c, inner, b.lse_c, b.lse_ld, s, drop, site + 2);
     RP_HIP(move_stream(b.x2, b.x1));
-    if ((st = fwd_gemm(b.att_c, n_tgt, Tp, l.co, D, inner, EpiDecF32<true>{b.x2, D, D, n_tgt}, s, RP_K_GEMM_O))) return st;
+    if ((st = resid_gemm(b.att_c, l.co, inner, b.x2, site + 3, RP_K_GEMM_O))) return st;
     // gated-GELU FFN
     norm(b.x2, l.ln_ff, b.h2, 1.f);
-    if ((st = fwd_gemm(b.h2, n_tgt, Tp, d->wi_il + (size_t)i * 2 * F * D, 2 * F, D, EpiDecGeglu{b.ff, F, F, n_tgt}, s,
-                       RP_K_GEMM_WI)))
-      return st;
+    if ((st = geglu_gemm(b.h2, d->wi_il + (size_t)i * 2 * F * D, b.ff, site + 4))) return st;
     RP_HIP(move_stream(b.x3, b.x2));
-    if ((st = fwd_gemm(b.ff, n_tgt, Tp, l.wo2, D, F, EpiDecF32<true>{b.x3, D, D, n_tgt}, s, RP_K_GEMM_WO))) return st;
+    if ((st = resid_gemm(b.ff, l.wo2, F, b.x3, site + 5, RP_K_GEMM_WO))) return st;
   }
-  norm(fin.x, d->final_ln, fin.h, fwd_head_scale(d));
+  if (drop.thresh)
+    hipLaunchKernelGGL(dec_rmsnorm_drop_kernel, dim3(n_tgt), dim3(256), 0, s, (const float*)fin.x, (const float*)d->final_ln,
+                       fin.h, D, eps, fwd_head_scale(d), drop);
+  else
+    norm(fin.x, d->final_ln, fin.h, fwd_head_scale(d));
   if ((st = fwd_gemm(fin.h, n_tgt, Tp, d->lm_head, V, D, EpiDecF32<false>{fin.logits, V, V, n_tgt}, s, RP_K_GEMM_O)))
     return st;
   hipLaunchKernelGGL(fwd_loss_row_kernel, dim3(n_tgt), dim3(256), 0, s, fin.logits, V, labels, label_logprobs, logprob_rows);

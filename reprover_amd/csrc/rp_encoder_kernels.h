@@ -99,6 +99,20 @@ __device__ __forceinline__ float drop_mul(const Drop& d, uint32_t site, uint32_t
 // element ids: (site, row = packed token index, col = feature) - attention probabilities: row = the query's packed token
 // index, col = (head << 20) | key offset inside the sequence (sequences of up to 2^20 tokens: far beyond any max_seq_len)
 enum { DROP_SITE_EMBED = 0, DROP_SITE_FINAL = 1, DROP_SITE_LAYER0 = 16 };  // layer i: 16 + 8 i + {0 probs, 1 attn residual, 2 FFN inner, 3 FFN residual}
+// The decoder's sites (rp_decoder_loss_grad_dropout): disjoint from the encoder's, so one seed serves a whole seq2seq step.
+// Rows are packed TARGET token indices; the probabilities' key offset counts inside the pair's own key sequence (the target
+// for self-attention, the source for cross-attention).
+enum {
+  DROP_SITE_DEC_EMBED = 2,
+  DROP_SITE_DEC_FINAL = 3,
+  DROP_SITE_DEC_LAYER0 = 0x4000  // layer i: 0x4000 + 8 i + {0 self probs, 1 self residual, 2 cross probs, 3 cross residual, 4 FFN inner, 5 FFN residual}
+};
+// 16-bit threshold of the column-pair hash (drop_mul2): at least 1 for p > 0 (0 switches dropout off)
+inline Drop make_drop(float p, uint32_t seed) {
+  if (!(p > 0.f)) return Drop{seed, 0u, 1.f};
+  const long t = lround((double)p * 65536.0);
+  return Drop{seed, (uint32_t)std::min(std::max(t, 1L), 65535L), 1.f / (1.f - p)};
+}
 
 // ------------------------------------------------------------------------------------------
 // The residual stream x lives in HBM as TWO bf16 planes: hi = bf16(x) and lo = bf16(x - hi), x = hi + lo to 2^-18

@@ -338,18 +338,22 @@ RpStatus pool_head(RpTrainer* tr, const int32_t* cu, int batch, int T, float* ou
 
 // head of rp_train_forward_hidden: the final RMSNorm's rows, last_hidden_state [T, D] bf16 (on raw pointers: the trainer
 // and the rp_dbg_hidden_head test entry both launch through here)
+// drop (thresh 0 = off): the final site's mask, rp_train_forward_hidden_dropout alone
 RpStatus launch_hidden_head(const bf16_t* xhi, const bf16_t* xlo, const float* rs, const float* ln, bf16_t* out_hidden, int T,
-                            int D, hipStream_t stream) {
+                            int D, hipStream_t stream, const Drop& drop = Drop{0u, 0u, 1.f}) {
   ProfScope ps(stream, RP_K_HIDDEN_HEAD);
-  hipLaunchKernelGGL(hidden_head_kernel, dim3((T + HIDDEN_ROWS - 1) / HIDDEN_ROWS), dim3(256), 0, stream, xhi, xlo, rs, ln,
-                     out_hidden, T, D);
+  const dim3 grid((T + HIDDEN_ROWS - 1) / HIDDEN_ROWS);
+  if (drop.thresh)
+    hipLaunchKernelGGL(hidden_head_kernel<true>, grid, dim3(256), 0, stream, xhi, xlo, rs, ln, out_hidden, T, D, drop);
+  else
+    hipLaunchKernelGGL(hidden_head_kernel<false>, grid, dim3(256), 0, stream, xhi, xlo, rs, ln, out_hidden, T, D, drop);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
 RpStatus hidden_head(RpTrainer* tr, int T, bf16_t* out_hidden, const TrainWs& w, hipStream_t stream) {
   RpEncoder* e = tr->enc;
   return launch_hidden_head((const bf16_t*)w.xa[e->cfg.num_layers], (const bf16_t*)w.xlo, (const float*)w.rs_final,
-                            (const float*)e->final_ln, out_hidden, T, e->cfg.d_model, stream);
+                            (const float*)e->final_ln, out_hidden, T, e->cfg.d_model, stream, tr->drop);
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------
@@ -393,17 +397,20 @@ RpStatus pool_bwd_head(RpTrainer* tr, const int32_t* cu, int batch, int T, const
 // rows of final_layer_norm.weight's gradient, one per workgroup, go through dhead_part to colsum_kernel.
 // (on raw pointers, as launch_hidden_head; dhead_part: ceil(T / HIDDEN_BWD_ROWS) rows of D floats)
 RpStatus launch_hidden_bwd_head(const bf16_t* xhi, const bf16_t* xlo, const float* rs, const float* ln, const float* d_hidden,
-                                bf16_t* dxhi, bf16_t* dxlo, float* dhead_part, float* dln, int T, int D, hipStream_t stream) {
+                                bf16_t* dxhi, bf16_t* dxlo, float* dhead_part, float* dln, int T, int D, hipStream_t stream,
+                                const Drop& drop = Drop{0u, 0u, 1.f}) {
   const float inv_d = 1.f / (float)D;
   const int nblk = (T + HIDDEN_BWD_ROWS - 1) / HIDDEN_BWD_ROWS;
   {
     ProfScope ps(stream, RP_K_BWD_HIDDEN_HEAD);
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, stream, xhi, xlo, rs, ln, d_hidden, dxhi, dxlo, dhead_part, T, D, inv_d,
+                         drop);
+    };
     if (D <= 3 * 512)
-      hipLaunchKernelGGL(hidden_head_bwd_kernel<3>, dim3(nblk), dim3(256), 0, stream, xhi, xlo, rs, ln, d_hidden, dxhi, dxlo,
-                         dhead_part, T, D, inv_d);
+      drop.thresh ? launch(hidden_head_bwd_kernel<3, true>) : launch(hidden_head_bwd_kernel<3, false>);
     else
-      hipLaunchKernelGGL(hidden_head_bwd_kernel<4>, dim3(nblk), dim3(256), 0, stream, xhi, xlo, rs, ln, d_hidden, dxhi, dxlo,
-                         dhead_part, T, D, inv_d);
+      drop.thresh ? launch(hidden_head_bwd_kernel<4, true>) : launch(hidden_head_bwd_kernel<4, false>);
   }
   ProfScope ps(stream, RP_K_BWD_OTHER);
   hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)dhead_part, nblk, D, dln);
@@ -414,7 +421,7 @@ RpStatus hidden_bwd_head(RpTrainer* tr, int T, const float* d_hidden, float* gra
   RpEncoder* e = tr->enc;
   return launch_hidden_bwd_head((const bf16_t*)w.xa[e->cfg.num_layers], (const bf16_t*)w.xlo, (const float*)w.rs_final,
                                 (const float*)e->final_ln, d_hidden, w.dxhi, w.dxlo, w.dhead_part, grads + tr->lay.final_ln(), T,
-                                e->cfg.d_model, stream);
+                                e->cfg.d_model, stream, tr->drop);
 }
 
 // The shared body of rp_train_backward and rp_train_backward_hidden: from the residual gradient of the final stream
@@ -673,13 +680,6 @@ extern "C" RpStatus rp_trainer_create(const RpT5Config* cfg, const float* params
 
 extern "C" RpEncoder* rp_trainer_encoder(RpTrainer* tr) { return tr ? tr->enc : nullptr; }
 
-// 16-bit threshold of the column-pair hash (rp_encoder_kernels.h::drop_mul2): at least 1 for p > 0 (0 switches dropout off)
-static Drop make_drop(float p, uint32_t seed) {
-  if (!(p > 0.f)) return Drop{seed, 0u, 1.f};
-  const long t = std::lround((double)p * 65536.0);
-  return Drop{seed, (uint32_t)std::min(std::max(t, 1L), 65535L), 1.f / (1.f - p)};
-}
-
 extern "C" RpStatus rp_trainer_set_dropout(RpTrainer* tr, float p, uint32_t seed) {
   RP_REQUIRE(tr && p >= 0.f && p < 1.f, "dropout probability %g", (double)p);
   tr->drop = make_drop(p, seed);
@@ -749,10 +749,12 @@ static RpStatus train_entry(RpTrainer* tr, int32_t batch, int32_t T, void* works
     return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, w->bytes);
   return RP_OK;
 }
-// the hidden entry points run without dropout only: the decoder behind them has none, and a half-dropped model is neither
-// the reference's training mode nor its eval mode
-static RpStatus hidden_entry(const RpTrainer* tr, const char* what) {
-  RP_REQUIRE(!tr->drop.thresh, "%s: dropout is set (rp_trainer_set_dropout p > 0); the hidden entry points take p = 0 only", what);
+// the plain hidden entry points run without dropout only: what follows them must drop too (rp_decoder_loss_grad_dropout), or
+// the model is half-dropped, neither the reference's training mode nor its eval mode; the _dropout pair is the opt-in
+static RpStatus hidden_entry(const RpTrainer* tr, const char* what, bool dropout_ok) {
+  RP_REQUIRE(dropout_ok || !tr->drop.thresh,
+             "%s: dropout is set (rp_trainer_set_dropout p > 0); this entry point takes p = 0 only, %s_dropout honours it", what,
+             what);
   RP_REQUIRE(tr->enc->cfg.d_model <= 4 * 512, "%s: d_model=%d > 2048", what, tr->enc->cfg.d_model);
   return RP_OK;
 }
@@ -791,13 +793,12 @@ static RpStatus check_no_empty_sequence(const int32_t* cu_dev, int32_t batch, in
   return RP_OK;
 }
 
-extern "C" RpStatus rp_train_forward_hidden(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
-                                            int32_t T, void* out_hidden_bf16, void* workspace, size_t workspace_bytes,
-                                            void* stream_) {
+static RpStatus forward_hidden(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch, int32_t T,
+                               void* out_hidden_bf16, void* workspace, size_t workspace_bytes, void* stream_, bool dropout_ok) {
   RP_REQUIRE(tr && ids && cu_seqlens && out_hidden_bf16, "null argument");
   TrainWs w;
   RpStatus st;
-  if ((st = hidden_entry(tr, "rp_train_forward_hidden"))) return st;
+  if ((st = hidden_entry(tr, "rp_train_forward_hidden", dropout_ok))) return st;
   if ((st = train_entry(tr, batch, T, workspace, workspace_bytes, &w))) return st;
   hipStream_t stream = (hipStream_t)stream_;
   if ((st = check_no_empty_sequence(cu_seqlens, batch, T, stream))) return st;
@@ -805,18 +806,39 @@ extern "C" RpStatus rp_train_forward_hidden(RpTrainer* tr, const int32_t* ids, c
   return hidden_head(tr, T, (bf16_t*)out_hidden_bf16, w, stream);
 }
 
-extern "C" RpStatus rp_train_backward_hidden(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens,
-                                             int32_t batch, int32_t T, const float* d_hidden, float* grads, void* workspace,
-                                             size_t workspace_bytes, void* stream_) {
+extern "C" RpStatus rp_train_forward_hidden(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
+                                            int32_t T, void* out_hidden_bf16, void* workspace, size_t workspace_bytes,
+                                            void* stream_) {
+  return forward_hidden(tr, ids, cu_seqlens, batch, T, out_hidden_bf16, workspace, workspace_bytes, stream_, false);
+}
+extern "C" RpStatus rp_train_forward_hidden_dropout(RpTrainer* tr, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
+                                                    int32_t T, void* out_hidden_bf16, void* workspace, size_t workspace_bytes,
+                                                    void* stream_) {
+  return forward_hidden(tr, ids, cu_seqlens, batch, T, out_hidden_bf16, workspace, workspace_bytes, stream_, true);
+}
+
+static RpStatus backward_hidden(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens, int32_t batch,
+                                int32_t T, const float* d_hidden, float* grads, void* workspace, size_t workspace_bytes,
+                                void* stream_, bool dropout_ok) {
   RP_REQUIRE(tr && params && ids && cu_seqlens && d_hidden && grads, "null argument");
   TrainWs w;
   RpStatus st;
-  if ((st = hidden_entry(tr, "rp_train_backward_hidden"))) return st;
+  if ((st = hidden_entry(tr, "rp_train_backward_hidden", dropout_ok))) return st;
   if ((st = train_entry(tr, batch, T, workspace, workspace_bytes, &w))) return st;
   hipStream_t stream = (hipStream_t)stream_;
   if ((st = backward_zero(tr, batch, T, w, stream))) return st;
   if ((st = hidden_bwd_head(tr, T, d_hidden, grads, w, stream))) return st;
   return backward_layers(tr, params, ids, batch, T, grads, w, stream);
+}
+extern "C" RpStatus rp_train_backward_hidden(RpTrainer* tr, const float* params, const int32_t* ids, const int32_t* cu_seqlens,
+                                             int32_t batch, int32_t T, const float* d_hidden, float* grads, void* workspace,
+                                             size_t workspace_bytes, void* stream_) {
+  return backward_hidden(tr, params, ids, cu_seqlens, batch, T, d_hidden, grads, workspace, workspace_bytes, stream_, false);
+}
+extern "C" RpStatus rp_train_backward_hidden_dropout(RpTrainer* tr, const float* params, const int32_t* ids,
+                                                     const int32_t* cu_seqlens, int32_t batch, int32_t T, const float* d_hidden,
+                                                     float* grads, void* workspace, size_t workspace_bytes, void* stream_) {
+  return backward_hidden(tr, params, ids, cu_seqlens, batch, T, d_hidden, grads, workspace, workspace_bytes, stream_, true);
 }
 
 // ||g||_2 of n floats -> out_norm[0] (device), deterministic; scratch = 1024 floats

@@ -1187,11 +1187,14 @@ __global__ __launch_bounds__(256) void pool_bwd_tok_kernel(const bf16_t* __restr
 //             d w  = sum_t dh_t x_t rs_t : per-workgroup partial rows in fixed row order, summed by colsum_kernel
 // Both are HBM-bound row passes (x = hi + lo as everywhere in the trainer), 16-byte accesses, one wave per token row with
 // two rows' loads in flight, as embed_kernel / pool_bwd_tok_kernel.
+// DROP (rp_train_*_hidden_dropout): HF's dropout after the encoder's final norm (DROP_SITE_FINAL, row = token, column =
+// feature): out[t] = bf16(mask * w * (x_t * rs_t)), and the backward reads dh times the regenerated mask before anything else.
 // ------------------------------------------------------------------------------------------
 constexpr int HIDDEN_ROWS = 8;  // token rows per workgroup of the forward head: two per wave
+template <bool DROP>
 static __global__ __launch_bounds__(256) void hidden_head_kernel(const bf16_t* __restrict__ xhi, const bf16_t* __restrict__ xlo,
                                                           const float* __restrict__ rs, const float* __restrict__ w,
-                                                          bf16_t* __restrict__ out, int T, int D) {
+                                                          bf16_t* __restrict__ out, int T, int D, Drop drop) {
   const int lane = threadIdx.x & 63;
   const int r0 = blockIdx.x * HIDDEN_ROWS + 2 * (threadIdx.x >> 6);
   if (r0 >= T) return;
@@ -1217,8 +1220,16 @@ static __global__ __launch_bounds__(256) void hidden_head_kernel(const bf16_t* _
       const float x01 = __uint_as_float(hw0[e] & 0xffff0000u) + __uint_as_float(lw0[e] & 0xffff0000u);
       const float x10 = __uint_as_float(hw1[e] << 16) + __uint_as_float(lw1[e] << 16);
       const float x11 = __uint_as_float(hw1[e] & 0xffff0000u) + __uint_as_float(lw1[e] & 0xffff0000u);
-      a[e] = pack_bf2(wv[2 * e] * (x00 * s0), wv[2 * e + 1] * (x01 * s0));
-      b[e] = pack_bf2(wv[2 * e] * (x10 * s1), wv[2 * e + 1] * (x11 * s1));
+      if constexpr (DROP) {
+        float ma0, ma1, mb0, mb1;
+        drop_mul2(drop, DROP_SITE_FINAL, (uint32_t)r0, (uint32_t)(c * 8 + 2 * e), ma0, ma1);
+        drop_mul2(drop, DROP_SITE_FINAL, (uint32_t)r1, (uint32_t)(c * 8 + 2 * e), mb0, mb1);
+        a[e] = pack_bf2(ma0 * (wv[2 * e] * (x00 * s0)), ma1 * (wv[2 * e + 1] * (x01 * s0)));
+        b[e] = pack_bf2(mb0 * (wv[2 * e] * (x10 * s1)), mb1 * (wv[2 * e + 1] * (x11 * s1)));
+      } else {
+        a[e] = pack_bf2(wv[2 * e] * (x00 * s0), wv[2 * e + 1] * (x01 * s0));
+        b[e] = pack_bf2(wv[2 * e] * (x10 * s1), wv[2 * e + 1] * (x11 * s1));
+      }
     }
     o0[c] = make_uint4(a[0], a[1], a[2], a[3]);
     if (two) o1[c] = make_uint4(b[0], b[1], b[2], b[3]);
@@ -1231,12 +1242,12 @@ static __global__ __launch_bounds__(256) void hidden_head_kernel(const bf16_t* _
 // 32 rows: 575 workgroups at the reference's training batch (18.4 k tokens), two per CU by registers; the partial rows add
 // 1 / 48 to the pass's traffic.
 constexpr int HIDDEN_BWD_ROWS = 32;
-template <int NV>
+template <int NV, bool DROP>
 __global__ __launch_bounds__(256) void hidden_head_bwd_kernel(const bf16_t* __restrict__ xhi, const bf16_t* __restrict__ xlo,
                                                               const float* __restrict__ rs, const float* __restrict__ w,
                                                               const float* __restrict__ dh, bf16_t* __restrict__ dxhi,
                                                               bf16_t* __restrict__ dxlo, float* __restrict__ dw_part, int T,
-                                                              int D, float inv_d) {
+                                                              int D, float inv_d, Drop drop) {
   __shared__ float red[4][NV * 64 * 8];
   const int t0 = blockIdx.x * HIDDEN_BWD_ROWS, t1 = min(T, t0 + HIDDEN_BWD_ROWS);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1280,7 +1291,16 @@ __global__ __launch_bounds__(256) void hidden_head_bwd_kernel(const bf16_t* __re
       for (int i = 0; i < NV; ++i) {
         const bool live = lane + 64 * i < nv;
         const uint32_t hw[4] = {vh[q][i].x, vh[q][i].y, vh[q][i].z, vh[q][i].w}, lw[4] = {vl[q][i].x, vl[q][i].y, vl[q][i].z, vl[q][i].w};
-        const float g[8] = {ga[q][i].x, ga[q][i].y, ga[q][i].z, ga[q][i].w, gb[q][i].x, gb[q][i].y, gb[q][i].z, gb[q][i].w};
+        float g[8] = {ga[q][i].x, ga[q][i].y, ga[q][i].z, ga[q][i].w, gb[q][i].x, gb[q][i].y, gb[q][i].z, gb[q][i].w};
+        if constexpr (DROP) {
+#pragma unroll
+          for (int e = 0; e < 8; e += 2) {
+            float m0, m1;
+            drop_mul2(drop, DROP_SITE_FINAL, (uint32_t)t, (uint32_t)(min(lane + 64 * i, nv - 1) * 8 + e), m0, m1);
+            g[e] *= m0;
+            g[e + 1] *= m1;
+          }
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           xv[i][2 * e] = __uint_as_float(hw[e] << 16) + __uint_as_float(lw[e] << 16);

@@ -24,6 +24,12 @@ from .generation import (BeamSearchOutput, SampleState, beam_search, beam_search
                          greedy_search_batch, sample_search_batch)
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
+# Dropout sites of the training step (include/reprover_hip.h RP_DROP_SITE_*; ``rp_dbg_dropout_mask`` reads a site's mask).
+# Encoder: embeddings, final norm output, layer i at 16 + 8 i + {0 probs, 1 attention residual, 2 FFN inner, 3 FFN residual}.
+DROP_SITE_EMBED, DROP_SITE_FINAL, DROP_SITE_LAYER0 = 0, 1, 16
+# Decoder (rows = packed target token indices): embeddings, final norm output, layer i at 0x4000 + 8 i + the offsets below
+DROP_SITE_DEC_EMBED, DROP_SITE_DEC_FINAL, DROP_SITE_DEC_LAYER0 = 2, 3, 0x4000
+DEC_SELF_PROBS, DEC_SELF_RESID, DEC_CROSS_PROBS, DEC_CROSS_RESID, DEC_FF_INNER, DEC_FF_RESID = range(6)
 _STATE_0 = np.zeros(1, dtype=np.int32)  # the active list of a one-state step
 
 _DEC_KEYS = {
@@ -297,23 +303,24 @@ class HipT5Decoder:
                        "rp_decoder_load_params")
 
     def loss_grad(self, enc_bf16: torch.Tensor, src_cu: np.ndarray, tokens: np.ndarray, labels: np.ndarray,
-                  tgt_cu: np.ndarray, want_d_enc: bool = True, grads: Optional[torch.Tensor] = None):
+                  tgt_cu: np.ndarray, want_d_enc: bool = True, grads: Optional[torch.Tensor] = None,
+                  dropout: Optional[Tuple[float, int]] = None):
         """``rp_decoder_loss_grad`` over packed pairs (arguments as ``forward``).  Returns (label log-probs [sum T_b],
         (sum of -log p, count), the flat fp32 gradient buffer of ``grad_layout``, d loss / d enc [sum S_b, d_model] fp32
-        or None).  ``grads``: a buffer to write into (its padding gaps are left as they are)."""
-        ws, src_cu, tgt_cu, B, T, S, tok, lab, lp, sc = self._teacher_forced_args("rp_decoder_loss_grad", src_cu, tokens,
-                                                                                  labels, tgt_cu)
+        or None).  ``grads``: a buffer to write into (its padding gaps are left as they are).  ``dropout=(p, seed)``: T5's
+        training mode (``rp_decoder_loss_grad_dropout``), masks at the ``DROP_SITE_DEC_*`` sites drawn from ``seed``."""
+        entry = "rp_decoder_loss_grad" if dropout is None else "rp_decoder_loss_grad_dropout"
+        extra = () if dropout is None else (float(dropout[0]), int(dropout[1]) & 0xFFFFFFFF)
+        ws, src_cu, tgt_cu, B, T, S, tok, lab, lp, sc = self._teacher_forced_args(entry, src_cu, tokens, labels, tgt_cu)
         ptr = lambda t: t.data_ptr() if T else None  # noqa: E731
         if grads is None:
             grads = torch.zeros(int(self.grad_layout()[1][-1]), dtype=torch.float32, device=self.device)
         d_enc = torch.empty((S, self.cfg["d_model"]), dtype=torch.float32, device=self.device) if want_d_enc else None
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_decoder_loss_grad(self._handle, ptr(enc_bf16), _pc(src_cu), ptr(tok), ptr(lab),
-                                                      _pc(tgt_cu), B, ptr(lp), sc.data_ptr(), grads.data_ptr(),
-                                                      d_enc.data_ptr() if (want_d_enc and S) else None,
-                                                      ws.data_ptr(), ws.numel(),
-                                                      _lib.current_stream()),
-                       "rp_decoder_loss_grad")
+            _lib.check(getattr(self._lib, entry)(self._handle, ptr(enc_bf16), _pc(src_cu), ptr(tok), ptr(lab), _pc(tgt_cu), B,
+                                                 *extra, ptr(lp), sc.data_ptr(), grads.data_ptr(),
+                                                 d_enc.data_ptr() if (want_d_enc and S) else None, ws.data_ptr(), ws.numel(),
+                                                 _lib.current_stream()), entry)
         s, c = sc.cpu().tolist()
         return lp, (s, c), grads, d_enc
 
@@ -627,22 +634,35 @@ class HipT5Generator:
 
 class HipSeq2SeqGradients:
     """d loss / d every parameter of a T5ForConditionalGeneration for the reference's ``training_step`` loss
-    (``generation/model.py:117-121``), in one deterministic pass without dropout:
+    (``generation/model.py:117-121``), in one deterministic pass:
     ``HipT5Trainer.forward_hidden`` (the encoder with saved activations) -> ``HipT5Decoder.loss_grad`` (the loss, the
     decoder's gradients and d_enc) -> ``HipT5Trainer.backward_hidden`` (the encoder's gradients from d_enc).
+
+    ``dropout_rate > 0``: T5's training mode.  Call number n draws one seed from
+    (``dropout_seed``, n) - the trainer's stream - and that seed drives both halves; ``last_dropout_seed`` is the last
+    call's (None without dropout).  Inference through the same weights (``HipT5Generator``) never drops.
 
     Holds the encoder's fp32 masters (``self.trainer``) and the decoder (``self.decoder``).  No optimizer, no weight
     reload and no ``fit`` here: those layers go on top of this gradient."""
 
-    def __init__(self, cfg: Dict, sd: Dict[str, torch.Tensor], device):
+    def __init__(self, cfg: Dict, sd: Dict[str, torch.Tensor], device, dropout_rate: float = 0.0,
+                 dropout_seed: Optional[int] = None):
         from .train import HipT5Trainer
 
         self.cfg = dict(cfg)
         self.device = _require_gpu(device)
         enc_sd = {k: v for k, v in sd.items() if k.startswith("encoder.") or k == "shared.weight"}
-        self.trainer = HipT5Trainer(cfg, enc_sd, self.device, dropout_rate=0.0)
+        self.trainer = HipT5Trainer(cfg, enc_sd, self.device, dropout_rate=dropout_rate, dropout_seed=dropout_seed)
         self.decoder = HipT5Decoder(cfg, sd, self.device)
         self.last_d_enc: Optional[torch.Tensor] = None
+
+    @property
+    def dropout_rate(self) -> float:
+        return self.trainer.dropout_rate
+
+    @property
+    def last_dropout_seed(self) -> Optional[int]:
+        return self.trainer.last_dropout_seed
 
     # the decoder's flat gradient buffer: None = a fresh zeroed one per call; HipSeq2SeqTrainer keeps one for its optimizer
     dec_grads: Optional[torch.Tensor] = None
@@ -659,10 +679,12 @@ class HipSeq2SeqGradients:
         packed, src_cu, tokens, labels, tgt_cu = packed_pairs(self.cfg, state_ids, state_mask, tactic_ids)
         if len(src_cu) < 2 or int(np.diff(src_cu).min()) <= 0:
             raise ValueError("every pair needs a source of at least one token")
-        hidden = self.trainer.forward_hidden(packed, src_cu)
-        _, (s, c), flat, d_enc = self.decoder.loss_grad(hidden, src_cu, tokens, labels, tgt_cu, want_d_enc=True,
-                                                        grads=self.dec_grads)
-        self.trainer.backward_hidden(d_enc)
+        drop = self.trainer.dropout_rate > 0
+        hidden = self.trainer.forward_hidden(packed, src_cu, dropout=drop)
+        _, (s, c), flat, d_enc = self.decoder.loss_grad(
+            hidden, src_cu, tokens, labels, tgt_cu, want_d_enc=True, grads=self.dec_grads,
+            dropout=(self.trainer.dropout_rate, self.trainer.last_dropout_seed) if drop else None)
+        self.trainer.backward_hidden(d_enc, dropout=drop)
         self.last_d_enc = d_enc
         names, off = self.decoder.grad_layout()
         shapes = self.decoder.grad_shapes()

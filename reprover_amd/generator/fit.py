@@ -1,13 +1,14 @@
 """``python -m reprover_amd.generator.fit --config <generation yaml> [--ckpt_path DIR] [--max-steps N] [--val-every N]
-[--log-dir DIR] [--ckpt-every N] [--resume-from DIR]``: the reference's generator training (generation/main.py ``fit``
-through Lightning) on the HIP engine, one GPU.  It reads the reference's ``model:`` / ``data:`` keys and
+[--log-dir DIR] [--ckpt-every N] [--resume-from DIR] [--dropout-rate RATE|config]``: the reference's generator training
+(generation/main.py ``fit`` through Lightning) on the HIP engine, one GPU.  It reads the reference's ``model:`` / ``data:`` keys and
 ``trainer.max_steps``, and mirrors ``reprover_amd.retrieval.main.run_fit``: per batch ``training_step`` (loss, gradients,
 AdamW, re-packing), epochs until ``max_steps``, a checkpoint directory swapped in atomically (a HuggingFace checkpoint of
 the current weights + the training state + ``loop_state.json``), and a resume that skips the batches already trained on at
 the index level.
 
-The step runs WITHOUT T5's dropout (the reference trains with ``dropout_rate`` 0.1): the decoder path has none
-(DESIGN.md section 14).  ``reprover_amd.generator.main fit`` is deliberately left as it is and does not route here."""
+By default the step runs WITHOUT T5's dropout; the reference trains with the checkpoint's ``dropout_rate`` (0.1), which
+``--dropout-rate config`` selects.  ``reprover_amd.generator.main fit`` is deliberately left as it is
+and does not route here."""
 from __future__ import annotations
 
 import argparse
@@ -71,7 +72,10 @@ def run_fit(model: RetrievalAugmentedGenerator, dm: GeneratorDataModule, max_ste
     if model.train_engine is None:
         model.configure_optimizers(weight_decay=weight_decay)
     engine = model.train_engine
-    log("fit: the step runs without T5's dropout (the reference trains with dropout_rate 0.1)")
+    if engine.dropout_rate > 0:
+        log(f"fit: the step runs with T5's dropout, rate {engine.dropout_rate:g}")
+    else:
+        log("fit: the step runs without T5's dropout (the reference trains with dropout_rate 0.1)")
     step, losses, epoch, skip = 0, [], 0, 0
     if resume_from:
         if not os.path.isdir(resume_from) and os.path.isdir(resume_from.rstrip("/") + ".old"):
@@ -87,6 +91,8 @@ def run_fit(model: RetrievalAugmentedGenerator, dm: GeneratorDataModule, max_ste
             if int(st.get("seed", seed)) != int(seed):
                 log(f"fit: the checkpoint's data seed {st['seed']} overrides the configured {seed}")
             seed = int(st.get("seed", seed))
+    if engine.dropout_rate > 0:  # (after the resume: a loaded training state replaces the seed base and the forward count)
+        log(f"fit: dropout seed base {engine.trainer.dropout_seed}, {engine.trainer._forwards} forwards drawn so far")
     caller_rng = random.getstate()  # the data draws from the global `random`, as upstream; the caller gets its stream back
     try:
         while step < max_steps:
@@ -117,8 +123,34 @@ def run_fit(model: RetrievalAugmentedGenerator, dm: GeneratorDataModule, max_ste
             "weight_decay": engine.weight_decay}
 
 
+def dropout_rate_arg(text: str):
+    """``--dropout-rate``: a float in [0, 1), or ``config`` = the checkpoint's ``config.json`` ``dropout_rate``."""
+    if text == "config":
+        return text
+    try:
+        rate = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is neither a number nor 'config'")
+    if not 0.0 <= rate < 1.0:
+        raise argparse.ArgumentTypeError(f"dropout rate {rate} outside [0, 1)")
+    return rate
+
+
+def resolve_dropout_rate(value, checkpoint: str) -> float:
+    """The rate ``--dropout-rate`` asks for: a number as given, ``config`` from ``<checkpoint>/config.json`` (HF's default
+    of 0.1 when the key is absent)."""
+    if value != "config":
+        return float(value)
+    path = os.path.join(checkpoint, "config.json")
+    if not os.path.exists(path):
+        raise SystemExit(f"fit: --dropout-rate config reads {path}, which does not exist: pass --ckpt_path with a local "
+                         "HuggingFace checkpoint directory (a hub name is not resolved), or give the rate as a number")
+    with open(path) as fh:
+        return float(json.load(fh).get("dropout_rate", 0.1))
+
+
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description="Tactic generator: fit on MI355X (one GPU, no dropout).")
+    ap = argparse.ArgumentParser(description="Tactic generator: fit on MI355X (one GPU; dropout off unless --dropout-rate).")
     ap.add_argument("--config", required=True, help="YAML with `model:`, `data:` and `trainer:` sections (reference layout)")
     ap.add_argument("--ckpt_path", default=None, help="HF checkpoint dir (overrides model.model_name)")
     ap.add_argument("--max-steps", type=int, default=None, help="overrides trainer.max_steps")
@@ -126,6 +158,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--log-dir", default=None, help="the checkpoint is written to <log-dir>/checkpoint")
     ap.add_argument("--ckpt-every", type=int, default=0, help="also checkpoint every N steps (0: only at the end)")
     ap.add_argument("--resume-from", default=None, help="a checkpoint directory written by an earlier fit")
+    ap.add_argument("--dropout-rate", type=dropout_rate_arg, default=0.0, metavar="RATE",
+                    help="T5's dropout in the training step: a rate in [0, 1), or 'config' for the checkpoint's "
+                         "config.json dropout_rate (the reference's mode); default 0")
     return ap
 
 
@@ -137,6 +172,7 @@ def main(argv=None) -> None:
     if int(d.get("batch_size", 0)) <= 0:
         raise SystemExit("fit: the config's data.batch_size must be a positive integer")
     wd = weight_decay_for(tcfg)
+    seed = cfg.get("seed_everything")
     print(f"fit: weight decay {wd} ("
           + ("DeepSpeedStrategy: FusedAdam(adam_w_mode=True)'s default" if wd == 0.0 else "torch.optim.AdamW's default") + ")",
           flush=True)
@@ -144,12 +180,13 @@ def main(argv=None) -> None:
         args.ckpt_path or m["model_name"], float(m.get("lr", 0.0)), int(m.get("warmup_steps", 0)), int(m["num_beams"]),
         int(m.get("eval_num_retrieved", 100)), int(m.get("eval_num_workers", 1)), int(m.get("eval_num_gpus", 1)),
         int(m.get("eval_num_theorems", 0)), int(d["max_inp_seq_len"]), int(d["max_oup_seq_len"]),
-        float(m.get("length_penalty", 0.0)), m.get("ret_ckpt_path"))
+        float(m.get("length_penalty", 0.0)), m.get("ret_ckpt_path"),
+        dropout_rate=resolve_dropout_rate(args.dropout_rate, args.ckpt_path or m["model_name"]),
+        dropout_seed=int(seed) if seed is not None else None)
     model.configure_optimizers(weight_decay=wd, gradient_clip_val=tcfg.get("gradient_clip_val"))
     dm = GeneratorDataModule(d["data_path"], m["model_name"], int(d["batch_size"]), int(d["eval_batch_size"]),
                              int(d["max_inp_seq_len"]), int(d["max_oup_seq_len"]), float(d.get("p_drop", 0.0)),
                              int(d.get("num_workers", 0)), d.get("corpus_path"), d.get("preds_path"))
-    seed = cfg.get("seed_everything")
     log_dir = args.log_dir or tcfg.get("default_root_dir") or os.path.join(os.getcwd(), "lightning_logs")
     print(f"fit: checkpoints go to {os.path.join(log_dir, 'checkpoint')}", flush=True)
     out = run_fit(model, dm, args.max_steps or int(tcfg.get("max_steps", 1)), args.val_every,

@@ -46,10 +46,13 @@ class RetrievalAugmentedGenerator:
     def __init__(self, model_name: str, lr: float, warmup_steps: int, num_beams: int, eval_num_retrieved: int,
                  eval_num_workers: int, eval_num_gpus: int, eval_num_theorems: int, max_inp_seq_len: int,
                  max_oup_seq_len: int, length_penalty: float = 0.0, ret_ckpt_path: Optional[str] = None,
-                 device="cuda:0") -> None:
+                 device="cuda:0", dropout_rate: float = 0.0, dropout_seed: Optional[int] = None) -> None:
         from ..decoder import HipT5Generator
 
         self.lr, self.warmup_steps = lr, warmup_steps
+        # T5's dropout of the TRAINING step (the reference's checkpoints carry dropout_rate 0.1); generation and validation
+        # never drop
+        self.dropout_rate, self.dropout_seed = float(dropout_rate), dropout_seed
         self.num_beams = num_beams
         self.length_penalty = length_penalty
         self.eval_num_retrieved, self.eval_num_workers = eval_num_retrieved, eval_num_workers
@@ -77,7 +80,8 @@ class RetrievalAugmentedGenerator:
         cfg, sd = load_seq2seq_checkpoint(self.model_name)
         self.generator = None  # (released before the training buffers are taken)
         self.train_engine = HipSeq2SeqTrainer(cfg, sd, self.device, lr=self.lr, warmup_steps=self.warmup_steps,
-                                              weight_decay=weight_decay, gradient_clip_val=gradient_clip_val)
+                                              weight_decay=weight_decay, gradient_clip_val=gradient_clip_val,
+                                              dropout_rate=self.dropout_rate, dropout_seed=self.dropout_seed)
         self.generator = self.train_engine.generator()
         return self.train_engine
 

@@ -7,7 +7,9 @@ end: the encoder's masters, gradients and moments live in its ``HipT5Trainer`` (
 decoder's in four flat buffers of ``rp_decoder_grad_layout``'s form owned here.  ``shared.weight`` has one master, one
 gradient and one pair of moments: the trainer's ``embed`` slot.  The decoder's ``shared`` slot receives a copy of the updated
 master and carries no optimizer state.  After the update both halves re-pack their compute copies
-(``rp_trainer_load_params`` / ``rp_decoder_load_params``).  No dropout (``rp_train_forward_hidden`` refuses p > 0).
+(``rp_trainer_load_params`` / ``rp_decoder_load_params``).  ``dropout_rate > 0`` is T5's training mode (DESIGN.md section
+15): one seed per step drives both halves' masks; the seed base and the number of forwards taken travel with the training
+state, so a resumed run draws the masks the uninterrupted run would.
 """
 from __future__ import annotations
 
@@ -74,7 +76,7 @@ class HipSeq2SeqTrainer(HipSeq2SeqGradients):
 
     def __init__(self, cfg: Dict, sd: Dict[str, torch.Tensor], device, lr: float = 0.0, warmup_steps: int = 0,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 gradient_clip_val: Optional[float] = None):
+                 gradient_clip_val: Optional[float] = None, dropout_rate: float = 0.0, dropout_seed: Optional[int] = None):
         self.cfg = dict(cfg)
         self.device = _require_gpu(device)
         self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
@@ -86,7 +88,8 @@ class HipSeq2SeqTrainer(HipSeq2SeqGradients):
                              "from shared.weight: such a model cannot be trained with one embedding master")
         enc_sd = {k: v for k, v in sd.items() if k.startswith("encoder.") or k == "shared.weight"}
         self.trainer = HipT5Trainer(cfg, enc_sd, self.device, lr=lr, warmup_steps=warmup_steps, betas=betas, eps=eps,
-                                    weight_decay=weight_decay, gradient_clip_val=gradient_clip_val, dropout_rate=0.0)
+                                    weight_decay=weight_decay, gradient_clip_val=gradient_clip_val, dropout_rate=dropout_rate,
+                                    dropout_seed=dropout_seed)
         names, shapes, off = decoder_param_layout(cfg, self.tied)
         self.dec_names, self.dec_shapes, self.dec_off = names, shapes, off
         total, self._opt0 = int(off[-1]), int(off[1])  # the optimizer runs over [off[1], total): everything but shared
@@ -180,7 +183,8 @@ class HipSeq2SeqTrainer(HipSeq2SeqGradients):
 
     def save_training_state(self, path: str) -> None:
         """Everything a resumed run needs, in directory ``path``: ``encoder_state.safetensors`` (``HipT5Trainer``'s:
-        masters, moments, the step counter) and ``decoder_state.safetensors`` (the decoder's masters and moments)."""
+        masters, moments, the step counter, the dropout seed base and the number of forwards drawn from it) and
+        ``decoder_state.safetensors`` (the decoder's masters and moments)."""
         from safetensors.torch import save_file
 
         os.makedirs(path, exist_ok=True)

@@ -128,7 +128,7 @@ class HipT5Trainer:
     def __init__(self, cfg: Dict, state_dict: Dict[str, torch.Tensor], device, lr: float = 0.0, warmup_steps: int = 0,
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  gradient_clip_val: Optional[float] = None, out_dtype: torch.dtype = torch.bfloat16,
-                 dropout_rate: float = 0.0, dropout_seed: int = 3407):
+                 dropout_rate: float = 0.0, dropout_seed: Optional[int] = None):
         if cfg.get("feed_forward_proj", "gated-gelu") != "gated-gelu":
             raise _lib.HipLibraryError(f"feed_forward_proj={cfg.get('feed_forward_proj')!r} is not implemented")
         self.device = _require_gpu(device)
@@ -138,7 +138,8 @@ class HipT5Trainer:
         # T5's dropout (HF config.dropout_rate; 0.1 in the reference's training): 0 = the deterministic step the fixtures
         # pin.  Masks are counter-based: forward number n of this trainer draws them from seed (dropout_seed, n), the
         # backward regenerates them.
-        self.dropout_rate, self.dropout_seed = float(dropout_rate), int(dropout_seed)
+        self.dropout_rate = float(dropout_rate)
+        self.dropout_seed = 3407 if dropout_seed is None else int(dropout_seed)  # (None: the default base)
         self._forwards = 0
         self.last_dropout_seed: Optional[int] = None
         self._lib = _lib.load()
@@ -232,15 +233,21 @@ class HipT5Trainer:
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def _set_next_dropout(self) -> None:
+        """Hand the engine the masks of the next forward: seed number ``_forwards`` of the stream that starts at
+        ``dropout_seed`` (the one source of the stream a resumed run continues); ``last_dropout_seed`` names it, None
+        without dropout."""
+        seed = (self.dropout_seed * 0x9E3779B1 + self._forwards * 0x85EBCA77 + 1) & 0xFFFFFFFF
+        self._forwards += 1
+        self.last_dropout_seed = seed if self.dropout_rate > 0 else None
+        _lib.check(self._lib.rp_trainer_set_dropout(self._handle, self.dropout_rate, seed), "rp_trainer_set_dropout")
+
     def forward(self, ids: np.ndarray, cu: np.ndarray) -> torch.Tensor:
         """Unit-norm fp32 embeddings [batch, d_model] of the packed sequences; the activations stay in the workspace
         for ``backward``."""
         batch, T = len(cu) - 1, int(cu[-1])
         assert batch > 0 and T > 0 and len(ids) == T and int(np.diff(cu).min()) > 0
-        seed = (self.dropout_seed * 0x9E3779B1 + self._forwards * 0x85EBCA77 + 1) & 0xFFFFFFFF
-        self._forwards += 1
-        self.last_dropout_seed = seed if self.dropout_rate > 0 else None
-        _lib.check(self._lib.rp_trainer_set_dropout(self._handle, self.dropout_rate, seed), "rp_trainer_set_dropout")
+        self._set_next_dropout()
         with torch.cuda.device(self.device):
             ids_d = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(self.device)
             cu_d = torch.from_numpy(np.ascontiguousarray(cu, dtype=np.int32)).to(self.device)
@@ -263,41 +270,51 @@ class HipT5Trainer:
                                                    self._ws.numel(), _lib.current_stream()), "rp_train_backward")
         return self.grads
 
-    def forward_hidden(self, ids: np.ndarray, cu: np.ndarray) -> torch.Tensor:
+    def forward_hidden(self, ids: np.ndarray, cu: np.ndarray, dropout: bool = False) -> torch.Tensor:
         """last_hidden_state [total_tokens, d_model] bf16 of the packed sequences (``rp_train_forward_hidden``: the same
         layers as ``forward``, the final RMSNorm's rows instead of the pooled embedding); the activations stay in the
-        workspace for ``backward_hidden``.  Without dropout only."""
-        if self.dropout_rate > 0:
-            raise ValueError(f"forward_hidden runs without dropout (dropout_rate={self.dropout_rate}): the decoder behind "
-                             "it has none")
+        workspace for ``backward_hidden``.  Without dropout unless ``dropout=True``: then the pass drops at
+        ``dropout_rate`` with the next seed of ``forward``'s stream (``last_dropout_seed``), the final site included
+        (``rp_train_forward_hidden_dropout``), and the caller owes the same (rate, seed) to the decoder behind it
+        (``HipT5Decoder.loss_grad(dropout=...)``) and ``dropout=True`` to ``backward_hidden``."""
+        if self.dropout_rate > 0 and not dropout:
+            raise ValueError(f"forward_hidden runs without dropout (dropout_rate={self.dropout_rate}) unless dropout=True "
+                             "is passed and the decoder behind it drops with the same seed")
         batch, T = len(cu) - 1, int(cu[-1])
         if batch <= 0 or T <= 0 or len(ids) != T or int(np.diff(cu).min()) <= 0:
             raise ValueError("forward_hidden needs at least one token per sequence")
-        _lib.check(self._lib.rp_trainer_set_dropout(self._handle, 0.0, 0), "rp_trainer_set_dropout")
+        entry = "rp_train_forward_hidden"
+        if dropout:
+            entry += "_dropout"
+        if dropout and self.dropout_rate > 0:
+            self._set_next_dropout()
+        else:  # (rate 0 draws nothing from the stream: the saved forward count speaks of dropped forwards only)
+            self.last_dropout_seed = None
+            _lib.check(self._lib.rp_trainer_set_dropout(self._handle, 0.0, 0), "rp_trainer_set_dropout")
         with torch.cuda.device(self.device):
             ids_d = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(self.device)
             cu_d = torch.from_numpy(np.ascontiguousarray(cu, dtype=np.int32)).to(self.device)
             ws = self._workspace(self._lib.rp_train_workspace_bytes(self._handle, T, batch))
             out = torch.empty((T, self.cfg["d_model"]), dtype=torch.bfloat16, device=self.device)
-            _lib.check(self._lib.rp_train_forward_hidden(self._handle, _lib.ptr(ids_d), _lib.ptr(cu_d), batch, T,
-                                                         _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
-                       "rp_train_forward_hidden")
+            _lib.check(getattr(self._lib, entry)(self._handle, _lib.ptr(ids_d), _lib.ptr(cu_d), batch, T, _lib.ptr(out),
+                                                 _lib.ptr(ws), ws.numel(), _lib.current_stream()), entry)
         self._pass = (ids_d, cu_d, batch, T)
         return out
 
-    def backward_hidden(self, d_hidden: torch.Tensor) -> torch.Tensor:
+    def backward_hidden(self, d_hidden: torch.Tensor, dropout: bool = False) -> torch.Tensor:
         """d loss / d every parameter (the flat gradient buffer, overwritten) from d loss / d last_hidden_state
-        [total_tokens, d_model] fp32 (``rp_decoder_loss_grad``'s d_enc); follows ``forward_hidden``."""
-        if self.dropout_rate > 0:
-            raise ValueError(f"backward_hidden runs without dropout (dropout_rate={self.dropout_rate})")
+        [total_tokens, d_model] fp32 (``rp_decoder_loss_grad``'s d_enc); follows ``forward_hidden`` with the same
+        ``dropout`` flag (the masks of that forward are regenerated)."""
+        if self.dropout_rate > 0 and not dropout:
+            raise ValueError(f"backward_hidden runs without dropout (dropout_rate={self.dropout_rate}) unless dropout=True")
+        entry = "rp_train_backward_hidden_dropout" if dropout else "rp_train_backward_hidden"
         assert self._pass is not None, "backward_hidden() follows forward_hidden()"
         ids_d, cu_d, batch, T = self._pass
         assert d_hidden.shape == (T, self.cfg["d_model"]) and d_hidden.dtype == torch.float32 and d_hidden.is_contiguous()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_train_backward_hidden(self._handle, _lib.ptr(self.params), _lib.ptr(ids_d), _lib.ptr(cu_d),
-                                                          batch, T, _lib.ptr(d_hidden), _lib.ptr(self.grads),
-                                                          _lib.ptr(self._ws), self._ws.numel(), _lib.current_stream()),
-                       "rp_train_backward_hidden")
+            _lib.check(getattr(self._lib, entry)(self._handle, _lib.ptr(self.params), _lib.ptr(ids_d), _lib.ptr(cu_d), batch, T,
+                                                 _lib.ptr(d_hidden), _lib.ptr(self.grads), _lib.ptr(self._ws),
+                                                 self._ws.numel(), _lib.current_stream()), entry)
         return self.grads
 
     def current_lr(self) -> float:

@@ -27,6 +27,12 @@ RP_K_OPTIMIZER class of one step and rp_decoder_load_params alone, the latter tu
 moves.  No threshold: figures only.
 
     python tools/seq2seq_bench.py --step --iters 9 --out profiles/seq2seq_train_bench.json
+
+--step --dropout P prices T5's dropout instead: two HipSeq2SeqTrainer of the same weights, one at
+p = 0 and one at p = P, alternate in one process at the same batch; the result holds both medians, their ratio and, from
+one profiled step of each (rp_profile_read), the time per kernel class, which says where the masks' share goes.
+
+    python tools/seq2seq_bench.py --step --dropout 0.1 --iters 9 --out profiles/seq2seq_dropout_bench.json
 """
 from __future__ import annotations
 
@@ -166,6 +172,60 @@ def reload_bytes(cfg, tied):
     return total
 
 
+def _step_dropout_leg(a, dev):
+    from reprover_amd.seq2seq_train import HipSeq2SeqTrainer
+
+    B, S, T = 8, 2300, 512
+    cfg = synth.seq2seq_config("byt5-small")
+    sd = synth.synth_seq2seq_state_dict(cfg, scale="hf")
+    make = lambda p: HipSeq2SeqTrainer(cfg, sd, dev, lr=5e-4, warmup_steps=2000, dropout_rate=p, dropout_seed=7)  # noqa: E731
+    trainers = {"p0": make(0.0), "dropout": make(a.dropout)}
+    rng = np.random.default_rng(0)
+    ids = np.stack([_source(S, 100 + b) for b in range(B)]).astype(np.int64)
+    mask = np.ones_like(ids)
+    y = np.concatenate([rng.integers(3, 259, size=(B, T - 1)), np.ones((B, 1), np.int64)], 1)
+
+    def step(tr):
+        tr.loss_and_grads(ids, mask, y)
+        tr.optimizer_step()
+
+    for _ in range(2):
+        for tr in trainers.values():
+            step(tr)
+    torch.cuda.synchronize()
+    ts = {k: [] for k in trainers}
+    for _ in range(a.iters):  # alternating: both see the same clocks and the same neighbours
+        for k, tr in trainers.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            step(tr)
+            torch.cuda.synchronize()
+            ts[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    prof = {}
+    for k, tr in trainers.items():  # one profiled step each (events around every launch group: slower host, classes apart)
+        _lib.profile_enable(True)
+        step(tr)
+        torch.cuda.synchronize()
+        prof[k] = {c: round(v[0], 3) for c, v in _lib.profile_read(heads=True).items() if v[1]}
+        _lib.profile_enable(False)
+    result = dict(metric="seq2seq_dropout_bench", measured=True, model="byt5-small (synthetic, hf)", batch=B, source_bytes=S,
+                  target_labels=T, iters=a.iters, dropout_rate=a.dropout, step_ms_p0=round(med["p0"], 3),
+                  step_ms_dropout=round(med["dropout"], 3), dropout_over_p0=round(med["dropout"] / med["p0"], 4),
+                  step_ms_p0_all=[round(x, 3) for x in ts["p0"]], step_ms_dropout_all=[round(x, 3) for x in ts["dropout"]],
+                  profiled_step_ms_by_class_p0=prof["p0"], profiled_step_ms_by_class_dropout=prof["dropout"],
+                  profiled_class_difference_ms={c: round(prof["dropout"].get(c, 0.0) - prof["p0"].get(c, 0.0), 3)
+                                                for c in sorted(set(prof["p0"]) | set(prof["dropout"]))},
+                  note="step = HipSeq2SeqTrainer.loss_and_grads + optimizer_step, median of iters alternating calls, host clock "
+                       "around synchronised calls; the class split is one profiled step of each trainer (decoder row kernels "
+                       "and attention launches carry no class of their own); one box, one run")
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
 def _step_leg(a, dev):
     from reprover_amd.seq2seq_train import HipSeq2SeqTrainer
 
@@ -268,10 +328,12 @@ def main():
     ap.add_argument("--grad", action="store_true", help="time rp_decoder_loss_grad against rp_decoder_forward")
     ap.add_argument("--full-grad", action="store_true", help="time HipSeq2SeqGradients against the decoder-only gradients")
     ap.add_argument("--step", action="store_true", help="time the whole training step against the --full-grad call")
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="P",
+                    help="with --step: time the step at p = 0 against the step at p = P (T5's dropout) instead")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.step:
-        return _step_leg(a, dev)
+        return _step_dropout_leg(a, dev) if a.dropout > 0 else _step_leg(a, dev)
     if a.full_grad:
         return _full_grad_leg(a, dev)
     cfg = synth.seq2seq_config("byt5-small")
