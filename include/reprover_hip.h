@@ -652,6 +652,45 @@ RpStatus rp_beam_select_batch(const float* logprobs, const float* running, int32
                               int32_t vocab, int32_t k, float* scores, int32_t* tokens, int32_t* parents,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* Beam books ("Per-step host sync, and device books"): beam search's bookkeeping -
+ * what generation.py's _BeamState keeps on the host - in one caller-owned device block for n states, and one launch per
+ * position that updates it from rp_beam_select_batch's outputs, so the host loop reads nothing back per
+ * step.  The block, every part starting at a multiple of 16 bytes, in this order (tables are int32 with
+ * max_len columns per row; a pair [2] is read at member t & 1 and written at the other by the step at t):
+ *   run_seq [2][n][nb][max_len]  running sequences          anc [2][n][nb][max_len]  their ancestry rows
+ *   fin_seq [2][n][nb][max_len]  finished hypotheses        run_scores, beam_scores fp32 [n][nb]
+ *   fin_flag, fin_len int32 [n][nb]  is_sent_finished; generated tokens of the hypothesis
+ *   heur, done, steps int32 [n]      heuristic_unsatisfied; stopped; advances taken (steps & 1 = the
+ *                                    current member of the state's pairs)
+ *   tokens int32 [n * nb], running fp32 [n * nb], anc_rows int32 [n * nb][max_len]: BY ROW (slot * nb + b),
+ *     the next rp_decoder_batch_step's tokens / ancestry (anc_stride = max_len) and the next
+ *     rp_beam_select_batch's running scores for the active list of the advance that wrote them
+ * rp_beam_books_bytes returns 0 on bad arguments (rp_last_error says why).
+ * rp_beam_books_init: _BeamState.__init__ for all n states (sequences eos with the start token in column
+ * 0, run_scores {0, -1e9, ..}, beam_scores -1e9, nothing finished, heur 1, done 0, identity ancestry
+ * c * nb + b, by-row inputs for the active list 0 .. n - 1).
+ * rp_beam_advance: _BeamState.advance for the states of `active` (HOST int32 [n_active], as
+ * rp_decoder_batch_step takes it) at position t, one workgroup per slot, in fp32 with one rounding per
+ * operation.  scores / tokens / parents are [n_active, 2 nb].  With idx the candidate's index:
+ *   1. hits = token == eos || t + 2 >= max_len;  run_lp = score + (hits ? -1e9 : -0.0)
+ *   2. the next running beams are the top nb of run_lp, descending, ties (-0.0 == +0.0) to the lower idx;
+ *      beam r takes run_seq / anc row parents[c] with token / (t + 1) * nb + r in column t + 1
+ *   3. fin = score / fin_div + (heur ? 0 : -1e9) + (hits && idx < nb ? -0.0 : -1e9); the new hypotheses are
+ *      the top nb of [the nb kept beam_scores, fin] in the same order
+ *   4. heur &= any(run_scores[0] / run_div > (fin_flag ? min(beam_scores) : -1e9));  done = !heur || all(hits)
+ *   5. the by-row inputs of the next step for the slot
+ *   6. a state whose done is set is left exactly as it is, whatever triples arrive
+ * fin_div, run_div: (t + 1) ** length_penalty, rounded to fp32 by the caller.
+ * RP_E_INVALID (nothing is launched): null pointers, nb outside 1..64, n outside 1..32, more than 1024
+ * rows, max_len outside 2..8192, active not distinct or outside [0, n), t + 1 >= max_len, bytes below
+ * rp_beam_books_bytes. */
+size_t   rp_beam_books_bytes(int32_t n, int32_t nb, int32_t max_len);
+RpStatus rp_beam_books_init(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len, int32_t eos,
+                            int32_t start_token, void* stream);
+RpStatus rp_beam_advance(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len, const int32_t* active,
+                         int32_t n_active, int32_t t, const float* scores, const int32_t* tokens,
+                         const int32_t* parents, float fin_div, float run_div, int32_t eos, void* stream);
+
 /* Sampled generation ("Sampling"): after rp_decoder_batch_step, one launch draws one
  * token per row (row = slot * nb + sample, the step's layout) from logprobs [n_active * nb, vocab] and
  * keeps the rows' books, so the host loop needs no readback.  HF's TemperatureLogitsWarper ->

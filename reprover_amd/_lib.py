@@ -323,6 +323,14 @@ SIGNATURES = {
          C.c_void_p],
     ),
     "rp_sample_uniform": (C.c_float, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rp_beam_books_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rp_beam_books_init": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_void_p]),
+    "rp_beam_advance": (
+        C.c_int32,
+        [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p],
+    ),
     "rp_set_option": (C.c_int32, [C.c_char_p, C.c_int32]),
     "rp_profile_enable": (C.c_int32, [C.c_int32]),
     "rp_profile_read": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

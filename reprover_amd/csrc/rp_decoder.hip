@@ -10,6 +10,8 @@
 // attentions run as one launch over (head, row), each row finding its state's cache, cross K/V and source length through
 // the slot table passed by value.  rp_decoder_step / rp_decoder_cross_kv / rp_beam_select are the one-state calls of
 // rp_decoder_batch_step / rp_decoder_batch_cross_kv / rp_beam_select_batch: there is one launch sequence.
+// rp_sample_step (sampling) and rp_beam_books_init / rp_beam_advance (beam search) keep a search's bookkeeping on the
+// device, one more launch per step, so that the host loop reads nothing back per position.
 //
 // Every output element of every kernel here is computed by a reduction whose order depends only on the shapes (K, the
 // key count), never on which other rows share the launch or where the row sits in it: a row's log-probs are the same
@@ -426,6 +428,202 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restric
     cum[idx] += r[tok];  // the model's log-prob: untempered, unfiltered
     ngen[idx] += 1;
     if (tok == eos) finished[idx] = 1;
+  }
+}
+
+// ---- beam books: beam search's bookkeeping on the device ------------------------------------------------------------------
+// What generation.py's _BeamState keeps on the host, for n states, in one caller-owned block (include/reprover_hip.h,
+// rp_beam_books_bytes).  Every part starts at a multiple of 16 bytes; the row tables have max_len int32 per row.  The
+// three row tables are pairs: the step at position t reads pair member t & 1 and writes the other, so no row is gathered
+// in place.  Columns a step has not reached hold their initial value in both members (eos / the identity entry).
+struct BeamBooks {
+  size_t bytes;
+  int32_t *run_seq, *anc, *fin_seq;  // [2][n][nb][max_len]: running sequences, their ancestry rows, finished hypotheses
+  float *run_scores, *beam_scores;   // [n][nb]
+  int32_t *fin_flag, *fin_len;       // [n][nb]: is_sent_finished, generated tokens (beam_indices' non-negative count)
+  int32_t *heur, *done, *steps;      // [n]: heuristic_unsatisfied, stopped, advances taken
+  int32_t* tokens;                   // [n * nb] by row (slot * nb + b): the next step's tokens
+  float* running;                    // [n * nb] by row: rp_beam_select_batch's running scores
+  int32_t* anc_rows;                 // [n * nb][max_len] by row: the next step's ancestry table
+};
+
+BeamBooks books_carve(char* base, int n, int nb, int max_len) {
+  BeamBooks b = {};
+  size_t off = 0;
+  auto take = [&](size_t words) {
+    char* p = base ? base + off : nullptr;
+    off += (words * 4 + 15) & ~(size_t)15;
+    return p;
+  };
+  const size_t rows = (size_t)n * nb, table = rows * max_len;
+  b.run_seq = (int32_t*)take(2 * table);
+  b.anc = (int32_t*)take(2 * table);
+  b.fin_seq = (int32_t*)take(2 * table);
+  b.run_scores = (float*)take(rows);
+  b.beam_scores = (float*)take(rows);
+  b.fin_flag = (int32_t*)take(rows);
+  b.fin_len = (int32_t*)take(rows);
+  b.heur = (int32_t*)take(n);
+  b.done = (int32_t*)take(n);
+  b.steps = (int32_t*)take(n);
+  b.tokens = (int32_t*)take(rows);
+  b.running = (float*)take(rows);
+  b.anc_rows = (int32_t*)take(table);
+  b.bytes = off;
+  return b;
+}
+
+constexpr float BEAM_NEG = -1.0e9f;  // generation.py's NEG (exact in fp32)
+
+// _BeamState.__init__ for state blockIdx.x, slot = state (the first step's active list is 0 .. n - 1)
+__global__ __launch_bounds__(256) void beam_books_init_kernel(BeamBooks bk, int n, int nb, int ld, int eos, int start) {
+  const int state = blockIdx.x, tid = threadIdx.x;
+  for (int i = tid; i < nb * ld; i += 256) {
+    const int r = i / ld, c = i - r * ld;
+    const int tok = c == 0 ? start : eos, id = c * nb + r;
+    for (int buf = 0; buf < 2; ++buf) {
+      const size_t at = ((size_t)(buf * n + state) * nb) * ld + i;
+      bk.run_seq[at] = tok;
+      bk.fin_seq[at] = tok;
+      bk.anc[at] = id;
+    }
+    bk.anc_rows[(size_t)state * nb * ld + i] = id;
+  }
+  for (int r = tid; r < nb; r += 256) {
+    const size_t at = (size_t)state * nb + r;
+    bk.run_scores[at] = bk.running[at] = r == 0 ? 0.f : BEAM_NEG;
+    bk.beam_scores[at] = BEAM_NEG;
+    bk.fin_flag[at] = 0;
+    bk.fin_len[at] = 0;
+    bk.tokens[at] = start;
+  }
+  if (tid == 0) {
+    bk.heur[state] = 1;
+    bk.done[state] = 0;
+    bk.steps[state] = 0;
+  }
+}
+
+// W int32 moved as one access (W = 4: 16 bytes, rows of a multiple of 4 columns)
+template <int W>
+struct alignas(4 * W) BookPack {
+  int32_t x[W];
+};
+template <int W>
+__device__ __forceinline__ BookPack<W> book_patch(BookPack<W> p, int v, int col, int value) {
+#pragma unroll
+  for (int e = 0; e < W; ++e)
+    if (v * W + e == col) p.x[e] = value;
+  return p;
+}
+
+// The three row gathers of one advance, in units of W columns: columns 0 .. t come from the source rows, column t + 1 is
+// the step's own (the candidate's token; the cache row (t + 1) * nb + r).  With W = 4 the last unit may carry up to three
+// columns past t + 1: they hold their initial values in source and destination alike.
+template <int W>
+__device__ __forceinline__ void beam_gather(const BeamBooks& bk, size_t src, size_t dst, size_t row0, int nb, int ld, int t,
+                                            const int* s_tok, const int* s_par, const int* s_nxt, const int* s_sel) {
+  typedef BookPack<W> P;
+  const int nv = (t + 2 + W - 1) / W, ldv = ld / W;
+  const P* run_s = reinterpret_cast<const P*>(bk.run_seq + src);
+  const P* anc_s = reinterpret_cast<const P*>(bk.anc + src);
+  const P* fin_s = reinterpret_cast<const P*>(bk.fin_seq + src);
+  P* run_d = reinterpret_cast<P*>(bk.run_seq + dst);
+  P* anc_d = reinterpret_cast<P*>(bk.anc + dst);
+  P* fin_d = reinterpret_cast<P*>(bk.fin_seq + dst);
+  P* rows_d = reinterpret_cast<P*>(bk.anc_rows + row0);
+  for (int i = threadIdx.x; i < nb * nv; i += 256) {
+    const int r = i / nv, v = i - r * nv;
+    const int c = s_nxt[r], p = s_par[c];
+    run_d[(size_t)r * ldv + v] = book_patch<W>(run_s[(size_t)p * ldv + v], v, t + 1, s_tok[c]);
+    const P a = book_patch<W>(anc_s[(size_t)p * ldv + v], v, t + 1, (t + 1) * nb + r);
+    anc_d[(size_t)r * ldv + v] = a;
+    rows_d[(size_t)r * ldv + v] = a;
+    const int m = s_sel[r];  // < nb: a kept hypothesis; else candidate m - nb
+    fin_d[(size_t)r * ldv + v] = m < nb ? fin_s[(size_t)m * ldv + v]
+                                        : book_patch<W>(run_s[(size_t)s_par[m - nb] * ldv + v], v, t + 1, s_tok[m - nb]);
+  }
+}
+
+// _BeamState.advance for the state in slot blockIdx.x, from the step's 2 nb selected triples (generation.py:92-130; the
+// numbered comments are include/reprover_hip.h's).  fp32, one rounding per operation, the reference's order.  Both
+// selections rank by counting in rp_beam_select's total order: descending, equal scores (-0.0 == +0.0) to the lower index.
+__global__ __launch_bounds__(256) void beam_advance_kernel(BeamBooks bk, int n, int nb, int ld, DecSlots slots, int t,
+                                                           const float* __restrict__ scores,
+                                                           const int32_t* __restrict__ tokens,
+                                                           const int32_t* __restrict__ parents, float fin_div,
+                                                           float run_div, int eos) {
+  __shared__ float s_run[2 * DEC_MAX_BEAMS], s_m[3 * DEC_MAX_BEAMS], s_score[DEC_MAX_BEAMS];
+  __shared__ int s_tok[2 * DEC_MAX_BEAMS], s_par[2 * DEC_MAX_BEAMS], s_hit[2 * DEC_MAX_BEAMS];
+  __shared__ int s_nxt[DEC_MAX_BEAMS], s_sel[DEC_MAX_BEAMS], s_kflag[DEC_MAX_BEAMS], s_klen[DEC_MAX_BEAMS];
+  __shared__ int s_flag[DEC_MAX_BEAMS], s_frozen;
+  const int tid = threadIdx.x, slot = blockIdx.x, state = slots.state[slot], K = 2 * nb;
+  const size_t srow = (size_t)state * nb;
+  if (tid == 0) s_frozen = bk.done[state];
+  __syncthreads();
+  if (s_frozen) return;  // 6. a stopped state takes nothing more (one value for the whole workgroup)
+  if (tid < K) {
+    const float val = scores[(size_t)slot * K + tid];
+    const int tok = tokens[(size_t)slot * K + tid];
+    const int hit = tok == eos || t + 2 >= ld;                             // 1.
+    s_tok[tid] = tok;
+    s_par[tid] = min(max(parents[(size_t)slot * K + tid], 0), nb - 1);     // (in range by contract)
+    s_hit[tid] = hit;
+    s_run[tid] = __fadd_rn(val, hit ? BEAM_NEG : -0.0f);
+    float fin = __fdiv_rn(val, fin_div);                                   // 3.
+    fin = __fadd_rn(fin, bk.heur[state] ? 0.0f : BEAM_NEG);
+    fin = __fadd_rn(fin, (hit && tid < nb) ? -0.0f : BEAM_NEG);
+    s_m[nb + tid] = fin;
+  }
+  if (tid < nb) {
+    s_m[tid] = bk.beam_scores[srow + tid];
+    s_kflag[tid] = bk.fin_flag[srow + tid];
+    s_klen[tid] = bk.fin_len[srow + tid];
+  }
+  __syncthreads();
+  if (tid < K) {  // 2. the next running beams: the candidates of rank < nb
+    const float x = s_run[tid];
+    int rank = 0;
+    for (int j = 0; j < K; ++j) rank += (s_run[j] > x || (s_run[j] == x && j < tid)) ? 1 : 0;
+    if (rank < nb) s_nxt[rank] = tid;
+  }
+  if (tid < 3 * nb) {  // 3. the kept hypotheses first, then the candidates: rank < nb stays
+    const float x = s_m[tid];
+    int rank = 0;
+    for (int j = 0; j < 3 * nb; ++j) rank += (s_m[j] > x || (s_m[j] == x && j < tid)) ? 1 : 0;
+    if (rank < nb) s_sel[rank] = tid;
+  }
+  __syncthreads();
+  const int cur = t & 1;
+  const size_t src = ((size_t)(cur * n + state) * nb) * ld, dst = ((size_t)((cur ^ 1) * n + state) * nb) * ld;
+  if (ld % 4 == 0)
+    beam_gather<4>(bk, src, dst, (size_t)slot * nb * ld, nb, ld, t, s_tok, s_par, s_nxt, s_sel);
+  else
+    beam_gather<1>(bk, src, dst, (size_t)slot * nb * ld, nb, ld, t, s_tok, s_par, s_nxt, s_sel);
+  if (tid < nb) {
+    const int c = s_nxt[tid], m = s_sel[tid];
+    bk.run_scores[srow + tid] = s_run[c];
+    bk.tokens[(size_t)slot * nb + tid] = s_tok[c];  // 5. the next step's inputs, by row
+    bk.running[(size_t)slot * nb + tid] = s_run[c];
+    const int flag = m < nb ? s_kflag[m] : (s_hit[m - nb] && m - nb < nb);
+    s_score[tid] = s_m[m];
+    s_flag[tid] = flag;
+    bk.beam_scores[srow + tid] = s_m[m];
+    bk.fin_flag[srow + tid] = flag;
+    bk.fin_len[srow + tid] = m < nb ? s_klen[m] : t + 1;
+  }
+  __syncthreads();
+  if (tid == 0) {  // 4.
+    const float best = __fdiv_rn(s_run[s_nxt[0]], run_div);
+    float worst = s_score[0];
+    for (int r = 1; r < nb; ++r) worst = fminf(worst, s_score[r]);
+    int any = 0, all = 1;
+    for (int r = 0; r < nb; ++r) any |= best > (s_flag[r] ? worst : BEAM_NEG);
+    for (int j = 0; j < K; ++j) all &= s_hit[j];
+    const int heur = bk.heur[state] && any;
+    bk.heur[state] = heur;
+    bk.done[state] = !heur || all;
+    bk.steps[state] = t + 1;
   }
 }
 
@@ -869,6 +1067,61 @@ extern "C" RpStatus rp_sample_step(const float* lp, int32_t V, const int32_t* ac
   hipLaunchKernelGGL(sample_step_kernel, dim3(n_active * nb), dim3(256), 0, (hipStream_t)stream_, lp, V, nb, slots, seeds,
                      t, max_len, temperature, top_k, drop_mass, eos, pad, seq, tokens_next, cum_logprob, n_generated,
                      finished);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+namespace {
+RpStatus books_check(int n, int nb, int max_len) {
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "nb=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(n >= 1 && n <= DEC_MAX_STATES, "states=%d (1..%d)", n, DEC_MAX_STATES);
+  RP_REQUIRE(n * nb <= DEC_MAX_ROWS, "rows = states * nb = %d > %d", n * nb, DEC_MAX_ROWS);
+  RP_REQUIRE(max_len >= 2 && max_len <= DEC_MAX_KEYS, "max_len=%d (2..%d)", max_len, DEC_MAX_KEYS);
+  return RP_OK;
+}
+}  // namespace
+
+extern "C" size_t rp_beam_books_bytes(int32_t n, int32_t nb, int32_t max_len) {
+  if (books_check(n, nb, max_len) != RP_OK) return 0;
+  return books_carve(nullptr, n, nb, max_len).bytes;
+}
+
+extern "C" RpStatus rp_beam_books_init(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len, int32_t eos,
+                                       int32_t start_token, void* stream_) {
+  RpStatus st = books_check(n, nb, max_len);
+  if (st) return st;
+  RP_REQUIRE(books, "null books");
+  const BeamBooks bk = books_carve((char*)books, n, nb, max_len);
+  RP_REQUIRE(bytes >= bk.bytes, "books %zu < required %zu bytes", bytes, bk.bytes);
+  hipStream_t s = (hipStream_t)stream_;
+  RP_HIP(hipMemsetAsync(books, 0, bk.bytes, s));  // the padding between the parts
+  hipLaunchKernelGGL(beam_books_init_kernel, dim3(n), dim3(256), 0, s, bk, n, nb, max_len, eos, start_token);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_beam_advance(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len,
+                                    const int32_t* active, int32_t n_active, int32_t t, const float* scores,
+                                    const int32_t* tokens, const int32_t* parents, float fin_div, float run_div,
+                                    int32_t eos, void* stream_) {
+  RpStatus st = books_check(n, nb, max_len);
+  if (st) return st;
+  RP_REQUIRE(books && active && scores && tokens && parents, "null argument");
+  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
+  RP_REQUIRE(t >= 0 && t + 1 < max_len, "t=%d: position t + 1 outside [1, max_len=%d)", t, max_len);
+  DecSlots slots = {};
+  uint32_t seen = 0;
+  for (int a = 0; a < n_active; ++a) {
+    const int sidx = active[a];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share books
+    seen |= 1u << sidx;
+    slots.state[a] = sidx;
+  }
+  const BeamBooks bk = books_carve((char*)books, n, nb, max_len);
+  RP_REQUIRE(bytes >= bk.bytes, "books %zu < required %zu bytes", bytes, bk.bytes);
+  hipLaunchKernelGGL(beam_advance_kernel, dim3(n_active), dim3(256), 0, (hipStream_t)stream_, bk, n, nb, max_len, slots, t,
+                     scores, tokens, parents, fin_div, run_div, eos);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }

@@ -4,8 +4,9 @@ The encoder is ``HipT5Encoder`` (``rp_encode_hidden``: last_hidden_state instead
 ``rp_decoder_*`` (one launch sequence per beam-search step for 1..32 states); the beam bookkeeping
 is ``reprover_amd.generation.beam_search_batch`` with the device top-2nb selection ``rp_beam_select_batch``.
 ``generate_many`` / ``greedy_many`` run the beams of several sources through that loop and return, per source, the bits
-of ``generate`` / ``greedy``, which are its one-state calls.  The teacher-forced loss (``forward`` /
-``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.
+of ``generate`` / ``greedy``, which are its one-state calls.  With ``sync_every=K`` the beam search keeps its books on the
+device instead (``rp_beam_books_init`` / ``rp_beam_advance``, ``generation.beam_search_batch_device``).  The
+teacher-forced loss (``forward`` / ``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.
 PyTorch tensors are containers only.
 """
 from __future__ import annotations
@@ -20,8 +21,8 @@ import torch
 
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
-from .generation import (BeamSearchOutput, SampleState, beam_search, beam_search_batch, check_sampling, greedy_search,
-                         greedy_search_batch, sample_search_batch)
+from .generation import (BeamBooks, BeamSearchOutput, SampleState, beam_search, beam_search_batch,
+                         beam_search_batch_device, check_sampling, greedy_search, greedy_search_batch, sample_search_batch)
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
 # Dropout sites of the training step (include/reprover_hip.h RP_DROP_SITE_*; ``rp_dbg_dropout_mask`` reads a site's mask).
@@ -408,6 +409,37 @@ class HipT5Decoder:
                                                 state.finished.data_ptr(), _lib.current_stream()),
                        "rp_sample_step")
 
+    def beam_books(self, n: int, nb: int, max_len: int, eos_token_id: int = 1,
+                   decoder_start_token_id: int = 0) -> BeamBooks:
+        """Device books of a beam search over ``n`` states, initialised (``rp_beam_books_init``;
+        ``beam_search_batch_device``'s ``init``)."""
+        need = int(self._lib.rp_beam_books_bytes(n, nb, max_len))
+        if need == 0:
+            raise _lib.HipLibraryError("beam_books: " + self._lib.rp_last_error().decode(errors="replace"))
+        books = BeamBooks(n, nb, max_len, block=torch.empty(need // 4, dtype=torch.int32, device=self.device))
+        assert books.nbytes == need, (books.nbytes, need)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_beam_books_init(books.block.data_ptr(), need, n, nb, max_len, eos_token_id,
+                                                    decoder_start_token_id, _lib.current_stream()), "rp_beam_books_init")
+        return books
+
+    def beam_advance(self, books: BeamBooks, active, t: int, scores: torch.Tensor, tokens: torch.Tensor,
+                     parents: torch.Tensor, fin_div: float, run_div: float, eos_token_id: int = 1) -> None:
+        """The books' update from one step's selected triples ``[n_active, 2 nb]``, on the device (``rp_beam_advance``;
+        ``beam_search_batch_device``'s ``advance``).  Nothing is read back."""
+        act = np.ascontiguousarray(active, dtype=np.int32)
+        want = (len(act), 2 * books.nb)
+        for x, dt in ((scores, torch.float32), (tokens, torch.int32), (parents, torch.int32)):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == dt, "rp_beam_advance takes contiguous device tensors"
+            if tuple(x.shape) != want:
+                raise _lib.HipLibraryError(f"beam_advance: triples of shape {tuple(x.shape)} for {want}")
+        assert books.block.is_cuda
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_beam_advance(books.block.data_ptr(), books.nbytes, books.n, books.nb, books.max_len,
+                                                 act.ctypes.data_as(C.c_void_p), len(act), t, scores.data_ptr(),
+                                                 tokens.data_ptr(), parents.data_ptr(), fin_div, run_div, eos_token_id,
+                                                 _lib.current_stream()), "rp_beam_advance")
+
     def select_many(self, log_probs: torch.Tensor, running: torch.Tensor, nb: int, k: int):
         """Per state the device top-k of its own ``[nb * V]`` block (``rp_beam_select_batch``): scores, tokens, parents,
         each ``[n_active, k]``, parents local to the state."""
@@ -556,9 +588,14 @@ class HipT5Generator:
                              decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device)
 
     def generate(self, ids: np.ndarray, num_beams: int, max_length: int, length_penalty: float = 1.0,
-                 trace: Optional[list] = None) -> BeamSearchOutput:
+                 trace: Optional[list] = None, sync_every: Optional[int] = None) -> BeamSearchOutput:
         """``generate(input_ids, num_beams=n, num_return_sequences=n, length_penalty, max_length, early_stopping=False,
-        do_sample=False)`` for one source.  Reads the selected candidates back once per step (generation.py)."""
+        do_sample=False)`` for one source.  Reads the selected candidates back once per step (generation.py);
+        ``sync_every``: as in ``generate_many``, whose one-state call it then is."""
+        if sync_every is not None:
+            if trace is not None:
+                raise ValueError("trace= needs the host books: it cannot be combined with sync_every")
+            return self.generate_many([ids], num_beams, max_length, length_penalty, sync_every=sync_every)[0]
         enc = self.encode_hidden(ids)
         self.decoder.start(enc, num_beams, max_length)
         return beam_search(self.decoder.step, num_beams, max_length, length_penalty,
@@ -583,12 +620,30 @@ class HipT5Generator:
                                    decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device)
 
     def generate_many(self, sources, num_beams: int, max_length: int, length_penalty: float = 1.0,
-                      traces: Optional[list] = None) -> List[BeamSearchOutput]:
+                      traces: Optional[list] = None, sync_every: Optional[int] = None) -> List[BeamSearchOutput]:
         """``generate`` for several sources at once: one packed encoder pass, one cross-K/V GEMM and one decode loop that
         runs until the last state stops, with one readback per step.  Entry ``i`` equals ``generate(sources[i], ...)``
         bit for bit (sequences, scores and, in ``traces[i]``, every step's selected triples), whichever other sources
-        share the call, in whatever order, and whenever they finish."""
+        share the call, in whatever order, and whenever they finish.
+
+        ``sync_every`` (an integer >= 1; the default None is the loop above): the books live on the device
+        (``rp_beam_advance``, DESIGN.md section 9 "device books"), nothing is uploaded or read back per position, and the
+        states' stop flags are read every ``sync_every`` positions.  The outputs are the same sequences and scores."""
+        if sync_every is not None:
+            if traces is not None:
+                raise ValueError("traces= needs the host books: it cannot be combined with sync_every")
+            if int(sync_every) != sync_every or sync_every < 1:
+                raise ValueError(f"sync_every={sync_every} must be an integer >= 1 (or None)")
+            if max_length <= 1:
+                raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
         n = self._start_many(sources, num_beams, max_length)
+        if sync_every is not None:
+            dec = self.decoder
+            return beam_search_batch_device(
+                lambda active, tokens, ancestry, t: dec.step_many(active, tokens, ancestry, t=t), dec.select_many,
+                dec.beam_advance, n, num_beams, max_length, length_penalty, eos_token_id=self.cfg.get("eos_token_id", 1),
+                decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), sync_every=int(sync_every),
+                device=self.device, init=dec.beam_books)
         return beam_search_batch(self.decoder.step_many, n, num_beams, max_length, length_penalty,
                                  eos_token_id=self.cfg.get("eos_token_id", 1),
                                  decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),

@@ -26,6 +26,11 @@ protocol and run it with one source.
 
 Sampling (``sample_search_batch``) keeps its whole state on the device and reads nothing back per step: rows never
 reorder, so the ancestry table is the identity, and the finished flags are read once every ``sync_every`` positions.
+
+``beam_search_batch_device`` is the beam search with the same property: the bookkeeping lives in a ``BeamBooks`` block on
+the device, ``advance`` (``rp_beam_advance``) updates it after every step, and the stop flags are read every
+``sync_every`` positions.  ``beam_advance_host`` restates that kernel on host tensors with its stable order (the kernel's
+oracle, and the ``advance`` of a CPU run).  ``beam_search_batch`` with its host books stays the default.
 """
 from __future__ import annotations
 
@@ -199,6 +204,219 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
     if traces is not None:
         traces.extend(per_state)
     return [st.result() for st in states]
+
+
+# ---- beam search with its books on the device ------------------------------------------------------------------------------
+# The parts of the books block (include/reprover_hip.h, rp_beam_books_bytes), in order: name, shape in terms of
+# (n, nb, max_len), fp32 or int32.  Every part starts at a multiple of 16 bytes.
+_BOOK_PARTS = (
+    ("run_seq", lambda n, nb, L: (2, n, nb, L), False), ("anc", lambda n, nb, L: (2, n, nb, L), False),
+    ("fin_seq", lambda n, nb, L: (2, n, nb, L), False), ("run_scores", lambda n, nb, L: (n, nb), True),
+    ("beam_scores", lambda n, nb, L: (n, nb), True), ("fin_flag", lambda n, nb, L: (n, nb), False),
+    ("fin_len", lambda n, nb, L: (n, nb), False), ("heur", lambda n, nb, L: (n,), False),
+    ("done", lambda n, nb, L: (n,), False), ("steps", lambda n, nb, L: (n,), False),
+    ("tokens", lambda n, nb, L: (n * nb,), False), ("running", lambda n, nb, L: (n * nb,), True),
+    ("anc_rows", lambda n, nb, L: (n * nb, L), False),
+)
+
+
+def beam_books_bytes(n: int, nb: int, max_len: int) -> int:
+    """The size of the books block (what ``rp_beam_books_bytes`` returns for arguments it accepts)."""
+    total = 0
+    for _, shape, _ in _BOOK_PARTS:
+        words = 1
+        for d in shape(n, nb, max_len):
+            words *= d
+        total += (4 * words + 15) // 16 * 16
+    return total
+
+
+class BeamBooks:
+    """The books of a beam search over ``n`` states: one int32 ``block`` (on any device) and typed views of its parts.
+    Row tables hold ``max_len`` columns; ``run_seq`` / ``anc`` / ``fin_seq`` are pairs of which the step at position ``t``
+    reads member ``t & 1`` and writes the other, so ``steps[s] & 1`` is state ``s``'s current member.  ``tokens``,
+    ``running`` and ``anc_rows`` are by row (slot * nb + beam): the next step's inputs.  ``rp_beam_advance`` (or
+    ``beam_advance_host``) updates all of it in place."""
+
+    def __init__(self, n: int, nb: int, max_len: int, device=None, block: Optional[torch.Tensor] = None):
+        self.n, self.nb, self.max_len = int(n), int(nb), int(max_len)
+        self.nbytes = beam_books_bytes(self.n, self.nb, self.max_len)
+        if block is None:
+            block = torch.zeros(self.nbytes // 4, dtype=torch.int32, device=device)
+        assert block.dtype == torch.int32 and block.is_contiguous() and block.numel() == self.nbytes // 4
+        self.block = block
+        off = 0
+        for name, shape, is_float in _BOOK_PARTS:
+            shp = shape(self.n, self.nb, self.max_len)
+            words = 1
+            for d in shp:
+                words *= d
+            part = block[off : off + words]
+            setattr(self, name, (part.view(torch.float32) if is_float else part).view(shp))
+            off += (words + 3) // 4 * 4
+
+    def cpu(self) -> "BeamBooks":
+        """A host copy (one device-to-host transfer of the block)."""
+        return BeamBooks(self.n, self.nb, self.max_len, block=self.block.cpu())
+
+    def result(self, state: int, num_return_sequences: Optional[int] = None) -> BeamSearchOutput:
+        """``_BeamState.result`` of one state from host books."""
+        nret = self.nb if num_return_sequences is None else int(num_return_sequences)
+        cur = int(self.steps[state]) & 1
+        max_generated = int(self.fin_len[state, :nret].max())  # beam_indices' count of non-negative entries (:3514-3517)
+        return BeamSearchOutput(self.fin_seq[cur, state, :nret, : 1 + max_generated].long().clone(),
+                                self.beam_scores[state, :nret].clone())
+
+
+def beam_books_init_host(n: int, nb: int, max_len: int, eos_token_id: int, decoder_start_token_id: int) -> BeamBooks:
+    """``rp_beam_books_init`` on host tensors: ``_BeamState.__init__``'s values for ``n`` states."""
+    bk = BeamBooks(n, nb, max_len)
+    for tab in (bk.run_seq, bk.fin_seq):
+        tab.fill_(eos_token_id)
+        tab[..., 0] = decoder_start_token_id
+    ident = (torch.arange(max_len, dtype=torch.int32)[None] * nb + torch.arange(nb, dtype=torch.int32)[:, None])
+    bk.anc.copy_(ident.expand(2, n, nb, max_len))
+    bk.anc_rows.copy_(ident.repeat(n, 1))
+    bk.run_scores.fill_(NEG)
+    bk.run_scores[:, 0] = 0.0
+    bk.running.copy_(bk.run_scores.reshape(-1))
+    bk.beam_scores.fill_(NEG)
+    bk.heur.fill_(1)
+    bk.tokens.fill_(decoder_start_token_id)
+    return bk
+
+
+def _stable_top(x: torch.Tensor, k: int) -> List[int]:
+    """Indices of the top ``k`` of ``x`` in ``rp_beam_select``'s total order: descending, equal values (-0.0 == +0.0) to
+    the lower index."""
+    v = x.tolist()
+    return sorted(range(len(v)), key=lambda j: (-v[j], j))[:k]
+
+
+BEAM_ADVANCE_MUTANTS = ("late_candidates_finish", "heuristic_not_sticky", "ancestry_not_reordered", "done_not_frozen")
+
+
+def beam_advance_host(books: BeamBooks, active: Sequence[int], t: int, scores: torch.Tensor, tokens: torch.Tensor,
+                      parents: torch.Tensor, fin_div: float, run_div: float, eos_token_id: int,
+                      mutant: Optional[str] = None) -> None:
+    """``rp_beam_advance`` restated on host books: ``_BeamState.advance`` for the states ``active`` at position ``t``
+    from the step's ``[n_active, 2 nb]`` selected triples, with both selections in the stated stable order
+    (``_stable_top``; ``torch.topk`` promises none among ties) and the same writes as the kernel, so that the whole block
+    compares bit for bit.  ``fin_div`` / ``run_div``: the two divisors ``(t + 1) ** length_penalty`` of
+    ``_BeamState.advance`` (finished scores; ``best_running`` after ``cur_len`` advanced), rounded to fp32 here as the C
+    ABI's float arguments are.  A state whose ``done`` is set is left as it is.  ``mutant`` plants known bugs (one name
+    of ``BEAM_ADVANCE_MUTANTS`` or several joined by "+") so that tests can show a comparison would notice them."""
+    mutants = set(mutant.split("+")) if mutant else set()
+    assert mutants <= set(BEAM_ADVANCE_MUTANTS), mutant
+    n, nb, L = books.n, books.nb, books.max_len
+    assert 0 <= t and t + 1 < L and len(set(active)) == len(active) and all(0 <= s < n for s in active)
+    K = 2 * nb
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32)  # noqa: E731
+    cur, new = t & 1, (t & 1) ^ 1
+    width = 4 if L % 4 == 0 else 1  # the kernel moves rows in units of `width` columns
+    ncol = (t + 2 + width - 1) // width * width
+    for slot, s in enumerate(active):
+        if int(books.done[s]) and "done_not_frozen" not in mutants:
+            continue
+        val = scores[slot].to(torch.float32).cpu()
+        tok = tokens[slot].to(torch.int32).cpu()
+        par = parents[slot].to(torch.int64).cpu().clamp(0, nb - 1)
+        heur = bool(books.heur[s])
+        hits = (tok == eos_token_id) | torch.tensor(t + 2 >= L)
+        run_lp = val + torch.where(hits, f32(NEG), f32(-0.0))
+        nxt = _stable_top(run_lp, nb)
+        just_finished = hits if "late_candidates_finish" in mutants else hits & (torch.arange(K) < nb)
+        fin = val / f32(fin_div)
+        fin = fin + f32(0.0 if heur else NEG)
+        fin = fin + torch.where(just_finished, f32(-0.0), f32(NEG))
+        merged = torch.cat([books.beam_scores[s], fin])
+        sel = _stable_top(merged, nb)
+        # the row gathers: columns 0 .. t of the source rows, column t + 1 the step's own
+        topk_seq = books.run_seq[cur, s][par, :ncol].clone()
+        topk_seq[:, t + 1] = tok
+        src = torch.arange(nb) if "ancestry_not_reordered" in mutants else par[nxt]
+        new_anc = books.anc[cur, s][src, :ncol].clone()
+        new_anc[:, t + 1] = (t + 1) * nb + torch.arange(nb, dtype=torch.int32)
+        books.run_seq[new, s][:, :ncol] = topk_seq[nxt]
+        books.anc[new, s][:, :ncol] = new_anc
+        books.anc_rows[slot * nb : (slot + 1) * nb, :ncol] = new_anc
+        books.fin_seq[new, s][:, :ncol] = torch.cat([books.fin_seq[cur, s][:, :ncol], topk_seq])[sel]
+        books.run_scores[s] = run_lp[nxt]
+        books.tokens[slot * nb : (slot + 1) * nb] = tok[nxt]
+        books.running[slot * nb : (slot + 1) * nb] = run_lp[nxt]
+        books.beam_scores[s] = merged[sel]
+        books.fin_flag[s] = torch.cat([books.fin_flag[s], just_finished.to(torch.int32)])[sel]
+        books.fin_len[s] = torch.cat([books.fin_len[s], torch.full((K,), t + 1, dtype=torch.int32)])[sel]
+        # the early-stop test and the stop flag
+        best_running = books.run_scores[s, 0] / f32(run_div)
+        worst = torch.where(books.fin_flag[s].bool(), books.beam_scores[s].min(), f32(NEG))
+        unsatisfied = bool((best_running > worst).any())
+        heur = unsatisfied if "heuristic_not_sticky" in mutants else (heur and unsatisfied)
+        books.heur[s] = int(heur)
+        books.done[s] = int(not heur or bool(hits.all()))
+        books.steps[s] = t + 1
+
+
+def beam_search_batch_device(step_many: Callable, select_many: Callable, advance: Callable, num_states: int,
+                             num_beams: int, max_length: int, length_penalty: float = 1.0, eos_token_id: int = 1,
+                             decoder_start_token_id: int = 0, num_return_sequences: Optional[int] = None,
+                             sync_every: int = 16, device=None, init: Optional[Callable] = None,
+                             to_host: Callable = lambda x: x.cpu()) -> List[BeamSearchOutput]:
+    """``beam_search_batch`` with the books on the device (``BeamBooks``): per position one ``step_many``, one
+    ``select_many`` and one ``advance``, nothing uploaded but their arguments and nothing read back.  Every
+    ``sync_every`` positions the ``num_states`` ``done`` flags are read once and the stopped states leave the active
+    list; a stopped state that is still listed keeps being stepped, and ``advance`` leaves its books alone.  The loop
+    ends when every state has stopped or at ``max_length``; then the block is read once.  Entry ``i`` is
+    ``beam_search_batch``'s for any ``sync_every`` wherever ``torch.topk`` and the stable order pick the same
+    candidates (always, unless live candidates tie exactly).
+
+    - ``init(n, nb, max_length, eos, start) -> BeamBooks``: initialised books (default ``beam_books_init_host``, moved to
+      ``device``).
+    - ``step_many(active, tokens, ancestry, t) -> log_probs``: as in ``sample_search_batch``; ``tokens`` int32
+      ``[n_active * nb]`` and ``ancestry`` int32 ``[n_active * nb, max_length]`` (columns ``0..t`` are read) are views
+      of the books' by-row parts.
+    - ``select_many(log_probs, running, nb, k)``: as in ``beam_search_batch``.
+    - ``advance(books, active, t, scores, tokens, parents, fin_div, run_div, eos)``: ``rp_beam_advance``
+      (``beam_advance_host`` on the host).
+    - ``to_host``: the loop's every device-to-host copy goes through it (tests count them)."""
+    n, nb = int(num_states), int(num_beams)
+    nret = nb if num_return_sequences is None else int(num_return_sequences)
+    if max_length <= 1:
+        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+    if nb < 1 or n < 1 or sync_every < 1 or not 1 <= nret <= nb:
+        raise ValueError(f"num_states={n}, num_beams={nb}, sync_every={sync_every} must all be >= 1 and "
+                         f"num_return_sequences={nret} in 1..num_beams")
+    if init is None:
+        books = beam_books_init_host(n, nb, max_length, eos_token_id, decoder_start_token_id)
+        if device is not None:
+            books = BeamBooks(n, nb, max_length, block=books.block.to(device))
+    else:
+        books = init(n, nb, max_length, eos_token_id, decoder_start_token_id)
+    prompt_len = 1
+    active = list(range(n))
+    t = 0
+    while active and t + 1 < max_length:
+        rows = len(active) * nb
+        log_probs = step_many(list(active), books.tokens[:rows], books.anc_rows[:rows], t)
+        vals, toks, parents = select_many(log_probs, books.running[:rows], nb, 2 * nb)
+        cur_len = t + 1
+        fin_div = float((cur_len + 1 - prompt_len) ** length_penalty)  # _BeamState.advance: the finished scores' divisor
+        cur_len = cur_len + 1
+        run_div = float((cur_len - prompt_len) ** length_penalty)      # ... and best_running's, after cur_len advanced
+        advance(books, list(active), t, vals, toks, parents, fin_div, run_div, eos_token_id)
+        t += 1
+        if t % sync_every == 0 and t + 1 < max_length:
+            done = to_host(books.done)  # the only host sync of the loop
+            still = [i for i in active if not bool(done[i])]
+            if still and len(still) != len(active):  # slots moved: the next step's inputs, by the new rows
+                idx = torch.tensor(still, dtype=torch.int64, device=books.block.device)
+                m = len(still) * nb
+                books.tokens[:m] = books.run_seq[t & 1, idx, :, t].reshape(-1)
+                books.running[:m] = books.run_scores[idx].reshape(-1)
+                books.anc_rows[:m] = books.anc[t & 1, idx].reshape(m, max_length)
+            active = still
+    host = BeamBooks(n, nb, max_length, block=to_host(books.block))
+    return [host.result(i, nret) for i in range(n)]
 
 
 def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], max_length: int, eos_token_id: int = 1,

@@ -6,7 +6,7 @@ with ``PremiseRetriever`` and generates from the augmented state.  No ``transfor
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 from ..common import Pos, format_augmented_state, remove_marks, zip_strict
 from ..decoder import HipT5Generator
@@ -31,11 +31,14 @@ class HuggingFaceGenerator(TacticGenerator):
     ``do_sample=True`` draws ``num_samples`` samples instead (temperature / top-k / top-p, ``HipT5Generator.sample_many``)
     and returns them sorted by score, best first (a stable sort), de-duplicated keeping the first occurrence.  The seed
     of a served state mixes ``seed`` with the number of states this object has served so far: repeated calls on one
-    state differ, and ``batch_generate_sync([a, b])`` equals ``generate_sync(a)`` then ``generate_sync(b)``."""
+    state differ, and ``batch_generate_sync([a, b])`` equals ``generate_sync(a)`` then ``generate_sync(b)``.
+
+    ``beam_sync_every`` (an integer >= 1; default None): the beam search keeps its books on the device and looks at the
+    states' stop flags every that many positions (``HipT5Generator.generate_many(sync_every=...)``); same outputs."""
 
     def __init__(self, model_path: str, device, max_inp_seq_len: int, max_oup_seq_len: int, length_penalty: float,
                  template: str = "%s", do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
-                 top_p: float = 1.0, seed: int = 0):
+                 top_p: float = 1.0, seed: int = 0, beam_sync_every: Optional[int] = None):
         self.model_path = model_path
         self.device = device
         self.max_inp_seq_len = max_inp_seq_len
@@ -45,6 +48,11 @@ class HuggingFaceGenerator(TacticGenerator):
         check_sampling(temperature, top_k, top_p)
         self.do_sample, self.temperature, self.top_k, self.top_p, self.seed = do_sample, temperature, top_k, top_p, seed
         self.states_served = 0
+        if beam_sync_every is not None and (int(beam_sync_every) != beam_sync_every or beam_sync_every < 1):
+            raise ValueError(f"beam_sync_every={beam_sync_every} must be an integer >= 1 (or None)")
+        self.beam_sync_every = beam_sync_every
+        # the default leaves the beam-search calls exactly as they were
+        self._books = {} if beam_sync_every is None else {"sync_every": int(beam_sync_every)}
 
     def _next_seeds(self, n: int) -> List[int]:
         """The 32-bit seeds of the next ``n`` served states (murmur3's finaliser over seed + golden-ratio steps)."""
@@ -90,7 +98,7 @@ class HuggingFaceGenerator(TacticGenerator):
         ids = encode_one(state, self.max_inp_seq_len)  # tokenizer(state, max_length=..., truncation=True)
         if self.do_sample:
             return self._sampled([ids], num_samples)[0]
-        out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty)
+        out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty, **self._books)
         raw_output_text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
         raw_scores = out.sequences_scores.tolist()
         output_text, output_score = [], []
@@ -116,7 +124,7 @@ class HuggingFaceGenerator(TacticGenerator):
         cap = self.generator.decoder.max_states(num_samples)  # the engine's cap on states per call
         for i in range(0, len(ids), cap):
             outs = self.generator.generate_many(ids[i : i + cap], num_samples, self.max_oup_seq_len,
-                                                self.length_penalty)
+                                                self.length_penalty, **self._books)
             for out in outs:
                 raw_output_text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
                 raw_scores = out.sequences_scores.tolist()
@@ -139,7 +147,8 @@ class RetrievalAugmentedGenerator(TacticGenerator):
 
     def __init__(self, gen_path: str, ret_path: str, indexed_corpus_path: str, device, max_inp_seq_len: int,
                  max_oup_seq_len: int, length_penalty: float, max_num_retrieved: int, do_sample: bool = False,
-                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0) -> None:
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
+                 beam_sync_every: Optional[int] = None) -> None:
         self.gen_path = gen_path
         self.ret_path = ret_path
         self.indexed_corpus_path = indexed_corpus_path
@@ -150,7 +159,7 @@ class RetrievalAugmentedGenerator(TacticGenerator):
         self.max_num_retrieved = max_num_retrieved
         self.hf_gen = HuggingFaceGenerator(gen_path, device, max_inp_seq_len, max_oup_seq_len, length_penalty,
                                            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
-                                           seed=seed)
+                                           seed=seed, beam_sync_every=beam_sync_every)
 
     def initialize(self) -> None:
         self.hf_gen.initialize()

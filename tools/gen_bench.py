@@ -16,6 +16,13 @@ per step, as one JSON line.
 milliseconds of both, as one JSON line.
 
     python tools/gen_bench.py --sample [--reps 3] [--out FILE]
+
+``--states B [B ...] --sync-every K [K ...]``: the beam search with its books on the device
+(``generate_many(sync_every=K)``) beside the host-books call of the same tree, in one process, alternating: per
+repetition the host-books call twice (the difference of its own two runs is the spread), then one call per K.  Whole-call
+and per-step milliseconds of each, and whether every device-books output equals the host-books one.
+
+    python tools/gen_bench.py --states 1 8 --sync-every 1 4 16 [--reps 2] [--out FILE]
 """
 from __future__ import annotations
 
@@ -112,6 +119,41 @@ def states_bench(gen, cfg, states, reps, nb=64, max_len=512, src_bytes=2048):
     return res
 
 
+def books_bench(gen, cfg, states, sync_every, reps, nb=64, max_len=512, src_bytes=2048):
+    rng = np.random.default_rng(0)
+    srcs = [np.concatenate([rng.integers(3, 259, size=src_bytes - 1), [1]]).astype(np.int32) for _ in range(max(states))]
+    L = cfg["num_decoder_layers"]
+    res = {"metric": "gen_device_books_bench", "beams": nb, "max_length": max_len, "length_penalty": 0.0,
+           "config": f"byt5-small ({L} decoder layers), distinct sources of {src_bytes} bytes", "reps": reps,
+           "launches_per_step": {"host_books": 12 * L + 4 + 2, "device_books": 12 * L + 4 + 3}, "states": {}}
+    gen.generate_many(srcs[:2], nb, 8, 0.0)  # warm-up: code objects
+    gen.generate_many(srcs[:2], nb, 8, 0.0, sync_every=2)
+    for B in states:
+        host_ms, dev_ms, same, steps = [], {k: [] for k in sync_every}, True, 0
+        for _ in range(reps):
+            pair = []
+            for _ in range(2):
+                tr = []
+                ms, want = _timed(lambda: gen.generate_many(srcs[:B], nb, max_len, 0.0, traces=tr))
+                pair.append(ms)
+                steps = max(len(t) for t in tr)
+            host_ms.append(pair)
+            for k in sync_every:
+                ms, got = _timed(lambda: gen.generate_many(srcs[:B], nb, max_len, 0.0, sync_every=k))
+                dev_ms[k].append(ms)
+                same = same and _same(got, want)
+        best = min(min(p) for p in host_ms)
+        res["states"][str(B)] = {
+            "steps": steps, "host_books_ms": [[round(x, 1) for x in p] for p in host_ms],
+            "host_books_spread_ms": [round(abs(p[0] - p[1]), 1) for p in host_ms],
+            "host_books_ms_per_step": round(best / steps, 3),
+            "device_books_ms": {str(k): [round(x, 1) for x in v] for k, v in dev_ms.items()},
+            "device_books_ms_per_step": {str(k): round(min(v) / steps, 3) for k, v in dev_ms.items()},
+            "ratio_host_over_device": {str(k): round(best / min(v), 3) for k, v in dev_ms.items()},
+            "outputs_identical": same}
+    return res
+
+
 def sample_bench(gen, cfg, reps, nb=64, max_len=512, src_bytes=2048):
     rng = np.random.default_rng(0)
     src = np.concatenate([rng.integers(3, 259, size=src_bytes - 1), [1]]).astype(np.int32)
@@ -141,9 +183,13 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--states", type=int, nargs="+", default=None, help="batched generation against the per-state loop")
+    ap.add_argument("--sync-every", type=int, nargs="+", default=None,
+                    help="with --states: device-books generate_many at these sync_every values against the host books")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--sample", action="store_true", help="the sampled call beside the beam-search prover call")
     args = ap.parse_args(argv)
+    if args.sync_every and (not args.states or min(args.sync_every) < 1):
+        ap.error("--sync-every takes values >= 1 and goes with --states")
     if args.sample:
         cfg = synth.seq2seq_config("byt5-small")
         gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
@@ -156,7 +202,10 @@ def main(argv=None):
     if args.states:
         cfg = synth.seq2seq_config("byt5-small")
         gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
-        line = json.dumps(states_bench(gen, cfg, sorted(args.states), args.reps))
+        if args.sync_every:
+            line = json.dumps(books_bench(gen, cfg, sorted(args.states), args.sync_every, args.reps))
+        else:
+            line = json.dumps(states_bench(gen, cfg, sorted(args.states), args.reps))
         print(line)
         if args.out:
             with open(args.out, "w") as fh:
