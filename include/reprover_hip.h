@@ -609,7 +609,8 @@ RpStatus rp_beam_select(const float* logprobs, const float* running, int32_t nb,
 
 /* Batched generation: one decode loop for the beams of n proof states ("One step,
  * 1 - 32 states").  All states start together and sit at the same position t; a state that has finished
- * is left out of the step's active list and costs nothing.  For every state the outputs are the bits
+ * is left out of the step's active list and costs nothing (states that join a running search, each at
+ * its own position: the slot pool below).  For every state the outputs are the bits
  * that rp_decoder_cross_kv / rp_decoder_step / rp_beam_select give that state alone, whichever other
  * states share the call and in whatever order: those three are the one-state calls of the functions
  * below (n = 1, src_cu = {0, src_len}, active = {0}), one implementation.
@@ -650,6 +651,53 @@ RpStatus rp_decoder_batch_step(RpDecoder* dec, const int32_t* src_cu, int32_t n,
  * workspace: n_active * nb * min(k, vocab) * 8 bytes of device memory. */
 RpStatus rp_beam_select_batch(const float* logprobs, const float* running, int32_t n_active, int32_t nb,
                               int32_t vocab, int32_t k, float* scores, int32_t* tokens, int32_t* parents,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* The slot pool: continuous batching ("Continuous batching").  A workspace of n_slots
+ * places, each able to carry one proof state's search; a state is admitted into a free slot between two
+ * steps and leaves it when it stops, so the states of one step stand at different positions.  The step is
+ * rp_decoder_batch_step's launch sequence with a position per slot instead of one t: a slot's beams store
+ * cache row pos * nb + b and attend over ancestry columns 0 .. pos.  For every state the log-probs are the
+ * bits rp_decoder_step gives it alone at that position, whichever states share the call, wherever they
+ * stand and in whatever slot order.  rp_beam_select_batch serves the pool as it is (selection reads no
+ * position).
+ * Layout: rp_decoder_batch_workspace_bytes' with n = n_slots and a cross K/V part of n_slots * src_cap rows.
+ * Slot s owns cross-K/V rows s * src_cap .. (s + 1) * src_cap and cache state s.
+ * Caps: 1 <= n_slots <= 32, n_slots * num_beams <= 1024, num_beams <= 64, max_len and src_cap in 1..8192.
+ * rp_decoder_pool_workspace_bytes returns 0 on bad arguments (rp_last_error says why).
+ *
+ * rp_decoder_pool_admit writes the cross K/V of m newly encoded sources into their slots' regions, one GEMM
+ * per source against the weight rp_decoder_batch_cross_kv uses (a GEMM row depends on no other row: the same
+ * bits):
+ *   slots     HOST int32 [m]: distinct slots in [0, n_slots), the place each source takes
+ *   enc_bf16  device bf16 [src_cu[m], d_model]: rp_encode_hidden over the packed newcomers
+ *   src_cu    HOST int32 [m + 1] prefix sums (start at 0), every source 1..src_cap rows
+ * A re-used slot needs no clearing: every cache row a state reads at position p was written by that state
+ * at a position <= p (its ancestry names only rows of its own earlier steps), and every cross key it reads
+ * lies below its own src_len, which its own admission wrote.  Nothing a previous tenant left is read.
+ *
+ * rp_decoder_pool_step: one decode step for the n_active slots listed; row a * nb + b is beam b of slot
+ * active[a]:
+ *   active    HOST int32 [n_active]: distinct slots in [0, n_slots)
+ *   pos       HOST int32 [n_active]: the position each slot's beams stand at, 0 <= pos < max_len
+ *   src_len   HOST int32 [n_active]: the source length each slot was admitted with, 1 .. src_cap
+ *   tokens    device int32 [n_active * nb]
+ *   ancestry  device int32 [n_active * nb, anc_stride]: row r's columns 0 .. pos[r / nb] are read (entries
+ *             local to the slot's cache, clamped to it); anc_stride >= the largest pos + 1
+ *   logprobs  device fp32 [n_active * nb, vocab]
+ * The self-attention sizes its LDS for the largest pos + 1 of the call.
+ * RP_E_INVALID (nothing is launched, rp_last_error says which): a null pointer, a slot outside
+ * [0, n_slots), a slot named twice, pos outside [0, max_len), src_len outside 1..src_cap, anc_stride below
+ * a pos + 1, the caps above.  RP_E_WORKSPACE (nothing is launched): workspace_bytes below
+ * rp_decoder_pool_workspace_bytes. */
+size_t   rp_decoder_pool_workspace_bytes(const RpDecoder* dec, int32_t n_slots, int32_t num_beams, int32_t max_len,
+                                         int32_t src_cap);
+RpStatus rp_decoder_pool_admit(RpDecoder* dec, int32_t n_slots, int32_t num_beams, int32_t max_len, int32_t src_cap,
+                               const int32_t* slots, const void* enc_bf16, const int32_t* src_cu, int32_t m,
+                               void* workspace, size_t workspace_bytes, void* stream);
+RpStatus rp_decoder_pool_step(RpDecoder* dec, int32_t n_slots, int32_t num_beams, int32_t max_len, int32_t src_cap,
+                              const int32_t* active, const int32_t* pos, const int32_t* src_len, int32_t n_active,
+                              const int32_t* tokens, const int32_t* ancestry, int32_t anc_stride, float* logprobs,
                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* Beam books ("Per-step host sync, and device books"): beam search's bookkeeping -

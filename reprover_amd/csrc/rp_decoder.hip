@@ -10,6 +10,8 @@
 // attentions run as one launch over (head, row), each row finding its state's cache, cross K/V and source length through
 // the slot table passed by value.  rp_decoder_step / rp_decoder_cross_kv / rp_beam_select are the one-state calls of
 // rp_decoder_batch_step / rp_decoder_batch_cross_kv / rp_beam_select_batch: there is one launch sequence.
+// rp_decoder_pool_step is that sequence with a position per slot (the batched call: every slot at t), over a workspace
+// whose slots states enter between steps (rp_decoder_pool_admit): continuous batching.
 // rp_sample_step (sampling) and rp_beam_books_init / rp_beam_advance (beam search) keep a search's bookkeeping on the
 // device, one more launch per step, so that the host loop reads nothing back per position.
 //
@@ -126,11 +128,14 @@ RpStatus launch_dec_gemm(const bf16_t* A, int lda, int M, const bf16_t* W, int N
   return RP_OK;
 }
 
-// per active slot: the state it carries and where that state's source sits in the packed cross K/V
+// per active slot: the state it carries, where that state's source sits in the cross K/V, and the position the slot's
+// beams stand at (the decode step's: one value for the whole call from rp_decoder_batch_step, one per slot from
+// rp_decoder_pool_step)
 struct DecSlots {
   int32_t state[DEC_MAX_STATES];
   int32_t src_off[DEC_MAX_STATES];
   int32_t src_len[DEC_MAX_STATES];
+  int32_t pos[DEC_MAX_STATES];
 };
 
 // One (head, row) of decoder attention: softmax(q k^T + bias) v over `len` keys, d_kv = 64, fp32 scores in s_sc (dynamic
@@ -192,13 +197,14 @@ __device__ __forceinline__ void dec_attention_row(float* __restrict__ s_sc, cons
 
 // One (head, row) per workgroup, row = slot * nb + beam.  Self-attention (CROSS = false): the state's own cache of
 // `rows` = max_len * nb rows at kv + state * state_stride, keys through the row's ancestry entries (local to that cache),
-// len keys.  Cross-attention: the state's source rows of the packed cross K/V, all src_len keys, no bias.
+// pos[slot] + 1 keys: columns 0 .. pos[slot] of the row's ancestry entries (the dynamic LDS holds the call's largest
+// pos + 1 scores).  Cross-attention: the state's source rows of the cross K/V, all src_len keys, no bias.
 template <bool CROSS>
 __global__ __launch_bounds__(256) void dec_attention_kernel(const bf16_t* __restrict__ q, int ldq,
                                                             const bf16_t* __restrict__ kv, int ldkv, int koff, int voff,
                                                             int rows, size_t state_stride,
                                                             const int32_t* __restrict__ anc, int astride,
-                                                            const float* __restrict__ tab, int nbias, int len, int nb,
+                                                            const float* __restrict__ tab, int nbias, int nb,
                                                             DecSlots slots, bf16_t* __restrict__ out, int ldo) {
   extern __shared__ float s_sc[];
   const int h = blockIdx.x, row = blockIdx.y;
@@ -208,15 +214,15 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(const bf16_t* __rest
                       slots.src_len[slot], nullptr, nullptr, 1, slots.src_len[slot], out + (size_t)row * ldo, h);
   else
     dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)slots.state[slot] * state_stride, ldkv, koff, voff, rows,
-                      anc + (size_t)row * astride, tab, nbias, len, out + (size_t)row * ldo, h);
+                      anc + (size_t)row * astride, tab, nbias, slots.pos[slot] + 1, out + (size_t)row * ldo, h);
 }
 
-// cache row row0 + beam of the row's state <- the k, v columns of qkv[row]
+// cache row pos[slot] * nb + beam of the row's state <- the k, v columns of qkv[row]
 __global__ __launch_bounds__(256) void dec_store_kv_kernel(const bf16_t* __restrict__ qkv, int inner,
-                                                           bf16_t* __restrict__ cache, size_t state_stride, int row0,
-                                                           int nb, DecSlots slots) {
+                                                           bf16_t* __restrict__ cache, size_t state_stride, int nb,
+                                                           DecSlots slots) {
   const int row = blockIdx.x, slot = row / nb, b = row - slot * nb;
-  bf16_t* dst = cache + (size_t)slots.state[slot] * state_stride + (size_t)(row0 + b) * 2 * inner;
+  bf16_t* dst = cache + (size_t)slots.state[slot] * state_stride + (size_t)(slots.pos[slot] * nb + b) * 2 * inner;
   for (int c = threadIdx.x; c < 2 * inner; c += 256) dst[c] = qkv[(size_t)row * 3 * inner + inner + c];
 }
 
@@ -952,33 +958,18 @@ extern "C" RpStatus rp_decoder_batch_cross_kv(RpDecoder* d, const void* enc, con
   return launch_dec_gemm<EPI_BF16>((const bf16_t*)enc, D, total, d->cross_kv_w, NKV, D, w.ckv, NKV, (hipStream_t)stream_);
 }
 
-extern "C" RpStatus rp_decoder_batch_step(RpDecoder* d, const int32_t* src_cu, int32_t n, const int32_t* active,
-                                          int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
-                                          int32_t nb, int32_t t, int32_t max_len, float* logprobs, void* ws,
-                                          size_t ws_bytes, void* stream_) {
-  int total = 0;
-  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
-  if (st) return st;
-  RP_REQUIRE(active && tokens && anc && logprobs, "null argument");
-  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
-  RP_REQUIRE(t >= 0 && t < max_len, "t=%d outside [0, max_len=%d)", t, max_len);
-  RP_REQUIRE(astride >= t + 1, "anc_stride=%d < t + 1 = %d", astride, t + 1);
-  DecSlots slots = {};
-  uint32_t seen = 0;
-  int max_src = 0;
+namespace {
+// The launch sequence of one decode step over the n_active * nb rows of a checked slot table: the one implementation
+// behind rp_decoder_batch_step (every slot at the call's t) and rp_decoder_pool_step (a position per slot).  Only the
+// cache store and the self-attention read a position, each its own slot's.
+RpStatus dec_step_launch(RpDecoder* d, const DecWs& w, const DecSlots& slots, int n_active, const int32_t* tokens,
+                         const int32_t* anc, int astride, int nb, int max_len, float* logprobs, hipStream_t s) {
+  RpStatus st;
+  int max_src = 0, max_keys = 0;  // the attentions' LDS: the longest key list of the call
   for (int a = 0; a < n_active; ++a) {
-    const int sidx = active[a];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share cache rows
-    seen |= 1u << sidx;
-    slots.state[a] = sidx;
-    slots.src_off[a] = src_cu[sidx];
-    slots.src_len[a] = src_cu[sidx + 1] - src_cu[sidx];
     max_src = std::max(max_src, slots.src_len[a]);
+    max_keys = std::max(max_keys, slots.pos[a] + 1);
   }
-  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
-  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
-  hipStream_t s = (hipStream_t)stream_;
   const RpT5Config& c = d->cfg;
   const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
   const float eps = c.layer_norm_eps;
@@ -992,9 +983,9 @@ extern "C" RpStatus rp_decoder_batch_step(RpDecoder* d, const int32_t* src_cu, i
     // self-attention (modeling_t5.py T5LayerSelfAttention): x += o(attn(rmsnorm(x)))
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_self, w.h, D, eps, 1.f);
     if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.wqkv, 3 * inner, D, w.qkv, 3 * inner, s))) return st;
-    hipLaunchKernelGGL(dec_store_kv_kernel, dim3(M), dim3(256), 0, s, w.qkv, inner, cache, state_stride, t * nb, nb, slots);
-    hipLaunchKernelGGL((dec_attention_kernel<false>), dim3(H, M), dim3(256), (t + 1) * sizeof(float), s, w.qkv, 3 * inner,
-                       cache, 2 * inner, 0, inner, rows, state_stride, anc, astride, d->bias_tab, d->nbias, t + 1, nb, slots,
+    hipLaunchKernelGGL(dec_store_kv_kernel, dim3(M), dim3(256), 0, s, w.qkv, inner, cache, state_stride, nb, slots);
+    hipLaunchKernelGGL((dec_attention_kernel<false>), dim3(H, M), dim3(256), max_keys * sizeof(float), s, w.qkv, 3 * inner,
+                       cache, 2 * inner, 0, inner, rows, state_stride, anc, astride, d->bias_tab, d->nbias, nb, slots,
                        w.att, inner);
     if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.wo, D, inner, w.x, D, s))) return st;
     // cross-attention (T5LayerCrossAttention): no position bias, all of the state's source keys
@@ -1002,7 +993,7 @@ extern "C" RpStatus rp_decoder_batch_step(RpDecoder* d, const int32_t* src_cu, i
     if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.cq, inner, D, w.qkv, inner, s))) return st;
     hipLaunchKernelGGL((dec_attention_kernel<true>), dim3(H, M), dim3(256), max_src * sizeof(float), s, w.qkv, inner, w.ckv,
                        ldckv, 2 * i * inner, (2 * i + 1) * inner, 0, (size_t)0, (const int32_t*)nullptr, 0,
-                       (const float*)nullptr, 1, 0, nb, slots, w.att, inner);
+                       (const float*)nullptr, 1, nb, slots, w.att, inner);
     if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.co, D, inner, w.x, D, s))) return st;
     // gated-GELU FFN (T5LayerFF / T5DenseGatedActDense)
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_ff, w.h, D, eps, 1.f);
@@ -1015,6 +1006,109 @@ extern "C" RpStatus rp_decoder_batch_step(RpDecoder* d, const int32_t* src_cu, i
   hipLaunchKernelGGL(dec_log_softmax_kernel, dim3(M), dim3(256), 0, s, logprobs, V);
   RP_CHECK_LAUNCH();
   return RP_OK;
+}
+
+// the caps of a slot pool: dec_check's, with every slot's source region src_cap rows long
+RpStatus pool_check(const RpDecoder* d, int n_slots, int nb, int max_len, int src_cap) {
+  RP_REQUIRE(d, "null decoder");
+  RP_REQUIRE(n_slots >= 1 && n_slots <= DEC_MAX_STATES, "slots=%d (1..%d)", n_slots, DEC_MAX_STATES);
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "num_beams=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(n_slots * nb <= DEC_MAX_ROWS, "rows = slots * num_beams = %d > %d", n_slots * nb, DEC_MAX_ROWS);
+  RP_REQUIRE(max_len >= 1 && max_len <= DEC_MAX_KEYS, "max_len=%d (1..%d)", max_len, DEC_MAX_KEYS);
+  RP_REQUIRE(src_cap >= 1 && src_cap <= DEC_MAX_KEYS, "src_cap=%d (1..%d)", src_cap, DEC_MAX_KEYS);
+  return RP_OK;
+}
+}  // namespace
+
+extern "C" RpStatus rp_decoder_batch_step(RpDecoder* d, const int32_t* src_cu, int32_t n, const int32_t* active,
+                                          int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
+                                          int32_t nb, int32_t t, int32_t max_len, float* logprobs, void* ws,
+                                          size_t ws_bytes, void* stream_) {
+  int total = 0;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
+  if (st) return st;
+  RP_REQUIRE(active && tokens && anc && logprobs, "null argument");
+  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
+  RP_REQUIRE(t >= 0 && t < max_len, "t=%d outside [0, max_len=%d)", t, max_len);
+  RP_REQUIRE(astride >= t + 1, "anc_stride=%d < t + 1 = %d", astride, t + 1);
+  DecSlots slots = {};
+  uint32_t seen = 0;
+  for (int a = 0; a < n_active; ++a) {
+    const int sidx = active[a];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share cache rows
+    seen |= 1u << sidx;
+    slots.state[a] = sidx;
+    slots.src_off[a] = src_cu[sidx];
+    slots.src_len[a] = src_cu[sidx + 1] - src_cu[sidx];
+    slots.pos[a] = t;  // all states started together
+  }
+  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
+  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  return dec_step_launch(d, w, slots, n_active, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
+}
+
+// ---- the slot pool: states that join a running search between steps ("Continuous batching") ---------
+extern "C" size_t rp_decoder_pool_workspace_bytes(const RpDecoder* d, int32_t n_slots, int32_t nb, int32_t max_len,
+                                                  int32_t src_cap) {
+  if (pool_check(d, n_slots, nb, max_len, src_cap) != RP_OK) return 0;
+  return dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, nullptr).bytes;
+}
+
+extern "C" RpStatus rp_decoder_pool_admit(RpDecoder* d, int32_t n_slots, int32_t nb, int32_t max_len, int32_t src_cap,
+                                          const int32_t* slot_ids, const void* enc, const int32_t* src_cu, int32_t m,
+                                          void* ws, size_t ws_bytes, void* stream_) {
+  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap);
+  if (st) return st;
+  RP_REQUIRE(slot_ids && enc && src_cu && ws, "null argument");
+  RP_REQUIRE(m >= 1 && m <= n_slots, "admitted sources=%d (1..slots=%d)", m, n_slots);
+  RP_REQUIRE(src_cu[0] == 0, "src_cu[0]=%d, not 0", src_cu[0]);
+  uint32_t seen = 0;
+  for (int j = 0; j < m; ++j) {
+    const int sl = slot_ids[j];
+    const int64_t S = (int64_t)src_cu[j + 1] - src_cu[j];
+    RP_REQUIRE(sl >= 0 && sl < n_slots, "slots[%d]=%d outside [0, slots=%d)", j, sl, n_slots);
+    RP_REQUIRE(!(seen & (1u << sl)), "slots[%d]=%d names a slot twice", j, sl);
+    seen |= 1u << sl;
+    RP_REQUIRE(S >= 1 && S <= src_cap, "src_len of source %d = %lld (1..src_cap=%d)", j, (long long)S, src_cap);
+  }
+  const DecWs w = dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, (char*)ws);
+  if (ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  const int D = d->cfg.d_model, NKV = d->cfg.num_layers * 2 * d->inner;
+  for (int j = 0; j < m; ++j)  // one GEMM per newcomer, into its slot's region (a row depends on no other row)
+    if ((st = launch_dec_gemm<EPI_BF16>((const bf16_t*)enc + (size_t)src_cu[j] * D, D, src_cu[j + 1] - src_cu[j],
+                                        d->cross_kv_w, NKV, D, w.ckv + (size_t)slot_ids[j] * src_cap * NKV, NKV,
+                                        (hipStream_t)stream_)))
+      return st;
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_decoder_pool_step(RpDecoder* d, int32_t n_slots, int32_t nb, int32_t max_len, int32_t src_cap,
+                                         const int32_t* active, const int32_t* pos, const int32_t* src_len,
+                                         int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
+                                         float* logprobs, void* ws, size_t ws_bytes, void* stream_) {
+  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap);
+  if (st) return st;
+  RP_REQUIRE(active && pos && src_len && tokens && anc && logprobs && ws, "null argument");
+  RP_REQUIRE(n_active >= 1 && n_active <= n_slots, "active slots=%d (1..slots=%d)", n_active, n_slots);
+  DecSlots slots = {};
+  uint32_t seen = 0;
+  for (int a = 0; a < n_active; ++a) {
+    const int sl = active[a];
+    RP_REQUIRE(sl >= 0 && sl < n_slots, "active[%d]=%d outside [0, slots=%d)", a, sl, n_slots);
+    RP_REQUIRE(!(seen & (1u << sl)), "active[%d]=%d names a slot twice", a, sl);  // two rows would share cache rows
+    seen |= 1u << sl;
+    RP_REQUIRE(pos[a] >= 0 && pos[a] < max_len, "pos[%d]=%d outside [0, max_len=%d)", a, pos[a], max_len);
+    RP_REQUIRE(src_len[a] >= 1 && src_len[a] <= src_cap, "src_len[%d]=%d (1..src_cap=%d)", a, src_len[a], src_cap);
+    RP_REQUIRE(astride >= pos[a] + 1, "anc_stride=%d < pos[%d] + 1 = %d", astride, a, pos[a] + 1);
+    slots.state[a] = sl;
+    slots.src_off[a] = sl * src_cap;
+    slots.src_len[a] = src_len[a];
+    slots.pos[a] = pos[a];
+  }
+  const DecWs w = dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, (char*)ws);
+  if (ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  return dec_step_launch(d, w, slots, n_active, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
 }
 
 extern "C" RpStatus rp_beam_select_batch(const float* lp, const float* running, int32_t n_active, int32_t nb, int32_t V,

@@ -5,7 +5,9 @@ The encoder is ``HipT5Encoder`` (``rp_encode_hidden``: last_hidden_state instead
 is ``reprover_amd.generation.beam_search_batch`` with the device top-2nb selection ``rp_beam_select_batch``.
 ``generate_many`` / ``greedy_many`` run the beams of several sources through that loop and return, per source, the bits
 of ``generate`` / ``greedy``, which are its one-state calls.  With ``sync_every=K`` the beam search keeps its books on the
-device instead (``rp_beam_books_init`` / ``rp_beam_advance``, ``generation.beam_search_batch_device``).  The
+device instead (``rp_beam_books_init`` / ``rp_beam_advance``, ``generation.beam_search_batch_device``).
+``generate_stream`` is the same search with admission: sources join a running loop between steps (``rp_decoder_pool_*``,
+``generation.BeamSearchPool``) and each returns, when it stops, the bits of ``generate``.  The
 teacher-forced loss (``forward`` / ``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.
 PyTorch tensors are containers only.
 """
@@ -21,7 +23,7 @@ import torch
 
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
-from .generation import (BeamBooks, BeamSearchOutput, SampleState, beam_search, beam_search_batch,
+from .generation import (BeamBooks, BeamSearchOutput, BeamSearchPool, SampleState, beam_search, beam_search_batch,
                          beam_search_batch_device, check_sampling, greedy_search, greedy_search_batch, sample_search_batch)
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
@@ -389,6 +391,53 @@ class HipT5Decoder:
                        "rp_decoder_batch_step")
         return out
 
+    # -- the slot pool (rp_decoder_pool_*): states join between steps, each slot at its own position ---------------------
+    def pool_open(self, n_slots: int, nb: int, max_len: int, src_cap: int) -> None:
+        """A workspace of ``n_slots`` places for searches of ``nb`` beams and ``max_len`` positions over sources of at
+        most ``src_cap`` tokens (its own allocation: ``start`` / ``start_many`` calls in between leave it alone)."""
+        need = int(self._lib.rp_decoder_pool_workspace_bytes(self._handle, n_slots, nb, max_len, src_cap))
+        if need == 0:
+            raise _lib.HipLibraryError("unsupported pool shape: " + self._lib.rp_last_error().decode(errors="replace"))
+        self._pool_ws = None  # (released before the next one is taken)
+        self._pool_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._pool = (int(n_slots), int(nb), int(max_len), int(src_cap))
+
+    def pool_admit(self, slots, enc_bf16: torch.Tensor, src_cu: np.ndarray) -> None:
+        """Cross K/V of the newcomers (enc_bf16 [sum S_j, d_model] bf16 packed, host ``src_cu [m + 1]``) into the
+        regions of ``slots`` (distinct, one per source)."""
+        assert enc_bf16.dtype == torch.bfloat16 and enc_bf16.is_contiguous()
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        cu = np.ascontiguousarray(src_cu, dtype=np.int32)
+        if len(cu) != len(sl) + 1 or enc_bf16.shape[0] != int(cu[-1]):
+            raise _lib.HipLibraryError(f"pool_admit: {len(sl)} slots, {len(cu)} src_cu entries, {enc_bf16.shape[0]} "
+                                       "encoder rows")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_pool_admit(self._handle, *self._pool, _pc(sl), enc_bf16.data_ptr(), _pc(cu),
+                                                       len(sl), self._pool_ws.data_ptr(), self._pool_ws.numel(),
+                                                       _lib.current_stream()), "rp_decoder_pool_admit")
+
+    def pool_step(self, active, pos, src_len, tokens: torch.Tensor, ancestry: torch.Tensor,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """log-probs [n_active * nb, V] of one step for the slots ``active`` (distinct), slot ``active[a]`` at position
+        ``pos[a]`` over a source of ``src_len[a]`` tokens; row ``a * nb + b`` is its beam ``b``, of whose ancestry row
+        columns ``0..pos[a]`` are read (``BeamSearchPool``'s ``step``)."""
+        nb = self._pool[1]
+        act, p, sl = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos, src_len))
+        rows, T = ancestry.shape
+        if not len(act) == len(p) == len(sl) or rows != len(act) * nb or tokens.numel() != rows:
+            raise _lib.HipLibraryError(f"pool_step: {rows} ancestry rows, {tokens.numel()} tokens, {len(p)} positions, "
+                                       f"{len(sl)} source lengths for {len(act)} slots of {nb} beams")
+        tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
+        anc = ancestry.to(device=self.device, dtype=torch.int32).contiguous()
+        if out is None:
+            out = torch.empty((rows, self.V), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_pool_step(self._handle, *self._pool, _pc(act), _pc(p), _pc(sl), len(act),
+                                                      tok.data_ptr(), anc.data_ptr(), T, out.data_ptr(),
+                                                      self._pool_ws.data_ptr(), self._pool_ws.numel(),
+                                                      _lib.current_stream()), "rp_decoder_pool_step")
+        return out
+
     def sample_step(self, log_probs: torch.Tensor, active, t: int, state: SampleState, temperature: float = 1.0,
                     top_k: int = 0, top_p: float = 1.0, eos_token_id: int = 1, pad_token_id: int = 0) -> None:
         """One token per row of ``log_probs [n_active * nb, V]`` and the rows' books in ``state``, on the device
@@ -649,6 +698,15 @@ class HipT5Generator:
                                  decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),
                                  select_many=self.decoder.select_many, device=self.device, traces=traces)
 
+    def generate_stream(self, num_beams: int, max_length: int, length_penalty: float = 1.0,
+                        n_slots: Optional[int] = None, src_cap: int = 2048) -> "GenerateStream":
+        """A running beam search that sources join while it runs (continuous batching): a
+        ``GenerateStream`` of ``n_slots`` places (default ``HipT5Decoder.max_states(num_beams)``) for sources of at most
+        ``src_cap`` tokens.  Every ticket's output is ``generate(source, num_beams, max_length, length_penalty)`` bit for
+        bit.  The decoder carries one stream at a time: opening another retires this one."""
+        return GenerateStream(self, num_beams, max_length, length_penalty,
+                              self.decoder.max_states(num_beams) if n_slots is None else n_slots, src_cap)
+
     def sample(self, ids: np.ndarray, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
                top_p: float = 1.0, seed: int = 0, length_penalty: float = 0.0, sync_every: int = 16) -> BeamSearchOutput:
         """``num_samples`` sampled continuations of one source (``sample_many`` with one state)."""
@@ -685,6 +743,65 @@ class HipT5Generator:
             n, num_samples, max_length, seeds, length_penalty, eos_token_id=eos,
             decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
             device=self.device)
+
+
+class GenerateStream:
+    """``HipT5Generator.generate_stream``'s object: ``generation.BeamSearchPool`` over the decoder's slot pool.
+    ``submit(ids)`` queues a source and returns its ticket; ``step()`` admits what fits (the newcomers encoded together,
+    one packed encoder pass), takes one decode step and returns the ``(ticket, BeamSearchOutput)`` pairs that finished;
+    ``drain()`` steps until the stream is idle.  ``in_flight`` / ``queued`` / ``steps`` are the pool's."""
+
+    def __init__(self, generator: HipT5Generator, num_beams: int, max_length: int, length_penalty: float, n_slots: int,
+                 src_cap: int):
+        self.generator, self.src_cap = generator, int(src_cap)
+        dec = self.decoder = generator.decoder
+        dec.pool_open(n_slots, num_beams, max_length, src_cap)
+        dec._pool_owner = self
+        self._src_len = [0] * int(n_slots)  # per slot: the source length of its tenant
+        cfg = generator.cfg
+        self.pool = BeamSearchPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
+                                   eos_token_id=cfg.get("eos_token_id", 1),
+                                   decoder_start_token_id=cfg.get("decoder_start_token_id", 0),
+                                   select_many=dec.select_many, device=generator.device)
+
+    def _mine(self) -> HipT5Decoder:
+        if getattr(self.decoder, "_pool_owner", None) is not self:
+            raise RuntimeError("this stream was retired: the decoder's slot pool was opened again")
+        return self.decoder
+
+    def _admit(self, slots, sources) -> None:
+        cu = np.concatenate([[0], np.cumsum([len(x) for x in sources])]).astype(np.int32)
+        enc = self.generator.encode_hidden_packed(np.concatenate(sources), cu)
+        self._mine().pool_admit(slots, enc, cu)
+        for s, x in zip(slots, sources):
+            self._src_len[s] = len(x)
+
+    def _step(self, active, pos, tokens, ancestry) -> torch.Tensor:
+        return self._mine().pool_step(active, pos, [self._src_len[s] for s in active], tokens, ancestry)
+
+    def submit(self, ids) -> int:
+        ids = np.asarray(ids, dtype=np.int32).reshape(-1)
+        if not 1 <= ids.size <= self.src_cap:
+            raise ValueError(f"a source of {ids.size} tokens does not fit the stream's src_cap={self.src_cap} (1..src_cap)")
+        return self.pool.submit(ids)
+
+    def step(self) -> List[Tuple[int, BeamSearchOutput]]:
+        return self.pool.step()
+
+    def drain(self) -> List[Tuple[int, BeamSearchOutput]]:
+        return self.pool.drain()
+
+    @property
+    def in_flight(self) -> int:
+        return self.pool.in_flight
+
+    @property
+    def queued(self) -> int:
+        return self.pool.queued
+
+    @property
+    def steps(self) -> int:
+        return self.pool.steps
 
 
 class HipSeq2SeqGradients:

@@ -31,6 +31,9 @@ reorder, so the ancestry table is the identity, and the finished flags are read 
 the device, ``advance`` (``rp_beam_advance``) updates it after every step, and the stop flags are read every
 ``sync_every`` positions.  ``beam_advance_host`` restates that kernel on host tensors with its stable order (the kernel's
 oracle, and the ``advance`` of a CPU run).  ``beam_search_batch`` with its host books stays the default.
+
+``BeamSearchPool`` is ``beam_search_batch``'s loop with admission: sources are submitted while it runs, each takes a free
+slot between two steps and is stepped at its own position, and its output is returned at the step where it stops.
 """
 from __future__ import annotations
 
@@ -204,6 +207,109 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
     if traces is not None:
         traces.extend(per_state)
     return [st.result() for st in states]
+
+
+# ---- continuous batching: states join a running search between steps -------------------------------------------------------
+POOL_MUTANTS = ("shared_position",)
+
+
+class BeamSearchPool:
+    """``beam_search_batch``'s loop opened up: ``n_slots`` places, each carrying one source's search (a ``_BeamState``)
+    at its own position.  ``submit`` queues a source; every ``step`` first admits queued sources into the free slots,
+    then runs one decode step and one selection over the slots in use, reads the selected triples back once, advances
+    every state's books and frees the slots of the states that stopped.  A ticket's output is ``beam_search``'s for that
+    source alone, whatever else is in flight and whenever it joined: a row's log-probs depend on its own state and
+    position only, and selection reads no position.
+
+    - ``admit(slots, sources)``: make the engine ready to step ``sources[j]`` in slot ``slots[j]`` (encode, cross K/V);
+      one call for all newcomers of a step.
+    - ``step(active, pos, tokens, ancestry) -> log_probs``: ``active`` the slots in use (ascending), ``pos[a]`` the
+      position of slot ``active[a]``; row ``a * nb + b`` of ``tokens [n_active * nb]`` / ``ancestry [n_active * nb, W]``
+      is beam ``b`` of that slot, ``W`` the widest ``pos + 1`` of the step, a narrower slot's rows right-padded with
+      zeros (columns ``0..pos[a]`` are its own).  Returns ``[n_active * nb, vocab]``.
+    - ``select_many(log_probs, running_scores, nb, k)``: as in ``beam_search_batch``.
+
+    ``steps`` counts the decode steps taken.  ``mutant`` plants a known bug (``POOL_MUTANTS``: "shared_position" hands
+    every slot the step's largest position, the uniform-``t`` engine's assumption) so that tests can show a comparison
+    would notice it."""
+
+    def __init__(self, admit: Callable, step: Callable, n_slots: int, num_beams: int, max_length: int,
+                 length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
+                 num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
+                 mutant: Optional[str] = None):
+        assert mutant is None or mutant in POOL_MUTANTS, mutant
+        if int(n_slots) < 1 or int(num_beams) < 1:
+            raise ValueError(f"n_slots={n_slots} and num_beams={num_beams} must be >= 1")
+        if max_length <= 1:
+            raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+        self._admit, self._step, self._select_many = admit, step, select_many
+        self.n_slots, self.nb, self.device, self.mutant = int(n_slots), int(num_beams), device, mutant
+        self._new_state = lambda: _BeamState(num_beams, max_length, length_penalty, eos_token_id, decoder_start_token_id,
+                                             num_return_sequences)
+        self._queue: List[Tuple[int, object]] = []               # (ticket, source), first in first out
+        self._slots: List[Optional[Tuple[int, _BeamState]]] = [None] * self.n_slots  # (ticket, books) per slot in use
+        self._next_ticket = 0
+        self.steps = 0
+
+    @property
+    def queued(self) -> int:
+        return len(self._queue)
+
+    @property
+    def in_flight(self) -> int:
+        return sum(s is not None for s in self._slots)
+
+    def submit(self, source) -> int:
+        """Queue a source; its ticket names it in ``step``'s return."""
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        self._queue.append((ticket, source))
+        return ticket
+
+    def step(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """Admit what fits, take one decode step, return the ``(ticket, output)`` pairs of the states that stopped."""
+        free = [s for s in range(self.n_slots) if self._slots[s] is None]  # ascending: the lowest free slots first
+        take = min(len(free), len(self._queue))
+        if take:
+            new, self._queue = self._queue[:take], self._queue[take:]
+            self._admit(free[:take], [src for _, src in new])
+            for s, (ticket, _) in zip(free, new):
+                self._slots[s] = (ticket, self._new_state())
+        active = [s for s in range(self.n_slots) if self._slots[s] is not None]
+        if not active:
+            return []
+        nb = self.nb
+        states = [self._slots[s][1] for s in active]
+        ins = [st.inputs() for st in states]
+        pos = [st.cur_len - 1 for st in states]
+        width = max(pos) + 1
+        tokens = torch.cat([x[0] for x in ins])
+        ancestry = torch.zeros((len(active) * nb, width), dtype=torch.int64)
+        for a, (_, anc) in enumerate(ins):
+            ancestry[a * nb : (a + 1) * nb, : anc.shape[1]] = anc
+        running = torch.cat([st.running_scores for st in states])
+        if self.device is not None:
+            tokens, ancestry, running = tokens.to(self.device), ancestry.to(self.device), running.to(self.device)
+        if self.mutant == "shared_position":
+            pos = [max(pos)] * len(pos)
+        log_probs = self._step(list(active), pos, tokens, ancestry)
+        vals, toks, parents = self._select_many(log_probs, running, nb, 2 * nb)
+        vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
+        self.steps += 1
+        done = []
+        for a, s in enumerate(active):
+            ticket, st = self._slots[s]
+            if st.advance(vals[a], toks[a], parents[a]):
+                done.append((ticket, st.result()))
+                self._slots[s] = None
+        return done
+
+    def drain(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """Step until nothing is queued or in flight; every pair that finished on the way, in finishing order."""
+        out = []
+        while self._queue or self.in_flight:
+            out.extend(self.step())
+        return out
 
 
 # ---- beam search with its books on the device ------------------------------------------------------------------------------

@@ -6,7 +6,8 @@ with ``PremiseRetriever`` and generates from the augmented state.  No ``transfor
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+import asyncio
+from typing import Dict, List, Optional, Tuple
 
 from ..common import Pos, format_augmented_state, remove_marks, zip_strict
 from ..decoder import HipT5Generator
@@ -34,11 +35,17 @@ class HuggingFaceGenerator(TacticGenerator):
     state differ, and ``batch_generate_sync([a, b])`` equals ``generate_sync(a)`` then ``generate_sync(b)``.
 
     ``beam_sync_every`` (an integer >= 1; default None): the beam search keeps its books on the device and looks at the
-    states' stop flags every that many positions (``HipT5Generator.generate_many(sync_every=...)``); same outputs."""
+    states' stop flags every that many positions (``HipT5Generator.generate_many(sync_every=...)``); same outputs.
+
+    ``continuous=True`` (beam search only): concurrent ``await generate(...)`` calls share one running decode loop
+    (``HipT5Generator.generate_stream``, ``continuous_slots`` places, default the engine's cap).  A call joins the loop
+    between two steps and returns as soon as its own state stops, with ``generate_sync``'s result.  One driver
+    coroutine steps the loop while anything is queued or in flight and yields to the event loop between steps."""
 
     def __init__(self, model_path: str, device, max_inp_seq_len: int, max_oup_seq_len: int, length_penalty: float,
                  template: str = "%s", do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
-                 top_p: float = 1.0, seed: int = 0, beam_sync_every: Optional[int] = None):
+                 top_p: float = 1.0, seed: int = 0, beam_sync_every: Optional[int] = None, continuous: bool = False,
+                 continuous_slots: Optional[int] = None):
         self.model_path = model_path
         self.device = device
         self.max_inp_seq_len = max_inp_seq_len
@@ -53,6 +60,15 @@ class HuggingFaceGenerator(TacticGenerator):
         self.beam_sync_every = beam_sync_every
         # the default leaves the beam-search calls exactly as they were
         self._books = {} if beam_sync_every is None else {"sync_every": int(beam_sync_every)}
+        if continuous and do_sample:
+            raise ValueError("continuous=True serves beam search only: it cannot be combined with do_sample=True")
+        if continuous_slots is not None and (int(continuous_slots) != continuous_slots or continuous_slots < 1):
+            raise ValueError(f"continuous_slots={continuous_slots} must be an integer >= 1 (or None)")
+        self.continuous, self.continuous_slots = bool(continuous), continuous_slots
+        self._stream = None       # the open GenerateStream and its num_samples
+        self._stream_beams: Optional[int] = None
+        self._waiters: Dict[int, "asyncio.Future"] = {}  # ticket -> the generate() call that awaits it
+        self._driver: Optional["asyncio.Task"] = None
 
     def _next_seeds(self, n: int) -> List[int]:
         """The 32-bit seeds of the next ``n`` served states (murmur3's finaliser over seed + golden-ratio steps)."""
@@ -99,10 +115,14 @@ class HuggingFaceGenerator(TacticGenerator):
         if self.do_sample:
             return self._sampled([ids], num_samples)[0]
         out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty, **self._books)
+        return self._suggestions(out, num_samples)
+
+    def _suggestions(self, out, num_samples: int) -> List[Tuple[str, float]]:
+        """A beam search's output as (tactic, score) pairs: decoded, marks removed, de-duplicated in order (:227-243)."""
         raw_output_text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
         raw_scores = out.sequences_scores.tolist()
         output_text, output_score = [], []
-        for j in range(num_samples):  # :227-243
+        for j in range(num_samples):
             t = remove_marks(raw_output_text[j])
             if t not in output_text:
                 output_text.append(t)
@@ -111,7 +131,43 @@ class HuggingFaceGenerator(TacticGenerator):
 
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
                        num_samples: int) -> List[Tuple[str, float]]:
-        return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+        if not self.continuous:
+            return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+        ids = encode_one(self.template % state, self.max_inp_seq_len)
+        # a stream serves one num_samples: a call with another waits until it has drained (the driver runs meanwhile)
+        while self._stream is not None and self._stream_beams != num_samples and (self._stream.queued
+                                                                                  or self._stream.in_flight):
+            await asyncio.sleep(0)
+        if self._stream is None or self._stream_beams != num_samples:
+            self._stream = self.generator.generate_stream(num_samples, self.max_oup_seq_len, self.length_penalty,
+                                                          n_slots=self.continuous_slots, src_cap=self.max_inp_seq_len)
+            self._stream_beams = num_samples
+        future = asyncio.get_running_loop().create_future()
+        self._waiters[self._stream.submit(ids)] = future
+        if self._driver is None:
+            self._driver = asyncio.ensure_future(self._drive())
+        return self._suggestions(await future, num_samples)
+
+    async def _drive(self) -> None:
+        """Step the open stream while it has work, resolving the waiting calls as their states finish; an exception
+        reaches every call that waits.  Between steps the event loop runs, so that other calls can submit (or, once the
+        stream is idle, open the next one: the loop looks at ``self._stream`` afresh every time)."""
+        try:
+            while self._stream is not None and (self._stream.queued or self._stream.in_flight):
+                for ticket, out in self._stream.step():
+                    future = self._waiters.pop(ticket)
+                    if not future.done():  # (a cancelled call)
+                        future.set_result(out)
+                if self._stream.queued or self._stream.in_flight:  # (idle: end now, before any waiter wakes)
+                    await asyncio.sleep(0)
+        except Exception as exc:  # the stream's state is unknown now: fail the waiters and open a fresh one next time
+            waiters, self._waiters = self._waiters, {}
+            self._stream = self._stream_beams = None
+            for future in waiters.values():
+                if not future.done():
+                    future.set_exception(exc)
+        finally:
+            self._driver = None
 
     def batch_generate_sync(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
                             theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:
@@ -125,16 +181,7 @@ class HuggingFaceGenerator(TacticGenerator):
         for i in range(0, len(ids), cap):
             outs = self.generator.generate_many(ids[i : i + cap], num_samples, self.max_oup_seq_len,
                                                 self.length_penalty, **self._books)
-            for out in outs:
-                raw_output_text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
-                raw_scores = out.sequences_scores.tolist()
-                output_text, output_score = [], []
-                for j in range(num_samples):
-                    t = remove_marks(raw_output_text[j])
-                    if t not in output_text:
-                        output_text.append(t)
-                        output_score.append(raw_scores[j])
-                results.append(list(zip_strict(output_text, output_score)))
+            results.extend(self._suggestions(out, num_samples) for out in outs)
         return results
 
     async def batch_generate(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
@@ -148,7 +195,8 @@ class RetrievalAugmentedGenerator(TacticGenerator):
     def __init__(self, gen_path: str, ret_path: str, indexed_corpus_path: str, device, max_inp_seq_len: int,
                  max_oup_seq_len: int, length_penalty: float, max_num_retrieved: int, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
-                 beam_sync_every: Optional[int] = None) -> None:
+                 beam_sync_every: Optional[int] = None, continuous: bool = False,
+                 continuous_slots: Optional[int] = None) -> None:
         self.gen_path = gen_path
         self.ret_path = ret_path
         self.indexed_corpus_path = indexed_corpus_path
@@ -159,7 +207,8 @@ class RetrievalAugmentedGenerator(TacticGenerator):
         self.max_num_retrieved = max_num_retrieved
         self.hf_gen = HuggingFaceGenerator(gen_path, device, max_inp_seq_len, max_oup_seq_len, length_penalty,
                                            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
-                                           seed=seed, beam_sync_every=beam_sync_every)
+                                           seed=seed, beam_sync_every=beam_sync_every, continuous=continuous,
+                                           continuous_slots=continuous_slots)
 
     def initialize(self) -> None:
         self.hf_gen.initialize()
@@ -175,7 +224,12 @@ class RetrievalAugmentedGenerator(TacticGenerator):
 
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
                        num_samples: int) -> List[Tuple[str, float]]:
-        return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+        if not self.hf_gen.continuous:
+            return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+        retrieved_premises, _ = self.retriever.retrieve(state, file_path, theorem_full_name, theorem_pos,
+                                                        self.max_num_retrieved)
+        aug_state = format_augmented_state(state, retrieved_premises, self.max_inp_seq_len)
+        return await self.hf_gen.generate(aug_state, file_path, theorem_full_name, theorem_pos, num_samples)
 
     def batch_generate_sync(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
                             theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:

@@ -23,6 +23,13 @@ repetition the host-books call twice (the difference of its own two runs is the 
 and per-step milliseconds of each, and whether every device-books output equals the host-books one.
 
     python tools/gen_bench.py --states 1 8 --sync-every 1 4 16 [--reps 2] [--out FILE]
+
+``--stream``: continuous batching.  16 queued sources of mixed lengths (64 beams, max_length 512) served by
+``generate_many`` in chunks of 8 and by a ``generate_stream`` of 8 slots, in one process, alternating: whole-call
+milliseconds of both, every search's own step count, the stream's finish step per source, and whether the outputs are
+equal.  Where every search runs to ``max_length`` the two do the same work and the figure says nothing about admission.
+
+    python tools/gen_bench.py --stream [--reps 2] [--out FILE]
 """
 from __future__ import annotations
 
@@ -179,6 +186,53 @@ def sample_bench(gen, cfg, reps, nb=64, max_len=512, src_bytes=2048):
             "launches_per_step": {"beam": 12 * L + 4 + 2, "sample": 12 * L + 4 + 1}}
 
 
+def stream_bench(gen, cfg, reps, nb=64, max_len=512, n_src=16, n_slots=8):
+    """16 queued sources of mixed lengths served (a) by ``generate_many`` in chunks of ``n_slots`` and (b) by a stream of
+    ``n_slots`` slots, alternating in one process; the per-source finish step beside the times.  The stream can only win
+    where states stop at different steps: ``finish_steps_differ`` says whether they did."""
+    rng = np.random.default_rng(0)
+    lens = [int(x) for x in rng.integers(64, 2049, size=n_src)]
+    srcs = [np.concatenate([rng.integers(3, 259, size=n - 1), [1]]).astype(np.int32) for n in lens]
+    L = cfg["num_decoder_layers"]
+    gen.generate_many(srcs[:2], nb, 8, 0.0)  # warm-up: code objects
+    warm = gen.generate_stream(nb, 8, 0.0, n_slots=2, src_cap=2048)
+    warm.submit(srcs[0])
+    warm.drain()
+
+    def chunks():
+        outs, steps = [], []
+        for i in range(0, n_src, n_slots):
+            tr = []
+            outs += gen.generate_many(srcs[i : i + n_slots], nb, max_len, 0.0, traces=tr)
+            steps += [len(t) for t in tr]
+        return outs, steps
+
+    def stream():
+        st = gen.generate_stream(nb, max_len, 0.0, n_slots=n_slots, src_cap=2048)
+        tickets = [st.submit(s) for s in srcs]
+        got, finish = {}, {}
+        while st.queued or st.in_flight:
+            for ticket, out in st.step():
+                got[ticket], finish[ticket] = out, st.steps
+        return [got[t] for t in tickets], [finish[t] for t in tickets], st.steps
+
+    chunk_ms, stream_ms, same = [], [], True
+    for _ in range(reps):
+        ms, (a, own_steps) = _timed(chunks)
+        chunk_ms.append(ms)
+        ms, (b, finish, total) = _timed(stream)
+        stream_ms.append(ms)
+        same = same and _same(a, b)
+    chunk_steps = sum(max(own_steps[i : i + n_slots]) for i in range(0, n_src, n_slots))
+    return {"metric": "gen_stream_bench", "beams": nb, "max_length": max_len, "length_penalty": 0.0, "sources": n_src,
+            "slots": n_slots, "config": f"byt5-small ({L} decoder layers), sources of {min(lens)}..{max(lens)} bytes",
+            "source_bytes": lens, "reps": reps, "chunked_generate_many_ms": [round(x, 1) for x in chunk_ms],
+            "stream_ms": [round(x, 1) for x in stream_ms],
+            "ratio_chunked_over_stream": round(min(chunk_ms) / min(stream_ms), 3),
+            "steps_of_each_search": own_steps, "stream_finish_step": finish, "chunked_decode_steps": chunk_steps,
+            "stream_decode_steps": total, "finish_steps_differ": len(set(own_steps)) > 1, "outputs_identical": same}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -187,13 +241,14 @@ def main(argv=None):
                     help="with --states: device-books generate_many at these sync_every values against the host books")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--sample", action="store_true", help="the sampled call beside the beam-search prover call")
+    ap.add_argument("--stream", action="store_true", help="a stream of 8 slots against generate_many in chunks of 8")
     args = ap.parse_args(argv)
     if args.sync_every and (not args.states or min(args.sync_every) < 1):
         ap.error("--sync-every takes values >= 1 and goes with --states")
-    if args.sample:
+    if args.sample or args.stream:
         cfg = synth.seq2seq_config("byt5-small")
         gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
-        line = json.dumps(sample_bench(gen, cfg, max(args.reps, 2)))
+        line = json.dumps(stream_bench(gen, cfg, args.reps) if args.stream else sample_bench(gen, cfg, max(args.reps, 2)))
         print(line)
         if args.out:
             with open(args.out, "w") as fh:
