@@ -731,13 +731,38 @@ RpStatus rp_decoder_pool_step(RpDecoder* dec, int32_t n_slots, int32_t num_beams
  * fin_div, run_div: (t + 1) ** length_penalty, rounded to fp32 by the caller.
  * RP_E_INVALID (nothing is launched): null pointers, nb outside 1..64, n outside 1..32, more than 1024
  * rows, max_len outside 2..8192, active not distinct or outside [0, n), t + 1 >= max_len, bytes below
- * rp_beam_books_bytes. */
+ * rp_beam_books_bytes.
+ *
+ * The slot pool's books (rp_decoder_pool_*: state index = slot place, n = n_slots), a position per slot.  `active` /
+ * `pos` are HOST int32 [n_active]: the slots in use in listing order (row a * nb + b of the by-row parts is beam b of
+ * slot active[a]) and the position each stands at; `states` is HOST int32 [m].
+ * rp_beam_books_admit: rp_beam_books_init's values for the listed states only (one device routine serves both): every
+ * by-state part of those states over all max_len columns in both pair members (the previous tenant wrote them, and the
+ * 16-byte gathers of an advance copy up to three columns past t + 1), scores, flags, heur 1, done 0, steps 0.  Nothing
+ * of another state and nothing by row is touched.
+ * rp_beam_pool_advance: rp_beam_advance with slot a's t = pos[a] throughout (the pair member read, the column written,
+ * the ancestry entry (pos[a] + 1) * nb + r, the max_len test, fin_len, steps) and its own divisors fin_div[a] /
+ * run_div[a] (HOST float [n_active], the caller's (pos[a] + 1) ** length_penalty).  One kernel: rp_beam_advance is the
+ * call in which every slot has pos = t.
+ * rp_beam_books_rows: the by-row inputs (tokens, running, anc_rows) of rows a * nb + b from the by-state parts of
+ * state active[a]: its current pair member pos[a] & 1, the token in column pos[a] of run_seq, the whole ancestry row.
+ * Needed whenever the active list changes (admission, departure); by-state and by-row parts are disjoint.
+ * RP_E_INVALID (nothing is launched): as above, and states / active not distinct or outside [0, n), m or n_active
+ * outside 1..n, a pos outside [0, max_len - 2]. */
 size_t   rp_beam_books_bytes(int32_t n, int32_t nb, int32_t max_len);
 RpStatus rp_beam_books_init(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len, int32_t eos,
                             int32_t start_token, void* stream);
 RpStatus rp_beam_advance(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len, const int32_t* active,
                          int32_t n_active, int32_t t, const float* scores, const int32_t* tokens,
                          const int32_t* parents, float fin_div, float run_div, int32_t eos, void* stream);
+RpStatus rp_beam_books_admit(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len, const int32_t* states,
+                             int32_t m, int32_t eos, int32_t start_token, void* stream);
+RpStatus rp_beam_pool_advance(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len, const int32_t* active,
+                              const int32_t* pos, int32_t n_active, const float* scores, const int32_t* tokens,
+                              const int32_t* parents, const float* fin_div, const float* run_div, int32_t eos,
+                              void* stream);
+RpStatus rp_beam_books_rows(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len, const int32_t* active,
+                            const int32_t* pos, int32_t n_active, void* stream);
 
 /* Sampled generation ("Sampling"): after rp_decoder_batch_step, one launch draws one
  * token per row (row = slot * nb + sample, the step's layout) from logprobs [n_active * nb, vocab] and

@@ -339,6 +339,15 @@ SIGNATURES = {
         [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
          C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p],
     ),
+    "rp_beam_books_admit": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_void_p]),
+    "rp_beam_pool_advance": (
+        C.c_int32,
+        [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
+    ),
+    "rp_beam_books_rows": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_void_p]),
     "rp_set_option": (C.c_int32, [C.c_char_p, C.c_int32]),
     "rp_profile_enable": (C.c_int32, [C.c_int32]),
     "rp_profile_read": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -13,7 +13,10 @@
 // rp_decoder_pool_step is that sequence with a position per slot (the batched call: every slot at t), over a workspace
 // whose slots states enter between steps (rp_decoder_pool_admit): continuous batching.
 // rp_sample_step (sampling) and rp_beam_books_init / rp_beam_advance (beam search) keep a search's bookkeeping on the
-// device, one more launch per step, so that the host loop reads nothing back per position.
+// device, one more launch per step, so that the host loop reads nothing back per position.  rp_beam_pool_advance is
+// rp_beam_advance with a position per slot (one kernel: the uniform call has every slot at t), and rp_beam_books_admit /
+// rp_beam_books_rows give a slot's next tenant fresh books and rebuild the by-row inputs when the active list changes:
+// the slot pool's books.
 //
 // Every output element of every kernel here is computed by a reduction whose order depends only on the shapes (K, the
 // key count), never on which other rows share the launch or where the row sits in it: a row's log-probs are the same
@@ -481,9 +484,12 @@ BeamBooks books_carve(char* base, int n, int nb, int max_len) {
 
 constexpr float BEAM_NEG = -1.0e9f;  // generation.py's NEG (exact in fp32)
 
-// _BeamState.__init__ for state blockIdx.x, slot = state (the first step's active list is 0 .. n - 1)
-__global__ __launch_bounds__(256) void beam_books_init_kernel(BeamBooks bk, int n, int nb, int ld, int eos, int start) {
-  const int state = blockIdx.x, tid = threadIdx.x;
+// _BeamState.__init__ for one state, by one workgroup: every by-state part over all ld columns, both pair members.  ROWS:
+// the by-row inputs of slot = state as well (rp_beam_books_init: the first step's active list is 0 .. n - 1); without it
+// nothing by row and nothing of another state is touched (rp_beam_books_admit: a slot's next tenant).
+template <bool ROWS>
+__device__ __forceinline__ void beam_state_init(const BeamBooks& bk, int n, int nb, int ld, int state, int eos, int start) {
+  const int tid = threadIdx.x;
   for (int i = tid; i < nb * ld; i += 256) {
     const int r = i / ld, c = i - r * ld;
     const int tok = c == 0 ? start : eos, id = c * nb + r;
@@ -493,21 +499,35 @@ __global__ __launch_bounds__(256) void beam_books_init_kernel(BeamBooks bk, int 
       bk.fin_seq[at] = tok;
       bk.anc[at] = id;
     }
-    bk.anc_rows[(size_t)state * nb * ld + i] = id;
+    if (ROWS) bk.anc_rows[(size_t)state * nb * ld + i] = id;
   }
   for (int r = tid; r < nb; r += 256) {
     const size_t at = (size_t)state * nb + r;
-    bk.run_scores[at] = bk.running[at] = r == 0 ? 0.f : BEAM_NEG;
+    const float run = r == 0 ? 0.f : BEAM_NEG;
+    bk.run_scores[at] = run;
     bk.beam_scores[at] = BEAM_NEG;
     bk.fin_flag[at] = 0;
     bk.fin_len[at] = 0;
-    bk.tokens[at] = start;
+    if (ROWS) {
+      bk.running[at] = run;
+      bk.tokens[at] = start;
+    }
   }
   if (tid == 0) {
     bk.heur[state] = 1;
     bk.done[state] = 0;
     bk.steps[state] = 0;
   }
+}
+
+__global__ __launch_bounds__(256) void beam_books_init_kernel(BeamBooks bk, int n, int nb, int ld, int eos, int start) {
+  beam_state_init<true>(bk, n, nb, ld, blockIdx.x, eos, start);
+}
+
+// the states listed in slots.state[0 .. gridDim.x), one workgroup each
+__global__ __launch_bounds__(256) void beam_books_admit_kernel(BeamBooks bk, int n, int nb, int ld, DecSlots slots, int eos,
+                                                               int start) {
+  beam_state_init<false>(bk, n, nb, ld, slots.state[blockIdx.x], eos, start);
 }
 
 // W int32 moved as one access (W = 4: 16 bytes, rows of a multiple of 4 columns)
@@ -554,16 +574,21 @@ __device__ __forceinline__ void beam_gather(const BeamBooks& bk, size_t src, siz
 // _BeamState.advance for the state in slot blockIdx.x, from the step's 2 nb selected triples (generation.py:92-130; the
 // numbered comments are include/reprover_hip.h's).  fp32, one rounding per operation, the reference's order.  Both
 // selections rank by counting in rp_beam_select's total order: descending, equal scores (-0.0 == +0.0) to the lower index.
-__global__ __launch_bounds__(256) void beam_advance_kernel(BeamBooks bk, int n, int nb, int ld, DecSlots slots, int t,
+// The slot's position t = slots.pos[slot] and its two divisors travel by value (rp_beam_advance: one t for every slot).
+struct BeamDivs {
+  float fin[DEC_MAX_STATES], run[DEC_MAX_STATES];
+};
+
+__global__ __launch_bounds__(256) void beam_advance_kernel(BeamBooks bk, int n, int nb, int ld, DecSlots slots, BeamDivs divs,
                                                            const float* __restrict__ scores,
                                                            const int32_t* __restrict__ tokens,
-                                                           const int32_t* __restrict__ parents, float fin_div,
-                                                           float run_div, int eos) {
+                                                           const int32_t* __restrict__ parents, int eos) {
   __shared__ float s_run[2 * DEC_MAX_BEAMS], s_m[3 * DEC_MAX_BEAMS], s_score[DEC_MAX_BEAMS];
   __shared__ int s_tok[2 * DEC_MAX_BEAMS], s_par[2 * DEC_MAX_BEAMS], s_hit[2 * DEC_MAX_BEAMS];
   __shared__ int s_nxt[DEC_MAX_BEAMS], s_sel[DEC_MAX_BEAMS], s_kflag[DEC_MAX_BEAMS], s_klen[DEC_MAX_BEAMS];
   __shared__ int s_flag[DEC_MAX_BEAMS], s_frozen;
-  const int tid = threadIdx.x, slot = blockIdx.x, state = slots.state[slot], K = 2 * nb;
+  const int tid = threadIdx.x, slot = blockIdx.x, state = slots.state[slot], t = slots.pos[slot], K = 2 * nb;
+  const float fin_div = divs.fin[slot], run_div = divs.run[slot];
   const size_t srow = (size_t)state * nb;
   if (tid == 0) s_frozen = bk.done[state];
   __syncthreads();
@@ -630,6 +655,25 @@ __global__ __launch_bounds__(256) void beam_advance_kernel(BeamBooks bk, int n, 
     bk.heur[state] = heur;
     bk.done[state] = !heur || all;
     bk.steps[state] = t + 1;
+  }
+}
+
+// The by-row inputs of slot blockIdx.x from the by-state parts of its state: the state's current pair member
+// (slots.pos[slot] & 1), the whole ancestry row, the token in column pos.  By-state and by-row parts are disjoint.
+__global__ __launch_bounds__(256) void beam_books_rows_kernel(BeamBooks bk, int n, int nb, int ld, DecSlots slots) {
+  const int tid = threadIdx.x, slot = blockIdx.x, state = slots.state[slot], t = slots.pos[slot];
+  const size_t src = ((size_t)((t & 1) * n + state) * nb) * ld, dst = (size_t)slot * nb * ld;
+  if (ld % 4 == 0) {
+    typedef BookPack<4> P;
+    const P* a = reinterpret_cast<const P*>(bk.anc + src);
+    P* d = reinterpret_cast<P*>(bk.anc_rows + dst);
+    for (int i = tid; i < nb * (ld / 4); i += 256) d[i] = a[i];
+  } else {
+    for (int i = tid; i < nb * ld; i += 256) bk.anc_rows[dst + i] = bk.anc[src + i];
+  }
+  for (int r = tid; r < nb; r += 256) {
+    bk.tokens[(size_t)slot * nb + r] = bk.run_seq[src + (size_t)r * ld + t];
+    bk.running[(size_t)slot * nb + r] = bk.run_scores[(size_t)state * nb + r];
   }
 }
 
@@ -1194,6 +1238,35 @@ extern "C" RpStatus rp_beam_books_init(void* books, size_t bytes, int32_t n, int
   return RP_OK;
 }
 
+namespace {
+// The slot list of a books launch: active[a] distinct and in [0, n), slot a at position pos[a] (null: t for all).
+RpStatus books_slots(DecSlots* slots, const int32_t* active, const int32_t* pos, int t, int n_active, int n, int max_len) {
+  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
+  uint32_t seen = 0;
+  for (int a = 0; a < n_active; ++a) {
+    const int sidx = active[a], p = pos ? pos[a] : t;
+    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share books
+    RP_REQUIRE(p >= 0 && p + 1 < max_len, "pos[%d]=%d: position pos + 1 outside [1, max_len=%d)", a, p, max_len);
+    seen |= 1u << sidx;
+    slots->state[a] = sidx;
+    slots->pos[a] = p;
+  }
+  return RP_OK;
+}
+
+RpStatus books_advance(void* books, size_t bytes, int n, int nb, int max_len, const DecSlots& slots, const BeamDivs& divs,
+                       int n_active, const float* scores, const int32_t* tokens, const int32_t* parents, int eos,
+                       void* stream_) {
+  const BeamBooks bk = books_carve((char*)books, n, nb, max_len);
+  RP_REQUIRE(bytes >= bk.bytes, "books %zu < required %zu bytes", bytes, bk.bytes);
+  hipLaunchKernelGGL(beam_advance_kernel, dim3(n_active), dim3(256), 0, (hipStream_t)stream_, bk, n, nb, max_len, slots, divs,
+                     scores, tokens, parents, eos);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+}  // namespace
+
 extern "C" RpStatus rp_beam_advance(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len,
                                     const int32_t* active, int32_t n_active, int32_t t, const float* scores,
                                     const int32_t* tokens, const int32_t* parents, float fin_div, float run_div,
@@ -1204,18 +1277,65 @@ extern "C" RpStatus rp_beam_advance(void* books, size_t bytes, int32_t n, int32_
   RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
   RP_REQUIRE(t >= 0 && t + 1 < max_len, "t=%d: position t + 1 outside [1, max_len=%d)", t, max_len);
   DecSlots slots = {};
-  uint32_t seen = 0;
+  BeamDivs divs = {};
+  if ((st = books_slots(&slots, active, nullptr, t, n_active, n, max_len))) return st;
   for (int a = 0; a < n_active; ++a) {
-    const int sidx = active[a];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share books
+    divs.fin[a] = fin_div;
+    divs.run[a] = run_div;
+  }
+  return books_advance(books, bytes, n, nb, max_len, slots, divs, n_active, scores, tokens, parents, eos, stream_);
+}
+
+extern "C" RpStatus rp_beam_pool_advance(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len,
+                                         const int32_t* active, const int32_t* pos, int32_t n_active, const float* scores,
+                                         const int32_t* tokens, const int32_t* parents, const float* fin_div,
+                                         const float* run_div, int32_t eos, void* stream_) {
+  RpStatus st = books_check(n, nb, max_len);
+  if (st) return st;
+  RP_REQUIRE(books && active && pos && scores && tokens && parents && fin_div && run_div, "null argument");
+  DecSlots slots = {};
+  BeamDivs divs = {};
+  if ((st = books_slots(&slots, active, pos, 0, n_active, n, max_len))) return st;
+  for (int a = 0; a < n_active; ++a) {
+    divs.fin[a] = fin_div[a];
+    divs.run[a] = run_div[a];
+  }
+  return books_advance(books, bytes, n, nb, max_len, slots, divs, n_active, scores, tokens, parents, eos, stream_);
+}
+
+extern "C" RpStatus rp_beam_books_admit(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len,
+                                        const int32_t* states, int32_t m, int32_t eos, int32_t start_token, void* stream_) {
+  RpStatus st = books_check(n, nb, max_len);
+  if (st) return st;
+  RP_REQUIRE(books && states, "null argument");
+  RP_REQUIRE(m >= 1 && m <= n, "admitted states=%d (1..states=%d)", m, n);
+  DecSlots slots = {};
+  uint32_t seen = 0;
+  for (int j = 0; j < m; ++j) {
+    const int sidx = states[j];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "states[%d]=%d outside [0, states=%d)", j, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "states[%d]=%d names a state twice", j, sidx);
     seen |= 1u << sidx;
-    slots.state[a] = sidx;
+    slots.state[j] = sidx;
   }
   const BeamBooks bk = books_carve((char*)books, n, nb, max_len);
   RP_REQUIRE(bytes >= bk.bytes, "books %zu < required %zu bytes", bytes, bk.bytes);
-  hipLaunchKernelGGL(beam_advance_kernel, dim3(n_active), dim3(256), 0, (hipStream_t)stream_, bk, n, nb, max_len, slots, t,
-                     scores, tokens, parents, fin_div, run_div, eos);
+  hipLaunchKernelGGL(beam_books_admit_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream_, bk, n, nb, max_len, slots, eos,
+                     start_token);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_beam_books_rows(void* books, size_t bytes, int32_t n, int32_t nb, int32_t max_len,
+                                       const int32_t* active, const int32_t* pos, int32_t n_active, void* stream_) {
+  RpStatus st = books_check(n, nb, max_len);
+  if (st) return st;
+  RP_REQUIRE(books && active && pos, "null argument");
+  DecSlots slots = {};
+  if ((st = books_slots(&slots, active, pos, 0, n_active, n, max_len))) return st;
+  const BeamBooks bk = books_carve((char*)books, n, nb, max_len);
+  RP_REQUIRE(bytes >= bk.bytes, "books %zu < required %zu bytes", bytes, bk.bytes);
+  hipLaunchKernelGGL(beam_books_rows_kernel, dim3(n_active), dim3(256), 0, (hipStream_t)stream_, bk, n, nb, max_len, slots);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }

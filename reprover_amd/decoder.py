@@ -7,7 +7,9 @@ is ``reprover_amd.generation.beam_search_batch`` with the device top-2nb selecti
 of ``generate`` / ``greedy``, which are its one-state calls.  With ``sync_every=K`` the beam search keeps its books on the
 device instead (``rp_beam_books_init`` / ``rp_beam_advance``, ``generation.beam_search_batch_device``).
 ``generate_stream`` is the same search with admission: sources join a running loop between steps (``rp_decoder_pool_*``,
-``generation.BeamSearchPool``) and each returns, when it stops, the bits of ``generate``.  The
+``generation.BeamSearchPool``) and each returns, when it stops, the bits of ``generate``; with ``sync_every=K`` the
+stream's books live on the device too (``rp_beam_books_admit`` / ``rp_beam_pool_advance`` / ``rp_beam_books_rows``,
+``generation.BeamBooksPool``).  The
 teacher-forced loss (``forward`` / ``label_log_probs``) is ``rp_decoder_forward`` over all pairs of a batch at once.
 PyTorch tensors are containers only.
 """
@@ -23,8 +25,9 @@ import torch
 
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
-from .generation import (BeamBooks, BeamSearchOutput, BeamSearchPool, SampleState, beam_search, beam_search_batch,
-                         beam_search_batch_device, check_sampling, greedy_search, greedy_search_batch, sample_search_batch)
+from .generation import (BeamBooks, BeamBooksPool, BeamSearchOutput, BeamSearchPool, SampleState, beam_search,
+                         beam_search_batch, beam_search_batch_device, check_sampling, greedy_search, greedy_search_batch,
+                         sample_search_batch)
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
 # Dropout sites of the training step (include/reprover_hip.h RP_DROP_SITE_*; ``rp_dbg_dropout_mask`` reads a site's mask).
@@ -489,6 +492,48 @@ class HipT5Decoder:
                                                  tokens.data_ptr(), parents.data_ptr(), fin_div, run_div, eos_token_id,
                                                  _lib.current_stream()), "rp_beam_advance")
 
+    # -- the slot pool's books: a position per slot (``generation.BeamBooksPool``'s callables) ---------------------------
+    def beam_books_admit(self, books: BeamBooks, states, eos_token_id: int = 1, decoder_start_token_id: int = 0) -> None:
+        """``_BeamState.__init__``'s values in the by-state parts of ``states`` only (``rp_beam_books_admit``)."""
+        st = np.ascontiguousarray(states, dtype=np.int32)
+        assert books.block.is_cuda
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_beam_books_admit(books.block.data_ptr(), books.nbytes, books.n, books.nb,
+                                                     books.max_len, _pc(st), len(st), eos_token_id,
+                                                     decoder_start_token_id, _lib.current_stream()), "rp_beam_books_admit")
+
+    def beam_pool_advance(self, books: BeamBooks, active, pos, scores: torch.Tensor, tokens: torch.Tensor,
+                          parents: torch.Tensor, fin_div, run_div, eos_token_id: int = 1) -> None:
+        """``beam_advance`` with slot ``active[a]`` at its own position ``pos[a]`` and its own divisors
+        (``rp_beam_pool_advance``).  Nothing is read back."""
+        act, p = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos))
+        fd, rd = (np.ascontiguousarray(x, dtype=np.float32) for x in (fin_div, run_div))
+        want = (len(act), 2 * books.nb)
+        for x, dt in ((scores, torch.float32), (tokens, torch.int32), (parents, torch.int32)):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == dt, "rp_beam_pool_advance takes contiguous device tensors"
+            if tuple(x.shape) != want:
+                raise _lib.HipLibraryError(f"beam_pool_advance: triples of shape {tuple(x.shape)} for {want}")
+        if not len(p) == len(fd) == len(rd) == len(act):
+            raise _lib.HipLibraryError(f"beam_pool_advance: {len(p)} positions, {len(fd)} / {len(rd)} divisors for "
+                                       f"{len(act)} slots")
+        assert books.block.is_cuda
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_beam_pool_advance(books.block.data_ptr(), books.nbytes, books.n, books.nb,
+                                                      books.max_len, _pc(act), _pc(p), len(act), scores.data_ptr(),
+                                                      tokens.data_ptr(), parents.data_ptr(), _pc(fd), _pc(rd),
+                                                      eos_token_id, _lib.current_stream()), "rp_beam_pool_advance")
+
+    def beam_books_rows(self, books: BeamBooks, active, pos) -> None:
+        """The by-row inputs of the slots ``active`` (in that order) from their by-state parts (``rp_beam_books_rows``)."""
+        act, p = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos))
+        if len(act) != len(p):
+            raise _lib.HipLibraryError(f"beam_books_rows: {len(p)} positions for {len(act)} slots")
+        assert books.block.is_cuda
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_beam_books_rows(books.block.data_ptr(), books.nbytes, books.n, books.nb,
+                                                    books.max_len, _pc(act), _pc(p), len(act), _lib.current_stream()),
+                       "rp_beam_books_rows")
+
     def select_many(self, log_probs: torch.Tensor, running: torch.Tensor, nb: int, k: int):
         """Per state the device top-k of its own ``[nb * V]`` block (``rp_beam_select_batch``): scores, tokens, parents,
         each ``[n_active, k]``, parents local to the state."""
@@ -699,13 +744,25 @@ class HipT5Generator:
                                  select_many=self.decoder.select_many, device=self.device, traces=traces)
 
     def generate_stream(self, num_beams: int, max_length: int, length_penalty: float = 1.0,
-                        n_slots: Optional[int] = None, src_cap: int = 2048) -> "GenerateStream":
+                        n_slots: Optional[int] = None, src_cap: int = 2048,
+                        sync_every: Optional[int] = None) -> "GenerateStream":
         """A running beam search that sources join while it runs (continuous batching): a
         ``GenerateStream`` of ``n_slots`` places (default ``HipT5Decoder.max_states(num_beams)``) for sources of at most
         ``src_cap`` tokens.  Every ticket's output is ``generate(source, num_beams, max_length, length_penalty)`` bit for
-        bit.  The decoder carries one stream at a time: opening another retires this one."""
+        bit.  The decoder carries one stream at a time: opening another retires this one.
+
+        ``sync_every`` (an integer >= 1; the default None is the host-books pool): the slots' books live on the device
+        (``generation.BeamBooksPool``, ``rp_beam_pool_advance``), nothing is uploaded or read back per step, and the
+        stop flags are read every ``sync_every`` steps.  The same outputs; with ``sync_every = K > 1`` a result is
+        delivered, and its slot taken again, up to ``K - 1`` steps after its state stopped."""
+        if sync_every is not None:
+            if int(sync_every) != sync_every or sync_every < 1:
+                raise ValueError(f"sync_every={sync_every} must be an integer >= 1 (or None)")
+            if max_length <= 1:
+                raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+            sync_every = int(sync_every)
         return GenerateStream(self, num_beams, max_length, length_penalty,
-                              self.decoder.max_states(num_beams) if n_slots is None else n_slots, src_cap)
+                              self.decoder.max_states(num_beams) if n_slots is None else n_slots, src_cap, sync_every)
 
     def sample(self, ids: np.ndarray, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
                top_p: float = 1.0, seed: int = 0, length_penalty: float = 0.0, sync_every: int = 16) -> BeamSearchOutput:
@@ -749,16 +806,26 @@ class GenerateStream:
     """``HipT5Generator.generate_stream``'s object: ``generation.BeamSearchPool`` over the decoder's slot pool.
     ``submit(ids)`` queues a source and returns its ticket; ``step()`` admits what fits (the newcomers encoded together,
     one packed encoder pass), takes one decode step and returns the ``(ticket, BeamSearchOutput)`` pairs that finished;
-    ``drain()`` steps until the stream is idle.  ``in_flight`` / ``queued`` / ``steps`` are the pool's."""
+    ``drain()`` steps until the stream is idle.  ``in_flight`` / ``queued`` / ``steps`` are the pool's.  With
+    ``sync_every`` the pool is ``generation.BeamBooksPool``: the books on the device, the pairs delivered at its sync
+    points."""
 
     def __init__(self, generator: HipT5Generator, num_beams: int, max_length: int, length_penalty: float, n_slots: int,
-                 src_cap: int):
+                 src_cap: int, sync_every: Optional[int] = None):
         self.generator, self.src_cap = generator, int(src_cap)
         dec = self.decoder = generator.decoder
         dec.pool_open(n_slots, num_beams, max_length, src_cap)
         dec._pool_owner = self
         self._src_len = [0] * int(n_slots)  # per slot: the source length of its tenant
         cfg = generator.cfg
+        if sync_every is not None:
+            self.pool = BeamBooksPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
+                                      eos_token_id=cfg.get("eos_token_id", 1),
+                                      decoder_start_token_id=cfg.get("decoder_start_token_id", 0),
+                                      select_many=dec.select_many, device=generator.device, sync_every=sync_every,
+                                      books_admit=dec.beam_books_admit, advance=dec.beam_pool_advance,
+                                      rows=dec.beam_books_rows)
+            return
         self.pool = BeamSearchPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
                                    eos_token_id=cfg.get("eos_token_id", 1),
                                    decoder_start_token_id=cfg.get("decoder_start_token_id", 0),

@@ -34,6 +34,9 @@ oracle, and the ``advance`` of a CPU run).  ``beam_search_batch`` with its host 
 
 ``BeamSearchPool`` is ``beam_search_batch``'s loop with admission: sources are submitted while it runs, each takes a free
 slot between two steps and is stepped at its own position, and its output is returned at the step where it stops.
+``BeamBooksPool`` is that pool with the books in a ``BeamBooks`` block of ``n_slots`` states: a position per slot
+(``rp_beam_pool_advance``), the stop flags read every ``sync_every`` steps, results delivered at those sync points.
+``beam_books_admit_host``, ``beam_pool_advance_host`` and ``beam_books_rows_host`` restate its three kernels.
 """
 from __future__ import annotations
 
@@ -402,6 +405,70 @@ def _stable_top(x: torch.Tensor, k: int) -> List[int]:
 BEAM_ADVANCE_MUTANTS = ("late_candidates_finish", "heuristic_not_sticky", "ancestry_not_reordered", "done_not_frozen")
 
 
+POOL_BOOKS_MUTANTS = ("shared_position", "admit_not_reset")
+
+
+def _state_init_host(books: BeamBooks, s: int, eos_token_id: int, decoder_start_token_id: int, tables: bool = True) -> None:
+    """``_BeamState.__init__``'s values in the by-state parts of state ``s`` (the device routine ``rp_beam_books_init``
+    and ``rp_beam_books_admit`` share)."""
+    nb, L = books.nb, books.max_len
+    if tables:
+        for tab in (books.run_seq, books.fin_seq):
+            tab[:, s] = eos_token_id
+            tab[:, s, :, 0] = decoder_start_token_id
+        books.anc[:, s] = (torch.arange(L, dtype=torch.int32)[None] * nb + torch.arange(nb, dtype=torch.int32)[:, None])
+    books.run_scores[s] = NEG
+    books.run_scores[s, 0] = 0.0
+    books.beam_scores[s] = NEG
+    books.fin_flag[s] = 0
+    books.fin_len[s] = 0
+    books.heur[s] = 1
+    books.done[s] = 0
+    books.steps[s] = 0
+
+
+def beam_books_admit_host(books: BeamBooks, states: Sequence[int], eos_token_id: int, decoder_start_token_id: int,
+                          mutant: Optional[str] = None) -> None:
+    """``rp_beam_books_admit`` on host books: ``beam_books_init_host``'s values for ``states`` only - every by-state part
+    of those states over all ``max_len`` columns, both pair members (a previous tenant wrote them).  Nothing by row and
+    nothing of another state is touched.  ``mutant`` "admit_not_reset" (``POOL_BOOKS_MUTANTS``): the row tables of a
+    state that was used before stay as its last tenant left them."""
+    assert mutant is None or mutant in POOL_BOOKS_MUTANTS, mutant
+    assert len(set(states)) == len(states) and all(0 <= s < books.n for s in states)
+    for s in states:
+        used = int(books.steps[s]) > 0
+        _state_init_host(books, s, eos_token_id, decoder_start_token_id,
+                         tables=not (mutant == "admit_not_reset" and used))
+
+
+def beam_books_rows_host(books: BeamBooks, active: Sequence[int], pos: Sequence[int]) -> None:
+    """``rp_beam_books_rows`` on host books: the by-row inputs (``tokens``, ``running``, ``anc_rows``) of rows
+    ``a * nb + b`` from the by-state parts of state ``active[a]``, read at its current pair member ``pos[a] & 1`` and
+    column ``pos[a]`` of ``run_seq``."""
+    nb, L = books.nb, books.max_len
+    assert len(active) == len(pos) and len(set(active)) == len(active) and all(0 <= s < books.n for s in active)
+    assert all(0 <= p <= L - 2 for p in pos)
+    for a, (s, p) in enumerate(zip(active, pos)):
+        books.anc_rows[a * nb : (a + 1) * nb] = books.anc[p & 1, s]
+        books.tokens[a * nb : (a + 1) * nb] = books.run_seq[p & 1, s, :, p]
+        books.running[a * nb : (a + 1) * nb] = books.run_scores[s]
+
+
+def beam_pool_advance_host(books: BeamBooks, active: Sequence[int], pos: Sequence[int], scores: torch.Tensor,
+                           tokens: torch.Tensor, parents: torch.Tensor, fin_div: Sequence[float],
+                           run_div: Sequence[float], eos_token_id: int, mutant: Optional[str] = None) -> None:
+    """``rp_beam_pool_advance`` on host books: ``beam_advance_host`` with slot ``a`` at its own position ``pos[a]`` and
+    with its own divisors ``fin_div[a]`` / ``run_div[a]``.  ``mutant``: ``BEAM_ADVANCE_MUTANTS`` joined by "+", or
+    "shared_position" (``POOL_BOOKS_MUTANTS``: every slot handed the step's largest position)."""
+    assert len(pos) == len(active) == len(fin_div) == len(run_div)
+    mutants = set(mutant.split("+")) if mutant else set()
+    if "shared_position" in mutants:
+        mutants.discard("shared_position")
+        pos = [max(pos)] * len(pos)
+    assert mutants <= set(BEAM_ADVANCE_MUTANTS), mutant
+    _advance_host(books, active, pos, scores, tokens, parents, fin_div, run_div, eos_token_id, mutants)
+
+
 def beam_advance_host(books: BeamBooks, active: Sequence[int], t: int, scores: torch.Tensor, tokens: torch.Tensor,
                       parents: torch.Tensor, fin_div: float, run_div: float, eos_token_id: int,
                       mutant: Optional[str] = None) -> None:
@@ -414,16 +481,27 @@ def beam_advance_host(books: BeamBooks, active: Sequence[int], t: int, scores: t
     of ``BEAM_ADVANCE_MUTANTS`` or several joined by "+") so that tests can show a comparison would notice them."""
     mutants = set(mutant.split("+")) if mutant else set()
     assert mutants <= set(BEAM_ADVANCE_MUTANTS), mutant
+    k = len(active)
+    _advance_host(books, active, [t] * k, scores, tokens, parents, [fin_div] * k, [run_div] * k, eos_token_id, mutants)
+
+
+def _advance_host(books: BeamBooks, active: Sequence[int], pos: Sequence[int], scores: torch.Tensor, tokens: torch.Tensor,
+                  parents: torch.Tensor, fin_divs: Sequence[float], run_divs: Sequence[float], eos_token_id: int,
+                  mutants: set) -> None:
+    """The one body of ``beam_advance_host`` and ``beam_pool_advance_host``, as the kernel is one: slot ``a`` at position
+    ``pos[a]``."""
     n, nb, L = books.n, books.nb, books.max_len
-    assert 0 <= t and t + 1 < L and len(set(active)) == len(active) and all(0 <= s < n for s in active)
+    assert len(set(active)) == len(active) and all(0 <= s < n for s in active)
+    assert all(0 <= t and t + 1 < L for t in pos)
     K = 2 * nb
     f32 = lambda x: torch.tensor(x, dtype=torch.float32)  # noqa: E731
-    cur, new = t & 1, (t & 1) ^ 1
     width = 4 if L % 4 == 0 else 1  # the kernel moves rows in units of `width` columns
-    ncol = (t + 2 + width - 1) // width * width
     for slot, s in enumerate(active):
         if int(books.done[s]) and "done_not_frozen" not in mutants:
             continue
+        t, fin_div, run_div = pos[slot], fin_divs[slot], run_divs[slot]
+        cur, new = t & 1, (t & 1) ^ 1
+        ncol = (t + 2 + width - 1) // width * width
         val = scores[slot].to(torch.float32).cpu()
         tok = tokens[slot].to(torch.int32).cpu()
         par = parents[slot].to(torch.int64).cpu().clamp(0, nb - 1)
@@ -523,6 +601,166 @@ def beam_search_batch_device(step_many: Callable, select_many: Callable, advance
             active = still
     host = BeamBooks(n, nb, max_length, block=to_host(books.block))
     return [host.result(i, nret) for i in range(n)]
+
+
+class BeamBooksPool:
+    """``BeamSearchPool`` with the books on the device: ``n_slots`` places, state index = slot place, one ``BeamBooks``
+    block of ``n_slots`` states, a position per slot kept on the host.  Per ``step`` it runs one engine ``step``, one
+    ``select_many`` and one ``advance``; nothing is uploaded but their arguments and the host ``active`` / ``pos`` lists,
+    and nothing is read back.  A ticket's output is ``beam_search``'s for that source alone.
+
+    At a *sync point* it (1) reads the ``done`` flags once, (2) reads the results of the states that stopped - their own
+    ``fin_seq`` rows of the current member, ``beam_scores``, ``fin_len`` and ``steps``, gathered on the device into one
+    buffer - (3) frees their slots, (4) admits queued sources into the lowest free slots (``admit``, then
+    ``books_admit``) and (5), if the active list changed, runs ``rows``.  So at most two device-to-host copies per sync
+    point, all through ``to_host``.  A sync point occurs after every ``sync_every`` steps since the last one, before a
+    step whenever something is queued and a slot is known to be free, and at the step where the pool starts from idle
+    (nothing is in flight then and nothing is read).  ``sync_points`` counts them.
+
+    The trade-off: with ``sync_every = K > 1`` a result is delivered, and its slot taken again, up to ``K - 1`` steps
+    after its state stopped.  Meanwhile the stopped slot is still stepped and ``advance`` leaves its books as they are.
+    ``K = 1`` still removes the ancestry upload and the host ``advance`` and reads ``n_slots`` flags per step.  No launch
+    carries ``pos + 1 >= max_length``: a slot that has advanced at ``max_length - 2`` is certainly done and is stepped
+    at ``max_length - 2`` again until the next sync point.
+
+    - ``admit(slots, sources)``: as in ``BeamSearchPool``.
+    - ``step(active, pos, tokens, ancestry) -> log_probs``: ``tokens`` int32 ``[n_active * nb]`` and ``ancestry`` int32
+      ``[n_active * nb, max_length]`` (columns ``0..pos[a]`` of slot ``active[a]``'s rows are read) are views of the
+      books' by-row parts.
+    - ``select_many(log_probs, running, nb, k)``: as in ``beam_search_batch``.
+    - ``books_admit(books, states, eos, start)``: ``rp_beam_books_admit`` (default ``beam_books_admit_host``).
+    - ``advance(books, active, pos, scores, tokens, parents, fin_div, run_div, eos)``: ``rp_beam_pool_advance``
+      (``beam_pool_advance_host``); the divisors are per-slot lists.
+    - ``rows(books, active, pos)``: ``rp_beam_books_rows`` (``beam_books_rows_host``).
+    - ``to_host(x)``: every device-to-host copy.
+
+    ``mutant`` (``POOL_BOOKS_MUTANTS``) plants a known bug in the host defaults."""
+
+    def __init__(self, admit: Callable, step: Callable, n_slots: int, num_beams: int, max_length: int,
+                 length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
+                 num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
+                 sync_every: int = 16, books_admit: Optional[Callable] = None, advance: Optional[Callable] = None,
+                 rows: Optional[Callable] = None, to_host: Callable = lambda x: x.cpu(), mutant: Optional[str] = None):
+        assert mutant is None or mutant in POOL_BOOKS_MUTANTS, mutant
+        if int(n_slots) < 1 or int(num_beams) < 1:
+            raise ValueError(f"n_slots={n_slots} and num_beams={num_beams} must be >= 1")
+        if max_length <= 1:
+            raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+        if int(sync_every) != sync_every or sync_every < 1:
+            raise ValueError(f"sync_every={sync_every} must be an integer >= 1")
+        self.n_slots, self.nb, self.max_length = int(n_slots), int(num_beams), int(max_length)
+        self.nret = self.nb if num_return_sequences is None else int(num_return_sequences)
+        if not 1 <= self.nret <= self.nb:
+            raise ValueError(f"num_return_sequences={self.nret} outside 1..num_beams={self.nb}")
+        self.sync_every, self.length_penalty = int(sync_every), length_penalty
+        self.eos, self.start = eos_token_id, decoder_start_token_id
+        self._admit, self._step, self._select_many, self._to_host = admit, step, select_many, to_host
+        self._books_admit = books_admit or (lambda bk, states, eos, start: beam_books_admit_host(
+            bk, states, eos, start, mutant="admit_not_reset" if mutant == "admit_not_reset" else None))
+        self._advance = advance or (lambda bk, *a: beam_pool_advance_host(
+            bk, *a, mutant="shared_position" if mutant == "shared_position" else None))
+        self._rows = rows or beam_books_rows_host
+        self.books = BeamBooks(self.n_slots, self.nb, self.max_length, device=device)  # every state is admitted before use
+        self._queue: List[Tuple[int, object]] = []                   # (ticket, source), first in first out
+        self._ticket: List[Optional[int]] = [None] * self.n_slots    # per slot: its tenant's ticket
+        self._pos = [0] * self.n_slots                               # per slot: the position of its next step
+        self._active: List[int] = []                                 # the slots in use, ascending: the by-row order
+        self._next_ticket = 0
+        self._since = 0                                              # steps since the last sync point
+        self.steps = 0
+        self.sync_points = 0
+
+    @property
+    def queued(self) -> int:
+        return len(self._queue)
+
+    @property
+    def in_flight(self) -> int:
+        return sum(t is not None for t in self._ticket)
+
+    def submit(self, source) -> int:
+        """Queue a source; its ticket names it in ``step``'s return."""
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        self._queue.append((ticket, source))
+        return ticket
+
+    def _results(self, stopped: List[int]) -> List[Tuple[int, BeamSearchOutput]]:
+        """``BeamBooks.result`` of the stopped states from one buffer gathered on the device: per state its ``nret``
+        ``fin_seq`` rows of the current member, ``beam_scores`` (as bits), ``fin_len``, ``steps``."""
+        bk, nret, L = self.books, self.nret, self.max_length
+        idx = torch.tensor(stopped, dtype=torch.int64, device=bk.block.device)
+        steps = bk.steps[idx]
+        buf = torch.cat([bk.fin_seq[(steps & 1).long(), idx, :nret].reshape(len(stopped), nret * L),
+                         bk.beam_scores[idx, :nret].view(torch.int32), bk.fin_len[idx, :nret], steps[:, None]], dim=1)
+        host = self._to_host(buf)
+        out = []
+        for j, s in enumerate(stopped):
+            max_generated = int(host[j, nret * L + nret : nret * L + 2 * nret].max())
+            seq = host[j, : nret * L].view(nret, L)[:, : 1 + max_generated].long().clone()
+            scores = host[j, nret * L : nret * L + nret].clone().view(torch.float32)
+            out.append((self._ticket[s], BeamSearchOutput(seq, scores)))
+        return out
+
+    def _sync(self) -> List[Tuple[int, BeamSearchOutput]]:
+        self.sync_points += 1
+        self._since = 0
+        out: List[Tuple[int, BeamSearchOutput]] = []
+        changed = False
+        if self._active:
+            done = self._to_host(self.books.done)
+            stopped = [s for s in self._active if bool(done[s])]
+            if stopped:
+                out = self._results(stopped)
+                for s in stopped:
+                    self._ticket[s] = None
+                changed = True
+        free = [s for s in range(self.n_slots) if self._ticket[s] is None]  # ascending: the lowest free slots first
+        take = min(len(free), len(self._queue))
+        if take:
+            new, self._queue = self._queue[:take], self._queue[take:]
+            self._admit(free[:take], [src for _, src in new])
+            self._books_admit(self.books, free[:take], self.eos, self.start)
+            for s, (ticket, _) in zip(free, new):
+                self._ticket[s], self._pos[s] = ticket, 0
+            changed = True
+        self._active = [s for s in range(self.n_slots) if self._ticket[s] is not None]
+        if changed and self._active:
+            self._rows(self.books, list(self._active), [self._pos[s] for s in self._active])
+        return out
+
+    def step(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """One decode step, with a sync point before it when a queued source can take a free slot and one after it
+        when ``sync_every`` steps have passed; the ``(ticket, output)`` pairs those sync points delivered."""
+        out: List[Tuple[int, BeamSearchOutput]] = []
+        if self._queue and self.in_flight < self.n_slots:
+            out.extend(self._sync())
+        if not self._active:
+            return out
+        bk, nb, prompt_len = self.books, self.nb, 1
+        active = list(self._active)
+        pos = [self._pos[s] for s in active]
+        rows = len(active) * nb
+        log_probs = self._step(active, pos, bk.tokens[:rows], bk.anc_rows[:rows])
+        vals, toks, parents = self._select_many(log_probs, bk.running[:rows], nb, 2 * nb)
+        # _BeamState.advance's two divisors at cur_len = pos + 1, as beam_search_batch_device computes them
+        fin_div = [float((p + 1 + 1 - prompt_len) ** self.length_penalty) for p in pos]
+        run_div = [float((p + 2 - prompt_len) ** self.length_penalty) for p in pos]
+        self._advance(bk, active, pos, vals, toks, parents, fin_div, run_div, self.eos)
+        self.steps += 1
+        self._since += 1
+        for s, p in zip(active, pos):
+            self._pos[s] = min(p + 1, self.max_length - 2)  # (past max_length - 2 the state is done: its books are frozen)
+        if self._since >= self.sync_every:
+            out.extend(self._sync())
+        return out
+
+    def drain(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """Step until nothing is queued or in flight; every pair that was delivered on the way, in delivery order."""
+        out = []
+        while self._queue or self.in_flight:
+            out.extend(self.step())
+        return out
 
 
 def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], max_length: int, eos_token_id: int = 1,

@@ -40,7 +40,9 @@ class HuggingFaceGenerator(TacticGenerator):
     ``continuous=True`` (beam search only): concurrent ``await generate(...)`` calls share one running decode loop
     (``HipT5Generator.generate_stream``, ``continuous_slots`` places, default the engine's cap).  A call joins the loop
     between two steps and returns as soon as its own state stops, with ``generate_sync``'s result.  One driver
-    coroutine steps the loop while anything is queued or in flight and yields to the event loop between steps."""
+    coroutine steps the loop while anything is queued or in flight and yields to the event loop between steps.  With
+    ``beam_sync_every=K`` as well, the stream keeps its books on the device (``generate_stream(sync_every=K)``): the same
+    results, each returned up to ``K - 1`` steps after its state stopped."""
 
     def __init__(self, model_path: str, device, max_inp_seq_len: int, max_oup_seq_len: int, length_penalty: float,
                  template: str = "%s", do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
@@ -140,7 +142,8 @@ class HuggingFaceGenerator(TacticGenerator):
             await asyncio.sleep(0)
         if self._stream is None or self._stream_beams != num_samples:
             self._stream = self.generator.generate_stream(num_samples, self.max_oup_seq_len, self.length_penalty,
-                                                          n_slots=self.continuous_slots, src_cap=self.max_inp_seq_len)
+                                                          n_slots=self.continuous_slots, src_cap=self.max_inp_seq_len,
+                                                          **self._books)
             self._stream_beams = num_samples
         future = asyncio.get_running_loop().create_future()
         self._waiters[self._stream.submit(ids)] = future

@@ -30,6 +30,15 @@ milliseconds of both, every search's own step count, the stream's finish step pe
 equal.  Where every search runs to ``max_length`` the two do the same work and the figure says nothing about admission.
 
     python tools/gen_bench.py --stream [--reps 2] [--out FILE]
+
+``--stream --sync-every K [K ...]``: the stream with its books on the device (``generate_stream(sync_every=K)``) beside
+the host-books stream of the same tree, in one process, alternating: per repetition the host-books stream twice (the
+difference of its own two runs is the spread), then one device-books stream per K.  Whole-call milliseconds, decode steps
+and sync points of each, whether every output equals the host-books one, and per K whether a speed-up may be claimed
+(every device-books run below the host-books stream's fastest run minus its largest spread).  As above: where every search
+runs to ``max_length`` the run measures the per-step host cost and says nothing about admission.
+
+    python tools/gen_bench.py --stream --sync-every 1 4 16 [--reps 2] [--out FILE]
 """
 from __future__ import annotations
 
@@ -233,22 +242,68 @@ def stream_bench(gen, cfg, reps, nb=64, max_len=512, n_src=16, n_slots=8):
             "stream_decode_steps": total, "finish_steps_differ": len(set(own_steps)) > 1, "outputs_identical": same}
 
 
+def stream_books_bench(gen, cfg, sync_every, reps, nb=64, max_len=512, n_src=16, n_slots=8):
+    """``stream_bench``'s 16 queued sources through a stream of ``n_slots`` slots with host books (the baseline, twice per
+    repetition) and with device books at every ``sync_every``, alternating in one process."""
+    rng = np.random.default_rng(0)
+    lens = [int(x) for x in rng.integers(64, 2049, size=n_src)]
+    srcs = [np.concatenate([rng.integers(3, 259, size=n - 1), [1]]).astype(np.int32) for n in lens]
+    L = cfg["num_decoder_layers"]
+
+    def stream(n, length, sources, **kw):
+        st = gen.generate_stream(nb, length, 0.0, n_slots=n, src_cap=2048, **kw)
+        tickets = [st.submit(s) for s in sources]
+        got = dict(st.drain())
+        return [got[t] for t in tickets], st.steps, getattr(st.pool, "sync_points", None)
+
+    stream(2, 8, srcs[:1])  # warm-up: code objects
+    stream(2, 8, srcs[:1], sync_every=2)
+    host_ms, dev_ms, same, host_steps = [], {k: [] for k in sync_every}, True, 0
+    dev_steps, dev_syncs = {}, {}
+    for _ in range(reps):
+        pair = []
+        for _ in range(2):
+            ms, (want, host_steps, _) = _timed(lambda: stream(n_slots, max_len, srcs))
+            pair.append(ms)
+        host_ms.append(pair)
+        for k in sync_every:
+            ms, (got, dev_steps[k], dev_syncs[k]) = _timed(lambda: stream(n_slots, max_len, srcs, sync_every=k))
+            dev_ms[k].append(ms)
+            same = same and _same(got, want)
+    best = min(min(p) for p in host_ms)
+    spread = max(abs(p[0] - p[1]) for p in host_ms)
+    return {"metric": "gen_stream_books_bench", "beams": nb, "max_length": max_len, "length_penalty": 0.0, "sources": n_src,
+            "slots": n_slots, "config": f"byt5-small ({L} decoder layers), sources of {min(lens)}..{max(lens)} bytes",
+            "reps": reps, "host_books_stream_ms": [[round(x, 1) for x in p] for p in host_ms],
+            "host_books_spread_ms": [round(abs(p[0] - p[1]), 1) for p in host_ms], "host_books_decode_steps": host_steps,
+            "device_books_stream_ms": {str(k): [round(x, 1) for x in v] for k, v in dev_ms.items()},
+            "device_books_decode_steps": {str(k): v for k, v in dev_steps.items()},
+            "device_books_sync_points": {str(k): v for k, v in dev_syncs.items()},
+            "ratio_host_over_device": {str(k): round(best / min(v), 3) for k, v in dev_ms.items()},
+            "speedup_claimed": {str(k): bool(max(v) < best - spread) for k, v in dev_ms.items()},
+            "outputs_identical": same}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--states", type=int, nargs="+", default=None, help="batched generation against the per-state loop")
     ap.add_argument("--sync-every", type=int, nargs="+", default=None,
-                    help="with --states: device-books generate_many at these sync_every values against the host books")
+                    help="with --states: device-books generate_many at these sync_every values against the host books; "
+                         "with --stream: the device-books stream against the host-books stream")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--sample", action="store_true", help="the sampled call beside the beam-search prover call")
     ap.add_argument("--stream", action="store_true", help="a stream of 8 slots against generate_many in chunks of 8")
     args = ap.parse_args(argv)
-    if args.sync_every and (not args.states or min(args.sync_every) < 1):
-        ap.error("--sync-every takes values >= 1 and goes with --states")
+    if args.sync_every and (not (args.states or args.stream) or args.sample or min(args.sync_every) < 1):
+        ap.error("--sync-every takes values >= 1 and goes with --states or --stream")
     if args.sample or args.stream:
         cfg = synth.seq2seq_config("byt5-small")
         gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
-        line = json.dumps(stream_bench(gen, cfg, args.reps) if args.stream else sample_bench(gen, cfg, max(args.reps, 2)))
+        if args.stream and args.sync_every:
+            line = json.dumps(stream_books_bench(gen, cfg, args.sync_every, args.reps))
+        else:
+            line = json.dumps(stream_bench(gen, cfg, args.reps) if args.stream else sample_bench(gen, cfg, max(args.reps, 2)))
         print(line)
         if args.out:
             with open(args.out, "w") as fh:
