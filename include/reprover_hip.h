@@ -797,6 +797,36 @@ RpStatus rp_sample_step(const float* logprobs, int32_t vocab, const int32_t* act
  * sample the row's index inside its state, position the step's t: nothing else enters. */
 float    rp_sample_uniform(uint32_t seed, uint32_t sample, uint32_t position);
 
+/* The slot pool's sampler ("Continuous batching for sampling"): rp_sample_step's books for
+ * rp_decoder_pool_*, state index = slot place and n = n_slots, a position per slot.  The books stay the separate
+ * caller-owned device arrays above (seeds, seq, cum_logprob, n_generated, finished by state; tokens_next by row).
+ * `active` / `pos` are HOST int32 [n_active]: the slots in use in listing order (row a * nb + b is sample b of slot
+ * active[a]) and the position each stands at; `states` is HOST int32 [m] and `new_seeds` HOST uint32 [m] (both travel
+ * as kernel arguments).  None of the three takes a workspace.
+ * rp_sample_pool_step: rp_sample_step with slot a's t = pos[a] throughout: u = rp_sample_uniform(seeds[state], sample,
+ * pos[a]), the token goes to column pos[a] + 1.  One kernel: rp_sample_step is the call in which every slot has pos = t.
+ * rp_sample_pool_admit: a slot's next tenant.  For the listed states only: seeds[s] = new_seeds[i]; every seq row of the
+ * state pad over ALL max_len columns with the start token in column 0 (the previous tenant wrote them, and a result is
+ * trimmed by n_generated, not by content); cum_logprob 0, n_generated 0, finished 0.  Nothing of another state and
+ * nothing by row is touched.
+ * rp_sample_pool_rows: tokens_next[a * nb + b] = seq[active[a], b, pos[a]], the by-row input of the next
+ * rp_decoder_pool_step.  Needed whenever the active list changes (admission, departure).  That step's ancestry is the
+ * identity table [n_slots * nb, max_len] with entry [r, p] = p * nb + r % nb, built once: it depends on r % nb only, so
+ * its first n_active * nb rows serve any active list.
+ * RP_E_INVALID (nothing is launched): everything rp_sample_step refuses (max_len < 2 included), and a null pos, a
+ * pos[a] outside [0, max_len - 2], states / active not distinct or outside [0, n), m or n_active outside 1..n, more
+ * than 1024 listed rows. */
+RpStatus rp_sample_pool_step(const float* logprobs, int32_t vocab, const int32_t* active, const int32_t* pos,
+                             int32_t n_active, int32_t n, int32_t nb, const uint32_t* seeds, int32_t max_len,
+                             float temperature, int32_t top_k, float top_p, int32_t eos, int32_t pad, int32_t* seq,
+                             int32_t* tokens_next, float* cum_logprob, int32_t* n_generated, int32_t* finished,
+                             void* stream);
+RpStatus rp_sample_pool_admit(const int32_t* states, const uint32_t* new_seeds, int32_t m, int32_t n, int32_t nb,
+                              int32_t max_len, int32_t start_token, int32_t pad, uint32_t* seeds, int32_t* seq,
+                              float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream);
+RpStatus rp_sample_pool_rows(const int32_t* active, const int32_t* pos, int32_t n_active, int32_t n, int32_t nb,
+                             int32_t max_len, const int32_t* seq, int32_t* tokens_next, void* stream);
+
 /* Teacher-forced seq2seq forward (T5ForConditionalGeneration(input_ids, attention_mask, labels)) over
  * `batch` (source, target) pairs packed varlen; DESIGN.md section 10.  src_cu / tgt_cu are HOST int32
  * [batch + 1] prefix sums (start at 0): source b is rows src_cu[b] .. src_cu[b+1] of enc_bf16, target b

@@ -331,6 +331,19 @@ SIGNATURES = {
          C.c_void_p],
     ),
     "rp_sample_uniform": (C.c_float, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rp_sample_pool_step": (
+        C.c_int32,
+        [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
+         C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p],
+    ),
+    "rp_sample_pool_admit": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "rp_sample_pool_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "rp_beam_books_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rp_beam_books_init": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p]),

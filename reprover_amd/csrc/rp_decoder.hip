@@ -16,7 +16,8 @@
 // device, one more launch per step, so that the host loop reads nothing back per position.  rp_beam_pool_advance is
 // rp_beam_advance with a position per slot (one kernel: the uniform call has every slot at t), and rp_beam_books_admit /
 // rp_beam_books_rows give a slot's next tenant fresh books and rebuild the by-row inputs when the active list changes:
-// the slot pool's books.
+// the slot pool's books.  rp_sample_pool_step / rp_sample_pool_admit / rp_sample_pool_rows are the same three for the
+// sampler's books (rp_sample_step: the call in which every slot has pos = t).
 //
 // Every output element of every kernel here is computed by a reduction whose order depends only on the shapes (K, the
 // key count), never on which other rows share the launch or where the row sits in it: a row's log-probs are the same
@@ -350,8 +351,9 @@ __device__ __forceinline__ void block_scan512(float* a, float* red) {
 //   the draw walks the kept ids in ascending order: the smallest v of non-zero mass with C(v) > u Z (C = the inclusive
 //     prefix sum of e, Z its last value), else the last kept id of non-zero mass.
 // State arrays are indexed by (state, sample): a finished row writes pad and changes nothing else.
+// The row's position t = slots.pos[slot] (rp_sample_step: one t for every slot; rp_sample_pool_step: one per slot).
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restrict__ lp, int V, int nb, DecSlots slots,
-                                                          const uint32_t* __restrict__ seeds, int t, int max_len,
+                                                          const uint32_t* __restrict__ seeds, int max_len,
                                                           float temperature, int top_k, float drop_mass, int eos, int pad,
                                                           int32_t* __restrict__ seq, int32_t* __restrict__ tokens_next,
                                                           float* __restrict__ cum, int32_t* __restrict__ ngen,
@@ -361,7 +363,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restric
   __shared__ float red[4];
   __shared__ int s_first[4], s_last[4];
   const int tid = threadIdx.x, row = blockIdx.x, slot = row / nb, b = row - slot * nb;
-  const int state = slots.state[slot];
+  const int state = slots.state[slot], t = slots.pos[slot];
   const size_t idx = (size_t)state * nb + b;
   int32_t* next = seq + idx * max_len + min(t + 1, max_len - 1);
   if (finished[idx]) {  // the same value for the whole workgroup
@@ -438,6 +440,39 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restric
     ngen[idx] += 1;
     if (tok == eos) finished[idx] = 1;
   }
+}
+
+// The sampler's books for a slot's next tenant (rp_sample_pool_admit): the states listed in slots.state[0 .. gridDim.x),
+// one workgroup each, their seeds by value.  Every seq row of the state over all ld columns (the previous tenant wrote
+// them), its scores, counts and flags, its seed; nothing of another state.
+struct SampleSeeds {
+  uint32_t seed[DEC_MAX_STATES];
+};
+
+__global__ __launch_bounds__(256) void sample_admit_kernel(DecSlots slots, SampleSeeds fresh, int nb, int ld, int start,
+                                                           int pad, uint32_t* __restrict__ seeds,
+                                                           int32_t* __restrict__ seq, float* __restrict__ cum,
+                                                           int32_t* __restrict__ ngen, int32_t* __restrict__ finished) {
+  const int tid = threadIdx.x, state = slots.state[blockIdx.x];
+  for (int r = 0; r < nb; ++r) {
+    int32_t* row = seq + ((size_t)state * nb + r) * ld;
+    for (int c = tid; c < ld; c += 256) row[c] = c == 0 ? start : pad;
+  }
+  for (int r = tid; r < nb; r += 256) {
+    const size_t at = (size_t)state * nb + r;
+    cum[at] = 0.f;
+    ngen[at] = 0;
+    finished[at] = 0;
+  }
+  if (tid == 0) seeds[state] = fresh.seed[blockIdx.x];
+}
+
+// The next step's tokens of slot blockIdx.x, by row, from its state's seq: column slots.pos[slot] (rp_sample_pool_rows).
+__global__ __launch_bounds__(64) void sample_rows_kernel(DecSlots slots, int nb, int ld, const int32_t* __restrict__ seq,
+                                                         int32_t* __restrict__ tokens_next) {
+  const int slot = blockIdx.x, state = slots.state[slot], t = slots.pos[slot];
+  for (int r = threadIdx.x; r < nb; r += 64)
+    tokens_next[(size_t)slot * nb + r] = seq[((size_t)state * nb + r) * ld + t];
 }
 
 // ---- beam books: beam search's bookkeeping on the device ------------------------------------------------------------------
@@ -1178,33 +1213,108 @@ extern "C" float rp_sample_uniform(uint32_t seed, uint32_t sample, uint32_t posi
   return sample_uniform(seed, sample, position);
 }
 
-extern "C" RpStatus rp_sample_step(const float* lp, int32_t V, const int32_t* active, int32_t n_active, int32_t n,
-                                   int32_t nb, const uint32_t* seeds, int32_t t, int32_t max_len, float temperature,
-                                   int32_t top_k, float top_p, int32_t eos, int32_t pad, int32_t* seq, int32_t* tokens_next,
-                                   float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream_) {
+namespace {
+// The slot list of a books launch: active[a] distinct and in [0, n), slot a at position pos[a] (null: t for all).
+RpStatus books_slots(DecSlots* slots, const int32_t* active, const int32_t* pos, int t, int n_active, int n, int max_len) {
+  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
+  uint32_t seen = 0;
+  for (int a = 0; a < n_active; ++a) {
+    const int sidx = active[a], p = pos ? pos[a] : t;
+    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share books
+    RP_REQUIRE(p >= 0 && p + 1 < max_len, "pos[%d]=%d: position pos + 1 outside [1, max_len=%d)", a, p, max_len);
+    seen |= 1u << sidx;
+    slots->state[a] = sidx;
+    slots->pos[a] = p;
+  }
+  return RP_OK;
+}
+
+// the caps the sampler's entry points share; `listed` = the states the call names (active, or admitted)
+RpStatus sample_caps(int n, int nb, int listed, int max_len) {
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "nb=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(n >= 1 && n <= DEC_MAX_STATES, "states=%d (1..%d)", n, DEC_MAX_STATES);
+  RP_REQUIRE(max_len >= 2, "max_len=%d < 2", max_len);
+  RP_REQUIRE((int64_t)listed * nb <= DEC_MAX_ROWS, "rows = listed states * nb = %lld > %d", (long long)listed * nb,
+             DEC_MAX_ROWS);
+  return RP_OK;
+}
+
+// rp_sample_step (pos null: every slot at t) and rp_sample_pool_step (slot a at pos[a]): one check list, one kernel
+RpStatus sample_step_launch(const float* lp, int V, const int32_t* active, const int32_t* pos, int t, int n_active, int n,
+                            int nb, const uint32_t* seeds, int max_len, float temperature, int top_k, float top_p, int eos,
+                            int pad, int32_t* seq, int32_t* tokens_next, float* cum_logprob, int32_t* n_generated,
+                            int32_t* finished, void* stream_) {
   RP_REQUIRE(lp && active && seeds && seq && tokens_next && cum_logprob && n_generated && finished, "null argument");
   RP_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "temperature=%g, not a positive finite number", (double)temperature);
   RP_REQUIRE(top_p > 0.f && top_p <= 1.f, "top_p=%g outside (0, 1]", (double)top_p);
   RP_REQUIRE(top_k >= 0, "top_k=%d < 0", top_k);
   RP_REQUIRE(V >= 1 && V <= DEC_SELECT_ROW, "vocab=%d (1..%d)", V, DEC_SELECT_ROW);
-  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "nb=%d (1..%d)", nb, DEC_MAX_BEAMS);
-  RP_REQUIRE(n >= 1 && n <= DEC_MAX_STATES, "states=%d (1..%d)", n, DEC_MAX_STATES);
-  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
-  RP_REQUIRE(n_active * nb <= DEC_MAX_ROWS, "rows = active states * nb = %d > %d", n_active * nb, DEC_MAX_ROWS);
-  RP_REQUIRE(max_len >= 2 && t >= 0 && t + 1 < max_len, "t=%d: position t + 1 outside [1, max_len=%d)", t, max_len);
+  RpStatus st = sample_caps(n, nb, n_active, max_len);
+  if (st) return st;
+  if (!pos) RP_REQUIRE(t >= 0 && t + 1 < max_len, "t=%d: position t + 1 outside [1, max_len=%d)", t, max_len);
   DecSlots slots = {};
-  uint32_t seen = 0;
-  for (int a = 0; a < n_active; ++a) {
-    const int sidx = active[a];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two rows would share a score
-    seen |= 1u << sidx;
-    slots.state[a] = sidx;
-  }
+  if ((st = books_slots(&slots, active, pos, t, n_active, n, max_len))) return st;
   const float drop_mass = (float)(1.0 - (double)top_p);
   hipLaunchKernelGGL(sample_step_kernel, dim3(n_active * nb), dim3(256), 0, (hipStream_t)stream_, lp, V, nb, slots, seeds,
-                     t, max_len, temperature, top_k, drop_mass, eos, pad, seq, tokens_next, cum_logprob, n_generated,
-                     finished);
+                     max_len, temperature, top_k, drop_mass, eos, pad, seq, tokens_next, cum_logprob, n_generated, finished);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+}  // namespace
+
+extern "C" RpStatus rp_sample_step(const float* lp, int32_t V, const int32_t* active, int32_t n_active, int32_t n,
+                                   int32_t nb, const uint32_t* seeds, int32_t t, int32_t max_len, float temperature,
+                                   int32_t top_k, float top_p, int32_t eos, int32_t pad, int32_t* seq, int32_t* tokens_next,
+                                   float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream_) {
+  return sample_step_launch(lp, V, active, nullptr, t, n_active, n, nb, seeds, max_len, temperature, top_k, top_p, eos, pad,
+                            seq, tokens_next, cum_logprob, n_generated, finished, stream_);
+}
+
+// ---- the slot pool's sampler ("Continuous batching for sampling"): state index = slot place ----------
+extern "C" RpStatus rp_sample_pool_step(const float* lp, int32_t V, const int32_t* active, const int32_t* pos,
+                                        int32_t n_active, int32_t n, int32_t nb, const uint32_t* seeds, int32_t max_len,
+                                        float temperature, int32_t top_k, float top_p, int32_t eos, int32_t pad,
+                                        int32_t* seq, int32_t* tokens_next, float* cum_logprob, int32_t* n_generated,
+                                        int32_t* finished, void* stream_) {
+  RP_REQUIRE(pos, "null argument");
+  return sample_step_launch(lp, V, active, pos, 0, n_active, n, nb, seeds, max_len, temperature, top_k, top_p, eos, pad, seq,
+                            tokens_next, cum_logprob, n_generated, finished, stream_);
+}
+
+extern "C" RpStatus rp_sample_pool_admit(const int32_t* states, const uint32_t* new_seeds, int32_t m, int32_t n, int32_t nb,
+                                         int32_t max_len, int32_t start_token, int32_t pad, uint32_t* seeds, int32_t* seq,
+                                         float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream_) {
+  RP_REQUIRE(states && new_seeds && seeds && seq && cum_logprob && n_generated && finished, "null argument");
+  RpStatus st = sample_caps(n, nb, m, max_len);
+  if (st) return st;
+  RP_REQUIRE(m >= 1 && m <= n, "admitted states=%d (1..states=%d)", m, n);
+  DecSlots slots = {};
+  SampleSeeds fresh = {};
+  uint32_t seen = 0;
+  for (int j = 0; j < m; ++j) {
+    const int sidx = states[j];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "states[%d]=%d outside [0, states=%d)", j, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "states[%d]=%d names a state twice", j, sidx);
+    seen |= 1u << sidx;
+    slots.state[j] = sidx;
+    fresh.seed[j] = new_seeds[j];
+  }
+  hipLaunchKernelGGL(sample_admit_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream_, slots, fresh, nb, max_len,
+                     start_token, pad, seeds, seq, cum_logprob, n_generated, finished);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_sample_pool_rows(const int32_t* active, const int32_t* pos, int32_t n_active, int32_t n, int32_t nb,
+                                        int32_t max_len, const int32_t* seq, int32_t* tokens_next, void* stream_) {
+  RP_REQUIRE(active && pos && seq && tokens_next, "null argument");
+  RpStatus st = sample_caps(n, nb, n_active, max_len);
+  if (st) return st;
+  DecSlots slots = {};
+  if ((st = books_slots(&slots, active, pos, 0, n_active, n, max_len))) return st;
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(n_active), dim3(64), 0, (hipStream_t)stream_, slots, nb, max_len, seq,
+                     tokens_next);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
@@ -1239,22 +1349,6 @@ extern "C" RpStatus rp_beam_books_init(void* books, size_t bytes, int32_t n, int
 }
 
 namespace {
-// The slot list of a books launch: active[a] distinct and in [0, n), slot a at position pos[a] (null: t for all).
-RpStatus books_slots(DecSlots* slots, const int32_t* active, const int32_t* pos, int t, int n_active, int n, int max_len) {
-  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
-  uint32_t seen = 0;
-  for (int a = 0; a < n_active; ++a) {
-    const int sidx = active[a], p = pos ? pos[a] : t;
-    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share books
-    RP_REQUIRE(p >= 0 && p + 1 < max_len, "pos[%d]=%d: position pos + 1 outside [1, max_len=%d)", a, p, max_len);
-    seen |= 1u << sidx;
-    slots->state[a] = sidx;
-    slots->pos[a] = p;
-  }
-  return RP_OK;
-}
-
 RpStatus books_advance(void* books, size_t bytes, int n, int nb, int max_len, const DecSlots& slots, const BeamDivs& divs,
                        int n_active, const float* scores, const int32_t* tokens, const int32_t* parents, int eos,
                        void* stream_) {

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
-from .generation import (BeamBooks, BeamBooksPool, BeamSearchOutput, BeamSearchPool, SampleState, beam_search,
+from .generation import (BeamBooks, BeamBooksPool, BeamSearchOutput, BeamSearchPool, SamplePool, SampleState, beam_search,
                          beam_search_batch, beam_search_batch_device, check_sampling, greedy_search, greedy_search_batch,
                          sample_search_batch)
 
@@ -534,6 +534,60 @@ class HipT5Decoder:
                                                     books.max_len, _pc(act), _pc(p), len(act), _lib.current_stream()),
                        "rp_beam_books_rows")
 
+    # -- the slot pool's sampler: a position per slot (``generation.SamplePool``'s callables) -----------------------------
+    @staticmethod
+    def _sample_books(state: SampleState, entry: str):
+        for x in (state.seeds, state.seq, state.cum_logprob, state.n_generated, state.finished, state.tokens):
+            assert x.is_cuda and x.is_contiguous(), f"{entry} takes contiguous device tensors"
+        assert state.seeds.dtype == state.seq.dtype == state.tokens.dtype == torch.int32
+        assert state.n_generated.dtype == state.finished.dtype == torch.int32 and state.cum_logprob.dtype == torch.float32
+        return state.seq.shape
+
+    def sample_pool_step(self, log_probs: torch.Tensor, active, pos, state: SampleState, temperature: float = 1.0,
+                         top_k: int = 0, top_p: float = 1.0, eos_token_id: int = 1, pad_token_id: int = 0) -> None:
+        """``sample_step`` with slot ``active[a]`` at its own position ``pos[a]`` (``rp_sample_pool_step``;
+        ``SamplePool``'s ``sample_step``).  Nothing is read back."""
+        act, p = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos))
+        n, nb, max_len = self._sample_books(state, "rp_sample_pool_step")
+        rows, V = log_probs.shape
+        if len(p) != len(act) or rows != len(act) * nb or state.tokens.numel() < rows:
+            raise _lib.HipLibraryError(f"sample_pool_step: {rows} rows, {len(p)} positions for {len(act)} slots of {nb} "
+                                       "samples")
+        assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dtype == torch.float32
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_sample_pool_step(log_probs.data_ptr(), V, _pc(act), _pc(p), len(act), n, nb,
+                                                     state.seeds.data_ptr(), max_len, temperature, top_k, top_p,
+                                                     eos_token_id, pad_token_id, state.seq.data_ptr(),
+                                                     state.tokens.data_ptr(), state.cum_logprob.data_ptr(),
+                                                     state.n_generated.data_ptr(), state.finished.data_ptr(),
+                                                     _lib.current_stream()), "rp_sample_pool_step")
+
+    def sample_books_admit(self, state: SampleState, states, seeds, decoder_start_token_id: int = 0,
+                           pad_token_id: int = 0) -> None:
+        """Fresh books for the next tenants of ``states`` with their 32-bit ``seeds`` (``rp_sample_pool_admit``)."""
+        st = np.ascontiguousarray(states, dtype=np.int32)
+        sd = np.array([int(x) & 0xFFFFFFFF for x in seeds], dtype=np.uint32)
+        n, nb, max_len = self._sample_books(state, "rp_sample_pool_admit")
+        if len(sd) != len(st):
+            raise _lib.HipLibraryError(f"sample_books_admit: {len(sd)} seeds for {len(st)} states")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_sample_pool_admit(_pc(st), _pc(sd), len(st), n, nb, max_len, decoder_start_token_id,
+                                                      pad_token_id, state.seeds.data_ptr(), state.seq.data_ptr(),
+                                                      state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
+                                                      state.finished.data_ptr(), _lib.current_stream()),
+                       "rp_sample_pool_admit")
+
+    def sample_books_rows(self, state: SampleState, active, pos) -> None:
+        """The next step's tokens of the slots ``active`` (in that order) from their ``seq`` rows (``rp_sample_pool_rows``)."""
+        act, p = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos))
+        n, nb, max_len = self._sample_books(state, "rp_sample_pool_rows")
+        if len(act) != len(p) or state.tokens.numel() < len(act) * nb:
+            raise _lib.HipLibraryError(f"sample_books_rows: {len(p)} positions for {len(act)} slots of {nb} samples")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_sample_pool_rows(_pc(act), _pc(p), len(act), n, nb, max_len, state.seq.data_ptr(),
+                                                     state.tokens.data_ptr(), _lib.current_stream()),
+                       "rp_sample_pool_rows")
+
     def select_many(self, log_probs: torch.Tensor, running: torch.Tensor, nb: int, k: int):
         """Per state the device top-k of its own ``[nb * V]`` block (``rp_beam_select_batch``): scores, tokens, parents,
         each ``[n_active, k]``, parents local to the state."""
@@ -801,6 +855,26 @@ class HipT5Generator:
             decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
             device=self.device)
 
+    def sample_stream(self, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
+                      top_p: float = 1.0, length_penalty: float = 0.0, n_slots: Optional[int] = None, src_cap: int = 2048,
+                      sync_every: int = 16) -> "SampleStream":
+        """A running sampled search that sources join while it runs (continuous batching): a
+        ``SampleStream`` of ``n_slots`` places (default ``HipT5Decoder.max_states(num_samples)``) for sources of at most
+        ``src_cap`` tokens, its books on the device (``generation.SamplePool``, ``rp_sample_pool_step``), nothing uploaded
+        or read back per step, the finished flags read every ``sync_every`` steps.  Every ticket's output is
+        ``sample(source, num_samples, max_length, temperature, top_k, top_p, seed, length_penalty)`` bit for bit, tokens
+        and scores, whichever sources share the stream, in whatever order and slots.  The sampling parameters are the
+        stream's.  The decoder carries one stream at a time, of either kind: opening another retires this one."""
+        check_sampling(temperature, top_k, top_p)
+        if num_samples < 1 or max_length <= 1:
+            raise ValueError(f"num_samples={num_samples} (>= 1), max_length={max_length} (>= 2)")
+        if int(sync_every) != sync_every or sync_every < 1:
+            raise ValueError(f"sync_every={sync_every} must be an integer >= 1")
+        if n_slots is not None and (int(n_slots) != n_slots or n_slots < 1):
+            raise ValueError(f"n_slots={n_slots} must be an integer >= 1 (or None)")
+        return SampleStream(self, num_samples, max_length, temperature, int(top_k), top_p, length_penalty,
+                            self.decoder.max_states(num_samples) if n_slots is None else n_slots, src_cap, int(sync_every))
+
 
 class GenerateStream:
     """``HipT5Generator.generate_stream``'s object: ``generation.BeamSearchPool`` over the decoder's slot pool.
@@ -812,11 +886,7 @@ class GenerateStream:
 
     def __init__(self, generator: HipT5Generator, num_beams: int, max_length: int, length_penalty: float, n_slots: int,
                  src_cap: int, sync_every: Optional[int] = None):
-        self.generator, self.src_cap = generator, int(src_cap)
-        dec = self.decoder = generator.decoder
-        dec.pool_open(n_slots, num_beams, max_length, src_cap)
-        dec._pool_owner = self
-        self._src_len = [0] * int(n_slots)  # per slot: the source length of its tenant
+        dec = self._open(generator, n_slots, num_beams, max_length, src_cap)
         cfg = generator.cfg
         if sync_every is not None:
             self.pool = BeamBooksPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
@@ -830,6 +900,15 @@ class GenerateStream:
                                    eos_token_id=cfg.get("eos_token_id", 1),
                                    decoder_start_token_id=cfg.get("decoder_start_token_id", 0),
                                    select_many=dec.select_many, device=generator.device)
+
+    def _open(self, generator: HipT5Generator, n_slots: int, nb: int, max_length: int, src_cap: int) -> HipT5Decoder:
+        """Take the decoder's slot pool (beam and sample streams alike: whoever held it is retired)."""
+        self.generator, self.src_cap = generator, int(src_cap)
+        dec = self.decoder = generator.decoder
+        dec.pool_open(n_slots, nb, max_length, src_cap)
+        dec._pool_owner = self
+        self._src_len = [0] * int(n_slots)  # per slot: the source length of its tenant
+        return dec
 
     def _mine(self) -> HipT5Decoder:
         if getattr(self.decoder, "_pool_owner", None) is not self:
@@ -846,11 +925,14 @@ class GenerateStream:
     def _step(self, active, pos, tokens, ancestry) -> torch.Tensor:
         return self._mine().pool_step(active, pos, [self._src_len[s] for s in active], tokens, ancestry)
 
-    def submit(self, ids) -> int:
+    def _source(self, ids) -> np.ndarray:
         ids = np.asarray(ids, dtype=np.int32).reshape(-1)
         if not 1 <= ids.size <= self.src_cap:
             raise ValueError(f"a source of {ids.size} tokens does not fit the stream's src_cap={self.src_cap} (1..src_cap)")
-        return self.pool.submit(ids)
+        return ids
+
+    def submit(self, ids) -> int:
+        return self.pool.submit(self._source(ids))
 
     def step(self) -> List[Tuple[int, BeamSearchOutput]]:
         return self.pool.step()
@@ -869,6 +951,29 @@ class GenerateStream:
     @property
     def steps(self) -> int:
         return self.pool.steps
+
+
+class SampleStream(GenerateStream):
+    """``HipT5Generator.sample_stream``'s object: ``generation.SamplePool`` over the decoder's slot pool, with
+    ``GenerateStream``'s admission (the newcomers encoded together, one packed encoder pass) and its retirement rule.
+    ``submit(ids, seed)`` queues a source with its 32-bit seed and returns its ticket; ``step()`` takes one decode step
+    and returns the ``(ticket, BeamSearchOutput)`` pairs its sync points delivered; ``drain()`` steps until the stream
+    is idle."""
+
+    def __init__(self, generator: HipT5Generator, num_samples: int, max_length: int, temperature: float, top_k: int,
+                 top_p: float, length_penalty: float, n_slots: int, src_cap: int, sync_every: int):
+        dec = self._open(generator, n_slots, num_samples, max_length, src_cap)
+        eos = generator.cfg.get("eos_token_id", 1)
+        self.pool = SamplePool(
+            self._admit, self._step,
+            lambda lp, active, pos, state: self._mine().sample_pool_step(lp, active, pos, state, temperature, top_k, top_p,
+                                                                         eos, 0),
+            n_slots, num_samples, max_length, length_penalty,
+            decoder_start_token_id=generator.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
+            device=generator.device, books_admit=dec.sample_books_admit, rows=dec.sample_books_rows)
+
+    def submit(self, ids, seed: int) -> int:
+        return self.pool.submit(self._source(ids), seed)
 
 
 class HipSeq2SeqGradients:

@@ -37,6 +37,9 @@ slot between two steps and is stepped at its own position, and its output is ret
 ``BeamBooksPool`` is that pool with the books in a ``BeamBooks`` block of ``n_slots`` states: a position per slot
 (``rp_beam_pool_advance``), the stop flags read every ``sync_every`` steps, results delivered at those sync points.
 ``beam_books_admit_host``, ``beam_pool_advance_host`` and ``beam_books_rows_host`` restate its three kernels.
+``SamplePool`` is the same pool for the sampled search: the sampler's books (``SampleState``) for ``n_slots`` states, a
+position per slot (``rp_sample_pool_step``), one forced sync point when a slot reaches ``max_length - 1``;
+``sample_books_admit_host`` and ``sample_books_rows_host`` restate its other two kernels.
 """
 from __future__ import annotations
 
@@ -900,3 +903,208 @@ def sample_search(step: Callable, sample_step: Callable, num_samples: int, max_l
     return sample_search_batch(lambda active, tokens, ancestry, t: step(tokens, ancestry, t), sample_step, 1,
                                num_samples, max_length, [seed], length_penalty, eos_token_id, decoder_start_token_id,
                                pad_token_id, sync_every, device)[0]
+
+
+# ---- continuous batching for the sampled search: a position per slot ---------------------------------------------------
+SAMPLE_POOL_MUTANTS = ("shared_position", "admit_not_reset", "stale_tokens")
+
+
+def _seed_bits(seed: int) -> int:
+    """A 32-bit seed as the int32 that holds its bits (``SampleState.seeds``)."""
+    bits = int(seed) & 0xFFFFFFFF
+    return bits - 2 ** 32 if bits >= 2 ** 31 else bits
+
+
+def sample_books_admit_host(state: SampleState, states: Sequence[int], seeds: Sequence[int],
+                            decoder_start_token_id: int = 0, pad_token_id: int = 0, mutant: Optional[str] = None) -> None:
+    """``rp_sample_pool_admit`` on host books: for ``states`` only, ``seeds[s]`` set, every ``seq`` row pad over all
+    ``max_length`` columns with the start token in column 0 (a previous tenant wrote them), ``cum_logprob``,
+    ``n_generated`` and ``finished`` zero.  Nothing of another state and nothing by row is touched.  ``mutant``
+    "admit_not_reset" (``SAMPLE_POOL_MUTANTS``): ``seq`` and ``finished`` stay as the last tenant left them."""
+    assert mutant is None or mutant in SAMPLE_POOL_MUTANTS, mutant
+    n = state.seq.shape[0]
+    assert len(states) == len(seeds) and len(set(states)) == len(states) and all(0 <= s < n for s in states)
+    for s, seed in zip(states, seeds):
+        state.seeds[s] = _seed_bits(seed)
+        if mutant != "admit_not_reset":
+            state.seq[s] = pad_token_id
+            state.seq[s, :, 0] = decoder_start_token_id
+            state.finished[s] = 0
+        state.cum_logprob[s] = 0.0
+        state.n_generated[s] = 0
+
+
+def sample_books_rows_host(state: SampleState, active: Sequence[int], pos: Sequence[int]) -> None:
+    """``rp_sample_pool_rows`` on host books: ``tokens[a * nb + b] = seq[active[a], b, pos[a]]``, the next step's tokens
+    by row."""
+    n, nb, L = state.seq.shape
+    assert len(active) == len(pos) and len(set(active)) == len(active) and all(0 <= s < n for s in active)
+    assert all(0 <= p <= L - 2 for p in pos)
+    for a, (s, p) in enumerate(zip(active, pos)):
+        state.tokens[a * nb : (a + 1) * nb] = state.seq[s, :, p]
+
+
+class SamplePool:
+    """``sample_search_batch``'s loop with admission, the sampled counterpart of ``BeamBooksPool``: ``n_slots`` places,
+    state index = slot place, the sampler's books (one ``SampleState`` of ``n_slots`` states) on the device, a position
+    per slot kept on the host.  ``submit(source, seed)`` queues a source; per ``step`` it runs one engine ``step`` and one
+    ``sample_step``, nothing is uploaded but their arguments and nothing is read back.  A ticket's output is
+    ``sample_search``'s for that source alone at that seed, whichever sources share the pool, in whatever order and
+    slots, for any ``n_slots`` and ``sync_every``: a row's log-probs depend on its own state and position only, and its
+    random numbers on (seed, sample, position).
+
+    At a *sync point* it (1) reads the ``finished`` flags once (reduced over a state's samples on the device: ``n_slots``
+    ints), (2) reads the results of the states that stopped - their ``seq`` rows, ``cum_logprob`` (as bits) and
+    ``n_generated``, gathered on the device into one buffer - (3) frees their slots, (4) admits queued sources into the
+    lowest free slots (``admit``, then ``books_admit``) and (5), if the active list changed, runs ``rows``.  So at most
+    two device-to-host copies per sync point, all through ``to_host``.  A sync point occurs after every ``sync_every``
+    steps since the last one, before a step whenever something is queued and a slot is known to be free, at the step
+    where the pool starts from idle, and after the step that took any slot to position ``max_length - 1``.  The last one
+    is forced: that slot is done by length, which the host knows without reading anything, and it must not be stepped
+    again - unlike a stopped beam state its books are not frozen, an unfinished row would draw again and add to
+    ``cum_logprob`` (and no launch may carry ``pos + 1 >= max_length``).  ``sync_points`` counts them.
+
+    Between sync points a state whose samples have all finished keeps being stepped; its rows write pad and change
+    nothing else, as in ``sample_search_batch``.  The trade-off is ``BeamBooksPool``'s: with ``sync_every = K > 1`` a
+    result is delivered, and its slot taken again, up to ``K - 1`` steps after its last sample finished.
+
+    - ``admit(slots, sources)``: as in ``BeamSearchPool``.
+    - ``step(active, pos, tokens, ancestry) -> log_probs``: ``tokens`` int32 ``[n_active * nb]`` is a view of the books'
+      by-row part; ``ancestry`` int32 ``[n_active * nb, max_length]`` the first rows of the identity table
+      ``[r, p] = p * nb + r % nb`` built here once (it depends on ``r % nb`` only, so it serves any active list), of
+      which columns ``0..pos[a]`` of slot ``active[a]``'s rows are read.
+    - ``sample_step(log_probs, active, pos, state)``: ``rp_sample_pool_step`` - ``sample_search_batch``'s ``sample_step``
+      with slot ``active[a]`` at ``pos[a]``.  It has no host default.
+    - ``books_admit(state, states, seeds, start, pad)``: ``rp_sample_pool_admit`` (default ``sample_books_admit_host``).
+    - ``rows(state, active, pos)``: ``rp_sample_pool_rows`` (default ``sample_books_rows_host``).
+    - ``to_host(x)``: every device-to-host copy.
+
+    ``mutant`` (``SAMPLE_POOL_MUTANTS``) plants a known bug: "shared_position" samples every slot at the first slot's
+    position, "admit_not_reset" leaves the previous tenant's ``seq`` / ``finished`` in place (host default), and
+    "stale_tokens" skips ``rows`` after the active list changed."""
+
+    def __init__(self, admit: Callable, step: Callable, sample_step: Callable, n_slots: int, num_samples: int,
+                 max_length: int, length_penalty: float = 0.0, decoder_start_token_id: int = 0, pad_token_id: int = 0,
+                 sync_every: int = 16, device=None, books_admit: Optional[Callable] = None,
+                 rows: Optional[Callable] = None, to_host: Callable = lambda x: x.cpu(), mutant: Optional[str] = None):
+        assert mutant is None or mutant in SAMPLE_POOL_MUTANTS, mutant
+        if int(n_slots) < 1 or int(num_samples) < 1:
+            raise ValueError(f"n_slots={n_slots} and num_samples={num_samples} must be >= 1")
+        if max_length <= 1:
+            raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+        if int(sync_every) != sync_every or sync_every < 1:
+            raise ValueError(f"sync_every={sync_every} must be an integer >= 1")
+        n, nb, L = int(n_slots), int(num_samples), int(max_length)
+        self.n_slots, self.nb, self.max_length = n, nb, L
+        self.sync_every, self.length_penalty, self.mutant = int(sync_every), length_penalty, mutant
+        self.start, self.pad = decoder_start_token_id, pad_token_id
+        self._admit, self._step, self._sample_step, self._to_host = admit, step, sample_step, to_host
+        self._books_admit = books_admit or (lambda st, states, seeds, start, pad: sample_books_admit_host(
+            st, states, seeds, start, pad, mutant="admit_not_reset" if mutant == "admit_not_reset" else None))
+        self._rows = rows or sample_books_rows_host
+        self.state = SampleState(  # every state is admitted before use
+            seeds=torch.zeros(n, dtype=torch.int32, device=device),
+            seq=torch.zeros((n, nb, L), dtype=torch.int32, device=device),
+            cum_logprob=torch.zeros((n, nb), dtype=torch.float32, device=device),
+            n_generated=torch.zeros((n, nb), dtype=torch.int32, device=device),
+            finished=torch.zeros((n, nb), dtype=torch.int32, device=device),
+            tokens=torch.zeros(n * nb, dtype=torch.int32, device=device))
+        ancestry = (torch.arange(L, dtype=torch.int32)[None] * nb
+                    + (torch.arange(n * nb, dtype=torch.int32) % nb)[:, None]).contiguous()
+        self.ancestry = ancestry if device is None else ancestry.to(device)
+        self._queue: List[Tuple[int, object, int]] = []              # (ticket, source, seed), first in first out
+        self._ticket: List[Optional[int]] = [None] * n               # per slot: its tenant's ticket
+        self._pos = [0] * n                                          # per slot: the position of its next step
+        self._active: List[int] = []                                 # the slots in use, ascending: the by-row order
+        self._next_ticket = 0
+        self._since = 0                                              # steps since the last sync point
+        self.steps = 0
+        self.sync_points = 0
+
+    @property
+    def queued(self) -> int:
+        return len(self._queue)
+
+    @property
+    def in_flight(self) -> int:
+        return sum(t is not None for t in self._ticket)
+
+    def submit(self, source, seed: int) -> int:
+        """Queue a source with its 32-bit seed; its ticket names it in ``step``'s return."""
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        self._queue.append((ticket, source, int(seed)))
+        return ticket
+
+    def _results(self, stopped: List[int]) -> List[Tuple[int, BeamSearchOutput]]:
+        """``sample_search_batch``'s outputs of the stopped states from one buffer gathered on the device: per state its
+        ``seq`` rows, ``cum_logprob`` (as bits), ``n_generated``."""
+        st, nb, L = self.state, self.nb, self.max_length
+        idx = torch.tensor(stopped, dtype=torch.int64, device=st.seq.device)
+        buf = torch.cat([st.seq[idx].reshape(len(stopped), nb * L), st.cum_logprob[idx].view(torch.int32),
+                         st.n_generated[idx]], dim=1)
+        host = self._to_host(buf)
+        out = []
+        for j, s in enumerate(stopped):
+            ngen = host[j, nb * L + nb :]
+            cum = host[j, nb * L : nb * L + nb].clone().view(torch.float32)
+            seq = host[j, : nb * L].view(nb, L)[:, : 1 + int(ngen.max())].long().clone()
+            out.append((self._ticket[s], BeamSearchOutput(seq, cum / ngen.to(torch.float32) ** float(self.length_penalty))))
+        return out
+
+    def _sync(self) -> List[Tuple[int, BeamSearchOutput]]:
+        self.sync_points += 1
+        self._since = 0
+        out: List[Tuple[int, BeamSearchOutput]] = []
+        changed = False
+        if self._active:
+            done = self._to_host(self.state.finished.bool().all(dim=1).to(torch.int32))
+            stopped = [s for s in self._active if bool(done[s]) or self._pos[s] + 1 >= self.max_length]
+            if stopped:
+                out = self._results(stopped)
+                for s in stopped:
+                    self._ticket[s] = None
+                changed = True
+        free = [s for s in range(self.n_slots) if self._ticket[s] is None]  # ascending: the lowest free slots first
+        take = min(len(free), len(self._queue))
+        if take:
+            new, self._queue = self._queue[:take], self._queue[take:]
+            self._admit(free[:take], [src for _, src, _ in new])
+            self._books_admit(self.state, free[:take], [seed for _, _, seed in new], self.start, self.pad)
+            for s, (ticket, _, _) in zip(free, new):
+                self._ticket[s], self._pos[s] = ticket, 0
+            changed = True
+        self._active = [s for s in range(self.n_slots) if self._ticket[s] is not None]
+        if changed and self._active and self.mutant != "stale_tokens":
+            self._rows(self.state, list(self._active), [self._pos[s] for s in self._active])
+        return out
+
+    def step(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """One decode step, with a sync point before it when a queued source can take a free slot and one after it when
+        ``sync_every`` steps have passed or a slot reached ``max_length - 1``; the ``(ticket, output)`` pairs those sync
+        points delivered."""
+        out: List[Tuple[int, BeamSearchOutput]] = []
+        if self._queue and self.in_flight < self.n_slots:
+            out.extend(self._sync())
+        if not self._active:
+            return out
+        active = list(self._active)
+        pos = [self._pos[s] for s in active]
+        rows = len(active) * self.nb
+        log_probs = self._step(active, pos, self.state.tokens[:rows], self.ancestry[:rows])
+        self._sample_step(log_probs, active, [pos[0]] * len(pos) if self.mutant == "shared_position" else list(pos),
+                          self.state)
+        self.steps += 1
+        self._since += 1
+        for s in active:
+            self._pos[s] += 1
+        if self._since >= self.sync_every or any(self._pos[s] + 1 >= self.max_length for s in active):
+            out.extend(self._sync())
+        return out
+
+    def drain(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """Step until nothing is queued or in flight; every pair that was delivered on the way, in delivery order."""
+        out = []
+        while self._queue or self.in_flight:
+            out.extend(self.step())
+        return out

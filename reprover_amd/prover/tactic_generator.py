@@ -42,12 +42,19 @@ class HuggingFaceGenerator(TacticGenerator):
     between two steps and returns as soon as its own state stops, with ``generate_sync``'s result.  One driver
     coroutine steps the loop while anything is queued or in flight and yields to the event loop between steps.  With
     ``beam_sync_every=K`` as well, the stream keeps its books on the device (``generate_stream(sync_every=K)``): the same
-    results, each returned up to ``K - 1`` steps after its state stopped."""
+    results, each returned up to ``K - 1`` steps after its state stopped.
+
+    ``sample_stream=True`` (with ``do_sample=True``, without ``continuous``) is the same for sampling: concurrent
+    ``await generate(...)`` calls share one ``HipT5Generator.sample_stream`` (``sample_stream_slots`` places, default the
+    engine's cap; its finished flags read every ``sample_sync_every`` steps) through the same driver.  A call takes its
+    seed when it submits, in call order, so ``asyncio.gather(generate(a), generate(b))`` equals ``generate_sync(a)`` then
+    ``generate_sync(b)`` on a fresh object with the same ``seed``."""
 
     def __init__(self, model_path: str, device, max_inp_seq_len: int, max_oup_seq_len: int, length_penalty: float,
                  template: str = "%s", do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
                  top_p: float = 1.0, seed: int = 0, beam_sync_every: Optional[int] = None, continuous: bool = False,
-                 continuous_slots: Optional[int] = None):
+                 continuous_slots: Optional[int] = None, sample_stream: bool = False,
+                 sample_stream_slots: Optional[int] = None, sample_sync_every: int = 16):
         self.model_path = model_path
         self.device = device
         self.max_inp_seq_len = max_inp_seq_len
@@ -67,7 +74,15 @@ class HuggingFaceGenerator(TacticGenerator):
         if continuous_slots is not None and (int(continuous_slots) != continuous_slots or continuous_slots < 1):
             raise ValueError(f"continuous_slots={continuous_slots} must be an integer >= 1 (or None)")
         self.continuous, self.continuous_slots = bool(continuous), continuous_slots
-        self._stream = None       # the open GenerateStream and its num_samples
+        if sample_stream and (not do_sample or continuous):
+            raise ValueError("sample_stream=True serves sampling only: it needs do_sample=True and continuous=False")
+        if sample_stream_slots is not None and (int(sample_stream_slots) != sample_stream_slots or sample_stream_slots < 1):
+            raise ValueError(f"sample_stream_slots={sample_stream_slots} must be an integer >= 1 (or None)")
+        if int(sample_sync_every) != sample_sync_every or sample_sync_every < 1:
+            raise ValueError(f"sample_sync_every={sample_sync_every} must be an integer >= 1")
+        self.sample_stream, self.sample_stream_slots = bool(sample_stream), sample_stream_slots
+        self.sample_sync_every = int(sample_sync_every)
+        self._stream = None       # the open GenerateStream (or SampleStream) and its num_samples
         self._stream_beams: Optional[int] = None
         self._waiters: Dict[int, "asyncio.Future"] = {}  # ticket -> the generate() call that awaits it
         self._driver: Optional["asyncio.Task"] = None
@@ -92,17 +107,21 @@ class HuggingFaceGenerator(TacticGenerator):
             chunk = ids[i : i + cap]
             outs = self.generator.sample_many(chunk, num_samples, self.max_oup_seq_len, self.temperature, self.top_k,
                                               self.top_p, self._next_seeds(len(chunk)), self.length_penalty)
-            for out in outs:
-                text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
-                scores = out.sequences_scores.tolist()
-                output_text, output_score = [], []
-                for j in sorted(range(len(scores)), key=lambda j: -scores[j]):  # sorted() is stable
-                    t = remove_marks(text[j])
-                    if t not in output_text:
-                        output_text.append(t)
-                        output_score.append(scores[j])
-                results.append(list(zip_strict(output_text, output_score)))
+            results.extend(self._sampled_suggestions(out) for out in outs)
         return results
+
+    def _sampled_suggestions(self, out) -> List[Tuple[str, float]]:
+        """A sampled search's output as (tactic, score) pairs: decoded, marks removed, sorted by score, best first (a
+        stable sort), de-duplicated keeping the first occurrence."""
+        text = self.tokenizer.batch_decode(out.sequences, skip_special_tokens=True)
+        scores = out.sequences_scores.tolist()
+        output_text, output_score = [], []
+        for j in sorted(range(len(scores)), key=lambda j: -scores[j]):  # sorted() is stable
+            t = remove_marks(text[j])
+            if t not in output_text:
+                output_text.append(t)
+                output_score.append(scores[j])
+        return list(zip_strict(output_text, output_score))
 
     def initialize(self) -> None:
         # A decoder-only checkpoint (the reference's AutoModelForCausalLM fallback) raises ValueError here.
@@ -133,7 +152,7 @@ class HuggingFaceGenerator(TacticGenerator):
 
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
                        num_samples: int) -> List[Tuple[str, float]]:
-        if not self.continuous:
+        if not (self.continuous or self.sample_stream):
             return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
         ids = encode_one(self.template % state, self.max_inp_seq_len)
         # a stream serves one num_samples: a call with another waits until it has drained (the driver runs meanwhile)
@@ -141,15 +160,25 @@ class HuggingFaceGenerator(TacticGenerator):
                                                                                   or self._stream.in_flight):
             await asyncio.sleep(0)
         if self._stream is None or self._stream_beams != num_samples:
-            self._stream = self.generator.generate_stream(num_samples, self.max_oup_seq_len, self.length_penalty,
-                                                          n_slots=self.continuous_slots, src_cap=self.max_inp_seq_len,
-                                                          **self._books)
+            if self.sample_stream:
+                self._stream = self.generator.sample_stream(num_samples, self.max_oup_seq_len, self.temperature,
+                                                            self.top_k, self.top_p, self.length_penalty,
+                                                            n_slots=self.sample_stream_slots,
+                                                            src_cap=self.max_inp_seq_len,
+                                                            sync_every=self.sample_sync_every)
+            else:
+                self._stream = self.generator.generate_stream(num_samples, self.max_oup_seq_len, self.length_penalty,
+                                                              n_slots=self.continuous_slots,
+                                                              src_cap=self.max_inp_seq_len, **self._books)
             self._stream_beams = num_samples
         future = asyncio.get_running_loop().create_future()
-        self._waiters[self._stream.submit(ids)] = future
+        # (a sampled call's seed is taken here, at submit time: in call order)
+        ticket = self._stream.submit(ids, self._next_seeds(1)[0]) if self.sample_stream else self._stream.submit(ids)
+        self._waiters[ticket] = future
         if self._driver is None:
             self._driver = asyncio.ensure_future(self._drive())
-        return self._suggestions(await future, num_samples)
+        out = await future
+        return self._sampled_suggestions(out) if self.sample_stream else self._suggestions(out, num_samples)
 
     async def _drive(self) -> None:
         """Step the open stream while it has work, resolving the waiting calls as their states finish; an exception
@@ -199,7 +228,8 @@ class RetrievalAugmentedGenerator(TacticGenerator):
                  max_oup_seq_len: int, length_penalty: float, max_num_retrieved: int, do_sample: bool = False,
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                  beam_sync_every: Optional[int] = None, continuous: bool = False,
-                 continuous_slots: Optional[int] = None) -> None:
+                 continuous_slots: Optional[int] = None, sample_stream: bool = False,
+                 sample_stream_slots: Optional[int] = None, sample_sync_every: int = 16) -> None:
         self.gen_path = gen_path
         self.ret_path = ret_path
         self.indexed_corpus_path = indexed_corpus_path
@@ -211,7 +241,9 @@ class RetrievalAugmentedGenerator(TacticGenerator):
         self.hf_gen = HuggingFaceGenerator(gen_path, device, max_inp_seq_len, max_oup_seq_len, length_penalty,
                                            do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
                                            seed=seed, beam_sync_every=beam_sync_every, continuous=continuous,
-                                           continuous_slots=continuous_slots)
+                                           continuous_slots=continuous_slots, sample_stream=sample_stream,
+                                           sample_stream_slots=sample_stream_slots,
+                                           sample_sync_every=sample_sync_every)
 
     def initialize(self) -> None:
         self.hf_gen.initialize()
@@ -227,7 +259,7 @@ class RetrievalAugmentedGenerator(TacticGenerator):
 
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
                        num_samples: int) -> List[Tuple[str, float]]:
-        if not self.hf_gen.continuous:
+        if not (self.hf_gen.continuous or self.hf_gen.sample_stream):
             return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
         retrieved_premises, _ = self.retriever.retrieve(state, file_path, theorem_full_name, theorem_pos,
                                                         self.max_num_retrieved)

@@ -39,6 +39,14 @@ and sync points of each, whether every output equals the host-books one, and per
 runs to ``max_length`` the run measures the per-step host cost and says nothing about admission.
 
     python tools/gen_bench.py --stream --sync-every 1 4 16 [--reps 2] [--out FILE]
+
+``--stream --sample``: continuous batching for sampling.  The same 16 queued sources, 64 samples each (temperature 1,
+top_k 0, top_p 0.95, max_length 512), served by ``sample_many`` in chunks of 8 and by a ``sample_stream`` of 8 slots, in
+one process, alternating; every stream output is checked equal to the chunked one.  The EOS row of ``lm_head.weight`` is
+multiplied by ``--eos-boost`` so that the states end at different lengths; the length of every state is recorded.  With
+plain synthetic weights everything runs to ``max_length`` and the comparison says nothing about admission.
+
+    python tools/gen_bench.py --stream --sample [--eos-boost 4.0] [--reps 2] [--out FILE]
 """
 from __future__ import annotations
 
@@ -284,6 +292,53 @@ def stream_books_bench(gen, cfg, sync_every, reps, nb=64, max_len=512, n_src=16,
             "outputs_identical": same}
 
 
+def sample_stream_bench(gen, cfg, reps, eos_boost, nb=64, max_len=512, n_src=16, n_slots=8):
+    """``stream_bench``'s 16 queued sources, sampled: (a) ``sample_many`` in chunks of ``n_slots`` and (b) a
+    ``sample_stream`` of ``n_slots`` slots, alternating in one process, every stream output checked equal to the chunked
+    one.  The generator's EOS row is boosted so that the states end at different lengths (recorded: the stream can only
+    win where they do)."""
+    rng = np.random.default_rng(0)
+    lens = [int(x) for x in rng.integers(64, 2049, size=n_src)]
+    srcs = [np.concatenate([rng.integers(3, 259, size=n - 1), [1]]).astype(np.int32) for n in lens]
+    seeds = list(range(100, 100 + n_src))
+    kw = dict(temperature=1.0, top_k=0, top_p=0.95)
+    L = cfg["num_decoder_layers"]
+
+    def chunks():
+        outs = []
+        for i in range(0, n_src, n_slots):
+            outs += gen.sample_many(srcs[i : i + n_slots], nb, max_len, seeds=seeds[i : i + n_slots], **kw)
+        return outs
+
+    def stream(n=n_slots, length=max_len, sources=srcs):
+        st = gen.sample_stream(nb, length, n_slots=n, src_cap=2048, **kw)
+        tickets = [st.submit(s, seed) for s, seed in zip(sources, seeds)]
+        got = dict(st.drain())
+        return [got[t] for t in tickets], st.steps, st.pool.sync_points
+
+    gen.sample_many(srcs[:2], nb, 8, seeds=seeds[:2], **kw)  # warm-up: code objects
+    stream(2, 8, srcs[:1])
+    chunk_ms, stream_ms, same, steps, syncs = [], [], True, 0, 0
+    for _ in range(reps):
+        ms, a = _timed(chunks)
+        chunk_ms.append(ms)
+        ms, (b, steps, syncs) = _timed(stream)
+        stream_ms.append(ms)
+        same = same and _same(a, b)
+    own = [o.sequences.shape[1] - 1 for o in a]  # a state's length: its longest sample
+    # the chunked call looks at the flags every 16 positions: a chunk runs to its longest member's next look
+    chunk_steps = sum(min(-(-max(own[i : i + n_slots]) // 16) * 16, max_len - 1) for i in range(0, n_src, n_slots))
+    return {"metric": "gen_sample_stream_bench", "measured": True, "rows": nb, "max_length": max_len, "length_penalty": 0.0,
+            "sampling": kw, "sync_every": 16, "eos_boost": eos_boost, "sources": n_src, "slots": n_slots,
+            "config": f"byt5-small ({L} decoder layers), sources of {min(lens)}..{max(lens)} bytes", "source_bytes": lens,
+            "reps": reps, "chunked_sample_many_ms": [round(x, 1) for x in chunk_ms],
+            "stream_ms": [round(x, 1) for x in stream_ms],
+            "ratio_chunked_over_stream": round(min(chunk_ms) / min(stream_ms), 3), "length_of_each_state": own,
+            "lengths_differ": len(set(own)) > 1, "states_ended_by_length": sum(n == max_len - 1 for n in own),
+            "chunked_decode_steps_upper_bound": chunk_steps, "stream_decode_steps": steps, "stream_sync_points": syncs,
+            "outputs_identical": same}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -294,13 +349,21 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--sample", action="store_true", help="the sampled call beside the beam-search prover call")
     ap.add_argument("--stream", action="store_true", help="a stream of 8 slots against generate_many in chunks of 8")
+    ap.add_argument("--eos-boost", type=float, default=4.0,
+                    help="with --stream --sample: the factor on the EOS row of lm_head.weight (states end at different lengths)")
     args = ap.parse_args(argv)
     if args.sync_every and (not (args.states or args.stream) or args.sample or min(args.sync_every) < 1):
         ap.error("--sync-every takes values >= 1 and goes with --states or --stream")
     if args.sample or args.stream:
         cfg = synth.seq2seq_config("byt5-small")
-        gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
-        if args.stream and args.sync_every:
+        sd = synth.synth_seq2seq_state_dict(cfg)
+        if args.stream and args.sample:  # as tests/test_sample_gpu.py's _gen boosts it
+            sd["lm_head.weight"] = sd["lm_head.weight"].clone()
+            sd["lm_head.weight"][1] *= args.eos_boost
+        gen = HipT5Generator(cfg, sd, "cuda:0")
+        if args.stream and args.sample:
+            line = json.dumps(sample_stream_bench(gen, cfg, args.reps, args.eos_boost))
+        elif args.stream and args.sync_every:
             line = json.dumps(stream_books_bench(gen, cfg, args.sync_every, args.reps))
         else:
             line = json.dumps(stream_bench(gen, cfg, args.reps) if args.stream else sample_bench(gen, cfg, max(args.reps, 2)))
