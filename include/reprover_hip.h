@@ -533,6 +533,32 @@ RpStatus rp_dbg_decoder_rows(int32_t mode, const void* a, const void* b, const i
                              void* stream);
 RpStatus rp_dbg_hidden_head(const void* xhi, const void* xlo, const float* rs, const float* ln, const float* d_hidden,
                             int32_t T, int32_t D, void* out_hidden, void* dxhi, void* dxlo, float* dln, void* stream);
+/* The decode step's kernels in isolation (tests/test_decode_step_kernels_gpu.py; test-only).  Device
+ * pointers unless said otherwise, launch only (stream-ordered), through the launch code rp_decoder_batch_step / _pool_step run.
+ *   rp_dbg_dec_gemm: dec_gemm_kernel<ceil(K / 512), epi>: out[m, n] = sum_k A[m, k] W[n, k], A bf16 [M, lda], W bf16 [N, K]
+ *     ([2 N, K] for epi 3), K % 8 == 0; epi 0: out bf16 [M, ldo]; 1: out f32, added to; 2: out f32; 3: out bf16 =
+ *     gelu_new(A W[n]) * (A W[n + N]).  K > 4096: RP_E_UNSUPPORTED, nothing launched.
+ *   rp_dbg_dec_rows: mode 0 dec_embed_kernel (ia = tokens [rows], a = table f32 [vocab, n]; o0 f32 [rows, n]); 1
+ *     dec_rmsnorm_kernel (a = x f32 [rows, n], b = ln f32 [n]; o0 bf16 [rows, n]; eps, scale); 2 dec_log_softmax_kernel (o0 f32
+ *     [rows, n], in place); 3 dec_store_kv_kernel (a = qkv bf16 [n_active * nb, 3 n], n = inner; o0 = the caches, state s at
+ *     s * state_stride elements, max_len * nb rows of 2 n; row pos[slot] * nb + beam of state[slot] <- k | v of its qkv row).
+ *   rp_dbg_dec_attention: dec_attention_kernel<cross != 0> over the n_active * nb rows of a slot table.  self: kv = the caches
+ *     (state s at s * state_stride elements, rows = max_len * nb rows of ldkv), keys 0 .. pos[slot] through anc int32
+ *     [n_active * nb, astride] (entries clamped to [0, rows)), bias tab f32 [H, nbias] by distance (clamped at nbias - 1).
+ *     cross: kv = `rows` rows of ldkv, slot a reads rows [src_off[a], src_off[a] + src_len[a]), no bias.  K at column
+ *     koff + 64 h, V at voff + 64 h; q bf16 [rows, ldq], out bf16 [rows, ldo].
+ *   state / src_off / src_len / pos are HOST arrays of n_active entries, checked as rp_decoder_pool_step checks its own
+ *   (counts, distinct states in [0, n_states), pos in [0, max_len), anc_stride > pos). */
+RpStatus rp_dbg_dec_gemm(int32_t epi, const void* A, int32_t lda, int32_t M, const void* W, int32_t N, int32_t K, void* out,
+                         int32_t ldo, void* stream);
+RpStatus rp_dbg_dec_rows(int32_t mode, const void* a, const void* b, const int32_t* ia, int32_t rows, int32_t n, int32_t vocab,
+                         float eps, float scale, const int32_t* state, const int32_t* pos, int32_t n_active, int32_t n_states,
+                         int32_t nb, int32_t max_len, int64_t state_stride, void* o0, void* stream);
+RpStatus rp_dbg_dec_attention(int32_t cross, const void* q, int32_t ldq, const void* kv, int32_t ldkv, int32_t koff, int32_t voff,
+                              int32_t rows, int64_t state_stride, int32_t n_states, const int32_t* anc, int32_t anc_stride,
+                              const float* bias_tab, int32_t nbias, int32_t nb, int32_t num_heads, const int32_t* state,
+                              const int32_t* src_off, const int32_t* src_len, const int32_t* pos, int32_t n_active,
+                              int32_t max_len, void* out, int32_t ldo, void* stream);
 /* Tuning knobs (integers), e.g. "gemm_variant"; returns RP_E_INVALID for unknown names. */
 RpStatus rp_set_option(const char* name, int32_t value);
 

@@ -221,6 +221,25 @@ __global__ __launch_bounds__(256) void dec_attention_kernel(const bf16_t* __rest
                       anc + (size_t)row * astride, tab, nbias, slots.pos[slot] + 1, out + (size_t)row * ldo, h);
 }
 
+// The step's two attention launches over the n_active * nb rows of a slot table (dec_step_launch and the test entry
+// rp_dbg_dec_attention both launch through here): the dynamic LDS holds the call's longest key list.
+void launch_dec_self_attention(const bf16_t* q, int ldq, const bf16_t* cache, int ldkv, int koff, int voff, int rows,
+                               size_t state_stride, const int32_t* anc, int astride, const float* tab, int nbias, int nb,
+                               int H, const DecSlots& slots, int n_active, bf16_t* out, int ldo, hipStream_t s) {
+  int max_keys = 0;
+  for (int a = 0; a < n_active; ++a) max_keys = std::max(max_keys, slots.pos[a] + 1);
+  hipLaunchKernelGGL((dec_attention_kernel<false>), dim3(H, n_active * nb), dim3(256), max_keys * sizeof(float), s, q, ldq,
+                     cache, ldkv, koff, voff, rows, state_stride, anc, astride, tab, nbias, nb, slots, out, ldo);
+}
+void launch_dec_cross_attention(const bf16_t* q, int ldq, const bf16_t* ckv, int ldkv, int koff, int voff, int nb, int H,
+                                const DecSlots& slots, int n_active, bf16_t* out, int ldo, hipStream_t s) {
+  int max_src = 0;
+  for (int a = 0; a < n_active; ++a) max_src = std::max(max_src, slots.src_len[a]);
+  hipLaunchKernelGGL((dec_attention_kernel<true>), dim3(H, n_active * nb), dim3(256), max_src * sizeof(float), s, q, ldq, ckv,
+                     ldkv, koff, voff, 0, (size_t)0, (const int32_t*)nullptr, 0, (const float*)nullptr, 1, nb, slots, out,
+                     ldo);
+}
+
 // cache row pos[slot] * nb + beam of the row's state <- the k, v columns of qkv[row]
 __global__ __launch_bounds__(256) void dec_store_kv_kernel(const bf16_t* __restrict__ qkv, int inner,
                                                            bf16_t* __restrict__ cache, size_t state_stride, int nb,
@@ -1044,11 +1063,6 @@ namespace {
 RpStatus dec_step_launch(RpDecoder* d, const DecWs& w, const DecSlots& slots, int n_active, const int32_t* tokens,
                          const int32_t* anc, int astride, int nb, int max_len, float* logprobs, hipStream_t s) {
   RpStatus st;
-  int max_src = 0, max_keys = 0;  // the attentions' LDS: the longest key list of the call
-  for (int a = 0; a < n_active; ++a) {
-    max_src = std::max(max_src, slots.src_len[a]);
-    max_keys = std::max(max_keys, slots.pos[a] + 1);
-  }
   const RpT5Config& c = d->cfg;
   const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
   const float eps = c.layer_norm_eps;
@@ -1063,16 +1077,14 @@ RpStatus dec_step_launch(RpDecoder* d, const DecWs& w, const DecSlots& slots, in
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_self, w.h, D, eps, 1.f);
     if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.wqkv, 3 * inner, D, w.qkv, 3 * inner, s))) return st;
     hipLaunchKernelGGL(dec_store_kv_kernel, dim3(M), dim3(256), 0, s, w.qkv, inner, cache, state_stride, nb, slots);
-    hipLaunchKernelGGL((dec_attention_kernel<false>), dim3(H, M), dim3(256), max_keys * sizeof(float), s, w.qkv, 3 * inner,
-                       cache, 2 * inner, 0, inner, rows, state_stride, anc, astride, d->bias_tab, d->nbias, nb, slots,
-                       w.att, inner);
+    launch_dec_self_attention(w.qkv, 3 * inner, cache, 2 * inner, 0, inner, rows, state_stride, anc, astride, d->bias_tab,
+                              d->nbias, nb, H, slots, n_active, w.att, inner, s);
     if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.wo, D, inner, w.x, D, s))) return st;
     // cross-attention (T5LayerCrossAttention): no position bias, all of the state's source keys
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_cross, w.h, D, eps, 1.f);
     if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.cq, inner, D, w.qkv, inner, s))) return st;
-    hipLaunchKernelGGL((dec_attention_kernel<true>), dim3(H, M), dim3(256), max_src * sizeof(float), s, w.qkv, inner, w.ckv,
-                       ldckv, 2 * i * inner, (2 * i + 1) * inner, 0, (size_t)0, (const int32_t*)nullptr, 0,
-                       (const float*)nullptr, 1, nb, slots, w.att, inner);
+    launch_dec_cross_attention(w.qkv, inner, w.ckv, ldckv, 2 * i * inner, (2 * i + 1) * inner, nb, H, slots, n_active, w.att,
+                               inner, s);
     if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.co, D, inner, w.x, D, s))) return st;
     // gated-GELU FFN (T5LayerFF / T5DenseGatedActDense)
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_ff, w.h, D, eps, 1.f);
@@ -1188,6 +1200,135 @@ extern "C" RpStatus rp_decoder_pool_step(RpDecoder* d, int32_t n_slots, int32_t 
   const DecWs w = dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, (char*)ws);
   if (ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
   return dec_step_launch(d, w, slots, n_active, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
+}
+
+// ---- the decode step's kernels one at a time (test-only: tests/test_decode_step_kernels_gpu.py) ---------------------------
+// Device pointers in, launch-only on the given stream, through the launch code dec_step_launch runs.
+extern "C" RpStatus rp_dbg_dec_gemm(int32_t epi, const void* A, int32_t lda, int32_t M, const void* W, int32_t N, int32_t K,
+                                    void* out, int32_t ldo, void* stream_) {
+  RP_REQUIRE(A && W && out, "null argument");
+  RP_REQUIRE(M >= 1 && N >= 1 && K >= 8 && K % 8 == 0, "M=%d N=%d K=%d (K a multiple of 8)", M, N, K);
+  RP_REQUIRE(lda >= K && lda % 8 == 0 && ldo >= N, "lda=%d (>= K, a multiple of 8), ldo=%d (>= N)", lda, ldo);
+  RP_REQUIRE((((uintptr_t)A | (uintptr_t)W) & 15) == 0, "A / W not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream_;
+  const bf16_t *a = (const bf16_t*)A, *w = (const bf16_t*)W;
+  switch (epi) {
+    case EPI_BF16: return launch_dec_gemm<EPI_BF16>(a, lda, M, w, N, K, out, ldo, s);
+    case EPI_RESID: return launch_dec_gemm<EPI_RESID>(a, lda, M, w, N, K, out, ldo, s);
+    case EPI_F32: return launch_dec_gemm<EPI_F32>(a, lda, M, w, N, K, out, ldo, s);
+    case EPI_GEGLU: return launch_dec_gemm<EPI_GEGLU>(a, lda, M, w, N, K, out, ldo, s);
+    default: return fail(RP_E_INVALID, "epi=%d", epi);
+  }
+}
+
+namespace {
+// a caller-supplied slot table under rp_decoder_pool_step's checks (state / pos are host arrays)
+RpStatus dbg_slots(DecSlots& slots, const int32_t* state, const int32_t* pos, int n_active, int n_states, int nb,
+                   int max_len) {
+  RP_REQUIRE(state && pos, "null slot table");
+  RP_REQUIRE(n_states >= 1 && n_states <= DEC_MAX_STATES, "states=%d (1..%d)", n_states, DEC_MAX_STATES);
+  RP_REQUIRE(n_active >= 1 && n_active <= n_states, "active slots=%d (1..states=%d)", n_active, n_states);
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "num_beams=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(n_active * nb <= DEC_MAX_ROWS, "rows = slots * num_beams = %d > %d", n_active * nb, DEC_MAX_ROWS);
+  RP_REQUIRE(max_len >= 1 && max_len <= DEC_MAX_KEYS, "max_len=%d (1..%d)", max_len, DEC_MAX_KEYS);
+  uint32_t seen = 0;
+  for (int a = 0; a < n_active; ++a) {
+    RP_REQUIRE(state[a] >= 0 && state[a] < n_states, "state[%d]=%d outside [0, states=%d)", a, state[a], n_states);
+    RP_REQUIRE(!(seen & (1u << state[a])), "state[%d]=%d names a state twice", a, state[a]);
+    seen |= 1u << state[a];
+    RP_REQUIRE(pos[a] >= 0 && pos[a] < max_len, "pos[%d]=%d outside [0, max_len=%d)", a, pos[a], max_len);
+    slots.state[a] = state[a];
+    slots.pos[a] = pos[a];
+  }
+  return RP_OK;
+}
+}  // namespace
+
+// The step's row kernels, one per mode (rows = grid size):
+//   0 embed        ia = tokens [rows], a = table f32 [vocab, n]; o0 = f32 [rows, n]
+//   1 rmsnorm      a = x f32 [rows, n], b = ln f32 [n]; o0 = bf16 [rows, n]; eps, scale
+//   2 log_softmax  o0 = f32 [rows, n], in place
+//   3 store_kv     a = qkv bf16 [n_active * nb, 3 n] (n = inner); o0 = caches bf16, state s at s * state_stride elements,
+//                  max_len * nb rows of 2 n each; the slot table (state, pos: host arrays) as rp_decoder_pool_step checks it
+extern "C" RpStatus rp_dbg_dec_rows(int32_t mode, const void* a, const void* b, const int32_t* ia, int32_t rows, int32_t n,
+                                    int32_t vocab, float eps, float scale, const int32_t* state, const int32_t* pos,
+                                    int32_t n_active, int32_t n_states, int32_t nb, int32_t max_len, int64_t state_stride,
+                                    void* o0, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  RP_REQUIRE(o0 && n >= 1, "bad argument");
+  switch (mode) {
+    case 0:
+      RP_REQUIRE(a && ia && rows >= 1 && vocab >= 1, "embed: bad argument");
+      hipLaunchKernelGGL(dec_embed_kernel, dim3(rows), dim3(256), 0, s, ia, (const float*)a, (float*)o0, n, vocab);
+      break;
+    case 1:
+      RP_REQUIRE(a && b && rows >= 1, "rmsnorm: bad argument");
+      hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(rows), dim3(256), 0, s, (const float*)a, (const float*)b, (bf16_t*)o0, n, eps,
+                         scale);
+      break;
+    case 2:
+      RP_REQUIRE(rows >= 1, "log_softmax: bad argument");
+      hipLaunchKernelGGL(dec_log_softmax_kernel, dim3(rows), dim3(256), 0, s, (float*)o0, n);
+      break;
+    case 3: {
+      DecSlots slots = {};
+      RpStatus st = dbg_slots(slots, state, pos, n_active, n_states, nb, max_len);
+      if (st) return st;
+      RP_REQUIRE(a && state_stride >= (int64_t)max_len * nb * 2 * n, "store_kv: state_stride=%lld < max_len * nb * 2 * inner",
+                 (long long)state_stride);
+      hipLaunchKernelGGL(dec_store_kv_kernel, dim3(n_active * nb), dim3(256), 0, s, (const bf16_t*)a, n, (bf16_t*)o0,
+                         (size_t)state_stride, nb, slots);
+      break;
+    }
+    default:
+      return fail(RP_E_INVALID, "mode=%d", mode);
+  }
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// The step's self- (cross = 0) or cross-attention launch over a caller-supplied slot table (state, src_off, src_len, pos:
+// host arrays of n_active entries), checked as rp_decoder_pool_step checks its own.
+//   self:  kv = the caches (state s at s * state_stride elements, `rows` = max_len * nb rows of ldkv), keys 0 .. pos[slot]
+//          through anc [n_active * nb, astride] (device), bias tab f32 [H, nbias]
+//   cross: kv = the cross K/V of `rows` rows of ldkv; slot a reads rows [src_off[a], src_off[a] + src_len[a]); no bias
+// K at column koff + 64 h, V at voff + 64 h; q [n_active * nb, ldq], out [n_active * nb, ldo], head h at column 64 h.
+extern "C" RpStatus rp_dbg_dec_attention(int32_t cross, const void* q, int32_t ldq, const void* kv, int32_t ldkv, int32_t koff,
+                                         int32_t voff, int32_t rows, int64_t state_stride, int32_t n_states,
+                                         const int32_t* anc, int32_t astride, const float* tab, int32_t nbias, int32_t nb,
+                                         int32_t H, const int32_t* state, const int32_t* src_off, const int32_t* src_len,
+                                         const int32_t* pos, int32_t n_active, int32_t max_len, void* out, int32_t ldo,
+                                         void* stream_) {
+  RP_REQUIRE(q && kv && out && (!cross || (src_off && src_len)), "null argument");
+  RP_REQUIRE(H >= 1 && ldq >= 64 * H && ldo >= 64 * H && ldq % 8 == 0, "H=%d ldq=%d ldo=%d", H, ldq, ldo);
+  RP_REQUIRE(ldkv % 8 == 0 && koff >= 0 && koff % 8 == 0 && voff >= 0 && koff + 64 * H <= ldkv && voff + 64 * H <= ldkv,
+             "ldkv=%d koff=%d voff=%d", ldkv, koff, voff);
+  RP_REQUIRE((((uintptr_t)q | (uintptr_t)kv) & 15) == 0, "q / kv not 16-byte aligned");
+  DecSlots slots = {};
+  RpStatus st = dbg_slots(slots, state, pos, n_active, n_states, nb, max_len);
+  if (st) return st;
+  hipStream_t s = (hipStream_t)stream_;
+  if (cross) {
+    for (int a = 0; a < n_active; ++a) {
+      RP_REQUIRE(src_len[a] >= 1 && src_len[a] <= DEC_MAX_KEYS, "src_len[%d]=%d (1..%d)", a, src_len[a], DEC_MAX_KEYS);
+      RP_REQUIRE(src_off[a] >= 0 && (int64_t)src_off[a] + src_len[a] <= rows, "src_off[%d]=%d + src_len outside [0, rows=%d]", a,
+                 src_off[a], rows);
+      slots.src_off[a] = src_off[a];
+      slots.src_len[a] = src_len[a];
+    }
+    launch_dec_cross_attention((const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, koff, voff, nb, H, slots, n_active, (bf16_t*)out,
+                               ldo, s);
+  } else {
+    RP_REQUIRE(anc && tab && nbias >= 1, "self-attention: null ancestry / bias table");
+    RP_REQUIRE(rows == max_len * nb && state_stride >= (int64_t)rows * ldkv && state_stride % 8 == 0,
+               "rows=%d (max_len * nb), state_stride=%lld", rows, (long long)state_stride);
+    for (int a = 0; a < n_active; ++a)
+      RP_REQUIRE(astride >= pos[a] + 1, "anc_stride=%d < pos[%d] + 1 = %d", astride, a, pos[a] + 1);
+    launch_dec_self_attention((const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, koff, voff, rows, (size_t)state_stride, anc,
+                              astride, tab, nbias, nb, H, slots, n_active, (bf16_t*)out, ldo, s);
+  }
+  RP_CHECK_LAUNCH();
+  return RP_OK;
 }
 
 extern "C" RpStatus rp_beam_select_batch(const float* lp, const float* running, int32_t n_active, int32_t nb, int32_t V,

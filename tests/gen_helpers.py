@@ -297,6 +297,9 @@ DECODER_TOL = {  # measured: max, rms, top-2nb candidates max
     "g21b/hf": (0.05,),                             # 0.023 (against HF fp32)
     "g21c/hf": (0.8,),                              # 0.39 (against HF fp32)
     "generate/rescore": (0.8,),                     # 0.42 (sums over up to 127 tokens)
+    # tests/test_decode_step_kernels_gpu.py's whole step (d_model 520, d_ff 2056, H 3, V 300, buckets (8, 16)): 2 x measured,
+    # the rms capped at tiny-sharp/nb3's
+    "step-d520-f2056-h3-v300/nb5": (0.28, 0.025),   # 0.14, 0.014
 }
 # running scores per beam row in the selection checks (nats between rows): candidates then mix many rows
 SELECT_SPREAD = {"tiny-sharp": 0.2, "byt5-small-sharp": 1.0, "tiny-tied": 0.025}
