@@ -853,6 +853,43 @@ RpStatus rp_sample_pool_admit(const int32_t* states, const uint32_t* new_seeds, 
 RpStatus rp_sample_pool_rows(const int32_t* active, const int32_t* pos, int32_t n_active, int32_t n, int32_t nb,
                              int32_t max_len, const int32_t* seq, int32_t* tokens_next, void* stream);
 
+/* Sampling parameters per row ("Sampling parameters per request"): rp_sample_step and
+ * rp_sample_pool_step with a parameter table in place of temperature / top_k / top_p, and rp_sample_pool_admit with a
+ * count of live rows per admitted state.  The same kernels; none of the three takes a workspace.
+ *   params  device int32 [n, nb, 4], 16-byte aligned, indexed by (state, sample) like the other books.  Block
+ *           (state, sample) = { the bits of fp32 temperature, top_k, the bits of fp32 top_p, 0 }.
+ * Two statements hold for every row:
+ *   - a row whose block holds (T, k, p) draws what rp_sample_step / rp_sample_pool_step with (T, k, p) draws for it, bit
+ *     for bit in every book: 1 - top_p is formed on the device by the expression the by-value call evaluates on the
+ *     host, (float)(1.0 - (double)top_p), and s[v] = logprobs[v] / temperature is the same fp32 division;
+ *   - a row depends on its own block only: the workgroup of row (state, sample) reads those 16 bytes and no other part
+ *     of the table, and the step writes none of it.  A finished row reads nothing of it.
+ * The table is device memory, so its VALUES cannot be checked here: the caller validates them (reprover_amd:
+ * generation.check_sampling, before the upload).  A block outside rp_sample_step's domain (temperature <= 0 or not
+ * finite, top_k < 0, top_p outside (0, 1]) makes that row draw an unspecified token in [0, vocab) and nothing else:
+ * no access leaves the buffers, because top_k is used as an index only inside 0 < top_k < vocab, temperature and
+ * top_p enter arithmetic alone, and the token is clamped to [0, vocab) before it addresses logprobs; the row's other
+ * books are updated as for any token, and no other row is affected.
+ * rp_sample_pool_admit_rows: rp_sample_pool_admit, except that rows b >= n_live[i] of admitted state states[i] start
+ * with finished = 1 (they write pad, keep n_generated = 0 and cum_logprob = 0, and count as finished when the state's
+ * flags are reduced).  n_live is HOST int32 [m] and travels as a kernel argument.  rp_sample_pool_admit is the call with
+ * every n_live[i] = nb.
+ * RP_E_INVALID (nothing is launched; rp_last_error says which): everything rp_sample_step / rp_sample_pool_step /
+ * rp_sample_pool_admit refuse apart from the three by-value parameter checks, a null params, a params that is not
+ * 16-byte aligned, a null n_live, an n_live[i] outside 1..nb. */
+RpStatus rp_sample_step_rows(const float* logprobs, int32_t vocab, const int32_t* active, int32_t n_active, int32_t n,
+                             int32_t nb, const uint32_t* seeds, int32_t t, int32_t max_len, const void* params,
+                             int32_t eos, int32_t pad, int32_t* seq, int32_t* tokens_next, float* cum_logprob,
+                             int32_t* n_generated, int32_t* finished, void* stream);
+RpStatus rp_sample_pool_step_rows(const float* logprobs, int32_t vocab, const int32_t* active, const int32_t* pos,
+                                  int32_t n_active, int32_t n, int32_t nb, const uint32_t* seeds, int32_t max_len,
+                                  const void* params, int32_t eos, int32_t pad, int32_t* seq, int32_t* tokens_next,
+                                  float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream);
+RpStatus rp_sample_pool_admit_rows(const int32_t* states, const uint32_t* new_seeds, const int32_t* n_live, int32_t m,
+                                   int32_t n, int32_t nb, int32_t max_len, int32_t start_token, int32_t pad,
+                                   uint32_t* seeds, int32_t* seq, float* cum_logprob, int32_t* n_generated,
+                                   int32_t* finished, void* stream);
+
 /* Teacher-forced seq2seq forward (T5ForConditionalGeneration(input_ids, attention_mask, labels)) over
  * `batch` (source, target) pairs packed varlen; DESIGN.md section 10.  src_cu / tgt_cu are HOST int32
  * [batch + 1] prefix sums (start at 0): source b is rows src_cu[b] .. src_cu[b+1] of enc_bf16, target b

@@ -371,9 +371,17 @@ __device__ __forceinline__ void block_scan512(float* a, float* red) {
 //     prefix sum of e, Z its last value), else the last kept id of non-zero mass.
 // State arrays are indexed by (state, sample): a finished row writes pad and changes nothing else.
 // The row's position t = slots.pos[slot] (rp_sample_step: one t for every slot; rp_sample_pool_step: one per slot).
+// params (rp_sample_step_rows / rp_sample_pool_step_rows; null: the three by-value parameters, for every row) is the
+// table int32 [n, nb, 4] by (state, sample) of {temperature's bits, top_k, top_p's bits, 0}: the row's workgroup loads its
+// own 16 bytes once, every thread the same address, so the values - and the top-p branch with its barriers - are uniform
+// over the workgroup.  drop_mass is then the host's expression evaluated here, and the division below the same fp32
+// division: a row whose block holds (T, k, p) draws the bits of the by-value call with (T, k, p).  A block outside the
+// domain (the ABI cannot look into device memory) reaches no address outside the buffers: top_k indexes keys[] only
+// inside 0 < top_k < V <= 512, temperature and drop_mass enter arithmetic alone, and the token is clamped to [0, V).
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restrict__ lp, int V, int nb, DecSlots slots,
                                                           const uint32_t* __restrict__ seeds, int max_len,
-                                                          float temperature, int top_k, float drop_mass, int eos, int pad,
+                                                          float temperature, int top_k, float drop_mass,
+                                                          const int4* __restrict__ params, int eos, int pad,
                                                           int32_t* __restrict__ seq, int32_t* __restrict__ tokens_next,
                                                           float* __restrict__ cum, int32_t* __restrict__ ngen,
                                                           int32_t* __restrict__ finished) {
@@ -391,6 +399,12 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restric
       tokens_next[row] = pad;
     }
     return;
+  }
+  if (params) {  // a kernel argument: the same for the whole grid
+    const int4 own = params[idx];
+    temperature = __int_as_float(own.x);
+    top_k = own.y;
+    drop_mass = (float)(1.0 - (double)__int_as_float(own.z));
   }
   const float* r = lp + (size_t)row * V;
   for (int i = tid; i < DEC_SELECT_ROW; i += 256) keys[i] = (i < V) ? sel_key(r[i] / temperature, (uint32_t)i) : 0ull;
@@ -463,16 +477,21 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* __restric
 
 // The sampler's books for a slot's next tenant (rp_sample_pool_admit): the states listed in slots.state[0 .. gridDim.x),
 // one workgroup each, their seeds by value.  Every seq row of the state over all ld columns (the previous tenant wrote
-// them), its scores, counts and flags, its seed; nothing of another state.
+// them), its scores, counts and flags, its seed; nothing of another state.  The tenant's live rows travel the same way
+// (rp_sample_pool_admit_rows; rp_sample_pool_admit: nb for every state): rows b >= n_live start finished, so the step
+// writes pad for them and nothing else, and their n_generated stays 0.
 struct SampleSeeds {
   uint32_t seed[DEC_MAX_STATES];
 };
+struct SampleLive {
+  int32_t n_live[DEC_MAX_STATES];
+};
 
-__global__ __launch_bounds__(256) void sample_admit_kernel(DecSlots slots, SampleSeeds fresh, int nb, int ld, int start,
-                                                           int pad, uint32_t* __restrict__ seeds,
+__global__ __launch_bounds__(256) void sample_admit_kernel(DecSlots slots, SampleSeeds fresh, SampleLive live, int nb, int ld,
+                                                           int start, int pad, uint32_t* __restrict__ seeds,
                                                            int32_t* __restrict__ seq, float* __restrict__ cum,
                                                            int32_t* __restrict__ ngen, int32_t* __restrict__ finished) {
-  const int tid = threadIdx.x, state = slots.state[blockIdx.x];
+  const int tid = threadIdx.x, state = slots.state[blockIdx.x], n_live = live.n_live[blockIdx.x];
   for (int r = 0; r < nb; ++r) {
     int32_t* row = seq + ((size_t)state * nb + r) * ld;
     for (int c = tid; c < ld; c += 256) row[c] = c == 0 ? start : pad;
@@ -481,7 +500,7 @@ __global__ __launch_bounds__(256) void sample_admit_kernel(DecSlots slots, Sampl
     const size_t at = (size_t)state * nb + r;
     cum[at] = 0.f;
     ngen[at] = 0;
-    finished[at] = 0;
+    finished[at] = r >= n_live;
   }
   if (tid == 0) seeds[state] = fresh.seed[blockIdx.x];
 }
@@ -1381,24 +1400,61 @@ RpStatus sample_caps(int n, int nb, int listed, int max_len) {
   return RP_OK;
 }
 
-// rp_sample_step (pos null: every slot at t) and rp_sample_pool_step (slot a at pos[a]): one check list, one kernel
+// rp_sample_step (pos null: every slot at t) and rp_sample_pool_step (slot a at pos[a]), and their _rows forms (by_row:
+// the parameters come from the table `params`, the three by-value ones are not looked at): one check list, one kernel
 RpStatus sample_step_launch(const float* lp, int V, const int32_t* active, const int32_t* pos, int t, int n_active, int n,
-                            int nb, const uint32_t* seeds, int max_len, float temperature, int top_k, float top_p, int eos,
-                            int pad, int32_t* seq, int32_t* tokens_next, float* cum_logprob, int32_t* n_generated,
-                            int32_t* finished, void* stream_) {
+                            int nb, const uint32_t* seeds, int max_len, float temperature, int top_k, float top_p,
+                            bool by_row, const void* params, int eos, int pad, int32_t* seq, int32_t* tokens_next,
+                            float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream_) {
   RP_REQUIRE(lp && active && seeds && seq && tokens_next && cum_logprob && n_generated && finished, "null argument");
-  RP_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "temperature=%g, not a positive finite number", (double)temperature);
-  RP_REQUIRE(top_p > 0.f && top_p <= 1.f, "top_p=%g outside (0, 1]", (double)top_p);
-  RP_REQUIRE(top_k >= 0, "top_k=%d < 0", top_k);
+  if (by_row) {
+    RP_REQUIRE(params, "null argument (params)");
+    RP_REQUIRE((uintptr_t)params % 16 == 0, "params=%p is not 16-byte aligned", params);
+  } else {
+    RP_REQUIRE(temperature > 0.f && temperature <= 3.0e38f, "temperature=%g, not a positive finite number",
+               (double)temperature);
+    RP_REQUIRE(top_p > 0.f && top_p <= 1.f, "top_p=%g outside (0, 1]", (double)top_p);
+    RP_REQUIRE(top_k >= 0, "top_k=%d < 0", top_k);
+  }
   RP_REQUIRE(V >= 1 && V <= DEC_SELECT_ROW, "vocab=%d (1..%d)", V, DEC_SELECT_ROW);
   RpStatus st = sample_caps(n, nb, n_active, max_len);
   if (st) return st;
   if (!pos) RP_REQUIRE(t >= 0 && t + 1 < max_len, "t=%d: position t + 1 outside [1, max_len=%d)", t, max_len);
   DecSlots slots = {};
   if ((st = books_slots(&slots, active, pos, t, n_active, n, max_len))) return st;
-  const float drop_mass = (float)(1.0 - (double)top_p);
+  const float drop_mass = by_row ? 0.f : (float)(1.0 - (double)top_p);
   hipLaunchKernelGGL(sample_step_kernel, dim3(n_active * nb), dim3(256), 0, (hipStream_t)stream_, lp, V, nb, slots, seeds,
-                     max_len, temperature, top_k, drop_mass, eos, pad, seq, tokens_next, cum_logprob, n_generated, finished);
+                     max_len, by_row ? 1.f : temperature, by_row ? 0 : top_k, drop_mass, by_row ? (const int4*)params : nullptr,
+                     eos, pad, seq, tokens_next, cum_logprob, n_generated, finished);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// rp_sample_pool_admit (n_live null: every row of every admitted state is live) and rp_sample_pool_admit_rows
+RpStatus sample_admit_launch(const int32_t* states, const uint32_t* new_seeds, const int32_t* n_live, bool live_rows, int m,
+                             int n, int nb, int max_len, int start_token, int pad, uint32_t* seeds, int32_t* seq,
+                             float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream_) {
+  RP_REQUIRE(states && new_seeds && seeds && seq && cum_logprob && n_generated && finished && (n_live || !live_rows),
+             "null argument");
+  RpStatus st = sample_caps(n, nb, m, max_len);
+  if (st) return st;
+  RP_REQUIRE(m >= 1 && m <= n, "admitted states=%d (1..states=%d)", m, n);
+  DecSlots slots = {};
+  SampleSeeds fresh = {};
+  SampleLive live = {};
+  uint32_t seen = 0;
+  for (int j = 0; j < m; ++j) {
+    const int sidx = states[j];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "states[%d]=%d outside [0, states=%d)", j, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "states[%d]=%d names a state twice", j, sidx);
+    if (live_rows) RP_REQUIRE(n_live[j] >= 1 && n_live[j] <= nb, "n_live[%d]=%d outside 1..nb=%d", j, n_live[j], nb);
+    seen |= 1u << sidx;
+    slots.state[j] = sidx;
+    fresh.seed[j] = new_seeds[j];
+    live.n_live[j] = live_rows ? n_live[j] : nb;
+  }
+  hipLaunchKernelGGL(sample_admit_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream_, slots, fresh, live, nb, max_len,
+                     start_token, pad, seeds, seq, cum_logprob, n_generated, finished);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
@@ -1408,7 +1464,15 @@ extern "C" RpStatus rp_sample_step(const float* lp, int32_t V, const int32_t* ac
                                    int32_t nb, const uint32_t* seeds, int32_t t, int32_t max_len, float temperature,
                                    int32_t top_k, float top_p, int32_t eos, int32_t pad, int32_t* seq, int32_t* tokens_next,
                                    float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream_) {
-  return sample_step_launch(lp, V, active, nullptr, t, n_active, n, nb, seeds, max_len, temperature, top_k, top_p, eos, pad,
+  return sample_step_launch(lp, V, active, nullptr, t, n_active, n, nb, seeds, max_len, temperature, top_k, top_p, false,
+                            nullptr, eos, pad, seq, tokens_next, cum_logprob, n_generated, finished, stream_);
+}
+
+extern "C" RpStatus rp_sample_step_rows(const float* lp, int32_t V, const int32_t* active, int32_t n_active, int32_t n,
+                                        int32_t nb, const uint32_t* seeds, int32_t t, int32_t max_len, const void* params,
+                                        int32_t eos, int32_t pad, int32_t* seq, int32_t* tokens_next, float* cum_logprob,
+                                        int32_t* n_generated, int32_t* finished, void* stream_) {
+  return sample_step_launch(lp, V, active, nullptr, t, n_active, n, nb, seeds, max_len, 0.f, 0, 0.f, true, params, eos, pad,
                             seq, tokens_next, cum_logprob, n_generated, finished, stream_);
 }
 
@@ -1419,32 +1483,33 @@ extern "C" RpStatus rp_sample_pool_step(const float* lp, int32_t V, const int32_
                                         int32_t* seq, int32_t* tokens_next, float* cum_logprob, int32_t* n_generated,
                                         int32_t* finished, void* stream_) {
   RP_REQUIRE(pos, "null argument");
-  return sample_step_launch(lp, V, active, pos, 0, n_active, n, nb, seeds, max_len, temperature, top_k, top_p, eos, pad, seq,
+  return sample_step_launch(lp, V, active, pos, 0, n_active, n, nb, seeds, max_len, temperature, top_k, top_p, false, nullptr,
+                            eos, pad, seq, tokens_next, cum_logprob, n_generated, finished, stream_);
+}
+
+extern "C" RpStatus rp_sample_pool_step_rows(const float* lp, int32_t V, const int32_t* active, const int32_t* pos,
+                                             int32_t n_active, int32_t n, int32_t nb, const uint32_t* seeds, int32_t max_len,
+                                             const void* params, int32_t eos, int32_t pad, int32_t* seq,
+                                             int32_t* tokens_next, float* cum_logprob, int32_t* n_generated,
+                                             int32_t* finished, void* stream_) {
+  RP_REQUIRE(pos, "null argument");
+  return sample_step_launch(lp, V, active, pos, 0, n_active, n, nb, seeds, max_len, 0.f, 0, 0.f, true, params, eos, pad, seq,
                             tokens_next, cum_logprob, n_generated, finished, stream_);
 }
 
 extern "C" RpStatus rp_sample_pool_admit(const int32_t* states, const uint32_t* new_seeds, int32_t m, int32_t n, int32_t nb,
                                          int32_t max_len, int32_t start_token, int32_t pad, uint32_t* seeds, int32_t* seq,
                                          float* cum_logprob, int32_t* n_generated, int32_t* finished, void* stream_) {
-  RP_REQUIRE(states && new_seeds && seeds && seq && cum_logprob && n_generated && finished, "null argument");
-  RpStatus st = sample_caps(n, nb, m, max_len);
-  if (st) return st;
-  RP_REQUIRE(m >= 1 && m <= n, "admitted states=%d (1..states=%d)", m, n);
-  DecSlots slots = {};
-  SampleSeeds fresh = {};
-  uint32_t seen = 0;
-  for (int j = 0; j < m; ++j) {
-    const int sidx = states[j];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "states[%d]=%d outside [0, states=%d)", j, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "states[%d]=%d names a state twice", j, sidx);
-    seen |= 1u << sidx;
-    slots.state[j] = sidx;
-    fresh.seed[j] = new_seeds[j];
-  }
-  hipLaunchKernelGGL(sample_admit_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream_, slots, fresh, nb, max_len,
-                     start_token, pad, seeds, seq, cum_logprob, n_generated, finished);
-  RP_CHECK_LAUNCH();
-  return RP_OK;
+  return sample_admit_launch(states, new_seeds, nullptr, false, m, n, nb, max_len, start_token, pad, seeds, seq, cum_logprob,
+                             n_generated, finished, stream_);
+}
+
+extern "C" RpStatus rp_sample_pool_admit_rows(const int32_t* states, const uint32_t* new_seeds, const int32_t* n_live,
+                                              int32_t m, int32_t n, int32_t nb, int32_t max_len, int32_t start_token,
+                                              int32_t pad, uint32_t* seeds, int32_t* seq, float* cum_logprob,
+                                              int32_t* n_generated, int32_t* finished, void* stream_) {
+  return sample_admit_launch(states, new_seeds, n_live, true, m, n, nb, max_len, start_token, pad, seeds, seq, cum_logprob,
+                             n_generated, finished, stream_);
 }
 
 extern "C" RpStatus rp_sample_pool_rows(const int32_t* active, const int32_t* pos, int32_t n_active, int32_t n, int32_t nb,

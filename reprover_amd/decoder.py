@@ -25,9 +25,9 @@ import torch
 
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
-from .generation import (BeamBooks, BeamBooksPool, BeamSearchOutput, BeamSearchPool, SamplePool, SampleState, beam_search,
-                         beam_search_batch, beam_search_batch_device, check_sampling, greedy_search, greedy_search_batch,
-                         sample_search_batch)
+from .generation import (BeamBooks, BeamBooksPool, BeamSearchOutput, BeamSearchPool, SamplePool, SampleState, SamplingParams,
+                         beam_search, beam_search_batch, beam_search_batch_device, check_sampling, greedy_search,
+                         greedy_search_batch, sample_search_batch)
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
 # Dropout sites of the training step (include/reprover_hip.h RP_DROP_SITE_*; ``rp_dbg_dropout_mask`` reads a site's mask).
@@ -444,7 +444,9 @@ class HipT5Decoder:
     def sample_step(self, log_probs: torch.Tensor, active, t: int, state: SampleState, temperature: float = 1.0,
                     top_k: int = 0, top_p: float = 1.0, eos_token_id: int = 1, pad_token_id: int = 0) -> None:
         """One token per row of ``log_probs [n_active * nb, V]`` and the rows' books in ``state``, on the device
-        (``rp_sample_step``; ``sample_search_batch``'s ``sample_step``).  Nothing is read back."""
+        (``rp_sample_step``; ``sample_search_batch``'s ``sample_step``).  Nothing is read back.  With ``state.params``
+        set, every row takes its parameters from its own block of that table (``rp_sample_step_rows``) and the three
+        arguments are not looked at."""
         act = np.ascontiguousarray(active, dtype=np.int32)
         n, nb, max_len = state.seq.shape
         rows, V = log_probs.shape
@@ -453,6 +455,16 @@ class HipT5Decoder:
         for x in (log_probs, state.seeds, state.seq, state.cum_logprob, state.n_generated, state.finished, state.tokens):
             assert x.is_cuda and x.is_contiguous(), "rp_sample_step takes contiguous device tensors"
         assert log_probs.dtype == torch.float32
+        if state.params is not None:
+            table = self._sample_table(state, "rp_sample_step_rows")
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.rp_sample_step_rows(log_probs.data_ptr(), V, _pc(act), len(act), n, nb,
+                                                         state.seeds.data_ptr(), t, max_len, table, eos_token_id,
+                                                         pad_token_id, state.seq.data_ptr(), state.tokens.data_ptr(),
+                                                         state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
+                                                         state.finished.data_ptr(), _lib.current_stream()),
+                           "rp_sample_step_rows")
+            return
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rp_sample_step(log_probs.data_ptr(), V, act.ctypes.data_as(C.c_void_p), len(act), n, nb,
                                                 state.seeds.data_ptr(), t, max_len, temperature, top_k, top_p,
@@ -543,10 +555,21 @@ class HipT5Decoder:
         assert state.n_generated.dtype == state.finished.dtype == torch.int32 and state.cum_logprob.dtype == torch.float32
         return state.seq.shape
 
+    @staticmethod
+    def _sample_table(state: SampleState, entry: str) -> int:
+        """The address of ``state.params``, the parameter table int32 ``[n, nb, 4]`` by (state, sample)."""
+        n, nb, _ = state.seq.shape
+        t = state.params
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32, f"{entry} takes a contiguous int32 device table"
+        if tuple(t.shape) != (n, nb, 4):
+            raise _lib.HipLibraryError(f"{entry}: a parameter table of shape {tuple(t.shape)} for {(n, nb, 4)}")
+        return t.data_ptr()
+
     def sample_pool_step(self, log_probs: torch.Tensor, active, pos, state: SampleState, temperature: float = 1.0,
                          top_k: int = 0, top_p: float = 1.0, eos_token_id: int = 1, pad_token_id: int = 0) -> None:
         """``sample_step`` with slot ``active[a]`` at its own position ``pos[a]`` (``rp_sample_pool_step``;
-        ``SamplePool``'s ``sample_step``).  Nothing is read back."""
+        ``SamplePool``'s ``sample_step``).  Nothing is read back.  With ``state.params`` set:
+        ``rp_sample_pool_step_rows``, as in ``sample_step``."""
         act, p = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos))
         n, nb, max_len = self._sample_books(state, "rp_sample_pool_step")
         rows, V = log_probs.shape
@@ -554,6 +577,16 @@ class HipT5Decoder:
             raise _lib.HipLibraryError(f"sample_pool_step: {rows} rows, {len(p)} positions for {len(act)} slots of {nb} "
                                        "samples")
         assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dtype == torch.float32
+        if state.params is not None:
+            table = self._sample_table(state, "rp_sample_pool_step_rows")
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.rp_sample_pool_step_rows(log_probs.data_ptr(), V, _pc(act), _pc(p), len(act), n, nb,
+                                                              state.seeds.data_ptr(), max_len, table, eos_token_id,
+                                                              pad_token_id, state.seq.data_ptr(), state.tokens.data_ptr(),
+                                                              state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
+                                                              state.finished.data_ptr(), _lib.current_stream()),
+                           "rp_sample_pool_step_rows")
+            return
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rp_sample_pool_step(log_probs.data_ptr(), V, _pc(act), _pc(p), len(act), n, nb,
                                                      state.seeds.data_ptr(), max_len, temperature, top_k, top_p,
@@ -563,13 +596,40 @@ class HipT5Decoder:
                                                      _lib.current_stream()), "rp_sample_pool_step")
 
     def sample_books_admit(self, state: SampleState, states, seeds, decoder_start_token_id: int = 0,
-                           pad_token_id: int = 0) -> None:
-        """Fresh books for the next tenants of ``states`` with their 32-bit ``seeds`` (``rp_sample_pool_admit``)."""
+                           pad_token_id: int = 0, n_live=None, params: Optional[torch.Tensor] = None) -> None:
+        """Fresh books for the next tenants of ``states`` with their 32-bit ``seeds`` (``rp_sample_pool_admit``).
+        ``n_live`` (a count in ``1..nb`` per state): the rows from there on start finished
+        (``rp_sample_pool_admit_rows``).  ``params`` (host int32 ``[len(states), nb, 4]``): the tenants' blocks of
+        ``state.params``, written in one host-to-device copy - the blocks travel with their state indices in one buffer
+        and are scattered on the device - and no other block."""
         st = np.ascontiguousarray(states, dtype=np.int32)
         sd = np.array([int(x) & 0xFFFFFFFF for x in seeds], dtype=np.uint32)
         n, nb, max_len = self._sample_books(state, "rp_sample_pool_admit")
         if len(sd) != len(st):
             raise _lib.HipLibraryError(f"sample_books_admit: {len(sd)} seeds for {len(st)} states")
+        if params is not None:
+            self._sample_table(state, "sample_books_admit")
+            m = len(st)
+            if tuple(params.shape) != (m, nb, 4) or params.dtype != torch.int32 or params.is_cuda:
+                raise _lib.HipLibraryError(f"sample_books_admit: host int32 blocks of shape {(m, nb, 4)} expected, got "
+                                           f"{tuple(params.shape)} {params.dtype}")
+            if not all(0 <= int(s) < n for s in st) or len(set(st.tolist())) != m:
+                raise _lib.HipLibraryError(f"sample_books_admit: states {st.tolist()} not distinct in [0, {n})")
+            packed = torch.cat([params.reshape(m, nb * 4), torch.from_numpy(st).reshape(m, 1)], dim=1)
+            dev = packed.to(state.params.device)  # the admission's one upload
+            state.params.index_copy_(0, dev[:, -1].long(), dev[:, :-1].reshape(m, nb, 4))
+        if n_live is not None:
+            nl = np.ascontiguousarray(n_live, dtype=np.int32)
+            if len(nl) != len(st):
+                raise _lib.HipLibraryError(f"sample_books_admit: {len(nl)} live-row counts for {len(st)} states")
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.rp_sample_pool_admit_rows(_pc(st), _pc(sd), _pc(nl), len(st), n, nb, max_len,
+                                                               decoder_start_token_id, pad_token_id,
+                                                               state.seeds.data_ptr(), state.seq.data_ptr(),
+                                                               state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
+                                                               state.finished.data_ptr(), _lib.current_stream()),
+                           "rp_sample_pool_admit_rows")
+            return
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rp_sample_pool_admit(_pc(st), _pc(sd), len(st), n, nb, max_len, decoder_start_token_id,
                                                       pad_token_id, state.seeds.data_ptr(), state.seq.data_ptr(),
@@ -819,26 +879,41 @@ class HipT5Generator:
                               self.decoder.max_states(num_beams) if n_slots is None else n_slots, src_cap, sync_every)
 
     def sample(self, ids: np.ndarray, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
-               top_p: float = 1.0, seed: int = 0, length_penalty: float = 0.0, sync_every: int = 16) -> BeamSearchOutput:
-        """``num_samples`` sampled continuations of one source (``sample_many`` with one state)."""
+               top_p: float = 1.0, seed: int = 0, length_penalty: float = 0.0, sync_every: int = 16,
+               params: Optional[SamplingParams] = None) -> BeamSearchOutput:
+        """``num_samples`` sampled continuations of one source (``sample_many`` with one state; ``params``: this
+        source's ``SamplingParams`` in place of the three scalars)."""
         return self.sample_many([ids], num_samples, max_length, temperature, top_k, top_p, [seed], length_penalty,
-                                sync_every)[0]
+                                sync_every, None if params is None else [params])[0]
 
     def sample_many(self, sources, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
                     top_p: float = 1.0, seeds=None, length_penalty: float = 0.0,
-                    sync_every: int = 16) -> List[BeamSearchOutput]:
+                    sync_every: int = 16, params=None) -> List[BeamSearchOutput]:
         """Temperature / top-k / top-p sampling (``generate(do_sample=True, num_return_sequences=num_samples)``'s warper
         chain with a stated order and random number, DESIGN.md section 9 "Sampling") for several sources through one
         decode loop with no per-step readback.  ``seeds[i]`` (default ``0..n-1``) is source ``i``'s 32-bit seed.  Entry
         ``i`` equals ``sample(sources[i], ..., seed=seeds[i])`` bit for bit, tokens and scores, whichever states share
         the call, in whatever order, for any ``sync_every``.  Rows come in sample order; ``sequences_scores`` is the
-        sum of the model's log-probs of the drawn tokens divided by ``n_generated ** length_penalty``."""
+        sum of the model's log-probs of the drawn tokens divided by ``n_generated ** length_penalty``.
+
+        ``params`` (default None: the path above, ``rp_sample_step``): a sequence with one ``SamplingParams`` or None per
+        source, None standing for the call's ``temperature`` / ``top_k`` / ``top_p``.  The sources' blocks form the
+        parameter table, uploaded once, and every step is ``rp_sample_step_rows``: row ``b`` of entry ``i`` is the same
+        bits as row ``b`` of ``sample(sources[i], ...)`` at that row's own three values (DESIGN.md section 9,
+        "Sampling parameters per request")."""
         check_sampling(temperature, top_k, top_p)
         if num_samples < 1 or max_length <= 1:
             raise ValueError(f"num_samples={num_samples} (>= 1), max_length={max_length} (>= 2)")
         if sync_every < 1:
             raise ValueError(f"sync_every={sync_every} must be >= 1")
         sources = list(sources)
+        table = None
+        if params is not None:
+            params = list(params)
+            if len(params) != len(sources) or not sources:
+                raise ValueError(f"{len(params)} entries of params for {len(sources)} sources")
+            own = SamplingParams(temperature, top_k, top_p)
+            table = torch.stack([(own if q is None else q).rows(num_samples) for q in params])
         seeds = list(range(len(sources))) if seeds is None else [int(x) for x in seeds]
         if len(seeds) != len(sources):
             raise ValueError(f"{len(seeds)} seeds for {len(sources)} sources")
@@ -853,18 +928,24 @@ class HipT5Generator:
             lambda lp, active, t, state: dec.sample_step(lp, active, t, state, temperature, int(top_k), top_p, eos, 0),
             n, num_samples, max_length, seeds, length_penalty, eos_token_id=eos,
             decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
-            device=self.device)
+            device=self.device, params=table)
 
     def sample_stream(self, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
                       top_p: float = 1.0, length_penalty: float = 0.0, n_slots: Optional[int] = None, src_cap: int = 2048,
-                      sync_every: int = 16) -> "SampleStream":
+                      sync_every: int = 16, per_request: bool = False) -> "SampleStream":
         """A running sampled search that sources join while it runs (continuous batching): a
         ``SampleStream`` of ``n_slots`` places (default ``HipT5Decoder.max_states(num_samples)``) for sources of at most
         ``src_cap`` tokens, its books on the device (``generation.SamplePool``, ``rp_sample_pool_step``), nothing uploaded
         or read back per step, the finished flags read every ``sync_every`` steps.  Every ticket's output is
         ``sample(source, num_samples, max_length, temperature, top_k, top_p, seed, length_penalty)`` bit for bit, tokens
-        and scores, whichever sources share the stream, in whatever order and slots.  The sampling parameters are the
-        stream's.  The decoder carries one stream at a time, of either kind: opening another retires this one."""
+        and scores, whichever sources share the stream, in whatever order and slots.  The decoder carries one stream at a
+        time, of either kind: opening another retires this one.
+
+        The sampling parameters are the stream's unless ``per_request=True``: then ``submit(ids, seed, params,
+        num_samples)`` takes a ``SamplingParams`` per ticket (None: the stream's three) and any ``1 <= num_samples <=``
+        the stream's (None: the stream's), and the ticket's output is ``sample(source, that num_samples, ..., seed,
+        params=those)``, bit for bit.  The stream then carries the parameter table on the device
+        (``rp_sample_pool_step_rows``), written at admission only."""
         check_sampling(temperature, top_k, top_p)
         if num_samples < 1 or max_length <= 1:
             raise ValueError(f"num_samples={num_samples} (>= 1), max_length={max_length} (>= 2)")
@@ -873,7 +954,8 @@ class HipT5Generator:
         if n_slots is not None and (int(n_slots) != n_slots or n_slots < 1):
             raise ValueError(f"n_slots={n_slots} must be an integer >= 1 (or None)")
         return SampleStream(self, num_samples, max_length, temperature, int(top_k), top_p, length_penalty,
-                            self.decoder.max_states(num_samples) if n_slots is None else n_slots, src_cap, int(sync_every))
+                            self.decoder.max_states(num_samples) if n_slots is None else n_slots, src_cap, int(sync_every),
+                            bool(per_request))
 
 
 class GenerateStream:
@@ -958,10 +1040,12 @@ class SampleStream(GenerateStream):
     ``GenerateStream``'s admission (the newcomers encoded together, one packed encoder pass) and its retirement rule.
     ``submit(ids, seed)`` queues a source with its 32-bit seed and returns its ticket; ``step()`` takes one decode step
     and returns the ``(ticket, BeamSearchOutput)`` pairs its sync points delivered; ``drain()`` steps until the stream
-    is idle."""
+    is idle.  Opened with ``per_request``, ``submit`` also takes the ticket's ``SamplingParams`` and ``num_samples``
+    (``SamplePool``'s ``per_request``); otherwise either is a ``ValueError``."""
 
     def __init__(self, generator: HipT5Generator, num_samples: int, max_length: int, temperature: float, top_k: int,
-                 top_p: float, length_penalty: float, n_slots: int, src_cap: int, sync_every: int):
+                 top_p: float, length_penalty: float, n_slots: int, src_cap: int, sync_every: int,
+                 per_request: bool = False):
         dec = self._open(generator, n_slots, num_samples, max_length, src_cap)
         eos = generator.cfg.get("eos_token_id", 1)
         self.pool = SamplePool(
@@ -970,10 +1054,14 @@ class SampleStream(GenerateStream):
                                                                          eos, 0),
             n_slots, num_samples, max_length, length_penalty,
             decoder_start_token_id=generator.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
-            device=generator.device, books_admit=dec.sample_books_admit, rows=dec.sample_books_rows)
+            device=generator.device, books_admit=dec.sample_books_admit, rows=dec.sample_books_rows,
+            **(dict(per_request=True, params=SamplingParams(temperature, top_k, top_p)) if per_request else {}))
+        self.num_samples, self.per_request = int(num_samples), bool(per_request)
 
-    def submit(self, ids, seed: int) -> int:
-        return self.pool.submit(self._source(ids), seed)
+    def submit(self, ids, seed: int, params: Optional[SamplingParams] = None, num_samples: Optional[int] = None) -> int:
+        if params is None and num_samples is None:
+            return self.pool.submit(self._source(ids), seed)
+        return self.pool.submit(self._source(ids), seed, params, num_samples)
 
 
 class HipSeq2SeqGradients:

@@ -39,13 +39,17 @@ slot between two steps and is stepped at its own position, and its output is ret
 ``beam_books_admit_host``, ``beam_pool_advance_host`` and ``beam_books_rows_host`` restate its three kernels.
 ``SamplePool`` is the same pool for the sampled search: the sampler's books (``SampleState``) for ``n_slots`` states, a
 position per slot (``rp_sample_pool_step``), one forced sync point when a slot reaches ``max_length - 1``;
-``sample_books_admit_host`` and ``sample_books_rows_host`` restate its other two kernels.
+``sample_books_admit_host`` and ``sample_books_rows_host`` restate its other two kernels.  ``SamplingParams`` and the
+pool's ``per_request`` make the sampling parameters and the number of samples a property of the request: a parameter
+table by (state, sample) in ``SampleState.params`` (``rp_sample_step_rows`` / ``rp_sample_pool_step_rows``;
+``sample_row_params_host`` restates the lookup) and a live-row count per admitted state (``rp_sample_pool_admit_rows``).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 NEG = -1.0e9  # HF's masking constant (utils.py: running_beam_scores[:, 1:] = -1e9, ... * -1.0e9)
@@ -817,6 +821,9 @@ class SampleState:
     n_generated: torch.Tensor  # int32 [n, nb]
     finished: torch.Tensor     # int32 [n, nb]
     tokens: torch.Tensor       # int32 [n * nb]: the next step's tokens by row (slot * nb + sample)
+    # int32 [n, nb, 4] or None: the parameter table by (state, sample), rows of {temperature's fp32 bits, top_k, top_p's
+    # fp32 bits, 0} (``SamplingParams.rows``).  None: the sampling parameters are ``sample_step``'s own, one set per call.
+    params: Optional[torch.Tensor] = None
 
 
 def check_sampling(temperature: float, top_k: int, top_p: float) -> None:
@@ -829,10 +836,60 @@ def check_sampling(temperature: float, top_k: int, top_p: float) -> None:
         raise ValueError(f"top_p={top_p} must lie in (0, 1]")
 
 
+def _f32_bits(x: float) -> int:
+    """The bits of ``x`` as fp32, as the int32 that holds them."""
+    return int(np.array([x], dtype=np.float32).view(np.int32)[0])
+
+
+class SamplingParams:
+    """One request's sampling parameters.  Each of ``temperature``, ``top_k`` and ``top_p`` is a scalar (every sample of
+    the state) or a sequence with one value per sample (a ladder over the state's samples).  ``rows(nb)`` is the state's
+    part of the sampler's parameter table."""
+
+    def __init__(self, temperature=1.0, top_k=0, top_p=1.0):
+        self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
+
+    def __repr__(self) -> str:
+        return f"SamplingParams(temperature={self.temperature!r}, top_k={self.top_k!r}, top_p={self.top_p!r})"
+
+    def values(self, nb: int) -> List[Tuple[float, int, float]]:
+        """``(temperature, top_k, top_p)`` of each of ``nb`` samples, every one through ``check_sampling``;
+        ``ValueError`` for a sequence that does not hold ``nb`` values."""
+        nb = int(nb)
+        if nb < 1:
+            raise ValueError(f"num_samples={nb} must be >= 1")
+        cols = []
+        for name in ("temperature", "top_k", "top_p"):
+            v = getattr(self, name)
+            if isinstance(v, (str, bytes)):
+                raise ValueError(f"{name}={v!r} is not a number or a sequence of numbers")
+            if hasattr(v, "__len__"):
+                if len(v) != nb:
+                    raise ValueError(f"{name} holds {len(v)} values for {nb} samples")
+                cols.append(list(v))
+            else:
+                cols.append([v] * nb)
+        out = []
+        for T, k, p in zip(*cols):
+            check_sampling(T, k, p)
+            if int(k) >= 2 ** 31:
+                raise ValueError(f"top_k={k} does not fit 32 bits")
+            out.append((float(T), int(k), float(p)))
+        return out
+
+    def rows(self, nb: int) -> torch.Tensor:
+        """int32 ``[nb, 4]``: per sample the bits of fp32 ``temperature``, ``top_k``, the bits of fp32 ``top_p``, 0."""
+        vals = self.values(nb)
+        with np.errstate(over="ignore"):
+            for T, _, p in vals:  # the domain holds for the fp32 values the kernel receives, too
+                check_sampling(float(np.float32(T)), 0, float(np.float32(p)))
+        return torch.tensor([[_f32_bits(T), k, _f32_bits(p), 0] for T, k, p in vals], dtype=torch.int32)
+
+
 def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: int, num_samples: int, max_length: int,
                         seeds: Sequence[int], length_penalty: float = 0.0, eos_token_id: int = 1,
                         decoder_start_token_id: int = 0, pad_token_id: int = 0, sync_every: int = 16,
-                        device=None) -> List[BeamSearchOutput]:
+                        device=None, params: Optional[torch.Tensor] = None) -> List[BeamSearchOutput]:
     """The sampling loop: ``num_states`` sources in lockstep with ``num_samples`` independent rows each; per position one
     ``step_many`` and one ``sample_step``, nothing read back.  Every ``sync_every`` positions the finished flags are
     read once and the states whose samples have all finished leave the active list; the loop ends when it is empty or
@@ -848,6 +905,10 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
     - ``sample_step(log_probs, active, t, state)``: draws one token per row and updates ``state`` (``SampleState``) as
       ``rp_sample_step`` does: token to ``seq[.., t + 1]`` and ``tokens``, the model's log-prob added to ``cum_logprob``,
       ``n_generated`` incremented, ``finished`` set at EOS; a finished row writes pad and nothing else.
+    - ``params``: the parameter table int32 ``[num_states, num_samples, 4]`` (``SamplingParams.rows`` per state), or None.
+      It becomes ``state.params``, from which ``sample_step`` takes row ``(state, sample)``'s parameters in place of
+      its own; then row ``b`` of entry ``i`` is the same bits as row ``b`` of the search of source ``i`` alone in which
+      every sample has the parameters of block ``(i, b)``.
 
     Returns per state ``sequences [num_samples, out_len]`` (start token first, pad after EOS, trimmed to the state's
     longest sample) in sample order and ``sequences_scores = cum_logprob / n_generated ** length_penalty`` (the
@@ -867,11 +928,17 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
         finished=torch.zeros((n, nb), dtype=torch.int32),
         tokens=torch.full((n * nb,), decoder_start_token_id, dtype=torch.int32))
     st.seq[:, :, 0] = decoder_start_token_id
+    if params is not None:
+        if tuple(params.shape) != (n, nb, 4) or params.dtype != torch.int32:
+            raise ValueError(f"params of shape {tuple(params.shape)}, {params.dtype} for int32 {(n, nb, 4)}")
+        st.params = params.contiguous()
     ancestry = (torch.arange(max_length, dtype=torch.int32)[None] * nb
                 + (torch.arange(n * nb, dtype=torch.int32) % nb)[:, None]).contiguous()
     if device is not None:
         for f in ("seeds", "seq", "cum_logprob", "n_generated", "finished", "tokens"):
             setattr(st, f, getattr(st, f).to(device))
+        if st.params is not None:
+            st.params = st.params.to(device)  # the search's one upload of the table
         ancestry = ancestry.to(device)
     active = list(range(n))
     t = 0
@@ -898,15 +965,21 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
 
 def sample_search(step: Callable, sample_step: Callable, num_samples: int, max_length: int, seed: int = 0,
                   length_penalty: float = 0.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
-                  pad_token_id: int = 0, sync_every: int = 16, device=None) -> BeamSearchOutput:
-    """``sample_search_batch`` with one state: ``step(tokens, ancestry, t)``, ``sample_step`` as there."""
+                  pad_token_id: int = 0, sync_every: int = 16, device=None,
+                  params: Optional[torch.Tensor] = None) -> BeamSearchOutput:
+    """``sample_search_batch`` with one state: ``step(tokens, ancestry, t)``, ``sample_step`` as there; ``params`` is the
+    state's int32 ``[num_samples, 4]`` block (``SamplingParams.rows``) or None."""
     return sample_search_batch(lambda active, tokens, ancestry, t: step(tokens, ancestry, t), sample_step, 1,
                                num_samples, max_length, [seed], length_penalty, eos_token_id, decoder_start_token_id,
-                               pad_token_id, sync_every, device)[0]
+                               pad_token_id, sync_every, device, None if params is None else params[None])[0]
 
 
 # ---- continuous batching for the sampled search: a position per slot ---------------------------------------------------
 SAMPLE_POOL_MUTANTS = ("shared_position", "admit_not_reset", "stale_tokens")
+# ... and for the parameters and live rows per request: "stale_params" leaves the previous tenant's parameter blocks in
+# place at admission, "params_by_row" reads the table at the launch row instead of (state, sample), "dead_rows_live"
+# ignores the live-row count
+SAMPLE_PARAMS_MUTANTS = ("stale_params", "params_by_row", "dead_rows_live")
 
 
 def _seed_bits(seed: int) -> int:
@@ -916,22 +989,51 @@ def _seed_bits(seed: int) -> int:
 
 
 def sample_books_admit_host(state: SampleState, states: Sequence[int], seeds: Sequence[int],
-                            decoder_start_token_id: int = 0, pad_token_id: int = 0, mutant: Optional[str] = None) -> None:
+                            decoder_start_token_id: int = 0, pad_token_id: int = 0, mutant: Optional[str] = None,
+                            n_live: Optional[Sequence[int]] = None, params: Optional[torch.Tensor] = None) -> None:
     """``rp_sample_pool_admit`` on host books: for ``states`` only, ``seeds[s]`` set, every ``seq`` row pad over all
     ``max_length`` columns with the start token in column 0 (a previous tenant wrote them), ``cum_logprob``,
     ``n_generated`` and ``finished`` zero.  Nothing of another state and nothing by row is touched.  ``mutant``
-    "admit_not_reset" (``SAMPLE_POOL_MUTANTS``): ``seq`` and ``finished`` stay as the last tenant left them."""
-    assert mutant is None or mutant in SAMPLE_POOL_MUTANTS, mutant
-    n = state.seq.shape[0]
+    "admit_not_reset" (``SAMPLE_POOL_MUTANTS``): ``seq`` and ``finished`` stay as the last tenant left them.
+
+    ``n_live`` (one count in ``1..nb`` per admitted state; ``rp_sample_pool_admit_rows``): rows ``b >= n_live[i]`` of
+    ``states[i]`` start with ``finished = 1``.  ``params`` (int32 ``[len(states), nb, 4]``): the admitted states' blocks
+    of ``state.params``, and no other block.  ``mutant`` "stale_params" (``SAMPLE_PARAMS_MUTANTS``) leaves the blocks as
+    they were, "dead_rows_live" ignores ``n_live``."""
+    assert mutant is None or mutant in SAMPLE_POOL_MUTANTS + SAMPLE_PARAMS_MUTANTS, mutant
+    n, nb, _ = state.seq.shape
     assert len(states) == len(seeds) and len(set(states)) == len(states) and all(0 <= s < n for s in states)
-    for s, seed in zip(states, seeds):
+    assert n_live is None or (len(n_live) == len(states) and all(1 <= k <= nb for k in n_live)), n_live
+    assert params is None or (state.params is not None and tuple(params.shape) == (len(states), nb, 4))
+    for j, (s, seed) in enumerate(zip(states, seeds)):
         state.seeds[s] = _seed_bits(seed)
         if mutant != "admit_not_reset":
             state.seq[s] = pad_token_id
             state.seq[s, :, 0] = decoder_start_token_id
             state.finished[s] = 0
+            if n_live is not None and mutant != "dead_rows_live":
+                state.finished[s, int(n_live[j]):] = 1
         state.cum_logprob[s] = 0.0
         state.n_generated[s] = 0
+        if params is not None and mutant != "stale_params":
+            state.params[s] = params[j].to(state.params.device)
+
+
+def sample_row_params_host(state: SampleState, active: Sequence[int], mutant: Optional[str] = None):
+    """The table lookup of ``rp_sample_step_rows`` / ``rp_sample_pool_step_rows`` on host books: per launch row
+    ``a * nb + b`` the ``(temperature, top_k, top_p)`` of block ``(active[a], b)`` of ``state.params``, the two floats
+    as the fp32 values the kernel receives.  ``mutant`` "params_by_row" (``SAMPLE_PARAMS_MUTANTS``): block ``a * nb + b``
+    of the flat table, the launch row's, instead."""
+    assert mutant is None or mutant in SAMPLE_PARAMS_MUTANTS, mutant
+    n, nb, _ = state.seq.shape
+    assert state.params is not None and tuple(state.params.shape) == (n, nb, 4) and state.params.dtype == torch.int32
+    table = state.params.cpu().contiguous().numpy().reshape(n * nb, 4)
+    out = []
+    for a, s in enumerate(active):
+        for b in range(nb):
+            w = table[a * nb + b if mutant == "params_by_row" else s * nb + b]
+            out.append((float(w[0:1].view(np.float32)[0]), int(w[1]), float(w[2:3].view(np.float32)[0])))
+    return out
 
 
 def sample_books_rows_host(state: SampleState, active: Sequence[int], pos: Sequence[int]) -> None:
@@ -981,13 +1083,30 @@ class SamplePool:
 
     ``mutant`` (``SAMPLE_POOL_MUTANTS``) plants a known bug: "shared_position" samples every slot at the first slot's
     position, "admit_not_reset" leaves the previous tenant's ``seq`` / ``finished`` in place (host default), and
-    "stale_tokens" skips ``rows`` after the active list changed."""
+    "stale_tokens" skips ``rows`` after the active list changed.
+
+    ``per_request=True`` (default off: everything above, call for call): the sampling parameters and the number of
+    samples belong to the ticket.  The books carry the parameter table ``state.params`` (int32 ``[n_slots, nb, 4]``),
+    from which ``sample_step`` takes row ``(state, sample)``'s parameters, and ``submit(source, seed, params,
+    num_samples)`` takes a ``SamplingParams`` (None: ``params``, the pool's own, default ``SamplingParams()``) and any
+    ``1 <= num_samples <= nb`` (None: ``nb``).  At admission ``books_admit`` is called with two keywords more,
+    ``n_live`` (the tenants' ``num_samples``) and ``params`` (their blocks, int32 ``[m, nb, 4]``; the rows past
+    ``num_samples`` hold the default parameters and are never read): ``rp_sample_pool_admit_rows`` and one upload of the
+    blocks.  Nothing is uploaded per step.  Rows ``b >= num_samples`` start finished: they are stepped like any finished
+    row (fed pad, their outputs ignored), keep ``n_generated = 0`` and do not delay the state's departure.  The ticket's
+    output has ``num_samples`` rows, trimmed to its longest live sample, and equals ``sample_search`` of that source
+    alone with ``num_samples`` rows at that seed and those parameters: row ``b`` of the engine's step depends on no
+    other row, its random number on (seed, sample, position), its parameters on (state, sample).  ``mutant``
+    (``SAMPLE_PARAMS_MUTANTS``, host default of ``books_admit``): "stale_params" and "dead_rows_live";
+    "params_by_row" is ``sample_row_params_host``'s, for a host ``sample_step``."""
 
     def __init__(self, admit: Callable, step: Callable, sample_step: Callable, n_slots: int, num_samples: int,
                  max_length: int, length_penalty: float = 0.0, decoder_start_token_id: int = 0, pad_token_id: int = 0,
                  sync_every: int = 16, device=None, books_admit: Optional[Callable] = None,
-                 rows: Optional[Callable] = None, to_host: Callable = lambda x: x.cpu(), mutant: Optional[str] = None):
-        assert mutant is None or mutant in SAMPLE_POOL_MUTANTS, mutant
+                 rows: Optional[Callable] = None, to_host: Callable = lambda x: x.cpu(), mutant: Optional[str] = None,
+                 per_request: bool = False, params: Optional[SamplingParams] = None):
+        assert mutant is None or mutant in SAMPLE_POOL_MUTANTS + SAMPLE_PARAMS_MUTANTS, mutant
+        assert per_request or (params is None and mutant not in SAMPLE_PARAMS_MUTANTS), "these need per_request=True"
         if int(n_slots) < 1 or int(num_samples) < 1:
             raise ValueError(f"n_slots={n_slots} and num_samples={num_samples} must be >= 1")
         if max_length <= 1:
@@ -999,9 +1118,14 @@ class SamplePool:
         self.sync_every, self.length_penalty, self.mutant = int(sync_every), length_penalty, mutant
         self.start, self.pad = decoder_start_token_id, pad_token_id
         self._admit, self._step, self._sample_step, self._to_host = admit, step, sample_step, to_host
-        self._books_admit = books_admit or (lambda st, states, seeds, start, pad: sample_books_admit_host(
-            st, states, seeds, start, pad, mutant="admit_not_reset" if mutant == "admit_not_reset" else None))
+        host_mutant = mutant if mutant in ("admit_not_reset", "stale_params", "dead_rows_live") else None
+        self._books_admit = books_admit or (lambda st, states, seeds, start, pad, **kw: sample_books_admit_host(
+            st, states, seeds, start, pad, mutant=host_mutant, **kw))
         self._rows = rows or sample_books_rows_host
+        self.per_request = bool(per_request)
+        self._own = None                                             # per_request: the pool's own block [nb, 4]
+        self._request = {}                                           # per_request: ticket -> (num_samples, block)
+        self._live = [nb] * n                                        # per slot: its tenant's num_samples
         self.state = SampleState(  # every state is admitted before use
             seeds=torch.zeros(n, dtype=torch.int32, device=device),
             seq=torch.zeros((n, nb, L), dtype=torch.int32, device=device),
@@ -1009,6 +1133,11 @@ class SamplePool:
             n_generated=torch.zeros((n, nb), dtype=torch.int32, device=device),
             finished=torch.zeros((n, nb), dtype=torch.int32, device=device),
             tokens=torch.zeros(n * nb, dtype=torch.int32, device=device))
+        if self.per_request:
+            self._own = (params or SamplingParams()).rows(nb)
+            self._pad_block = SamplingParams().rows(nb)  # what the rows past a tenant's num_samples hold
+            table = self._own[None].repeat(n, 1, 1).contiguous()
+            self.state.params = table if device is None else table.to(device)
         ancestry = (torch.arange(L, dtype=torch.int32)[None] * nb
                     + (torch.arange(n * nb, dtype=torch.int32) % nb)[:, None]).contiguous()
         self.ancestry = ancestry if device is None else ancestry.to(device)
@@ -1029,10 +1158,27 @@ class SamplePool:
     def in_flight(self) -> int:
         return sum(t is not None for t in self._ticket)
 
-    def submit(self, source, seed: int) -> int:
-        """Queue a source with its 32-bit seed; its ticket names it in ``step``'s return."""
+    def submit(self, source, seed: int, params: Optional[SamplingParams] = None,
+               num_samples: Optional[int] = None) -> int:
+        """Queue a source with its 32-bit seed; its ticket names it in ``step``'s return.  With ``per_request``:
+        ``params`` are the ticket's sampling parameters (None: the pool's own) and ``num_samples`` its number of rows
+        (None: the pool's); without it either is a ``ValueError``."""
+        request = None
+        if not self.per_request:
+            if params is not None or num_samples is not None:
+                raise ValueError("params / num_samples per ticket need a pool opened with per_request=True")
+        else:
+            k = self.nb if num_samples is None else num_samples
+            if int(k) != k or not 1 <= k <= self.nb:
+                raise ValueError(f"num_samples={num_samples} must be an integer in 1..{self.nb}, the pool's num_samples")
+            k = int(k)
+            # (every row of a ticket's own parameters goes through check_sampling here)
+            block = torch.cat([self._own[:k] if params is None else params.rows(k), self._pad_block[k:]])
+            request = (k, block)
         ticket = self._next_ticket
         self._next_ticket += 1
+        if request is not None:
+            self._request[ticket] = request
         self._queue.append((ticket, source, int(seed)))
         return ticket
 
@@ -1046,10 +1192,12 @@ class SamplePool:
         host = self._to_host(buf)
         out = []
         for j, s in enumerate(stopped):
+            k = self._live[s]  # the tenant's rows: the rows past them never drew (n_generated 0), so the trim is the live rows'
             ngen = host[j, nb * L + nb :]
-            cum = host[j, nb * L : nb * L + nb].clone().view(torch.float32)
-            seq = host[j, : nb * L].view(nb, L)[:, : 1 + int(ngen.max())].long().clone()
-            out.append((self._ticket[s], BeamSearchOutput(seq, cum / ngen.to(torch.float32) ** float(self.length_penalty))))
+            cum = host[j, nb * L : nb * L + nb].clone().view(torch.float32)[:k]
+            seq = host[j, : nb * L].view(nb, L)[:k, : 1 + int(ngen.max())].long().clone()
+            out.append((self._ticket[s],
+                        BeamSearchOutput(seq, cum / ngen[:k].to(torch.float32) ** float(self.length_penalty))))
         return out
 
     def _sync(self) -> List[Tuple[int, BeamSearchOutput]]:
@@ -1070,7 +1218,14 @@ class SamplePool:
         if take:
             new, self._queue = self._queue[:take], self._queue[take:]
             self._admit(free[:take], [src for _, src, _ in new])
-            self._books_admit(self.state, free[:take], [seed for _, _, seed in new], self.start, self.pad)
+            if self.per_request:
+                requests = [self._request.pop(ticket) for ticket, _, _ in new]
+                self._books_admit(self.state, free[:take], [seed for _, _, seed in new], self.start, self.pad,
+                                  n_live=[k for k, _ in requests], params=torch.stack([blk for _, blk in requests]))
+                for s, (k, _) in zip(free, requests):
+                    self._live[s] = k
+            else:
+                self._books_admit(self.state, free[:take], [seed for _, _, seed in new], self.start, self.pad)
             for s, (ticket, _, _) in zip(free, new):
                 self._ticket[s], self._pos[s] = ticket, 0
             changed = True

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Tuple
 
 from ..common import Pos, format_augmented_state, remove_marks, zip_strict
 from ..decoder import HipT5Generator
-from ..generation import check_sampling
+from ..generation import SamplingParams, check_sampling
 from ..retrieval.model import PremiseRetriever
 from ..tokenizer import ByT5Tokenizer, encode_one
 
@@ -48,13 +48,23 @@ class HuggingFaceGenerator(TacticGenerator):
     ``await generate(...)`` calls share one ``HipT5Generator.sample_stream`` (``sample_stream_slots`` places, default the
     engine's cap; its finished flags read every ``sample_sync_every`` steps) through the same driver.  A call takes its
     seed when it submits, in call order, so ``asyncio.gather(generate(a), generate(b))`` equals ``generate_sync(a)`` then
-    ``generate_sync(b)`` on a fresh object with the same ``seed``."""
+    ``generate_sync(b)`` on a fresh object with the same ``seed``.
+
+    Sampling parameters per request: ``generate``, ``generate_sync`` (keyword ``sampling``, a ``SamplingParams``) and
+    ``batch_generate_sync`` (keyword ``sampling``, a sequence with one ``SamplingParams`` or None per state) sample that
+    state under its own temperature / top-k / top-p - scalars or a ladder over its ``num_samples`` samples - in place of
+    the object's; None is the object's.  It needs ``do_sample=True``.  With ``sample_stream=True`` it also needs
+    ``per_request_sampling=True``: the stream is then opened per request (``sample_stream(per_request=True)``) with
+    ``sample_stream_samples`` rows (default: the first call's ``num_samples``), and a call with ``num_samples`` up to
+    that joins the running stream with that many live rows instead of waiting for it to drain; a call that asks for
+    more rows waits and re-opens.  Seeds are taken at submit time in call order, as above."""
 
     def __init__(self, model_path: str, device, max_inp_seq_len: int, max_oup_seq_len: int, length_penalty: float,
                  template: str = "%s", do_sample: bool = False, temperature: float = 1.0, top_k: int = 0,
                  top_p: float = 1.0, seed: int = 0, beam_sync_every: Optional[int] = None, continuous: bool = False,
                  continuous_slots: Optional[int] = None, sample_stream: bool = False,
-                 sample_stream_slots: Optional[int] = None, sample_sync_every: int = 16):
+                 sample_stream_slots: Optional[int] = None, sample_sync_every: int = 16,
+                 per_request_sampling: bool = False, sample_stream_samples: Optional[int] = None):
         self.model_path = model_path
         self.device = device
         self.max_inp_seq_len = max_inp_seq_len
@@ -82,6 +92,13 @@ class HuggingFaceGenerator(TacticGenerator):
             raise ValueError(f"sample_sync_every={sample_sync_every} must be an integer >= 1")
         self.sample_stream, self.sample_stream_slots = bool(sample_stream), sample_stream_slots
         self.sample_sync_every = int(sample_sync_every)
+        if per_request_sampling and not sample_stream:
+            raise ValueError("per_request_sampling=True is a property of the sample stream: it needs sample_stream=True")
+        if sample_stream_samples is not None and (not per_request_sampling or int(sample_stream_samples) != sample_stream_samples
+                                                  or sample_stream_samples < 1):
+            raise ValueError(f"sample_stream_samples={sample_stream_samples} must be an integer >= 1 (or None) and needs "
+                             "per_request_sampling=True")
+        self.per_request_sampling, self.sample_stream_samples = bool(per_request_sampling), sample_stream_samples
         self._stream = None       # the open GenerateStream (or SampleStream) and its num_samples
         self._stream_beams: Optional[int] = None
         self._waiters: Dict[int, "asyncio.Future"] = {}  # ticket -> the generate() call that awaits it
@@ -100,13 +117,31 @@ class HuggingFaceGenerator(TacticGenerator):
             out.append(h ^ (h >> 16))
         return out
 
-    def _sampled(self, ids, num_samples: int) -> List[List[Tuple[str, float]]]:
+    def _check_request(self, sampling, n: Optional[int] = None):
+        """``sampling`` as given to a call: refused without ``do_sample``; for ``n`` states, a sequence of ``n``."""
+        if sampling is None:
+            return None
+        if not self.do_sample:
+            raise ValueError("sampling parameters per request need do_sample=True")
+        if n is None:
+            if not isinstance(sampling, SamplingParams):
+                raise ValueError(f"sampling={sampling!r} is not a SamplingParams")
+            return sampling
+        sampling = list(sampling)
+        if len(sampling) != n or not all(q is None or isinstance(q, SamplingParams) for q in sampling):
+            raise ValueError(f"sampling holds {len(sampling)} entries for {n} states (one SamplingParams or None each)")
+        return sampling
+
+    def _sampled(self, ids, num_samples: int, sampling=None) -> List[List[Tuple[str, float]]]:
         results: List[List[Tuple[str, float]]] = []
         cap = self.generator.decoder.max_states(num_samples)
+        if sampling is not None and all(q is None for q in sampling):
+            sampling = None  # the object's parameters throughout: the call as it always was
         for i in range(0, len(ids), cap):
             chunk = ids[i : i + cap]
+            kw = {} if sampling is None else {"params": sampling[i : i + cap]}
             outs = self.generator.sample_many(chunk, num_samples, self.max_oup_seq_len, self.temperature, self.top_k,
-                                              self.top_p, self._next_seeds(len(chunk)), self.length_penalty)
+                                              self.top_p, self._next_seeds(len(chunk)), self.length_penalty, **kw)
             results.extend(self._sampled_suggestions(out) for out in outs)
         return results
 
@@ -130,11 +165,12 @@ class HuggingFaceGenerator(TacticGenerator):
         self.tokenizer = ByT5Tokenizer()
 
     def generate_sync(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
-                      num_samples: int) -> List[Tuple[str, float]]:
+                      num_samples: int, *, sampling: Optional[SamplingParams] = None) -> List[Tuple[str, float]]:
+        sampling = self._check_request(sampling)
         state = self.template % state
         ids = encode_one(state, self.max_inp_seq_len)  # tokenizer(state, max_length=..., truncation=True)
         if self.do_sample:
-            return self._sampled([ids], num_samples)[0]
+            return self._sampled([ids], num_samples, None if sampling is None else [sampling])[0]
         out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty, **self._books)
         return self._suggestions(out, num_samples)
 
@@ -151,9 +187,14 @@ class HuggingFaceGenerator(TacticGenerator):
         return list(zip_strict(output_text, output_score))
 
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
-                       num_samples: int) -> List[Tuple[str, float]]:
+                       num_samples: int, *, sampling: Optional[SamplingParams] = None) -> List[Tuple[str, float]]:
+        sampling = self._check_request(sampling)
         if not (self.continuous or self.sample_stream):
-            return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+            return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples, sampling=sampling)
+        if self.per_request_sampling:
+            return await self._generate_per_request(state, num_samples, sampling)
+        if sampling is not None:
+            raise ValueError("sampling parameters per request on a sample stream need per_request_sampling=True")
         ids = encode_one(self.template % state, self.max_inp_seq_len)
         # a stream serves one num_samples: a call with another waits until it has drained (the driver runs meanwhile)
         while self._stream is not None and self._stream_beams != num_samples and (self._stream.queued
@@ -180,6 +221,32 @@ class HuggingFaceGenerator(TacticGenerator):
         out = await future
         return self._sampled_suggestions(out) if self.sample_stream else self._suggestions(out, num_samples)
 
+    async def _generate_per_request(self, state: str, num_samples: int,
+                                    sampling: Optional[SamplingParams]) -> List[Tuple[str, float]]:
+        """``generate`` on a stream opened per request: a call whose ``num_samples`` fits the stream's rows joins it with
+        that many live rows and its own parameters; only a call that asks for more rows waits for the drain."""
+        if int(num_samples) != num_samples or num_samples < 1:
+            raise ValueError(f"num_samples={num_samples} must be an integer >= 1")
+        if sampling is not None:
+            sampling.rows(num_samples)  # refused here, before a seed is taken
+        ids = encode_one(self.template % state, self.max_inp_seq_len)
+        while self._stream is not None and num_samples > self._stream_beams and (self._stream.queued
+                                                                                 or self._stream.in_flight):
+            await asyncio.sleep(0)
+        if self._stream is None or num_samples > self._stream_beams:
+            rows = max(int(num_samples), int(self.sample_stream_samples or 0))
+            self._stream = self.generator.sample_stream(rows, self.max_oup_seq_len, self.temperature, self.top_k,
+                                                        self.top_p, self.length_penalty,
+                                                        n_slots=self.sample_stream_slots, src_cap=self.max_inp_seq_len,
+                                                        sync_every=self.sample_sync_every, per_request=True)
+            self._stream_beams = rows
+        future = asyncio.get_running_loop().create_future()
+        ticket = self._stream.submit(ids, self._next_seeds(1)[0], params=sampling, num_samples=num_samples)
+        self._waiters[ticket] = future
+        if self._driver is None:
+            self._driver = asyncio.ensure_future(self._drive())
+        return self._sampled_suggestions(await future)
+
     async def _drive(self) -> None:
         """Step the open stream while it has work, resolving the waiting calls as their states finish; an exception
         reaches every call that waits.  Between steps the event loop runs, so that other calls can submit (or, once the
@@ -202,12 +269,13 @@ class HuggingFaceGenerator(TacticGenerator):
             self._driver = None
 
     def batch_generate_sync(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
-                            theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:
+                            theorem_poses: List[Pos], num_samples: int, *, sampling=None) -> List[List[Tuple[str, float]]]:
         """``generate_sync`` for several states through one decode loop (``HipT5Generator.generate_many``): entry ``i``
-        is ``generate_sync(states[i], ...)`` exactly, de-duplication order included."""
+        is ``generate_sync(states[i], ...)`` exactly (with ``sampling=sampling[i]``), de-duplication order included."""
+        sampling = self._check_request(sampling, len(states))
         ids = [encode_one(self.template % s, self.max_inp_seq_len) for s in states]
         if self.do_sample:
-            return self._sampled(ids, num_samples)
+            return self._sampled(ids, num_samples, sampling)
         results: List[List[Tuple[str, float]]] = []
         cap = self.generator.decoder.max_states(num_samples)  # the engine's cap on states per call
         for i in range(0, len(ids), cap):
@@ -229,7 +297,8 @@ class RetrievalAugmentedGenerator(TacticGenerator):
                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0,
                  beam_sync_every: Optional[int] = None, continuous: bool = False,
                  continuous_slots: Optional[int] = None, sample_stream: bool = False,
-                 sample_stream_slots: Optional[int] = None, sample_sync_every: int = 16) -> None:
+                 sample_stream_slots: Optional[int] = None, sample_sync_every: int = 16,
+                 per_request_sampling: bool = False, sample_stream_samples: Optional[int] = None) -> None:
         self.gen_path = gen_path
         self.ret_path = ret_path
         self.indexed_corpus_path = indexed_corpus_path
@@ -243,7 +312,9 @@ class RetrievalAugmentedGenerator(TacticGenerator):
                                            seed=seed, beam_sync_every=beam_sync_every, continuous=continuous,
                                            continuous_slots=continuous_slots, sample_stream=sample_stream,
                                            sample_stream_slots=sample_stream_slots,
-                                           sample_sync_every=sample_sync_every)
+                                           sample_sync_every=sample_sync_every,
+                                           per_request_sampling=per_request_sampling,
+                                           sample_stream_samples=sample_stream_samples)
 
     def initialize(self) -> None:
         self.hf_gen.initialize()
@@ -251,34 +322,40 @@ class RetrievalAugmentedGenerator(TacticGenerator):
         self.retriever.load_corpus(self.indexed_corpus_path)
 
     def generate_sync(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
-                      num_samples: int) -> List[Tuple[str, float]]:
+                      num_samples: int, *, sampling: Optional[SamplingParams] = None) -> List[Tuple[str, float]]:
+        self.hf_gen._check_request(sampling)
         retrieved_premises, _ = self.retriever.retrieve(state, file_path, theorem_full_name, theorem_pos,
                                                         self.max_num_retrieved)
         aug_state = format_augmented_state(state, retrieved_premises, self.max_inp_seq_len)
-        return self.hf_gen.generate_sync(aug_state, file_path, theorem_full_name, theorem_pos, num_samples)
+        kw = {} if sampling is None else {"sampling": sampling}
+        return self.hf_gen.generate_sync(aug_state, file_path, theorem_full_name, theorem_pos, num_samples, **kw)
 
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
-                       num_samples: int) -> List[Tuple[str, float]]:
+                       num_samples: int, *, sampling: Optional[SamplingParams] = None) -> List[Tuple[str, float]]:
+        kw = {} if sampling is None else {"sampling": sampling}
         if not (self.hf_gen.continuous or self.hf_gen.sample_stream):
-            return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples)
+            return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples, **kw)
+        self.hf_gen._check_request(sampling)
         retrieved_premises, _ = self.retriever.retrieve(state, file_path, theorem_full_name, theorem_pos,
                                                         self.max_num_retrieved)
         aug_state = format_augmented_state(state, retrieved_premises, self.max_inp_seq_len)
-        return await self.hf_gen.generate(aug_state, file_path, theorem_full_name, theorem_pos, num_samples)
+        return await self.hf_gen.generate(aug_state, file_path, theorem_full_name, theorem_pos, num_samples, **kw)
 
     def batch_generate_sync(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
-                            theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:
+                            theorem_poses: List[Pos], num_samples: int, *, sampling=None) -> List[List[Tuple[str, float]]]:
         """Retrieve per state (``retrieve``, as ``generate_sync``), format each augmented state, then one batched
         generate."""
+        sampling = self.hf_gen._check_request(sampling, len(states))
         aug_states = []
         for state, path, name, pos in zip_strict(states, file_paths, theorem_full_names, theorem_poses):
             retrieved_premises, _ = self.retriever.retrieve(state, path, name, pos, self.max_num_retrieved)
             aug_states.append(format_augmented_state(state, retrieved_premises, self.max_inp_seq_len))
-        return self.hf_gen.batch_generate_sync(aug_states, file_paths, theorem_full_names, theorem_poses, num_samples)
+        kw = {} if sampling is None else {"sampling": sampling}
+        return self.hf_gen.batch_generate_sync(aug_states, file_paths, theorem_full_names, theorem_poses, num_samples, **kw)
 
     async def batch_generate(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
                              theorem_poses: List[Pos], num_samples: int) -> List[List[Tuple[str, float]]]:
         return self.batch_generate_sync(states, file_paths, theorem_full_names, theorem_poses, num_samples)
 
 
-__all__ = ["TacticGenerator", "HuggingFaceGenerator", "RetrievalAugmentedGenerator"]
+__all__ = ["TacticGenerator", "HuggingFaceGenerator", "RetrievalAugmentedGenerator", "SamplingParams"]

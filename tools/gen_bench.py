@@ -47,6 +47,15 @@ multiplied by ``--eos-boost`` so that the states end at different lengths; the l
 plain synthetic weights everything runs to ``max_length`` and the comparison says nothing about admission.
 
     python tools/gen_bench.py --stream --sample [--eos-boost 4.0] [--reps 2] [--out FILE]
+
+``--stream --sample --per-request``: sampling parameters per request.  The same 16 sources through a ``sample_stream`` of
+8 slots twice in one process, alternating: once with the stream's scalars (``rp_sample_pool_step``, the parameters by
+value) and once on a stream opened ``per_request`` with the same values handed in per ticket
+(``rp_sample_pool_step_rows``, the parameter table).  Milliseconds per decode step of both, the table form as a ratio to
+the scalar form beside the scalar form's own spread over the repetitions, and whether the outputs are equal (they are the
+same bits by contract).  No threshold: the scalar form measured in the same run is the bar.
+
+    python tools/gen_bench.py --stream --sample --per-request [--reps 3] [--out profiles/gen_sample_params_bench.json]
 """
 from __future__ import annotations
 
@@ -339,6 +348,46 @@ def sample_stream_bench(gen, cfg, reps, eos_boost, nb=64, max_len=512, n_src=16,
             "outputs_identical": same}
 
 
+def sample_params_bench(gen, cfg, reps, eos_boost, nb=64, max_len=512, n_src=16, n_slots=8):
+    """``sample_stream_bench``'s sources through (a) a stream with the parameters by value and (b) a stream opened
+    ``per_request`` with the same values per ticket, alternating in one process: ms per decode step of both."""
+    from reprover_amd.generation import SamplingParams
+
+    rng = np.random.default_rng(0)
+    lens = [int(x) for x in rng.integers(64, 2049, size=n_src)]
+    srcs = [np.concatenate([rng.integers(3, 259, size=n - 1), [1]]).astype(np.int32) for n in lens]
+    seeds = list(range(100, 100 + n_src))
+    kw = dict(temperature=1.0, top_k=0, top_p=0.95)
+    L = cfg["num_decoder_layers"]
+
+    def stream(per_request, n=n_slots, length=max_len, sources=srcs):
+        st = gen.sample_stream(nb, length, n_slots=n, src_cap=2048, per_request=per_request, **kw)
+        extra = dict(params=SamplingParams(**kw), num_samples=nb) if per_request else {}
+        tickets = [st.submit(s, seed, **extra) for s, seed in zip(sources, seeds)]
+        got = dict(st.drain())
+        return [got[t] for t in tickets], st.steps
+
+    for per_request in (False, True):  # warm-up: code objects
+        stream(per_request, 2, 8, srcs[:1])
+    scalar_ms, table_ms, same, steps = [], [], True, 0
+    for _ in range(reps):
+        ms, (a, steps) = _timed(lambda: stream(False))
+        scalar_ms.append(ms / steps)
+        ms, (b, steps_b) = _timed(lambda: stream(True))
+        table_ms.append(ms / steps_b)
+        same = same and _same(a, b) and steps == steps_b
+    base = min(scalar_ms)
+    return {"metric": "gen_sample_params_bench", "measured": True, "rows": nb, "max_length": max_len, "sampling": kw,
+            "sync_every": 16, "eos_boost": eos_boost, "sources": n_src, "slots": n_slots,
+            "config": f"byt5-small ({L} decoder layers), sources of {min(lens)}..{max(lens)} bytes", "reps": reps,
+            "decode_steps": steps, "scalar_ms_per_step": [round(x, 4) for x in scalar_ms],
+            "table_ms_per_step": [round(x, 4) for x in table_ms],
+            "scalar_spread": round(max(scalar_ms) / base - 1.0, 4),
+            "ratio_table_over_scalar": round(min(table_ms) / base, 4),
+            "ratio_table_over_scalar_by_rep": [round(t / s_, 4) for t, s_ in zip(table_ms, scalar_ms)],
+            "outputs_identical": same}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -351,7 +400,11 @@ def main(argv=None):
     ap.add_argument("--stream", action="store_true", help="a stream of 8 slots against generate_many in chunks of 8")
     ap.add_argument("--eos-boost", type=float, default=4.0,
                     help="with --stream --sample: the factor on the EOS row of lm_head.weight (states end at different lengths)")
+    ap.add_argument("--per-request", action="store_true",
+                    help="with --stream --sample: the stream's scalars against the same values per ticket (the parameter table)")
     args = ap.parse_args(argv)
+    if args.per_request and not (args.stream and args.sample):
+        ap.error("--per-request goes with --stream --sample")
     if args.sync_every and (not (args.states or args.stream) or args.sample or min(args.sync_every) < 1):
         ap.error("--sync-every takes values >= 1 and goes with --states or --stream")
     if args.sample or args.stream:
@@ -361,7 +414,11 @@ def main(argv=None):
             sd["lm_head.weight"] = sd["lm_head.weight"].clone()
             sd["lm_head.weight"][1] *= args.eos_boost
         gen = HipT5Generator(cfg, sd, "cuda:0")
-        if args.stream and args.sample:
+        if args.per_request:
+            line = json.dumps(sample_params_bench(gen, cfg, max(args.reps, 3), args.eos_boost))
+            args.out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                "gen_sample_params_bench.json")
+        elif args.stream and args.sample:
             line = json.dumps(sample_stream_bench(gen, cfg, args.reps, args.eos_boost))
         elif args.stream and args.sync_every:
             line = json.dumps(stream_books_bench(gen, cfg, args.sync_every, args.reps))
