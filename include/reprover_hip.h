@@ -726,6 +726,41 @@ RpStatus rp_decoder_pool_step(RpDecoder* dec, int32_t n_slots, int32_t num_beams
                               const int32_t* tokens, const int32_t* ancestry, int32_t anc_stride, float* logprobs,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* rp_decoder_batch_step with a position per listed state: pos HOST int32 [n_active] in place of t, each checked as t
+ * is (0 <= pos < max_len, anc_stride >= pos + 1).  The same launch sequence; with every pos = t the same bits. */
+RpStatus rp_decoder_batch_step_pos(RpDecoder* dec, const int32_t* src_cu, int32_t n, const int32_t* active,
+                                   int32_t n_active, const int32_t* tokens, const int32_t* ancestry,
+                                   int32_t anc_stride, int32_t nb, const int32_t* pos, int32_t max_len,
+                                   float* logprobs, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Prompt prefill ("Tactic prefix").  A decoder prompt [start, b_1 .. b_P] is shared by
+ * all beams of its state, so one cache row per prompt position serves them all: beam 0's, row p * nb.  The
+ * prefill carries the first R = P prompt tokens (the prompt without its last token, which the search feeds
+ * itself at t = R) through the layers, all positions of all listed states in one launch sequence, and writes
+ * in every layer cache rows p * nb, p = 0 .. R - 1, of each listed state - nothing else of the cache, no
+ * lm_head, no log-softmax.  The rows are, bit for bit, those that R calls of rp_decoder_batch_step write for
+ * beam 0 when fed the prompt's tokens with identity ancestry.  Runs between steps: the activation block is its
+ * scratch, and it takes the rows in passes of at most n * nb (pool: n_slots * nb) rows, lower positions first.
+ *   states / slots  HOST int32 [m]: distinct, 1 <= m <= n (n_slots)
+ *   src_len         (pool) HOST int32 [m]: as rp_decoder_pool_step takes it
+ *   prompt_cu       HOST int32 [m + 1] prefix sums (start at 0): listed state j has R_j = prompt_cu[j+1] -
+ *                   prompt_cu[j] rows, 1 <= R_j, R_j + 1 < max_len
+ *   tokens          device int32 [prompt_cu[m]]: row prompt_cu[j] + p is position p of listed state j
+ *                   (clamped to the vocabulary on the device, as the step's)
+ *   anc             device int32 [anc_len]: the prompt ancestry anc[p] = p * nb, one vector for every row
+ *                   (entries are clamped to the state's cache); anc_len >= every R_j
+ * RP_E_INVALID (nothing is launched): a null pointer, a state or slot out of range or named twice,
+ * prompt_cu[0] != 0, an R_j outside the above, anc_len below an R_j, the caps of the step.  RP_E_WORKSPACE
+ * (nothing is launched): a workspace below rp_decoder_batch_workspace_bytes / rp_decoder_pool_workspace_bytes. */
+RpStatus rp_decoder_batch_prefill(RpDecoder* dec, const int32_t* src_cu, int32_t n, const int32_t* states,
+                                  const int32_t* prompt_cu, int32_t m, const int32_t* tokens, const int32_t* anc,
+                                  int32_t anc_len, int32_t nb, int32_t max_len, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+RpStatus rp_decoder_pool_prefill(RpDecoder* dec, int32_t n_slots, int32_t num_beams, int32_t max_len, int32_t src_cap,
+                                 const int32_t* slots, const int32_t* src_len, const int32_t* prompt_cu, int32_t m,
+                                 const int32_t* tokens, const int32_t* anc, int32_t anc_len, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 /* Beam books ("Per-step host sync, and device books"): beam search's bookkeeping -
  * what generation.py's _BeamState keeps on the host - in one caller-owned device block for n states, and one launch per
  * position that updates it from rp_beam_select_batch's outputs, so the host loop reads nothing back per

@@ -12,6 +12,10 @@
 // rp_decoder_batch_step / rp_decoder_batch_cross_kv / rp_beam_select_batch: there is one launch sequence.
 // rp_decoder_pool_step is that sequence with a position per slot (the batched call: every slot at t), over a workspace
 // whose slots states enter between steps (rp_decoder_pool_admit): continuous batching.
+// rp_decoder_batch_step_pos is the batched call with a position per listed state.  rp_decoder_batch_prefill /
+// rp_decoder_pool_prefill write a decoder prompt's cache rows - one per prompt position, beam 0's, shared by all beams of
+// the state - for all positions of all listed states in one launch sequence (dec_prefill_launch), with the step's own
+// row-wise kernels and dec_attention_row, so that the rows are the bits the step writes.
 // rp_sample_step (sampling) and rp_beam_books_init / rp_beam_advance (beam search) keep a search's bookkeeping on the
 // device, one more launch per step, so that the host loop reads nothing back per position.  rp_beam_pool_advance is
 // rp_beam_advance with a position per slot (one kernel: the uniform call has every slot at t), and rp_beam_books_admit /
@@ -247,6 +251,56 @@ __global__ __launch_bounds__(256) void dec_store_kv_kernel(const bf16_t* __restr
   const int row = blockIdx.x, slot = row / nb, b = row - slot * nb;
   bf16_t* dst = cache + (size_t)slots.state[slot] * state_stride + (size_t)(slots.pos[slot] * nb + b) * 2 * inner;
   for (int c = threadIdx.x; c < 2 * inner; c += 256) dst[c] = qkv[(size_t)row * 3 * inner + inner + c];
+}
+
+// ---- prompt prefill ("Tactic prefix") ---------------------------------------------------------------
+// The rows of one prefill pass, by segment: segment g is rows row0[g] .. row0[g + 1] of the pass (row0 ascending, the
+// last segment runs to the pass's end), the prompt positions pos0[g], pos0[g] + 1, ... of one state.  A prompt is shared
+// by the state's beams: the row at position p is stored as cache row p * nb (beam 0's) and nowhere else.
+struct DecSegs {
+  int32_t n;
+  int32_t state[DEC_MAX_STATES];
+  int32_t src_off[DEC_MAX_STATES];
+  int32_t src_len[DEC_MAX_STATES];
+  int32_t pos0[DEC_MAX_STATES];
+  int32_t row0[DEC_MAX_STATES];
+};
+__device__ __forceinline__ int dec_seg_of(const DecSegs& segs, int row) {
+  int g = 0;
+  for (int i = 1; i < segs.n; ++i)
+    if (row >= segs.row0[i]) g = i;
+  return g;
+}
+
+// cache row p * nb of the row's state <- the k, v columns of qkv[row], p the row's prompt position
+__global__ __launch_bounds__(256) void dec_prefill_store_kv_kernel(const bf16_t* __restrict__ qkv, int inner,
+                                                                   bf16_t* __restrict__ cache, size_t state_stride, int nb,
+                                                                   DecSegs segs) {
+  const int row = blockIdx.x, g = dec_seg_of(segs, row), p = segs.pos0[g] + (row - segs.row0[g]);
+  bf16_t* dst = cache + (size_t)segs.state[g] * state_stride + (size_t)p * nb * 2 * inner;
+  for (int c = threadIdx.x; c < 2 * inner; c += 256) dst[c] = qkv[(size_t)row * 3 * inner + inner + c];
+}
+
+// dec_attention_kernel for prompt rows: one (head, row) per workgroup, the row at position p of its segment's state.
+// Self-attention: p + 1 keys, key p' in cache row anc[p'] of the state (the caller's vector p' -> p' * nb, the same for
+// every row).  Cross-attention: all of the state's source keys.  dec_attention_row as the step runs it, so a row's bits
+// are those of the step at position p for beam 0.
+template <bool CROSS>
+__global__ __launch_bounds__(256) void dec_prefill_attention_kernel(const bf16_t* __restrict__ q, int ldq,
+                                                                    const bf16_t* __restrict__ kv, int ldkv, int koff,
+                                                                    int voff, int rows, size_t state_stride,
+                                                                    const int32_t* __restrict__ anc,
+                                                                    const float* __restrict__ tab, int nbias, DecSegs segs,
+                                                                    bf16_t* __restrict__ out, int ldo) {
+  extern __shared__ float s_sc[];
+  const int h = blockIdx.x, row = blockIdx.y;
+  const int g = dec_seg_of(segs, row);
+  if constexpr (CROSS)
+    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)segs.src_off[g] * ldkv, ldkv, koff, voff, segs.src_len[g],
+                      nullptr, nullptr, 1, segs.src_len[g], out + (size_t)row * ldo, h);
+  else
+    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)segs.state[g] * state_stride, ldkv, koff, voff, rows, anc,
+                      tab, nbias, segs.pos0[g] + (row - segs.row0[g]) + 1, out + (size_t)row * ldo, h);
 }
 
 __global__ __launch_bounds__(256) void dec_log_softmax_kernel(float* __restrict__ x, int V) {
@@ -1219,6 +1273,176 @@ extern "C" RpStatus rp_decoder_pool_step(RpDecoder* d, int32_t n_slots, int32_t 
   const DecWs w = dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, (char*)ws);
   if (ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
   return dec_step_launch(d, w, slots, n_active, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
+}
+
+// rp_decoder_batch_step with a position per listed state: dec_step_launch's third caller (the lockstep loop over states
+// whose prompts differ in length)
+extern "C" RpStatus rp_decoder_batch_step_pos(RpDecoder* d, const int32_t* src_cu, int32_t n, const int32_t* active,
+                                              int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
+                                              int32_t nb, const int32_t* pos, int32_t max_len, float* logprobs, void* ws,
+                                              size_t ws_bytes, void* stream_) {
+  int total = 0;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
+  if (st) return st;
+  RP_REQUIRE(active && pos && tokens && anc && logprobs, "null argument");
+  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
+  DecSlots slots = {};
+  uint32_t seen = 0;
+  for (int a = 0; a < n_active; ++a) {
+    const int sidx = active[a];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);
+    seen |= 1u << sidx;
+    RP_REQUIRE(pos[a] >= 0 && pos[a] < max_len, "pos[%d]=%d outside [0, max_len=%d)", a, pos[a], max_len);
+    RP_REQUIRE(astride >= pos[a] + 1, "anc_stride=%d < pos[%d] + 1 = %d", astride, a, pos[a] + 1);
+    slots.state[a] = sidx;
+    slots.src_off[a] = src_cu[sidx];
+    slots.src_len[a] = src_cu[sidx + 1] - src_cu[sidx];
+    slots.pos[a] = pos[a];
+  }
+  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
+  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  return dec_step_launch(d, w, slots, n_active, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
+}
+
+// ---- prompt prefill: the prompt rows of the listed states through the layers, all positions in one launch sequence --------
+namespace {
+struct PrefillState {
+  int state, src_off, src_len, rows;
+};
+
+// One pass: M <= the activation block's rows, rows in segment order, tokens[row] their tokens.  The step's sequence per
+// layer with the segment kernels in place of the slot kernels; all rows' K/V are stored before the self-attention reads
+// them.  The last layer ends at its cache store: nothing after it reaches the cache, and there is no lm_head.
+RpStatus dec_prefill_pass(RpDecoder* d, const DecWs& w, const DecSegs& segs, int M, int max_keys, const int32_t* tokens,
+                          const int32_t* anc, int nb, int max_len, hipStream_t s) {
+  RpStatus st;
+  const RpT5Config& c = d->cfg;
+  const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
+  const float eps = c.layer_norm_eps;
+  const int rows = max_len * nb, ldckv = L * 2 * inner;
+  const size_t layer_stride = (size_t)rows * 2 * inner, state_stride = (size_t)L * layer_stride;
+  bf16_t* ffn = w.h + (size_t)M * D;
+  int max_src = 0;
+  for (int g = 0; g < segs.n; ++g) max_src = std::max(max_src, segs.src_len[g]);
+  hipLaunchKernelGGL(dec_embed_kernel, dim3(M), dim3(256), 0, s, tokens, d->embed, w.x, D, V);
+  for (int i = 0; i < L; ++i) {
+    const RpDecoder::Layer& l = d->layers[i];
+    bf16_t* cache = w.cache + (size_t)i * layer_stride;
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_self, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.wqkv, 3 * inner, D, w.qkv, 3 * inner, s))) return st;
+    hipLaunchKernelGGL(dec_prefill_store_kv_kernel, dim3(M), dim3(256), 0, s, w.qkv, inner, cache, state_stride, nb, segs);
+    if (i == L - 1) break;
+    hipLaunchKernelGGL((dec_prefill_attention_kernel<false>), dim3(H, M), dim3(256), max_keys * sizeof(float), s, w.qkv,
+                       3 * inner, cache, 2 * inner, 0, inner, rows, state_stride, anc, d->bias_tab, d->nbias, segs, w.att,
+                       inner);
+    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.wo, D, inner, w.x, D, s))) return st;
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_cross, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.cq, inner, D, w.qkv, inner, s))) return st;
+    hipLaunchKernelGGL((dec_prefill_attention_kernel<true>), dim3(H, M), dim3(256), max_src * sizeof(float), s, w.qkv, inner,
+                       w.ckv, ldckv, 2 * i * inner, (2 * i + 1) * inner, 0, (size_t)0, (const int32_t*)nullptr,
+                       (const float*)nullptr, 1, segs, w.att, inner);
+    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.co, D, inner, w.x, D, s))) return st;
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_ff, w.h, D, eps, 1.f);
+    if ((st = launch_dec_gemm<EPI_GEGLU>(w.h, D, M, l.wi, F, D, ffn, F, s))) return st;
+    if ((st = launch_dec_gemm<EPI_RESID>(ffn, F, M, l.wo2, D, F, w.x, D, s))) return st;
+  }
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// The one routine behind rp_decoder_batch_prefill and rp_decoder_pool_prefill.  The prompt rows, state after state and
+// position after position (the order of `tokens`), are cut into passes of at most `cap` rows - the activation block's -
+// so a state's lower positions are stored, in every layer, before a later pass attends over them.
+RpStatus dec_prefill_launch(RpDecoder* d, const DecWs& w, const PrefillState* ps, int m, const int32_t* tokens,
+                            const int32_t* anc, int nb, int max_len, int cap, hipStream_t s) {
+  RpStatus st;
+  DecSegs segs = {};
+  int used = 0, first = 0, max_keys = 0, row = 0;
+  for (int j = 0; j < m; ++j) {
+    int p = 0;
+    while (p < ps[j].rows) {
+      const int take = std::min(ps[j].rows - p, cap - used);
+      const int g = segs.n++;
+      segs.state[g] = ps[j].state;
+      segs.src_off[g] = ps[j].src_off;
+      segs.src_len[g] = ps[j].src_len;
+      segs.pos0[g] = p;
+      segs.row0[g] = used;
+      used += take;
+      p += take;
+      row += take;
+      max_keys = std::max(max_keys, p);
+      if (used == cap || (j == m - 1 && p == ps[j].rows)) {
+        if ((st = dec_prefill_pass(d, w, segs, used, max_keys, tokens + first, anc, nb, max_len, s))) return st;
+        first = row;
+        used = max_keys = 0;
+        segs = DecSegs{};
+      }
+    }
+  }
+  return RP_OK;
+}
+
+// what both prefill entries check of the prompts: prompt_cu[0] = 0, 1 <= R_j, R_j + 1 < max_len, anc_len >= every R_j
+RpStatus prefill_check(const int32_t* prompt_cu, int m, int max_len, int anc_len) {
+  RP_REQUIRE(prompt_cu[0] == 0, "prompt_cu[0]=%d, not 0", prompt_cu[0]);
+  for (int j = 0; j < m; ++j) {
+    const int64_t R = (int64_t)prompt_cu[j + 1] - prompt_cu[j];
+    RP_REQUIRE(R >= 1, "prompt %d has %lld rows (>= 1)", j, (long long)R);
+    RP_REQUIRE(R + 1 < max_len, "prompt %d: %lld rows + 1 >= max_len=%d", j, (long long)R, max_len);
+    RP_REQUIRE(anc_len >= R, "anc_len=%d < the %lld rows of prompt %d", anc_len, (long long)R, j);
+  }
+  return RP_OK;
+}
+}  // namespace
+
+extern "C" RpStatus rp_decoder_batch_prefill(RpDecoder* d, const int32_t* src_cu, int32_t n, const int32_t* states,
+                                             const int32_t* prompt_cu, int32_t m, const int32_t* tokens,
+                                             const int32_t* anc, int32_t anc_len, int32_t nb, int32_t max_len, void* ws,
+                                             size_t ws_bytes, void* stream_) {
+  int total = 0;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
+  if (st) return st;
+  RP_REQUIRE(states && prompt_cu && tokens && anc, "null argument");
+  RP_REQUIRE(m >= 1 && m <= n, "listed states=%d (1..states=%d)", m, n);
+  if ((st = prefill_check(prompt_cu, m, max_len, anc_len))) return st;
+  PrefillState ps[DEC_MAX_STATES];
+  uint32_t seen = 0;
+  for (int j = 0; j < m; ++j) {
+    const int sidx = states[j];
+    RP_REQUIRE(sidx >= 0 && sidx < n, "states[%d]=%d outside [0, states=%d)", j, sidx, n);
+    RP_REQUIRE(!(seen & (1u << sidx)), "states[%d]=%d names a state twice", j, sidx);
+    seen |= 1u << sidx;
+    ps[j] = PrefillState{sidx, src_cu[sidx], src_cu[sidx + 1] - src_cu[sidx], prompt_cu[j + 1] - prompt_cu[j]};
+  }
+  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
+  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  return dec_prefill_launch(d, w, ps, m, tokens, anc, nb, max_len, n * nb, (hipStream_t)stream_);
+}
+
+extern "C" RpStatus rp_decoder_pool_prefill(RpDecoder* d, int32_t n_slots, int32_t nb, int32_t max_len, int32_t src_cap,
+                                            const int32_t* slot_ids, const int32_t* src_len, const int32_t* prompt_cu,
+                                            int32_t m, const int32_t* tokens, const int32_t* anc, int32_t anc_len,
+                                            void* ws, size_t ws_bytes, void* stream_) {
+  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap);
+  if (st) return st;
+  RP_REQUIRE(slot_ids && src_len && prompt_cu && tokens && anc && ws, "null argument");
+  RP_REQUIRE(m >= 1 && m <= n_slots, "listed slots=%d (1..slots=%d)", m, n_slots);
+  if ((st = prefill_check(prompt_cu, m, max_len, anc_len))) return st;
+  PrefillState ps[DEC_MAX_STATES];
+  uint32_t seen = 0;
+  for (int j = 0; j < m; ++j) {
+    const int sl = slot_ids[j];
+    RP_REQUIRE(sl >= 0 && sl < n_slots, "slots[%d]=%d outside [0, slots=%d)", j, sl, n_slots);
+    RP_REQUIRE(!(seen & (1u << sl)), "slots[%d]=%d names a slot twice", j, sl);
+    seen |= 1u << sl;
+    RP_REQUIRE(src_len[j] >= 1 && src_len[j] <= src_cap, "src_len[%d]=%d (1..src_cap=%d)", j, src_len[j], src_cap);
+    ps[j] = PrefillState{sl, sl * src_cap, src_len[j], prompt_cu[j + 1] - prompt_cu[j]};
+  }
+  const DecWs w = dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, (char*)ws);
+  if (ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  return dec_prefill_launch(d, w, ps, m, tokens, anc, nb, max_len, n_slots * nb, (hipStream_t)stream_);
 }
 
 // ---- the decode step's kernels one at a time (test-only: tests/test_decode_step_kernels_gpu.py) ---------------------------

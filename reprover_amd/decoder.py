@@ -368,14 +368,18 @@ class HipT5Decoder:
                        "rp_decoder_batch_cross_kv")
 
     def step_many(self, active, tokens: torch.Tensor, ancestry: torch.Tensor, out: Optional[torch.Tensor] = None,
-                  t: Optional[int] = None) -> torch.Tensor:
+                  t: Optional[int] = None, pos=None) -> torch.Tensor:
         """log-probs [n_active * nb, V] of one step for the states ``active`` (distinct indices into ``start_many``'s
         sources): row ``a * nb + b`` is beam ``b`` of state ``active[a]`` (``beam_search_batch``'s ``step_many``).
         The position is the table's last column; with ``t`` given it is ``t`` and ``ancestry`` a wider table of which
-        columns ``0..t`` are read (``sample_search_batch`` passes one table for the whole search)."""
+        columns ``0..t`` are read (``sample_search_batch`` passes one table for the whole search).  With ``pos`` (one
+        position per active state, in place of ``t``) the call is ``rp_decoder_batch_step_pos``: state ``active[a]`` at
+        ``pos[a]``, columns ``0..pos[a]`` of its rows read (``beam_search_batch`` over prompts of different lengths)."""
         cu, n, nb, max_len = self._many
         act = np.ascontiguousarray(active, dtype=np.int32)
         rows, T = ancestry.shape
+        if pos is not None and t is not None:
+            raise _lib.HipLibraryError("step_many: t= and pos= exclude each other")
         if t is not None and not 0 <= t < T:
             raise _lib.HipLibraryError(f"step_many: t={t} outside the {T} columns of the ancestry table")
         if rows != len(act) * nb or tokens.numel() != rows:
@@ -385,6 +389,16 @@ class HipT5Decoder:
         anc = ancestry.to(device=self.device, dtype=torch.int32).contiguous()
         if out is None:
             out = torch.empty((rows, self.V), dtype=torch.float32, device=self.device)
+        if pos is not None:
+            p = np.ascontiguousarray(pos, dtype=np.int32)
+            if len(p) != len(act):
+                raise _lib.HipLibraryError(f"step_many: {len(p)} positions for {len(act)} states")
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.rp_decoder_batch_step_pos(self._handle, _pc(cu), n, _pc(act), len(act), tok.data_ptr(),
+                                                               anc.data_ptr(), T, nb, _pc(p), max_len, out.data_ptr(),
+                                                               self._ws.data_ptr(), self._ws.numel(),
+                                                               _lib.current_stream()), "rp_decoder_batch_step_pos")
+            return out
         with torch.cuda.device(self.device):
             _lib.check(self._lib.rp_decoder_batch_step(self._handle, cu.ctypes.data_as(C.c_void_p), n,
                                                        act.ctypes.data_as(C.c_void_p), len(act), tok.data_ptr(),
@@ -393,6 +407,30 @@ class HipT5Decoder:
                                                        self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
                        "rp_decoder_batch_step")
         return out
+
+    def _prefill_args(self, rows, nb: int):
+        """(prompt_cu host int32, device tokens, device ancestry vector p -> p * nb, its length) of a prefill call."""
+        rows = [np.asarray(r, dtype=np.int32).reshape(-1) for r in rows]
+        cu = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+        tok = torch.from_numpy(np.concatenate(rows).astype(np.int32)).to(self.device)
+        longest = int(max(len(r) for r in rows))
+        anc = (torch.arange(longest, dtype=torch.int32) * int(nb)).to(self.device)
+        return cu, tok, anc, longest
+
+    def prefill_many(self, states, rows) -> None:
+        """The prompt rows of ``states`` (distinct indices into ``start_many``'s sources) in one pass
+        (``rp_decoder_batch_prefill``, ``beam_search_batch``'s ``prefill_many``): ``rows[j]`` are the tokens of positions
+        ``0 .. R_j - 1`` of state ``states[j]``; cache row ``p * nb`` of every layer is written, nothing else."""
+        cu, n, nb, max_len = self._many
+        st = np.ascontiguousarray(states, dtype=np.int32)
+        if len(st) != len(rows) or not len(st):
+            raise _lib.HipLibraryError(f"prefill_many: {len(rows)} prompts for {len(st)} states")
+        pcu, tok, anc, longest = self._prefill_args(rows, nb)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_batch_prefill(self._handle, _pc(cu), n, _pc(st), _pc(pcu), len(st),
+                                                          tok.data_ptr(), anc.data_ptr(), longest, nb, max_len,
+                                                          self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
+                       "rp_decoder_batch_prefill")
 
     # -- the slot pool (rp_decoder_pool_*): states join between steps, each slot at its own position ---------------------
     def pool_open(self, n_slots: int, nb: int, max_len: int, src_cap: int) -> None:
@@ -418,6 +456,20 @@ class HipT5Decoder:
             _lib.check(self._lib.rp_decoder_pool_admit(self._handle, *self._pool, _pc(sl), enc_bf16.data_ptr(), _pc(cu),
                                                        len(sl), self._pool_ws.data_ptr(), self._pool_ws.numel(),
                                                        _lib.current_stream()), "rp_decoder_pool_admit")
+
+    def pool_prefill(self, slots, src_len, rows) -> None:
+        """``prefill_many`` for the slot pool (``rp_decoder_pool_prefill``, ``BeamSearchPool``'s ``prefill``): the prompt
+        rows ``rows[j]`` of slot ``slots[j]``, admitted with a source of ``src_len[j]`` tokens."""
+        nb = self._pool[1]
+        sl, ln = (np.ascontiguousarray(x, dtype=np.int32) for x in (slots, src_len))
+        if not len(sl) == len(ln) == len(rows) or not len(sl):
+            raise _lib.HipLibraryError(f"pool_prefill: {len(rows)} prompts, {len(ln)} source lengths for {len(sl)} slots")
+        pcu, tok, anc, longest = self._prefill_args(rows, nb)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_decoder_pool_prefill(self._handle, *self._pool, _pc(sl), _pc(ln), _pc(pcu), len(sl),
+                                                         tok.data_ptr(), anc.data_ptr(), longest,
+                                                         self._pool_ws.data_ptr(), self._pool_ws.numel(),
+                                                         _lib.current_stream()), "rp_decoder_pool_prefill")
 
     def pool_step(self, active, pos, src_len, tokens: torch.Tensor, ancestry: torch.Tensor,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -787,19 +839,51 @@ class HipT5Generator:
             out[b, :n] = lp[int(tgt_cu[b]) : int(tgt_cu[b]) + n]
         return out
 
-    def greedy(self, ids: np.ndarray, max_length: int) -> BeamSearchOutput:
+    @staticmethod
+    def _prefix(prefix) -> Optional[List[int]]:
+        """A prefix (token ids after the start token; None or empty: none) as a list, or None."""
+        if prefix is None:
+            return None
+        return [int(x) for x in np.asarray(prefix).reshape(-1).tolist()] or None
+
+    def _check_prefixes(self, prefixes, n: int, max_length: int):
+        """``prefixes`` (None, or one entry or None per source) as lists; None when no source has one."""
+        if prefixes is None:
+            return None
+        prefixes = [self._prefix(p) for p in prefixes]
+        if len(prefixes) != n:
+            raise ValueError(f"{len(prefixes)} prefixes for {n} sources")
+        for p in prefixes:
+            if p and max_length <= 1 + len(p):
+                raise ValueError(f"max_length={max_length} leaves no room after the decoder prompt of 1 + {len(p)} tokens")
+        return prefixes if any(prefixes) else None
+
+    def greedy(self, ids: np.ndarray, max_length: int, prefix=None) -> BeamSearchOutput:
         """``generate(input_ids, num_beams=1, max_length)``: HF's greedy search (argmax, ties to the lowest id), not a
-        one-beam beam search."""
+        one-beam beam search.  ``prefix``: as in ``generate``."""
+        if self._check_prefixes([prefix], 1, max_length) is not None:
+            return self.greedy_many([ids], max_length, prefixes=[prefix])[0]
         enc = self.encode_hidden(ids)
         self.decoder.start(enc, 1, max_length)
         return greedy_search(self.decoder.step, max_length, eos_token_id=self.cfg.get("eos_token_id", 1),
                              decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device)
 
     def generate(self, ids: np.ndarray, num_beams: int, max_length: int, length_penalty: float = 1.0,
-                 trace: Optional[list] = None, sync_every: Optional[int] = None) -> BeamSearchOutput:
+                 trace: Optional[list] = None, sync_every: Optional[int] = None, prefix=None) -> BeamSearchOutput:
         """``generate(input_ids, num_beams=n, num_return_sequences=n, length_penalty, max_length, early_stopping=False,
         do_sample=False)`` for one source.  Reads the selected candidates back once per step (generation.py);
-        ``sync_every``: as in ``generate_many``, whose one-state call it then is."""
+        ``sync_every``: as in ``generate_many``, whose one-state call it then is.
+
+        ``prefix`` (token ids; None or empty: none): HF's ``decoder_input_ids = [start] + prefix`` - every returned
+        sequence begins with it, ``max_length`` counts it, the scores sum the generated tokens only.  Its cache rows are
+        written in one pass (``rp_decoder_batch_prefill``, DESIGN.md section 9 "Tactic prefix"); host books only."""
+        if self._check_prefixes([prefix], 1, max_length) is not None:
+            traces = None if trace is None else []
+            out, = self.generate_many([ids], num_beams, max_length, length_penalty, traces=traces, sync_every=sync_every,
+                                      prefixes=[prefix])
+            if trace is not None:
+                trace.extend(traces[0])
+            return out
         if sync_every is not None:
             if trace is not None:
                 raise ValueError("trace= needs the host books: it cannot be combined with sync_every")
@@ -820,15 +904,20 @@ class HipT5Generator:
         self.decoder.start_many(enc, cu, num_beams, max_length)
         return len(srcs)
 
-    def greedy_many(self, sources, max_length: int) -> List[BeamSearchOutput]:
+    def greedy_many(self, sources, max_length: int, prefixes=None) -> List[BeamSearchOutput]:
         """``greedy`` for several sources through one decode loop: entry ``i`` is ``greedy(sources[i], max_length)`` bit
-        for bit, whichever other sources share the call."""
+        for bit, whichever other sources share the call.  ``prefixes``: as in ``generate_many``."""
+        sources = list(sources)
+        prefixes = self._check_prefixes(prefixes, len(sources), max_length)
         n = self._start_many(sources, 1, max_length)
+        kw = {} if prefixes is None else dict(prompts=prefixes, prefill_many=self.decoder.prefill_many)
         return greedy_search_batch(self.decoder.step_many, n, max_length, eos_token_id=self.cfg.get("eos_token_id", 1),
-                                   decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device)
+                                   decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device,
+                                   **kw)
 
     def generate_many(self, sources, num_beams: int, max_length: int, length_penalty: float = 1.0,
-                      traces: Optional[list] = None, sync_every: Optional[int] = None) -> List[BeamSearchOutput]:
+                      traces: Optional[list] = None, sync_every: Optional[int] = None,
+                      prefixes=None) -> List[BeamSearchOutput]:
         """``generate`` for several sources at once: one packed encoder pass, one cross-K/V GEMM and one decode loop that
         runs until the last state stops, with one readback per step.  Entry ``i`` equals ``generate(sources[i], ...)``
         bit for bit (sequences, scores and, in ``traces[i]``, every step's selected triples), whichever other sources
@@ -836,7 +925,17 @@ class HipT5Generator:
 
         ``sync_every`` (an integer >= 1; the default None is the loop above): the books live on the device
         (``rp_beam_advance``, DESIGN.md section 9 "device books"), nothing is uploaded or read back per position, and the
-        states' stop flags are read every ``sync_every`` positions.  The outputs are the same sequences and scores."""
+        states' stop flags are read every ``sync_every`` positions.  The outputs are the same sequences and scores.
+
+        ``prefixes`` (None, or one token id sequence or None per source): source ``i``'s decoder prompt after the start
+        token (``generate``'s ``prefix``).  All prompts' cache rows are written by one ``rp_decoder_batch_prefill``, then
+        state ``i`` searches from position ``len(prefixes[i])`` (``rp_decoder_batch_step_pos``).  Entry ``i`` equals
+        ``generate(sources[i], ..., prefix=prefixes[i])`` bit for bit.  Together with ``sync_every`` a ``ValueError``:
+        the device books with a prompt are not built yet."""
+        sources = list(sources)
+        prefixes = self._check_prefixes(prefixes, len(sources), max_length)
+        if prefixes is not None and sync_every is not None:
+            raise ValueError("a decoder prompt together with the device books (sync_every) is not built yet")
         if sync_every is not None:
             if traces is not None:
                 raise ValueError("traces= needs the host books: it cannot be combined with sync_every")
@@ -852,10 +951,11 @@ class HipT5Generator:
                 dec.beam_advance, n, num_beams, max_length, length_penalty, eos_token_id=self.cfg.get("eos_token_id", 1),
                 decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), sync_every=int(sync_every),
                 device=self.device, init=dec.beam_books)
+        kw = {} if prefixes is None else dict(prompts=prefixes, prefill_many=self.decoder.prefill_many)
         return beam_search_batch(self.decoder.step_many, n, num_beams, max_length, length_penalty,
                                  eos_token_id=self.cfg.get("eos_token_id", 1),
                                  decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),
-                                 select_many=self.decoder.select_many, device=self.device, traces=traces)
+                                 select_many=self.decoder.select_many, device=self.device, traces=traces, **kw)
 
     def generate_stream(self, num_beams: int, max_length: int, length_penalty: float = 1.0,
                         n_slots: Optional[int] = None, src_cap: int = 2048,
@@ -981,7 +1081,7 @@ class GenerateStream:
         self.pool = BeamSearchPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
                                    eos_token_id=cfg.get("eos_token_id", 1),
                                    decoder_start_token_id=cfg.get("decoder_start_token_id", 0),
-                                   select_many=dec.select_many, device=generator.device)
+                                   select_many=dec.select_many, device=generator.device, prefill=self._prefill)
 
     def _open(self, generator: HipT5Generator, n_slots: int, nb: int, max_length: int, src_cap: int) -> HipT5Decoder:
         """Take the decoder's slot pool (beam and sample streams alike: whoever held it is retired)."""
@@ -1004,6 +1104,9 @@ class GenerateStream:
         for s, x in zip(slots, sources):
             self._src_len[s] = len(x)
 
+    def _prefill(self, slots, rows) -> None:
+        self._mine().pool_prefill(slots, [self._src_len[s] for s in slots], rows)
+
     def _step(self, active, pos, tokens, ancestry) -> torch.Tensor:
         return self._mine().pool_step(active, pos, [self._src_len[s] for s in active], tokens, ancestry)
 
@@ -1013,8 +1116,14 @@ class GenerateStream:
             raise ValueError(f"a source of {ids.size} tokens does not fit the stream's src_cap={self.src_cap} (1..src_cap)")
         return ids
 
-    def submit(self, ids) -> int:
-        return self.pool.submit(self._source(ids))
+    def submit(self, ids, prefix=None) -> int:
+        """Queue a source.  ``prefix`` (token ids; None or empty: none): the ticket's decoder prompt, as in
+        ``HipT5Generator.generate``; its cache rows are written in one pass at admission
+        (``rp_decoder_pool_prefill``).  Host-books stream only: with ``sync_every`` a ``ValueError``."""
+        prefix = HipT5Generator._prefix(prefix)
+        if prefix is None:
+            return self.pool.submit(self._source(ids))
+        return self.pool.submit(self._source(ids), prompt=prefix)
 
     def step(self) -> List[Tuple[int, BeamSearchOutput]]:
         return self.pool.step()
@@ -1058,7 +1167,10 @@ class SampleStream(GenerateStream):
             **(dict(per_request=True, params=SamplingParams(temperature, top_k, top_p)) if per_request else {}))
         self.num_samples, self.per_request = int(num_samples), bool(per_request)
 
-    def submit(self, ids, seed: int, params: Optional[SamplingParams] = None, num_samples: Optional[int] = None) -> int:
+    def submit(self, ids, seed: int, params: Optional[SamplingParams] = None, num_samples: Optional[int] = None,
+               prefix=None) -> int:
+        if HipT5Generator._prefix(prefix) is not None:
+            raise ValueError("a decoder prompt together with sampling is not built yet")
         if params is None and num_samples is None:
             return self.pool.submit(self._source(ids), seed)
         return self.pool.submit(self._source(ids), seed, params, num_samples)

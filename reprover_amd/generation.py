@@ -32,6 +32,13 @@ the device, ``advance`` (``rp_beam_advance``) updates it after every step, and t
 ``sync_every`` positions.  ``beam_advance_host`` restates that kernel on host tensors with its stable order (the kernel's
 oracle, and the ``advance`` of a CPU run).  ``beam_search_batch`` with its host books stays the default.
 
+A decoder prompt (HF's ``decoder_input_ids``: tokens after the start token that every returned sequence begins with) is
+``prompt=`` / ``prompts=`` of ``beam_search``, ``beam_search_batch``, the two greedy functions and
+``BeamSearchPool.submit``: ``_BeamState`` starts at ``cur_len = prompt_len = P + 1`` with an ancestry that names one cache
+row per prompt position (beam 0's, ``p * nb``), written before the loop by a ``prefill`` callable (the engine's one-pass
+``rp_decoder_batch_prefill``, or ``prefill_by_steps`` through ordinary steps).  The device books and sampling refuse a
+prompt (``ValueError``: not built yet).
+
 ``BeamSearchPool`` is ``beam_search_batch``'s loop with admission: sources are submitted while it runs, each takes a free
 slot between two steps and is stepped at its own position, and its output is returned at the step where it stops.
 ``BeamBooksPool`` is that pool with the books in a ``BeamBooks`` block of ``n_slots`` states: a position per slot
@@ -69,26 +76,93 @@ def topk_select(log_probs: torch.Tensor, running_scores: torch.Tensor, k: int):
     return vals, idx % V, torch.div(idx, V, rounding_mode="floor")
 
 
+def _prompt_tokens(prompt) -> List[int]:
+    """A decoder prompt (the tokens after the start token; None: none) as a list of ints."""
+    if prompt is None:
+        return []
+    return [int(x) for x in np.asarray(prompt).reshape(-1).tolist()]
+
+
+def _no_room(max_length: int, P: int) -> str:
+    if P == 0:
+        return f"max_length={max_length} leaves no room after the decoder start token"
+    return f"max_length={max_length} leaves no room after the decoder prompt of 1 + {P} tokens"
+
+
+def _refuse_prompts(prompts, what: str) -> None:
+    """The search kinds without a decoder prompt: a ``ValueError`` when any entry of ``prompts`` has tokens."""
+    if prompts is not None and any(_prompt_tokens(p) for p in prompts):
+        raise ValueError(f"a decoder prompt together with {what} is not built yet")
+
+
+def _prompt_rows(prompt: Sequence[int], decoder_start_token_id: int) -> List[int]:
+    """The tokens of the prompt's cache rows, positions ``0 .. P - 1``: the prompt ``[start, b_1 .. b_P]`` without its
+    last token, which the search feeds itself at position ``P``."""
+    return [int(decoder_start_token_id)] + list(prompt[:-1])
+
+
+def prefill_by_steps(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], nb: int, rows: Sequence[int],
+                     device=None) -> None:
+    """Write a prompt's cache rows through ordinary decode steps, for models that have only ``step``: position ``p``
+    is fed ``rows[p]`` repeated over the ``nb`` beams with identity ancestry, so beam 0's row ``p * nb`` - the one a
+    prompted search reads - holds what a one-pass prefill writes there.  The log-probs are dropped."""
+    nb = int(nb)
+    beams = torch.arange(nb, dtype=torch.int64)
+    for p, tok in enumerate(rows):
+        tokens = torch.full((nb,), int(tok), dtype=torch.int64)
+        anc = torch.arange(p + 1, dtype=torch.int64)[None] * nb + beams[:, None]
+        if device is not None:
+            tokens, anc = tokens.to(device), anc.to(device)
+        step(tokens, anc)
+
+
+def _check_prompts(prompts, n: int, max_length: int) -> Optional[List[List[int]]]:
+    """``prompts`` (None, or one entry or None per state) as token lists; None when no state has a prompt."""
+    if prompts is None:
+        return None
+    prompts = [_prompt_tokens(p) for p in prompts]
+    if len(prompts) != n:
+        raise ValueError(f"{len(prompts)} prompts for {n} states")
+    for p in prompts:
+        if max_length <= 1 + len(p):
+            raise ValueError(_no_room(max_length, len(p)))
+    return prompts if any(prompts) else None
+
+
+# "divisors_count_prompt" plants a known bug: both length-penalty divisors count the prompt's tokens (prompt_len left at
+# 1 there), so that tests can show the fixture tells HF's semantics from it
+PROMPT_MUTANTS = ("divisors_count_prompt",)
+
+
 class _BeamState:
     """The host bookkeeping of one source's beam search: ``inputs`` gives the step's tokens and ancestry table,
     ``advance`` takes the step's top-``2 nb`` candidates (host tensors) and says whether the search is over.
     ``beam_search_batch`` drives one per source in lockstep; ``beam_search`` is its one-source call."""
 
     def __init__(self, num_beams: int, max_length: int, length_penalty: float, eos_token_id: int,
-                 decoder_start_token_id: int, num_return_sequences: Optional[int]):
+                 decoder_start_token_id: int, num_return_sequences: Optional[int],
+                 prompt: Optional[Sequence[int]] = None, mutant: Optional[str] = None):
+        assert mutant is None or mutant in PROMPT_MUTANTS, mutant
+        self.mutant = mutant
         nb = self.nb = int(num_beams)
         self.nret = nb if num_return_sequences is None else int(num_return_sequences)
         assert 1 <= self.nret <= nb
-        self.prompt_len = 1  # the decoder prompt is the start token alone (utils.py:3266 decoder_prompt_len = cur_len)
+        # the decoder prompt is the start token and the ``prompt`` tokens (utils.py:3278 decoder_prompt_len = cur_len):
+        # max_length counts it, the returned sequences hold it, the scores and both divisors count generated tokens only
+        prompt = _prompt_tokens(prompt)
+        P = len(prompt)
+        self.prompt_len = 1 + P
         self.cur_len = self.prompt_len
         self.keep = 2 * nb  # beams_to_keep = max(2, 1 + n_eos_tokens) * num_beams with one EOS id (:3271)
         fill = eos_token_id  # output_fill_value = pad_token_id (0, falsy) or eos_token_id[0] (:3294)
         if max_length <= self.cur_len:
-            raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+            raise ValueError(_no_room(max_length, P))
         self.max_length, self.length_penalty, self.eos_token_id = max_length, length_penalty, eos_token_id
 
         self.running_seq = torch.full((nb, max_length), fill, dtype=torch.int64)
         self.running_seq[:, 0] = decoder_start_token_id
+        if P:
+            self.running_seq[:, 1 : 1 + P] = torch.tensor(prompt, dtype=torch.int64)
         self.sequences = self.running_seq.clone()
         self.running_scores = torch.zeros(nb, dtype=torch.float32)
         self.running_scores[1:] = NEG  # :3301 - only beam 0 is live at the first step
@@ -99,7 +173,8 @@ class _BeamState:
         self.beam_indices = self.running_bi.clone()
         self.top_num_beam_mask = torch.cat([torch.ones(nb, dtype=torch.bool),
                                             torch.zeros(self.keep - nb, dtype=torch.bool)])
-        self.ancestry = torch.zeros((nb, 0), dtype=torch.int64)
+        # the prompt's cache rows are shared by all beams: one row per prompt position, beam 0's (p * nb)
+        self.ancestry = (torch.arange(P, dtype=torch.int64) * nb)[None].repeat(nb, 1)
 
     def inputs(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(tokens [nb], ancestry [nb, t + 1]) of the step at position ``t = cur_len - 1``."""
@@ -125,7 +200,8 @@ class _BeamState:
         new_running_bi = topk_bi[nxt]
         # _update_finished_beams (:3153-3206)
         just_finished = hits & self.top_num_beam_mask
-        fin_lp = vals / ((cur_len + 1 - prompt_len) ** length_penalty)
+        div_prompt = 1 if self.mutant == "divisors_count_prompt" else prompt_len
+        fin_lp = vals / ((cur_len + 1 - div_prompt) ** length_penalty)
         fin_lp = fin_lp + (0.0 if self.heuristic_unsatisfied else NEG)
         fin_lp = fin_lp + (~just_finished).to(torch.float32) * NEG
         m_seq = torch.cat([self.sequences, topk_seq], 0)
@@ -141,7 +217,7 @@ class _BeamState:
         self.running_seq, self.running_bi, self.running_scores = new_running_seq, new_running_bi, running_scores
         self.cur_len = cur_len = cur_len + 1
         # _check_early_stop_heuristic (:3008-3053), early_stopping=False: best length = cur_len - prompt_len
-        best_running = running_scores[0] / ((cur_len - prompt_len) ** length_penalty)
+        best_running = running_scores[0] / ((cur_len - div_prompt) ** length_penalty)
         worst_finished = torch.where(self.is_sent_finished, self.beam_scores.min(), torch.tensor(NEG))
         self.heuristic_unsatisfied = self.heuristic_unsatisfied and bool((best_running > worst_finished).any())
         # _beam_search_has_unfinished_sequences (:3055-3075), early_stopping=False
@@ -158,13 +234,22 @@ class _BeamState:
 def beam_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], num_beams: int, max_length: int,
                 length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
                 num_return_sequences: Optional[int] = None, select: Callable = topk_select,
-                device=None, trace: Optional[list] = None) -> BeamSearchOutput:
+                device=None, trace: Optional[list] = None, prompt: Optional[Sequence[int]] = None,
+                prefill: Optional[Callable] = None, mutant: Optional[str] = None) -> BeamSearchOutput:
     """Beam search over ``step`` (module docstring): ``beam_search_batch`` with one state.  ``trace``, when a list,
-    receives the per-step top-``2 nb`` candidates ``(scores, tokens, parents)`` as host tensors."""
+    receives the per-step top-``2 nb`` candidates ``(scores, tokens, parents)`` as host tensors.
+
+    ``prompt``: decoder tokens after the start token that every returned sequence begins with (HF's
+    ``decoder_input_ids = [start] + prompt``); ``prefill(rows)`` writes the prompt's cache rows (``beam_search_batch``),
+    by default through ``step`` (``prefill_by_steps``)."""
     traces: Optional[list] = None if trace is None else []
-    out, = beam_search_batch(lambda active, tokens, ancestry: step(tokens, ancestry), 1, num_beams, max_length,
+    step_one = lambda active, tokens, ancestry, pos=None: step(tokens, ancestry)  # noqa: E731
+    out, = beam_search_batch(step_one, 1, num_beams, max_length,
                              length_penalty, eos_token_id, decoder_start_token_id, num_return_sequences,
-                             lambda lp, running, nb, k: tuple(x[None] for x in select(lp, running, k)), device, traces)
+                             lambda lp, running, nb, k: tuple(x[None] for x in select(lp, running, k)), device, traces,
+                             prompts=None if prompt is None else [prompt],
+                             prefill_many=None if prefill is None else (lambda states, rows: prefill(rows[0])),
+                             mutant=mutant)
     if trace is not None:
         trace.extend(traces[0])
     return out
@@ -180,7 +265,8 @@ def topk_select_many(log_probs: torch.Tensor, running_scores: torch.Tensor, nb: 
 def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_length: int, length_penalty: float = 1.0,
                       eos_token_id: int = 1, decoder_start_token_id: int = 0,
                       num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
-                      traces: Optional[list] = None) -> List[BeamSearchOutput]:
+                      traces: Optional[list] = None, prompts: Optional[Sequence] = None,
+                      prefill_many: Optional[Callable] = None, mutant: Optional[str] = None) -> List[BeamSearchOutput]:
     """The search loop: ``num_states`` sources in lockstep, one ``step_many`` and one ``select_many`` per position, one
     readback of the ``n_active x 2 nb`` triples.  Every state keeps its own bookkeeping (``_BeamState``) and leaves the
     active list at the step where it would stop alone; the loop runs until the last one has.
@@ -191,20 +277,48 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
     - ``select_many(log_probs, running_scores, nb, k)``: per state the top ``k`` of its own ``[nb * vocab]`` block,
       each output ``[n_active, k]``, parents local to the state.
 
-    ``traces``, when a list, receives one per-state list of ``(scores, tokens, parents)`` per step."""
+    ``traces``, when a list, receives one per-state list of ``(scores, tokens, parents)`` per step.
+
+    ``prompts`` (None, or one token sequence or None per state): state ``i``'s decoder prompt after the start token, of
+    ``P_i >= 0`` tokens.  Its search starts at position ``P_i`` with the prompt in every sequence; the prompt's cache rows
+    ``p * nb``, ``p < P_i``, are written before the loop by ``prefill_many(states, rows)`` - ``states`` the indices with
+    ``P_i >= 1``, ``rows[j]`` the tokens of positions ``0 .. P - 1`` (``_prompt_rows``) - by default through
+    ``step_many``, one state and one position at a time (``prefill_by_steps``).  With any prompt the loop hands
+    ``step_many`` a position per active state, ``step_many(active, tokens, ancestry, pos=pos)``, and pads the ancestry
+    table as ``BeamSearchPool.step`` does: state ``i`` stands at ``P_i + k`` after ``k`` steps.  Without prompts the
+    loop is the one above, call for call.  ``mutant``: one of ``PROMPT_MUTANTS``."""
+    prompts = _check_prompts(prompts, num_states, max_length)
     states = [_BeamState(num_beams, max_length, length_penalty, eos_token_id, decoder_start_token_id,
-                         num_return_sequences) for _ in range(num_states)]
+                         num_return_sequences, None if prompts is None else prompts[i], mutant)
+              for i in range(num_states)]
     per_state = [[] for _ in states]
     active = list(range(num_states))
     nb = int(num_beams)
+    if prompts is not None:
+        listed = [i for i in range(num_states) if prompts[i]]
+        rows = [_prompt_rows(prompts[i], decoder_start_token_id) for i in listed]
+        if prefill_many is not None:
+            prefill_many(listed, rows)
+        else:
+            for i, r in zip(listed, rows):
+                prefill_by_steps(lambda tok, anc, i=i: step_many([i], tok, anc, pos=[anc.shape[1] - 1]), nb, r, device)
     while active:
         ins = [states[i].inputs() for i in active]
         tokens = torch.cat([x[0] for x in ins])
-        ancestry = torch.cat([x[1] for x in ins])
         running = torch.cat([states[i].running_scores for i in active])
+        if prompts is None:
+            ancestry = torch.cat([x[1] for x in ins])
+        else:
+            pos = [states[i].cur_len - 1 for i in active]
+            ancestry = torch.zeros((len(active) * nb, max(pos) + 1), dtype=torch.int64)
+            for a, (_, anc) in enumerate(ins):
+                ancestry[a * nb : (a + 1) * nb, : anc.shape[1]] = anc
         if device is not None:
             tokens, ancestry, running = tokens.to(device), ancestry.to(device), running.to(device)
-        log_probs = step_many(list(active), tokens, ancestry)
+        if prompts is None:
+            log_probs = step_many(list(active), tokens, ancestry)
+        else:
+            log_probs = step_many(list(active), tokens, ancestry, pos=pos)
         vals, toks, parents = select_many(log_probs, running, nb, 2 * nb)
         vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
         still = []
@@ -246,16 +360,18 @@ class BeamSearchPool:
     def __init__(self, admit: Callable, step: Callable, n_slots: int, num_beams: int, max_length: int,
                  length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
                  num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
-                 mutant: Optional[str] = None):
+                 mutant: Optional[str] = None, prefill: Optional[Callable] = None):
         assert mutant is None or mutant in POOL_MUTANTS, mutant
         if int(n_slots) < 1 or int(num_beams) < 1:
             raise ValueError(f"n_slots={n_slots} and num_beams={num_beams} must be >= 1")
         if max_length <= 1:
             raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
-        self._admit, self._step, self._select_many = admit, step, select_many
+        self._admit, self._step, self._select_many, self._prefill = admit, step, select_many, prefill
         self.n_slots, self.nb, self.device, self.mutant = int(n_slots), int(num_beams), device, mutant
-        self._new_state = lambda: _BeamState(num_beams, max_length, length_penalty, eos_token_id, decoder_start_token_id,
-                                             num_return_sequences)
+        self.max_length, self._start_token = max_length, decoder_start_token_id
+        self._new_state = lambda prompt=None: _BeamState(num_beams, max_length, length_penalty, eos_token_id,
+                                                         decoder_start_token_id, num_return_sequences, prompt)
+        self._prompt: dict = {}                                   # ticket -> its decoder prompt, where it has one
         self._queue: List[Tuple[int, object]] = []               # (ticket, source), first in first out
         self._slots: List[Optional[Tuple[int, _BeamState]]] = [None] * self.n_slots  # (ticket, books) per slot in use
         self._next_ticket = 0
@@ -269,12 +385,23 @@ class BeamSearchPool:
     def in_flight(self) -> int:
         return sum(s is not None for s in self._slots)
 
-    def submit(self, source) -> int:
-        """Queue a source; its ticket names it in ``step``'s return."""
+    def submit(self, source, prompt: Optional[Sequence[int]] = None) -> int:
+        """Queue a source; its ticket names it in ``step``'s return.  ``prompt``: the ticket's decoder prompt after
+        the start token (``beam_search``'s): its slot starts at position ``len(prompt)``, its prompt rows written right
+        after ``admit`` by ``prefill(slots, rows)`` - by default through ``step``, a position at a time."""
+        prompt = _prompt_tokens(prompt)
+        if self.max_length <= 1 + len(prompt):
+            raise ValueError(_no_room(self.max_length, len(prompt)))
         ticket = self._next_ticket
         self._next_ticket += 1
+        if prompt:
+            self._prompt[ticket] = prompt
         self._queue.append((ticket, source))
         return ticket
+
+    def _prefill_by_steps(self, slots, rows) -> None:
+        for s, r in zip(slots, rows):
+            prefill_by_steps(lambda tok, anc, s=s: self._step([s], [anc.shape[1] - 1], tok, anc), self.nb, r, self.device)
 
     def step(self) -> List[Tuple[int, BeamSearchOutput]]:
         """Admit what fits, take one decode step, return the ``(ticket, output)`` pairs of the states that stopped."""
@@ -283,8 +410,14 @@ class BeamSearchPool:
         if take:
             new, self._queue = self._queue[:take], self._queue[take:]
             self._admit(free[:take], [src for _, src in new])
+            prompted = []
             for s, (ticket, _) in zip(free, new):
-                self._slots[s] = (ticket, self._new_state())
+                prompt = self._prompt.pop(ticket, None)
+                self._slots[s] = (ticket, self._new_state(prompt))
+                if prompt:
+                    prompted.append((s, _prompt_rows(prompt, self._start_token)))
+            if prompted:
+                (self._prefill or self._prefill_by_steps)([s for s, _ in prompted], [r for _, r in prompted])
         active = [s for s in range(self.n_slots) if self._slots[s] is not None]
         if not active:
             return []
@@ -552,7 +685,8 @@ def beam_search_batch_device(step_many: Callable, select_many: Callable, advance
                              num_beams: int, max_length: int, length_penalty: float = 1.0, eos_token_id: int = 1,
                              decoder_start_token_id: int = 0, num_return_sequences: Optional[int] = None,
                              sync_every: int = 16, device=None, init: Optional[Callable] = None,
-                             to_host: Callable = lambda x: x.cpu()) -> List[BeamSearchOutput]:
+                             to_host: Callable = lambda x: x.cpu(), prompts: Optional[Sequence] = None
+                             ) -> List[BeamSearchOutput]:
     """``beam_search_batch`` with the books on the device (``BeamBooks``): per position one ``step_many``, one
     ``select_many`` and one ``advance``, nothing uploaded but their arguments and nothing read back.  Every
     ``sync_every`` positions the ``num_states`` ``done`` flags are read once and the stopped states leave the active
@@ -570,6 +704,7 @@ def beam_search_batch_device(step_many: Callable, select_many: Callable, advance
     - ``advance(books, active, t, scores, tokens, parents, fin_div, run_div, eos)``: ``rp_beam_advance``
       (``beam_advance_host`` on the host).
     - ``to_host``: the loop's every device-to-host copy goes through it (tests count them)."""
+    _refuse_prompts(prompts, "the device books (sync_every)")
     n, nb = int(num_states), int(num_beams)
     nret = nb if num_return_sequences is None else int(num_return_sequences)
     if max_length <= 1:
@@ -685,8 +820,10 @@ class BeamBooksPool:
     def in_flight(self) -> int:
         return sum(t is not None for t in self._ticket)
 
-    def submit(self, source) -> int:
-        """Queue a source; its ticket names it in ``step``'s return."""
+    def submit(self, source, prompt: Optional[Sequence[int]] = None) -> int:
+        """Queue a source; its ticket names it in ``step``'s return.  (A decoder ``prompt`` is ``BeamSearchPool``'s: a
+        ``ValueError`` here.)"""
+        _refuse_prompts([prompt], "the device books (sync_every)")
         ticket = self._next_ticket
         self._next_ticket += 1
         self._queue.append((ticket, source))
@@ -771,26 +908,64 @@ class BeamBooksPool:
 
 
 def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], max_length: int, eos_token_id: int = 1,
-                  decoder_start_token_id: int = 0, device=None) -> BeamSearchOutput:
+                  decoder_start_token_id: int = 0, device=None, prompt: Optional[Sequence[int]] = None,
+                  prefill: Optional[Callable] = None) -> BeamSearchOutput:
     """``generate(num_beams=1, do_sample=False, max_length=L)``, which HF runs as greedy search (``_sample`` without
     sampling), not as a one-beam beam search: the argmax token (ties to the lowest id) until EOS or ``max_length``
     tokens including the start token.  After an EOS candidate a beam search keeps looking and may return a longer
     sequence; greedy stops.  ``sequences_scores`` holds the sum of the chosen tokens' log-probs (HF reports none).
-    ``greedy_search_batch`` with one state."""
-    return greedy_search_batch(lambda active, tokens, ancestry: step(tokens, ancestry), 1, max_length, eos_token_id,
-                               decoder_start_token_id, device)[0]
+    ``greedy_search_batch`` with one state.  ``prompt`` / ``prefill``: as in ``beam_search``; the result starts with
+    the start token and the prompt, as HF's does, and the score sums the generated tokens only."""
+    return greedy_search_batch(lambda active, tokens, ancestry, pos=None: step(tokens, ancestry), 1, max_length,
+                               eos_token_id, decoder_start_token_id, device,
+                               prompts=None if prompt is None else [prompt],
+                               prefill_many=None if prefill is None else (lambda states, rows: prefill(rows[0])))[0]
 
 
 def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, eos_token_id: int = 1,
-                        decoder_start_token_id: int = 0, device=None) -> List[BeamSearchOutput]:
+                        decoder_start_token_id: int = 0, device=None, prompts: Optional[Sequence] = None,
+                        prefill_many: Optional[Callable] = None) -> List[BeamSearchOutput]:
     """The greedy loop (``greedy_search``'s semantics per source): ``num_states`` sources in lockstep, one beam each,
     one ``step_many`` (as in ``beam_search_batch``) and one readback of the active states' log-prob rows per position.
-    A state leaves the active list at its EOS; the loop ends with the last one or at ``max_length``."""
+    A state leaves the active list at its EOS; the loop ends with the last one or at ``max_length``.
+
+    ``prompts`` / ``prefill_many``: as in ``beam_search_batch`` with one beam.  State ``i`` starts at position ``P_i``
+    with ``[start] + prompt`` as its sequence, ``step_many`` is handed ``pos=``, and a state leaves at its EOS or when
+    its sequence holds ``max_length`` tokens.  Without prompts the loop is the one above, call for call."""
     if max_length <= 1:
         raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+    prompts = _check_prompts(prompts, num_states, max_length)
     seqs = [[int(decoder_start_token_id)] for _ in range(num_states)]
     totals = [0.0] * num_states
     active = list(range(num_states))
+    if prompts is not None:
+        listed = [i for i in range(num_states) if prompts[i]]
+        rows = [_prompt_rows(prompts[i], decoder_start_token_id) for i in listed]
+        if prefill_many is not None:
+            prefill_many(listed, rows)
+        else:
+            for i, r in zip(listed, rows):
+                prefill_by_steps(lambda tok, anc, i=i: step_many([i], tok, anc, pos=[anc.shape[1] - 1]), 1, r, device)
+        for i in range(num_states):
+            seqs[i].extend(prompts[i])
+    while prompts is not None and active:
+        pos = [len(seqs[i]) - 1 for i in active]
+        tokens = torch.tensor([seqs[i][-1] for i in active], dtype=torch.int64)
+        anc = torch.zeros((len(active), max(pos) + 1), dtype=torch.int64)
+        for a, p in enumerate(pos):
+            anc[a, : p + 1] = torch.arange(p + 1, dtype=torch.int64)
+        if device is not None:
+            tokens, anc = tokens.to(device), anc.to(device)
+        lps = step_many(list(active), tokens, anc, pos=pos).float().cpu()
+        still = []
+        for a, i in enumerate(active):
+            lp = lps[a]
+            best = int(torch.nonzero(lp == lp.max())[0, 0])
+            totals[i] += float(lp[best])
+            seqs[i].append(best)
+            if best != eos_token_id and len(seqs[i]) < max_length:
+                still.append(i)
+        active = still
     t = 0
     while active and t + 1 < max_length:
         tokens = torch.tensor([seqs[i][-1] for i in active], dtype=torch.int64)
@@ -889,7 +1064,8 @@ class SamplingParams:
 def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: int, num_samples: int, max_length: int,
                         seeds: Sequence[int], length_penalty: float = 0.0, eos_token_id: int = 1,
                         decoder_start_token_id: int = 0, pad_token_id: int = 0, sync_every: int = 16,
-                        device=None, params: Optional[torch.Tensor] = None) -> List[BeamSearchOutput]:
+                        device=None, params: Optional[torch.Tensor] = None,
+                        prompts: Optional[Sequence] = None) -> List[BeamSearchOutput]:
     """The sampling loop: ``num_states`` sources in lockstep with ``num_samples`` independent rows each; per position one
     ``step_many`` and one ``sample_step``, nothing read back.  Every ``sync_every`` positions the finished flags are
     read once and the states whose samples have all finished leave the active list; the loop ends when it is empty or
@@ -913,6 +1089,7 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
     Returns per state ``sequences [num_samples, out_len]`` (start token first, pad after EOS, trimmed to the state's
     longest sample) in sample order and ``sequences_scores = cum_logprob / n_generated ** length_penalty`` (the
     finished-beam formula; the default 0.0 gives the sum)."""
+    _refuse_prompts(prompts, "sampling")
     n, nb = int(num_states), int(num_samples)
     if max_length <= 1:
         raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
@@ -966,9 +1143,11 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
 def sample_search(step: Callable, sample_step: Callable, num_samples: int, max_length: int, seed: int = 0,
                   length_penalty: float = 0.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
                   pad_token_id: int = 0, sync_every: int = 16, device=None,
-                  params: Optional[torch.Tensor] = None) -> BeamSearchOutput:
+                  params: Optional[torch.Tensor] = None, prompt: Optional[Sequence[int]] = None) -> BeamSearchOutput:
     """``sample_search_batch`` with one state: ``step(tokens, ancestry, t)``, ``sample_step`` as there; ``params`` is the
-    state's int32 ``[num_samples, 4]`` block (``SamplingParams.rows``) or None."""
+    state's int32 ``[num_samples, 4]`` block (``SamplingParams.rows``) or None.  (A decoder ``prompt`` is beam search's
+    and greedy's: a ``ValueError`` here, as ``prompts`` is in ``sample_search_batch``.)"""
+    _refuse_prompts([prompt], "sampling")
     return sample_search_batch(lambda active, tokens, ancestry, t: step(tokens, ancestry, t), sample_step, 1,
                                num_samples, max_length, [seed], length_penalty, eos_token_id, decoder_start_token_id,
                                pad_token_id, sync_every, device, None if params is None else params[None])[0]
@@ -1159,10 +1338,11 @@ class SamplePool:
         return sum(t is not None for t in self._ticket)
 
     def submit(self, source, seed: int, params: Optional[SamplingParams] = None,
-               num_samples: Optional[int] = None) -> int:
+               num_samples: Optional[int] = None, prompt: Optional[Sequence[int]] = None) -> int:
         """Queue a source with its 32-bit seed; its ticket names it in ``step``'s return.  With ``per_request``:
         ``params`` are the ticket's sampling parameters (None: the pool's own) and ``num_samples`` its number of rows
-        (None: the pool's); without it either is a ``ValueError``."""
+        (None: the pool's); without it either is a ``ValueError``.  A decoder ``prompt`` is a ``ValueError``."""
+        _refuse_prompts([prompt], "sampling")
         request = None
         if not self.per_request:
             if params is not None or num_samples is not None:

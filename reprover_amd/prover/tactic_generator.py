@@ -132,6 +132,23 @@ class HuggingFaceGenerator(TacticGenerator):
             raise ValueError(f"sampling holds {len(sampling)} entries for {n} states (one SamplingParams or None each)")
         return sampling
 
+    def _prefix_ids(self, prefix: Optional[str]) -> Optional[List[int]]:
+        """A tactic prefix as decoder prompt tokens: its UTF-8 bytes + 3, no EOS (None or "": no prompt, the call as it
+        always was).  Refused with ``do_sample``, with ``beam_sync_every``, and when the start token and the prefix leave
+        no room under ``max_oup_seq_len``."""
+        if prefix is None or prefix == "":
+            return None
+        if not isinstance(prefix, str):
+            raise ValueError(f"prefix={prefix!r} is not a string")
+        if self.do_sample:
+            raise ValueError("a tactic prefix together with do_sample=True is not built yet")
+        if self.beam_sync_every is not None:
+            raise ValueError("a tactic prefix together with beam_sync_every (the device books) is not built yet")
+        ids = [b + 3 for b in prefix.encode("utf-8")]
+        if self.max_oup_seq_len <= 1 + len(ids):
+            raise ValueError(f"the prefix of {len(ids)} bytes leaves no room under max_oup_seq_len={self.max_oup_seq_len}")
+        return ids
+
     def _sampled(self, ids, num_samples: int, sampling=None) -> List[List[Tuple[str, float]]]:
         results: List[List[Tuple[str, float]]] = []
         cap = self.generator.decoder.max_states(num_samples)
@@ -165,13 +182,18 @@ class HuggingFaceGenerator(TacticGenerator):
         self.tokenizer = ByT5Tokenizer()
 
     def generate_sync(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
-                      num_samples: int, *, sampling: Optional[SamplingParams] = None) -> List[Tuple[str, float]]:
+                      num_samples: int, *, sampling: Optional[SamplingParams] = None,
+                      prefix: Optional[str] = None) -> List[Tuple[str, float]]:
+        """``prefix``: the tactics returned all begin with it (HF's ``decoder_input_ids``: the decoder prompt is the
+        start token and the prefix's bytes), scored by HF's ``sequences_scores`` over the generated tokens."""
         sampling = self._check_request(sampling)
+        prompt = self._prefix_ids(prefix)
         state = self.template % state
         ids = encode_one(state, self.max_inp_seq_len)  # tokenizer(state, max_length=..., truncation=True)
         if self.do_sample:
             return self._sampled([ids], num_samples, None if sampling is None else [sampling])[0]
-        out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty, **self._books)
+        kw = {} if prompt is None else {"prefix": prompt}
+        out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty, **self._books, **kw)
         return self._suggestions(out, num_samples)
 
     def _suggestions(self, out, num_samples: int) -> List[Tuple[str, float]]:
@@ -187,10 +209,14 @@ class HuggingFaceGenerator(TacticGenerator):
         return list(zip_strict(output_text, output_score))
 
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
-                       num_samples: int, *, sampling: Optional[SamplingParams] = None) -> List[Tuple[str, float]]:
+                       num_samples: int, *, sampling: Optional[SamplingParams] = None,
+                       prefix: Optional[str] = None) -> List[Tuple[str, float]]:
         sampling = self._check_request(sampling)
+        prompt = self._prefix_ids(prefix)
         if not (self.continuous or self.sample_stream):
-            return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples, sampling=sampling)
+            kw = {} if prompt is None else {"prefix": prefix}
+            return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples, sampling=sampling,
+                                      **kw)
         if self.per_request_sampling:
             return await self._generate_per_request(state, num_samples, sampling)
         if sampling is not None:
@@ -214,7 +240,12 @@ class HuggingFaceGenerator(TacticGenerator):
             self._stream_beams = num_samples
         future = asyncio.get_running_loop().create_future()
         # (a sampled call's seed is taken here, at submit time: in call order)
-        ticket = self._stream.submit(ids, self._next_seeds(1)[0]) if self.sample_stream else self._stream.submit(ids)
+        if self.sample_stream:
+            ticket = self._stream.submit(ids, self._next_seeds(1)[0])
+        elif prompt is None:
+            ticket = self._stream.submit(ids)
+        else:
+            ticket = self._stream.submit(ids, prefix=prompt)  # the prefix travels with the ticket
         self._waiters[ticket] = future
         if self._driver is None:
             self._driver = asyncio.ensure_future(self._drive())
@@ -269,18 +300,29 @@ class HuggingFaceGenerator(TacticGenerator):
             self._driver = None
 
     def batch_generate_sync(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
-                            theorem_poses: List[Pos], num_samples: int, *, sampling=None) -> List[List[Tuple[str, float]]]:
+                            theorem_poses: List[Pos], num_samples: int, *, sampling=None,
+                            prefixes=None) -> List[List[Tuple[str, float]]]:
         """``generate_sync`` for several states through one decode loop (``HipT5Generator.generate_many``): entry ``i``
-        is ``generate_sync(states[i], ...)`` exactly (with ``sampling=sampling[i]``), de-duplication order included."""
+        is ``generate_sync(states[i], ...)`` exactly (with ``sampling=sampling[i]`` and ``prefix=prefixes[i]``),
+        de-duplication order included.  ``prefixes``: one string or None per state."""
         sampling = self._check_request(sampling, len(states))
+        prompts = None
+        if prefixes is not None:
+            prefixes = list(prefixes)
+            if len(prefixes) != len(states):
+                raise ValueError(f"prefixes holds {len(prefixes)} entries for {len(states)} states")
+            prompts = [self._prefix_ids(p) for p in prefixes]
+            if all(p is None for p in prompts):
+                prompts = None  # no prompt anywhere: the call as it always was
         ids = [encode_one(self.template % s, self.max_inp_seq_len) for s in states]
         if self.do_sample:
             return self._sampled(ids, num_samples, sampling)
         results: List[List[Tuple[str, float]]] = []
         cap = self.generator.decoder.max_states(num_samples)  # the engine's cap on states per call
         for i in range(0, len(ids), cap):
+            kw = {} if prompts is None else {"prefixes": prompts[i : i + cap]}
             outs = self.generator.generate_many(ids[i : i + cap], num_samples, self.max_oup_seq_len,
-                                                self.length_penalty, **self._books)
+                                                self.length_penalty, **self._books, **kw)
             results.extend(self._suggestions(out, num_samples) for out in outs)
         return results
 
@@ -322,35 +364,50 @@ class RetrievalAugmentedGenerator(TacticGenerator):
         self.retriever.load_corpus(self.indexed_corpus_path)
 
     def generate_sync(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
-                      num_samples: int, *, sampling: Optional[SamplingParams] = None) -> List[Tuple[str, float]]:
+                      num_samples: int, *, sampling: Optional[SamplingParams] = None,
+                      prefix: Optional[str] = None) -> List[Tuple[str, float]]:
         self.hf_gen._check_request(sampling)
+        self.hf_gen._prefix_ids(prefix)
         retrieved_premises, _ = self.retriever.retrieve(state, file_path, theorem_full_name, theorem_pos,
                                                         self.max_num_retrieved)
         aug_state = format_augmented_state(state, retrieved_premises, self.max_inp_seq_len)
         kw = {} if sampling is None else {"sampling": sampling}
+        if prefix:
+            kw["prefix"] = prefix
         return self.hf_gen.generate_sync(aug_state, file_path, theorem_full_name, theorem_pos, num_samples, **kw)
 
     async def generate(self, state: str, file_path: str, theorem_full_name: str, theorem_pos: Pos,
-                       num_samples: int, *, sampling: Optional[SamplingParams] = None) -> List[Tuple[str, float]]:
+                       num_samples: int, *, sampling: Optional[SamplingParams] = None,
+                       prefix: Optional[str] = None) -> List[Tuple[str, float]]:
         kw = {} if sampling is None else {"sampling": sampling}
+        if prefix:
+            kw["prefix"] = prefix
         if not (self.hf_gen.continuous or self.hf_gen.sample_stream):
             return self.generate_sync(state, file_path, theorem_full_name, theorem_pos, num_samples, **kw)
         self.hf_gen._check_request(sampling)
+        self.hf_gen._prefix_ids(prefix)
         retrieved_premises, _ = self.retriever.retrieve(state, file_path, theorem_full_name, theorem_pos,
                                                         self.max_num_retrieved)
         aug_state = format_augmented_state(state, retrieved_premises, self.max_inp_seq_len)
         return await self.hf_gen.generate(aug_state, file_path, theorem_full_name, theorem_pos, num_samples, **kw)
 
     def batch_generate_sync(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],
-                            theorem_poses: List[Pos], num_samples: int, *, sampling=None) -> List[List[Tuple[str, float]]]:
+                            theorem_poses: List[Pos], num_samples: int, *, sampling=None,
+                            prefixes=None) -> List[List[Tuple[str, float]]]:
         """Retrieve per state (``retrieve``, as ``generate_sync``), format each augmented state, then one batched
         generate."""
         sampling = self.hf_gen._check_request(sampling, len(states))
+        if prefixes is not None:
+            prefixes = list(prefixes)
+            for p in prefixes:
+                self.hf_gen._prefix_ids(p)  # refused here, before any retrieval
         aug_states = []
         for state, path, name, pos in zip_strict(states, file_paths, theorem_full_names, theorem_poses):
             retrieved_premises, _ = self.retriever.retrieve(state, path, name, pos, self.max_num_retrieved)
             aug_states.append(format_augmented_state(state, retrieved_premises, self.max_inp_seq_len))
         kw = {} if sampling is None else {"sampling": sampling}
+        if prefixes is not None:
+            kw["prefixes"] = prefixes
         return self.hf_gen.batch_generate_sync(aug_states, file_paths, theorem_full_names, theorem_poses, num_samples, **kw)
 
     async def batch_generate(self, states: List[str], file_paths: List[str], theorem_full_names: List[str],

@@ -56,6 +56,15 @@ the scalar form beside the scalar form's own spread over the repetitions, and wh
 same bits by contract).  No threshold: the scalar form measured in the same run is the bar.
 
     python tools/gen_bench.py --stream --sample --per-request [--reps 3] [--out profiles/gen_sample_params_bench.json]
+
+``--prefix-bytes N [N ...]``: the tactic prefix.  At 64 and at 8 beams, for every N: the one-pass prefill of an N-byte
+prefix (``rp_decoder_batch_prefill``) against the same cache rows written by N ordinary decode steps
+(``prefill_by_steps`` through ``rp_decoder_batch_step``), alternating in one process, device time per call; and in a
+host-books ``generate_stream`` of 8 slots with 7 searches running, the wall time of the step that admits an eighth
+source without a prefix, with an N-byte prefix prefilled in one pass, and with the prefix fed through steps, beside the
+ordinary steps around it.  No threshold: the by-steps path measured in the same run is the bar.
+
+    python tools/gen_bench.py --prefix-bytes 4 16 64 [--reps 5] [--out FILE]
 """
 from __future__ import annotations
 
@@ -388,6 +397,79 @@ def sample_params_bench(gen, cfg, reps, eos_boost, nb=64, max_len=512, n_src=16,
             "outputs_identical": same}
 
 
+def prefix_bench(gen, cfg, prefix_bytes, reps, max_len=512, src_bytes=2048, n_slots=8):
+    """One-pass prefill against ``prefill_by_steps`` (device milliseconds, alternating), and the admission step of a
+    host-books stream with and without a prefixed newcomer (wall milliseconds), at 64 and 8 beams."""
+    from reprover_amd.generation import prefill_by_steps
+
+    rng = np.random.default_rng(0)
+    srcs = [np.concatenate([rng.integers(3, 259, size=src_bytes - 1), [1]]).astype(np.int32) for _ in range(n_slots)]
+    text = rng.integers(3 + 32, 3 + 127, size=max(prefix_bytes)).astype(np.int32)
+    enc = gen.encode_hidden(srcs[0])
+    dec = gen.decoder
+    L = cfg["num_decoder_layers"]
+    res = {"metric": "gen_prefix_bench", "config": f"byt5-small ({L} decoder layers), sources of {src_bytes} bytes",
+           "max_length": max_len, "reps": reps, "slots": n_slots, "beams": {}}
+
+    def device_ms(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    def admission(nb, prefix, by_steps):
+        """(the admitting step's wall ms, the other steps' wall ms): 7 searches run 6 steps, the eighth joins."""
+        st = gen.generate_stream(nb, max_len, 0.0, n_slots=n_slots, src_cap=src_bytes)
+        if by_steps:
+            st.pool._prefill = None  # BeamSearchPool's default: the prompt through ordinary steps
+        for s in srcs[:-1]:
+            st.submit(s)
+        plain = []
+        for _ in range(6):
+            plain.append(_timed(st.step)[0])
+        st.submit(srcs[-1], prefix=prefix)
+        admit = _timed(st.step)[0]
+        for _ in range(4):
+            plain.append(_timed(st.step)[0])
+        return admit, plain[1:]  # (the first step admitted the seven)
+
+    for nb in (64, 8):
+        dec.start(enc, nb, max_len)
+        rows_warm = [0] + text[:3].tolist()
+        dec.prefill_many([0], [rows_warm])
+        prefill_by_steps(dec.step, nb, rows_warm, gen.device)
+        admission(nb, text[:2], False)
+        admission(nb, text[:2], True)
+        per = {}
+        for N in prefix_bytes:
+            rows = [0] + text[: N - 1].tolist()  # the N prompt rows: [start] + the prefix without its last byte
+            dec.start(enc, nb, max_len)
+            one, steps = [], []
+            for _ in range(reps):
+                one.append(device_ms(lambda: dec.prefill_many([0], [rows])))
+                steps.append(device_ms(lambda: prefill_by_steps(dec.step, nb, rows, gen.device)))
+            none_ms, pass_ms, step_ms, plain = [], [], [], []
+            for _ in range(max(2, reps // 2)):
+                for kind, prefix, by_steps in ((none_ms, None, False), (pass_ms, text[:N], False), (step_ms, text[:N], True)):
+                    a, p = admission(nb, prefix, by_steps)
+                    kind.append(a)
+                    plain += p
+            per[str(N)] = {
+                "one_pass_ms": [round(x, 3) for x in one], "by_steps_ms": [round(x, 3) for x in steps],
+                "ratio_by_steps_over_one_pass": round(min(steps) / min(one), 2),
+                "one_pass_faster": max(one) < min(steps),
+                "stream_admission_step_ms": {"no_prefix": [round(x, 2) for x in none_ms],
+                                             "prefix_one_pass": [round(x, 2) for x in pass_ms],
+                                             "prefix_by_steps": [round(x, 2) for x in step_ms]},
+                "stream_plain_step_ms_median": round(float(np.median(plain)), 2),
+            }
+        res["beams"][str(nb)] = per
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -402,7 +484,20 @@ def main(argv=None):
                     help="with --stream --sample: the factor on the EOS row of lm_head.weight (states end at different lengths)")
     ap.add_argument("--per-request", action="store_true",
                     help="with --stream --sample: the stream's scalars against the same values per ticket (the parameter table)")
+    ap.add_argument("--prefix-bytes", type=int, nargs="+", default=None,
+                    help="the one-pass prompt prefill against prefill_by_steps, and a stream's admission step with a prefix")
     args = ap.parse_args(argv)
+    if args.prefix_bytes:
+        if min(args.prefix_bytes) < 1 or max(args.prefix_bytes) > 500 or args.states or args.stream or args.sample:
+            ap.error("--prefix-bytes takes values in 1..500 and goes alone")
+        cfg = synth.seq2seq_config("byt5-small")
+        gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
+        line = json.dumps(prefix_bench(gen, cfg, sorted(args.prefix_bytes), max(args.reps, 3)))
+        print(line)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     if args.per_request and not (args.stream and args.sample):
         ap.error("--per-request goes with --stream --sample")
     if args.sync_every and (not (args.states or args.stream) or args.sample or min(args.sync_every) < 1):
