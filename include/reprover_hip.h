@@ -533,6 +533,62 @@ RpStatus rp_dbg_decoder_rows(int32_t mode, const void* a, const void* b, const i
                              void* stream);
 RpStatus rp_dbg_hidden_head(const void* xhi, const void* xlo, const float* rs, const float* ln, const float* d_hidden,
                             int32_t T, int32_t D, void* out_hidden, void* dxhi, void* dxlo, float* dln, void* stream);
+/* The encoder's pooling head, its training row kernels and the weight pack / unpack kernels in isolation
+ * (tests/test_encoder_train_kernels_gpu.py; test-only).  Device pointers; each runs the launch functions
+ * the encoder pass and the trainer run, with the same grids and in the same order; arguments are checked before anything is
+ * launched (RP_E_INVALID: nothing launched, nothing written) and no output is zeroed first.
+ *   rp_dbg_train_rows (launch only): one kernel per mode; (p, seed) = the dropout of modes 1, 2, 5 (p = 0: off).
+ *     0 embed_kernel<false>, 1 embed_train_kernel (p > 0): ia = ids [T], a = table f32 [vocab, n]; o0 / o1 = the planes bf16
+ *       [rows, n] (rows = Tp >= T; rows T .. Tp get token 0), o2 = ssp f32 [np, rows] (slot 0 = the row's sum of squares).  Ids
+ *       are clamped to [0, vocab).
+ *     2 mask_dx_kernel: a / b = dxhi / dxlo bf16 [rows, n]; o0 = bf16((hi + lo) * mask(site)) [rows, n].
+ *     3 qkv_scale_dot_kernel: o0 = dqkv bf16 [rows, n] IN PLACE (rows < T scaled by rs, rows T .. rows zeroed), a = qkv bf16
+ *       [rows, n], b = rs f32 [rows]; o1 = rcoef f32 [rows] = rs^2 (dqkv . qkv) inv_d (0 on rows >= T).
+ *     4 rowdot_finish_kernel: a = rdp f32 [np, ld], b = rs f32 [rows]; o0 = rcoef f32 [rows] = rs^2 (sum_p rdp[p]) inv_d.
+ *     5 embed_bwd_kernel: ia = ids [T], a / b = dxhi / dxlo bf16 [T, n]; o0 = d table f32 [vocab, n], every row written; an
+ *       id is clamped to [0, vocab) exactly as the forward's gather clamps it (a negative id lands in row 0).
+ *   rp_dbg_pool_head (synchronises; the lists' scratch is allocated inside): worklist_kernel, the forward head, and with
+ *     d_emb != NULL pool_bwd_seq_kernel + colsum_kernel + pool_bwd_tok_kernel.  xhi bf16 [>= T, D]; xlo: the bf16 lo plane, or
+ *     with lo8 the uint8 extension plane of the 24-bit form; rs f32 [T]; cu int32 [batch + 1]; w f32 [D]; chunk 32 / 64 / 128.
+ *     p > 0: pool_partial_train_kernel (the mask of RP_DROP_SITE_FINAL).  Dropout and the backward take the trainer's form only
+ *     (chunk 128, fuse 0, bf16 lo plane, fp32 out).  out [batch, D] f32 / bf16; partial f32 [T / chunk + batch, D]: chunk c of
+ *     sequence b at row cu[b] / chunk + b + c, gap rows untouched, and with fuse the rows of one-chunk sequences untouched;
+ *     pwork int32 [T / chunk + batch, 4] = {first token, length, chunk, sequence}, gap entries zero; ds, dwf f32 [batch, D];
+ *     d_final_ln f32 [D]; dxhi / dxlo bf16 [>= T, D] (rows < T written).  Every sequence holds at least its EOS: cu must run
+ *     0 .. T strictly increasing - an empty sequence is outside the pooling head's contract (rp_encode_varlen and
+ *     rp_train_forward launch no chunk for it, so its `out` row is not written, and the pooled backward divides by its length)
+ *     and is RP_E_INVALID here.
+ *   rp_dbg_repack (launch only): ONE repack_layer_kernel launch over 1 .. 4 matrices.  Per matrix: mode 0 = q | k | v rows
+ *     (s0, s1, s2 f32 [n, cols], rows = 3 n), 1 = 32 rows of s0 then the same 32 of s1 (f32 [rows / 2, cols]), 2 = copy of s0;
+ *     colscale f32 [cols] or NULL; dst bf16 [rows, cols] = bf16(master * colscale), dst_t bf16 [cols, rows] = its transpose.
+ *     rows and cols are multiples of 64.
+ *   rp_dbg_bias_table (launch only): tab f32 [H, ntab], tab[h, o] = rel_bias[bucket_of[o], h] (rel_bias f32 [buckets, H]).
+ *   rp_dbg_unfold (launch only): ONE unfold_kernel launch, then (modes 1, 2) the colsum_kernel over dln_part the trainer
+ *     runs.  part f32 [splits] x [rows, C] at split_stride elements; mode 0: g0 [rows, C] = the sum over the splits; 1: rows
+ *     [k n, (k + 1) n) -> g_k [n, C] (rows = 3 n); 2: rows 64 j + {0 .. 31} -> g0 rows 32 j .., 64 j + {32 .. 63} -> g1 (rows %
+ *     64 == 0), each times ln [C]; w0 / w1 / w2: the masters, shaped as g; dln_part f32 [ceil(rows / 32), C]; dln f32 [C] =
+ *     sum_r (sum over the splits)[r, c] * master[r, c].  C % 4 == 0. */
+typedef struct RpDbgRepackMat {
+  const float* s0;
+  const float* s1;
+  const float* s2;
+  const float* colscale;
+  void* dst;
+  void* dst_t;
+  int32_t rows, cols, n, mode;
+} RpDbgRepackMat;
+RpStatus rp_dbg_train_rows(int32_t mode, const void* a, const void* b, const int32_t* ia, int32_t T, int32_t rows, int32_t n,
+                           int32_t vocab, int32_t np, int32_t ld, float inv_d, float p, uint32_t seed, uint32_t site, void* o0,
+                           void* o1, void* o2, void* stream);
+RpStatus rp_dbg_pool_head(const void* xhi, const void* xlo, int32_t lo8, const float* rs, const int32_t* cu_seqlens,
+                          int32_t batch, int32_t T, int32_t D, const float* w, int32_t chunk, int32_t fuse, int32_t out_bf16,
+                          const float* d_emb, float p, uint32_t seed, void* out, float* partial, void* pwork, float* ds,
+                          float* dwf, float* d_final_ln, void* dxhi, void* dxlo, void* stream);
+RpStatus rp_dbg_repack(const RpDbgRepackMat* mats, int32_t n_mats, void* stream);
+RpStatus rp_dbg_bias_table(const float* rel_bias, const int32_t* bucket_of, int32_t H, int32_t ntab, float* tab, void* stream);
+RpStatus rp_dbg_unfold(const float* part, int64_t split_stride, int32_t splits, int32_t rows, int32_t C, int32_t mode, int32_t n,
+                       float* g0, float* g1, float* g2, const float* w0, const float* w1, const float* w2, const float* ln,
+                       float* dln_part, float* dln, void* stream);
 /* The decode step's kernels in isolation (tests/test_decode_step_kernels_gpu.py; test-only).  Device
  * pointers unless said otherwise, launch only (stream-ordered), through the launch code rp_decoder_batch_step / _pool_step run.
  *   rp_dbg_dec_gemm: dec_gemm_kernel<ceil(K / 512), epi>: out[m, n] = sum_k A[m, k] W[n, k], A bf16 [M, lda], W bf16 [N, K]

@@ -69,6 +69,12 @@ class RpT5DecoderWeights(C.Structure):
     ]
 
 
+class RpDbgRepackMat(C.Structure):
+    """One matrix of rp_dbg_repack (test-only)."""
+    _fields_ = [(n, C.c_void_p) for n in ("s0", "s1", "s2", "colscale", "dst", "dst_t")] + [
+        (n, C.c_int32) for n in ("rows", "cols", "n", "mode")]
+
+
 class HipLibraryError(RuntimeError):
     """A libreprover_hip call returned a non-zero status."""
 
@@ -244,6 +250,26 @@ SIGNATURES = {
         C.c_int32,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
          C.c_void_p, C.c_void_p],
+    ),
+    # the encoder's pooling head, training row kernels and weight pack / unpack kernels in isolation (test-only:
+    # tests/test_encoder_train_kernels_gpu.py)
+    "rp_dbg_train_rows": (
+        C.c_int32,
+        [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+         C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "rp_dbg_pool_head": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+         C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "rp_dbg_repack": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "rp_dbg_bias_table": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rp_dbg_unfold": (
+        C.c_int32,
+        [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     ),
     # the decode step's kernels in isolation (test-only: tests/test_decode_step_kernels_gpu.py)
     "rp_dbg_dec_gemm": (

@@ -409,8 +409,7 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
   RP_CHECK_LAUNCH();
   const dim3 att_grid(H, T / ATT_Q + batch);  // upper bound of the number of 128-query blocks
   const int pc = g_pool_chunk;
-  hipLaunchKernelGGL(worklist_kernel, dim3(1), dim3(1024), 0, stream, cu_seqlens, batch, w.work, (int)att_grid.y, w.pwork,
-                     T / pc + batch, pc);
+  launch_worklist(cu_seqlens, batch, w.work, (int)att_grid.y, w.pwork, T / pc + batch, pc, stream);
   for (int i = 0; i < c.num_layers; ++i) {
     const LayerPacked& L = e->layers[i];
     // attention sub-layer: qkv = rs * (xb Wqkv'^T)  ->  attention  ->  x += att Wo^T  (+ xb, ssp refreshed)
@@ -451,8 +450,7 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
     ProfScope ps(stream, RP_K_POOL);
     launch_pool_partial(dim3(T / pc + batch), stream, w.xb, w.xlo, w.rs, (const int4*)w.pwork, w.pool, D, pc, e->final_ln, out,
                         out_dtype == RP_DT_BF16 ? 1 : 0, 1, true);
-    hipLaunchKernelGGL(pool_finish_kernel, dim3(batch), dim3(256), 0, stream, w.pool, e->final_ln, cu_seqlens, out,
-                       out_dtype == RP_DT_BF16 ? 1 : 0, D, pc, 1);
+    launch_pool_finish(batch, stream, w.pool, e->final_ln, cu_seqlens, out, out_dtype == RP_DT_BF16 ? 1 : 0, D, pc, 1);
   }
   RP_CHECK_LAUNCH();
   return RP_OK;

@@ -1400,6 +1400,22 @@ static __global__ __launch_bounds__(256, DROP ? 2 : 4) void attention_kernel(con
 //   across XCDs costs ~2 us per workgroup, serialised per XCD: 0.13 -> 0.45 ms per pass).
 // ------------------------------------------------------------------------------------------
 
+// A thread's share of |e|^2 over its N columns (unused entries 0), ONE explicit rounding sequence for pool_partial_kernel's
+// fused finish and pool_finish_kernel: e[1]^2 rounded, then fused multiply-adds of e[0], e[2], e[3], ...  Left to the
+// compiler's contraction of `part += e * e` the two kernels disagreed - pool_finish_kernel's unrolled sum came out in this
+// order, the fused path's loop as e[0], e[1], e[2], ... - so for d_model > 256 a one-chunk sequence's norm, and with it every
+// element of its row, could differ in the last bit between fuse = 1 and fuse = 0 (tests/test_encoder_train_kernels_gpu.py,
+// fuse against no fuse).  pool_finish_kernel's order is the one kept: the trainer's rows and every multi-chunk row keep
+// their bits.
+template <int N>
+__device__ __forceinline__ float pool_sumsq(const float (&e)[N]) {
+  static_assert(N >= 2, "at least two columns per thread");
+  float part = __fmaf_rn(e[0], e[0], __fmul_rn(e[1], e[1]));
+#pragma unroll
+  for (int i = 2; i < N; ++i) part = __fmaf_rn(e[i], e[i], part);
+  return part;
+}
+
 // NV = 16-byte pieces (8 features) per lane and plane covering a row (ceil(D / 512)): 3 for d_model 1472 / 1536,
 // 4 up to 2048.  R token rows of a wave are in flight before the first is consumed (the rows are independent
 // streams: rs comes from rowscale).  `chunk` = tokens per workgroup.  A sequence of ONE chunk is finished here (weight,
@@ -1483,14 +1499,14 @@ __global__ __launch_bounds__(256) void pool_partial_kernel(const bf16_t* __restr
   // the whole sequence: pool_finish_kernel's arithmetic on the sums (0 + sum is sum: the same bits as through `partial`)
   const float inv_len = 1.f / (float)len;
   float vals[NV * 2];
-  float part = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV * 2; ++i) vals[i] = 0.f;
   int cnt = 0;
   for (int col = threadIdx.x; col < D; col += 256) {
     const float sum = (red[0][col] + red[1][col]) + (red[2][col] + red[3][col]);
-    const float e = sum * inv_len * w[col];
-    vals[cnt++] = e;
-    part += e * e;
+    vals[cnt++] = sum * inv_len * w[col];
   }
+  float part = pool_sumsq(vals);
   part = wave_sum(part);
   if (lane == 0) nrm[wave] = part;
   __syncthreads();
@@ -1561,14 +1577,12 @@ static __global__ __launch_bounds__(256) void pool_finish_kernel(const float* __
       }
   }
   float vals[NC];
-  float part = 0.f;
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
     const int col = threadIdx.x + 256 * i;
-    const float e = (col < D) ? sum[i] * inv_len * w[min(col, D - 1)] : 0.f;
-    vals[i] = e;
-    part += e * e;
+    vals[i] = (col < D) ? sum[i] * inv_len * w[min(col, D - 1)] : 0.f;
   }
+  float part = pool_sumsq(vals);
   part = wave_sum(part);
   if (lane == 0) nrm[wave] = part;
   __syncthreads();
@@ -1585,6 +1599,17 @@ static __global__ __launch_bounds__(256) void pool_finish_kernel(const float* __
         reinterpret_cast<float*>(out)[(size_t)b * D + col] = e;
     }
   }
+}
+
+// The two launches around the pooling kernels, on raw pointers: the encoder pass, the trainer and the rp_dbg_pool_head test
+// entry all launch through these.
+static void launch_worklist(const int32_t* cu, int batch, int4* work, int n_slots, int4* pwork, int n_pslots, int pool_chunk,
+                            hipStream_t stream) {
+  hipLaunchKernelGGL(worklist_kernel, dim3(1), dim3(1024), 0, stream, cu, batch, work, n_slots, pwork, n_pslots, pool_chunk);
+}
+static void launch_pool_finish(int batch, hipStream_t stream, const float* partial, const float* w, const int32_t* cu, void* out,
+                               int out_bf16, int D, int chunk, int fuse) {
+  hipLaunchKernelGGL(pool_finish_kernel, dim3(batch), dim3(256), 0, stream, partial, w, cu, out, out_bf16, D, chunk, fuse);
 }
 
 // ------------------------------------------------------------------------------------------

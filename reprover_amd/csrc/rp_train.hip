@@ -243,6 +243,88 @@ RpStatus run_unfold(const UnfoldArgs& a, hipStream_t stream) {
   return RP_OK;
 }
 
+// ---- the memory-bound launches of the step, on raw pointers ------------------------------------------------
+// The trainer and the kernel-level test entry points (rp_dbg_train_rows, rp_dbg_pool_head, rp_dbg_repack, rp_dbg_unfold) both
+// launch through these: one grid rule per kernel.  No profiling scope and no launch check inside: the caller's.
+void launch_embed(const int32_t* ids, const float* table, bf16_t* xhi, bf16_t* xlo, float* ssp, int np, int T, int Tp, int D,
+                  int vocab, const Drop& drop, hipStream_t stream) {
+  if (drop.thresh)
+    hipLaunchKernelGGL(embed_train_kernel, dim3((Tp + 3) / 4), dim3(256), 0, stream, ids, table, xhi, xlo, ssp, np, T, Tp, D, vocab,
+                       drop);
+  else
+    hipLaunchKernelGGL(embed_kernel<false>, dim3((Tp + 3) / 4), dim3(256), 0, stream, ids, table, xhi, xlo, ssp, np, T, Tp, D, vocab,
+                       (const int32_t*)nullptr);
+}
+void launch_mask_dx(const bf16_t* dxhi, const bf16_t* dxlo, bf16_t* dxm, int rows, int D, const Drop& drop, uint32_t site,
+                    hipStream_t stream) {
+  hipLaunchKernelGGL(mask_dx_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, dxhi, dxlo, dxm, rows, D, drop, site);
+}
+void launch_rowdot_finish(const float* rdp, int np, int ld, const float* rs, float inv_d, float* rcoef, int rows,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(rowdot_finish_kernel, dim3((rows + 63) / 64), dim3(64), 0, stream, rdp, np, ld, rs, inv_d, rcoef, rows);
+}
+void launch_qkv_scale_dot(bf16_t* dqkv, const bf16_t* qkv, const float* rs, float* rcoef, int T, int rows, int width, float inv_d,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(qkv_scale_dot_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, dqkv, qkv, rs, rcoef, T, rows, width, inv_d);
+}
+void launch_embed_bwd(const int32_t* ids, int T, int vocab, const bf16_t* dxhi, const bf16_t* dxlo, int D, float* dtable,
+                      const Drop& drop, hipStream_t stream) {
+  hipLaunchKernelGGL(embed_bwd_kernel, dim3(vocab, (D + 255) / 256), dim3(256), 0, stream, ids, T, vocab, dxhi, dxlo, D, dtable,
+                     drop);
+}
+void launch_colsum(const float* part, int rows, int C, float* out, hipStream_t stream) {
+  hipLaunchKernelGGL(colsum_kernel, dim3((C + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, part, rows, C, out);
+}
+void launch_bias_table(const float* rel_bias, const int32_t* bucket_of, int H, int ntab, float* tab, hipStream_t stream) {
+  hipLaunchKernelGGL(bias_table_kernel, dim3((H * ntab + 255) / 256), dim3(256), 0, stream, rel_bias, bucket_of, H, ntab, tab);
+}
+// one repack_layer_kernel launch over up to four matrices: add() in order, then launch (an unused entry starts behind the
+// last tile, so no workgroup selects it)
+struct RepackPlan {
+  RepackArgs a{};
+  int count = 0, tiles = 0;
+  void add(const float* s0, const float* s1, const float* s2, const float* cs, bf16_t* dst, bf16_t* dst_t, int rows, int cols,
+           int n, int mode) {
+    a.m[count++] = RepackMat{s0, s1, s2, cs, dst, dst_t, rows, cols, n, mode, tiles};
+    tiles += (rows / 64) * (cols / 64);
+  }
+  void launch(hipStream_t stream) {
+    for (int k = count; k < 4; ++k) a.m[k].tile0 = tiles;
+    hipLaunchKernelGGL(repack_layer_kernel, dim3(tiles), dim3(256), 0, stream, a);
+  }
+};
+
+// The pooling head's forward on raw pointers: the chunk sums (the inference kernel; under dropout the training one, which
+// masks the final norm's output), then the per-sequence finish.  The trainer runs chunk = POOL_CHUNK, fuse = 0, bf16 lo plane.
+void launch_pool_head(const bf16_t* xhi, const bf16_t* xlo, bool lo8, const float* rs, const int4* pwork, float* partial,
+                      const int32_t* cu, int batch, int T, int D, int chunk, const float* w, void* out, int out_bf16, int fuse,
+                      const Drop& drop, hipStream_t stream) {
+  const dim3 pg(T / chunk + batch);
+  if (!drop.thresh)
+    launch_pool_partial(pg, stream, xhi, xlo, rs, pwork, partial, D, chunk, w, out, out_bf16, fuse, lo8);
+  else if (D <= 3 * 512)
+    hipLaunchKernelGGL(pool_partial_train_kernel<3>, pg, dim3(256), 0, stream, xhi, xlo, rs, pwork, partial, D, drop);
+  else
+    hipLaunchKernelGGL(pool_partial_train_kernel<4>, pg, dim3(256), 0, stream, xhi, xlo, rs, pwork, partial, D, drop);
+  launch_pool_finish(batch, stream, partial, w, cu, out, out_bf16, D, chunk, fuse);
+}
+// ... and its backward: per sequence ds / dwf from the forward's chunk sums, d final_layer_norm.weight = the column sums of
+// dwf, then per token the two planes of the residual gradient
+void launch_pool_bwd_head(const bf16_t* xhi, const bf16_t* xlo, const float* rs, const int4* pwork, const float* partial,
+                          const float* w, const int32_t* cu, int batch, int T, int D, const float* d_emb, float* ds, float* dwf,
+                          float* d_final_ln, bf16_t* dxhi, bf16_t* dxlo, const Drop& drop, hipStream_t stream) {
+  const float inv_d = 1.f / (float)D;
+  hipLaunchKernelGGL(pool_bwd_seq_kernel, dim3(batch), dim3(256), 0, stream, partial, w, cu, d_emb, ds, dwf, D);
+  launch_colsum(dwf, batch, D, d_final_ln, stream);
+  const dim3 pg(T / POOL_CHUNK + batch);
+  if (D <= 3 * 512)
+    hipLaunchKernelGGL(pool_bwd_tok_kernel<3>, pg, dim3(256), 0, stream, xhi, xlo, rs, pwork, (const float*)ds, dxhi, dxlo, D, inv_d,
+                       drop);
+  else
+    hipLaunchKernelGGL(pool_bwd_tok_kernel<4>, pg, dim3(256), 0, stream, xhi, xlo, rs, pwork, (const float*)ds, dxhi, dxlo, D, inv_d,
+                       drop);
+}
+
 // ---- forward with saved activations -----------------------------------------------------------------------
 // The shared body of rp_train_forward and rp_train_forward_hidden: embedding, every layer, the final RMSNorm's row
 // statistic.  Leaves the final residual stream in xa[L] + xlo and rs_final; the entry point's head follows.
@@ -262,16 +344,10 @@ RpStatus forward_layers(RpTrainer* tr, const int32_t* ids, const int32_t* cu, in
   const Drop drop = tr->drop;
   {
     ProfScope ps(stream, RP_K_EMBED);
-    if (drop.thresh)
-      hipLaunchKernelGGL(embed_train_kernel, dim3((Tp + 3) / 4), dim3(256), 0, stream, ids, (const float*)e->embed, w.xa[0], w.xlo,
-                         w.ssp, np, T, Tp, D, c.vocab_size, drop);
-    else
-      hipLaunchKernelGGL(embed_kernel<false>, dim3((Tp + 3) / 4), dim3(256), 0, stream, ids, e->embed, w.xa[0], w.xlo, w.ssp, np, T, Tp,
-                         D, c.vocab_size, (const int32_t*)nullptr);
+    launch_embed(ids, (const float*)e->embed, w.xa[0], w.xlo, w.ssp, np, T, Tp, D, c.vocab_size, drop, stream);
   }
   const dim3 att_grid(H, T / ATT_Q + batch);
-  hipLaunchKernelGGL(worklist_kernel, dim3(1), dim3(1024), 0, stream, cu, batch, w.work, (int)att_grid.y, w.pwork,
-                     T / POOL_CHUNK + batch, POOL_CHUNK);
+  launch_worklist(cu, batch, w.work, (int)att_grid.y, w.pwork, T / POOL_CHUNK + batch, POOL_CHUNK, stream);
   RP_CHECK_LAUNCH();
   for (int i = 0; i < L; ++i) {
     const LayerPacked& Lw = e->layers[i];
@@ -319,18 +395,9 @@ RpStatus pool_head(RpTrainer* tr, const int32_t* cu, int batch, int T, float* ou
   const Drop drop = tr->drop;
   {
     ProfScope ps(stream, RP_K_POOL);
-    const dim3 pg(T / POOL_CHUNK + batch);
-    if (!drop.thresh)
-      launch_pool_partial(pg, stream, w.xa[L], w.xlo, w.rs_final, (const int4*)w.pwork, w.pool, D, POOL_CHUNK, (const float*)e->final_ln,
-                          (void*)out_emb, 0, 0 /* the backward reads every chunk's sums from `pool` */, false);
-    else if (D <= 3 * 512)
-      hipLaunchKernelGGL(pool_partial_train_kernel<3>, pg, dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
-                         (const float*)w.rs_final, (const int4*)w.pwork, w.pool, D, drop);
-    else
-      hipLaunchKernelGGL(pool_partial_train_kernel<4>, pg, dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
-                         (const float*)w.rs_final, (const int4*)w.pwork, w.pool, D, drop);
-    hipLaunchKernelGGL(pool_finish_kernel, dim3(batch), dim3(256), 0, stream, (const float*)w.pool, (const float*)e->final_ln,
-                       cu, (void*)out_emb, 0, D, POOL_CHUNK, 0);
+    launch_pool_head(w.xa[L], w.xlo, false, w.rs_final, (const int4*)w.pwork, w.pool, cu, batch, T, D, POOL_CHUNK,
+                     (const float*)e->final_ln, (void*)out_emb, 0, 0 /* the backward reads every chunk's sums from `pool` */, drop,
+                     stream);
   }
   RP_CHECK_LAUNCH();
   return RP_OK;
@@ -375,20 +442,10 @@ RpStatus pool_bwd_head(RpTrainer* tr, const int32_t* cu, int batch, int T, const
                        hipStream_t stream) {
   RpEncoder* e = tr->enc;
   const int D = e->cfg.d_model, L = e->cfg.num_layers;
-  const float inv_d = 1.f / (float)D;
-  const Drop drop = tr->drop;
   ProfScope ps(stream, RP_K_BWD_OTHER);
-  hipLaunchKernelGGL(pool_bwd_seq_kernel, dim3(batch), dim3(256), 0, stream, (const float*)w.pool, (const float*)e->final_ln, cu,
-                     d_emb, w.ds_seq, w.dwf_seq, D);
-  hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)w.dwf_seq, batch, D,
-                     grads + tr->lay.final_ln());
-  const dim3 pg(T / POOL_CHUNK + batch);
-  if (D <= 3 * 512)
-    hipLaunchKernelGGL(pool_bwd_tok_kernel<3>, pg, dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
-                       (const float*)w.rs_final, (const int4*)w.pwork, (const float*)w.ds_seq, w.dxhi, w.dxlo, D, inv_d, drop);
-  else
-    hipLaunchKernelGGL(pool_bwd_tok_kernel<4>, pg, dim3(256), 0, stream, (const bf16_t*)w.xa[L], (const bf16_t*)w.xlo,
-                       (const float*)w.rs_final, (const int4*)w.pwork, (const float*)w.ds_seq, w.dxhi, w.dxlo, D, inv_d, drop);
+  launch_pool_bwd_head((const bf16_t*)w.xa[L], (const bf16_t*)w.xlo, (const float*)w.rs_final, (const int4*)w.pwork,
+                       (const float*)w.pool, (const float*)e->final_ln, cu, batch, T, D, d_emb, w.ds_seq, w.dwf_seq,
+                       grads + tr->lay.final_ln(), w.dxhi, w.dxlo, tr->drop, stream);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
@@ -413,7 +470,7 @@ RpStatus launch_hidden_bwd_head(const bf16_t* xhi, const bf16_t* xlo, const floa
       drop.thresh ? launch(hidden_head_bwd_kernel<4, true>) : launch(hidden_head_bwd_kernel<4, false>);
   }
   ProfScope ps(stream, RP_K_BWD_OTHER);
-  hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)dhead_part, nblk, D, dln);
+  launch_colsum(dhead_part, nblk, D, dln, stream);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
@@ -445,8 +502,7 @@ RpStatus backward_layers(RpTrainer* tr, const float* params, const int32_t* ids,
   auto mask_first = [&](uint32_t site) {
     if (!drop.thresh) return;
     ProfScope ps(stream, RP_K_BWD_OTHER);
-    hipLaunchKernelGGL(mask_dx_kernel, dim3((Tp + 3) / 4), dim3(256), 0, stream, (const bf16_t*)w.dxhi, (const bf16_t*)w.dxlo,
-                       w.dxm, Tp, D, drop, site);
+    launch_mask_dx((const bf16_t*)w.dxhi, (const bf16_t*)w.dxlo, w.dxm, Tp, D, drop, site, stream);
   };
   // dx += A W - x rcoef (RMSNorm backward in the epilogue), and dxm for the branch whose backward comes next (0 = none)
   auto rms_bwd_gemm = [&](const bf16_t* A, int K, const bf16_t* Wt, const bf16_t* x_saved, uint32_t next_site) -> RpStatus {
@@ -484,8 +540,7 @@ RpStatus backward_layers(RpTrainer* tr, const float* params, const int32_t* ids,
       return st;
     {
       ProfScope ps(stream, RP_K_BWD_OTHER);
-      hipLaunchKernelGGL(rowdot_finish_kernel, dim3((Tp + 63) / 64), dim3(64), 0, stream, (const float*)w.rdp, (F + 63) / 64, Tp,
-                         (const float*)w.rsf[i], inv_d, w.rcoef, Tp);
+      launch_rowdot_finish((const float*)w.rdp, (F + 63) / 64, Tp, (const float*)w.rsf[i], inv_d, w.rcoef, Tp, stream);
     }
     // dWi' = dzs^T x  -> unfold (de-interleave gate / up, x ln_ff, d ln_ff); with the pair plan dWo2 rides in the same launch
     // (dxb is still the branch's masked gradient: the epilogue that overwrites it comes below)
@@ -516,8 +571,7 @@ RpStatus backward_layers(RpTrainer* tr, const float* params, const int32_t* ids,
         if ((st = run_unfold(a, stream))) return st;
       }
       ProfScope ps(stream, RP_K_BWD_OTHER);
-      hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)w.dln_part, (2 * F + 31) / 32,
-                         D, grads + lay.layer(i, P_LN_FF));
+      launch_colsum((const float*)w.dln_part, (2 * F + 31) / 32, D, grads + lay.layer(i, P_LN_FF), stream);
     }
     // dx += dzs Wi' - x rcoef   (RMSNorm backward in the epilogue)
     if ((st = rms_bwd_gemm(w.dzs, 2 * F, Lt.wi_t, w.xf[i], site + 1))) return st;
@@ -559,8 +613,7 @@ RpStatus backward_layers(RpTrainer* tr, const float* params, const int32_t* ids,
     }
     {
       ProfScope ps(stream, RP_K_BWD_OTHER);
-      hipLaunchKernelGGL(qkv_scale_dot_kernel, dim3((Tp + 3) / 4), dim3(256), 0, stream, w.dqkv, (const bf16_t*)w.qkv[i],
-                         (const float*)w.rsa[i], w.rcoef, T, Tp, 3 * inner, inv_d);
+      launch_qkv_scale_dot(w.dqkv, (const bf16_t*)w.qkv[i], (const float*)w.rsa[i], w.rcoef, T, Tp, 3 * inner, inv_d, stream);
     }
     {
       const int S = apair.splits ? apair.splits : wgrad_splits(3 * inner, D, nk);
@@ -581,15 +634,13 @@ RpStatus backward_layers(RpTrainer* tr, const float* params, const int32_t* ids,
       a.ln = params + lay.layer(i, P_LN_ATTN); a.dln_part = w.dln_part;
       if ((st = run_unfold(a, stream))) return st;
       ProfScope ps(stream, RP_K_BWD_OTHER);
-      hipLaunchKernelGGL(colsum_kernel, dim3((D + 63) / 64), dim3(64 * COLSUM_WAVES), 0, stream, (const float*)w.dln_part, (3 * inner + 31) / 32,
-                         D, grads + lay.layer(i, P_LN_ATTN));
+      launch_colsum((const float*)w.dln_part, (3 * inner + 31) / 32, D, grads + lay.layer(i, P_LN_ATTN), stream);
     }
     if ((st = rms_bwd_gemm(w.dqkv, 3 * inner, Lt.wqkv_t, w.xa[i], i > 0 ? site - 8u + 3u : 0u))) return st;
   }
   {
     ProfScope ps(stream, RP_K_BWD_OTHER);
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3(c.vocab_size, (D + 255) / 256), dim3(256), 0, stream, ids, T, c.vocab_size,
-                       (const bf16_t*)w.dxhi, (const bf16_t*)w.dxlo, D, grads + lay.embed(), drop);
+    launch_embed_bwd(ids, T, c.vocab_size, (const bf16_t*)w.dxhi, (const bf16_t*)w.dxlo, D, grads + lay.embed(), drop, stream);
     hipLaunchKernelGGL(bias_grad_kernel, dim3(H), dim3(256), 0, stream, (const float*)w.dtab_part, (int)att_grid.y, H, ntab,
                        (const int32_t*)tr->bucket_of, c.rel_num_buckets, grads + lay.rel_bias());
     RP_CHECK_LAUNCH();
@@ -710,27 +761,20 @@ extern "C" RpStatus rp_trainer_load_params(RpTrainer* tr, const float* params, v
   embed_table_x24(e, stream);  // the inference pass's pre-encoded copy of the table follows the masters
   RP_HIP(hipMemcpyAsync(e->final_ln, params + lay.final_ln(), (size_t)D * 4, hipMemcpyDeviceToDevice, stream));
   const int ntab = 2 * e->maxd + 1;
-  hipLaunchKernelGGL(bias_table_kernel, dim3((H * ntab + 255) / 256), dim3(256), 0, stream, params + lay.rel_bias(),
-                     (const int32_t*)tr->bucket_of, H, ntab, e->bias_tab);
+  launch_bias_table(params + lay.rel_bias(), (const int32_t*)tr->bucket_of, H, ntab, e->bias_tab, stream);
   for (int i = 0; i < c.num_layers; ++i) {
     LayerPacked& L = e->layers[i];
     const LayerT& t = tr->lt[i];
     const float* ln_a = params + lay.layer(i, P_LN_ATTN);
     const float* ln_f = params + lay.layer(i, P_LN_FF);
-    RepackArgs a{};
-    int tile0 = 0;
-    auto mat = [&](int k, const float* s0, const float* s1, const float* s2, const float* cs, bf16_t* dst, bf16_t* dst_t,
-                   int rows, int cols, int n, int mode) {
-      a.m[k] = RepackMat{s0, s1, s2, cs, dst, dst_t, rows, cols, n, mode, tile0};
-      tile0 += (rows / 64) * (cols / 64);
-    };
-    mat(0, params + lay.layer(i, P_Q), params + lay.layer(i, P_K), params + lay.layer(i, P_V), ln_a, L.wqkv, t.wqkv_t,
-        3 * inner, D, inner, (int)PACK_CONCAT3);
-    mat(1, params + lay.layer(i, P_O), nullptr, nullptr, nullptr, L.wo, t.wo_t, D, inner, 0, (int)PACK_COPY);
-    mat(2, params + lay.layer(i, P_WI0), params + lay.layer(i, P_WI1), nullptr, ln_f, L.wi, t.wi_t, 2 * F, D, 0,
-        (int)PACK_GEGLU);
-    mat(3, params + lay.layer(i, P_WO), nullptr, nullptr, nullptr, L.wo2, t.wo2_t, D, F, 0, (int)PACK_COPY);
-    hipLaunchKernelGGL(repack_layer_kernel, dim3(tile0), dim3(256), 0, stream, a);
+    RepackPlan plan;
+    plan.add(params + lay.layer(i, P_Q), params + lay.layer(i, P_K), params + lay.layer(i, P_V), ln_a, L.wqkv, t.wqkv_t,
+             3 * inner, D, inner, (int)PACK_CONCAT3);
+    plan.add(params + lay.layer(i, P_O), nullptr, nullptr, nullptr, L.wo, t.wo_t, D, inner, 0, (int)PACK_COPY);
+    plan.add(params + lay.layer(i, P_WI0), params + lay.layer(i, P_WI1), nullptr, ln_f, L.wi, t.wi_t, 2 * F, D, 0,
+             (int)PACK_GEGLU);
+    plan.add(params + lay.layer(i, P_WO), nullptr, nullptr, nullptr, L.wo2, t.wo2_t, D, F, 0, (int)PACK_COPY);
+    plan.launch(stream);
   }
   RP_CHECK_LAUNCH();
   return RP_OK;
@@ -953,8 +997,7 @@ extern "C" RpStatus rp_dbg_dgrad(const void* A, const void* W, int32_t M, int32_
                               stream, RP_K_BWD_DGRAD, 0, nullptr, variant);
     // out1 = sum of the slots (rs = 1, inv_d = 1 turns rowdot_finish into a plain slot sum)
     if (st == RP_OK)
-      hipLaunchKernelGGL(rowdot_finish_kernel, dim3((M + 63) / 64), dim3(64), 0, stream, (const float*)rdp, np, M,
-                         (const float*)ones, 1.f, out1, M);
+      launch_rowdot_finish(rdp, np, M, ones, 1.f, out1, M, stream);
     (void)hipStreamSynchronize(stream);
     (void)hipFree(rdp);
     (void)hipFree(ones);
@@ -963,4 +1006,134 @@ extern "C" RpStatus rp_dbg_dgrad(const void* A, const void* W, int32_t M, int32_
   return launch_gemm(a, K, M, w, K, N, K,
                      EpiRmsBwdResid{(bf16_t*)out0, (bf16_t*)out0 + (size_t)M * N, N, N, (const bf16_t*)aux0, aux1}, stream,
                      RP_K_BWD_DGRAD, 0, nullptr, variant);
+}
+
+// ---- the encoder's pooling head, training row kernels and weight pack / unpack kernels in isolation -------------------------
+// (tests/test_encoder_train_kernels_gpu.py).  Device pointers, the launch functions the trainer and the
+// encoder pass run, arguments checked before anything is launched, no output zeroed first.
+extern "C" RpStatus rp_dbg_train_rows(int32_t mode, const void* a, const void* b, const int32_t* ia, int32_t T, int32_t rows,
+                                      int32_t n, int32_t vocab, int32_t np, int32_t ld, float inv_d, float p, uint32_t seed,
+                                      uint32_t site, void* o0, void* o1, void* o2, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RP_REQUIRE(mode >= 0 && mode <= 5, "mode=%d", mode);
+  RP_REQUIRE(p >= 0.f && p < 1.f, "dropout probability %g", (double)p);
+  RP_REQUIRE(rows >= 1 && n >= 8 && n % 8 == 0, "rows=%d, n=%d", rows, n);
+  const Drop drop = make_drop(p, seed);
+  switch (mode) {
+    case 0:  // embed_kernel<false>
+    case 1:  // embed_train_kernel
+      RP_REQUIRE(ia && a && o0 && o1 && o2, "null argument");
+      RP_REQUIRE(T >= 1 && T <= rows && vocab >= 1 && np >= 1, "T=%d, Tp=%d, vocab=%d, np=%d", T, rows, vocab, np);
+      RP_REQUIRE((mode == 1) == (drop.thresh != 0), "mode %d %s p > 0", mode, mode == 1 ? "needs" : "takes no");
+      launch_embed(ia, (const float*)a, (bf16_t*)o0, (bf16_t*)o1, (float*)o2, np, T, rows, n, vocab, drop, stream);
+      break;
+    case 2:  // mask_dx_kernel
+      RP_REQUIRE(a && b && o0, "null argument");
+      launch_mask_dx((const bf16_t*)a, (const bf16_t*)b, (bf16_t*)o0, rows, n, drop, site, stream);
+      break;
+    case 3:  // qkv_scale_dot_kernel (o0 = dqkv, in place)
+      RP_REQUIRE(a && b && o0 && o1, "null argument");
+      RP_REQUIRE(T >= 0 && T <= rows, "T=%d, rows=%d", T, rows);
+      launch_qkv_scale_dot((bf16_t*)o0, (const bf16_t*)a, (const float*)b, (float*)o1, T, rows, n, inv_d, stream);
+      break;
+    case 4:  // rowdot_finish_kernel (n unused)
+      RP_REQUIRE(a && b && o0, "null argument");
+      RP_REQUIRE(np >= 1 && ld >= rows, "np=%d, ld=%d, rows=%d", np, ld, rows);
+      launch_rowdot_finish((const float*)a, np, ld, (const float*)b, inv_d, (float*)o0, rows, stream);
+      break;
+    default:  // embed_bwd_kernel (rows = T)
+      RP_REQUIRE(ia && a && b && o0, "null argument");
+      RP_REQUIRE(T >= 1 && vocab >= 1, "T=%d, vocab=%d", T, vocab);
+      launch_embed_bwd(ia, T, vocab, (const bf16_t*)a, (const bf16_t*)b, n, (float*)o0, drop, stream);
+      break;
+  }
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_dbg_pool_head(const void* xhi, const void* xlo, int32_t lo8, const float* rs, const int32_t* cu,
+                                     int32_t batch, int32_t T, int32_t D, const float* w, int32_t chunk, int32_t fuse,
+                                     int32_t out_bf16, const float* d_emb, float p, uint32_t seed, void* out, float* partial,
+                                     void* pwork, float* ds, float* dwf, float* d_final_ln, void* dxhi, void* dxlo,
+                                     void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RP_REQUIRE(xhi && xlo && rs && cu && w && out && partial && pwork, "null argument");
+  RP_REQUIRE(batch >= 1 && T >= 1 && D >= 8 && D % 8 == 0 && D <= 4 * 512, "batch=%d, T=%d, D=%d", batch, T, D);
+  RP_REQUIRE(chunk == 32 || chunk == 64 || chunk == 128, "chunk=%d", chunk);
+  RP_REQUIRE(p >= 0.f && p < 1.f, "dropout probability %g", (double)p);
+  const Drop drop = make_drop(p, seed);
+  const bool training_form = chunk == POOL_CHUNK && !fuse && !lo8 && !out_bf16;
+  RP_REQUIRE(!drop.thresh || training_form, "dropout: the training form only (chunk 128, fuse 0, bf16 lo plane, fp32 out)");
+  if (d_emb) {
+    RP_REQUIRE(training_form, "the backward: the training form only (chunk 128, fuse 0, bf16 lo plane, fp32 out)");
+    RP_REQUIRE(ds && dwf && d_final_ln && dxhi && dxlo, "null argument");
+  }
+  {  // every sequence holds at least its EOS: an empty one is outside the pooling head's contract and refused here
+    std::vector<int32_t> h((size_t)batch + 1);
+    RP_HIP(hipMemcpyAsync(h.data(), cu, h.size() * 4, hipMemcpyDeviceToHost, stream));
+    RP_HIP(hipStreamSynchronize(stream));
+    RP_REQUIRE(h[0] == 0 && h[batch] == T, "cu_seqlens runs %d .. %d for T=%d", h[0], h[batch], T);
+    for (int i = 0; i < batch; ++i) RP_REQUIRE(h[i + 1] > h[i], "sequence %d is empty (cu_seqlens %d, %d)", i, h[i], h[i + 1]);
+  }
+  const int n_att = T / ATT_Q + batch;
+  int4* work = nullptr;  // the attention list of the same launch
+  RP_HIP(hipMalloc((void**)&work, (size_t)n_att * sizeof(int4)));
+  launch_worklist(cu, batch, work, n_att, (int4*)pwork, T / chunk + batch, chunk, stream);
+  launch_pool_head((const bf16_t*)xhi, (const bf16_t*)xlo, lo8 != 0, rs, (const int4*)pwork, partial, cu, batch, T, D, chunk, w, out,
+                   out_bf16, fuse, drop, stream);
+  if (d_emb)
+    launch_pool_bwd_head((const bf16_t*)xhi, (const bf16_t*)xlo, rs, (const int4*)pwork, partial, w, cu, batch, T, D, d_emb, ds, dwf,
+                         d_final_ln, (bf16_t*)dxhi, (bf16_t*)dxlo, drop, stream);
+  const hipError_t le = hipGetLastError();
+  (void)hipStreamSynchronize(stream);
+  (void)hipFree(work);
+  if (le != hipSuccess) return fail(RP_E_HIP, "pooling head launch failed: %s", hipGetErrorString(le));
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_dbg_repack(const RpDbgRepackMat* mats, int32_t n_mats, void* stream_) {
+  RP_REQUIRE(mats && n_mats >= 1 && n_mats <= 4, "n_mats=%d", n_mats);
+  RepackPlan plan;
+  for (int k = 0; k < n_mats; ++k) {
+    const RpDbgRepackMat& m = mats[k];
+    RP_REQUIRE(m.s0 && m.dst && m.dst_t, "matrix %d: null argument", k);
+    RP_REQUIRE(m.rows >= 64 && m.cols >= 64 && m.rows % 64 == 0 && m.cols % 64 == 0, "matrix %d: rows=%d, cols=%d", k, m.rows,
+               m.cols);
+    RP_REQUIRE(m.mode == PACK_CONCAT3 || m.mode == PACK_GEGLU || m.mode == PACK_COPY, "matrix %d: mode=%d", k, m.mode);
+    if (m.mode == PACK_CONCAT3) RP_REQUIRE(m.s1 && m.s2 && m.n >= 1 && m.rows == 3 * m.n, "matrix %d: rows=%d, n=%d", k, m.rows, m.n);
+    if (m.mode == PACK_GEGLU) RP_REQUIRE(m.s1, "matrix %d: null argument", k);
+    plan.add(m.s0, m.s1, m.s2, m.colscale, (bf16_t*)m.dst, (bf16_t*)m.dst_t, m.rows, m.cols, m.n, m.mode);
+  }
+  plan.launch((hipStream_t)stream_);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_dbg_bias_table(const float* rel_bias, const int32_t* bucket_of, int32_t H, int32_t ntab, float* tab,
+                                      void* stream_) {
+  RP_REQUIRE(rel_bias && bucket_of && tab && H >= 1 && ntab >= 1, "bad argument");
+  launch_bias_table(rel_bias, bucket_of, H, ntab, tab, (hipStream_t)stream_);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_dbg_unfold(const float* part, int64_t split_stride, int32_t splits, int32_t rows, int32_t C, int32_t mode,
+                                  int32_t n, float* g0, float* g1, float* g2, const float* w0, const float* w1, const float* w2,
+                                  const float* ln, float* dln_part, float* dln, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RP_REQUIRE(part && g0, "null argument");
+  RP_REQUIRE(splits >= 1 && rows >= 1 && C >= 4 && C % 4 == 0, "splits=%d, rows=%d, C=%d", splits, rows, C);
+  RP_REQUIRE(split_stride >= (int64_t)rows * C, "split_stride=%lld < rows * C", (long long)split_stride);
+  RP_REQUIRE(mode == UNFOLD_PLAIN || mode == UNFOLD_QKV || mode == UNFOLD_GEGLU, "mode=%d", mode);
+  if (mode == UNFOLD_QKV) RP_REQUIRE(n >= 1 && rows == 3 * n && g1 && g2 && w0 && w1 && w2, "QKV: rows=%d, n=%d", rows, n);
+  if (mode == UNFOLD_GEGLU) RP_REQUIRE(rows % 64 == 0 && g1 && w0 && w1, "GEGLU: rows=%d", rows);
+  if (mode != UNFOLD_PLAIN) RP_REQUIRE(ln && dln_part && dln, "null argument");
+  UnfoldArgs a{};
+  a.part = part; a.split_stride = (size_t)split_stride; a.splits = splits; a.rows = rows; a.C = C; a.mode = mode; a.n = n;
+  a.g0 = g0; a.g1 = g1; a.g2 = g2; a.w0 = w0; a.w1 = w1; a.w2 = w2; a.ln = ln; a.dln_part = dln_part;
+  RpStatus st = run_unfold(a, stream);
+  if (st) return st;
+  if (mode != UNFOLD_PLAIN) launch_colsum(dln_part, (rows + 31) / 32, C, dln, stream);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
 }

@@ -1348,7 +1348,7 @@ __global__ __launch_bounds__(256) void hidden_head_bwd_kernel(const bf16_t* __re
 }
 
 // ------------------------------------------------------------------------------------------
-// embedding backward:  d table[v] = sum over the tokens t with ids[t] == v, in token order, of dx[t]  (no float atomics).
+// embedding backward:  d table[v] = sum over the tokens t with clamp(ids[t]) == v, in token order, of dx[t]  (no float atomics).
 // grid = (vocab, ceil(D / 256)); the workgroup scans the pass's ids 256 at a time, ballots the matches and walks the set
 // bits in order (uniform control flow).
 // ------------------------------------------------------------------------------------------
@@ -1361,8 +1361,9 @@ static __global__ __launch_bounds__(256) void embed_bwd_kernel(const int32_t* __
   float acc = 0.f;
   for (int base = 0; base < T; base += 256) {
     const int t = base + threadIdx.x;
-    int id = (t < T) ? ids[t] : -1;
-    if (id >= 0) id = min(max(id, 0), vocab - 1);  // as the forward's gather clamps
+    // clamped exactly as the forward's gather clamps (a negative id read table row 0 there, so its gradient belongs to row 0);
+    // -1 is the "past T" sentinel alone, as in the decoder's bwd_embed_kernel
+    const int id = (t < T) ? min(max(ids[t], 0), vocab - 1) : -1;
     const unsigned long long m = __ballot(id == v);
     if ((threadIdx.x & 63) == 0) masks[wave] = m;
     __syncthreads();
