@@ -26,8 +26,8 @@ import torch
 from . import _lib
 from .encoder import HipT5Encoder, _require_gpu
 from .generation import (BeamBooks, BeamBooksPool, BeamSearchOutput, BeamSearchPool, SamplePool, SampleState, SamplingParams,
-                         beam_search, beam_search_batch, beam_search_batch_device, check_sampling, greedy_search,
-                         greedy_search_batch, sample_search_batch)
+                         _check_count, _check_prompts, _check_room, _prompt_tokens, beam_search, beam_search_batch,
+                         beam_search_batch_device, check_sampling, greedy_search, greedy_search_batch, sample_search_batch)
 
 IGNORE_INDEX = -100  # the label HF's CrossEntropyLoss(ignore_index=-100) skips
 # Dropout sites of the training step (include/reprover_hip.h RP_DROP_SITE_*; ``rp_dbg_dropout_mask`` reads a site's mask).
@@ -375,62 +375,82 @@ class HipT5Decoder:
         columns ``0..t`` are read (``sample_search_batch`` passes one table for the whole search).  With ``pos`` (one
         position per active state, in place of ``t``) the call is ``rp_decoder_batch_step_pos``: state ``active[a]`` at
         ``pos[a]``, columns ``0..pos[a]`` of its rows read (``beam_search_batch`` over prompts of different lengths)."""
-        cu, n, nb, max_len = self._many
-        act = np.ascontiguousarray(active, dtype=np.int32)
-        rows, T = ancestry.shape
+        T = ancestry.shape[1]
         if pos is not None and t is not None:
             raise _lib.HipLibraryError("step_many: t= and pos= exclude each other")
         if t is not None and not 0 <= t < T:
             raise _lib.HipLibraryError(f"step_many: t={t} outside the {T} columns of the ancestry table")
-        if rows != len(act) * nb or tokens.numel() != rows:
-            raise _lib.HipLibraryError(f"step_many: {rows} ancestry rows, {tokens.numel()} tokens for {len(act)} states "
+        return self._step("step_many", active, tokens, ancestry, out, t=t, pos=pos)
+
+    def _step(self, what: str, active, tokens: torch.Tensor, ancestry: torch.Tensor, out: Optional[torch.Tensor],
+              t: Optional[int] = None, pos=None, src_len=None) -> torch.Tensor:
+        """The one caller of the decoder step's three entries.  ``src_len`` given: the slot pool's
+        (``rp_decoder_pool_step``, ``active`` its slots at ``pos``).  Else ``start_many``'s states: at ``pos`` where it is
+        given (``rp_decoder_batch_step_pos``), otherwise all at ``t``, None standing for the table's last column
+        (``rp_decoder_batch_step``)."""
+        pool = src_len is not None
+        nb = self._pool[1] if pool else self._many[2]
+        act = np.ascontiguousarray(active, dtype=np.int32)
+        by_state = [np.ascontiguousarray(x, dtype=np.int32) for x in (pos, src_len) if x is not None]
+        rows, T = ancestry.shape
+        if rows != len(act) * nb or tokens.numel() != rows or any(len(x) != len(act) for x in by_state):
+            raise _lib.HipLibraryError(f"{what}: {rows} ancestry rows, {tokens.numel()} tokens, "
+                                       f"{[len(x) for x in by_state]} positions / source lengths for {len(act)} states "
                                        f"of {nb} beams")
         tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
         anc = ancestry.to(device=self.device, dtype=torch.int32).contiguous()
         if out is None:
             out = torch.empty((rows, self.V), dtype=torch.float32, device=self.device)
-        if pos is not None:
-            p = np.ascontiguousarray(pos, dtype=np.int32)
-            if len(p) != len(act):
-                raise _lib.HipLibraryError(f"step_many: {len(p)} positions for {len(act)} states")
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.rp_decoder_batch_step_pos(self._handle, _pc(cu), n, _pc(act), len(act), tok.data_ptr(),
-                                                               anc.data_ptr(), T, nb, _pc(p), max_len, out.data_ptr(),
-                                                               self._ws.data_ptr(), self._ws.numel(),
-                                                               _lib.current_stream()), "rp_decoder_batch_step_pos")
-            return out
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_decoder_batch_step(self._handle, cu.ctypes.data_as(C.c_void_p), n,
-                                                       act.ctypes.data_as(C.c_void_p), len(act), tok.data_ptr(),
-                                                       anc.data_ptr(), T, nb, T - 1 if t is None else t, max_len,
-                                                       out.data_ptr(),
-                                                       self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
-                       "rp_decoder_batch_step")
+            if pool:
+                p, sl = by_state
+                _lib.check(self._lib.rp_decoder_pool_step(self._handle, *self._pool, _pc(act), _pc(p), _pc(sl), len(act),
+                                                          tok.data_ptr(), anc.data_ptr(), T, out.data_ptr(),
+                                                          self._pool_ws.data_ptr(), self._pool_ws.numel(),
+                                                          _lib.current_stream()), "rp_decoder_pool_step")
+                return out
+            cu, n, _, max_len = self._many
+            entry, where = ("rp_decoder_batch_step", T - 1 if t is None else t) if pos is None else (
+                "rp_decoder_batch_step_pos", _pc(by_state[0]))
+            _lib.check(getattr(self._lib, entry)(self._handle, _pc(cu), n, _pc(act), len(act), tok.data_ptr(),
+                                                 anc.data_ptr(), T, nb, where, max_len, out.data_ptr(),
+                                                 self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()), entry)
         return out
 
-    def _prefill_args(self, rows, nb: int):
-        """(prompt_cu host int32, device tokens, device ancestry vector p -> p * nb, its length) of a prefill call."""
+    def _prefill(self, what: str, states, rows, src_len=None) -> None:
+        """The one caller of the two prefill entries: the prompt rows ``rows[j]`` (tokens of positions ``0 .. R_j - 1``)
+        of ``start_many``'s state ``states[j]`` (``rp_decoder_batch_prefill``) or, with ``src_len``, of the pool's slot
+        ``states[j]`` (``rp_decoder_pool_prefill``).  Cache row ``p * nb`` of every layer is written, nothing else."""
+        pool = src_len is not None
+        nb = self._pool[1] if pool else self._many[2]
+        st = np.ascontiguousarray(states, dtype=np.int32)
+        ln = np.ascontiguousarray(src_len, dtype=np.int32) if pool else None
+        if len(st) != len(rows) or not len(st) or (pool and len(ln) != len(st)):
+            raise _lib.HipLibraryError(f"{what}: {len(rows)} prompts" + (f", {len(ln)} source lengths" if pool else "")
+                                       + f" for {len(st)} " + ("slots" if pool else "states"))
         rows = [np.asarray(r, dtype=np.int32).reshape(-1) for r in rows]
-        cu = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+        pcu = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
         tok = torch.from_numpy(np.concatenate(rows).astype(np.int32)).to(self.device)
         longest = int(max(len(r) for r in rows))
-        anc = (torch.arange(longest, dtype=torch.int32) * int(nb)).to(self.device)
-        return cu, tok, anc, longest
+        anc = (torch.arange(longest, dtype=torch.int32) * int(nb)).to(self.device)  # prompt position p -> cache row p * nb
+        with torch.cuda.device(self.device):
+            if pool:
+                _lib.check(self._lib.rp_decoder_pool_prefill(self._handle, *self._pool, _pc(st), _pc(ln), _pc(pcu), len(st),
+                                                             tok.data_ptr(), anc.data_ptr(), longest,
+                                                             self._pool_ws.data_ptr(), self._pool_ws.numel(),
+                                                             _lib.current_stream()), "rp_decoder_pool_prefill")
+                return
+            cu, n, _, max_len = self._many
+            _lib.check(self._lib.rp_decoder_batch_prefill(self._handle, _pc(cu), n, _pc(st), _pc(pcu), len(st),
+                                                          tok.data_ptr(), anc.data_ptr(), longest, nb, max_len,
+                                                          self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
+                       "rp_decoder_batch_prefill")
 
     def prefill_many(self, states, rows) -> None:
         """The prompt rows of ``states`` (distinct indices into ``start_many``'s sources) in one pass
         (``rp_decoder_batch_prefill``, ``beam_search_batch``'s ``prefill_many``): ``rows[j]`` are the tokens of positions
         ``0 .. R_j - 1`` of state ``states[j]``; cache row ``p * nb`` of every layer is written, nothing else."""
-        cu, n, nb, max_len = self._many
-        st = np.ascontiguousarray(states, dtype=np.int32)
-        if len(st) != len(rows) or not len(st):
-            raise _lib.HipLibraryError(f"prefill_many: {len(rows)} prompts for {len(st)} states")
-        pcu, tok, anc, longest = self._prefill_args(rows, nb)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_decoder_batch_prefill(self._handle, _pc(cu), n, _pc(st), _pc(pcu), len(st),
-                                                          tok.data_ptr(), anc.data_ptr(), longest, nb, max_len,
-                                                          self._ws.data_ptr(), self._ws.numel(), _lib.current_stream()),
-                       "rp_decoder_batch_prefill")
+        self._prefill("prefill_many", states, rows)
 
     # -- the slot pool (rp_decoder_pool_*): states join between steps, each slot at its own position ---------------------
     def pool_open(self, n_slots: int, nb: int, max_len: int, src_cap: int) -> None:
@@ -460,38 +480,14 @@ class HipT5Decoder:
     def pool_prefill(self, slots, src_len, rows) -> None:
         """``prefill_many`` for the slot pool (``rp_decoder_pool_prefill``, ``BeamSearchPool``'s ``prefill``): the prompt
         rows ``rows[j]`` of slot ``slots[j]``, admitted with a source of ``src_len[j]`` tokens."""
-        nb = self._pool[1]
-        sl, ln = (np.ascontiguousarray(x, dtype=np.int32) for x in (slots, src_len))
-        if not len(sl) == len(ln) == len(rows) or not len(sl):
-            raise _lib.HipLibraryError(f"pool_prefill: {len(rows)} prompts, {len(ln)} source lengths for {len(sl)} slots")
-        pcu, tok, anc, longest = self._prefill_args(rows, nb)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_decoder_pool_prefill(self._handle, *self._pool, _pc(sl), _pc(ln), _pc(pcu), len(sl),
-                                                         tok.data_ptr(), anc.data_ptr(), longest,
-                                                         self._pool_ws.data_ptr(), self._pool_ws.numel(),
-                                                         _lib.current_stream()), "rp_decoder_pool_prefill")
+        self._prefill("pool_prefill", slots, rows, src_len)
 
     def pool_step(self, active, pos, src_len, tokens: torch.Tensor, ancestry: torch.Tensor,
                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """log-probs [n_active * nb, V] of one step for the slots ``active`` (distinct), slot ``active[a]`` at position
         ``pos[a]`` over a source of ``src_len[a]`` tokens; row ``a * nb + b`` is its beam ``b``, of whose ancestry row
         columns ``0..pos[a]`` are read (``BeamSearchPool``'s ``step``)."""
-        nb = self._pool[1]
-        act, p, sl = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos, src_len))
-        rows, T = ancestry.shape
-        if not len(act) == len(p) == len(sl) or rows != len(act) * nb or tokens.numel() != rows:
-            raise _lib.HipLibraryError(f"pool_step: {rows} ancestry rows, {tokens.numel()} tokens, {len(p)} positions, "
-                                       f"{len(sl)} source lengths for {len(act)} slots of {nb} beams")
-        tok = tokens.to(device=self.device, dtype=torch.int32).contiguous()
-        anc = ancestry.to(device=self.device, dtype=torch.int32).contiguous()
-        if out is None:
-            out = torch.empty((rows, self.V), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_decoder_pool_step(self._handle, *self._pool, _pc(act), _pc(p), _pc(sl), len(act),
-                                                      tok.data_ptr(), anc.data_ptr(), T, out.data_ptr(),
-                                                      self._pool_ws.data_ptr(), self._pool_ws.numel(),
-                                                      _lib.current_stream()), "rp_decoder_pool_step")
-        return out
+        return self._step("pool_step", active, tokens, ancestry, out, pos=pos, src_len=src_len)
 
     def sample_step(self, log_probs: torch.Tensor, active, t: int, state: SampleState, temperature: float = 1.0,
                     top_k: int = 0, top_p: float = 1.0, eos_token_id: int = 1, pad_token_id: int = 0) -> None:
@@ -499,31 +495,30 @@ class HipT5Decoder:
         (``rp_sample_step``; ``sample_search_batch``'s ``sample_step``).  Nothing is read back.  With ``state.params``
         set, every row takes its parameters from its own block of that table (``rp_sample_step_rows``) and the three
         arguments are not looked at."""
+        self._sample("sample_step", log_probs, active, int(t), state, temperature, top_k, top_p, eos_token_id, pad_token_id)
+
+    def _sample(self, what: str, log_probs: torch.Tensor, active, where, state: SampleState, temperature: float,
+                top_k: int, top_p: float, eos_token_id: int, pad_token_id: int) -> None:
+        """The one caller of the sampler's four entries: ``where`` an int, every state at that position
+        (``rp_sample_step``), or a position per slot (``rp_sample_pool_step``); with ``state.params`` set the ``_rows``
+        entry of either, which takes the table in place of the three scalars."""
+        pool = not isinstance(where, int)
+        entry = ("rp_sample_pool_step" if pool else "rp_sample_step") + ("" if state.params is None else "_rows")
         act = np.ascontiguousarray(active, dtype=np.int32)
-        n, nb, max_len = state.seq.shape
+        p = np.ascontiguousarray(where, dtype=np.int32) if pool else None
+        n, nb, max_len = self._sample_books(state, entry)
         rows, V = log_probs.shape
-        if rows != len(act) * nb or state.tokens.numel() < rows:
-            raise _lib.HipLibraryError(f"sample_step: {rows} rows for {len(act)} states of {nb} samples")
-        for x in (log_probs, state.seeds, state.seq, state.cum_logprob, state.n_generated, state.finished, state.tokens):
-            assert x.is_cuda and x.is_contiguous(), "rp_sample_step takes contiguous device tensors"
-        assert log_probs.dtype == torch.float32
-        if state.params is not None:
-            table = self._sample_table(state, "rp_sample_step_rows")
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.rp_sample_step_rows(log_probs.data_ptr(), V, _pc(act), len(act), n, nb,
-                                                         state.seeds.data_ptr(), t, max_len, table, eos_token_id,
-                                                         pad_token_id, state.seq.data_ptr(), state.tokens.data_ptr(),
-                                                         state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
-                                                         state.finished.data_ptr(), _lib.current_stream()),
-                           "rp_sample_step_rows")
-            return
+        if rows != len(act) * nb or state.tokens.numel() < rows or (pool and len(p) != len(act)):
+            raise _lib.HipLibraryError(f"{what}: {rows} rows" + (f", {len(p)} positions" if pool else "")
+                                       + f" for {len(act)} states of {nb} samples")
+        assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dtype == torch.float32
+        head = (_pc(p), len(act), n, nb, state.seeds.data_ptr()) if pool else (len(act), n, nb, state.seeds.data_ptr(), where)
+        how = (temperature, top_k, top_p) if state.params is None else (self._sample_table(state, entry),)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_sample_step(log_probs.data_ptr(), V, act.ctypes.data_as(C.c_void_p), len(act), n, nb,
-                                                state.seeds.data_ptr(), t, max_len, temperature, top_k, top_p,
-                                                eos_token_id, pad_token_id, state.seq.data_ptr(), state.tokens.data_ptr(),
-                                                state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
-                                                state.finished.data_ptr(), _lib.current_stream()),
-                       "rp_sample_step")
+            _lib.check(getattr(self._lib, entry)(log_probs.data_ptr(), V, _pc(act), *head, max_len, *how, eos_token_id,
+                                                 pad_token_id, state.seq.data_ptr(), state.tokens.data_ptr(),
+                                                 state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
+                                                 state.finished.data_ptr(), _lib.current_stream()), entry)
 
     def beam_books(self, n: int, nb: int, max_len: int, eos_token_id: int = 1,
                    decoder_start_token_id: int = 0) -> BeamBooks:
@@ -543,18 +538,37 @@ class HipT5Decoder:
                      parents: torch.Tensor, fin_div: float, run_div: float, eos_token_id: int = 1) -> None:
         """The books' update from one step's selected triples ``[n_active, 2 nb]``, on the device (``rp_beam_advance``;
         ``beam_search_batch_device``'s ``advance``).  Nothing is read back."""
+        self._advance("beam_advance", books, active, int(t), scores, tokens, parents, float(fin_div), float(run_div),
+                      eos_token_id)
+
+    def _advance(self, what: str, books: BeamBooks, active, where, scores: torch.Tensor, tokens: torch.Tensor,
+                 parents: torch.Tensor, fin_div, run_div, eos_token_id: int) -> None:
+        """The one caller of the books' two update entries: ``where`` an int and the divisors floats
+        (``rp_beam_advance``: every state at that position), or a position and a pair of divisors per slot
+        (``rp_beam_pool_advance``)."""
+        pool = not isinstance(where, int)
+        entry = "rp_beam_pool_advance" if pool else "rp_beam_advance"
         act = np.ascontiguousarray(active, dtype=np.int32)
         want = (len(act), 2 * books.nb)
         for x, dt in ((scores, torch.float32), (tokens, torch.int32), (parents, torch.int32)):
-            assert x.is_cuda and x.is_contiguous() and x.dtype == dt, "rp_beam_advance takes contiguous device tensors"
+            assert x.is_cuda and x.is_contiguous() and x.dtype == dt, f"{entry} takes contiguous device tensors"
             if tuple(x.shape) != want:
-                raise _lib.HipLibraryError(f"beam_advance: triples of shape {tuple(x.shape)} for {want}")
+                raise _lib.HipLibraryError(f"{what}: triples of shape {tuple(x.shape)} for {want}")
         assert books.block.is_cuda
+        if pool:
+            p = np.ascontiguousarray(where, dtype=np.int32)
+            fd, rd = (np.ascontiguousarray(x, dtype=np.float32) for x in (fin_div, run_div))
+            if not len(p) == len(fd) == len(rd) == len(act):
+                raise _lib.HipLibraryError(f"{what}: {len(p)} positions, {len(fd)} / {len(rd)} divisors for "
+                                           f"{len(act)} slots")
+            where, fin_div, run_div = (_pc(p), len(act)), _pc(fd), _pc(rd)
+        else:
+            where = (len(act), where)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_beam_advance(books.block.data_ptr(), books.nbytes, books.n, books.nb, books.max_len,
-                                                 act.ctypes.data_as(C.c_void_p), len(act), t, scores.data_ptr(),
-                                                 tokens.data_ptr(), parents.data_ptr(), fin_div, run_div, eos_token_id,
-                                                 _lib.current_stream()), "rp_beam_advance")
+            _lib.check(getattr(self._lib, entry)(books.block.data_ptr(), books.nbytes, books.n, books.nb, books.max_len,
+                                                 _pc(act), *where, scores.data_ptr(), tokens.data_ptr(),
+                                                 parents.data_ptr(), fin_div, run_div, eos_token_id,
+                                                 _lib.current_stream()), entry)
 
     # -- the slot pool's books: a position per slot (``generation.BeamBooksPool``'s callables) ---------------------------
     def beam_books_admit(self, books: BeamBooks, states, eos_token_id: int = 1, decoder_start_token_id: int = 0) -> None:
@@ -570,22 +584,7 @@ class HipT5Decoder:
                           parents: torch.Tensor, fin_div, run_div, eos_token_id: int = 1) -> None:
         """``beam_advance`` with slot ``active[a]`` at its own position ``pos[a]`` and its own divisors
         (``rp_beam_pool_advance``).  Nothing is read back."""
-        act, p = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos))
-        fd, rd = (np.ascontiguousarray(x, dtype=np.float32) for x in (fin_div, run_div))
-        want = (len(act), 2 * books.nb)
-        for x, dt in ((scores, torch.float32), (tokens, torch.int32), (parents, torch.int32)):
-            assert x.is_cuda and x.is_contiguous() and x.dtype == dt, "rp_beam_pool_advance takes contiguous device tensors"
-            if tuple(x.shape) != want:
-                raise _lib.HipLibraryError(f"beam_pool_advance: triples of shape {tuple(x.shape)} for {want}")
-        if not len(p) == len(fd) == len(rd) == len(act):
-            raise _lib.HipLibraryError(f"beam_pool_advance: {len(p)} positions, {len(fd)} / {len(rd)} divisors for "
-                                       f"{len(act)} slots")
-        assert books.block.is_cuda
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_beam_pool_advance(books.block.data_ptr(), books.nbytes, books.n, books.nb,
-                                                      books.max_len, _pc(act), _pc(p), len(act), scores.data_ptr(),
-                                                      tokens.data_ptr(), parents.data_ptr(), _pc(fd), _pc(rd),
-                                                      eos_token_id, _lib.current_stream()), "rp_beam_pool_advance")
+        self._advance("beam_pool_advance", books, active, list(pos), scores, tokens, parents, fin_div, run_div, eos_token_id)
 
     def beam_books_rows(self, books: BeamBooks, active, pos) -> None:
         """The by-row inputs of the slots ``active`` (in that order) from their by-state parts (``rp_beam_books_rows``)."""
@@ -622,30 +621,8 @@ class HipT5Decoder:
         """``sample_step`` with slot ``active[a]`` at its own position ``pos[a]`` (``rp_sample_pool_step``;
         ``SamplePool``'s ``sample_step``).  Nothing is read back.  With ``state.params`` set:
         ``rp_sample_pool_step_rows``, as in ``sample_step``."""
-        act, p = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos))
-        n, nb, max_len = self._sample_books(state, "rp_sample_pool_step")
-        rows, V = log_probs.shape
-        if len(p) != len(act) or rows != len(act) * nb or state.tokens.numel() < rows:
-            raise _lib.HipLibraryError(f"sample_pool_step: {rows} rows, {len(p)} positions for {len(act)} slots of {nb} "
-                                       "samples")
-        assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dtype == torch.float32
-        if state.params is not None:
-            table = self._sample_table(state, "rp_sample_pool_step_rows")
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.rp_sample_pool_step_rows(log_probs.data_ptr(), V, _pc(act), _pc(p), len(act), n, nb,
-                                                              state.seeds.data_ptr(), max_len, table, eos_token_id,
-                                                              pad_token_id, state.seq.data_ptr(), state.tokens.data_ptr(),
-                                                              state.cum_logprob.data_ptr(), state.n_generated.data_ptr(),
-                                                              state.finished.data_ptr(), _lib.current_stream()),
-                           "rp_sample_pool_step_rows")
-            return
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.rp_sample_pool_step(log_probs.data_ptr(), V, _pc(act), _pc(p), len(act), n, nb,
-                                                     state.seeds.data_ptr(), max_len, temperature, top_k, top_p,
-                                                     eos_token_id, pad_token_id, state.seq.data_ptr(),
-                                                     state.tokens.data_ptr(), state.cum_logprob.data_ptr(),
-                                                     state.n_generated.data_ptr(), state.finished.data_ptr(),
-                                                     _lib.current_stream()), "rp_sample_pool_step")
+        self._sample("sample_pool_step", log_probs, active, list(pos), state, temperature, top_k, top_p, eos_token_id,
+                     pad_token_id)
 
     def sample_books_admit(self, state: SampleState, states, seeds, decoder_start_token_id: int = 0,
                            pad_token_id: int = 0, n_live=None, params: Optional[torch.Tensor] = None) -> None:
@@ -839,24 +816,23 @@ class HipT5Generator:
             out[b, :n] = lp[int(tgt_cu[b]) : int(tgt_cu[b]) + n]
         return out
 
+    @property
+    def _eos(self) -> int:
+        return self.cfg.get("eos_token_id", 1)
+
+    @property
+    def _start(self) -> int:
+        return self.cfg.get("decoder_start_token_id", 0)
+
     @staticmethod
     def _prefix(prefix) -> Optional[List[int]]:
         """A prefix (token ids after the start token; None or empty: none) as a list, or None."""
-        if prefix is None:
-            return None
-        return [int(x) for x in np.asarray(prefix).reshape(-1).tolist()] or None
+        return _prompt_tokens(prefix) or None
 
-    def _check_prefixes(self, prefixes, n: int, max_length: int):
+    @staticmethod
+    def _check_prefixes(prefixes, n: int, max_length: int):
         """``prefixes`` (None, or one entry or None per source) as lists; None when no source has one."""
-        if prefixes is None:
-            return None
-        prefixes = [self._prefix(p) for p in prefixes]
-        if len(prefixes) != n:
-            raise ValueError(f"{len(prefixes)} prefixes for {n} sources")
-        for p in prefixes:
-            if p and max_length <= 1 + len(p):
-                raise ValueError(f"max_length={max_length} leaves no room after the decoder prompt of 1 + {len(p)} tokens")
-        return prefixes if any(prefixes) else None
+        return _check_prompts(prefixes, n, max_length, "prefixes", "sources")
 
     def greedy(self, ids: np.ndarray, max_length: int, prefix=None) -> BeamSearchOutput:
         """``generate(input_ids, num_beams=1, max_length)``: HF's greedy search (argmax, ties to the lowest id), not a
@@ -865,8 +841,8 @@ class HipT5Generator:
             return self.greedy_many([ids], max_length, prefixes=[prefix])[0]
         enc = self.encode_hidden(ids)
         self.decoder.start(enc, 1, max_length)
-        return greedy_search(self.decoder.step, max_length, eos_token_id=self.cfg.get("eos_token_id", 1),
-                             decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device)
+        return greedy_search(self.decoder.step, max_length, eos_token_id=self._eos,
+                             decoder_start_token_id=self._start, device=self.device)
 
     def generate(self, ids: np.ndarray, num_beams: int, max_length: int, length_penalty: float = 1.0,
                  trace: Optional[list] = None, sync_every: Optional[int] = None, prefix=None) -> BeamSearchOutput:
@@ -891,8 +867,8 @@ class HipT5Generator:
         enc = self.encode_hidden(ids)
         self.decoder.start(enc, num_beams, max_length)
         return beam_search(self.decoder.step, num_beams, max_length, length_penalty,
-                           eos_token_id=self.cfg.get("eos_token_id", 1),
-                           decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),
+                           eos_token_id=self._eos,
+                           decoder_start_token_id=self._start,
                            select=self.decoder.select, device=self.device, trace=trace)
 
     def _start_many(self, sources, num_beams: int, max_length: int) -> int:
@@ -911,8 +887,8 @@ class HipT5Generator:
         prefixes = self._check_prefixes(prefixes, len(sources), max_length)
         n = self._start_many(sources, 1, max_length)
         kw = {} if prefixes is None else dict(prompts=prefixes, prefill_many=self.decoder.prefill_many)
-        return greedy_search_batch(self.decoder.step_many, n, max_length, eos_token_id=self.cfg.get("eos_token_id", 1),
-                                   decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), device=self.device,
+        return greedy_search_batch(self.decoder.step_many, n, max_length, eos_token_id=self._eos,
+                                   decoder_start_token_id=self._start, device=self.device,
                                    **kw)
 
     def generate_many(self, sources, num_beams: int, max_length: int, length_penalty: float = 1.0,
@@ -939,22 +915,20 @@ class HipT5Generator:
         if sync_every is not None:
             if traces is not None:
                 raise ValueError("traces= needs the host books: it cannot be combined with sync_every")
-            if int(sync_every) != sync_every or sync_every < 1:
-                raise ValueError(f"sync_every={sync_every} must be an integer >= 1 (or None)")
-            if max_length <= 1:
-                raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+            sync_every = _check_count("sync_every", sync_every, " (or None)")
+            _check_room(max_length)
         n = self._start_many(sources, num_beams, max_length)
         if sync_every is not None:
             dec = self.decoder
             return beam_search_batch_device(
                 lambda active, tokens, ancestry, t: dec.step_many(active, tokens, ancestry, t=t), dec.select_many,
-                dec.beam_advance, n, num_beams, max_length, length_penalty, eos_token_id=self.cfg.get("eos_token_id", 1),
-                decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), sync_every=int(sync_every),
+                dec.beam_advance, n, num_beams, max_length, length_penalty, eos_token_id=self._eos,
+                decoder_start_token_id=self._start, sync_every=sync_every,
                 device=self.device, init=dec.beam_books)
         kw = {} if prefixes is None else dict(prompts=prefixes, prefill_many=self.decoder.prefill_many)
         return beam_search_batch(self.decoder.step_many, n, num_beams, max_length, length_penalty,
-                                 eos_token_id=self.cfg.get("eos_token_id", 1),
-                                 decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0),
+                                 eos_token_id=self._eos,
+                                 decoder_start_token_id=self._start,
                                  select_many=self.decoder.select_many, device=self.device, traces=traces, **kw)
 
     def generate_stream(self, num_beams: int, max_length: int, length_penalty: float = 1.0,
@@ -970,11 +944,8 @@ class HipT5Generator:
         stop flags are read every ``sync_every`` steps.  The same outputs; with ``sync_every = K > 1`` a result is
         delivered, and its slot taken again, up to ``K - 1`` steps after its state stopped."""
         if sync_every is not None:
-            if int(sync_every) != sync_every or sync_every < 1:
-                raise ValueError(f"sync_every={sync_every} must be an integer >= 1 (or None)")
-            if max_length <= 1:
-                raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
-            sync_every = int(sync_every)
+            sync_every = _check_count("sync_every", sync_every, " (or None)")
+            _check_room(max_length)
         return GenerateStream(self, num_beams, max_length, length_penalty,
                               self.decoder.max_states(num_beams) if n_slots is None else n_slots, src_cap, sync_every)
 
@@ -1021,13 +992,13 @@ class HipT5Generator:
             raise ValueError(f"sample_many takes 1..{self.decoder.max_states(num_samples)} sources at "
                              f"{num_samples} samples, got {len(sources)}")
         n = self._start_many(sources, num_samples, max_length)
-        eos = self.cfg.get("eos_token_id", 1)
+        eos = self._eos
         dec = self.decoder
         return sample_search_batch(
             lambda active, tokens, ancestry, t: dec.step_many(active, tokens, ancestry, t=t),
             lambda lp, active, t, state: dec.sample_step(lp, active, t, state, temperature, int(top_k), top_p, eos, 0),
             n, num_samples, max_length, seeds, length_penalty, eos_token_id=eos,
-            decoder_start_token_id=self.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
+            decoder_start_token_id=self._start, pad_token_id=0, sync_every=sync_every,
             device=self.device, params=table)
 
     def sample_stream(self, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
@@ -1049,12 +1020,11 @@ class HipT5Generator:
         check_sampling(temperature, top_k, top_p)
         if num_samples < 1 or max_length <= 1:
             raise ValueError(f"num_samples={num_samples} (>= 1), max_length={max_length} (>= 2)")
-        if int(sync_every) != sync_every or sync_every < 1:
-            raise ValueError(f"sync_every={sync_every} must be an integer >= 1")
-        if n_slots is not None and (int(n_slots) != n_slots or n_slots < 1):
-            raise ValueError(f"n_slots={n_slots} must be an integer >= 1 (or None)")
+        sync_every = _check_count("sync_every", sync_every)
+        if n_slots is not None:
+            _check_count("n_slots", n_slots, " (or None)")
         return SampleStream(self, num_samples, max_length, temperature, int(top_k), top_p, length_penalty,
-                            self.decoder.max_states(num_samples) if n_slots is None else n_slots, src_cap, int(sync_every),
+                            self.decoder.max_states(num_samples) if n_slots is None else n_slots, src_cap, sync_every,
                             bool(per_request))
 
 
@@ -1069,19 +1039,15 @@ class GenerateStream:
     def __init__(self, generator: HipT5Generator, num_beams: int, max_length: int, length_penalty: float, n_slots: int,
                  src_cap: int, sync_every: Optional[int] = None):
         dec = self._open(generator, n_slots, num_beams, max_length, src_cap)
-        cfg = generator.cfg
+        kw = dict(eos_token_id=generator._eos, decoder_start_token_id=generator._start, select_many=dec.select_many,
+                  device=generator.device)
         if sync_every is not None:
             self.pool = BeamBooksPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
-                                      eos_token_id=cfg.get("eos_token_id", 1),
-                                      decoder_start_token_id=cfg.get("decoder_start_token_id", 0),
-                                      select_many=dec.select_many, device=generator.device, sync_every=sync_every,
-                                      books_admit=dec.beam_books_admit, advance=dec.beam_pool_advance,
-                                      rows=dec.beam_books_rows)
-            return
-        self.pool = BeamSearchPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
-                                   eos_token_id=cfg.get("eos_token_id", 1),
-                                   decoder_start_token_id=cfg.get("decoder_start_token_id", 0),
-                                   select_many=dec.select_many, device=generator.device, prefill=self._prefill)
+                                      sync_every=sync_every, books_admit=dec.beam_books_admit,
+                                      advance=dec.beam_pool_advance, rows=dec.beam_books_rows, **kw)
+        else:
+            self.pool = BeamSearchPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
+                                       prefill=self._prefill, **kw)
 
     def _open(self, generator: HipT5Generator, n_slots: int, nb: int, max_length: int, src_cap: int) -> HipT5Decoder:
         """Take the decoder's slot pool (beam and sample streams alike: whoever held it is retired)."""
@@ -1156,13 +1122,13 @@ class SampleStream(GenerateStream):
                  top_p: float, length_penalty: float, n_slots: int, src_cap: int, sync_every: int,
                  per_request: bool = False):
         dec = self._open(generator, n_slots, num_samples, max_length, src_cap)
-        eos = generator.cfg.get("eos_token_id", 1)
+        eos = generator._eos
         self.pool = SamplePool(
             self._admit, self._step,
             lambda lp, active, pos, state: self._mine().sample_pool_step(lp, active, pos, state, temperature, top_k, top_p,
                                                                          eos, 0),
             n_slots, num_samples, max_length, length_penalty,
-            decoder_start_token_id=generator.cfg.get("decoder_start_token_id", 0), pad_token_id=0, sync_every=sync_every,
+            decoder_start_token_id=generator._start, pad_token_id=0, sync_every=sync_every,
             device=generator.device, books_admit=dec.sample_books_admit, rows=dec.sample_books_rows,
             **(dict(per_request=True, params=SamplingParams(temperature, top_k, top_p)) if per_request else {}))
         self.num_samples, self.per_request = int(num_samples), bool(per_request)

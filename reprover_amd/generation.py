@@ -20,36 +20,40 @@ The model enters through two callables:
 Host synchronisation: the ``2 nb`` selected triples are read back once per step (``.cpu()``) because the finished-beam
 bookkeeping below runs on the host.  At 64 beams that is one ~1.5 KB copy and one stream sync per step.
 
-There is one loop per search kind, over 1..n sources (``beam_search_batch``, ``greedy_search_batch``,
-``sample_search_batch``); ``beam_search``, ``greedy_search`` and ``sample_search`` wrap their callables into its ``_many``
-protocol and run it with one source.
+The drivers, by where the beam books live and whether sources may join a running search:
 
-Sampling (``sample_search_batch``) keeps its whole state on the device and reads nothing back per step: rows never
-reorder, so the ancestry table is the identity, and the finished flags are read once every ``sync_every`` positions.
+- Lockstep, books on the host: ``beam_search_batch`` (one ``_BeamState`` per source) and ``greedy_search_batch``, over
+  1..n sources; ``beam_search`` and ``greedy_search`` wrap their callables into the ``_many`` protocol and run them
+  with one source.  A decoder prompt (HF's ``decoder_input_ids``: tokens after the start token that every returned
+  sequence begins with) is ``prompt=`` / ``prompts=`` here and in ``BeamSearchPool.submit``: a state starts at
+  ``cur_len = prompt_len = P + 1`` with an ancestry that names one cache row per prompt position (beam 0's, ``p * nb``),
+  written before its first step by a ``prefill`` callable (the engine's one-pass ``rp_decoder_batch_prefill``) or, without
+  one, through ordinary steps (``prefill_by_steps``); ``_prefill_prompts`` is that dispatch.  With any prompt the loops
+  hand ``step_many`` a position per state (``pos=``).
+- Lockstep, books on the device: ``beam_search_batch_device`` (a ``BeamBooks`` block that ``advance``,
+  ``rp_beam_advance``, updates after every step) and ``sample_search_batch`` (a ``SampleState``; rows never reorder, so
+  the ancestry table is the identity).  Nothing is read back per step: the stop flags are read every ``sync_every``
+  positions.  ``sample_search`` is the one-source call.
+- With admission (continuous batching): sources are submitted while the pool runs, each takes a free slot between two
+  steps, is stepped at its own position and is returned when it has stopped.  ``BeamSearchPool`` keeps host books;
+  ``BeamBooksPool`` (``rp_beam_pool_advance``) and ``SamplePool`` (``rp_sample_pool_step``) keep them on the device and
+  look only at sync points.  The device books and sampling refuse a prompt (``ValueError``: not built yet).
 
-``beam_search_batch_device`` is the beam search with the same property: the bookkeeping lives in a ``BeamBooks`` block on
-the device, ``advance`` (``rp_beam_advance``) updates it after every step, and the stop flags are read every
-``sync_every`` positions.  ``beam_advance_host`` restates that kernel on host tensors with its stable order (the kernel's
-oracle, and the ``advance`` of a CPU run).  ``beam_search_batch`` with its host books stays the default.
+What the drivers share exists once.  ``_SlotPool`` is the slot scheduler of the three pools: the queue, the tickets, a
+position per slot, ``queued`` / ``in_flight`` / ``drain``, and for the two device-books pools the sync point (``_sync``:
+read the flags, deliver the stopped, free their slots, admit into the lowest free slots, re-gather the by-row inputs if
+the active list changed) and the ``step`` around it; a pool adds its done flags, its results, its ``books_admit`` call
+and its per-step launch.  ``_beam_inputs`` / ``_beam_take`` are the host-books step body (the step's tokens, padded
+ancestry, running scores and positions from the ``_BeamState``s; the one readback of the selected triples and every
+state's ``advance``) of ``beam_search_batch`` and ``BeamSearchPool.step``.
 
-A decoder prompt (HF's ``decoder_input_ids``: tokens after the start token that every returned sequence begins with) is
-``prompt=`` / ``prompts=`` of ``beam_search``, ``beam_search_batch``, the two greedy functions and
-``BeamSearchPool.submit``: ``_BeamState`` starts at ``cur_len = prompt_len = P + 1`` with an ancestry that names one cache
-row per prompt position (beam 0's, ``p * nb``), written before the loop by a ``prefill`` callable (the engine's one-pass
-``rp_decoder_batch_prefill``, or ``prefill_by_steps`` through ordinary steps).  The device books and sampling refuse a
-prompt (``ValueError``: not built yet).
-
-``BeamSearchPool`` is ``beam_search_batch``'s loop with admission: sources are submitted while it runs, each takes a free
-slot between two steps and is stepped at its own position, and its output is returned at the step where it stops.
-``BeamBooksPool`` is that pool with the books in a ``BeamBooks`` block of ``n_slots`` states: a position per slot
-(``rp_beam_pool_advance``), the stop flags read every ``sync_every`` steps, results delivered at those sync points.
-``beam_books_admit_host``, ``beam_pool_advance_host`` and ``beam_books_rows_host`` restate its three kernels.
-``SamplePool`` is the same pool for the sampled search: the sampler's books (``SampleState``) for ``n_slots`` states, a
-position per slot (``rp_sample_pool_step``), one forced sync point when a slot reaches ``max_length - 1``;
-``sample_books_admit_host`` and ``sample_books_rows_host`` restate its other two kernels.  ``SamplingParams`` and the
-pool's ``per_request`` make the sampling parameters and the number of samples a property of the request: a parameter
-table by (state, sample) in ``SampleState.params`` (``rp_sample_step_rows`` / ``rp_sample_pool_step_rows``;
-``sample_row_params_host`` restates the lookup) and a live-row count per admitted state (``rp_sample_pool_admit_rows``).
+The kernels' host restatements, which are their oracles and the callables of a CPU run: ``beam_advance_host`` /
+``beam_pool_advance_host`` (one body, ``_advance_host``, with the kernel's stable order), ``beam_books_init_host``,
+``beam_books_admit_host``, ``beam_books_rows_host``, ``sample_books_admit_host``, ``sample_books_rows_host`` and
+``sample_row_params_host``.  ``SamplingParams`` and ``SamplePool``'s ``per_request`` make the sampling parameters and the
+number of samples a property of the request: a parameter table by (state, sample) in ``SampleState.params``
+(``rp_sample_step_rows`` / ``rp_sample_pool_step_rows``) and a live-row count per admitted state
+(``rp_sample_pool_admit_rows``).
 """
 from __future__ import annotations
 
@@ -116,17 +120,44 @@ def prefill_by_steps(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor],
         step(tokens, anc)
 
 
-def _check_prompts(prompts, n: int, max_length: int) -> Optional[List[List[int]]]:
-    """``prompts`` (None, or one entry or None per state) as token lists; None when no state has a prompt."""
+def _check_prompts(prompts, n: int, max_length: int, what: str = "prompts", whose: str = "states"
+                   ) -> Optional[List[List[int]]]:
+    """``prompts`` (None, or one entry or None per state) as token lists; None when no state has a prompt.  (A state
+    without one is the search's own to refuse when ``max_length`` leaves it no room.)"""
     if prompts is None:
         return None
     prompts = [_prompt_tokens(p) for p in prompts]
     if len(prompts) != n:
-        raise ValueError(f"{len(prompts)} prompts for {n} states")
+        raise ValueError(f"{len(prompts)} {what} for {n} {whose}")
     for p in prompts:
-        if max_length <= 1 + len(p):
+        if p and max_length <= 1 + len(p):
             raise ValueError(_no_room(max_length, len(p)))
     return prompts if any(prompts) else None
+
+
+def _prefill_prompts(prefill: Optional[Callable], step_at: Callable, listed: Sequence[int], prompts: Sequence[Sequence[int]],
+                     decoder_start_token_id: int, nb: int, device) -> None:
+    """Write the prompt rows of the states (or slots) ``listed``, ``prompts[j]`` being ``listed[j]``'s: one
+    ``prefill(listed, rows)`` where there is one, else one state and one position at a time through
+    ``step_at(i, p, tokens, ancestry)``, an ordinary step of state ``i`` alone at position ``p`` (``prefill_by_steps``)."""
+    rows = [_prompt_rows(p, decoder_start_token_id) for p in prompts]
+    if prefill is not None:
+        prefill(list(listed), rows)
+        return
+    for i, r in zip(listed, rows):
+        prefill_by_steps(lambda tok, anc, i=i: step_at(i, anc.shape[1] - 1, tok, anc), nb, r, device)
+
+
+def _check_room(max_length: int) -> None:
+    if max_length <= 1:
+        raise ValueError(_no_room(max_length, 0))
+
+
+def _check_count(name: str, value, or_none: str = "") -> int:
+    """``value`` as an int; a ``ValueError`` unless it is an integer >= 1 (``sync_every``, ``n_slots``)."""
+    if int(value) != value or value < 1:
+        raise ValueError(f"{name}={value} must be an integer >= 1{or_none}")
+    return int(value)
 
 
 # "divisors_count_prompt" plants a known bug: both length-penalty divisors count the prompt's tokens (prompt_len left at
@@ -262,6 +293,39 @@ def topk_select_many(log_probs: torch.Tensor, running_scores: torch.Tensor, nb: 
     return tuple(torch.stack(x) for x in zip(*outs))
 
 
+def _beam_inputs(states: Sequence[_BeamState], nb: int, device=None):
+    """The host-books step's ``(tokens [n * nb], ancestry [n * nb, W], running scores [n * nb], pos)`` over ``states``:
+    ``pos[a]`` is the position of ``states[a]``, ``W`` the widest ``pos + 1``, a narrower state's ancestry rows
+    right-padded with zeros (columns ``0..pos[a]`` are its own).  The tensors are moved to ``device`` when there is one."""
+    ins = [st.inputs() for st in states]
+    pos = [st.cur_len - 1 for st in states]
+    tokens = torch.cat([x[0] for x in ins])
+    running = torch.cat([st.running_scores for st in states])
+    if min(pos) == max(pos):
+        ancestry = torch.cat([x[1] for x in ins])
+    else:
+        ancestry = torch.zeros((len(states) * nb, max(pos) + 1), dtype=torch.int64)
+        for a, (_, anc) in enumerate(ins):
+            ancestry[a * nb : (a + 1) * nb, : anc.shape[1]] = anc
+    if device is not None:
+        tokens, ancestry, running = tokens.to(device), ancestry.to(device), running.to(device)
+    return tokens, ancestry, running, pos
+
+
+def _beam_take(states: Sequence[_BeamState], selected, traces: Optional[Sequence[list]] = None) -> List[bool]:
+    """Hand the step's selected triples (``select_many``'s three ``[n, 2 nb]`` outputs) to ``states``: one readback, then
+    every state's ``advance``; entry ``a`` says whether ``states[a]`` has stopped.  ``traces[a]``, when given, receives
+    that state's triples of this step."""
+    vals, toks, parents = selected
+    vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
+    stopped = []
+    for a, st in enumerate(states):
+        if traces is not None:
+            traces[a].append((vals[a].clone(), toks[a].clone(), parents[a].clone()))
+        stopped.append(st.advance(vals[a], toks[a], parents[a]))
+    return stopped
+
+
 def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_length: int, length_penalty: float = 1.0,
                       eos_token_id: int = 1, decoder_start_token_id: int = 0,
                       num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
@@ -296,38 +360,18 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
     nb = int(num_beams)
     if prompts is not None:
         listed = [i for i in range(num_states) if prompts[i]]
-        rows = [_prompt_rows(prompts[i], decoder_start_token_id) for i in listed]
-        if prefill_many is not None:
-            prefill_many(listed, rows)
-        else:
-            for i, r in zip(listed, rows):
-                prefill_by_steps(lambda tok, anc, i=i: step_many([i], tok, anc, pos=[anc.shape[1] - 1]), nb, r, device)
+        _prefill_prompts(prefill_many, lambda i, p, tok, anc: step_many([i], tok, anc, pos=[p]), listed,
+                         [prompts[i] for i in listed], decoder_start_token_id, nb, device)
     while active:
-        ins = [states[i].inputs() for i in active]
-        tokens = torch.cat([x[0] for x in ins])
-        running = torch.cat([states[i].running_scores for i in active])
-        if prompts is None:
-            ancestry = torch.cat([x[1] for x in ins])
-        else:
-            pos = [states[i].cur_len - 1 for i in active]
-            ancestry = torch.zeros((len(active) * nb, max(pos) + 1), dtype=torch.int64)
-            for a, (_, anc) in enumerate(ins):
-                ancestry[a * nb : (a + 1) * nb, : anc.shape[1]] = anc
-        if device is not None:
-            tokens, ancestry, running = tokens.to(device), ancestry.to(device), running.to(device)
+        stepped = [states[i] for i in active]
+        tokens, ancestry, running, pos = _beam_inputs(stepped, nb, device)
         if prompts is None:
             log_probs = step_many(list(active), tokens, ancestry)
         else:
             log_probs = step_many(list(active), tokens, ancestry, pos=pos)
-        vals, toks, parents = select_many(log_probs, running, nb, 2 * nb)
-        vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
-        still = []
-        for a, i in enumerate(active):
-            if traces is not None:
-                per_state[i].append((vals[a].clone(), toks[a].clone(), parents[a].clone()))
-            if not states[i].advance(vals[a], toks[a], parents[a]):
-                still.append(i)
-        active = still
+        stopped = _beam_take(stepped, select_many(log_probs, running, nb, 2 * nb),
+                             None if traces is None else [per_state[i] for i in active])
+        active = [i for i, over in zip(active, stopped) if not over]
     if traces is not None:
         traces.extend(per_state)
     return [st.result() for st in states]
@@ -337,7 +381,109 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
 POOL_MUTANTS = ("shared_position",)
 
 
-class BeamSearchPool:
+class _SlotPool:
+    """The slot scheduler of the three pools: ``n_slots`` places, a first-in-first-out queue of ``(ticket, source, ...)``
+    entries, per slot its tenant's ticket (None: free) and, for the device-books pools, the position of its next step.
+    ``BeamSearchPool`` takes the queue, the tickets and the slots from it and looks at its host books every step.  The
+    device-books pools (``sync_every`` given) take ``_sync`` and ``step`` too and supply what differs: ``_stopped()``
+    (read the done flags through ``to_host``; the slots in use that are over), ``_results(stopped)``, ``_admit_books(slots,
+    entries)`` (their ``books_admit`` call), ``_launch(active, pos)`` (the step's engine calls), ``_book`` (what ``rows``
+    is handed) and ``_last_pos`` (where a slot's position stays)."""
+
+    def __init__(self, n_slots: int, width_name: str, width: int, max_length: int, sync_every: Optional[int] = None):
+        if int(n_slots) < 1 or int(width) < 1:
+            raise ValueError(f"n_slots={n_slots} and {width_name}={width} must be >= 1")
+        _check_room(max_length)
+        self.n_slots, self.nb, self.max_length = int(n_slots), int(width), int(max_length)
+        self._queue: List[tuple] = []                                # (ticket, source, ...), first in first out
+        self._ticket: List[Optional[int]] = [None] * self.n_slots    # per slot: its tenant's ticket
+        self._next_ticket = 0
+        self.steps = 0
+        if sync_every is not None:
+            self.sync_every = _check_count("sync_every", sync_every)
+            self._pos = [0] * self.n_slots                           # per slot: the position of its next step
+            self._active: List[int] = []                             # the slots in use, ascending: the by-row order
+            self._since = 0                                          # steps since the last sync point
+            self.sync_points = 0
+
+    @property
+    def queued(self) -> int:
+        return len(self._queue)
+
+    @property
+    def in_flight(self) -> int:
+        return sum(t is not None for t in self._ticket)
+
+    def _issue(self, *entry) -> int:
+        """Queue ``(ticket, *entry)`` under the next ticket."""
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        self._queue.append((ticket,) + entry)
+        return ticket
+
+    def _take(self) -> Tuple[List[int], List[tuple]]:
+        """The lowest free slots (ascending) and the queue entries that take them, first in first out."""
+        free = [s for s in range(self.n_slots) if self._ticket[s] is None]
+        take = min(len(free), len(self._queue))
+        new, self._queue = self._queue[:take], self._queue[take:]
+        return free[:take], new
+
+    def _sync(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """A sync point (``BeamBooksPool``): the pairs it delivered."""
+        self.sync_points += 1
+        self._since = 0
+        out: List[Tuple[int, BeamSearchOutput]] = []
+        changed = False
+        if self._active:
+            stopped = self._stopped()
+            if stopped:
+                out = self._results(stopped)
+                for s in stopped:
+                    self._ticket[s] = None
+                changed = True
+        slots, new = self._take()
+        if slots:
+            self._admit(slots, [entry[1] for entry in new])
+            self._admit_books(slots, new)
+            for s, entry in zip(slots, new):
+                self._ticket[s], self._pos[s] = entry[0], 0
+            changed = True
+        self._active = [s for s in range(self.n_slots) if self._ticket[s] is not None]
+        if changed and self._active:
+            self._rows(self._book, list(self._active), [self._pos[s] for s in self._active])
+        return out
+
+    def step(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """One decode step, with a sync point before it when a queued source can take a free slot and one after it when
+        ``sync_every`` steps have passed or a slot stands at ``max_length - 1``; the ``(ticket, output)`` pairs those
+        sync points delivered."""
+        out: List[Tuple[int, BeamSearchOutput]] = []
+        if self._queue and self.in_flight < self.n_slots:
+            out.extend(self._sync())
+        if not self._active:
+            return out
+        active = list(self._active)
+        pos = [self._pos[s] for s in active]
+        self._launch(active, pos)
+        self.steps += 1
+        self._since += 1
+        last = self._last_pos
+        pos = [p + 1 if p < last else last for p in pos]
+        for s, p in zip(active, pos):
+            self._pos[s] = p
+        if self._since >= self.sync_every or max(pos) + 1 >= self.max_length:
+            out.extend(self._sync())
+        return out
+
+    def drain(self) -> List[Tuple[int, BeamSearchOutput]]:
+        """Step until nothing is queued or in flight; every pair that was delivered on the way, in delivery order."""
+        out = []
+        while self._queue or self.in_flight:
+            out.extend(self.step())
+        return out
+
+
+class BeamSearchPool(_SlotPool):
     """``beam_search_batch``'s loop opened up: ``n_slots`` places, each carrying one source's search (a ``_BeamState``)
     at its own position.  ``submit`` queues a source; every ``step`` first admits queued sources into the free slots,
     then runs one decode step and one selection over the slots in use, reads the selected triples back once, advances
@@ -362,28 +508,13 @@ class BeamSearchPool:
                  num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
                  mutant: Optional[str] = None, prefill: Optional[Callable] = None):
         assert mutant is None or mutant in POOL_MUTANTS, mutant
-        if int(n_slots) < 1 or int(num_beams) < 1:
-            raise ValueError(f"n_slots={n_slots} and num_beams={num_beams} must be >= 1")
-        if max_length <= 1:
-            raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+        super().__init__(n_slots, "num_beams", num_beams, max_length)
         self._admit, self._step, self._select_many, self._prefill = admit, step, select_many, prefill
-        self.n_slots, self.nb, self.device, self.mutant = int(n_slots), int(num_beams), device, mutant
-        self.max_length, self._start_token = max_length, decoder_start_token_id
+        self.device, self.mutant, self._start_token = device, mutant, decoder_start_token_id
         self._new_state = lambda prompt=None: _BeamState(num_beams, max_length, length_penalty, eos_token_id,
                                                          decoder_start_token_id, num_return_sequences, prompt)
-        self._prompt: dict = {}                                   # ticket -> its decoder prompt, where it has one
-        self._queue: List[Tuple[int, object]] = []               # (ticket, source), first in first out
-        self._slots: List[Optional[Tuple[int, _BeamState]]] = [None] * self.n_slots  # (ticket, books) per slot in use
-        self._next_ticket = 0
-        self.steps = 0
-
-    @property
-    def queued(self) -> int:
-        return len(self._queue)
-
-    @property
-    def in_flight(self) -> int:
-        return sum(s is not None for s in self._slots)
+        self._prompt: dict = {}                                       # ticket -> its decoder prompt, where it has one
+        self._state: List[Optional[_BeamState]] = [None] * self.n_slots  # per slot in use: its tenant's books
 
     def submit(self, source, prompt: Optional[Sequence[int]] = None) -> int:
         """Queue a source; its ticket names it in ``step``'s return.  ``prompt``: the ticket's decoder prompt after
@@ -392,67 +523,43 @@ class BeamSearchPool:
         prompt = _prompt_tokens(prompt)
         if self.max_length <= 1 + len(prompt):
             raise ValueError(_no_room(self.max_length, len(prompt)))
-        ticket = self._next_ticket
-        self._next_ticket += 1
+        ticket = self._issue(source)
         if prompt:
             self._prompt[ticket] = prompt
-        self._queue.append((ticket, source))
         return ticket
-
-    def _prefill_by_steps(self, slots, rows) -> None:
-        for s, r in zip(slots, rows):
-            prefill_by_steps(lambda tok, anc, s=s: self._step([s], [anc.shape[1] - 1], tok, anc), self.nb, r, self.device)
 
     def step(self) -> List[Tuple[int, BeamSearchOutput]]:
         """Admit what fits, take one decode step, return the ``(ticket, output)`` pairs of the states that stopped."""
-        free = [s for s in range(self.n_slots) if self._slots[s] is None]  # ascending: the lowest free slots first
-        take = min(len(free), len(self._queue))
-        if take:
-            new, self._queue = self._queue[:take], self._queue[take:]
-            self._admit(free[:take], [src for _, src in new])
+        slots, new = self._take()
+        if slots:
+            self._admit(slots, [src for _, src in new])
             prompted = []
-            for s, (ticket, _) in zip(free, new):
+            for s, (ticket, _) in zip(slots, new):
                 prompt = self._prompt.pop(ticket, None)
-                self._slots[s] = (ticket, self._new_state(prompt))
+                self._ticket[s], self._state[s] = ticket, self._new_state(prompt)
                 if prompt:
-                    prompted.append((s, _prompt_rows(prompt, self._start_token)))
+                    prompted.append((s, prompt))
             if prompted:
-                (self._prefill or self._prefill_by_steps)([s for s, _ in prompted], [r for _, r in prompted])
-        active = [s for s in range(self.n_slots) if self._slots[s] is not None]
+                _prefill_prompts(self._prefill, lambda s, p, tok, anc: self._step([s], [p], tok, anc),
+                                 [s for s, _ in prompted], [q for _, q in prompted], self._start_token, self.nb,
+                                 self.device)
+        active = [s for s in range(self.n_slots) if self._ticket[s] is not None]
         if not active:
             return []
         nb = self.nb
-        states = [self._slots[s][1] for s in active]
-        ins = [st.inputs() for st in states]
-        pos = [st.cur_len - 1 for st in states]
-        width = max(pos) + 1
-        tokens = torch.cat([x[0] for x in ins])
-        ancestry = torch.zeros((len(active) * nb, width), dtype=torch.int64)
-        for a, (_, anc) in enumerate(ins):
-            ancestry[a * nb : (a + 1) * nb, : anc.shape[1]] = anc
-        running = torch.cat([st.running_scores for st in states])
-        if self.device is not None:
-            tokens, ancestry, running = tokens.to(self.device), ancestry.to(self.device), running.to(self.device)
+        states = [self._state[s] for s in active]
+        tokens, ancestry, running, pos = _beam_inputs(states, nb, self.device)
         if self.mutant == "shared_position":
             pos = [max(pos)] * len(pos)
         log_probs = self._step(list(active), pos, tokens, ancestry)
-        vals, toks, parents = self._select_many(log_probs, running, nb, 2 * nb)
-        vals, toks, parents = vals.float().cpu(), toks.long().cpu(), parents.long().cpu()  # the per-step host sync
+        stopped = _beam_take(states, self._select_many(log_probs, running, nb, 2 * nb))
         self.steps += 1
         done = []
-        for a, s in enumerate(active):
-            ticket, st = self._slots[s]
-            if st.advance(vals[a], toks[a], parents[a]):
-                done.append((ticket, st.result()))
-                self._slots[s] = None
+        for s, st, over in zip(active, states, stopped):
+            if over:
+                done.append((self._ticket[s], st.result()))
+                self._ticket[s] = self._state[s] = None
         return done
-
-    def drain(self) -> List[Tuple[int, BeamSearchOutput]]:
-        """Step until nothing is queued or in flight; every pair that finished on the way, in finishing order."""
-        out = []
-        while self._queue or self.in_flight:
-            out.extend(self.step())
-        return out
 
 
 # ---- beam search with its books on the device ------------------------------------------------------------------------------
@@ -707,8 +814,7 @@ def beam_search_batch_device(step_many: Callable, select_many: Callable, advance
     _refuse_prompts(prompts, "the device books (sync_every)")
     n, nb = int(num_states), int(num_beams)
     nret = nb if num_return_sequences is None else int(num_return_sequences)
-    if max_length <= 1:
-        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+    _check_room(max_length)
     if nb < 1 or n < 1 or sync_every < 1 or not 1 <= nret <= nb:
         raise ValueError(f"num_states={n}, num_beams={nb}, sync_every={sync_every} must all be >= 1 and "
                          f"num_return_sequences={nret} in 1..num_beams")
@@ -745,7 +851,7 @@ def beam_search_batch_device(step_many: Callable, select_many: Callable, advance
     return [host.result(i, nret) for i in range(n)]
 
 
-class BeamBooksPool:
+class BeamBooksPool(_SlotPool):
     """``BeamSearchPool`` with the books on the device: ``n_slots`` places, state index = slot place, one ``BeamBooks``
     block of ``n_slots`` states, a position per slot kept on the host.  Per ``step`` it runs one engine ``step``, one
     ``select_many`` and one ``advance``; nothing is uploaded but their arguments and the host ``active`` / ``pos`` lists,
@@ -784,50 +890,30 @@ class BeamBooksPool:
                  sync_every: int = 16, books_admit: Optional[Callable] = None, advance: Optional[Callable] = None,
                  rows: Optional[Callable] = None, to_host: Callable = lambda x: x.cpu(), mutant: Optional[str] = None):
         assert mutant is None or mutant in POOL_BOOKS_MUTANTS, mutant
-        if int(n_slots) < 1 or int(num_beams) < 1:
-            raise ValueError(f"n_slots={n_slots} and num_beams={num_beams} must be >= 1")
-        if max_length <= 1:
-            raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
-        if int(sync_every) != sync_every or sync_every < 1:
-            raise ValueError(f"sync_every={sync_every} must be an integer >= 1")
-        self.n_slots, self.nb, self.max_length = int(n_slots), int(num_beams), int(max_length)
+        super().__init__(n_slots, "num_beams", num_beams, max_length, sync_every)
         self.nret = self.nb if num_return_sequences is None else int(num_return_sequences)
         if not 1 <= self.nret <= self.nb:
             raise ValueError(f"num_return_sequences={self.nret} outside 1..num_beams={self.nb}")
-        self.sync_every, self.length_penalty = int(sync_every), length_penalty
-        self.eos, self.start = eos_token_id, decoder_start_token_id
+        self.length_penalty, self.eos, self.start = length_penalty, eos_token_id, decoder_start_token_id
         self._admit, self._step, self._select_many, self._to_host = admit, step, select_many, to_host
         self._books_admit = books_admit or (lambda bk, states, eos, start: beam_books_admit_host(
             bk, states, eos, start, mutant="admit_not_reset" if mutant == "admit_not_reset" else None))
         self._advance = advance or (lambda bk, *a: beam_pool_advance_host(
             bk, *a, mutant="shared_position" if mutant == "shared_position" else None))
         self._rows = rows or beam_books_rows_host
-        self.books = BeamBooks(self.n_slots, self.nb, self.max_length, device=device)  # every state is admitted before use
-        self._queue: List[Tuple[int, object]] = []                   # (ticket, source), first in first out
-        self._ticket: List[Optional[int]] = [None] * self.n_slots    # per slot: its tenant's ticket
-        self._pos = [0] * self.n_slots                               # per slot: the position of its next step
-        self._active: List[int] = []                                 # the slots in use, ascending: the by-row order
-        self._next_ticket = 0
-        self._since = 0                                              # steps since the last sync point
-        self.steps = 0
-        self.sync_points = 0
-
-    @property
-    def queued(self) -> int:
-        return len(self._queue)
-
-    @property
-    def in_flight(self) -> int:
-        return sum(t is not None for t in self._ticket)
+        # every state is admitted before use
+        self.books = self._book = BeamBooks(self.n_slots, self.nb, self.max_length, device=device)
+        self._last_pos = self.max_length - 2  # (having advanced there the state is done: its books are frozen)
 
     def submit(self, source, prompt: Optional[Sequence[int]] = None) -> int:
         """Queue a source; its ticket names it in ``step``'s return.  (A decoder ``prompt`` is ``BeamSearchPool``'s: a
         ``ValueError`` here.)"""
         _refuse_prompts([prompt], "the device books (sync_every)")
-        ticket = self._next_ticket
-        self._next_ticket += 1
-        self._queue.append((ticket, source))
-        return ticket
+        return self._issue(source)
+
+    def _stopped(self) -> List[int]:
+        done = self._to_host(self.books.done)
+        return [s for s in self._active if bool(done[s])]
 
     def _results(self, stopped: List[int]) -> List[Tuple[int, BeamSearchOutput]]:
         """``BeamBooks.result`` of the stopped states from one buffer gathered on the device: per state its ``nret``
@@ -846,44 +932,11 @@ class BeamBooksPool:
             out.append((self._ticket[s], BeamSearchOutput(seq, scores)))
         return out
 
-    def _sync(self) -> List[Tuple[int, BeamSearchOutput]]:
-        self.sync_points += 1
-        self._since = 0
-        out: List[Tuple[int, BeamSearchOutput]] = []
-        changed = False
-        if self._active:
-            done = self._to_host(self.books.done)
-            stopped = [s for s in self._active if bool(done[s])]
-            if stopped:
-                out = self._results(stopped)
-                for s in stopped:
-                    self._ticket[s] = None
-                changed = True
-        free = [s for s in range(self.n_slots) if self._ticket[s] is None]  # ascending: the lowest free slots first
-        take = min(len(free), len(self._queue))
-        if take:
-            new, self._queue = self._queue[:take], self._queue[take:]
-            self._admit(free[:take], [src for _, src in new])
-            self._books_admit(self.books, free[:take], self.eos, self.start)
-            for s, (ticket, _) in zip(free, new):
-                self._ticket[s], self._pos[s] = ticket, 0
-            changed = True
-        self._active = [s for s in range(self.n_slots) if self._ticket[s] is not None]
-        if changed and self._active:
-            self._rows(self.books, list(self._active), [self._pos[s] for s in self._active])
-        return out
+    def _admit_books(self, slots: List[int], new: List[tuple]) -> None:
+        self._books_admit(self.books, slots, self.eos, self.start)
 
-    def step(self) -> List[Tuple[int, BeamSearchOutput]]:
-        """One decode step, with a sync point before it when a queued source can take a free slot and one after it
-        when ``sync_every`` steps have passed; the ``(ticket, output)`` pairs those sync points delivered."""
-        out: List[Tuple[int, BeamSearchOutput]] = []
-        if self._queue and self.in_flight < self.n_slots:
-            out.extend(self._sync())
-        if not self._active:
-            return out
+    def _launch(self, active: List[int], pos: List[int]) -> None:
         bk, nb, prompt_len = self.books, self.nb, 1
-        active = list(self._active)
-        pos = [self._pos[s] for s in active]
         rows = len(active) * nb
         log_probs = self._step(active, pos, bk.tokens[:rows], bk.anc_rows[:rows])
         vals, toks, parents = self._select_many(log_probs, bk.running[:rows], nb, 2 * nb)
@@ -891,20 +944,6 @@ class BeamBooksPool:
         fin_div = [float((p + 1 + 1 - prompt_len) ** self.length_penalty) for p in pos]
         run_div = [float((p + 2 - prompt_len) ** self.length_penalty) for p in pos]
         self._advance(bk, active, pos, vals, toks, parents, fin_div, run_div, self.eos)
-        self.steps += 1
-        self._since += 1
-        for s, p in zip(active, pos):
-            self._pos[s] = min(p + 1, self.max_length - 2)  # (past max_length - 2 the state is done: its books are frozen)
-        if self._since >= self.sync_every:
-            out.extend(self._sync())
-        return out
-
-    def drain(self) -> List[Tuple[int, BeamSearchOutput]]:
-        """Step until nothing is queued or in flight; every pair that was delivered on the way, in delivery order."""
-        out = []
-        while self._queue or self.in_flight:
-            out.extend(self.step())
-        return out
 
 
 def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], max_length: int, eos_token_id: int = 1,
@@ -930,33 +969,29 @@ def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, e
     A state leaves the active list at its EOS; the loop ends with the last one or at ``max_length``.
 
     ``prompts`` / ``prefill_many``: as in ``beam_search_batch`` with one beam.  State ``i`` starts at position ``P_i``
-    with ``[start] + prompt`` as its sequence, ``step_many`` is handed ``pos=``, and a state leaves at its EOS or when
-    its sequence holds ``max_length`` tokens.  Without prompts the loop is the one above, call for call."""
-    if max_length <= 1:
-        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+    with ``[start] + prompt`` as its sequence and ``step_many`` is handed ``pos=``; without prompts every state stands
+    at the same position and ``pos=`` is not passed.  Either way a state leaves at its EOS or when its sequence holds
+    ``max_length`` tokens."""
+    _check_room(max_length)
     prompts = _check_prompts(prompts, num_states, max_length)
     seqs = [[int(decoder_start_token_id)] for _ in range(num_states)]
     totals = [0.0] * num_states
     active = list(range(num_states))
     if prompts is not None:
         listed = [i for i in range(num_states) if prompts[i]]
-        rows = [_prompt_rows(prompts[i], decoder_start_token_id) for i in listed]
-        if prefill_many is not None:
-            prefill_many(listed, rows)
-        else:
-            for i, r in zip(listed, rows):
-                prefill_by_steps(lambda tok, anc, i=i: step_many([i], tok, anc, pos=[anc.shape[1] - 1]), 1, r, device)
+        _prefill_prompts(prefill_many, lambda i, p, tok, anc: step_many([i], tok, anc, pos=[p]), listed,
+                         [prompts[i] for i in listed], decoder_start_token_id, 1, device)
         for i in range(num_states):
             seqs[i].extend(prompts[i])
-    while prompts is not None and active:
+    while active:
         pos = [len(seqs[i]) - 1 for i in active]
         tokens = torch.tensor([seqs[i][-1] for i in active], dtype=torch.int64)
-        anc = torch.zeros((len(active), max(pos) + 1), dtype=torch.int64)
-        for a, p in enumerate(pos):
-            anc[a, : p + 1] = torch.arange(p + 1, dtype=torch.int64)
+        cols = torch.arange(max(pos) + 1, dtype=torch.int64)[None]
+        anc = cols * (cols <= torch.tensor(pos, dtype=torch.int64)[:, None])  # row a: 0..pos[a], then zeros
         if device is not None:
             tokens, anc = tokens.to(device), anc.to(device)
-        lps = step_many(list(active), tokens, anc, pos=pos).float().cpu()
+        kw = {} if prompts is None else dict(pos=pos)
+        lps = step_many(list(active), tokens, anc, **kw).float().cpu()
         still = []
         for a, i in enumerate(active):
             lp = lps[a]
@@ -966,23 +1001,6 @@ def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, e
             if best != eos_token_id and len(seqs[i]) < max_length:
                 still.append(i)
         active = still
-    t = 0
-    while active and t + 1 < max_length:
-        tokens = torch.tensor([seqs[i][-1] for i in active], dtype=torch.int64)
-        anc = torch.arange(t + 1, dtype=torch.int64)[None].repeat(len(active), 1)
-        if device is not None:
-            tokens, anc = tokens.to(device), anc.to(device)
-        lps = step_many(list(active), tokens, anc).float().cpu()
-        still = []
-        for a, i in enumerate(active):
-            lp = lps[a]
-            best = int(torch.nonzero(lp == lp.max())[0, 0])
-            totals[i] += float(lp[best])
-            seqs[i].append(best)
-            if best != eos_token_id:
-                still.append(i)
-        active = still
-        t += 1
     return [BeamSearchOutput(torch.tensor([s], dtype=torch.int64), torch.tensor([tot], dtype=torch.float32))
             for s, tot in zip(seqs, totals)]
 
@@ -1091,8 +1109,7 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
     finished-beam formula; the default 0.0 gives the sum)."""
     _refuse_prompts(prompts, "sampling")
     n, nb = int(num_states), int(num_samples)
-    if max_length <= 1:
-        raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
+    _check_room(max_length)
     if len(seeds) != n:
         raise ValueError(f"{len(seeds)} seeds for {n} states")
     if nb < 1 or n < 1 or sync_every < 1:
@@ -1225,7 +1242,7 @@ def sample_books_rows_host(state: SampleState, active: Sequence[int], pos: Seque
         state.tokens[a * nb : (a + 1) * nb] = state.seq[s, :, p]
 
 
-class SamplePool:
+class SamplePool(_SlotPool):
     """``sample_search_batch``'s loop with admission, the sampled counterpart of ``BeamBooksPool``: ``n_slots`` places,
     state index = slot place, the sampler's books (one ``SampleState`` of ``n_slots`` states) on the device, a position
     per slot kept on the host.  ``submit(source, seed)`` queues a source; per ``step`` it runs one engine ``step`` and one
@@ -1286,26 +1303,20 @@ class SamplePool:
                  per_request: bool = False, params: Optional[SamplingParams] = None):
         assert mutant is None or mutant in SAMPLE_POOL_MUTANTS + SAMPLE_PARAMS_MUTANTS, mutant
         assert per_request or (params is None and mutant not in SAMPLE_PARAMS_MUTANTS), "these need per_request=True"
-        if int(n_slots) < 1 or int(num_samples) < 1:
-            raise ValueError(f"n_slots={n_slots} and num_samples={num_samples} must be >= 1")
-        if max_length <= 1:
-            raise ValueError(f"max_length={max_length} leaves no room after the decoder start token")
-        if int(sync_every) != sync_every or sync_every < 1:
-            raise ValueError(f"sync_every={sync_every} must be an integer >= 1")
-        n, nb, L = int(n_slots), int(num_samples), int(max_length)
-        self.n_slots, self.nb, self.max_length = n, nb, L
-        self.sync_every, self.length_penalty, self.mutant = int(sync_every), length_penalty, mutant
+        super().__init__(n_slots, "num_samples", num_samples, max_length, sync_every)
+        n, nb, L = self.n_slots, self.nb, self.max_length
+        self.length_penalty, self.mutant = length_penalty, mutant
         self.start, self.pad = decoder_start_token_id, pad_token_id
         self._admit, self._step, self._sample_step, self._to_host = admit, step, sample_step, to_host
         host_mutant = mutant if mutant in ("admit_not_reset", "stale_params", "dead_rows_live") else None
         self._books_admit = books_admit or (lambda st, states, seeds, start, pad, **kw: sample_books_admit_host(
             st, states, seeds, start, pad, mutant=host_mutant, **kw))
-        self._rows = rows or sample_books_rows_host
+        self._rows = (lambda *a: None) if mutant == "stale_tokens" else (rows or sample_books_rows_host)
         self.per_request = bool(per_request)
         self._own = None                                             # per_request: the pool's own block [nb, 4]
         self._request = {}                                           # per_request: ticket -> (num_samples, block)
         self._live = [nb] * n                                        # per slot: its tenant's num_samples
-        self.state = SampleState(  # every state is admitted before use
+        self.state = self._book = SampleState(  # every state is admitted before use
             seeds=torch.zeros(n, dtype=torch.int32, device=device),
             seq=torch.zeros((n, nb, L), dtype=torch.int32, device=device),
             cum_logprob=torch.zeros((n, nb), dtype=torch.float32, device=device),
@@ -1320,22 +1331,7 @@ class SamplePool:
         ancestry = (torch.arange(L, dtype=torch.int32)[None] * nb
                     + (torch.arange(n * nb, dtype=torch.int32) % nb)[:, None]).contiguous()
         self.ancestry = ancestry if device is None else ancestry.to(device)
-        self._queue: List[Tuple[int, object, int]] = []              # (ticket, source, seed), first in first out
-        self._ticket: List[Optional[int]] = [None] * n               # per slot: its tenant's ticket
-        self._pos = [0] * n                                          # per slot: the position of its next step
-        self._active: List[int] = []                                 # the slots in use, ascending: the by-row order
-        self._next_ticket = 0
-        self._since = 0                                              # steps since the last sync point
-        self.steps = 0
-        self.sync_points = 0
-
-    @property
-    def queued(self) -> int:
-        return len(self._queue)
-
-    @property
-    def in_flight(self) -> int:
-        return sum(t is not None for t in self._ticket)
+        self._last_pos = L - 1  # (a slot that stands there is freed at the forced sync point, before any step)
 
     def submit(self, source, seed: int, params: Optional[SamplingParams] = None,
                num_samples: Optional[int] = None, prompt: Optional[Sequence[int]] = None) -> int:
@@ -1355,12 +1351,14 @@ class SamplePool:
             # (every row of a ticket's own parameters goes through check_sampling here)
             block = torch.cat([self._own[:k] if params is None else params.rows(k), self._pad_block[k:]])
             request = (k, block)
-        ticket = self._next_ticket
-        self._next_ticket += 1
+        ticket = self._issue(source, int(seed))
         if request is not None:
             self._request[ticket] = request
-        self._queue.append((ticket, source, int(seed)))
         return ticket
+
+    def _stopped(self) -> List[int]:
+        done = self._to_host(self.state.finished.bool().all(dim=1).to(torch.int32))
+        return [s for s in self._active if bool(done[s]) or self._pos[s] + 1 >= self.max_length]
 
     def _results(self, stopped: List[int]) -> List[Tuple[int, BeamSearchOutput]]:
         """``sample_search_batch``'s outputs of the stopped states from one buffer gathered on the device: per state its
@@ -1380,66 +1378,19 @@ class SamplePool:
                         BeamSearchOutput(seq, cum / ngen[:k].to(torch.float32) ** float(self.length_penalty))))
         return out
 
-    def _sync(self) -> List[Tuple[int, BeamSearchOutput]]:
-        self.sync_points += 1
-        self._since = 0
-        out: List[Tuple[int, BeamSearchOutput]] = []
-        changed = False
-        if self._active:
-            done = self._to_host(self.state.finished.bool().all(dim=1).to(torch.int32))
-            stopped = [s for s in self._active if bool(done[s]) or self._pos[s] + 1 >= self.max_length]
-            if stopped:
-                out = self._results(stopped)
-                for s in stopped:
-                    self._ticket[s] = None
-                changed = True
-        free = [s for s in range(self.n_slots) if self._ticket[s] is None]  # ascending: the lowest free slots first
-        take = min(len(free), len(self._queue))
-        if take:
-            new, self._queue = self._queue[:take], self._queue[take:]
-            self._admit(free[:take], [src for _, src, _ in new])
-            if self.per_request:
-                requests = [self._request.pop(ticket) for ticket, _, _ in new]
-                self._books_admit(self.state, free[:take], [seed for _, _, seed in new], self.start, self.pad,
-                                  n_live=[k for k, _ in requests], params=torch.stack([blk for _, blk in requests]))
-                for s, (k, _) in zip(free, requests):
-                    self._live[s] = k
-            else:
-                self._books_admit(self.state, free[:take], [seed for _, _, seed in new], self.start, self.pad)
-            for s, (ticket, _, _) in zip(free, new):
-                self._ticket[s], self._pos[s] = ticket, 0
-            changed = True
-        self._active = [s for s in range(self.n_slots) if self._ticket[s] is not None]
-        if changed and self._active and self.mutant != "stale_tokens":
-            self._rows(self.state, list(self._active), [self._pos[s] for s in self._active])
-        return out
+    def _admit_books(self, slots: List[int], new: List[tuple]) -> None:
+        seeds = [seed for _, _, seed in new]
+        if not self.per_request:
+            self._books_admit(self.state, slots, seeds, self.start, self.pad)
+            return
+        requests = [self._request.pop(ticket) for ticket, _, _ in new]
+        self._books_admit(self.state, slots, seeds, self.start, self.pad, n_live=[k for k, _ in requests],
+                          params=torch.stack([blk for _, blk in requests]))
+        for s, (k, _) in zip(slots, requests):
+            self._live[s] = k
 
-    def step(self) -> List[Tuple[int, BeamSearchOutput]]:
-        """One decode step, with a sync point before it when a queued source can take a free slot and one after it when
-        ``sync_every`` steps have passed or a slot reached ``max_length - 1``; the ``(ticket, output)`` pairs those sync
-        points delivered."""
-        out: List[Tuple[int, BeamSearchOutput]] = []
-        if self._queue and self.in_flight < self.n_slots:
-            out.extend(self._sync())
-        if not self._active:
-            return out
-        active = list(self._active)
-        pos = [self._pos[s] for s in active]
+    def _launch(self, active: List[int], pos: List[int]) -> None:
         rows = len(active) * self.nb
         log_probs = self._step(active, pos, self.state.tokens[:rows], self.ancestry[:rows])
         self._sample_step(log_probs, active, [pos[0]] * len(pos) if self.mutant == "shared_position" else list(pos),
                           self.state)
-        self.steps += 1
-        self._since += 1
-        for s in active:
-            self._pos[s] += 1
-        if self._since >= self.sync_every or any(self._pos[s] + 1 >= self.max_length for s in active):
-            out.extend(self._sync())
-        return out
-
-    def drain(self) -> List[Tuple[int, BeamSearchOutput]]:
-        """Step until nothing is queued or in flight; every pair that was delivered on the way, in delivery order."""
-        out = []
-        while self._queue or self.in_flight:
-            out.extend(self.step())
-        return out
