@@ -596,9 +596,9 @@ RpStatus rp_dbg_unfold(const float* part, int64_t split_stride, int32_t splits, 
  *     gelu_new(A W[n]) * (A W[n + N]).  K > 4096: RP_E_UNSUPPORTED, nothing launched.
  *   rp_dbg_dec_rows: mode 0 dec_embed_kernel (ia = tokens [rows], a = table f32 [vocab, n]; o0 f32 [rows, n]); 1
  *     dec_rmsnorm_kernel (a = x f32 [rows, n], b = ln f32 [n]; o0 bf16 [rows, n]; eps, scale); 2 dec_log_softmax_kernel (o0 f32
- *     [rows, n], in place); 3 dec_store_kv_kernel (a = qkv bf16 [n_active * nb, 3 n], n = inner; o0 = the caches, state s at
+ *     [rows, n], in place); 3 dec_store_kv_kernel<DecSlots> (a = qkv bf16 [n_active * nb, 3 n], n = inner; o0 = the caches, state s at
  *     s * state_stride elements, max_len * nb rows of 2 n; row pos[slot] * nb + beam of state[slot] <- k | v of its qkv row).
- *   rp_dbg_dec_attention: dec_attention_kernel<cross != 0> over the n_active * nb rows of a slot table.  self: kv = the caches
+ *   rp_dbg_dec_attention: dec_attention_kernel<cross != 0, DecSlots> over the n_active * nb rows of a slot table.  self: kv = the caches
  *     (state s at s * state_stride elements, rows = max_len * nb rows of ldkv), keys 0 .. pos[slot] through anc int32
  *     [n_active * nb, astride] (entries clamped to [0, rows)), bias tab f32 [H, nbias] by distance (clamped at nbias - 1).
  *     cross: kv = `rows` rows of ldkv, slot a reads rows [src_off[a], src_off[a] + src_len[a]), no bias.  K at column

@@ -14,8 +14,10 @@
 // whose slots states enter between steps (rp_decoder_pool_admit): continuous batching.
 // rp_decoder_batch_step_pos is the batched call with a position per listed state.  rp_decoder_batch_prefill /
 // rp_decoder_pool_prefill write a decoder prompt's cache rows - one per prompt position, beam 0's, shared by all beams of
-// the state - for all positions of all listed states in one launch sequence (dec_prefill_launch), with the step's own
-// row-wise kernels and dec_attention_row, so that the rows are the bits the step writes.
+// the state - for all positions of all listed states through the step's own launch sequence (dec_layers_launch) and
+// kernels, the rows found through a segment table (DecSegs) instead of the slot table, so that the rows are the bits the
+// step writes.  Behind the entries: one list check (dec_list), one geometry of the workspace (DecGeom, from src_cu or from
+// the pool's slots), one step (dec_step) and one prefill (dec_prefill).
 // rp_sample_step (sampling) and rp_beam_books_init / rp_beam_advance (beam search) keep a search's bookkeeping on the
 // device, one more launch per step, so that the host loop reads nothing back per position.  rp_beam_pool_advance is
 // rp_beam_advance with a position per slot (one kernel: the uniform call has every slot at t), and rp_beam_books_admit /
@@ -146,6 +148,56 @@ struct DecSlots {
   int32_t pos[DEC_MAX_STATES];
 };
 
+// ---- prompt prefill (DESIGN.md section 9, "Tactic prefix") ---------------------------------------------------------------
+// The rows of one prefill pass, by segment: segment g is rows row0[g] .. row0[g + 1] of the pass (row0 ascending, the
+// last segment runs to the pass's end), the prompt positions pos0[g], pos0[g] + 1, ... of one state.  A prompt is shared
+// by the state's beams: the row at position p is stored as cache row p * nb (beam 0's) and nowhere else.
+struct DecSegs {
+  int32_t n;
+  int32_t state[DEC_MAX_STATES];
+  int32_t src_off[DEC_MAX_STATES];
+  int32_t src_len[DEC_MAX_STATES];
+  int32_t pos0[DEC_MAX_STATES];
+  int32_t row0[DEC_MAX_STATES];
+};
+__device__ __forceinline__ int dec_seg_of(const DecSegs& segs, int row) {
+  int g = 0;
+  for (int i = 1; i < segs.n; ++i)
+    if (row >= segs.row0[i]) g = i;
+  return g;
+}
+
+// What a row table (DecSlots: the rows of a step; DecSegs: the rows of a prefill pass) says of one row of its launch: the
+// row's state, that state's source rows of the cross K/V, the row's position and beam - it is stored in row pos * nb + beam
+// of the state's cache - and its ancestry row.  A step's row is beam row - slot * nb of its slot, with its own row of the
+// ancestry table; a prompt row is beam 0's, and every prompt row reads the caller's one vector p' -> p' * nb.
+struct DecRow {
+  int state, src_off, src_len, pos, beam;
+  const int32_t* anc;
+  __device__ __forceinline__ int cache_row(int nb) const { return pos * nb + beam; }
+};
+__device__ __forceinline__ DecRow dec_row(const DecSlots& slots, int row, int nb, const int32_t* anc, int astride) {
+  const int slot = row / nb, b = row - slot * nb;
+  return {slots.state[slot], slots.src_off[slot], slots.src_len[slot], slots.pos[slot], b, anc + (size_t)row * astride};
+}
+__device__ __forceinline__ DecRow dec_row(const DecSegs& segs, int row, int, const int32_t* anc, int) {
+  const int g = dec_seg_of(segs, row);
+  return {segs.state[g], segs.src_off[g], segs.src_len[g], segs.pos0[g] + (row - segs.row0[g]), 0, anc};
+}
+// the longest self-attention key list and the longest source among the M rows of a launch (the dynamic LDS holds them)
+int dec_max_keys(const DecSlots& slots, int M, int nb) {
+  int keys = 0;
+  for (int a = 0; a < M / nb; ++a) keys = std::max(keys, slots.pos[a] + 1);
+  return keys;
+}
+int dec_max_keys(const DecSegs& segs, int M, int) {
+  int keys = 0;  // the largest position the pass reaches, plus one
+  for (int g = 0; g < segs.n; ++g) keys = std::max(keys, segs.pos0[g] + (g + 1 < segs.n ? segs.row0[g + 1] : M) - segs.row0[g]);
+  return keys;
+}
+int dec_max_src(const DecSlots& slots, int M, int nb) { return *std::max_element(slots.src_len, slots.src_len + M / nb); }
+int dec_max_src(const DecSegs& segs, int, int) { return *std::max_element(segs.src_len, segs.src_len + segs.n); }
+
 // One (head, row) of decoder attention: softmax(q k^T + bias) v over `len` keys, d_kv = 64, fp32 scores in s_sc (dynamic
 // LDS, >= len floats), by one 256-thread workgroup.  q / out point at the row's own q and output row, anc at its ancestry
 // row (or null).  Key p lives in row r(p) of kv (r = anc[p] clamped to [0, rows), or p); K at column koff + 64 h, V at
@@ -203,104 +255,55 @@ __device__ __forceinline__ void dec_attention_row(float* __restrict__ s_sc, cons
   }
 }
 
-// One (head, row) per workgroup, row = slot * nb + beam.  Self-attention (CROSS = false): the state's own cache of
-// `rows` = max_len * nb rows at kv + state * state_stride, keys through the row's ancestry entries (local to that cache),
-// pos[slot] + 1 keys: columns 0 .. pos[slot] of the row's ancestry entries (the dynamic LDS holds the call's largest
-// pos + 1 scores).  Cross-attention: the state's source rows of the cross K/V, all src_len keys, no bias.
-template <bool CROSS>
+// One (head, row) per workgroup, the row found through its table (dec_row).  Self-attention (CROSS = false): the state's
+// own cache of `rows` = max_len * nb rows at kv + state * state_stride, keys through the row's ancestry entries (local to
+// that cache), pos + 1 keys: entries 0 .. pos (the dynamic LDS holds the launch's largest pos + 1 scores).  Cross-attention:
+// the state's source rows of the cross K/V, all src_len keys, no bias.  A prompt row (DecSegs) runs dec_attention_row as
+// the step runs it, so its bits are those of the step at its position for beam 0.
+template <bool CROSS, typename Rows>
 __global__ __launch_bounds__(256) void dec_attention_kernel(const bf16_t* __restrict__ q, int ldq,
                                                             const bf16_t* __restrict__ kv, int ldkv, int koff, int voff,
                                                             int rows, size_t state_stride,
                                                             const int32_t* __restrict__ anc, int astride,
-                                                            const float* __restrict__ tab, int nbias, int nb,
-                                                            DecSlots slots, bf16_t* __restrict__ out, int ldo) {
+                                                            const float* __restrict__ tab, int nbias, int nb, Rows table,
+                                                            bf16_t* __restrict__ out, int ldo) {
   extern __shared__ float s_sc[];
   const int h = blockIdx.x, row = blockIdx.y;
-  const int slot = row / nb;
+  const DecRow r = dec_row(table, row, nb, anc, astride);
   if constexpr (CROSS)
-    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)slots.src_off[slot] * ldkv, ldkv, koff, voff,
-                      slots.src_len[slot], nullptr, nullptr, 1, slots.src_len[slot], out + (size_t)row * ldo, h);
+    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)r.src_off * ldkv, ldkv, koff, voff, r.src_len, nullptr,
+                      nullptr, 1, r.src_len, out + (size_t)row * ldo, h);
   else
-    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)slots.state[slot] * state_stride, ldkv, koff, voff, rows,
-                      anc + (size_t)row * astride, tab, nbias, slots.pos[slot] + 1, out + (size_t)row * ldo, h);
+    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)r.state * state_stride, ldkv, koff, voff, rows, r.anc, tab,
+                      nbias, r.pos + 1, out + (size_t)row * ldo, h);
 }
 
-// The step's two attention launches over the n_active * nb rows of a slot table (dec_step_launch and the test entry
-// rp_dbg_dec_attention both launch through here): the dynamic LDS holds the call's longest key list.
+// The two attention launches over the M rows of a row table (dec_layers_launch and the test entry rp_dbg_dec_attention
+// both launch through here): one workgroup per (head, row), the dynamic LDS holds the launch's longest key list.
+template <typename Rows>
 void launch_dec_self_attention(const bf16_t* q, int ldq, const bf16_t* cache, int ldkv, int koff, int voff, int rows,
                                size_t state_stride, const int32_t* anc, int astride, const float* tab, int nbias, int nb,
-                               int H, const DecSlots& slots, int n_active, bf16_t* out, int ldo, hipStream_t s) {
-  int max_keys = 0;
-  for (int a = 0; a < n_active; ++a) max_keys = std::max(max_keys, slots.pos[a] + 1);
-  hipLaunchKernelGGL((dec_attention_kernel<false>), dim3(H, n_active * nb), dim3(256), max_keys * sizeof(float), s, q, ldq,
-                     cache, ldkv, koff, voff, rows, state_stride, anc, astride, tab, nbias, nb, slots, out, ldo);
+                               int H, const Rows& table, int M, bf16_t* out, int ldo, hipStream_t s) {
+  hipLaunchKernelGGL((dec_attention_kernel<false, Rows>), dim3(H, M), dim3(256), dec_max_keys(table, M, nb) * sizeof(float), s,
+                     q, ldq, cache, ldkv, koff, voff, rows, state_stride, anc, astride, tab, nbias, nb, table, out, ldo);
 }
+template <typename Rows>
 void launch_dec_cross_attention(const bf16_t* q, int ldq, const bf16_t* ckv, int ldkv, int koff, int voff, int nb, int H,
-                                const DecSlots& slots, int n_active, bf16_t* out, int ldo, hipStream_t s) {
-  int max_src = 0;
-  for (int a = 0; a < n_active; ++a) max_src = std::max(max_src, slots.src_len[a]);
-  hipLaunchKernelGGL((dec_attention_kernel<true>), dim3(H, n_active * nb), dim3(256), max_src * sizeof(float), s, q, ldq, ckv,
-                     ldkv, koff, voff, 0, (size_t)0, (const int32_t*)nullptr, 0, (const float*)nullptr, 1, nb, slots, out,
-                     ldo);
+                                const Rows& table, int M, bf16_t* out, int ldo, hipStream_t s) {
+  hipLaunchKernelGGL((dec_attention_kernel<true, Rows>), dim3(H, M), dim3(256), dec_max_src(table, M, nb) * sizeof(float), s, q,
+                     ldq, ckv, ldkv, koff, voff, 0, (size_t)0, (const int32_t*)nullptr, 0, (const float*)nullptr, 1, nb, table,
+                     out, ldo);
 }
 
-// cache row pos[slot] * nb + beam of the row's state <- the k, v columns of qkv[row]
+// the row's cache row of its state <- the k, v columns of qkv[row]
+template <typename Rows>
 __global__ __launch_bounds__(256) void dec_store_kv_kernel(const bf16_t* __restrict__ qkv, int inner,
                                                            bf16_t* __restrict__ cache, size_t state_stride, int nb,
-                                                           DecSlots slots) {
-  const int row = blockIdx.x, slot = row / nb, b = row - slot * nb;
-  bf16_t* dst = cache + (size_t)slots.state[slot] * state_stride + (size_t)(slots.pos[slot] * nb + b) * 2 * inner;
+                                                           Rows table) {
+  const int row = blockIdx.x;
+  const DecRow r = dec_row(table, row, nb, nullptr, 0);
+  bf16_t* dst = cache + (size_t)r.state * state_stride + (size_t)r.cache_row(nb) * 2 * inner;
   for (int c = threadIdx.x; c < 2 * inner; c += 256) dst[c] = qkv[(size_t)row * 3 * inner + inner + c];
-}
-
-// ---- prompt prefill (DESIGN.md section 9, "Tactic prefix") ---------------------------------------------------------------
-// The rows of one prefill pass, by segment: segment g is rows row0[g] .. row0[g + 1] of the pass (row0 ascending, the
-// last segment runs to the pass's end), the prompt positions pos0[g], pos0[g] + 1, ... of one state.  A prompt is shared
-// by the state's beams: the row at position p is stored as cache row p * nb (beam 0's) and nowhere else.
-struct DecSegs {
-  int32_t n;
-  int32_t state[DEC_MAX_STATES];
-  int32_t src_off[DEC_MAX_STATES];
-  int32_t src_len[DEC_MAX_STATES];
-  int32_t pos0[DEC_MAX_STATES];
-  int32_t row0[DEC_MAX_STATES];
-};
-__device__ __forceinline__ int dec_seg_of(const DecSegs& segs, int row) {
-  int g = 0;
-  for (int i = 1; i < segs.n; ++i)
-    if (row >= segs.row0[i]) g = i;
-  return g;
-}
-
-// cache row p * nb of the row's state <- the k, v columns of qkv[row], p the row's prompt position
-__global__ __launch_bounds__(256) void dec_prefill_store_kv_kernel(const bf16_t* __restrict__ qkv, int inner,
-                                                                   bf16_t* __restrict__ cache, size_t state_stride, int nb,
-                                                                   DecSegs segs) {
-  const int row = blockIdx.x, g = dec_seg_of(segs, row), p = segs.pos0[g] + (row - segs.row0[g]);
-  bf16_t* dst = cache + (size_t)segs.state[g] * state_stride + (size_t)p * nb * 2 * inner;
-  for (int c = threadIdx.x; c < 2 * inner; c += 256) dst[c] = qkv[(size_t)row * 3 * inner + inner + c];
-}
-
-// dec_attention_kernel for prompt rows: one (head, row) per workgroup, the row at position p of its segment's state.
-// Self-attention: p + 1 keys, key p' in cache row anc[p'] of the state (the caller's vector p' -> p' * nb, the same for
-// every row).  Cross-attention: all of the state's source keys.  dec_attention_row as the step runs it, so a row's bits
-// are those of the step at position p for beam 0.
-template <bool CROSS>
-__global__ __launch_bounds__(256) void dec_prefill_attention_kernel(const bf16_t* __restrict__ q, int ldq,
-                                                                    const bf16_t* __restrict__ kv, int ldkv, int koff,
-                                                                    int voff, int rows, size_t state_stride,
-                                                                    const int32_t* __restrict__ anc,
-                                                                    const float* __restrict__ tab, int nbias, DecSegs segs,
-                                                                    bf16_t* __restrict__ out, int ldo) {
-  extern __shared__ float s_sc[];
-  const int h = blockIdx.x, row = blockIdx.y;
-  const int g = dec_seg_of(segs, row);
-  if constexpr (CROSS)
-    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)segs.src_off[g] * ldkv, ldkv, koff, voff, segs.src_len[g],
-                      nullptr, nullptr, 1, segs.src_len[g], out + (size_t)row * ldo, h);
-  else
-    dec_attention_row(s_sc, q + (size_t)row * ldq, kv + (size_t)segs.state[g] * state_stride, ldkv, koff, voff, rows, anc,
-                      tab, nbias, segs.pos0[g] + (row - segs.row0[g]) + 1, out + (size_t)row * ldo, h);
 }
 
 __global__ __launch_bounds__(256) void dec_log_softmax_kernel(float* __restrict__ x, int V) {
@@ -1031,8 +1034,32 @@ RpStatus dec_reload_table(RpDecoder* d) {
   return RP_OK;
 }
 
-// the caps of a call; total_src = src_cu[n]
-RpStatus dec_check(const RpDecoder* d, const int32_t* src_cu, int n, int nb, int max_len, int& total_src) {
+// The ids a call lists: n of them, each in [0, bound), none named twice (bound <= DEC_MAX_STATES: a 32-bit mask).  `list`
+// is the argument's name in the messages and `what` the thing an id names ("state" or "slot").  each(index, id) checks
+// what else the caller keeps per entry and fills its by-value table; its refusal ends the walk.
+template <typename Each>
+RpStatus dec_list(const int32_t* ids, int n, int bound, const char* list, const char* what, Each each) {
+  uint32_t seen = 0;
+  for (int a = 0; a < n; ++a) {
+    const int id = ids[a];
+    RP_REQUIRE(id >= 0 && id < bound, "%s[%d]=%d outside [0, %ss=%d)", list, a, id, what, bound);
+    RP_REQUIRE(!(seen & (1u << id)), "%s[%d]=%d names a %s twice", list, a, id, what);  // two entries would share rows
+    seen |= 1u << id;
+    if (RpStatus st = each(a, id)) return st;
+  }
+  return RP_OK;
+}
+
+// Where the states of a workspace live: n caches and a cross K/V of total_src rows, state s's source in rows
+// [off[s], off[s] + len[s]).  dec_check fills it from src_cu, pool_check with every slot's region src_cap rows long (the
+// pool's calls say how much of a region is in use).
+struct DecGeom {
+  int n, total_src;
+  int32_t off[DEC_MAX_STATES], len[DEC_MAX_STATES];
+};
+
+// the caps of a call over packed sources
+RpStatus dec_check(const RpDecoder* d, const int32_t* src_cu, int n, int nb, int max_len, DecGeom& g) {
   RP_REQUIRE(d, "null decoder");
   RP_REQUIRE(src_cu, "null src_cu");
   RP_REQUIRE(n >= 1 && n <= DEC_MAX_STATES, "states=%d (1..%d)", n, DEC_MAX_STATES);
@@ -1043,8 +1070,35 @@ RpStatus dec_check(const RpDecoder* d, const int32_t* src_cu, int n, int nb, int
   for (int b = 0; b < n; ++b) {
     const int64_t S = (int64_t)src_cu[b + 1] - src_cu[b];
     RP_REQUIRE(S >= 1 && S <= DEC_MAX_KEYS, "src_len of state %d = %lld (1..%d)", b, (long long)S, DEC_MAX_KEYS);
+    g.off[b] = src_cu[b];
+    g.len[b] = (int32_t)S;
   }
-  total_src = src_cu[n];
+  g.n = n;
+  g.total_src = src_cu[n];
+  return RP_OK;
+}
+
+// the caps of a slot pool: dec_check's, with every slot's source region src_cap rows long
+RpStatus pool_check(const RpDecoder* d, int n_slots, int nb, int max_len, int src_cap, DecGeom& g) {
+  RP_REQUIRE(d, "null decoder");
+  RP_REQUIRE(n_slots >= 1 && n_slots <= DEC_MAX_STATES, "slots=%d (1..%d)", n_slots, DEC_MAX_STATES);
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "num_beams=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(n_slots * nb <= DEC_MAX_ROWS, "rows = slots * num_beams = %d > %d", n_slots * nb, DEC_MAX_ROWS);
+  RP_REQUIRE(max_len >= 1 && max_len <= DEC_MAX_KEYS, "max_len=%d (1..%d)", max_len, DEC_MAX_KEYS);
+  RP_REQUIRE(src_cap >= 1 && src_cap <= DEC_MAX_KEYS, "src_cap=%d (1..%d)", src_cap, DEC_MAX_KEYS);
+  for (int sl = 0; sl < n_slots; ++sl) {
+    g.off[sl] = sl * src_cap;
+    g.len[sl] = src_cap;
+  }
+  g.n = n_slots;
+  g.total_src = n_slots * src_cap;
+  return RP_OK;
+}
+
+// the workspace of a geometry, carved; refused when the caller's is absent or smaller
+RpStatus dec_workspace(const RpDecoder* d, const DecGeom& g, int nb, int max_len, void* ws, size_t ws_bytes, DecWs& w) {
+  w = dec_carve(d, g.n, g.total_src, nb, max_len, (char*)ws);
+  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
   return RP_OK;
 }
 
@@ -1112,34 +1166,37 @@ extern "C" void rp_decoder_destroy(RpDecoder* d) {
 
 extern "C" size_t rp_decoder_batch_workspace_bytes(const RpDecoder* d, const int32_t* src_cu, int32_t n, int32_t nb,
                                                    int32_t max_len) {
-  int total = 0;
-  if (dec_check(d, src_cu, n, nb, max_len, total) != RP_OK) return 0;
-  return dec_carve(d, n, total, nb, max_len, nullptr).bytes;
+  DecGeom g;
+  if (dec_check(d, src_cu, n, nb, max_len, g) != RP_OK) return 0;
+  return dec_carve(d, g.n, g.total_src, nb, max_len, nullptr).bytes;
 }
 
 extern "C" RpStatus rp_decoder_batch_cross_kv(RpDecoder* d, const void* enc, const int32_t* src_cu, int32_t n, int32_t nb,
                                               int32_t max_len, void* ws, size_t ws_bytes, void* stream_) {
-  int total = 0;
-  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
+  DecGeom g;
+  DecWs w;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, g);
   if (st) return st;
   RP_REQUIRE(enc, "null encoder states");
-  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
-  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+  if ((st = dec_workspace(d, g, nb, max_len, ws, ws_bytes, w))) return st;
   const int D = d->cfg.d_model, NKV = d->cfg.num_layers * 2 * d->inner;
-  return launch_dec_gemm<EPI_BF16>((const bf16_t*)enc, D, total, d->cross_kv_w, NKV, D, w.ckv, NKV, (hipStream_t)stream_);
+  return launch_dec_gemm<EPI_BF16>((const bf16_t*)enc, D, g.total_src, d->cross_kv_w, NKV, D, w.ckv, NKV, (hipStream_t)stream_);
 }
 
 namespace {
-// The launch sequence of one decode step over the n_active * nb rows of a checked slot table: the one implementation
-// behind rp_decoder_batch_step (every slot at the call's t) and rp_decoder_pool_step (a position per slot).  Only the
-// cache store and the self-attention read a position, each its own slot's.
-RpStatus dec_step_launch(RpDecoder* d, const DecWs& w, const DecSlots& slots, int n_active, const int32_t* tokens,
-                         const int32_t* anc, int astride, int nb, int max_len, float* logprobs, hipStream_t s) {
+// The launch sequence over the M rows of a row table: a decode step's (DecSlots: rp_decoder_batch_step, every slot at the
+// call's t; rp_decoder_batch_step_pos and rp_decoder_pool_step, a position per slot) or a prefill pass's (DecSegs).  Only
+// the cache store and the two attentions look at the table; everything else is row-wise.  All rows' K/V are stored before
+// the self-attention reads them.  Without `logprobs` (a prefill pass) the last layer ends at its cache store - nothing
+// after it reaches the cache - and there is no final norm, lm_head or log_softmax.
+template <typename Rows>
+RpStatus dec_layers_launch(RpDecoder* d, const DecWs& w, const Rows& table, int M, const int32_t* tokens, const int32_t* anc,
+                           int astride, int nb, int max_len, float* logprobs, hipStream_t s) {
   RpStatus st;
   const RpT5Config& c = d->cfg;
   const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
   const float eps = c.layer_norm_eps;
-  const int M = n_active * nb, rows = max_len * nb, ldckv = L * 2 * inner;
+  const int rows = max_len * nb, ldckv = L * 2 * inner;
   const size_t layer_stride = (size_t)rows * 2 * inner, state_stride = (size_t)L * layer_stride;
   bf16_t* ffn = w.h + (size_t)M * D;
   hipLaunchKernelGGL(dec_embed_kernel, dim3(M), dim3(256), 0, s, tokens, d->embed, w.x, D, V);
@@ -1149,38 +1206,59 @@ RpStatus dec_step_launch(RpDecoder* d, const DecWs& w, const DecSlots& slots, in
     // self-attention (modeling_t5.py T5LayerSelfAttention): x += o(attn(rmsnorm(x)))
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_self, w.h, D, eps, 1.f);
     if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.wqkv, 3 * inner, D, w.qkv, 3 * inner, s))) return st;
-    hipLaunchKernelGGL(dec_store_kv_kernel, dim3(M), dim3(256), 0, s, w.qkv, inner, cache, state_stride, nb, slots);
+    hipLaunchKernelGGL(dec_store_kv_kernel<Rows>, dim3(M), dim3(256), 0, s, w.qkv, inner, cache, state_stride, nb, table);
+    if (!logprobs && i == L - 1) break;
     launch_dec_self_attention(w.qkv, 3 * inner, cache, 2 * inner, 0, inner, rows, state_stride, anc, astride, d->bias_tab,
-                              d->nbias, nb, H, slots, n_active, w.att, inner, s);
+                              d->nbias, nb, H, table, M, w.att, inner, s);
     if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.wo, D, inner, w.x, D, s))) return st;
     // cross-attention (T5LayerCrossAttention): no position bias, all of the state's source keys
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_cross, w.h, D, eps, 1.f);
     if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.cq, inner, D, w.qkv, inner, s))) return st;
-    launch_dec_cross_attention(w.qkv, inner, w.ckv, ldckv, 2 * i * inner, (2 * i + 1) * inner, nb, H, slots, n_active, w.att,
-                               inner, s);
+    launch_dec_cross_attention(w.qkv, inner, w.ckv, ldckv, 2 * i * inner, (2 * i + 1) * inner, nb, H, table, M, w.att, inner,
+                               s);
     if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.co, D, inner, w.x, D, s))) return st;
     // gated-GELU FFN (T5LayerFF / T5DenseGatedActDense)
     hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_ff, w.h, D, eps, 1.f);
     if ((st = launch_dec_gemm<EPI_GEGLU>(w.h, D, M, l.wi, F, D, ffn, F, s))) return st;
     if ((st = launch_dec_gemm<EPI_RESID>(ffn, F, M, l.wo2, D, F, w.x, D, s))) return st;
   }
-  const float scale = d->tied ? 1.f / sqrtf((float)D) : 1.f;
-  hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, d->final_ln, w.h, D, eps, scale);
-  if ((st = launch_dec_gemm<EPI_F32>(w.h, D, M, d->lm_head, V, D, logprobs, V, s))) return st;
-  hipLaunchKernelGGL(dec_log_softmax_kernel, dim3(M), dim3(256), 0, s, logprobs, V);
+  if (logprobs) {
+    const float scale = d->tied ? 1.f / sqrtf((float)D) : 1.f;
+    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, d->final_ln, w.h, D, eps, scale);
+    if ((st = launch_dec_gemm<EPI_F32>(w.h, D, M, d->lm_head, V, D, logprobs, V, s))) return st;
+    hipLaunchKernelGGL(dec_log_softmax_kernel, dim3(M), dim3(256), 0, s, logprobs, V);
+  }
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
 
-// the caps of a slot pool: dec_check's, with every slot's source region src_cap rows long
-RpStatus pool_check(const RpDecoder* d, int n_slots, int nb, int max_len, int src_cap) {
-  RP_REQUIRE(d, "null decoder");
-  RP_REQUIRE(n_slots >= 1 && n_slots <= DEC_MAX_STATES, "slots=%d (1..%d)", n_slots, DEC_MAX_STATES);
-  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "num_beams=%d (1..%d)", nb, DEC_MAX_BEAMS);
-  RP_REQUIRE(n_slots * nb <= DEC_MAX_ROWS, "rows = slots * num_beams = %d > %d", n_slots * nb, DEC_MAX_ROWS);
-  RP_REQUIRE(max_len >= 1 && max_len <= DEC_MAX_KEYS, "max_len=%d (1..%d)", max_len, DEC_MAX_KEYS);
-  RP_REQUIRE(src_cap >= 1 && src_cap <= DEC_MAX_KEYS, "src_cap=%d (1..%d)", src_cap, DEC_MAX_KEYS);
-  return RP_OK;
+// One decode step over a checked geometry: the one routine behind rp_decoder_batch_step (pos null: every listed state at
+// t), rp_decoder_batch_step_pos (state active[a] at pos[a]) and rp_decoder_pool_step (src_len[a] rows of slot active[a]'s
+// region in use).  `what` is what the list names, "state" or "slot".
+RpStatus dec_step(RpDecoder* d, const DecGeom& g, const char* what, const int32_t* active, int n_active, const int32_t* pos,
+                  int t, const int32_t* src_len, const int32_t* tokens, const int32_t* anc, int astride, int nb,
+                  int max_len, float* logprobs, void* ws, size_t ws_bytes, void* stream_) {
+  RP_REQUIRE(n_active >= 1 && n_active <= g.n, "active %ss=%d (1..%ss=%d)", what, n_active, what, g.n);
+  if (!pos) {  // all states started together
+    RP_REQUIRE(t >= 0 && t < max_len, "t=%d outside [0, max_len=%d)", t, max_len);
+    RP_REQUIRE(astride >= t + 1, "anc_stride=%d < t + 1 = %d", astride, t + 1);
+  }
+  DecSlots slots = {};
+  DecWs w;
+  RpStatus st = dec_list(active, n_active, g.n, "active", what, [&](int a, int id) -> RpStatus {
+    if (pos) {
+      RP_REQUIRE(pos[a] >= 0 && pos[a] < max_len, "pos[%d]=%d outside [0, max_len=%d)", a, pos[a], max_len);
+      if (src_len) RP_REQUIRE(src_len[a] >= 1 && src_len[a] <= g.len[id], "src_len[%d]=%d (1..src_cap=%d)", a, src_len[a], g.len[id]);
+      RP_REQUIRE(astride >= pos[a] + 1, "anc_stride=%d < pos[%d] + 1 = %d", astride, a, pos[a] + 1);
+    }
+    slots.state[a] = id;
+    slots.src_off[a] = g.off[id];
+    slots.src_len[a] = src_len ? src_len[a] : g.len[id];
+    slots.pos[a] = pos ? pos[a] : t;
+    return RP_OK;
+  });
+  if (st || (st = dec_workspace(d, g, nb, max_len, ws, ws_bytes, w))) return st;
+  return dec_layers_launch(d, w, slots, n_active * nb, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
 }
 }  // namespace
 
@@ -1188,60 +1266,55 @@ extern "C" RpStatus rp_decoder_batch_step(RpDecoder* d, const int32_t* src_cu, i
                                           int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
                                           int32_t nb, int32_t t, int32_t max_len, float* logprobs, void* ws,
                                           size_t ws_bytes, void* stream_) {
-  int total = 0;
-  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
+  DecGeom g;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, g);
   if (st) return st;
   RP_REQUIRE(active && tokens && anc && logprobs, "null argument");
-  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
-  RP_REQUIRE(t >= 0 && t < max_len, "t=%d outside [0, max_len=%d)", t, max_len);
-  RP_REQUIRE(astride >= t + 1, "anc_stride=%d < t + 1 = %d", astride, t + 1);
-  DecSlots slots = {};
-  uint32_t seen = 0;
-  for (int a = 0; a < n_active; ++a) {
-    const int sidx = active[a];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share cache rows
-    seen |= 1u << sidx;
-    slots.state[a] = sidx;
-    slots.src_off[a] = src_cu[sidx];
-    slots.src_len[a] = src_cu[sidx + 1] - src_cu[sidx];
-    slots.pos[a] = t;  // all states started together
-  }
-  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
-  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
-  return dec_step_launch(d, w, slots, n_active, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
+  return dec_step(d, g, "state", active, n_active, nullptr, t, nullptr, tokens, anc, astride, nb, max_len, logprobs, ws,
+                  ws_bytes, stream_);
+}
+
+// rp_decoder_batch_step with a position per listed state (the lockstep loop over states whose prompts differ in length)
+extern "C" RpStatus rp_decoder_batch_step_pos(RpDecoder* d, const int32_t* src_cu, int32_t n, const int32_t* active,
+                                              int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
+                                              int32_t nb, const int32_t* pos, int32_t max_len, float* logprobs, void* ws,
+                                              size_t ws_bytes, void* stream_) {
+  DecGeom g;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, g);
+  if (st) return st;
+  RP_REQUIRE(active && pos && tokens && anc && logprobs, "null argument");
+  return dec_step(d, g, "state", active, n_active, pos, 0, nullptr, tokens, anc, astride, nb, max_len, logprobs, ws, ws_bytes,
+                  stream_);
 }
 
 // ---- the slot pool: states that join a running search between steps ("Continuous batching") ---------
 extern "C" size_t rp_decoder_pool_workspace_bytes(const RpDecoder* d, int32_t n_slots, int32_t nb, int32_t max_len,
                                                   int32_t src_cap) {
-  if (pool_check(d, n_slots, nb, max_len, src_cap) != RP_OK) return 0;
-  return dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, nullptr).bytes;
+  DecGeom g;
+  if (pool_check(d, n_slots, nb, max_len, src_cap, g) != RP_OK) return 0;
+  return dec_carve(d, g.n, g.total_src, nb, max_len, nullptr).bytes;
 }
 
 extern "C" RpStatus rp_decoder_pool_admit(RpDecoder* d, int32_t n_slots, int32_t nb, int32_t max_len, int32_t src_cap,
                                           const int32_t* slot_ids, const void* enc, const int32_t* src_cu, int32_t m,
                                           void* ws, size_t ws_bytes, void* stream_) {
-  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap);
+  DecGeom g;
+  DecWs w;
+  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap, g);
   if (st) return st;
   RP_REQUIRE(slot_ids && enc && src_cu && ws, "null argument");
   RP_REQUIRE(m >= 1 && m <= n_slots, "admitted sources=%d (1..slots=%d)", m, n_slots);
   RP_REQUIRE(src_cu[0] == 0, "src_cu[0]=%d, not 0", src_cu[0]);
-  uint32_t seen = 0;
-  for (int j = 0; j < m; ++j) {
-    const int sl = slot_ids[j];
+  st = dec_list(slot_ids, m, n_slots, "slots", "slot", [&](int j, int) -> RpStatus {
     const int64_t S = (int64_t)src_cu[j + 1] - src_cu[j];
-    RP_REQUIRE(sl >= 0 && sl < n_slots, "slots[%d]=%d outside [0, slots=%d)", j, sl, n_slots);
-    RP_REQUIRE(!(seen & (1u << sl)), "slots[%d]=%d names a slot twice", j, sl);
-    seen |= 1u << sl;
     RP_REQUIRE(S >= 1 && S <= src_cap, "src_len of source %d = %lld (1..src_cap=%d)", j, (long long)S, src_cap);
-  }
-  const DecWs w = dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, (char*)ws);
-  if (ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
+    return RP_OK;
+  });
+  if (st || (st = dec_workspace(d, g, nb, max_len, ws, ws_bytes, w))) return st;
   const int D = d->cfg.d_model, NKV = d->cfg.num_layers * 2 * d->inner;
   for (int j = 0; j < m; ++j)  // one GEMM per newcomer, into its slot's region (a row depends on no other row)
     if ((st = launch_dec_gemm<EPI_BF16>((const bf16_t*)enc + (size_t)src_cu[j] * D, D, src_cu[j + 1] - src_cu[j],
-                                        d->cross_kv_w, NKV, D, w.ckv + (size_t)slot_ids[j] * src_cap * NKV, NKV,
+                                        d->cross_kv_w, NKV, D, w.ckv + (size_t)g.off[slot_ids[j]] * NKV, NKV,
                                         (hipStream_t)stream_)))
       return st;
   return RP_OK;
@@ -1251,58 +1324,12 @@ extern "C" RpStatus rp_decoder_pool_step(RpDecoder* d, int32_t n_slots, int32_t 
                                          const int32_t* active, const int32_t* pos, const int32_t* src_len,
                                          int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
                                          float* logprobs, void* ws, size_t ws_bytes, void* stream_) {
-  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap);
+  DecGeom g;
+  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap, g);
   if (st) return st;
   RP_REQUIRE(active && pos && src_len && tokens && anc && logprobs && ws, "null argument");
-  RP_REQUIRE(n_active >= 1 && n_active <= n_slots, "active slots=%d (1..slots=%d)", n_active, n_slots);
-  DecSlots slots = {};
-  uint32_t seen = 0;
-  for (int a = 0; a < n_active; ++a) {
-    const int sl = active[a];
-    RP_REQUIRE(sl >= 0 && sl < n_slots, "active[%d]=%d outside [0, slots=%d)", a, sl, n_slots);
-    RP_REQUIRE(!(seen & (1u << sl)), "active[%d]=%d names a slot twice", a, sl);  // two rows would share cache rows
-    seen |= 1u << sl;
-    RP_REQUIRE(pos[a] >= 0 && pos[a] < max_len, "pos[%d]=%d outside [0, max_len=%d)", a, pos[a], max_len);
-    RP_REQUIRE(src_len[a] >= 1 && src_len[a] <= src_cap, "src_len[%d]=%d (1..src_cap=%d)", a, src_len[a], src_cap);
-    RP_REQUIRE(astride >= pos[a] + 1, "anc_stride=%d < pos[%d] + 1 = %d", astride, a, pos[a] + 1);
-    slots.state[a] = sl;
-    slots.src_off[a] = sl * src_cap;
-    slots.src_len[a] = src_len[a];
-    slots.pos[a] = pos[a];
-  }
-  const DecWs w = dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, (char*)ws);
-  if (ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
-  return dec_step_launch(d, w, slots, n_active, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
-}
-
-// rp_decoder_batch_step with a position per listed state: dec_step_launch's third caller (the lockstep loop over states
-// whose prompts differ in length)
-extern "C" RpStatus rp_decoder_batch_step_pos(RpDecoder* d, const int32_t* src_cu, int32_t n, const int32_t* active,
-                                              int32_t n_active, const int32_t* tokens, const int32_t* anc, int32_t astride,
-                                              int32_t nb, const int32_t* pos, int32_t max_len, float* logprobs, void* ws,
-                                              size_t ws_bytes, void* stream_) {
-  int total = 0;
-  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
-  if (st) return st;
-  RP_REQUIRE(active && pos && tokens && anc && logprobs, "null argument");
-  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
-  DecSlots slots = {};
-  uint32_t seen = 0;
-  for (int a = 0; a < n_active; ++a) {
-    const int sidx = active[a];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);
-    seen |= 1u << sidx;
-    RP_REQUIRE(pos[a] >= 0 && pos[a] < max_len, "pos[%d]=%d outside [0, max_len=%d)", a, pos[a], max_len);
-    RP_REQUIRE(astride >= pos[a] + 1, "anc_stride=%d < pos[%d] + 1 = %d", astride, a, pos[a] + 1);
-    slots.state[a] = sidx;
-    slots.src_off[a] = src_cu[sidx];
-    slots.src_len[a] = src_cu[sidx + 1] - src_cu[sidx];
-    slots.pos[a] = pos[a];
-  }
-  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
-  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
-  return dec_step_launch(d, w, slots, n_active, tokens, anc, astride, nb, max_len, logprobs, (hipStream_t)stream_);
+  return dec_step(d, g, "slot", active, n_active, pos, 0, src_len, tokens, anc, astride, nb, max_len, logprobs, ws, ws_bytes,
+                  stream_);
 }
 
 // ---- prompt prefill: the prompt rows of the listed states through the layers, all positions in one launch sequence --------
@@ -1311,54 +1338,14 @@ struct PrefillState {
   int state, src_off, src_len, rows;
 };
 
-// One pass: M <= the activation block's rows, rows in segment order, tokens[row] their tokens.  The step's sequence per
-// layer with the segment kernels in place of the slot kernels; all rows' K/V are stored before the self-attention reads
-// them.  The last layer ends at its cache store: nothing after it reaches the cache, and there is no lm_head.
-RpStatus dec_prefill_pass(RpDecoder* d, const DecWs& w, const DecSegs& segs, int M, int max_keys, const int32_t* tokens,
-                          const int32_t* anc, int nb, int max_len, hipStream_t s) {
-  RpStatus st;
-  const RpT5Config& c = d->cfg;
-  const int D = c.d_model, F = c.d_ff, inner = d->inner, H = c.num_heads, V = c.vocab_size, L = c.num_layers;
-  const float eps = c.layer_norm_eps;
-  const int rows = max_len * nb, ldckv = L * 2 * inner;
-  const size_t layer_stride = (size_t)rows * 2 * inner, state_stride = (size_t)L * layer_stride;
-  bf16_t* ffn = w.h + (size_t)M * D;
-  int max_src = 0;
-  for (int g = 0; g < segs.n; ++g) max_src = std::max(max_src, segs.src_len[g]);
-  hipLaunchKernelGGL(dec_embed_kernel, dim3(M), dim3(256), 0, s, tokens, d->embed, w.x, D, V);
-  for (int i = 0; i < L; ++i) {
-    const RpDecoder::Layer& l = d->layers[i];
-    bf16_t* cache = w.cache + (size_t)i * layer_stride;
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_self, w.h, D, eps, 1.f);
-    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.wqkv, 3 * inner, D, w.qkv, 3 * inner, s))) return st;
-    hipLaunchKernelGGL(dec_prefill_store_kv_kernel, dim3(M), dim3(256), 0, s, w.qkv, inner, cache, state_stride, nb, segs);
-    if (i == L - 1) break;
-    hipLaunchKernelGGL((dec_prefill_attention_kernel<false>), dim3(H, M), dim3(256), max_keys * sizeof(float), s, w.qkv,
-                       3 * inner, cache, 2 * inner, 0, inner, rows, state_stride, anc, d->bias_tab, d->nbias, segs, w.att,
-                       inner);
-    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.wo, D, inner, w.x, D, s))) return st;
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_cross, w.h, D, eps, 1.f);
-    if ((st = launch_dec_gemm<EPI_BF16>(w.h, D, M, l.cq, inner, D, w.qkv, inner, s))) return st;
-    hipLaunchKernelGGL((dec_prefill_attention_kernel<true>), dim3(H, M), dim3(256), max_src * sizeof(float), s, w.qkv, inner,
-                       w.ckv, ldckv, 2 * i * inner, (2 * i + 1) * inner, 0, (size_t)0, (const int32_t*)nullptr,
-                       (const float*)nullptr, 1, segs, w.att, inner);
-    if ((st = launch_dec_gemm<EPI_RESID>(w.att, inner, M, l.co, D, inner, w.x, D, s))) return st;
-    hipLaunchKernelGGL(dec_rmsnorm_kernel, dim3(M), dim3(256), 0, s, w.x, l.ln_ff, w.h, D, eps, 1.f);
-    if ((st = launch_dec_gemm<EPI_GEGLU>(w.h, D, M, l.wi, F, D, ffn, F, s))) return st;
-    if ((st = launch_dec_gemm<EPI_RESID>(ffn, F, M, l.wo2, D, F, w.x, D, s))) return st;
-  }
-  RP_CHECK_LAUNCH();
-  return RP_OK;
-}
-
-// The one routine behind rp_decoder_batch_prefill and rp_decoder_pool_prefill.  The prompt rows, state after state and
-// position after position (the order of `tokens`), are cut into passes of at most `cap` rows - the activation block's -
-// so a state's lower positions are stored, in every layer, before a later pass attends over them.
+// The prompt rows, state after state and position after position (the order of `tokens`), are cut into passes of at most
+// `cap` rows - the activation block's - so a state's lower positions are stored, in every layer, before a later pass
+// attends over them.  A pass is dec_layers_launch over its segments, without log-probs.
 RpStatus dec_prefill_launch(RpDecoder* d, const DecWs& w, const PrefillState* ps, int m, const int32_t* tokens,
                             const int32_t* anc, int nb, int max_len, int cap, hipStream_t s) {
   RpStatus st;
   DecSegs segs = {};
-  int used = 0, first = 0, max_keys = 0, row = 0;
+  int used = 0, first = 0, row = 0;
   for (int j = 0; j < m; ++j) {
     int p = 0;
     while (p < ps[j].rows) {
@@ -1372,11 +1359,10 @@ RpStatus dec_prefill_launch(RpDecoder* d, const DecWs& w, const PrefillState* ps
       used += take;
       p += take;
       row += take;
-      max_keys = std::max(max_keys, p);
       if (used == cap || (j == m - 1 && p == ps[j].rows)) {
-        if ((st = dec_prefill_pass(d, w, segs, used, max_keys, tokens + first, anc, nb, max_len, s))) return st;
+        if ((st = dec_layers_launch(d, w, segs, used, tokens + first, anc, 0, nb, max_len, nullptr, s))) return st;
         first = row;
-        used = max_keys = 0;
+        used = 0;
         segs = DecSegs{};
       }
     }
@@ -1384,8 +1370,12 @@ RpStatus dec_prefill_launch(RpDecoder* d, const DecWs& w, const PrefillState* ps
   return RP_OK;
 }
 
-// what both prefill entries check of the prompts: prompt_cu[0] = 0, 1 <= R_j, R_j + 1 < max_len, anc_len >= every R_j
-RpStatus prefill_check(const int32_t* prompt_cu, int m, int max_len, int anc_len) {
+// The one routine behind rp_decoder_batch_prefill and rp_decoder_pool_prefill (src_len: the rows of each listed slot's
+// region in use): prompt_cu[0] = 0, 1 <= R_j, R_j + 1 < max_len, anc_len >= every R_j, then the list.
+RpStatus dec_prefill(RpDecoder* d, const DecGeom& g, const char* list, const char* what, const int32_t* ids,
+                     const int32_t* src_len, const int32_t* prompt_cu, int m, const int32_t* tokens, const int32_t* anc,
+                     int anc_len, int nb, int max_len, void* ws, size_t ws_bytes, void* stream_) {
+  RP_REQUIRE(m >= 1 && m <= g.n, "listed %ss=%d (1..%ss=%d)", what, m, what, g.n);
   RP_REQUIRE(prompt_cu[0] == 0, "prompt_cu[0]=%d, not 0", prompt_cu[0]);
   for (int j = 0; j < m; ++j) {
     const int64_t R = (int64_t)prompt_cu[j + 1] - prompt_cu[j];
@@ -1393,7 +1383,15 @@ RpStatus prefill_check(const int32_t* prompt_cu, int m, int max_len, int anc_len
     RP_REQUIRE(R + 1 < max_len, "prompt %d: %lld rows + 1 >= max_len=%d", j, (long long)R, max_len);
     RP_REQUIRE(anc_len >= R, "anc_len=%d < the %lld rows of prompt %d", anc_len, (long long)R, j);
   }
-  return RP_OK;
+  PrefillState ps[DEC_MAX_STATES];
+  DecWs w;
+  RpStatus st = dec_list(ids, m, g.n, list, what, [&](int j, int id) -> RpStatus {
+    if (src_len) RP_REQUIRE(src_len[j] >= 1 && src_len[j] <= g.len[id], "src_len[%d]=%d (1..src_cap=%d)", j, src_len[j], g.len[id]);
+    ps[j] = PrefillState{id, g.off[id], src_len ? src_len[j] : g.len[id], prompt_cu[j + 1] - prompt_cu[j]};
+    return RP_OK;
+  });
+  if (st || (st = dec_workspace(d, g, nb, max_len, ws, ws_bytes, w))) return st;
+  return dec_prefill_launch(d, w, ps, m, tokens, anc, nb, max_len, g.n * nb, (hipStream_t)stream_);
 }
 }  // namespace
 
@@ -1401,52 +1399,28 @@ extern "C" RpStatus rp_decoder_batch_prefill(RpDecoder* d, const int32_t* src_cu
                                              const int32_t* prompt_cu, int32_t m, const int32_t* tokens,
                                              const int32_t* anc, int32_t anc_len, int32_t nb, int32_t max_len, void* ws,
                                              size_t ws_bytes, void* stream_) {
-  int total = 0;
-  RpStatus st = dec_check(d, src_cu, n, nb, max_len, total);
+  DecGeom g;
+  RpStatus st = dec_check(d, src_cu, n, nb, max_len, g);
   if (st) return st;
   RP_REQUIRE(states && prompt_cu && tokens && anc, "null argument");
-  RP_REQUIRE(m >= 1 && m <= n, "listed states=%d (1..states=%d)", m, n);
-  if ((st = prefill_check(prompt_cu, m, max_len, anc_len))) return st;
-  PrefillState ps[DEC_MAX_STATES];
-  uint32_t seen = 0;
-  for (int j = 0; j < m; ++j) {
-    const int sidx = states[j];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "states[%d]=%d outside [0, states=%d)", j, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "states[%d]=%d names a state twice", j, sidx);
-    seen |= 1u << sidx;
-    ps[j] = PrefillState{sidx, src_cu[sidx], src_cu[sidx + 1] - src_cu[sidx], prompt_cu[j + 1] - prompt_cu[j]};
-  }
-  const DecWs w = dec_carve(d, n, total, nb, max_len, (char*)ws);
-  if (!ws || ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
-  return dec_prefill_launch(d, w, ps, m, tokens, anc, nb, max_len, n * nb, (hipStream_t)stream_);
+  return dec_prefill(d, g, "states", "state", states, nullptr, prompt_cu, m, tokens, anc, anc_len, nb, max_len, ws, ws_bytes,
+                     stream_);
 }
 
 extern "C" RpStatus rp_decoder_pool_prefill(RpDecoder* d, int32_t n_slots, int32_t nb, int32_t max_len, int32_t src_cap,
                                             const int32_t* slot_ids, const int32_t* src_len, const int32_t* prompt_cu,
                                             int32_t m, const int32_t* tokens, const int32_t* anc, int32_t anc_len,
                                             void* ws, size_t ws_bytes, void* stream_) {
-  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap);
+  DecGeom g;
+  RpStatus st = pool_check(d, n_slots, nb, max_len, src_cap, g);
   if (st) return st;
   RP_REQUIRE(slot_ids && src_len && prompt_cu && tokens && anc && ws, "null argument");
-  RP_REQUIRE(m >= 1 && m <= n_slots, "listed slots=%d (1..slots=%d)", m, n_slots);
-  if ((st = prefill_check(prompt_cu, m, max_len, anc_len))) return st;
-  PrefillState ps[DEC_MAX_STATES];
-  uint32_t seen = 0;
-  for (int j = 0; j < m; ++j) {
-    const int sl = slot_ids[j];
-    RP_REQUIRE(sl >= 0 && sl < n_slots, "slots[%d]=%d outside [0, slots=%d)", j, sl, n_slots);
-    RP_REQUIRE(!(seen & (1u << sl)), "slots[%d]=%d names a slot twice", j, sl);
-    seen |= 1u << sl;
-    RP_REQUIRE(src_len[j] >= 1 && src_len[j] <= src_cap, "src_len[%d]=%d (1..src_cap=%d)", j, src_len[j], src_cap);
-    ps[j] = PrefillState{sl, sl * src_cap, src_len[j], prompt_cu[j + 1] - prompt_cu[j]};
-  }
-  const DecWs w = dec_carve(d, n_slots, n_slots * src_cap, nb, max_len, (char*)ws);
-  if (ws_bytes < w.bytes) return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", ws_bytes, w.bytes);
-  return dec_prefill_launch(d, w, ps, m, tokens, anc, nb, max_len, n_slots * nb, (hipStream_t)stream_);
+  return dec_prefill(d, g, "slots", "slot", slot_ids, src_len, prompt_cu, m, tokens, anc, anc_len, nb, max_len, ws, ws_bytes,
+                     stream_);
 }
 
 // ---- the decode step's kernels one at a time (test-only: tests/test_decode_step_kernels_gpu.py) ---------------------------
-// Device pointers in, launch-only on the given stream, through the launch code dec_step_launch runs.
+// Device pointers in, launch-only on the given stream, through the launch code dec_layers_launch runs.
 extern "C" RpStatus rp_dbg_dec_gemm(int32_t epi, const void* A, int32_t lda, int32_t M, const void* W, int32_t N, int32_t K,
                                     void* out, int32_t ldo, void* stream_) {
   RP_REQUIRE(A && W && out, "null argument");
@@ -1474,16 +1448,12 @@ RpStatus dbg_slots(DecSlots& slots, const int32_t* state, const int32_t* pos, in
   RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "num_beams=%d (1..%d)", nb, DEC_MAX_BEAMS);
   RP_REQUIRE(n_active * nb <= DEC_MAX_ROWS, "rows = slots * num_beams = %d > %d", n_active * nb, DEC_MAX_ROWS);
   RP_REQUIRE(max_len >= 1 && max_len <= DEC_MAX_KEYS, "max_len=%d (1..%d)", max_len, DEC_MAX_KEYS);
-  uint32_t seen = 0;
-  for (int a = 0; a < n_active; ++a) {
-    RP_REQUIRE(state[a] >= 0 && state[a] < n_states, "state[%d]=%d outside [0, states=%d)", a, state[a], n_states);
-    RP_REQUIRE(!(seen & (1u << state[a])), "state[%d]=%d names a state twice", a, state[a]);
-    seen |= 1u << state[a];
+  return dec_list(state, n_active, n_states, "state", "state", [&](int a, int id) -> RpStatus {
     RP_REQUIRE(pos[a] >= 0 && pos[a] < max_len, "pos[%d]=%d outside [0, max_len=%d)", a, pos[a], max_len);
-    slots.state[a] = state[a];
+    slots.state[a] = id;
     slots.pos[a] = pos[a];
-  }
-  return RP_OK;
+    return RP_OK;
+  });
 }
 }  // namespace
 
@@ -1519,7 +1489,7 @@ extern "C" RpStatus rp_dbg_dec_rows(int32_t mode, const void* a, const void* b, 
       if (st) return st;
       RP_REQUIRE(a && state_stride >= (int64_t)max_len * nb * 2 * n, "store_kv: state_stride=%lld < max_len * nb * 2 * inner",
                  (long long)state_stride);
-      hipLaunchKernelGGL(dec_store_kv_kernel, dim3(n_active * nb), dim3(256), 0, s, (const bf16_t*)a, n, (bf16_t*)o0,
+      hipLaunchKernelGGL(dec_store_kv_kernel<DecSlots>, dim3(n_active * nb), dim3(256), 0, s, (const bf16_t*)a, n, (bf16_t*)o0,
                          (size_t)state_stride, nb, slots);
       break;
     }
@@ -1559,8 +1529,8 @@ extern "C" RpStatus rp_dbg_dec_attention(int32_t cross, const void* q, int32_t l
       slots.src_off[a] = src_off[a];
       slots.src_len[a] = src_len[a];
     }
-    launch_dec_cross_attention((const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, koff, voff, nb, H, slots, n_active, (bf16_t*)out,
-                               ldo, s);
+    launch_dec_cross_attention((const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, koff, voff, nb, H, slots, n_active * nb,
+                               (bf16_t*)out, ldo, s);
   } else {
     RP_REQUIRE(anc && tab && nbias >= 1, "self-attention: null ancestry / bias table");
     RP_REQUIRE(rows == max_len * nb && state_stride >= (int64_t)rows * ldkv && state_stride % 8 == 0,
@@ -1568,7 +1538,7 @@ extern "C" RpStatus rp_dbg_dec_attention(int32_t cross, const void* q, int32_t l
     for (int a = 0; a < n_active; ++a)
       RP_REQUIRE(astride >= pos[a] + 1, "anc_stride=%d < pos[%d] + 1 = %d", astride, a, pos[a] + 1);
     launch_dec_self_attention((const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, koff, voff, rows, (size_t)state_stride, anc,
-                              astride, tab, nbias, nb, H, slots, n_active, (bf16_t*)out, ldo, s);
+                              astride, tab, nbias, nb, H, slots, n_active * nb, (bf16_t*)out, ldo, s);
   }
   RP_CHECK_LAUNCH();
   return RP_OK;
@@ -1601,17 +1571,13 @@ namespace {
 // The slot list of a books launch: active[a] distinct and in [0, n), slot a at position pos[a] (null: t for all).
 RpStatus books_slots(DecSlots* slots, const int32_t* active, const int32_t* pos, int t, int n_active, int n, int max_len) {
   RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
-  uint32_t seen = 0;
-  for (int a = 0; a < n_active; ++a) {
-    const int sidx = active[a], p = pos ? pos[a] : t;
-    RP_REQUIRE(sidx >= 0 && sidx < n, "active[%d]=%d outside [0, states=%d)", a, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "active[%d]=%d names a state twice", a, sidx);  // two slots would share books
+  return dec_list(active, n_active, n, "active", "state", [&](int a, int id) -> RpStatus {
+    const int p = pos ? pos[a] : t;
     RP_REQUIRE(p >= 0 && p + 1 < max_len, "pos[%d]=%d: position pos + 1 outside [1, max_len=%d)", a, p, max_len);
-    seen |= 1u << sidx;
-    slots->state[a] = sidx;
+    slots->state[a] = id;
     slots->pos[a] = p;
-  }
-  return RP_OK;
+    return RP_OK;
+  });
 }
 
 // the caps the sampler's entry points share; `listed` = the states the call names (active, or admitted)
@@ -1666,17 +1632,14 @@ RpStatus sample_admit_launch(const int32_t* states, const uint32_t* new_seeds, c
   DecSlots slots = {};
   SampleSeeds fresh = {};
   SampleLive live = {};
-  uint32_t seen = 0;
-  for (int j = 0; j < m; ++j) {
-    const int sidx = states[j];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "states[%d]=%d outside [0, states=%d)", j, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "states[%d]=%d names a state twice", j, sidx);
+  st = dec_list(states, m, n, "states", "state", [&](int j, int id) -> RpStatus {
     if (live_rows) RP_REQUIRE(n_live[j] >= 1 && n_live[j] <= nb, "n_live[%d]=%d outside 1..nb=%d", j, n_live[j], nb);
-    seen |= 1u << sidx;
-    slots.state[j] = sidx;
+    slots.state[j] = id;
     fresh.seed[j] = new_seeds[j];
     live.n_live[j] = live_rows ? n_live[j] : nb;
-  }
+    return RP_OK;
+  });
+  if (st) return st;
   hipLaunchKernelGGL(sample_admit_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream_, slots, fresh, live, nb, max_len,
                      start_token, pad, seeds, seq, cum_logprob, n_generated, finished);
   RP_CHECK_LAUNCH();
@@ -1834,14 +1797,11 @@ extern "C" RpStatus rp_beam_books_admit(void* books, size_t bytes, int32_t n, in
   RP_REQUIRE(books && states, "null argument");
   RP_REQUIRE(m >= 1 && m <= n, "admitted states=%d (1..states=%d)", m, n);
   DecSlots slots = {};
-  uint32_t seen = 0;
-  for (int j = 0; j < m; ++j) {
-    const int sidx = states[j];
-    RP_REQUIRE(sidx >= 0 && sidx < n, "states[%d]=%d outside [0, states=%d)", j, sidx, n);
-    RP_REQUIRE(!(seen & (1u << sidx)), "states[%d]=%d names a state twice", j, sidx);
-    seen |= 1u << sidx;
-    slots.state[j] = sidx;
-  }
+  st = dec_list(states, m, n, "states", "state", [&](int j, int id) -> RpStatus {
+    slots.state[j] = id;
+    return RP_OK;
+  });
+  if (st) return st;
   const BeamBooks bk = books_carve((char*)books, n, nb, max_len);
   RP_REQUIRE(bytes >= bk.bytes, "books %zu < required %zu bytes", bytes, bk.bytes);
   hipLaunchKernelGGL(beam_books_admit_kernel, dim3(m), dim3(256), 0, (hipStream_t)stream_, bk, n, nb, max_len, slots, eos,

@@ -21,7 +21,7 @@ for line in r.stderr.splitlines():
         cur[k.split(" ")[0] if "Spill" not in k else k] = v
 names = subprocess.run(["c++filt"], input="\n".join(x["name"] for x in rows), capture_output=True, text=True).stdout.splitlines()
 for x, n in zip(rows, names):
-    n = re.sub(r"\(.*", "", n).replace("rp::", "")
+    n = re.sub(r"\(.*", "", n.replace("(anonymous namespace)::", "")).replace("rp::", "")
     if flt and flt not in n:
         continue
     print(f'{n[:150]:150s} v{x.get("VGPRs","?"):>4} a{x.get("AGPRs","?"):>4} s{x.get("SGPRs","?"):>4} scratch{x.get("ScratchSize","?"):>5} occ{x.get("Occupancy","?"):>2}')
