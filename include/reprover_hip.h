@@ -458,6 +458,36 @@ RpStatus rp_dbg_rowscale(const float* ssp /* [np, rows] */, float* rs /* [rows] 
 RpStatus rp_dbg_attention(const void* qkv_bf16, const int32_t* cu_seqlens, const float* bias_tab,
                           void* out_bf16, int32_t batch, int32_t max_len, int32_t num_heads,
                           int32_t rows_total, void* stream);
+/* The encoder's forward kernels in isolation with every launch option reachable (tests/test_encoder_forward_kernels_gpu.py).
+ * Each runs the launch code of the encoder pass; arguments are checked before anything is launched (RP_E_INVALID, nothing
+ * written); no output is zeroed first.
+ *   rp_dbg_gemm_ex: rp_dbg_gemm_fused with the operands' geometry free: A bf16 [M, lda] (lda % 8 == 0), W bf16 [n_rows_w, K] (exactly that many
+ *     rows: the operand's row clamp serves the last feature tile), out with leading dimension ldo (RESID: planes [2, M, ldo];
+ *     RESID8: bf16 plane [M, ldo] then byte plane [M, ldo]; GEGLU: [M, ldo], n_valid / 2 columns written), the first n_valid
+ *     features written.  tokens_valid (0: all M) and t_dev (device int32 or NULL) as encode_pass passes them; prof_class one
+ *     of RP_K_GEMM_QKV / O / WI / WO (the class's tile and launch-form options apply).  rs_form 0: no row scale; 1: rs_buf
+ *     f32 [M] = rowscale_kernel(ssp_in [np_in, M]), then the RowScale epilogue; 2: the RowScaleFromSlots epilogue on ssp_in
+ *     (STORE / GEGLU on the small tiles only).  ssp_out f32 [np_out, M] (RESID / RESID8, optional).  plan: HOST int32 [6] =
+ *     what was launched: tile configuration, form (0 one workgroup per tile, 1 persistent, 2 mixed full + half tiles),
+ *     feature tiles, token tiles, prefetch helpers, full token rows of the mixed plan.
+ *   rp_dbg_attention_ex: rp_dbg_attention with the table's max_distance (bias_tab f32 [H, ntab], ntab = 2 max_distance + 1;
+ *     refused when the table with its padding exceeds the kernel's, as rp_encoder_create refuses it).
+ *   rp_dbg_encoder_rows (launch only): mode 0 the embedding table into the 24-bit form (a = table f32 [vocab, n]; o0 bf16
+ *     [vocab, n], o1 u8 [vocab, n], o2 f32 [vocab]); mode 1 the pass's embedding rows (a / b / c = mode 0's outputs, ia = ids
+ *     [T], rows = Tp, a multiple of 256; o0 bf16 [Tp, n], o1 u8 [Tp, n], and o3 = rs f32 [Tp] when given, else o2 = ssp f32
+ *     [np, Tp]; the kernel form by n <= 1536 and Tp < 8192 as the pass picks it); mode 2 the last_hidden_state rows (a / b =
+ *     planes [rows, n], c = rs [rows], d = final norm weight f32 [n]; o0 bf16 [rows, n]). */
+RpStatus rp_dbg_gemm_ex(const void* A, int32_t lda, const void* W, int32_t n_rows_w, void* out, int32_t ldo, int32_t M, int32_t K,
+                        int32_t n_valid, int32_t epilogue, int32_t prof_class, int32_t tokens_valid, const int32_t* t_dev,
+                        int32_t rs_form, const float* ssp_in, int32_t np_in, float inv_d, float eps, float* rs_buf, float* ssp_out,
+                        int32_t np_out, int32_t* plan, void* stream);
+/* The current value of an option rp_set_option knows by a variable of its own (not the compound gemm_variant_all). */
+RpStatus rp_dbg_get_option(const char* name, int32_t* value);
+RpStatus rp_dbg_attention_ex(const void* qkv_bf16, const int32_t* cu_seqlens, const float* bias_tab, void* out_bf16, int32_t batch,
+                             int32_t num_heads, int32_t rows_total, int32_t max_distance, int32_t ntab, void* stream);
+RpStatus rp_dbg_encoder_rows(int32_t mode, const void* a, const void* b, const void* c, const void* d, const int32_t* ia,
+                             const int32_t* t_dev, int32_t T, int32_t rows, int32_t n, int32_t vocab, int32_t np, float inv_d,
+                             float eps, void* o0, void* o1, void* o2, void* o3, void* stream);
 /* Training kernels in isolation (tests/test_train_kernels_gpu.py).
  *   rp_dbg_wgrad: out f32 [|splits|, ny, nx], partial s = Y[rows of split s]^T X;  Y bf16 [T, ny], X bf16 [T, nx], T % 64 == 0;
  *     splits > 0: 256 x 256 tiles, splits < 0: 128 x 128 tiles.

@@ -296,6 +296,22 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
          C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
     ),
+    "rp_dbg_gemm_ex": (
+        C.c_int32,
+        [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+         C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32,
+         C.POINTER(C.c_int32), C.c_void_p],
+    ),
+    "rp_dbg_get_option": (C.c_int32, [C.c_char_p, C.POINTER(C.c_int32)]),
+    "rp_dbg_attention_ex": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
+    ),
+    "rp_dbg_encoder_rows": (
+        C.c_int32,
+        [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+         C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
     "rp_dbg_mfma_probe": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "rp_dbg_rowscale": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_void_p]),
     "rp_dbg_attention": (

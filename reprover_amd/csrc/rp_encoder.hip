@@ -170,6 +170,21 @@ extern "C" RpStatus rp_set_option(const char* name, int32_t value) {
   return fail(RP_E_INVALID, "unknown option %s", name);
 }
 
+// The current value of an option of the table above or of gemm_helpers (tests restore what they found, not a copy of the defaults).
+extern "C" RpStatus rp_dbg_get_option(const char* name, int32_t* value) {
+  RP_REQUIRE(name && value, "null argument");
+  if (!strcmp(name, "gemm_helpers")) {
+    *value = g_gemm_helpers;
+    return RP_OK;
+  }
+  for (const Option& o : g_options) {
+    if (strcmp(name, o.name)) continue;
+    *value = *o.var;
+    return RP_OK;
+  }
+  return fail(RP_E_INVALID, "unknown option %s", name);
+}
+
 extern "C" RpStatus rp_profile_enable(int32_t on) {
   for (auto& r : g_prof_recs) {
     g_prof_pool.push_back(r.a);
@@ -357,6 +372,40 @@ __global__ __launch_bounds__(256) void hidden_out_kernel(const bf16_t* __restric
     out[row + c] = f2bf(w[c] * (__uint_as_float(word - 0x8000u) * r));
   }
 }
+
+// The three launches below are encode_pass's own, as functions: the kernel-level test entry points (rp_dbg_attention*,
+// rp_dbg_encoder_rows) call the same ones.
+// Embedding rows from the pre-encoded table: four token rows per wave, all their loads in flight before the first store
+// (round 6, exp10: 66 -> 57 us at 70 k tokens; one row per wave 66, two 61 - 63, eight 61).  Few tokens (a single proof state:
+// 8 workgroups of four rows per wave took 11.4 us, 32 of one row 5.2): one row per wave, as many workgroups as there are rows
+// to spread.
+void launch_embed_copy(const int32_t* ids, const bf16_t* thi, const uint8_t* tlo, const float* tss, bf16_t* xhi, uint8_t* xlo,
+                       float* ssp, int np, float* rs_out, float inv_d, float eps, int T, int Tp, int D, int vocab,
+                       const int32_t* t_dev, hipStream_t stream) {
+  auto launch_embed = [&](auto kern, int rows_per_wave) {
+    hipLaunchKernelGGL(kern, dim3((Tp + 4 * rows_per_wave - 1) / (4 * rows_per_wave)), dim3(256), 0, stream, ids, thi, tlo, tss, xhi,
+                       xlo, ssp, np, rs_out, inv_d, eps, T, Tp, D, vocab, t_dev);
+  };
+  const bool few = Tp < 8192;
+  if (D <= 1536) {
+    if (few) launch_embed(embed_copy_kernel<3, 1>, 1);
+    else launch_embed(embed_copy_kernel<3, 4>, 4);
+  } else {
+    if (few) launch_embed(embed_copy_kernel<4, 1>, 1);
+    else launch_embed(embed_copy_kernel<4, 4>, 4);
+  }
+}
+
+void launch_attention_fwd(dim3 grid, const bf16_t* qkv, const int4* work, const float* bias_tab, bf16_t* att, int H, int maxd,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(attention_kernel<false>, grid, dim3(256), 0, stream, qkv, work, bias_tab, att, H, maxd, (float*)nullptr, 0,
+                     Drop{0u, 0u, 1.f}, 0u);
+}
+
+void launch_hidden_out(int T, const bf16_t* xb, const uint8_t* xlo, const float* rs, const float* w, bf16_t* hidden, int D,
+                       hipStream_t stream) {
+  hipLaunchKernelGGL(hidden_out_kernel, dim3(T), dim3(256), 0, stream, xb, xlo, rs, w, hidden, D);
+}
 }  // namespace
 
 // The launch sequence of one encoder pass.  T / batch size the grids; when t_dev is given (rp_encode_padded) the
@@ -380,31 +429,15 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
   auto launch_rowscale = [&](bool needed_anyway = false) {
     if (fused_rs && !needed_anyway) return;
     ProfScope ps(stream, RP_K_RMSNORM);
-    hipLaunchKernelGGL(rowscale_kernel, dim3((Tp + 63) / 64), dim3(64), 0, stream, w.ssp, w.rs, Tp, np,
-                       1.f / (float)D, c.layer_norm_eps);
+    launch_rowscale_kernel(w.ssp, w.rs, Tp, np, 1.f / (float)D, c.layer_norm_eps, stream);
   };
   // the first QKV projection's RMSNorm factor straight from the embedding kernel (the table carries every row's sum of
   // squares) unless the consumer reads the statistic slots itself (few-token passes)
   const bool embed_rs = !fused_rs;
   {
     ProfScope ps(stream, RP_K_EMBED);
-    // four token rows per wave, all their loads in flight before the first store (round 6, exp10: 66 -> 57 us at 70 k tokens;
-    // one row per wave 66, two 61 - 63, eight 61).  Few tokens (a single proof state: 8 workgroups of four rows per wave
-    // took 11.4 us, 32 of one row 5.2): one row per wave, as many workgroups as there are rows to spread.
-    auto launch_embed = [&](auto kern, int rows_per_wave) {
-      hipLaunchKernelGGL(kern, dim3((Tp + 4 * rows_per_wave - 1) / (4 * rows_per_wave)), dim3(256), 0, stream, ids,
-                         (const bf16_t*)e->embed_hi, (const uint8_t*)e->embed_lo, (const float*)e->embed_ss, w.xb,
-                         reinterpret_cast<uint8_t*>(w.xlo), w.ssp, np, embed_rs ? w.rs : (float*)nullptr, 1.f / (float)D,
-                         c.layer_norm_eps, T, Tp, D, c.vocab_size, t_dev);
-    };
-    const bool few = Tp < 8192;
-    if (D <= 1536) {
-      if (few) launch_embed(embed_copy_kernel<3, 1>, 1);
-      else launch_embed(embed_copy_kernel<3, 4>, 4);
-    } else {
-      if (few) launch_embed(embed_copy_kernel<4, 1>, 1);
-      else launch_embed(embed_copy_kernel<4, 4>, 4);
-    }
+    launch_embed_copy(ids, e->embed_hi, e->embed_lo, e->embed_ss, w.xb, reinterpret_cast<uint8_t*>(w.xlo), w.ssp, np,
+                      embed_rs ? w.rs : (float*)nullptr, 1.f / (float)D, c.layer_norm_eps, T, Tp, D, c.vocab_size, t_dev, stream);
   }
   RP_CHECK_LAUNCH();
   const dim3 att_grid(H, T / ATT_Q + batch);  // upper bound of the number of 128-query blocks
@@ -421,8 +454,7 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
     if (st) return st;
     {
       ProfScope ps(stream, RP_K_ATTENTION);
-      hipLaunchKernelGGL(attention_kernel<false>, att_grid, dim3(256), 0, stream, w.qkv, (const int4*)w.work, e->bias_tab, w.att,
-                         H, e->maxd, (float*)nullptr, 0, Drop{0u, 0u, 1.f}, 0u);
+      launch_attention_fwd(att_grid, w.qkv, w.work, e->bias_tab, w.att, H, e->maxd, stream);
     }
     if ((st = launch_gemm(w.att, inner, Tp, L.wo, inner, D, inner, EpiResid8{w.xb, w.xlo, D, D, w.ssp, np, Tp}, stream,
                           RP_K_GEMM_O, tv, t_dev)))
@@ -441,8 +473,7 @@ static RpStatus encode_pass(RpEncoder* e, const int32_t* ids, const int32_t* cu_
   }
   launch_rowscale(true);  // final RMSNorm statistic (the pooling pass reads rs per token row)
   if (hidden) {  // rp_encode_hidden: last_hidden_state rows instead of the pool
-    hipLaunchKernelGGL(hidden_out_kernel, dim3(T), dim3(256), 0, stream, w.xb, reinterpret_cast<const uint8_t*>(w.xlo), w.rs,
-                       e->final_ln, hidden, D);
+    launch_hidden_out(T, w.xb, reinterpret_cast<const uint8_t*>(w.xlo), w.rs, e->final_ln, hidden, D, stream);
     RP_CHECK_LAUNCH();
     return RP_OK;
   }
@@ -707,7 +738,7 @@ extern "C" RpStatus rp_dbg_gemm_fused(const void* A, const void* W, void* out, i
   float* rs_buf = nullptr;
   if (ssp_in) {  // test entry only: a scratch allocation is fine here
     RP_HIP(hipMalloc((void**)&rs_buf, (size_t)M * 4));
-    hipLaunchKernelGGL(rowscale_kernel, dim3((M + 63) / 64), dim3(64), 0, stream, ssp_in, rs_buf, M, np_in, inv_d, eps);
+    launch_rowscale_kernel(ssp_in, rs_buf, M, np_in, inv_d, eps, stream);
   }
   const RowScale rs{rs_buf};
   struct Free {
@@ -781,28 +812,131 @@ extern "C" RpStatus rp_dbg_mfma_probe(int32_t waves_per_cu, int32_t mfmas, float
 extern "C" RpStatus rp_dbg_rowscale(const float* ssp, float* rs, int32_t rows, int32_t np, float inv_d, float eps,
                                     void* stream_) {
   RP_REQUIRE(ssp && rs && rows > 0 && np > 0 && np <= 32, "rows=%d np=%d", rows, np);
-  hipLaunchKernelGGL(rowscale_kernel, dim3((rows + 63) / 64), dim3(64), 0, (hipStream_t)stream_, ssp, rs, rows, np, inv_d,
-                     eps);
+  launch_rowscale_kernel(ssp, rs, rows, np, inv_d, eps, (hipStream_t)stream_);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
 
-extern "C" RpStatus rp_dbg_attention(const void* qkv, const int32_t* cu, const float* bias_tab, void* out,
-                                     int32_t batch, int32_t max_len, int32_t H, int32_t rows_total, void* stream_) {
-  const int maxd = 128;
-  (void)max_len;
-  hipStream_t stream = (hipStream_t)stream_;
+static RpStatus dbg_attention(const void* qkv, const int32_t* cu, const float* bias_tab, void* out, int32_t batch, int32_t H,
+                              int32_t rows_total, int maxd, hipStream_t stream) {
   const dim3 grid(H, rows_total / ATT_Q + batch);  // rows_total >= the packed token count
   // test entry only: a stream-ordered scratch allocation is fine here (attention list | pooling list)
   const int n_p = rows_total / POOL_CHUNK + batch;
   int4* work = nullptr;
   RP_HIP(hipMallocAsync((void**)&work, ((size_t)grid.y + n_p) * sizeof(int4), stream));
   hipLaunchKernelGGL(worklist_kernel, dim3(1), dim3(1024), 0, stream, cu, batch, work, (int)grid.y, work + grid.y, n_p, POOL_CHUNK);
-  hipLaunchKernelGGL(attention_kernel<false>, grid, dim3(256), 0, stream, (const bf16_t*)qkv, (const int4*)work, bias_tab,
-                     (bf16_t*)out, H, maxd, (float*)nullptr, 0, Drop{0u, 0u, 1.f}, 0u);
+  launch_attention_fwd(grid, (const bf16_t*)qkv, (const int4*)work, bias_tab, (bf16_t*)out, H, maxd, stream);
   const hipError_t le = hipGetLastError();
   (void)hipFreeAsync(work, stream);
   if (le != hipSuccess) return rp::fail(RP_E_HIP, "attention launch failed: %s", hipGetErrorString(le));
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_dbg_attention(const void* qkv, const int32_t* cu, const float* bias_tab, void* out,
+                                     int32_t batch, int32_t max_len, int32_t H, int32_t rows_total, void* stream_) {
+  (void)max_len;
+  return dbg_attention(qkv, cu, bias_tab, out, batch, H, rows_total, 128, (hipStream_t)stream_);
+}
+
+// ---- the encoder's forward kernels in isolation, every launch option reachable (tests/test_encoder_forward_kernels_gpu.py;
+// DESIGN.md section 11).  Device pointers, the launch functions encode_pass runs, arguments checked before anything is
+// launched, no output zeroed first.
+extern "C" RpStatus rp_dbg_attention_ex(const void* qkv, const int32_t* cu, const float* bias_tab, void* out, int32_t batch,
+                                        int32_t H, int32_t rows_total, int32_t max_distance, int32_t ntab, void* stream_) {
+  RP_REQUIRE(qkv && cu && bias_tab && out, "null argument");
+  RP_REQUIRE(batch >= 1 && H >= 1 && rows_total >= 1, "batch=%d, H=%d, rows_total=%d", batch, H, rows_total);
+  RP_REQUIRE(max_distance >= 1 && ntab == 2 * max_distance + 1, "max_distance=%d, table width %d", max_distance, ntab);
+  RP_REQUIRE(ntab + 128 <= ATT_TAB_MAX, "max_distance=%d too large", max_distance);  // as rp_encoder_create
+  return dbg_attention(qkv, cu, bias_tab, out, batch, H, rows_total, max_distance, (hipStream_t)stream_);
+}
+
+extern "C" RpStatus rp_dbg_gemm_ex(const void* A, int32_t lda, const void* W, int32_t n_rows_w, void* out, int32_t ldo, int32_t M,
+                                   int32_t K, int32_t n_valid, int32_t epilogue, int32_t prof_class, int32_t tokens_valid,
+                                   const int32_t* t_dev, int32_t rs_form, const float* ssp_in, int32_t np_in, float inv_d, float eps,
+                                   float* rs_buf, float* ssp_out, int32_t np_out, int32_t* plan, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RP_REQUIRE(A && W && out && plan, "null argument");
+  // (lda % 8: the operand's rows are fetched in 16-byte pieces)
+  RP_REQUIRE(M >= 64 && K >= 32 && K % 32 == 0 && lda >= K && lda % 8 == 0 && n_rows_w >= 1, "M=%d, K=%d, lda=%d, n_rows_w=%d", M, K,
+             lda, n_rows_w);
+  RP_REQUIRE(n_valid >= 8 && n_valid % 8 == 0 && n_valid <= n_rows_w, "n_valid=%d, n_rows_w=%d", n_valid, n_rows_w);
+  RP_REQUIRE(prof_class >= RP_K_GEMM_QKV && prof_class <= RP_K_GEMM_WO && prof_class != RP_K_ATTENTION, "prof_class=%d", prof_class);
+  RP_REQUIRE(tokens_valid >= 0 && tokens_valid <= M, "tokens_valid=%d, M=%d", tokens_valid, M);
+  const bool resid = epilogue == RP_EPI_RESID || epilogue == RP_EPI_RESID8, geglu = epilogue == RP_EPI_GEGLU_BF16;
+  RP_REQUIRE(resid || geglu || epilogue == RP_EPI_STORE_BF16, "unknown epilogue %d", epilogue);
+  RP_REQUIRE(!geglu || n_valid % 64 == 0, "gated GELU: n_valid=%d is not whole 32 / 32 row blocks", n_valid);
+  RP_REQUIRE(ldo >= (geglu ? n_valid / 2 : n_valid) && ldo % 8 == 0, "ldo=%d, n_valid=%d", ldo, n_valid);
+  RP_REQUIRE(rs_form >= 0 && rs_form <= 2 && !(resid && rs_form), "rs_form=%d, epilogue %d", rs_form, epilogue);
+  if (rs_form) RP_REQUIRE(ssp_in && np_in >= 1 && np_in <= 32 && (rs_form == 2 || rs_buf), "row scale: np=%d or a null argument", np_in);
+  if (ssp_out) RP_REQUIRE(resid && np_out >= 1, "ssp_out: epilogue %d, np=%d", epilogue, np_out);
+  const bf16_t* a = (const bf16_t*)A;
+  const bf16_t* w = (const bf16_t*)W;
+  const RowScale rs{rs_form == 1 ? rs_buf : nullptr};
+  const RowScaleFromSlots rs_slots{ssp_in, np_in, M, inv_d, eps};
+  bf16_t* o = (bf16_t*)out;
+  auto gemm = [&]() -> RpStatus {
+    switch (epilogue) {
+      case RP_EPI_STORE_BF16:
+        return rs_form == 2 ? launch_gemm<true>(a, lda, M, w, K, n_rows_w, K, EpiStoreBf16Slots{o, ldo, n_valid, rs_slots}, stream,
+                                                prof_class, tokens_valid, t_dev)
+                            : launch_gemm(a, lda, M, w, K, n_rows_w, K, EpiStoreBf16{o, ldo, n_valid, rs}, stream, prof_class,
+                                          tokens_valid, t_dev);
+      case RP_EPI_RESID:  // out = the two bf16 planes [2, M, ldo] (hi, then lo)
+        return launch_gemm(a, lda, M, w, K, n_rows_w, K, EpiResid{o, o + (size_t)M * ldo, ldo, n_valid, ssp_out, np_out, M}, stream,
+                           prof_class, tokens_valid, t_dev);
+      case RP_EPI_RESID8:  // out = the bf16 plane [M, ldo], then the one-byte extension plane [M, ldo]
+        return launch_gemm(a, lda, M, w, K, n_rows_w, K, EpiResid8{o, o + (size_t)M * ldo, ldo, n_valid, ssp_out, np_out, M}, stream,
+                           prof_class, tokens_valid, t_dev);
+      default:
+        return rs_form == 2 ? launch_gemm<true>(a, lda, M, w, K, n_rows_w, K, EpiGegluBf16Slots{o, ldo, n_valid, rs_slots}, stream,
+                                                prof_class, tokens_valid, t_dev)
+                            : launch_gemm(a, lda, M, w, K, n_rows_w, K, EpiGegluBf16{o, ldo, n_valid, rs}, stream, prof_class,
+                                          tokens_valid, t_dev);
+    }
+  };
+  // launch_gemm's and launch_gemm_cfg's own checks first (the tile configuration in the build, its fused row-scale form, K and M
+  // multiples of its tile), nothing launched: the row-scale launch below never runs for a call the GEMM refuses
+  g_gemm_check_only = true;
+  RpStatus st = gemm();
+  g_gemm_check_only = false;
+  if (st) return st;
+  if (rs_form == 1) launch_rowscale_kernel(ssp_in, rs_buf, M, np_in, inv_d, eps, stream);
+  st = gemm();
+  const GemmLaunchPlan& p = g_last_gemm_plan;
+  plan[0] = p.variant, plan[1] = p.form, plan[2] = p.tiles_f, plan[3] = p.tiles_t, plan[4] = p.n_helpers, plan[5] = p.full_rows;
+  return st;
+}
+
+// mode 0: embed_table_x24's launch over a = table f32 [vocab, n] -> o0 bf16 plane [vocab, n], o1 extension plane u8 [vocab, n],
+//         o2 f32 [vocab] sums of squares of the rows as stored;
+// mode 1: encode_pass's embedding launch (form by n <= 1536 and rows < 8192): a / b / c = the pre-encoded table (mode 0's
+//         outputs), ia = ids [T], rows = Tp (a multiple of 256) -> o0 bf16 [Tp, n], o1 u8 [Tp, n], o3 = rs [Tp] when given,
+//         else o2 = ssp [np, Tp]; t_dev optional;
+// mode 2: hidden_out_kernel: a / b = the 24-bit planes [rows, n], c = rs [rows], d = w [n] -> o0 bf16 [rows, n].
+extern "C" RpStatus rp_dbg_encoder_rows(int32_t mode, const void* a, const void* b, const void* c, const void* d,
+                                        const int32_t* ia, const int32_t* t_dev, int32_t T, int32_t rows, int32_t n, int32_t vocab,
+                                        int32_t np, float inv_d, float eps, void* o0, void* o1, void* o2, void* o3, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RP_REQUIRE(mode >= 0 && mode <= 2, "mode=%d", mode);
+  RP_REQUIRE(rows >= 1 && n >= 8 && n % 8 == 0, "rows=%d, n=%d", rows, n);
+  switch (mode) {
+    case 0:
+      RP_REQUIRE(a && o0 && o1 && o2 && vocab >= 1, "null argument or vocab=%d", vocab);
+      launch_embed_table_x24((const float*)a, (bf16_t*)o0, (uint8_t*)o1, (float*)o2, vocab, n, stream);
+      break;
+    case 1:
+      RP_REQUIRE(a && b && c && ia && o0 && o1 && (o2 || o3), "null argument");
+      RP_REQUIRE(T >= 1 && T <= rows && rows % GEMM_M_ALIGN == 0 && vocab >= 1 && np >= 1 && n <= RMS_MAX_V4 * 256,
+                 "T=%d, Tp=%d, vocab=%d, np=%d, n=%d", T, rows, vocab, np, n);
+      launch_embed_copy(ia, (const bf16_t*)a, (const uint8_t*)b, (const float*)c, (bf16_t*)o0, (uint8_t*)o1, (float*)o2, np,
+                        (float*)o3, inv_d, eps, T, rows, n, vocab, t_dev, stream);
+      break;
+    default:
+      RP_REQUIRE(a && b && c && d && o0, "null argument");
+      launch_hidden_out(rows, (const bf16_t*)a, (const uint8_t*)b, (const float*)c, (const float*)d, (bf16_t*)o0, n, stream);
+      break;
+  }
+  RP_CHECK_LAUNCH();
   return RP_OK;
 }
 

@@ -371,6 +371,10 @@ static __global__ __launch_bounds__(64) void rowscale_kernel(const float* __rest
   for (int i = 0; i < 32; ++i) s += v[i];  // index order; the zero padding adds exactly nothing
   rs[t] = rsqrtf(s * inv_d + eps);
 }
+// the kernel's one launch form: the passes (rp_encoder.hip, rp_train.hip) and the kernel-level test entry points call it
+inline void launch_rowscale_kernel(const float* ssp, float* rs, int rows, int np, float inv_d, float eps, hipStream_t stream) {
+  hipLaunchKernelGGL(rowscale_kernel, dim3((rows + 63) / 64), dim3(64), 0, stream, ssp, rs, rows, np, inv_d, eps);
+}
 
 template <class RS>
 struct EpiStoreBf16T {  // out[token, feature] = bf16(acc * rs[token])
@@ -910,6 +914,18 @@ static auto pick_gemm_kernel() {
     return gemm_kernel<C, Epi>;
 }
 
+// What the last launch_gemm() of this host thread actually launched (rp_dbg_gemm_ex reports it, so that a test cannot run
+// another form than it names): launch_gemm writes the tile configuration, launch_gemm_cfg the rest just before its launch.
+// Host side only: no kernel and no kernel argument knows of it.
+struct GemmLaunchPlan {
+  int variant = -1, form = -1;  // form: 0 one workgroup per tile, 1 persistent, 2 mixed full + half tiles
+  int tiles_f = 0, tiles_t = 0, n_helpers = 0, full_rows = 0;
+};
+inline thread_local GemmLaunchPlan g_last_gemm_plan;
+// rp_dbg_gemm_ex: run launch_gemm's choice of tile configuration and launch_gemm_cfg's own requirements, launch nothing (so that
+// whatever the entry point launches in front of the GEMM never runs for a call the GEMM refuses).  Host side only.
+inline thread_local bool g_gemm_check_only = false;
+
 // `w` = weight matrix [n_rows_w, K] (row operand: tile rows = output features, clamped at the edge),
 // `a` = activations [M, K] (column operand: tile cols = tokens, M a multiple of the token tile).
 template <class C, class Epi>
@@ -921,6 +937,7 @@ static RpStatus launch_gemm_cfg(GemmOperand w, GemmOperand a, int K, Epi epi, hi
   RP_HIP(attr.ensure((const void*)kern, C::LDS_BYTES));
   RP_REQUIRE(K % C::BK == 0 && a.rows % C::BN == 0, "gemm: K=%d must be a multiple of %d, M=%d of %d", K, C::BK,
              a.rows, C::BN);
+  if (g_gemm_check_only) return RP_OK;
   const int rows_needed = (tokens_valid > 0 && tokens_valid < a.rows) ? tokens_valid : a.rows;
   const int tiles_f = (w.rows + C::BM - 1) / C::BM, tiles_t = (rows_needed + C::BN - 1) / C::BN;
   // tile order: feature tiles fastest inside groups of `group` token tiles (shared activation panels)
@@ -950,6 +967,7 @@ static RpStatus launch_gemm_cfg(GemmOperand w, GemmOperand a, int K, Epi epi, hi
         static LdsAttrOnce mattr;
         RP_HIP(mattr.ensure((const void*)mk, C::LDS_BYTES));
         const int nh1 = mp.half_first * tiles_f, nh1_pad = (nh1 + 7) & ~7;
+        g_last_gemm_plan = GemmLaunchPlan{g_last_gemm_plan.variant, 2, tiles_f, tiles_t, 0, mp.full_rows};
         hipLaunchKernelGGL(mk, dim3(nh1_pad + mp.full_rows * tiles_f + mp.half_last * tiles_f), dim3(C::THREADS), C::LDS_BYTES,
                            stream, w, a, K, tiles_f, mp.full_rows, nh1, nh1_pad, group, g_gemm_edge_layout, epi);
         RP_CHECK_LAUNCH();
@@ -966,12 +984,14 @@ static RpStatus launch_gemm_cfg(GemmOperand w, GemmOperand a, int K, Epi epi, hi
       auto pk = gemm_kernel_persist<C, Epi>;
       static LdsAttrOnce pattr;
       RP_HIP(pattr.ensure((const void*)pk, PERSIST_LDS_BYTES));
+      g_last_gemm_plan = GemmLaunchPlan{g_last_gemm_plan.variant, 1, tiles_f, tiles_t, 0, 0};
       hipLaunchKernelGGL(pk, dim3(slots), dim3(C::THREADS), PERSIST_LDS_BYTES, stream, w, a, K, tiles_f, tiles_t, group,
                          g_gemm_edge_layout, t_dev, epi);
       RP_CHECK_LAUNCH();
       return RP_OK;
     }
   }
+  g_last_gemm_plan = GemmLaunchPlan{g_last_gemm_plan.variant, 0, tiles_f, tiles_t, n_helpers, 0};
   hipLaunchKernelGGL(kern, dim3(n_grid + n_helpers), dim3(C::THREADS), C::LDS_BYTES, stream, w, a, K, tiles_f, tiles_t, group,
                      stagger_ticks, t_dev, epi, n_helpers);
   RP_CHECK_LAUNCH();
@@ -1038,6 +1058,8 @@ static RpStatus launch_gemm(const bf16_t* A, int lda, int M, const bf16_t* W, in
   // (force_variant: the training step's dgrad GEMMs choose their tile themselves, rp_train.hip bwd_variant)
   const int v = force_variant >= 0 ? force_variant : pick_gemm_variant(prof_class, M, n_rows_w, K, tokens_valid);
   RP_REQUIRE(gemm_variant_known(v), "tile configuration %d is not in this build", v);
+  g_last_gemm_plan = GemmLaunchPlan{};
+  g_last_gemm_plan.variant = v;
   if constexpr (!SMALL_ONLY) {
     switch (v) {
       case 26: return launch_gemm_cfg<GemmCfg<256, 256, 64, 4, 2, 2, 1>>(w, a, K, epi, stream, prof_class, tokens_valid, t_dev);
@@ -1643,9 +1665,11 @@ struct RpEncoder {
 namespace rp {
 // (Re-)encode the embedding table into the 24-bit form: embed_kernel<true> over the vocabulary (token r = row r), the row
 // statistic into embed_ss (slot 0 of a one-slot layout).  Launch-only; e->embed_* are allocated by rp_encoder_create.
+inline void launch_embed_table_x24(const float* table, bf16_t* hi, uint8_t* lo, float* ss, int V, int D, hipStream_t stream) {
+  hipLaunchKernelGGL(embed_kernel<true>, dim3((V + 3) / 4), dim3(256), 0, stream, (const int32_t*)nullptr, table, hi,
+                     reinterpret_cast<bf16_t*>(lo), ss, 1, V, V, D, V, (const int32_t*)nullptr);
+}
 inline void embed_table_x24(RpEncoder* e, hipStream_t stream) {
-  const int V = e->cfg.vocab_size, D = e->cfg.d_model;
-  hipLaunchKernelGGL(embed_kernel<true>, dim3((V + 3) / 4), dim3(256), 0, stream, (const int32_t*)nullptr, (const float*)e->embed,
-                     e->embed_hi, reinterpret_cast<bf16_t*>(e->embed_lo), e->embed_ss, 1, V, V, D, V, (const int32_t*)nullptr);
+  launch_embed_table_x24(e->embed, e->embed_hi, e->embed_lo, e->embed_ss, e->cfg.vocab_size, e->cfg.d_model, stream);
 }
 }  // namespace rp

@@ -338,8 +338,7 @@ RpStatus forward_layers(RpTrainer* tr, const int32_t* ids, const int32_t* cu, in
   RpStatus st;
   auto rowscale = [&](float* rs) {
     ProfScope ps(stream, RP_K_RMSNORM);
-    hipLaunchKernelGGL(rowscale_kernel, dim3((Tp + 63) / 64), dim3(64), 0, stream, w.ssp, rs, Tp, np, 1.f / (float)D,
-                       c.layer_norm_eps);
+    launch_rowscale_kernel(w.ssp, rs, Tp, np, 1.f / (float)D, c.layer_norm_eps, stream);
   };
   const Drop drop = tr->drop;
   {
