@@ -974,6 +974,30 @@ RpStatus rp_sample_pool_admit(const int32_t* states, const uint32_t* new_seeds, 
 RpStatus rp_sample_pool_rows(const int32_t* active, const int32_t* pos, int32_t n_active, int32_t n, int32_t nb,
                              int32_t max_len, const int32_t* seq, int32_t* tokens_next, void* stream);
 
+/* Constrained decoding ("Constrained decoding"): one launch between a decode step and its selection
+ * or sampler launch that overwrites the forbidden entries of the step's log-probs with -inf and leaves every other bit
+ * of them as it was.  The constraint is a deterministic automaton over token ids:
+ *   next  device int16 [n_q, vocab], contiguous: next[s][v] is the state after token v in state s, < 0 = forbidden.
+ * rp_constraint_mask: row r of logprobs [rows, vocab] is masked by state q_rows[r] (device int32 [rows], by launch row:
+ * the host-books loops upload it with the step's tokens).
+ * rp_constraint_mask_step: the form for loops that read nothing back.  q is device int32 [n, nb] by (state, sample) like
+ * the sampler's books; `active` / `pos` are HOST int32 [n_active] and travel as kernel arguments; tokens_in is the step's
+ * by-row input (the sampler's tokens_next).  For row a * nb + b of slot active[a]: pos[a] == 0 sets q = 0 (which is
+ * also how an admitted slot's next tenant starts clean); else q moves to next[q][tokens_in[row]] where that is >= 0 and
+ * stays where it is not (a finished row that is fed pad); then the row is masked by the new q, which is stored.  q of
+ * a state that is not listed is not touched.
+ * q, q_rows, tokens_in and the table are device memory, so their VALUES cannot be checked here: a state is clamped into
+ * [0, n_q) and a token into [0, vocab) before either indexes anything, so no value reaches an address outside the
+ * buffers (a wrong value masks its own row by the clamped state and harms nothing else).
+ * Neither takes a workspace.  RP_E_INVALID (nothing is launched): a null pointer, logprobs / next not aligned to their
+ * element type, vocab outside 1..512, rows outside 1..1024, n_q outside 1..4096, nb outside 1..64, n outside 1..32,
+ * n_active outside 1..n, more than 1024 listed rows, active not distinct or outside [0, n), a negative pos. */
+RpStatus rp_constraint_mask(float* logprobs, int32_t vocab, int32_t rows, const int32_t* q_rows, const int16_t* next,
+                            int32_t n_q, void* stream);
+RpStatus rp_constraint_mask_step(float* logprobs, int32_t vocab, const int32_t* active, const int32_t* pos,
+                                 int32_t n_active, int32_t n, int32_t nb, const int32_t* tokens_in, int32_t* q,
+                                 const int16_t* next, int32_t n_q, void* stream);
+
 /* Sampling parameters per row ("Sampling parameters per request"): rp_sample_step and
  * rp_sample_pool_step with a parameter table in place of temperature / top_k / top_p, and rp_sample_pool_admit with a
  * count of live rows per admitted state.  The same kernels; none of the three takes a workspace.

@@ -1712,6 +1712,132 @@ extern "C" RpStatus rp_sample_pool_rows(const int32_t* active, const int32_t* po
   return RP_OK;
 }
 
+// ---- constrained decoding ("Constrained decoding") -----------------------------------------------------
+// (The kernels stand here, after every other kernel of the file, so that adding them moves no existing kernel inside
+// the code object: a kernel's cycles shift by a few per cent with its placement.)
+namespace {
+// One wave per row, four rows per workgroup, no LDS: the row's V log-probs (as bits) and the V int16 of its automaton
+// state's row of `next` are walked in vectors of W = 4, 2 or 1 elements, the widest for which one shared head of < W
+// elements leaves both the log-prob pointer 4 W-byte aligned and the table pointer 2 W-byte aligned.  Rows of a width
+// that is a multiple of 4 take W = 4 with no head (16-byte and 8-byte accesses, 256 elements per pass of the wave); other
+// widths take what the two row starts allow.  An entry is rewritten to -inf where next < 0; every other word is stored
+// back as the bits that were loaded.
+template <int W>
+__device__ __forceinline__ void mask_row(uint32_t* __restrict__ lp, const int16_t* __restrict__ nx, int V, int lane) {
+  typedef uint32_t U __attribute__((ext_vector_type(W)));
+  typedef int16_t S __attribute__((ext_vector_type(W)));
+  constexpr uint32_t NEG_INF = 0xff800000u;
+  int head = 0;
+  if (W > 1) head = min(V, (int)((W - (((uintptr_t)lp >> 2) & (W - 1))) & (W - 1)));
+  if (lane < head && nx[lane] < 0) lp[lane] = NEG_INF;
+  const int nvec = (V - head) / W;
+  for (int i = lane; i < nvec; i += 64) {
+    const int at = head + i * W;
+    if constexpr (W == 1) {
+      if (nx[at] < 0) lp[at] = NEG_INF;
+    } else {
+      U x = *reinterpret_cast<const U*>(lp + at);
+      const S s = *reinterpret_cast<const S*>(nx + at);
+#pragma unroll
+      for (int j = 0; j < W; ++j)
+        if (s[j] < 0) x[j] = NEG_INF;
+      *reinterpret_cast<U*>(lp + at) = x;
+    }
+  }
+  const int tail = head + nvec * W + lane;
+  if (tail < V && nx[tail] < 0) lp[tail] = NEG_INF;
+}
+
+// row `row` of logprobs masked by state q (already inside [0, n_q)) of the table
+__device__ __forceinline__ void mask_row_any(float* __restrict__ logprobs, const int16_t* __restrict__ next, int V, int row,
+                                             int q, int lane) {
+  uint32_t* lp = reinterpret_cast<uint32_t*>(logprobs) + (size_t)row * V;
+  const int16_t* nx = next + (size_t)q * V;
+  const unsigned d = (unsigned)(((uintptr_t)lp >> 2) - ((uintptr_t)nx >> 1)) & 3u;  // the two starts, in elements, mod 4
+  if (d == 0) mask_row<4>(lp, nx, V, lane);
+  else if (d == 2) mask_row<2>(lp, nx, V, lane);
+  else mask_row<1>(lp, nx, V, lane);
+}
+
+// rp_constraint_mask: row r by state q_rows[r].  q_rows is device memory, so its values are clamped into [0, n_q) here.
+__global__ __launch_bounds__(256) void constraint_mask_kernel(float* __restrict__ logprobs, int V, int rows,
+                                                              const int32_t* __restrict__ q_rows,
+                                                              const int16_t* __restrict__ next, int n_q) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int q = min(max(q_rows[row], 0), n_q - 1);
+  mask_row_any(logprobs, next, V, row, q, lane);
+}
+
+// rp_constraint_mask_step: the state of row a * nb + b lives in q[state, b] like the sampler's books.  It is advanced by
+// the token the step was fed (pos 0: back to the start state, which is also how a slot's next tenant starts clean; a
+// forbidden token - the pad a finished row is fed - leaves it), written back by lane 0, and the row is masked by it.
+// Every value read from device memory (q, the token, the table's entry) is clamped before it indexes anything.
+__global__ __launch_bounds__(256) void constraint_mask_step_kernel(float* __restrict__ logprobs, int V, int rows, int nb,
+                                                                   DecSlots slots, const int32_t* __restrict__ tokens_in,
+                                                                   int32_t* __restrict__ q, const int16_t* __restrict__ next,
+                                                                   int n_q) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int slot = row / nb, b = row - slot * nb;
+  const size_t idx = (size_t)slots.state[slot] * nb + b;
+  int qn = 0;
+  if (slots.pos[slot] != 0) {
+    qn = min(max(q[idx], 0), n_q - 1);
+    const int tok = min(max(tokens_in[row], 0), V - 1);
+    const int to = next[(size_t)qn * V + tok];
+    if (to >= 0) qn = min(to, n_q - 1);
+  }
+  if (lane == 0) q[idx] = qn;
+  mask_row_any(logprobs, next, V, row, qn, lane);
+}
+
+// what the two entries ask of the log-probs and the table
+RpStatus constraint_caps(const float* logprobs, int V, const int16_t* next, int n_q) {
+  RP_REQUIRE((uintptr_t)logprobs % 4 == 0 && (uintptr_t)next % 2 == 0, "logprobs=%p / next=%p is not aligned to its type",
+             (const void*)logprobs, (const void*)next);
+  RP_REQUIRE(V >= 1 && V <= DEC_SELECT_ROW, "vocab=%d (1..%d)", V, DEC_SELECT_ROW);
+  RP_REQUIRE(n_q >= 1 && n_q <= 4096, "n_q=%d (1..4096)", n_q);
+  return RP_OK;
+}
+}  // namespace
+
+extern "C" RpStatus rp_constraint_mask(float* logprobs, int32_t V, int32_t rows, const int32_t* q_rows, const int16_t* next,
+                                       int32_t n_q, void* stream_) {
+  RP_REQUIRE(logprobs && q_rows && next, "null argument");
+  if (RpStatus st = constraint_caps(logprobs, V, next, n_q)) return st;
+  RP_REQUIRE(rows >= 1 && rows <= DEC_MAX_ROWS, "rows=%d (1..%d)", rows, DEC_MAX_ROWS);
+  hipLaunchKernelGGL(constraint_mask_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream_, logprobs, V, rows,
+                     q_rows, next, n_q);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+extern "C" RpStatus rp_constraint_mask_step(float* logprobs, int32_t V, const int32_t* active, const int32_t* pos,
+                                            int32_t n_active, int32_t n, int32_t nb, const int32_t* tokens_in, int32_t* q,
+                                            const int16_t* next, int32_t n_q, void* stream_) {
+  RP_REQUIRE(logprobs && active && pos && tokens_in && q && next, "null argument");
+  if (RpStatus st = constraint_caps(logprobs, V, next, n_q)) return st;
+  RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "nb=%d (1..%d)", nb, DEC_MAX_BEAMS);
+  RP_REQUIRE(n >= 1 && n <= DEC_MAX_STATES, "states=%d (1..%d)", n, DEC_MAX_STATES);
+  RP_REQUIRE(n_active >= 1 && n_active <= n, "active states=%d (1..states=%d)", n_active, n);
+  RP_REQUIRE((int64_t)n_active * nb <= DEC_MAX_ROWS, "rows = listed states * nb = %lld > %d", (long long)n_active * nb,
+             DEC_MAX_ROWS);
+  DecSlots slots = {};
+  RpStatus st = dec_list(active, n_active, n, "active", "state", [&](int a, int id) -> RpStatus {
+    RP_REQUIRE(pos[a] >= 0, "pos[%d]=%d < 0", a, pos[a]);
+    slots.state[a] = id;
+    slots.pos[a] = pos[a];
+    return RP_OK;
+  });
+  if (st) return st;
+  const int rows = n_active * nb;
+  hipLaunchKernelGGL(constraint_mask_step_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream_, logprobs, V, rows,
+                     nb, slots, tokens_in, q, next, n_q);
+  RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
 namespace {
 RpStatus books_check(int n, int nb, int max_len) {
   RP_REQUIRE(nb >= 1 && nb <= DEC_MAX_BEAMS, "nb=%d (1..%d)", nb, DEC_MAX_BEAMS);

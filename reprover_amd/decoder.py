@@ -677,6 +677,49 @@ class HipT5Decoder:
                                                      state.tokens.data_ptr(), _lib.current_stream()),
                        "rp_sample_pool_rows")
 
+    # -- constrained decoding (``generation``'s ``mask`` callables) ------------------------------------------------------
+    def _constraint_table(self, constraint, log_probs: torch.Tensor) -> torch.Tensor:
+        assert log_probs.is_cuda and log_probs.is_contiguous() and log_probs.dtype == torch.float32
+        table = constraint.device_table(self.device)
+        if table.shape[1] != log_probs.shape[1]:
+            raise ValueError(f"a constraint over {table.shape[1]} ids for a model of {log_probs.shape[1]}")
+        return table
+
+    def constraint_mask(self, log_probs: torch.Tensor, q_rows: torch.Tensor, constraint) -> torch.Tensor:
+        """``-inf`` (in place) into the entries of ``log_probs [rows, V]`` that ``constraint`` forbids in state
+        ``q_rows[r]`` (device int32 ``[rows]``), every other bit as it was (``rp_constraint_mask``; the host-books
+        loops' ``mask``).  Returns ``log_probs``."""
+        table = self._constraint_table(constraint, log_probs)
+        rows, V = log_probs.shape
+        q = q_rows.to(device=self.device, dtype=torch.int32).contiguous()
+        if q.numel() != rows:
+            raise _lib.HipLibraryError(f"constraint_mask: {q.numel()} states for {rows} rows")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_constraint_mask(log_probs.data_ptr(), V, rows, q.data_ptr(), table.data_ptr(),
+                                                    table.shape[0], _lib.current_stream()), "rp_constraint_mask")
+        return log_probs
+
+    def constraint_mask_step(self, log_probs: torch.Tensor, active, pos, tokens_in: torch.Tensor, q: torch.Tensor,
+                             constraint) -> torch.Tensor:
+        """The sampled loops' ``mask`` (``rp_constraint_mask_step``): the automaton states ``q`` (device int32
+        ``[n, nb]`` by (state, sample)) of the slots ``active`` advance by the tokens the step was fed (``tokens_in``, by
+        row; slot ``active[a]`` at ``pos[a]``, position 0 starting over) and mask the rows.  Nothing is read back."""
+        table = self._constraint_table(constraint, log_probs)
+        act, p = (np.ascontiguousarray(x, dtype=np.int32) for x in (active, pos))
+        n, nb = q.shape
+        rows, V = log_probs.shape
+        for x in (q, tokens_in):
+            assert x.is_cuda and x.is_contiguous() and x.dtype == torch.int32, "rp_constraint_mask_step takes int32 device tensors"
+        if rows != len(act) * nb or len(p) != len(act) or tokens_in.numel() < rows:
+            raise _lib.HipLibraryError(f"constraint_mask_step: {rows} rows, {len(p)} positions, {tokens_in.numel()} tokens "
+                                       f"for {len(act)} states of {nb} samples")
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.rp_constraint_mask_step(log_probs.data_ptr(), V, _pc(act), _pc(p), len(act), n, nb,
+                                                         tokens_in.data_ptr(), q.data_ptr(), table.data_ptr(),
+                                                         table.shape[0], _lib.current_stream()),
+                       "rp_constraint_mask_step")
+        return log_probs
+
     def select_many(self, log_probs: torch.Tensor, running: torch.Tensor, nb: int, k: int):
         """Per state the device top-k of its own ``[nb * V]`` block (``rp_beam_select_batch``): scores, tokens, parents,
         each ``[n_active, k]``, parents local to the state."""
@@ -834,29 +877,52 @@ class HipT5Generator:
         """``prefixes`` (None, or one entry or None per source) as lists; None when no source has one."""
         return _check_prompts(prefixes, n, max_length, "prefixes", "sources")
 
-    def greedy(self, ids: np.ndarray, max_length: int, prefix=None) -> BeamSearchOutput:
+    def _constrained(self, constraint, fused: bool = False) -> Dict:
+        """The loops' ``constraint=`` / ``mask=`` keywords for ``constraint`` (None: none): the decoder's
+        ``rp_constraint_mask`` launch, or with ``fused`` its ``rp_constraint_mask_step``."""
+        if constraint is None:
+            return {}
+        dec = self.decoder
+        if constraint.vocab != dec.V or constraint.eos != self._eos:
+            raise ValueError(f"a constraint over {constraint.vocab} ids with eos={constraint.eos} for a model of "
+                             f"{dec.V} ids with eos={self._eos}")
+        if fused:
+            return dict(constraint=constraint, mask=lambda lp, active, pos, tokens, q: dec.constraint_mask_step(
+                lp, active, pos, tokens, q, constraint))
+        return dict(constraint=constraint, mask=lambda lp, q_rows: dec.constraint_mask(lp, q_rows, constraint))
+
+    def greedy(self, ids: np.ndarray, max_length: int, prefix=None, constraint=None) -> BeamSearchOutput:
         """``generate(input_ids, num_beams=1, max_length)``: HF's greedy search (argmax, ties to the lowest id), not a
-        one-beam beam search.  ``prefix``: as in ``generate``."""
+        one-beam beam search.  ``prefix`` / ``constraint``: as in ``generate``."""
         if self._check_prefixes([prefix], 1, max_length) is not None:
-            return self.greedy_many([ids], max_length, prefixes=[prefix])[0]
+            return self.greedy_many([ids], max_length, prefixes=[prefix], constraint=constraint)[0]
+        kw = self._constrained(constraint)
         enc = self.encode_hidden(ids)
         self.decoder.start(enc, 1, max_length)
         return greedy_search(self.decoder.step, max_length, eos_token_id=self._eos,
-                             decoder_start_token_id=self._start, device=self.device)
+                             decoder_start_token_id=self._start, device=self.device, **kw)
 
     def generate(self, ids: np.ndarray, num_beams: int, max_length: int, length_penalty: float = 1.0,
-                 trace: Optional[list] = None, sync_every: Optional[int] = None, prefix=None) -> BeamSearchOutput:
+                 trace: Optional[list] = None, sync_every: Optional[int] = None, prefix=None,
+                 constraint=None) -> BeamSearchOutput:
         """``generate(input_ids, num_beams=n, num_return_sequences=n, length_penalty, max_length, early_stopping=False,
         do_sample=False)`` for one source.  Reads the selected candidates back once per step (generation.py);
         ``sync_every``: as in ``generate_many``, whose one-state call it then is.
 
         ``prefix`` (token ids; None or empty: none): HF's ``decoder_input_ids = [start] + prefix`` - every returned
         sequence begins with it, ``max_length`` counts it, the scores sum the generated tokens only.  Its cache rows are
-        written in one pass (``rp_decoder_batch_prefill``, DESIGN.md section 9 "Tactic prefix"); host books only."""
+        written in one pass (``rp_decoder_batch_prefill``, DESIGN.md section 9 "Tactic prefix"); host books only.
+
+        ``constraint`` (a ``constraint.ByteAutomaton``; None: none): HF's ``prefix_allowed_tokens_fn`` walking that
+        automaton - one ``rp_constraint_mask`` launch between every step and its selection writes ``-inf`` over the
+        forbidden log-probs (DESIGN.md section 9 "Constrained decoding").  A prefix the automaton rejects is a
+        ``ValueError``; host books only (``ValueError`` with ``sync_every``)."""
+        if constraint is not None and sync_every is not None:
+            raise ValueError("a constraint together with the device books (sync_every) is not built yet")
         if self._check_prefixes([prefix], 1, max_length) is not None:
             traces = None if trace is None else []
             out, = self.generate_many([ids], num_beams, max_length, length_penalty, traces=traces, sync_every=sync_every,
-                                      prefixes=[prefix])
+                                      prefixes=[prefix], constraint=constraint)
             if trace is not None:
                 trace.extend(traces[0])
             return out
@@ -864,12 +930,13 @@ class HipT5Generator:
             if trace is not None:
                 raise ValueError("trace= needs the host books: it cannot be combined with sync_every")
             return self.generate_many([ids], num_beams, max_length, length_penalty, sync_every=sync_every)[0]
+        kw = self._constrained(constraint)
         enc = self.encode_hidden(ids)
         self.decoder.start(enc, num_beams, max_length)
         return beam_search(self.decoder.step, num_beams, max_length, length_penalty,
                            eos_token_id=self._eos,
                            decoder_start_token_id=self._start,
-                           select=self.decoder.select, device=self.device, trace=trace)
+                           select=self.decoder.select, device=self.device, trace=trace, **kw)
 
     def _start_many(self, sources, num_beams: int, max_length: int) -> int:
         srcs = [np.asarray(x, dtype=np.int32).reshape(-1) for x in sources]
@@ -880,20 +947,25 @@ class HipT5Generator:
         self.decoder.start_many(enc, cu, num_beams, max_length)
         return len(srcs)
 
-    def greedy_many(self, sources, max_length: int, prefixes=None) -> List[BeamSearchOutput]:
+    def greedy_many(self, sources, max_length: int, prefixes=None, constraint=None) -> List[BeamSearchOutput]:
         """``greedy`` for several sources through one decode loop: entry ``i`` is ``greedy(sources[i], max_length)`` bit
-        for bit, whichever other sources share the call.  ``prefixes``: as in ``generate_many``."""
+        for bit, whichever other sources share the call.  ``prefixes`` / ``constraint`` (one automaton, shared by every
+        source): as in ``generate_many``."""
         sources = list(sources)
         prefixes = self._check_prefixes(prefixes, len(sources), max_length)
+        ckw = self._constrained(constraint)
+        if constraint is not None:
+            for p in prefixes or []:
+                constraint.state_after(p)  # a rejected prefix: ValueError before anything is launched
         n = self._start_many(sources, 1, max_length)
-        kw = {} if prefixes is None else dict(prompts=prefixes, prefill_many=self.decoder.prefill_many)
+        kw = dict(ckw, **({} if prefixes is None else dict(prompts=prefixes, prefill_many=self.decoder.prefill_many)))
         return greedy_search_batch(self.decoder.step_many, n, max_length, eos_token_id=self._eos,
                                    decoder_start_token_id=self._start, device=self.device,
                                    **kw)
 
     def generate_many(self, sources, num_beams: int, max_length: int, length_penalty: float = 1.0,
                       traces: Optional[list] = None, sync_every: Optional[int] = None,
-                      prefixes=None) -> List[BeamSearchOutput]:
+                      prefixes=None, constraint=None) -> List[BeamSearchOutput]:
         """``generate`` for several sources at once: one packed encoder pass, one cross-K/V GEMM and one decode loop that
         runs until the last state stops, with one readback per step.  Entry ``i`` equals ``generate(sources[i], ...)``
         bit for bit (sequences, scores and, in ``traces[i]``, every step's selected triples), whichever other sources
@@ -907,11 +979,20 @@ class HipT5Generator:
         token (``generate``'s ``prefix``).  All prompts' cache rows are written by one ``rp_decoder_batch_prefill``, then
         state ``i`` searches from position ``len(prefixes[i])`` (``rp_decoder_batch_step_pos``).  Entry ``i`` equals
         ``generate(sources[i], ..., prefix=prefixes[i])`` bit for bit.  Together with ``sync_every`` a ``ValueError``:
-        the device books with a prompt are not built yet."""
+        the device books with a prompt are not built yet.
+
+        ``constraint``: ``generate``'s, one automaton shared by every source; entry ``i`` equals
+        ``generate(sources[i], ..., constraint=constraint)`` bit for bit.  With ``sync_every`` a ``ValueError``."""
         sources = list(sources)
         prefixes = self._check_prefixes(prefixes, len(sources), max_length)
         if prefixes is not None and sync_every is not None:
             raise ValueError("a decoder prompt together with the device books (sync_every) is not built yet")
+        if constraint is not None and sync_every is not None:
+            raise ValueError("a constraint together with the device books (sync_every) is not built yet")
+        ckw = self._constrained(constraint)
+        if constraint is not None:
+            for p in prefixes or []:
+                constraint.state_after(p)  # a rejected prefix: ValueError before anything is launched
         if sync_every is not None:
             if traces is not None:
                 raise ValueError("traces= needs the host books: it cannot be combined with sync_every")
@@ -925,7 +1006,7 @@ class HipT5Generator:
                 dec.beam_advance, n, num_beams, max_length, length_penalty, eos_token_id=self._eos,
                 decoder_start_token_id=self._start, sync_every=sync_every,
                 device=self.device, init=dec.beam_books)
-        kw = {} if prefixes is None else dict(prompts=prefixes, prefill_many=self.decoder.prefill_many)
+        kw = dict(ckw, **({} if prefixes is None else dict(prompts=prefixes, prefill_many=self.decoder.prefill_many)))
         return beam_search_batch(self.decoder.step_many, n, num_beams, max_length, length_penalty,
                                  eos_token_id=self._eos,
                                  decoder_start_token_id=self._start,
@@ -933,7 +1014,7 @@ class HipT5Generator:
 
     def generate_stream(self, num_beams: int, max_length: int, length_penalty: float = 1.0,
                         n_slots: Optional[int] = None, src_cap: int = 2048,
-                        sync_every: Optional[int] = None) -> "GenerateStream":
+                        sync_every: Optional[int] = None, constraint=None) -> "GenerateStream":
         """A running beam search that sources join while it runs (continuous batching): a
         ``GenerateStream`` of ``n_slots`` places (default ``HipT5Decoder.max_states(num_beams)``) for sources of at most
         ``src_cap`` tokens.  Every ticket's output is ``generate(source, num_beams, max_length, length_penalty)`` bit for
@@ -942,24 +1023,31 @@ class HipT5Generator:
         ``sync_every`` (an integer >= 1; the default None is the host-books pool): the slots' books live on the device
         (``generation.BeamBooksPool``, ``rp_beam_pool_advance``), nothing is uploaded or read back per step, and the
         stop flags are read every ``sync_every`` steps.  The same outputs; with ``sync_every = K > 1`` a result is
-        delivered, and its slot taken again, up to ``K - 1`` steps after its state stopped."""
+        delivered, and its slot taken again, up to ``K - 1`` steps after its state stopped.
+
+        ``constraint``: ``generate``'s, one automaton for the whole stream; every ticket's output is
+        ``generate(source, ..., constraint=constraint)`` bit for bit.  With ``sync_every`` a ``ValueError``."""
+        if constraint is not None and sync_every is not None:
+            raise ValueError("a constraint together with the device books (sync_every) is not built yet")
+        ckw = self._constrained(constraint)
         if sync_every is not None:
             sync_every = _check_count("sync_every", sync_every, " (or None)")
             _check_room(max_length)
         return GenerateStream(self, num_beams, max_length, length_penalty,
-                              self.decoder.max_states(num_beams) if n_slots is None else n_slots, src_cap, sync_every)
+                              self.decoder.max_states(num_beams) if n_slots is None else n_slots, src_cap, sync_every,
+                              **ckw)
 
     def sample(self, ids: np.ndarray, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
                top_p: float = 1.0, seed: int = 0, length_penalty: float = 0.0, sync_every: int = 16,
-               params: Optional[SamplingParams] = None) -> BeamSearchOutput:
+               params: Optional[SamplingParams] = None, constraint=None) -> BeamSearchOutput:
         """``num_samples`` sampled continuations of one source (``sample_many`` with one state; ``params``: this
-        source's ``SamplingParams`` in place of the three scalars)."""
+        source's ``SamplingParams`` in place of the three scalars; ``constraint``: as there)."""
         return self.sample_many([ids], num_samples, max_length, temperature, top_k, top_p, [seed], length_penalty,
-                                sync_every, None if params is None else [params])[0]
+                                sync_every, None if params is None else [params], constraint=constraint)[0]
 
     def sample_many(self, sources, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
                     top_p: float = 1.0, seeds=None, length_penalty: float = 0.0,
-                    sync_every: int = 16, params=None) -> List[BeamSearchOutput]:
+                    sync_every: int = 16, params=None, constraint=None) -> List[BeamSearchOutput]:
         """Temperature / top-k / top-p sampling (``generate(do_sample=True, num_return_sequences=num_samples)``'s warper
         chain with a stated order and random number, DESIGN.md section 9 "Sampling") for several sources through one
         decode loop with no per-step readback.  ``seeds[i]`` (default ``0..n-1``) is source ``i``'s 32-bit seed.  Entry
@@ -971,12 +1059,18 @@ class HipT5Generator:
         source, None standing for the call's ``temperature`` / ``top_k`` / ``top_p``.  The sources' blocks form the
         parameter table, uploaded once, and every step is ``rp_sample_step_rows``: row ``b`` of entry ``i`` is the same
         bits as row ``b`` of ``sample(sources[i], ...)`` at that row's own three values (DESIGN.md section 9,
-        "Sampling parameters per request")."""
+        "Sampling parameters per request").
+
+        ``constraint`` (a ``constraint.ByteAutomaton``, shared by every source; None: none): the rows' automaton states
+        live on the device and one ``rp_constraint_mask_step`` launch between every step and the sampler advances them
+        and writes ``-inf`` over the forbidden log-probs, which the sampler then gives no mass (DESIGN.md section 9
+        "Constrained decoding").  Nothing is read back; the scores stay sums of the model's own log-probs."""
         check_sampling(temperature, top_k, top_p)
         if num_samples < 1 or max_length <= 1:
             raise ValueError(f"num_samples={num_samples} (>= 1), max_length={max_length} (>= 2)")
         if sync_every < 1:
             raise ValueError(f"sync_every={sync_every} must be >= 1")
+        ckw = self._constrained(constraint, fused=True)
         sources = list(sources)
         table = None
         if params is not None:
@@ -999,11 +1093,11 @@ class HipT5Generator:
             lambda lp, active, t, state: dec.sample_step(lp, active, t, state, temperature, int(top_k), top_p, eos, 0),
             n, num_samples, max_length, seeds, length_penalty, eos_token_id=eos,
             decoder_start_token_id=self._start, pad_token_id=0, sync_every=sync_every,
-            device=self.device, params=table)
+            device=self.device, params=table, **ckw)
 
     def sample_stream(self, num_samples: int, max_length: int, temperature: float = 1.0, top_k: int = 0,
                       top_p: float = 1.0, length_penalty: float = 0.0, n_slots: Optional[int] = None, src_cap: int = 2048,
-                      sync_every: int = 16, per_request: bool = False) -> "SampleStream":
+                      sync_every: int = 16, per_request: bool = False, constraint=None) -> "SampleStream":
         """A running sampled search that sources join while it runs (continuous batching): a
         ``SampleStream`` of ``n_slots`` places (default ``HipT5Decoder.max_states(num_samples)``) for sources of at most
         ``src_cap`` tokens, its books on the device (``generation.SamplePool``, ``rp_sample_pool_step``), nothing uploaded
@@ -1016,8 +1110,12 @@ class HipT5Generator:
         num_samples)`` takes a ``SamplingParams`` per ticket (None: the stream's three) and any ``1 <= num_samples <=``
         the stream's (None: the stream's), and the ticket's output is ``sample(source, that num_samples, ..., seed,
         params=those)``, bit for bit.  The stream then carries the parameter table on the device
-        (``rp_sample_pool_step_rows``), written at admission only."""
+        (``rp_sample_pool_step_rows``), written at admission only.
+
+        ``constraint``: ``sample_many``'s, one automaton for the whole stream (``rp_constraint_mask_step`` with the
+        slots' own positions; a slot's next tenant starts in the start state at its position 0)."""
         check_sampling(temperature, top_k, top_p)
+        ckw = self._constrained(constraint, fused=True)
         if num_samples < 1 or max_length <= 1:
             raise ValueError(f"num_samples={num_samples} (>= 1), max_length={max_length} (>= 2)")
         sync_every = _check_count("sync_every", sync_every)
@@ -1025,7 +1123,7 @@ class HipT5Generator:
             _check_count("n_slots", n_slots, " (or None)")
         return SampleStream(self, num_samples, max_length, temperature, int(top_k), top_p, length_penalty,
                             self.decoder.max_states(num_samples) if n_slots is None else n_slots, src_cap, sync_every,
-                            bool(per_request))
+                            bool(per_request), **ckw)
 
 
 class GenerateStream:
@@ -1037,17 +1135,19 @@ class GenerateStream:
     points."""
 
     def __init__(self, generator: HipT5Generator, num_beams: int, max_length: int, length_penalty: float, n_slots: int,
-                 src_cap: int, sync_every: Optional[int] = None):
+                 src_cap: int, sync_every: Optional[int] = None, constraint=None, mask=None):
         dec = self._open(generator, n_slots, num_beams, max_length, src_cap)
         kw = dict(eos_token_id=generator._eos, decoder_start_token_id=generator._start, select_many=dec.select_many,
                   device=generator.device)
         if sync_every is not None:
             self.pool = BeamBooksPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
                                       sync_every=sync_every, books_admit=dec.beam_books_admit,
-                                      advance=dec.beam_pool_advance, rows=dec.beam_books_rows, **kw)
+                                      advance=dec.beam_pool_advance, rows=dec.beam_books_rows, constraint=constraint,
+                                      **kw)  # (with a constraint: BeamBooksPool's own refusal)
         else:
             self.pool = BeamSearchPool(self._admit, self._step, n_slots, num_beams, max_length, length_penalty,
-                                       prefill=self._prefill, **kw)
+                                       prefill=self._prefill, **kw,
+                                       **({} if constraint is None else dict(constraint=constraint, mask=mask)))
 
     def _open(self, generator: HipT5Generator, n_slots: int, nb: int, max_length: int, src_cap: int) -> HipT5Decoder:
         """Take the decoder's slot pool (beam and sample streams alike: whoever held it is retired)."""
@@ -1120,7 +1220,7 @@ class SampleStream(GenerateStream):
 
     def __init__(self, generator: HipT5Generator, num_samples: int, max_length: int, temperature: float, top_k: int,
                  top_p: float, length_penalty: float, n_slots: int, src_cap: int, sync_every: int,
-                 per_request: bool = False):
+                 per_request: bool = False, constraint=None, mask=None):
         dec = self._open(generator, n_slots, num_samples, max_length, src_cap)
         eos = generator._eos
         self.pool = SamplePool(
@@ -1130,7 +1230,8 @@ class SampleStream(GenerateStream):
             n_slots, num_samples, max_length, length_penalty,
             decoder_start_token_id=generator._start, pad_token_id=0, sync_every=sync_every,
             device=generator.device, books_admit=dec.sample_books_admit, rows=dec.sample_books_rows,
-            **(dict(per_request=True, params=SamplingParams(temperature, top_k, top_p)) if per_request else {}))
+            **(dict(per_request=True, params=SamplingParams(temperature, top_k, top_p)) if per_request else {}),
+            **({} if constraint is None else dict(constraint=constraint, mask=mask)))
         self.num_samples, self.per_request = int(num_samples), bool(per_request)
 
     def submit(self, ids, seed: int, params: Optional[SamplingParams] = None, num_samples: Optional[int] = None,

@@ -80,6 +80,101 @@ def topk_select(log_probs: torch.Tensor, running_scores: torch.Tensor, k: int):
     return vals, idx % V, torch.div(idx, V, rounding_mode="floor")
 
 
+# ---- constrained decoding: an automaton state per row, the forbidden log-probs overwritten with -inf ------------------------
+# Planted bugs of the constraint's bookkeeping, so that tests can show a comparison would notice them: "state_by_row" takes
+# a candidate's automaton state from the launch row it sits in instead of its parent beam (``_BeamState.advance``) or the
+# (state, sample) entry (``constraint_mask_step_host``); "admit_not_reset" leaves a slot's states as its last tenant left
+# them (no reset at position 0); "mask_wrong_row" masks row r by the state of row r + 1; "eos_anywhere" lets EOS through in
+# a state that does not accept.
+CONSTRAINT_MUTANTS = ("state_by_row", "admit_not_reset", "mask_wrong_row", "eos_anywhere")
+
+
+def _mask_rows(log_probs: torch.Tensor, q: torch.Tensor, constraint, mutant: Optional[str]) -> torch.Tensor:
+    """``log_probs [rows, vocab]`` with ``-inf`` (in place) wherever ``constraint.next[q[r], v] < 0``; every other entry
+    keeps its bits."""
+    table = constraint.device_table(log_probs.device)
+    if log_probs.shape[1] != table.shape[1]:
+        raise ValueError(f"a constraint over {table.shape[1]} ids for log-probs over {log_probs.shape[1]}")
+    q = q.to(device=log_probs.device, dtype=torch.int64).clamp(0, table.shape[0] - 1)
+    if mutant == "mask_wrong_row":
+        q = torch.roll(q, -1)
+    forbidden = table[q] < 0
+    if mutant == "eos_anywhere":
+        forbidden[:, constraint.eos] = False
+    log_probs.masked_fill_(forbidden, float("-inf"))
+    return log_probs
+
+
+def constraint_mask_host(log_probs: torch.Tensor, q_rows: torch.Tensor, constraint, mutant: Optional[str] = None
+                         ) -> torch.Tensor:
+    """``rp_constraint_mask`` on any device's tensors: row ``r`` of ``log_probs`` masked by state ``q_rows[r]`` (values
+    clamped into the table, as the kernel does).  In place; returns ``log_probs``.  ``mutant``: ``CONSTRAINT_MUTANTS``."""
+    assert mutant is None or mutant in CONSTRAINT_MUTANTS, mutant
+    assert q_rows.numel() == log_probs.shape[0], (q_rows.shape, log_probs.shape)
+    return _mask_rows(log_probs, q_rows.reshape(-1), constraint, mutant)
+
+
+def constraint_mask_step_host(log_probs: torch.Tensor, active: Sequence[int], pos: Sequence[int], tokens_in: torch.Tensor,
+                              q: torch.Tensor, constraint, mutant: Optional[str] = None) -> torch.Tensor:
+    """``rp_constraint_mask_step`` on any device's tensors: ``q`` int32 ``[n, nb]`` by (state, sample).  Row ``a * nb + b``
+    of slot ``active[a]``: at ``pos[a] == 0`` its state becomes 0, else it moves to ``next[q][tokens_in[row]]`` where that
+    is ``>= 0`` and stays where it is not; the new state is stored and masks the row.  Values are clamped as the kernel
+    clamps them.  In place; returns ``log_probs``.  ``mutant``: ``CONSTRAINT_MUTANTS``."""
+    assert mutant is None or mutant in CONSTRAINT_MUTANTS, mutant
+    n, nb = q.shape
+    assert len(active) == len(pos) and len(set(active)) == len(active) and all(0 <= s < n for s in active)
+    rows = len(active) * nb
+    assert log_probs.shape[0] == rows and tokens_in.numel() >= rows and all(p >= 0 for p in pos)
+    table = constraint.device_table(q.device)
+    S, V = table.shape
+    at = (torch.tensor(list(active), dtype=torch.int64, device=q.device)[:, None] * nb
+          + torch.arange(nb, dtype=torch.int64, device=q.device)[None]).reshape(-1)
+    if mutant == "state_by_row":
+        at = torch.arange(rows, dtype=torch.int64, device=q.device)
+    flat = q.view(-1)
+    old = flat[at].long().clamp(0, S - 1)
+    tok = tokens_in.reshape(-1)[:rows].to(device=q.device, dtype=torch.int64).clamp(0, V - 1)
+    to = table[old, tok].long()
+    new = torch.where(to >= 0, to.clamp(max=S - 1), old)
+    if mutant != "admit_not_reset":
+        first = torch.tensor([p == 0 for p in pos], device=q.device).repeat_interleave(nb)
+        new = torch.where(first, torch.zeros_like(new), new)
+    flat[at] = new.to(flat.dtype)
+    return _mask_rows(log_probs, new, constraint, mutant)
+
+
+def _constraint_mask(constraint, mask: Optional[Callable], fused: bool, mutant: Optional[str] = None) -> Optional[Callable]:
+    """The loops' one ``mask`` callable: None without a constraint; else ``mask`` (the engine's launch) or the host
+    emulation over ``constraint``.  ``fused`` False: ``mask(log_probs, q_rows)``, the by-row states uploaded with the
+    step's tokens (the host-books loops).  ``fused`` True: ``mask(log_probs, active, pos, tokens_in, q)``, the states on
+    the device by (state, sample) (the sampled loops)."""
+    if constraint is None:
+        if mask is not None:
+            raise ValueError("mask= without constraint=")
+        return None
+    if mask is not None:
+        return mask
+    mutant = mutant if mutant in CONSTRAINT_MUTANTS else None
+    if fused:
+        return lambda lp, active, pos, tokens_in, q: constraint_mask_step_host(lp, active, pos, tokens_in, q, constraint,
+                                                                               mutant)
+    return lambda lp, q_rows: constraint_mask_host(lp, q_rows, constraint, mutant)
+
+
+def _refuse_constraint(constraint, what: str) -> None:
+    if constraint is not None:
+        raise ValueError(f"a constraint together with {what} is not built yet")
+
+
+def _with_states(tokens: torch.Tensor, q_rows: torch.Tensor, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The step's tokens and its by-row automaton states in one upload: (tokens, int32 q_rows) on ``device``."""
+    rows = tokens.numel()
+    both = torch.cat([tokens.to(torch.int64), q_rows.to(torch.int64)])
+    if device is not None:
+        both = both.to(device)
+    return both[:rows], both[rows:].to(torch.int32)
+
+
 def _prompt_tokens(prompt) -> List[int]:
     """A decoder prompt (the tokens after the start token; None: none) as a list of ints."""
     if prompt is None:
@@ -172,9 +267,9 @@ class _BeamState:
 
     def __init__(self, num_beams: int, max_length: int, length_penalty: float, eos_token_id: int,
                  decoder_start_token_id: int, num_return_sequences: Optional[int],
-                 prompt: Optional[Sequence[int]] = None, mutant: Optional[str] = None):
-        assert mutant is None or mutant in PROMPT_MUTANTS, mutant
-        self.mutant = mutant
+                 prompt: Optional[Sequence[int]] = None, mutant: Optional[str] = None, constraint=None):
+        assert mutant is None or mutant in PROMPT_MUTANTS + CONSTRAINT_MUTANTS, mutant
+        self.mutant, self.constraint = mutant, constraint
         nb = self.nb = int(num_beams)
         self.nret = nb if num_return_sequences is None else int(num_return_sequences)
         assert 1 <= self.nret <= nb
@@ -206,6 +301,8 @@ class _BeamState:
                                             torch.zeros(self.keep - nb, dtype=torch.bool)])
         # the prompt's cache rows are shared by all beams: one row per prompt position, beam 0's (p * nb)
         self.ancestry = (torch.arange(P, dtype=torch.int64) * nb)[None].repeat(nb, 1)
+        if constraint is not None:  # an automaton state per running beam; a prompt the automaton rejects raises here
+            self.q = torch.full((nb,), constraint.state_after(prompt), dtype=torch.int64)
 
     def inputs(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """(tokens [nb], ancestry [nb, t + 1]) of the step at position ``t = cur_len - 1``."""
@@ -245,6 +342,10 @@ class _BeamState:
         # the cache reorder (:3478-3489) is a reorder of the ancestry table here
         src = parents[nxt]
         self.ancestry = self.ancestry[src]
+        if self.constraint is not None:  # next[old[parent], token] of the nb kept beams (a dead candidate's stays)
+            old = self.q[torch.arange(self.keep) % nb if self.mutant == "state_by_row" else parents]
+            to = self.constraint.table()[old, toks].long()
+            self.q = torch.where(to >= 0, to, old)[nxt]
         self.running_seq, self.running_bi, self.running_scores = new_running_seq, new_running_bi, running_scores
         self.cur_len = cur_len = cur_len + 1
         # _check_early_stop_heuristic (:3008-3053), early_stopping=False: best length = cur_len - prompt_len
@@ -266,13 +367,14 @@ def beam_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], num_
                 length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
                 num_return_sequences: Optional[int] = None, select: Callable = topk_select,
                 device=None, trace: Optional[list] = None, prompt: Optional[Sequence[int]] = None,
-                prefill: Optional[Callable] = None, mutant: Optional[str] = None) -> BeamSearchOutput:
+                prefill: Optional[Callable] = None, mutant: Optional[str] = None, constraint=None,
+                mask: Optional[Callable] = None) -> BeamSearchOutput:
     """Beam search over ``step`` (module docstring): ``beam_search_batch`` with one state.  ``trace``, when a list,
     receives the per-step top-``2 nb`` candidates ``(scores, tokens, parents)`` as host tensors.
 
     ``prompt``: decoder tokens after the start token that every returned sequence begins with (HF's
     ``decoder_input_ids = [start] + prompt``); ``prefill(rows)`` writes the prompt's cache rows (``beam_search_batch``),
-    by default through ``step`` (``prefill_by_steps``)."""
+    by default through ``step`` (``prefill_by_steps``).  ``constraint`` / ``mask``: as in ``beam_search_batch``."""
     traces: Optional[list] = None if trace is None else []
     step_one = lambda active, tokens, ancestry, pos=None: step(tokens, ancestry)  # noqa: E731
     out, = beam_search_batch(step_one, 1, num_beams, max_length,
@@ -280,7 +382,7 @@ def beam_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], num_
                              lambda lp, running, nb, k: tuple(x[None] for x in select(lp, running, k)), device, traces,
                              prompts=None if prompt is None else [prompt],
                              prefill_many=None if prefill is None else (lambda states, rows: prefill(rows[0])),
-                             mutant=mutant)
+                             mutant=mutant, constraint=constraint, mask=mask)
     if trace is not None:
         trace.extend(traces[0])
     return out
@@ -296,10 +398,16 @@ def topk_select_many(log_probs: torch.Tensor, running_scores: torch.Tensor, nb: 
 def _beam_inputs(states: Sequence[_BeamState], nb: int, device=None):
     """The host-books step's ``(tokens [n * nb], ancestry [n * nb, W], running scores [n * nb], pos)`` over ``states``:
     ``pos[a]`` is the position of ``states[a]``, ``W`` the widest ``pos + 1``, a narrower state's ancestry rows
-    right-padded with zeros (columns ``0..pos[a]`` are its own).  The tensors are moved to ``device`` when there is one."""
+    right-padded with zeros (columns ``0..pos[a]`` are its own).  The tensors are moved to ``device`` when there is one.
+    The fifth value is None, or with constrained states their automaton states by row (int32 ``[n * nb]``), which travel
+    in the tokens' upload."""
     ins = [st.inputs() for st in states]
     pos = [st.cur_len - 1 for st in states]
     tokens = torch.cat([x[0] for x in ins])
+    if states[0].constraint is not None:
+        tokens, q_rows = _with_states(tokens, torch.cat([st.q for st in states]), device)
+    else:
+        q_rows = None
     running = torch.cat([st.running_scores for st in states])
     if min(pos) == max(pos):
         ancestry = torch.cat([x[1] for x in ins])
@@ -309,7 +417,7 @@ def _beam_inputs(states: Sequence[_BeamState], nb: int, device=None):
             ancestry[a * nb : (a + 1) * nb, : anc.shape[1]] = anc
     if device is not None:
         tokens, ancestry, running = tokens.to(device), ancestry.to(device), running.to(device)
-    return tokens, ancestry, running, pos
+    return tokens, ancestry, running, pos, q_rows
 
 
 def _beam_take(states: Sequence[_BeamState], selected, traces: Optional[Sequence[list]] = None) -> List[bool]:
@@ -330,7 +438,8 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
                       eos_token_id: int = 1, decoder_start_token_id: int = 0,
                       num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
                       traces: Optional[list] = None, prompts: Optional[Sequence] = None,
-                      prefill_many: Optional[Callable] = None, mutant: Optional[str] = None) -> List[BeamSearchOutput]:
+                      prefill_many: Optional[Callable] = None, mutant: Optional[str] = None, constraint=None,
+                      mask: Optional[Callable] = None) -> List[BeamSearchOutput]:
     """The search loop: ``num_states`` sources in lockstep, one ``step_many`` and one ``select_many`` per position, one
     readback of the ``n_active x 2 nb`` triples.  Every state keeps its own bookkeeping (``_BeamState``) and leaves the
     active list at the step where it would stop alone; the loop runs until the last one has.
@@ -350,10 +459,17 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
     ``step_many``, one state and one position at a time (``prefill_by_steps``).  With any prompt the loop hands
     ``step_many`` a position per active state, ``step_many(active, tokens, ancestry, pos=pos)``, and pads the ancestry
     table as ``BeamSearchPool.step`` does: state ``i`` stands at ``P_i + k`` after ``k`` steps.  Without prompts the
-    loop is the one above, call for call.  ``mutant``: one of ``PROMPT_MUTANTS``."""
+    loop is the one above, call for call.  ``mutant``: one of ``PROMPT_MUTANTS`` or ``CONSTRAINT_MUTANTS``.
+
+    ``constraint`` (a ``constraint.ByteAutomaton``; None: the loop above, call for call): every state keeps an automaton
+    state per running beam (after its prompt: ``state_after(prompt)``, a rejected prompt a ``ValueError`` before anything
+    is launched), the by-row states go up with the step's tokens, and ``mask(log_probs, q_rows)`` overwrites the
+    forbidden entries with ``-inf`` between the step and the selection (default ``constraint_mask_host``; the engine
+    passes ``rp_constraint_mask``)."""
     prompts = _check_prompts(prompts, num_states, max_length)
+    mask = _constraint_mask(constraint, mask, False, mutant)
     states = [_BeamState(num_beams, max_length, length_penalty, eos_token_id, decoder_start_token_id,
-                         num_return_sequences, None if prompts is None else prompts[i], mutant)
+                         num_return_sequences, None if prompts is None else prompts[i], mutant, constraint)
               for i in range(num_states)]
     per_state = [[] for _ in states]
     active = list(range(num_states))
@@ -364,11 +480,13 @@ def beam_search_batch(step_many: Callable, num_states: int, num_beams: int, max_
                          [prompts[i] for i in listed], decoder_start_token_id, nb, device)
     while active:
         stepped = [states[i] for i in active]
-        tokens, ancestry, running, pos = _beam_inputs(stepped, nb, device)
+        tokens, ancestry, running, pos, q_rows = _beam_inputs(stepped, nb, device)
         if prompts is None:
             log_probs = step_many(list(active), tokens, ancestry)
         else:
             log_probs = step_many(list(active), tokens, ancestry, pos=pos)
+        if mask is not None:
+            log_probs = mask(log_probs, q_rows)
         stopped = _beam_take(stepped, select_many(log_probs, running, nb, 2 * nb),
                              None if traces is None else [per_state[i] for i in active])
         active = [i for i, over in zip(active, stopped) if not over]
@@ -506,13 +624,17 @@ class BeamSearchPool(_SlotPool):
     def __init__(self, admit: Callable, step: Callable, n_slots: int, num_beams: int, max_length: int,
                  length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
                  num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
-                 mutant: Optional[str] = None, prefill: Optional[Callable] = None):
-        assert mutant is None or mutant in POOL_MUTANTS, mutant
+                 mutant: Optional[str] = None, prefill: Optional[Callable] = None, constraint=None,
+                 mask: Optional[Callable] = None):
+        assert mutant is None or mutant in POOL_MUTANTS + CONSTRAINT_MUTANTS, mutant
         super().__init__(n_slots, "num_beams", num_beams, max_length)
+        self.constraint, self._mask = constraint, _constraint_mask(constraint, mask, False, mutant)
+        state_mutant = mutant if mutant in CONSTRAINT_MUTANTS else None
         self._admit, self._step, self._select_many, self._prefill = admit, step, select_many, prefill
         self.device, self.mutant, self._start_token = device, mutant, decoder_start_token_id
         self._new_state = lambda prompt=None: _BeamState(num_beams, max_length, length_penalty, eos_token_id,
-                                                         decoder_start_token_id, num_return_sequences, prompt)
+                                                         decoder_start_token_id, num_return_sequences, prompt,
+                                                         state_mutant, constraint)
         self._prompt: dict = {}                                       # ticket -> its decoder prompt, where it has one
         self._state: List[Optional[_BeamState]] = [None] * self.n_slots  # per slot in use: its tenant's books
 
@@ -523,6 +645,8 @@ class BeamSearchPool(_SlotPool):
         prompt = _prompt_tokens(prompt)
         if self.max_length <= 1 + len(prompt):
             raise ValueError(_no_room(self.max_length, len(prompt)))
+        if self.constraint is not None:
+            self.constraint.state_after(prompt)  # a rejected prompt: ValueError before it is queued
         ticket = self._issue(source)
         if prompt:
             self._prompt[ticket] = prompt
@@ -548,10 +672,12 @@ class BeamSearchPool(_SlotPool):
             return []
         nb = self.nb
         states = [self._state[s] for s in active]
-        tokens, ancestry, running, pos = _beam_inputs(states, nb, self.device)
+        tokens, ancestry, running, pos, q_rows = _beam_inputs(states, nb, self.device)
         if self.mutant == "shared_position":
             pos = [max(pos)] * len(pos)
         log_probs = self._step(list(active), pos, tokens, ancestry)
+        if self._mask is not None:
+            log_probs = self._mask(log_probs, q_rows)
         stopped = _beam_take(states, self._select_many(log_probs, running, nb, 2 * nb))
         self.steps += 1
         done = []
@@ -792,8 +918,8 @@ def beam_search_batch_device(step_many: Callable, select_many: Callable, advance
                              num_beams: int, max_length: int, length_penalty: float = 1.0, eos_token_id: int = 1,
                              decoder_start_token_id: int = 0, num_return_sequences: Optional[int] = None,
                              sync_every: int = 16, device=None, init: Optional[Callable] = None,
-                             to_host: Callable = lambda x: x.cpu(), prompts: Optional[Sequence] = None
-                             ) -> List[BeamSearchOutput]:
+                             to_host: Callable = lambda x: x.cpu(), prompts: Optional[Sequence] = None,
+                             constraint=None) -> List[BeamSearchOutput]:
     """``beam_search_batch`` with the books on the device (``BeamBooks``): per position one ``step_many``, one
     ``select_many`` and one ``advance``, nothing uploaded but their arguments and nothing read back.  Every
     ``sync_every`` positions the ``num_states`` ``done`` flags are read once and the stopped states leave the active
@@ -810,8 +936,12 @@ def beam_search_batch_device(step_many: Callable, select_many: Callable, advance
     - ``select_many(log_probs, running, nb, k)``: as in ``beam_search_batch``.
     - ``advance(books, active, t, scores, tokens, parents, fin_div, run_div, eos)``: ``rp_beam_advance``
       (``beam_advance_host`` on the host).
-    - ``to_host``: the loop's every device-to-host copy goes through it (tests count them)."""
+    - ``to_host``: the loop's every device-to-host copy goes through it (tests count them).
+
+    ``constraint``: a ``ValueError`` (not built yet): after a device-side ``advance`` the automaton states would have to
+    follow the parents that advance chose ("Constrained decoding")."""
     _refuse_prompts(prompts, "the device books (sync_every)")
+    _refuse_constraint(constraint, "the device books (sync_every)")
     n, nb = int(num_states), int(num_beams)
     nret = nb if num_return_sequences is None else int(num_return_sequences)
     _check_room(max_length)
@@ -888,8 +1018,10 @@ class BeamBooksPool(_SlotPool):
                  length_penalty: float = 1.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
                  num_return_sequences: Optional[int] = None, select_many: Callable = topk_select_many, device=None,
                  sync_every: int = 16, books_admit: Optional[Callable] = None, advance: Optional[Callable] = None,
-                 rows: Optional[Callable] = None, to_host: Callable = lambda x: x.cpu(), mutant: Optional[str] = None):
+                 rows: Optional[Callable] = None, to_host: Callable = lambda x: x.cpu(), mutant: Optional[str] = None,
+                 constraint=None):
         assert mutant is None or mutant in POOL_BOOKS_MUTANTS, mutant
+        _refuse_constraint(constraint, "the device books (sync_every)")
         super().__init__(n_slots, "num_beams", num_beams, max_length, sync_every)
         self.nret = self.nb if num_return_sequences is None else int(num_return_sequences)
         if not 1 <= self.nret <= self.nb:
@@ -948,7 +1080,8 @@ class BeamBooksPool(_SlotPool):
 
 def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], max_length: int, eos_token_id: int = 1,
                   decoder_start_token_id: int = 0, device=None, prompt: Optional[Sequence[int]] = None,
-                  prefill: Optional[Callable] = None) -> BeamSearchOutput:
+                  prefill: Optional[Callable] = None, constraint=None, mask: Optional[Callable] = None
+                  ) -> BeamSearchOutput:
     """``generate(num_beams=1, do_sample=False, max_length=L)``, which HF runs as greedy search (``_sample`` without
     sampling), not as a one-beam beam search: the argmax token (ties to the lowest id) until EOS or ``max_length``
     tokens including the start token.  After an EOS candidate a beam search keeps looking and may return a longer
@@ -958,12 +1091,14 @@ def greedy_search(step: Callable[[torch.Tensor, torch.Tensor], torch.Tensor], ma
     return greedy_search_batch(lambda active, tokens, ancestry, pos=None: step(tokens, ancestry), 1, max_length,
                                eos_token_id, decoder_start_token_id, device,
                                prompts=None if prompt is None else [prompt],
-                               prefill_many=None if prefill is None else (lambda states, rows: prefill(rows[0])))[0]
+                               prefill_many=None if prefill is None else (lambda states, rows: prefill(rows[0])),
+                               constraint=constraint, mask=mask)[0]
 
 
 def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, eos_token_id: int = 1,
                         decoder_start_token_id: int = 0, device=None, prompts: Optional[Sequence] = None,
-                        prefill_many: Optional[Callable] = None) -> List[BeamSearchOutput]:
+                        prefill_many: Optional[Callable] = None, constraint=None, mask: Optional[Callable] = None
+                        ) -> List[BeamSearchOutput]:
     """The greedy loop (``greedy_search``'s semantics per source): ``num_states`` sources in lockstep, one beam each,
     one ``step_many`` (as in ``beam_search_batch``) and one readback of the active states' log-prob rows per position.
     A state leaves the active list at its EOS; the loop ends with the last one or at ``max_length``.
@@ -971,9 +1106,15 @@ def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, e
     ``prompts`` / ``prefill_many``: as in ``beam_search_batch`` with one beam.  State ``i`` starts at position ``P_i``
     with ``[start] + prompt`` as its sequence and ``step_many`` is handed ``pos=``; without prompts every state stands
     at the same position and ``pos=`` is not passed.  Either way a state leaves at its EOS or when its sequence holds
-    ``max_length`` tokens."""
+    ``max_length`` tokens.
+
+    ``constraint`` / ``mask``: as in ``beam_search_batch`` with one beam - an automaton state per source, uploaded with the
+    step's tokens, the row masked before it is read back."""
     _check_room(max_length)
     prompts = _check_prompts(prompts, num_states, max_length)
+    mask = _constraint_mask(constraint, mask, False)
+    if constraint is not None:  # (a rejected prompt: ValueError before anything is launched)
+        q = [constraint.state_after(prompts[i] if prompts is not None else []) for i in range(num_states)]
     seqs = [[int(decoder_start_token_id)] for _ in range(num_states)]
     totals = [0.0] * num_states
     active = list(range(num_states))
@@ -988,14 +1129,23 @@ def greedy_search_batch(step_many: Callable, num_states: int, max_length: int, e
         tokens = torch.tensor([seqs[i][-1] for i in active], dtype=torch.int64)
         cols = torch.arange(max(pos) + 1, dtype=torch.int64)[None]
         anc = cols * (cols <= torch.tensor(pos, dtype=torch.int64)[:, None])  # row a: 0..pos[a], then zeros
-        if device is not None:
+        if mask is not None:
+            tokens, q_rows = _with_states(tokens, torch.tensor([q[i] for i in active], dtype=torch.int64), device)
+            anc = anc if device is None else anc.to(device)
+        elif device is not None:
             tokens, anc = tokens.to(device), anc.to(device)
         kw = {} if prompts is None else dict(pos=pos)
-        lps = step_many(list(active), tokens, anc, **kw).float().cpu()
+        lps = step_many(list(active), tokens, anc, **kw)
+        if mask is not None:
+            lps = mask(lps, q_rows)
+        lps = lps.float().cpu()
         still = []
         for a, i in enumerate(active):
             lp = lps[a]
             best = int(torch.nonzero(lp == lp.max())[0, 0])
+            if mask is not None:
+                to = int(constraint.next[q[i], best])
+                q[i] = to if to >= 0 else q[i]
             totals[i] += float(lp[best])
             seqs[i].append(best)
             if best != eos_token_id and len(seqs[i]) < max_length:
@@ -1083,7 +1233,8 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
                         seeds: Sequence[int], length_penalty: float = 0.0, eos_token_id: int = 1,
                         decoder_start_token_id: int = 0, pad_token_id: int = 0, sync_every: int = 16,
                         device=None, params: Optional[torch.Tensor] = None,
-                        prompts: Optional[Sequence] = None) -> List[BeamSearchOutput]:
+                        prompts: Optional[Sequence] = None, constraint=None, mask: Optional[Callable] = None,
+                        mutant: Optional[str] = None) -> List[BeamSearchOutput]:
     """The sampling loop: ``num_states`` sources in lockstep with ``num_samples`` independent rows each; per position one
     ``step_many`` and one ``sample_step``, nothing read back.  Every ``sync_every`` positions the finished flags are
     read once and the states whose samples have all finished leave the active list; the loop ends when it is empty or
@@ -1106,8 +1257,16 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
 
     Returns per state ``sequences [num_samples, out_len]`` (start token first, pad after EOS, trimmed to the state's
     longest sample) in sample order and ``sequences_scores = cum_logprob / n_generated ** length_penalty`` (the
-    finished-beam formula; the default 0.0 gives the sum)."""
+    finished-beam formula; the default 0.0 gives the sum).
+
+    ``constraint`` (a ``constraint.ByteAutomaton``; None: the loop above, call for call): the rows' automaton states live
+    on the device, int32 ``[num_states, num_samples]`` by (state, sample), and between ``step_many`` and ``sample_step``
+    ``mask(log_probs, active, [t] * n_active, tokens, q)`` advances them by the tokens the step was fed and overwrites the
+    forbidden entries with ``-inf`` (default ``constraint_mask_step_host``; the engine passes
+    ``rp_constraint_mask_step``).  Nothing is read back.  The sampler gives a ``-inf`` entry no mass, and ``cum_logprob``
+    stays the model's own log-prob of the drawn token.  ``mutant``: one of ``CONSTRAINT_MUTANTS`` (host default)."""
     _refuse_prompts(prompts, "sampling")
+    mask = _constraint_mask(constraint, mask, True, mutant)
     n, nb = int(num_states), int(num_samples)
     _check_room(max_length)
     if len(seeds) != n:
@@ -1134,11 +1293,15 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
         if st.params is not None:
             st.params = st.params.to(device)  # the search's one upload of the table
         ancestry = ancestry.to(device)
+    if mask is not None:
+        q = torch.zeros((n, nb), dtype=torch.int32, device=device)
     active = list(range(n))
     t = 0
     while active and t + 1 < max_length:
         rows = len(active) * nb
         log_probs = step_many(list(active), st.tokens[:rows], ancestry[:rows], t)
+        if mask is not None:
+            log_probs = mask(log_probs, list(active), [t] * len(active), st.tokens[:rows], q)
         sample_step(log_probs, list(active), t, st)
         t += 1
         if t % sync_every == 0 and t + 1 < max_length:
@@ -1160,14 +1323,17 @@ def sample_search_batch(step_many: Callable, sample_step: Callable, num_states: 
 def sample_search(step: Callable, sample_step: Callable, num_samples: int, max_length: int, seed: int = 0,
                   length_penalty: float = 0.0, eos_token_id: int = 1, decoder_start_token_id: int = 0,
                   pad_token_id: int = 0, sync_every: int = 16, device=None,
-                  params: Optional[torch.Tensor] = None, prompt: Optional[Sequence[int]] = None) -> BeamSearchOutput:
+                  params: Optional[torch.Tensor] = None, prompt: Optional[Sequence[int]] = None, constraint=None,
+                  mask: Optional[Callable] = None, mutant: Optional[str] = None) -> BeamSearchOutput:
     """``sample_search_batch`` with one state: ``step(tokens, ancestry, t)``, ``sample_step`` as there; ``params`` is the
     state's int32 ``[num_samples, 4]`` block (``SamplingParams.rows``) or None.  (A decoder ``prompt`` is beam search's
-    and greedy's: a ``ValueError`` here, as ``prompts`` is in ``sample_search_batch``.)"""
+    and greedy's: a ``ValueError`` here, as ``prompts`` is in ``sample_search_batch``.)  ``constraint`` / ``mask`` /
+    ``mutant``: as there."""
     _refuse_prompts([prompt], "sampling")
     return sample_search_batch(lambda active, tokens, ancestry, t: step(tokens, ancestry, t), sample_step, 1,
                                num_samples, max_length, [seed], length_penalty, eos_token_id, decoder_start_token_id,
-                               pad_token_id, sync_every, device, None if params is None else params[None])[0]
+                               pad_token_id, sync_every, device, None if params is None else params[None],
+                               constraint=constraint, mask=mask, mutant=mutant)[0]
 
 
 # ---- continuous batching for the sampled search: a position per slot ---------------------------------------------------
@@ -1300,11 +1466,17 @@ class SamplePool(_SlotPool):
                  max_length: int, length_penalty: float = 0.0, decoder_start_token_id: int = 0, pad_token_id: int = 0,
                  sync_every: int = 16, device=None, books_admit: Optional[Callable] = None,
                  rows: Optional[Callable] = None, to_host: Callable = lambda x: x.cpu(), mutant: Optional[str] = None,
-                 per_request: bool = False, params: Optional[SamplingParams] = None):
-        assert mutant is None or mutant in SAMPLE_POOL_MUTANTS + SAMPLE_PARAMS_MUTANTS, mutant
+                 per_request: bool = False, params: Optional[SamplingParams] = None, constraint=None,
+                 mask: Optional[Callable] = None):
+        assert mutant is None or mutant in SAMPLE_POOL_MUTANTS + SAMPLE_PARAMS_MUTANTS + CONSTRAINT_MUTANTS, mutant
         assert per_request or (params is None and mutant not in SAMPLE_PARAMS_MUTANTS), "these need per_request=True"
         super().__init__(n_slots, "num_samples", num_samples, max_length, sync_every)
         n, nb, L = self.n_slots, self.nb, self.max_length
+        # the constraint (None: the pool above, call for call): the rows' automaton states by (state, sample) on the
+        # device; a slot's next tenant starts clean because its first step stands at position 0
+        self._mask = _constraint_mask(constraint, mask, True, mutant)
+        if self._mask is not None:
+            self.q = torch.zeros((n, nb), dtype=torch.int32, device=device)
         self.length_penalty, self.mutant = length_penalty, mutant
         self.start, self.pad = decoder_start_token_id, pad_token_id
         self._admit, self._step, self._sample_step, self._to_host = admit, step, sample_step, to_host
@@ -1392,5 +1564,7 @@ class SamplePool(_SlotPool):
     def _launch(self, active: List[int], pos: List[int]) -> None:
         rows = len(active) * self.nb
         log_probs = self._step(active, pos, self.state.tokens[:rows], self.ancestry[:rows])
+        if self._mask is not None:
+            log_probs = self._mask(log_probs, list(active), list(pos), self.state.tokens[:rows], self.q)
         self._sample_step(log_probs, active, [pos[0]] * len(pos) if self.mutant == "shared_position" else list(pos),
                           self.state)

@@ -7,9 +7,10 @@ with ``PremiseRetriever`` and generates from the augmented state.  No ``transfor
 from __future__ import annotations
 
 import asyncio
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 from ..common import Pos, format_augmented_state, remove_marks, zip_strict
+from ..constraint import ByteAutomaton
 from ..decoder import HipT5Generator
 from ..generation import SamplingParams, check_sampling
 from ..retrieval.model import PremiseRetriever
@@ -64,7 +65,8 @@ class HuggingFaceGenerator(TacticGenerator):
                  top_p: float = 1.0, seed: int = 0, beam_sync_every: Optional[int] = None, continuous: bool = False,
                  continuous_slots: Optional[int] = None, sample_stream: bool = False,
                  sample_stream_slots: Optional[int] = None, sample_sync_every: int = 16,
-                 per_request_sampling: bool = False, sample_stream_samples: Optional[int] = None):
+                 per_request_sampling: bool = False, sample_stream_samples: Optional[int] = None,
+                 valid_utf8: bool = False, banned: Sequence[str] = ()):
         self.model_path = model_path
         self.device = device
         self.max_inp_seq_len = max_inp_seq_len
@@ -99,6 +101,16 @@ class HuggingFaceGenerator(TacticGenerator):
             raise ValueError(f"sample_stream_samples={sample_stream_samples} must be an integer >= 1 (or None) and needs "
                              "per_request_sampling=True")
         self.per_request_sampling, self.sample_stream_samples = bool(per_request_sampling), sample_stream_samples
+        # constrained decoding (defaults: none, every engine call as it was): the tactics are well-formed UTF-8 and / or
+        # hold none of the ``banned`` strings - one automaton, ``utf8 & ban``, handed to every engine call
+        if isinstance(banned, (str, bytes)):
+            raise ValueError(f"banned={banned!r} is one string: a sequence of strings is expected")
+        self.valid_utf8, self.banned = bool(valid_utf8), tuple(banned)
+        if any(not isinstance(b, str) or not b for b in self.banned):
+            raise ValueError(f"banned={banned!r} must hold non-empty strings")
+        if (self.valid_utf8 or self.banned) and beam_sync_every is not None:
+            raise ValueError("valid_utf8 / banned together with beam_sync_every (the device books) is not built yet")
+        self._automaton = None
         self._stream = None       # the open GenerateStream (or SampleStream) and its num_samples
         self._stream_beams: Optional[int] = None
         self._waiters: Dict[int, "asyncio.Future"] = {}  # ticket -> the generate() call that awaits it
@@ -132,6 +144,18 @@ class HuggingFaceGenerator(TacticGenerator):
             raise ValueError(f"sampling holds {len(sampling)} entries for {n} states (one SamplingParams or None each)")
         return sampling
 
+    def _constraint(self) -> Dict:
+        """The engine calls' ``constraint=`` keyword: nothing without ``valid_utf8`` / ``banned``, else the one automaton
+        (built at first use over the engine's vocabulary; ByT5's 384 ids where the engine names none)."""
+        if not (self.valid_utf8 or self.banned):
+            return {}
+        if self._automaton is None:
+            vocab = int(getattr(self.generator, "cfg", {}).get("vocab_size", 384))
+            parts = ([ByteAutomaton.utf8(vocab)] if self.valid_utf8 else []) + (
+                [ByteAutomaton.ban(self.banned, vocab)] if self.banned else [])
+            self._automaton = parts[0] if len(parts) == 1 else parts[0] & parts[1]
+        return {"constraint": self._automaton}
+
     def _prefix_ids(self, prefix: Optional[str]) -> Optional[List[int]]:
         """A tactic prefix as decoder prompt tokens: its UTF-8 bytes + 3, no EOS (None or "": no prompt, the call as it
         always was).  Refused with ``do_sample``, with ``beam_sync_every``, and when the start token and the prefix leave
@@ -156,7 +180,7 @@ class HuggingFaceGenerator(TacticGenerator):
             sampling = None  # the object's parameters throughout: the call as it always was
         for i in range(0, len(ids), cap):
             chunk = ids[i : i + cap]
-            kw = {} if sampling is None else {"params": sampling[i : i + cap]}
+            kw = dict({} if sampling is None else {"params": sampling[i : i + cap]}, **self._constraint())
             outs = self.generator.sample_many(chunk, num_samples, self.max_oup_seq_len, self.temperature, self.top_k,
                                               self.top_p, self._next_seeds(len(chunk)), self.length_penalty, **kw)
             results.extend(self._sampled_suggestions(out) for out in outs)
@@ -192,7 +216,7 @@ class HuggingFaceGenerator(TacticGenerator):
         ids = encode_one(state, self.max_inp_seq_len)  # tokenizer(state, max_length=..., truncation=True)
         if self.do_sample:
             return self._sampled([ids], num_samples, None if sampling is None else [sampling])[0]
-        kw = {} if prompt is None else {"prefix": prompt}
+        kw = dict({} if prompt is None else {"prefix": prompt}, **self._constraint())
         out = self.generator.generate(ids, num_samples, self.max_oup_seq_len, self.length_penalty, **self._books, **kw)
         return self._suggestions(out, num_samples)
 
@@ -232,11 +256,12 @@ class HuggingFaceGenerator(TacticGenerator):
                                                             self.top_k, self.top_p, self.length_penalty,
                                                             n_slots=self.sample_stream_slots,
                                                             src_cap=self.max_inp_seq_len,
-                                                            sync_every=self.sample_sync_every)
+                                                            sync_every=self.sample_sync_every, **self._constraint())
             else:
                 self._stream = self.generator.generate_stream(num_samples, self.max_oup_seq_len, self.length_penalty,
                                                               n_slots=self.continuous_slots,
-                                                              src_cap=self.max_inp_seq_len, **self._books)
+                                                              src_cap=self.max_inp_seq_len, **self._books,
+                                                              **self._constraint())
             self._stream_beams = num_samples
         future = asyncio.get_running_loop().create_future()
         # (a sampled call's seed is taken here, at submit time: in call order)
@@ -269,7 +294,8 @@ class HuggingFaceGenerator(TacticGenerator):
             self._stream = self.generator.sample_stream(rows, self.max_oup_seq_len, self.temperature, self.top_k,
                                                         self.top_p, self.length_penalty,
                                                         n_slots=self.sample_stream_slots, src_cap=self.max_inp_seq_len,
-                                                        sync_every=self.sample_sync_every, per_request=True)
+                                                        sync_every=self.sample_sync_every, per_request=True,
+                                                        **self._constraint())
             self._stream_beams = rows
         future = asyncio.get_running_loop().create_future()
         ticket = self._stream.submit(ids, self._next_seeds(1)[0], params=sampling, num_samples=num_samples)
@@ -320,7 +346,7 @@ class HuggingFaceGenerator(TacticGenerator):
         results: List[List[Tuple[str, float]]] = []
         cap = self.generator.decoder.max_states(num_samples)  # the engine's cap on states per call
         for i in range(0, len(ids), cap):
-            kw = {} if prompts is None else {"prefixes": prompts[i : i + cap]}
+            kw = dict({} if prompts is None else {"prefixes": prompts[i : i + cap]}, **self._constraint())
             outs = self.generator.generate_many(ids[i : i + cap], num_samples, self.max_oup_seq_len,
                                                 self.length_penalty, **self._books, **kw)
             results.extend(self._suggestions(out, num_samples) for out in outs)
@@ -340,7 +366,8 @@ class RetrievalAugmentedGenerator(TacticGenerator):
                  beam_sync_every: Optional[int] = None, continuous: bool = False,
                  continuous_slots: Optional[int] = None, sample_stream: bool = False,
                  sample_stream_slots: Optional[int] = None, sample_sync_every: int = 16,
-                 per_request_sampling: bool = False, sample_stream_samples: Optional[int] = None) -> None:
+                 per_request_sampling: bool = False, sample_stream_samples: Optional[int] = None,
+                 valid_utf8: bool = False, banned: Sequence[str] = ()) -> None:
         self.gen_path = gen_path
         self.ret_path = ret_path
         self.indexed_corpus_path = indexed_corpus_path
@@ -356,7 +383,8 @@ class RetrievalAugmentedGenerator(TacticGenerator):
                                            sample_stream_slots=sample_stream_slots,
                                            sample_sync_every=sample_sync_every,
                                            per_request_sampling=per_request_sampling,
-                                           sample_stream_samples=sample_stream_samples)
+                                           sample_stream_samples=sample_stream_samples, valid_utf8=valid_utf8,
+                                           banned=banned)
 
     def initialize(self) -> None:
         self.hf_gen.initialize()

@@ -470,6 +470,45 @@ def prefix_bench(gen, cfg, prefix_bytes, reps, max_len=512, src_bytes=2048, n_sl
     return res
 
 
+def constraint_bench(gen, cfg, reps, max_len=512, src_bytes=2048):
+    """The same call with and without ``constraint=ByteAutomaton.utf8`` (one ``rp_constraint_mask`` /
+    ``rp_constraint_mask_step`` launch more per step), alternating in one process: greedy, 8 and 64 beams, 64 samples.
+    Device milliseconds between two events round the whole call, and per decode step (the two searches need not take
+    the same number of steps)."""
+    from reprover_amd.constraint import ByteAutomaton
+
+    aut = ByteAutomaton.utf8(cfg["vocab_size"])
+    rng = np.random.default_rng(0)
+    src = np.concatenate([rng.integers(3, 259, size=src_bytes - 1), [1]]).astype(np.int32)
+    calls = {
+        "greedy": lambda kw: gen.greedy(src, max_len, **kw),
+        "beams8": lambda kw: gen.generate(src, 8, max_len, 0.0, **kw),
+        "beams64": lambda kw: gen.generate(src, 64, max_len, 0.0, **kw),
+        "samples64": lambda kw: gen.sample(src, 64, max_len, 1.0, 0, 1.0, seed=1, **kw),
+    }
+    res = {"metric": "gen_constraint_bench", "config": f"byt5-small, source {src_bytes} bytes, max_length {max_len}, utf8 "
+           f"automaton of {aut.n_states} states", "reps": reps, "rows": {}}
+    for name, call in calls.items():
+        for kw in ({}, {"constraint": aut}):  # warm-up: code objects, the table's upload
+            call(kw)
+        ms = {"free": [], "utf8": []}
+        steps = {}
+        for _ in range(reps):
+            for arm, kw in (("free", {}), ("utf8", {"constraint": aut})):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                out = call(kw)
+                e1.record()
+                torch.cuda.synchronize()
+                ms[arm].append(round(e0.elapsed_time(e1), 2))
+                steps[arm] = int(out.sequences.shape[1]) - 1
+        res["rows"][name] = {"free_ms": ms["free"], "utf8_ms": ms["utf8"], "steps": steps,
+                             "free_us_per_step": round(1e3 * float(np.median(ms["free"])) / steps["free"], 1),
+                             "utf8_us_per_step": round(1e3 * float(np.median(ms["utf8"])) / steps["utf8"], 1)}
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -486,7 +525,21 @@ def main(argv=None):
                     help="with --stream --sample: the stream's scalars against the same values per ticket (the parameter table)")
     ap.add_argument("--prefix-bytes", type=int, nargs="+", default=None,
                     help="the one-pass prompt prefill against prefill_by_steps, and a stream's admission step with a prefix")
+    ap.add_argument("--constraint", choices=["utf8"], default=None,
+                    help="the same calls with and without the constraint, alternating (goes alone)")
     args = ap.parse_args(argv)
+    if args.constraint:
+        if args.prefix_bytes or args.states or args.stream or args.sample or args.sync_every:
+            ap.error("--constraint goes alone")
+        cfg = synth.seq2seq_config("byt5-small")
+        gen = HipT5Generator(cfg, synth.synth_seq2seq_state_dict(cfg), "cuda:0")
+        line = json.dumps(constraint_bench(gen, cfg, max(args.reps, 5)))
+        print(line)
+        args.out = args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                            "gen_constraint_bench.json")
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+        return
     if args.prefix_bytes:
         if min(args.prefix_bytes) < 1 or max(args.prefix_bytes) > 500 or args.states or args.stream or args.sample:
             ap.error("--prefix-bytes takes values in 1..500 and goes alone")
