@@ -483,6 +483,37 @@ RpStatus rp_dbg_gemm_ex(const void* A, int32_t lda, const void* W, int32_t n_row
                         int32_t np_out, int32_t* plan, void* stream);
 /* The current value of an option rp_set_option knows by a variable of its own (not the compound gemm_variant_all). */
 RpStatus rp_dbg_get_option(const char* name, int32_t* value);
+/* The similarity scan's plan, without a GPU call (tests/test_scan_plan_cpu.py, tests/test_scan_tiles_gpu.py): what
+ * rp_sim_topk[_fp8][_after] would launch for (B, N, D, k, flags) under the current options - fp8 != 0: the e4m3 entry points,
+ * paged != 0: the _after ones.  The arguments are checked as those calls check them (same status, same message).
+ * out: HOST int64 [RP_SIM_PLAN_FIELDS], indexed by RpSimPlanField.  Pass 0 is the dense pass or the sample pass, pass 1 the
+ * filter pass (tile -1, 0 workgroups when dense-only); stage 0 is the select behind pass 0, stage 1 the per-query stage behind
+ * pass 1 (-1 when dense-only). */
+typedef enum {
+  /* first-generation kernel (queries are the MFMA rows): dense, sample and fallback filter passes */
+  RP_SIM_TILE_Q256 = 0, RP_SIM_TILE_Q128W8, RP_SIM_TILE_Q128K32W8, RP_SIM_TILE_Q64, RP_SIM_TILE_Q32,
+  RP_SIM_TILE_SAMPLE, RP_SIM_TILE_SAMPLE_K64W8, RP_SIM_TILE_SAMPLE_Q32, RP_SIM_TILE_SAMPLE_BIG,
+  RP_SIM_TILE_8Q256, RP_SIM_TILE_8Q128W8, RP_SIM_TILE_8Q64, RP_SIM_TILE_8Q64_TAIL, RP_SIM_TILE_8Q32, RP_SIM_TILE_8Q32_TAIL,
+  RP_SIM_TILE_8SAMPLE, RP_SIM_TILE_8SAMPLE_K64W8, RP_SIM_TILE_8SAMPLE_K64_TAILW8, RP_SIM_TILE_8SAMPLE_Q32,
+  RP_SIM_TILE_8SAMPLE_Q32_TAIL,
+  /* second-generation filter kernel (premises are the MFMA rows); each has a paged twin */
+  RP_SIM_TILE_FILTER_NT8, RP_SIM_TILE_8FILTER_W8, RP_SIM_TILE_8FILTER_TAILW8,
+  RP_SIM_TILE_COUNT
+} RpSimTile;
+typedef enum {
+  RP_SIM_STAGE_SELECT = 0,   /* select_kernel, 1024 threads */
+  RP_SIM_STAGE_SELECT_SMALL, /* select_kernel, 256 threads */
+  RP_SIM_STAGE_GATHER,       /* gather_select_kernel, 1024 threads */
+  RP_SIM_STAGE_GATHER_MID,   /* gather_select_kernel, 512 threads */
+  RP_SIM_STAGE_GATHER_SMALL  /* gather_select_kernel, 256 threads */
+} RpSimStage;
+typedef enum {
+  RP_SIM_PLAN_DENSE_ONLY = 0, RP_SIM_PLAN_NEW_FILTER, RP_SIM_PLAN_STRIDE, RP_SIM_PLAN_SAMPLE_BLOCKS, RP_SIM_PLAN_FILTER_BLOCKS,
+  RP_SIM_PLAN_CAP, RP_SIM_PLAN_BYTES, RP_SIM_PLAN_TILE0, RP_SIM_PLAN_WGS0, RP_SIM_PLAN_TILE1, RP_SIM_PLAN_WGS1,
+  RP_SIM_PLAN_PAGED_FILTER /* pass 1 runs the paged twin of its filter tile */, RP_SIM_PLAN_STAGE0, RP_SIM_PLAN_STAGE1,
+  RP_SIM_PLAN_FIELDS
+} RpSimPlanField;
+RpStatus rp_dbg_sim_plan(int32_t B, int32_t N, int32_t D, int32_t k, int32_t flags, int32_t fp8, int32_t paged, int64_t* out);
 RpStatus rp_dbg_attention_ex(const void* qkv_bf16, const int32_t* cu_seqlens, const float* bias_tab, void* out_bf16, int32_t batch,
                              int32_t num_heads, int32_t rows_total, int32_t max_distance, int32_t ntab, void* stream);
 RpStatus rp_dbg_encoder_rows(int32_t mode, const void* a, const void* b, const void* c, const void* d, const int32_t* ia,

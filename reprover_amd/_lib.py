@@ -17,6 +17,13 @@ LIB_PATH = os.path.join(_HERE, "lib", "libreprover_hip.so")
 RP_OK = 0
 RP_DT_F32, RP_DT_BF16 = 0, 1
 RP_TOPK_AUTO, RP_TOPK_DENSE = 0, 1
+# rp_dbg_sim_plan (tests): RpSimTile, RpSimStage and RpSimPlanField of include/reprover_hip.h, in the header's order
+SIM_TILES = ("Q256", "Q128W8", "Q128K32W8", "Q64", "Q32", "SAMPLE", "SAMPLE_K64W8", "SAMPLE_Q32", "SAMPLE_BIG", "8Q256", "8Q128W8",
+             "8Q64", "8Q64_TAIL", "8Q32", "8Q32_TAIL", "8SAMPLE", "8SAMPLE_K64W8", "8SAMPLE_K64_TAILW8", "8SAMPLE_Q32",
+             "8SAMPLE_Q32_TAIL", "FILTER_NT8", "8FILTER_W8", "8FILTER_TAILW8")
+SIM_STAGES = ("SELECT", "SELECT_SMALL", "GATHER", "GATHER_MID", "GATHER_SMALL")
+SIM_PLAN_FIELDS = ("dense_only", "new_filter", "stride", "sample_blocks", "filter_blocks", "cap", "bytes", "tile0", "wgs0", "tile1",
+                   "wgs1", "paged_filter", "stage0", "stage1")
 RP_EPI_STORE_BF16, RP_EPI_RESID, RP_EPI_GEGLU_BF16, RP_EPI_RESID8 = 0, 1, 2, 3
 ABI_VERSION = 7  # 7: the tactic generator's decoder (rp_decoder_*, rp_beam_select, rp_encode_hidden); 5 was skipped
 KERNEL_CLASSES = ["embed", "rmsnorm", "gemm_qkv", "attention", "gemm_o", "gemm_wi", "gemm_wo", "pool", "scan",
@@ -303,6 +310,7 @@ SIGNATURES = {
          C.POINTER(C.c_int32), C.c_void_p],
     ),
     "rp_dbg_get_option": (C.c_int32, [C.c_char_p, C.POINTER(C.c_int32)]),
+    "rp_dbg_sim_plan": (C.c_int32, [C.c_int32] * 7 + [C.POINTER(C.c_int64)]),
     "rp_dbg_attention_ex": (
         C.c_int32,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],

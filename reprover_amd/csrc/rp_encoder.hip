@@ -122,10 +122,7 @@ const Option g_options[] = {
     {"gemm_mixed_bwd", &g_gemm_mixed_bwd, ANY_LO, ANY_HI, OPT_BOOL, nullptr},
     {"gemm_skinny", &g_gemm_skinny, ANY_LO, ANY_HI, OPT_BOOL, nullptr},
     {"scan_cfg", &g_scan_cfg, 0, 1, OPT_PLAIN, nullptr},
-#ifdef RP_EXPERIMENTS  // knobs of measured-and-rejected alternatives and timing probes: probe builds only
-    {"scan_filter_cfg", &g_scan_filter_cfg, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
-    {"scan_sample_cfg", &g_scan_sample_cfg, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
-    {"scan_waves", &g_scan_waves, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
+#ifdef RP_EXPERIMENTS  // timing probes: probe builds only
     {"scan_stride", &g_scan_stride, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
     {"train_dbg", &g_train_dbg, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},
     {"scan_no_epilogue", &g_scan_no_epilogue, ANY_LO, ANY_HI, OPT_PLAIN, nullptr},

@@ -16,7 +16,7 @@ namespace rp {
 // the others in rp_encoder.hip
 extern int g_gemm_group_m, g_gemm_variant, g_gemm_variant_qkv, g_gemm_variant_wo, g_gemm_variant_o, g_debug_skip_ffn, g_gemm_skinny,
     g_gemm_skinny_variant, g_gemm_small_pipe, g_gemm_helpers, g_gemm_persist, g_pool_chunk, g_gemm_edge_layout, g_gemm_mixed,
-    g_gemm_mixed_bwd, g_scan_waves, g_scan_small_tiles, g_scan_cfg, g_scan_impl, g_scan_filter_cfg, g_scan_sample_cfg, g_scan_stride,
+    g_gemm_mixed_bwd, g_scan_small_tiles, g_scan_cfg, g_scan_impl, g_scan_stride,
     g_scan_no_epilogue, g_scan_impl_force_new, g_scan_cap, g_train_dbg, g_train_wgrad_form;
 extern int g_gemm_stagger_us[RP_K_COUNT];
 

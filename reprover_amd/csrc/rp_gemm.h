@@ -58,12 +58,12 @@ struct GemmCfg {
   // 256 registers per lane, at most 80 KiB of LDS): the hardware scheduler then runs one workgroup's main loop under the
   // other's prologue / hand-over stalls / epilogue.  0: whatever the register allocation allows.
   static constexpr int OCC = OCC_;
-  // KTAIL = 1 (gemm_tile_pipe): K may end half a k-tile early (K % BK == BK / 2).  The last tile then carries only its
-  // first half: the lanes whose 16-byte chunk lies in the missing half fetch the chunk BK/2 earlier instead (a duplicate,
-  // never multiplied, never out of bounds) and the tile runs half its k-steps.
+  // KTAIL = 1 (gemm_tile, e4m3 operands): K may end half a k-tile early (K % BK == BK / 2).  The last tile then carries only
+  // its first half: the lanes whose 16-byte chunk lies in the missing half fetch the chunk BK/2 earlier instead (a duplicate,
+  // never multiplied, never out of bounds) and the upper k-steps of that tile multiply zeros.
   static constexpr int KTAIL = KTAIL_;
   static constexpr int AAUX = AAUX_;  // cache-policy bits of the A operand's LDS-DMA (2 = nt: streamed once)
-  // FP8 = 1: the operands are e4m3 bytes, addressed as if they were bf16 rows of half the length (BK,
+  // FP8 = 1 (gemm_tile): the operands are e4m3 bytes, addressed as if they were bf16 rows of half the length (BK,
   // K and the operands' ld all count 2-byte units); only the fragment reads and the MFMA differ.
   static constexpr int FP8 = FP8_;
   static constexpr int BM = BM_, BN = BN_, BK = BK_, WM = WM_, WN = WN_, NSTAGE = NSTAGE_;
@@ -177,8 +177,10 @@ __device__ __forceinline__ void gemm_tile(const GemmOperand A, const GemmOperand
     const int kc = (lane % C::SLOTS) ^ C::swz(row);
     w_src[d] = W.ptr + W.row_off(tile_n * C::BN + row, kc);
   }
-  // KTAIL (as in gemm_tile_pipe): K % BK is 0 or BK / 2; in the half tile the lanes whose 16-byte chunk lies beyond K fetch the
-  // chunk 64 bytes earlier (a duplicate, never out of bounds) and the upper k-steps' A fragments are zeroed by selects
+  // KTAIL: K % BK is 0 or BK / 2; in the half tile the lanes whose 16-byte chunk lies beyond K fetch the chunk 64 bytes earlier
+  // (a duplicate, never out of bounds) and the upper k-steps' A fragments are zeroed by selects.  With 128-byte rows (8 rows,
+  // 8 chunks per DMA piece) the swizzle's top bit is the parity of the piece index, so the chunk lies in the upper half iff
+  // ((lane >> 2) ^ piece) & 1: two values per lane, one for even and one for odd pieces.
   static_assert(C::KTAIL == 0 || (BK == 64 && C::SLOTS == 8 && C::ROWS_PER_DMA == 8 && C::FP8 != 0), "KTAIL: 128-byte e4m3 rows");
   const int nk = C::KTAIL != 0 ? (K + BK / 2) / BK : K / BK;
   const bool has_tail = C::KTAIL != 0 && nk * BK != K;
@@ -309,11 +311,9 @@ template <class C, class Epilogue, class L = C>
 __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOperand W, int K, int tile_m,
                                                int tile_n, Epilogue& epi, char* smem) {
   static_assert(L::WM * L::WN == C::NWAVES && L::WM * L::FM * 32 <= C::BM && L::WN * L::FN * 32 <= C::BN, "wave layout");
-  // bf16: one MFMA k-step = 16 values = two 16-B slots of a row (one per lane half); e4m3: one k-step =
-  // 64 values = four slots (two per lane half), so a 128-B row holds 4 bf16 or 2 e4m3 k-steps.
-  constexpr int BK = C::BK, FM = L::FM, FN = L::FN, KS = C::FP8 ? C::ROW_BYTES / 64 : BK / 16;
-  constexpr int RPF = C::FP8 ? 2 : 1;  // ds_read_b128 per fragment
-  using frag_t = std::conditional_t<C::FP8 != 0, i32x8, bf16x8>;
+  static_assert(C::FP8 == 0 && C::KTAIL == 0, "bf16 operands, whole k-tiles: e4m3 and half k-tiles run the plain loop (gemm_tile)");
+  // one MFMA k-step = 16 values = two 16-B slots of a row (one per lane half)
+  constexpr int BK = C::BK, FM = L::FM, FN = L::FN, KS = BK / 16;
   RP_TS(0);
   static_assert(KS % 2 == 0 && KS >= 2, "even number of k-steps (fragment double-buffer parity)");
   const int tid = threadIdx.x;
@@ -344,24 +344,16 @@ __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOp
     const int kc = (lane % C::SLOTS) ^ C::swz(row);
     w_src[d] = W.ptr + W.row_off(tile_n * C::BN + row, kc);
   }
-  const int nk = C::KTAIL != 0 ? (K + BK / 2) / BK : K / BK;  // (KTAIL: K % BK is 0 or BK / 2)
-  const bool has_tail = C::KTAIL != 0 && nk * BK != K;
-  // tail tile: element offset added to the DMA source of lanes whose chunk lies beyond K (0 for the others).  With 128-byte
-  // rows (8 rows, 8 chunks per DMA piece) the swizzle's top bit is the parity of the piece index, so the chunk lies in the
-  // upper half iff ((lane >> 2) ^ piece) & 1: two values per lane, one for even and one for odd pieces.
-  static_assert(C::KTAIL == 0 || (BK == 64 && C::SLOTS == 8 && C::ROWS_PER_DMA == 8), "KTAIL: 128-byte rows");
-  const int fix_lane = (lane >> 2) & 1;
+  const int nk = K / BK;
   if constexpr (has_prologue<Epilogue>::value) epi.prologue(smem + C::RING_BYTES, wave, lane, tile_n * C::BN);
   // half 0: the A image of a stage, half 1: the W image (issued one k-step apart, see tile_body)
   auto stage_half = [&](int kt, int buf, int half) {
     char* base = smem + buf * C::STAGE_BYTES;
     RP_PROBE_STAGE_FILTER(kt, half);
-    const int fix_mask = (C::KTAIL != 0 && has_tail && kt == nk - 1) ? -1 : 0;  // (scalar)
     if (half == 0) {
 #pragma unroll
       for (int d = 0; d < C::A_DMA; ++d) {
         const bf16_t* src = a_src[d] + A.k_off(kt, BK);
-        if constexpr (C::KTAIL != 0) src += ((((fix_lane ^ (wave * C::A_DMA + d)) & 1) ? -(BK / 2) : 0) & fix_mask);
         if constexpr (C::AAUX == 2)
           __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(base + (wave * C::A_DMA + d) * 1024), 16, 0, 2);
         else
@@ -371,7 +363,6 @@ __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOp
 #pragma unroll
       for (int d = 0; d < C::W_DMA; ++d) {
         const bf16_t* src = w_src[d] + W.k_off(kt, BK);
-        if constexpr (C::KTAIL != 0) src += ((((fix_lane ^ (wave * C::W_DMA + d)) & 1) ? -(BK / 2) : 0) & fix_mask);
         __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)(base + C::A_BYTES + (wave * C::W_DMA + d) * 1024), 16, 0, 0);
       }
     }
@@ -381,61 +372,30 @@ __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOp
     stage_half(kt, buf, 1);
   };
 
-  int a_off[FM][KS * RPF], b_off[FN][KS * RPF];
+  int a_off[FM][KS], b_off[FN][KS];
 #pragma unroll
-  for (int ks = 0; ks < KS * RPF; ++ks) {
-    // bf16: slot 2 ks + hi.  e4m3: k-step s = ks / 2 takes slots 4 s + 2 hi + {0, 1} (both operands split alike)
-    const int slot = C::FP8 ? ((ks >> 1) * 4 + hi * 2 + (ks & 1)) : (ks * 2 + hi);
+  for (int ks = 0; ks < KS; ++ks) {
+    const int slot = ks * 2 + hi;
 #pragma unroll
     for (int f = 0; f < FM; ++f) a_off[f][ks] = C::off(wave_row * (FM * 32) + f * 32 + (lane & 31), slot);
 #pragma unroll
     for (int f = 0; f < FN; ++f) b_off[f][ks] = C::A_BYTES + C::off(wave_col * (FN * 32) + f * 32 + (lane & 31), slot);
   }
 
-  frag_t af[2][FM], bfr[2][FN];  // double-buffered fragments, parity = k-step & 1
+  bf16x8 af[2][FM], bfr[2][FN];  // double-buffered fragments, parity = k-step & 1
   RP_PROBE_READS_DECL;
   auto read_frags = [&](const char* st, int ks, int p) {
     RP_PROBE_READS_GATE;
-    if constexpr (C::FP8 != 0) {
 #pragma unroll
-      for (int f = 0; f < FM; ++f) {
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(st + a_off[f][2 * ks]);
-        const i32x4 up = *reinterpret_cast<const i32x4*>(st + a_off[f][2 * ks + 1]);
-        af[p][f] = i32x8{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
-      }
+    for (int f = 0; f < FM; ++f) af[p][f] = *reinterpret_cast<const bf16x8*>(st + a_off[f][ks]);
 #pragma unroll
-      for (int f = 0; f < FN; ++f) {
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(st + b_off[f][2 * ks]);
-        const i32x4 up = *reinterpret_cast<const i32x4*>(st + b_off[f][2 * ks + 1]);
-        bfr[p][f] = i32x8{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
-      }
-    } else {
-#pragma unroll
-      for (int f = 0; f < FM; ++f) af[p][f] = *reinterpret_cast<const bf16x8*>(st + a_off[f][ks]);
-#pragma unroll
-      for (int f = 0; f < FN; ++f) bfr[p][f] = *reinterpret_cast<const bf16x8*>(st + b_off[f][ks]);
-    }
-  };
-  auto zero_a_if = [&](int p, bool z) {
-#pragma unroll
-    for (int f = 0; f < FM; ++f)
-#pragma unroll
-      for (int e = 0; e < (int)(sizeof(frag_t) / 4); ++e) {
-        int v = reinterpret_cast<int*>(&af[p][f])[e];
-        reinterpret_cast<int*>(&af[p][f])[e] = z ? 0 : v;
-      }
+    for (int f = 0; f < FN; ++f) bfr[p][f] = *reinterpret_cast<const bf16x8*>(st + b_off[f][ks]);
   };
   auto mma = [&](int p) {
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        if constexpr (C::FP8 != 0)  // block-scaled MFMA with every E8M0 scale = 127 (2^0): e4m3 x e4m3 at the MX rate
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[p][i], bfr[p][j], acc[i][j], 0, 0, 0, 0x7f7f7f7f,
-                                                                      0, 0x7f7f7f7f);
-        else
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[p][i], bfr[p][j], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[p][i], bfr[p][j], acc[i][j], 0, 0, 0);
   };
 
   constexpr int NSTAGE = C::NSTAGE, DPS = C::A_DMA + C::W_DMA;
@@ -478,22 +438,16 @@ __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOp
     }
   };
   using NoDma = std::integral_constant<int, 0>;
-  using Reads = std::integral_constant<int, (FM + FN) * RPF>;
+  using Reads = std::integral_constant<int, FM + FN>;
   int buf = 0;
   auto tile_body = [&](int kt, auto mode_tag, auto pend_tag) {
     constexpr int MODE = decltype(mode_tag)::value;
     constexpr bool PEND = decltype(pend_tag)::value != 0;
     const char* st = smem + buf * C::STAGE_BYTES;
-    // KTAIL: the last tile of a K that ends half a tile early multiplies its lower k-steps only: the A fragments of the
-    // upper ones are replaced by zeros (selects, no branch: a branch around MFMAs made the register allocator copy
-    // accumulators), and acc + (+0 x b) is acc bit for bit - an accumulator that starts at +0 never holds -0, and the
-    // duplicate chunks the B side reads are finite values of the operand itself
-    const bool half_tile = C::KTAIL != 0 && MODE == 0 && has_tail;
 #pragma unroll
     for (int ks = 0; ks < KS - 1; ++ks) {
       read_frags(st, ks + 1, (ks + 1) & 1);
       if (PEND && ks == 0) stage_half(kt - 1 + NSTAGE, buf == 0 ? NSTAGE - 1 : buf - 1, 1);
-      if (C::KTAIL != 0 && MODE == 0 && ks >= KS / 2) zero_a_if(ks & 1, half_tile);
       mma(ks & 1);
       if (PEND && ks == 0)
         hint_order(Reads(), std::integral_constant<int, C::W_DMA>());
@@ -516,7 +470,6 @@ __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOp
       read_frags(smem + buf * C::STAGE_BYTES, 0, 0);
       if (MODE == 2) stage_half(kt + NSTAGE, freed, 0);
     }
-    if (C::KTAIL != 0 && MODE == 0) zero_a_if((KS - 1) & 1, half_tile);
     mma((KS - 1) & 1);
     if (MODE == 2)
       hint_order(Reads(), std::integral_constant<int, C::A_DMA>());
@@ -534,7 +487,7 @@ __device__ __forceinline__ void gemm_tile_pipe(const GemmOperand A, const GemmOp
     ++kt;
   }
   for (; kt + 1 < nk; ++kt) tile_body(kt, I1(), I0());
-  tile_body(kt, I0(), I0());  // (a half tile skips its upper k-steps inside the body: no second set of MFMA code)
+  tile_body(kt, I0(), I0());
   __syncthreads();
   RP_TS(2);
 

@@ -27,36 +27,23 @@ constexpr int SIM_MAX_K = 1024;
 constexpr int SIM_COUNT_STRIDE = 32;  // one candidate counter per 128-B line: contended atomics of different
                                       // queries must not serialise in the same L2 line
 constexpr int SIM_PB = 256;           // two-pass plan: premises are sampled / skipped in blocks of 256 rows
+// The tiles of the scan, one typedef per row of RpSimTile (include/reprover_hip.h); plan_sim picks them.  Tiles that were measured
+// and rejected are listed in DESIGN.md section 7.
 // Dense single-pass configurations (small shards, RP_TOPK_DENSE): BM queries x 128 premises, queries are the
 // MFMA row operand, premises the column operand (lane = premise: dense key rows are written coalesced).
 typedef GemmCfg<256, 128, 32, 4, 2, 3> SimCfgQ256;  // B > 128: 8 waves, one workgroup sees up to 256 queries
-typedef GemmCfg<128, 128, 64, 2, 2, 2> SimCfgQ128;  // B <= 128, D % 64 == 0
-typedef GemmCfg<128, 128, 32, 2, 2, 3> SimCfgQ128K32;  // B <= 128, D % 32 == 0
 // e4m3 index (rp_sim_topk_fp8): 64 fp8 values per K-step = the 64-B rows of the "BK = 32" geometry
 typedef GemmCfg<256, 128, 32, 4, 2, 3, 0, 1> SimCfg8Q256;
-typedef GemmCfg<128, 128, 32, 2, 2, 3, 0, 1> SimCfg8Q128;
 // Sample pass of the two-pass plan: 1/stride of the rows, as many small workgroups as possible (128 queries x
 // 64 premises, 6-deep ring: every workgroup is a latency-bound K loop, so depth and count are what matter).
-typedef GemmCfg<128, 64, 32, 2, 2, 6> SimCfgSample;
+typedef GemmCfg<128, 64, 32, 2, 2, 6> SimCfgSample;  // D % 64 != 0: 32-wide K slices
 typedef GemmCfg<128, 64, 32, 2, 2, 6, 0, 1> SimCfg8Sample;
-// Filter pass: the encoder's software-pipelined 256 x 256 x 64 tile (one wave per SIMD, 128 x 128 per wave) with
-// PREMISES as the MFMA row operand and QUERIES as the column operand: a lane then owns ONE query per column
-// fragment, so the per-query bound sits in 4 registers and the pre-test is one v_cmp per score (EpiSimFilter).
-typedef GemmCfg<256, 256, 64, 2, 2, 2, 1> SimCfgFilter;
-typedef GemmCfg<256, 256, 64, 2, 2, 2, 1, 1> SimCfg8Filter;
-// the same for rows that end half a k-tile early (D = 1472 e4m3 bytes = 11.5 tiles of 128): GemmCfg::KTAIL
-typedef GemmCfg<256, 256, 64, 2, 2, 2, 1, 1, 0, 1> SimCfg8FilterTail;
-// the same tile with 32-wide K slices in a 4-deep ring: three slices (48 KB of premises) in flight per CU instead of
-// one (32 KB) - the premise operand streams from HBM, not from L2 like an encoder GEMM's weights
-typedef GemmCfg<256, 256, 32, 2, 2, 4, 1> SimCfgFilterK32;
-typedef GemmCfg<128, 64, 64, 2, 2, 3> SimCfgSampleK64;
 // Round 6: the plain-loop tiles of this kernel run on EIGHT waves where their DMA split allows it (4 x 2: 32 queries per wave).
 // One wave per SIMD waited out every LDS round trip of its k-steps by itself (~900 cycles per 64-wide k-tile for 256 of MFMA);
 // with two per SIMD one multiplies while the other waits: sample pass at C2 23.3 -> 20.6 us, the first-generation filter pass
-// 90.7 -> 83.9 us for a single query and 129 -> 109 us at 64 queries, the same bits (profiles/r06_raw/exp28*).  The four-wave
-// forms stay selectable in probe builds (scan_waves = 4).
-typedef GemmCfg<128, 128, 64, 4, 2, 2> SimCfgQ128W8;
-typedef GemmCfg<128, 128, 32, 4, 2, 3> SimCfgQ128K32W8;
+// 90.7 -> 83.9 us for a single query and 129 -> 109 us at 64 queries, the same bits (profiles/r06_raw/exp28*).
+typedef GemmCfg<128, 128, 64, 4, 2, 2> SimCfgQ128W8;     // B <= 128, D % 64 == 0
+typedef GemmCfg<128, 128, 32, 4, 2, 3> SimCfgQ128K32W8;  // B <= 128, D % 32 == 0
 typedef GemmCfg<128, 128, 32, 4, 2, 3, 0, 1> SimCfg8Q128W8;
 typedef GemmCfg<128, 64, 64, 4, 2, 3> SimCfgSampleK64W8;
 typedef GemmCfg<128, 64, 64, 4, 2, 3, 0, 1> SimCfg8SampleK64W8;            // e4m3 rows of whole 128-byte k-tiles
@@ -77,33 +64,28 @@ typedef GemmCfg<32, 64, 64, 1, 2, 6, 0, 1, 0, 1> SimCfg8SampleQ32Tail;
 typedef GemmCfg<64, 128, 64, 2, 4, 3> SimCfgQ64;
 typedef GemmCfg<64, 128, 64, 2, 4, 3, 0, 1> SimCfg8Q64;
 typedef GemmCfg<64, 128, 64, 2, 4, 3, 0, 1, 0, 1> SimCfg8Q64Tail;
-typedef GemmCfg<32, 128, 64, 1, 4, 3> SimCfgQ32S3;   // (probe builds: three stages)
-typedef GemmCfg<32, 256, 64, 1, 4, 4> SimCfgQ32P256;  // (probe builds: 256 premises per tile, one workgroup per CU)
 // the sample pass when MANY queries share few rows (its 256 x 128 tiles fill the chip): MFMA-bound there, on the pipelined loop
 typedef GemmCfg<256, 128, 64, 4, 2, 2, 1> SimCfgSampleBig;
-// default: the premise stream (read once, by one CU) carries the nt cache policy: -7 % filter time
-typedef GemmCfg<256, 256, 64, 2, 2, 2, 1, 0, 2> SimCfgFilterNt;
-// the same tile on EIGHT waves, 2 x 4 (128 premises x 64 queries per wave: the epilogue's runs - 64 scores per lane and query,
-// part = 2 x premise half + lane half - do not change): two waves per SIMD, one multiplies while the other waits
+// Filter pass, second generation: the encoder's software-pipelined 256 x 256 x 64 tile with PREMISES as the MFMA row operand
+// and QUERIES as the column operand: a lane then owns ONE query per column fragment, so the per-query bound sits in 4
+// registers and the pre-test is one v_cmp per score (EpiSimFilter).  The premise stream (read once, by one CU) carries the
+// nt cache policy: -7 % filter time.  EIGHT waves, 2 x 4 (128 premises x 64 queries per wave: the epilogue's runs - 64 scores
+// per lane and query, part = 2 x premise half + lane half - are those of the four-wave tile this one replaced): two waves per
+// SIMD, one multiplies while the other waits.
 typedef GemmCfg<256, 256, 64, 2, 4, 2, 1, 0, 2> SimCfgFilterNt8;
 // The e4m3 tile on eight waves runs the PLAIN loop: the pipelined loop's double-buffered 32-byte fragments do not fit 256
 // registers beside 128 accumulators (192 bytes of scratch), one fragment set does (188 registers) - and with two waves per SIMD
 // the compiler-scheduled loop beats the hand-pipelined four-wave one: filter pass at 256 queries x 130 k rows of 1536 e4m3
 // bytes 76.7 -> 64.1 us, x 1 M rows 545 -> 487 us (configs[4]), 2048 queries x 16 k rows 65 -> 57 us, the same bits
-// (profiles/r06_raw/exp29*); rows that end half a k-tile early (1472 bytes): SimCfg8FilterTailW8, the same half-tile handling
-// as the pipelined loop's (GemmCfg::KTAIL).
+// (profiles/r06_raw/exp29*); rows that end half a k-tile early (D = 1472 e4m3 bytes = 11.5 tiles of 128): SimCfg8FilterTailW8
+// (GemmCfg::KTAIL).
 typedef GemmCfg<256, 256, 64, 2, 4, 2, 0, 1> SimCfg8FilterW8;
 typedef GemmCfg<256, 256, 64, 2, 4, 2, 0, 1, 0, 1> SimCfg8FilterTailW8;  // rows that end half a k-tile early (1472 e4m3 bytes)
 constexpr int SIM_FILTER_META_BYTES = 5120;  // per-tile metadata behind the ring (EpiSimFilter::prologue)
 int g_scan_cfg = 0;   // 0: auto; 1: force 128-query tiles in the dense path
 int g_scan_impl = 0;  // 0: auto (pipelined filter kernel when the shape allows); 1: first-generation filter kernel
 int g_scan_impl_force_new = 0;  // experiments: second-generation filter for every batch size
-int g_scan_filter_cfg = 0;   // experiments: 0 = 8 waves, nt premise stream (default), 1 = 256x256x32 4-stage, 2 = 4 waves, default cache policy,
-                             // 4 = 4 waves (the default until round 6)
 int g_scan_small_tiles = 1;  // tests / A-B runs: 0 = calls of at most 64 queries on the 128-query sample and filter tiles, as before round 6
-int g_scan_waves = 8;        // experiments: 4 = the four-wave forms of the plain-loop tiles
-int g_scan_sample_cfg = 0;   // experiments: 0 = 128x64x64 3-stage when D % 64 == 0, 32x64x64 at <= 32 queries (default), 1 = 128x64x32 6-stage
-                             // (a 6-stage 64-wide ring - five slices in flight - measured the same 23.5 us: not the depth)
 int g_scan_stride = 0;       // experiments: > 0 overrides the sampling stride (power of two)
 int g_scan_cap = 0;          // tests: > 0 overrides the candidate-list capacity (forces the overflow -> dense contract)
 int g_scan_no_epilogue = 0;  // timing only: the filter pass drops every score (main loop in isolation)
@@ -114,35 +96,35 @@ __device__ __forceinline__ uint64_t make_key(float score, int32_t id) {
 
 struct EpiSim {
   // premise side (NULL file_of => no accessibility mask)
-  const int32_t* file_of;
-  const int64_t* end_key;
-  int N;
+  const int32_t* file_of = nullptr;
+  const int64_t* end_key = nullptr;
+  int N = 0;
   // query side
-  const uint32_t* bits_t;  // [F, bits_words]
-  int bits_words;
-  const int32_t* own_file;
-  const int64_t* q_key;
-  int B;
-  int id_offset;
+  const uint32_t* bits_t = nullptr;  // [F, bits_words]
+  int bits_words = 0;
+  const int32_t* own_file = nullptr;
+  const int64_t* q_key = nullptr;
+  int B = 0;
+  int id_offset = 0;
   // e4m3 operands: score = acc * q_scale[query] * e_scale[premise] (NULL: bf16 operands, score = acc)
-  const float* q_scale;
-  const float* e_scale;
+  const float* q_scale = nullptr;
+  const float* e_scale = nullptr;
   // paging (rp_sim_topk_after): only keys strictly BELOW key(after_score[q], after_id[q]) qualify (NULL: no bound)
-  const float* after_score;
-  const int32_t* after_id;
+  const float* after_score = nullptr;
+  const int32_t* after_id = nullptr;
   // output
-  int filter;          // 0: dense write, 1: append keys > thr
-  uint64_t* dense;     // [B, dense_ld]
-  size_t dense_ld;
-  int slot_shift;      // slot = premise_row + slot_shift (set per workgroup)
-  const uint64_t* thr; // [B]
-  uint64_t* cand;      // [B, cap]
-  int cap;
-  int32_t* count;      // [B]
-  char* smem;          // GEMM LDS, free once the main loop is done
-  int tile_q0;         // first query of this workgroup's tile (set per workgroup)
-  int bm;              // queries per workgroup tile
-  int debug_skip;      // timing only: 64 = the dense (sample) pass writes nothing
+  int filter = 0;                 // 0: dense write, 1: append keys > thr
+  uint64_t* dense = nullptr;      // [B, dense_ld]
+  size_t dense_ld = 0;
+  int slot_shift = 0;             // slot = premise_row + slot_shift (set per workgroup)
+  const uint64_t* thr = nullptr;  // [B]
+  uint64_t* cand = nullptr;       // [B, cap]
+  int cap = 0;
+  int32_t* count = nullptr;       // [B]
+  char* smem = nullptr;           // GEMM LDS, free once the main loop is done (set per workgroup)
+  int tile_q0 = 0;                // first query of this workgroup's tile (set per workgroup)
+  int bm = 0;                     // queries per workgroup tile (set per workgroup)
+  int debug_skip = 0;             // timing only: 64 = the dense (sample) pass writes nothing
 
   // Accessibility predicate + key of one score.  imported/own exactly as common.py:280-289.
   __device__ __forceinline__ bool accessible(uint32_t word, int bit, int32_t f, int64_t ek, int32_t own,
@@ -448,23 +430,23 @@ __global__ __launch_bounds__(C::THREADS) void sim_filter_kernel(GemmOperand Eop,
 // four entries per thread in flight; the rare excess beyond the LDS list is handled entry by entry.
 // ------------------------------------------------------------------------------------------
 struct GatherArgs {
-  const uint2* slots;
-  const int32_t* scnt;
-  int filter_blocks, tiles_q, stride;
-  int N, B, id_offset;
-  const int32_t* file_of;  // NULL: no mask
-  const int64_t* end_key;
-  const uint32_t* bits_t;
-  int bits_words;
-  const int32_t* own_file;
-  const int64_t* q_key;
-  const uint64_t* thr;
-  const float* after_score;  // paging bound (NULL: none), as EpiSim
-  const int32_t* after_id;
-  uint64_t* cand;  // [B, cap]: entries [0, count) hold the sample's top keys on entry
-  size_t cap;
-  int32_t* count;  // [B * SIM_COUNT_STRIDE]
-  int debug;       // timing only: 8 = return at once, 16 = skip the entry loops of phase A, 32 = skip phase B
+  const uint2* slots = nullptr;
+  const int32_t* scnt = nullptr;
+  int filter_blocks = 0, tiles_q = 0, stride = 0;
+  int N = 0, B = 0, id_offset = 0;
+  const int32_t* file_of = nullptr;  // NULL: no mask
+  const int64_t* end_key = nullptr;
+  const uint32_t* bits_t = nullptr;
+  int bits_words = 0;
+  const int32_t* own_file = nullptr;
+  const int64_t* q_key = nullptr;
+  const uint64_t* thr = nullptr;
+  const float* after_score = nullptr;  // paging bound (NULL: none), as EpiSim
+  const int32_t* after_id = nullptr;
+  uint64_t* cand = nullptr;  // [B, cap]: entries [0, count) hold the sample's top keys on entry
+  size_t cap = 0;
+  int32_t* count = nullptr;  // [B * SIM_COUNT_STRIDE]
+  int debug = 0;             // timing only: 8 = return at once, 16 = skip the entry loops of phase A, 32 = skip phase B
 };
 
 // ------------------------------------------------------------------------------------------
@@ -472,25 +454,25 @@ struct GatherArgs {
 //   keys are distinct (ids differ) except for 0 = "not a candidate".
 // ------------------------------------------------------------------------------------------
 struct SelectArgs {
-  const uint64_t* keys;   // [B, ld]
-  size_t ld;
-  const int32_t* counts;  // per-query list length at counts[q * count_stride] (NULL: n_fixed); > cap => overflow
-  int count_stride;
-  int n_fixed;
-  int cap;
-  int k;
+  const uint64_t* keys = nullptr;   // [B, ld]
+  size_t ld = 0;
+  const int32_t* counts = nullptr;  // per-query list length at counts[q * count_stride] (NULL: n_fixed); > cap => overflow
+  int count_stride = 1;
+  int n_fixed = 0;
+  int cap = 0;
+  int k = 0;
   // mode A outputs (sample stage): top keys into out_keys[q, 0..kk), out_cnt[q] = kk, thr[q]
-  uint64_t* out_keys;
-  size_t out_ld;
-  int32_t* out_cnt;
-  uint64_t* out_thr;
-  float* out_tau;  // score of out_thr (-inf when fewer than k keys were found): the filter pass's float pre-test
+  uint64_t* out_keys = nullptr;
+  size_t out_ld = 0;
+  int32_t* out_cnt = nullptr;
+  uint64_t* out_thr = nullptr;
+  float* out_tau = nullptr;  // score of out_thr (-inf when fewer than k keys were found): the filter pass's float pre-test
   // mode B outputs (final)
-  float* out_scores;   // [B, k]
-  int32_t* out_ids;    // [B, k]
-  int32_t* out_count;  // [B]
-  int debug;           // timing only (scan_no_epilogue): 256 = return once the list is loaded, 512 = after the first barrier,
-                       // 1024 = after the radix passes, 2048 = after the sort
+  float* out_scores = nullptr;   // [B, k]
+  int32_t* out_ids = nullptr;    // [B, k]
+  int32_t* out_count = nullptr;  // [B]
+  int debug = 0;                 // timing only (scan_no_epilogue): 256 = return once the list is loaded, 512 = after the first
+                                 // barrier, 1024 = after the radix passes, 2048 = after the sort
 };
 
 // Per-query stages: what bounds them is LATENCY (a chain of ~10 dependent global / LDS round trips per query), so what they
@@ -1042,13 +1024,148 @@ static bool select_small(int B, int64_t list_bound) {
   return B >= 512 && list_bound <= SELECT_KPT_SMALL * SELECT_THREADS_SMALL;
 }
 
-static void launch_select(const SelectArgs& a, int B, hipStream_t stream) {
+static void launch_select(const SelectArgs& a, int B, bool small, hipStream_t stream) {
   ProfScope ps(stream, RP_K_SELECT);
-  if (select_small(B, a.counts ? (int64_t)a.cap : (int64_t)a.n_fixed))
+  if (small)
     hipLaunchKernelGGL((select_kernel<SELECT_THREADS_SMALL, SELECT_KPT_SMALL>), dim3(B), dim3(SELECT_THREADS_SMALL), 0,
                        stream, a);
   else
     hipLaunchKernelGGL((select_kernel<SELECT_THREADS, SELECT_KPT>), dim3(B), dim3(SELECT_THREADS), 0, stream, a);
+}
+
+// The k best keys of every query's n sampled keys into the candidate list, with the bound they give (thr, tau).
+static SelectArgs select_into_cand(const uint64_t* keys, size_t n, int k, uint64_t* cand, size_t cap, int32_t* count,
+                                   uint64_t* thr, float* tau) {
+  SelectArgs a;
+  a.keys = keys;
+  a.ld = n;
+  a.n_fixed = a.cap = (int)n;
+  a.k = k;
+  a.out_keys = cand;
+  a.out_ld = cap;
+  a.out_cnt = count;
+  a.out_thr = thr;
+  a.out_tau = tau;
+  return a;
+}
+
+// The k best keys of every query's list, sorted, into the caller's outputs.  counts == NULL: every list holds ld keys;
+// else list q holds counts[q * SIM_COUNT_STRIDE] of at most ld (more: the query reports the overflow).
+static SelectArgs select_into_outputs(const uint64_t* keys, size_t ld, const int32_t* counts, int k, float* out_scores,
+                                      int32_t* out_ids, int32_t* out_count) {
+  SelectArgs a;
+  a.keys = keys;
+  a.ld = ld;
+  a.counts = counts;
+  a.count_stride = counts ? SIM_COUNT_STRIDE : 1;
+  a.n_fixed = counts ? 0 : (int)ld;
+  a.cap = (int)ld;
+  a.k = k;
+  a.out_scores = out_scores;
+  a.out_ids = out_ids;
+  a.out_count = out_count;
+  return a;
+}
+
+// ------------------------------------------------------------------------------------------
+// The plan: everything a call launches follows from (B, N, row shape, k, flags) and the options - a pure function, so it
+// runs on a machine without a GPU (rp_dbg_sim_plan).
+// ------------------------------------------------------------------------------------------
+// What the k loop needs of a row of D2 2-byte units.  bf16: 64-wide k-tiles or 32-wide ones.  e4m3: whole 128-byte k-tiles,
+// rows that end half a k-tile early (1472 bytes = 11.5 x 128), or a single 64-byte row (D = 64).
+enum SimRows { ROWS_K64, ROWS_K32, ROWS_8WHOLE, ROWS_8TAIL, ROWS_8SHORT };
+static SimRows sim_rows(bool fp8, int D2) {
+  if (!fp8) return D2 % 64 == 0 ? ROWS_K64 : ROWS_K32;
+  return D2 % 64 == 0 ? ROWS_8WHOLE : (D2 % 64 == 32 && D2 > 64) ? ROWS_8TAIL : ROWS_8SHORT;
+}
+
+constexpr int SIM_CHIP_CUS = 256;  // the MI355X's CU count: the big sample tile pays once its workgroups fill the chip
+
+// One row per scan tile: f(C()) for the tile's configuration C; false when id names none.
+template <class F>
+static bool with_scan_tile(int id, F&& f) {
+  switch (id) {
+#define RP_TILE(ID, C)   \
+  case RP_SIM_TILE_##ID: \
+    f(C());              \
+    return true;
+    RP_TILE(Q256, SimCfgQ256)
+    RP_TILE(Q128W8, SimCfgQ128W8)
+    RP_TILE(Q128K32W8, SimCfgQ128K32W8)
+    RP_TILE(Q64, SimCfgQ64)
+    RP_TILE(Q32, SimCfgQ32)
+    RP_TILE(SAMPLE, SimCfgSample)
+    RP_TILE(SAMPLE_K64W8, SimCfgSampleK64W8)
+    RP_TILE(SAMPLE_Q32, SimCfgSampleQ32)
+    RP_TILE(SAMPLE_BIG, SimCfgSampleBig)
+    RP_TILE(8Q256, SimCfg8Q256)
+    RP_TILE(8Q128W8, SimCfg8Q128W8)
+    RP_TILE(8Q64, SimCfg8Q64)
+    RP_TILE(8Q64_TAIL, SimCfg8Q64Tail)
+    RP_TILE(8Q32, SimCfg8Q32)
+    RP_TILE(8Q32_TAIL, SimCfg8Q32Tail)
+    RP_TILE(8SAMPLE, SimCfg8Sample)
+    RP_TILE(8SAMPLE_K64W8, SimCfg8SampleK64W8)
+    RP_TILE(8SAMPLE_K64_TAILW8, SimCfg8SampleK64TailW8)
+    RP_TILE(8SAMPLE_Q32, SimCfg8SampleQ32)
+    RP_TILE(8SAMPLE_Q32_TAIL, SimCfg8SampleQ32Tail)
+#undef RP_TILE
+    default:
+      return false;
+  }
+}
+
+// workgroups of a first-generation pass over `blocks` 256-row premise blocks (dense plans: `blocks` 128-row tiles, per_block 0)
+static int scan_tile_wgs(int id, int B, int blocks, bool per_block) {
+  int wgs = 0;
+  with_scan_tile(id, [&](auto c) {
+    using C = decltype(c);
+    wgs = ((B + C::BM - 1) / C::BM) * blocks * (per_block ? SIM_PB / C::BN : 1);
+  });
+  return wgs;
+}
+
+// dense pass, and the first-generation filter pass of more than 64 queries
+static int dense_tile(SimRows rows, int bm) {
+  switch (rows) {
+    case ROWS_K64: return bm == 256 ? RP_SIM_TILE_Q256 : RP_SIM_TILE_Q128W8;
+    case ROWS_K32: return bm == 256 ? RP_SIM_TILE_Q256 : RP_SIM_TILE_Q128K32W8;
+    default: return bm == 256 ? RP_SIM_TILE_8Q256 : RP_SIM_TILE_8Q128W8;
+  }
+}
+
+// Sample pass: 4 sub-tiles of 64 rows per sampled block.  big: many queries - a shard under the queries of an 8-GPU step: the
+// sample is a quarter of the rows there, MFMA-bound, and the dense pass's 256-query x 128-row tile runs it faster than the
+// 128 x 64 one - 45 vs 52 us, e4m3 34 vs 44 - once its tiles fill the chip; with fewer it is slower: 41 vs 29 us at 1024
+// queries x 32.5 k rows.  q32: at most 32 queries, on the 32-query tiles.
+static int sample_tile(SimRows rows, bool big, bool q32) {
+  switch (rows) {
+    case ROWS_K64: return big ? RP_SIM_TILE_SAMPLE_BIG : q32 ? RP_SIM_TILE_SAMPLE_Q32 : RP_SIM_TILE_SAMPLE_K64W8;
+    case ROWS_K32: return big ? RP_SIM_TILE_Q256 : RP_SIM_TILE_SAMPLE;
+    case ROWS_8WHOLE: return big ? RP_SIM_TILE_8Q256 : q32 ? RP_SIM_TILE_8SAMPLE_Q32 : RP_SIM_TILE_8SAMPLE_K64W8;
+    case ROWS_8TAIL: return big ? RP_SIM_TILE_8Q256 : q32 ? RP_SIM_TILE_8SAMPLE_Q32_TAIL : RP_SIM_TILE_8SAMPLE_K64_TAILW8;
+    default: return big ? RP_SIM_TILE_8Q256 : RP_SIM_TILE_8SAMPLE;
+  }
+}
+
+// first-generation filter pass: the 32- and 64-query tiles where the rows allow them, else the dense pass's tile
+static int filter_tile_gen1(SimRows rows, int bm, bool q32, bool q64) {
+  switch (rows) {
+    case ROWS_K64: return q32 ? RP_SIM_TILE_Q32 : q64 ? RP_SIM_TILE_Q64 : dense_tile(rows, bm);
+    case ROWS_8WHOLE: return q32 ? RP_SIM_TILE_8Q32 : q64 ? RP_SIM_TILE_8Q64 : dense_tile(rows, bm);
+    case ROWS_8TAIL: return q32 ? RP_SIM_TILE_8Q32_TAIL : q64 ? RP_SIM_TILE_8Q64_TAIL : dense_tile(rows, bm);
+    default: return dense_tile(rows, bm);
+  }
+}
+
+// second-generation filter pass (rows of whole 128-byte k-tiles, or e4m3 rows ending half a tile early); -1: none for these rows
+static int filter_tile_gen2(SimRows rows) {
+  switch (rows) {
+    case ROWS_K64: return RP_SIM_TILE_FILTER_NT8;
+    case ROWS_8WHOLE: return RP_SIM_TILE_8FILTER_W8;
+    case ROWS_8TAIL: return RP_SIM_TILE_8FILTER_TAILW8;
+    default: return -1;
+  }
 }
 
 struct SimPlan {
@@ -1056,18 +1173,22 @@ struct SimPlan {
   bool new_filter;  // two-pass: second-generation filter kernel (needs whole 128-B operand rows per K-tile)
   int stride;       // two-pass: every stride-th 256-row block is sampled
   int blocks, sample_blocks, filter_blocks;
-  int bm, tiles_q, tiles_p;  // dense-only: first-generation kernel, bm queries x 128 premises per tile
   size_t dense_ld;           // keys per query in the dense buffer
   size_t cap;                // candidate-list capacity per query: every row could pass, so it cannot overflow
+  // what is launched: pass 0 = the dense pass or the sample pass, pass 1 = the filter pass (tile -1: dense-only)
+  int tile0, wgs0, tile1, wgs1;  // RpSimTile and workgroups
+  bool paged_filter;             // pass 1 on the PAGED twin of its second-generation tile
+  int stage0, stage1;            // RpSimStage behind each pass (stage1 -1: dense-only)
   size_t off_dense, off_cand, off_count, off_thr, off_tau, off_slots, off_scnt, bytes;
 };
 
 // D2 = operand row length in 2-byte units
-static SimPlan plan_sim(int B, int N, int D2, int k, int flags, bool fp8 = false) {
+static SimPlan plan_sim(int B, int N, int D2, int k, int flags, bool fp8 = false, bool paged = false) {
   SimPlan p;
-  p.bm = (B > 128 && g_scan_cfg != 1) ? 256 : 128;
-  p.tiles_q = (B + p.bm - 1) / p.bm;
-  p.tiles_p = (N + 127) / 128;
+  const SimRows rows = sim_rows(fp8, D2);
+  const int bm = (B > 128 && g_scan_cfg != 1) ? 256 : 128;  // queries per tile of the dense pass
+  const bool q32 = B <= 32 && g_scan_small_tiles, q64 = B <= 64 && g_scan_small_tiles;
+  const int tiles_q256 = (B + 255) / 256;
   p.blocks = (N + SIM_PB - 1) / SIM_PB;
   // Sampling stride: the k-th best of a 1/stride sample leaves ~k*stride candidates above it in the
   // full set (spread ~stride*sqrt(k)), and the sample select reads N/stride keys per query.  The two
@@ -1081,15 +1202,15 @@ static SimPlan plan_sim(int B, int N, int D2, int k, int flags, bool fp8 = false
   // queries share it (the 8-GPU shape: 2048 queries x 16k rows would write and re-read 266 MB of keys)
   p.dense_only = (flags & RP_TOPK_DENSE) != 0 || p.blocks < 2 * stride ||
                  (N <= SIM_DENSE_MAX_N && (int64_t)B * N <= SIM_DENSE_MAX_KEYS);
-  // second-generation filter: needs whole 128-B operand rows per K-tile; its 256-query tile does the MFMA work of
-  // 256 queries whatever B is, so small batches (single-state queries) stay on the first-generation kernel, whose
-  // 128-query tiles are HBM-bound there (measured at B = 1: 142 vs 171 us per call)
-  // (e4m3 rows may end half a k-tile early - 1472 bytes = 11.5 x 128: SimCfg8FilterTail)
-  p.new_filter = !p.dense_only && g_scan_impl == 0 && (D2 % 64 == 0 || (fp8 && D2 % 64 == 32 && D2 > 64)) &&
-                 (B > 128 || g_scan_impl_force_new);
+  // second-generation filter: its 256-query tile does the MFMA work of 256 queries whatever B is, so small batches
+  // (single-state queries) stay on the first-generation kernel, whose 128-query tiles are HBM-bound there (measured at
+  // B = 1: 142 vs 171 us per call)
+  p.new_filter = !p.dense_only && g_scan_impl == 0 && filter_tile_gen2(rows) >= 0 && (B > 128 || g_scan_impl_force_new);
+  p.paged_filter = p.new_filter && paged;
   p.sample_blocks = p.dense_only ? 0 : (p.blocks + stride - 1) / stride;
   p.filter_blocks = p.dense_only ? 0 : p.blocks - p.sample_blocks;
-  p.dense_ld = p.dense_only ? (size_t)p.tiles_p * 128 : (size_t)p.sample_blocks * SIM_PB;
+  const int tiles_p = (N + 127) / 128;  // dense-only: 128 premises per tile
+  p.dense_ld = p.dense_only ? (size_t)tiles_p * 128 : (size_t)p.sample_blocks * SIM_PB;
   // Candidate-list capacity per query.  About k * stride keys lie above the sampled bound (spread ~ stride * sqrt(k)):
   // eight times that, never less than 8192 keys, never more than every row.  A query whose list would not fit (adversarial
   // scores, or a sample that gave no bound because fewer than k sampled rows were accessible) reports out_count = -1 and
@@ -1097,6 +1218,32 @@ static SimPlan plan_sim(int B, int N, int D2, int k, int flags, bool fp8 = false
   // B * N * 8 bytes: 2 GB at 256 x 1M, as large as the dense plan the two-pass one exists to avoid.)
   p.cap = std::min((size_t)N + k, std::max((size_t)8192, (size_t)8 * k * stride) + k);
   if (g_scan_cap > 0) p.cap = std::min((size_t)N + k, (size_t)g_scan_cap + k);  // tests: force the overflow path
+  p.stage0 = select_small(B, (int64_t)p.dense_ld) ? RP_SIM_STAGE_SELECT_SMALL : RP_SIM_STAGE_SELECT;
+  if (p.dense_only) {
+    p.tile0 = dense_tile(rows, bm);
+    p.wgs0 = scan_tile_wgs(p.tile0, B, tiles_p, false);
+    p.tile1 = p.stage1 = -1;
+    p.wgs1 = 0;
+  } else {
+    const bool big = tiles_q256 * p.sample_blocks * (SIM_PB / 128) >= SIM_CHIP_CUS;
+    p.tile0 = sample_tile(rows, big, q32);
+    p.wgs0 = scan_tile_wgs(p.tile0, B, p.sample_blocks, true);
+    if (p.new_filter) {
+      p.tile1 = filter_tile_gen2(rows);
+      p.wgs1 = tiles_q256 * p.filter_blocks;
+      // ~k * stride keys lie above the sampled bound, ~3 x that before the accessibility predicate: the smallest shape whose
+      // raw list holds that when many queries share the chip (longer lists stay correct - they spill to the slow path)
+      const int64_t raw_bound = (int64_t)k * p.stride * 4;
+      const bool many = B >= 512 && k <= SELECT_SMALL_MAX_K;
+      p.stage1 = many && raw_bound <= GATHER_ENTRIES_SMALL ? RP_SIM_STAGE_GATHER_SMALL
+                 : many && raw_bound <= GATHER_ENTRIES_MID ? RP_SIM_STAGE_GATHER_MID
+                                                           : RP_SIM_STAGE_GATHER;
+    } else {
+      p.tile1 = filter_tile_gen1(rows, bm, q32, q64);
+      p.wgs1 = scan_tile_wgs(p.tile1, B, p.filter_blocks, true);
+      p.stage1 = select_small(B, (int64_t)p.cap) ? RP_SIM_STAGE_SELECT_SMALL : RP_SIM_STAGE_SELECT;
+    }
+  }
   size_t off = 0;
   p.off_dense = off;
   off += align_up((size_t)B * p.dense_ld * 8, 256);
@@ -1111,7 +1258,7 @@ static SimPlan plan_sim(int B, int N, int D2, int k, int flags, bool fp8 = false
   p.off_slots = off;  // second-generation filter kernel: private runs + their counts
   p.off_scnt = off;
   if (p.new_filter) {
-    const size_t wg_tiles = (size_t)((B + 255) / 256) * p.filter_blocks;
+    const size_t wg_tiles = (size_t)tiles_q256 * p.filter_blocks;
     off += align_up(wg_tiles * SLOTS_PER_TILE * sizeof(uint2), 256);
     p.off_scnt = off;
     off += align_up(wg_tiles * 256 * 4 * sizeof(int32_t), 256);
@@ -1122,42 +1269,69 @@ static SimPlan plan_sim(int B, int N, int D2, int k, int flags, bool fp8 = false
 
 // first-generation kernel (queries = MFMA rows): dense pass, sample pass, fallback filter pass
 template <class C>
-static RpStatus launch_scan_cfg(GemmOperand q, GemmOperand e, int D2, int n_tiles, int stride, const EpiSim& epi,
+static RpStatus launch_scan_cfg(GemmOperand q, GemmOperand e, int D2, int wgs, int stride, const EpiSim& epi,
                                 hipStream_t stream) {
-  if (n_tiles <= 0) return RP_OK;
+  if (wgs <= 0) return RP_OK;
   static LdsAttrOnce attr;
   RP_HIP(attr.ensure((const void*)sim_scan_kernel<C>, C::LDS_BYTES));
   const int tiles_q = (epi.B + C::BM - 1) / C::BM;
   const int sub = (stride > 1 || epi.filter) ? SIM_PB / C::BN : 1;
   ProfScope ps(stream, (stride > 1 && !epi.filter) ? RP_K_SCAN_SAMPLE : RP_K_SCAN);
-  hipLaunchKernelGGL((sim_scan_kernel<C>), dim3(tiles_q * n_tiles), dim3(C::THREADS), C::LDS_BYTES, stream, q, e, D2,
-                     tiles_q, stride, sub, epi);
+  hipLaunchKernelGGL((sim_scan_kernel<C>), dim3(wgs), dim3(C::THREADS), C::LDS_BYTES, stream, q, e, D2, tiles_q, stride,
+                     sub, epi);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
 
-// the eight-wave form of a plain-loop tile (the four-wave one only in probe builds)
-template <class C4, class C8>
-static RpStatus launch_scan_w(GemmOperand q, GemmOperand e, int D2, int n_tiles, int stride, const EpiSim& epi, hipStream_t stream) {
-  static_assert(C4::BM == C8::BM && C4::BN == C8::BN && C4::FP8 == C8::FP8, "the same tile");
-#ifdef RP_EXPERIMENTS
-  if (g_scan_waves == 4) return launch_scan_cfg<C4>(q, e, D2, n_tiles, stride, epi, stream);
-#endif
-  return launch_scan_cfg<C8>(q, e, D2, n_tiles, stride, epi, stream);
+static RpStatus launch_scan_tile(int id, GemmOperand q, GemmOperand e, int D2, int wgs, int stride, const EpiSim& epi,
+                                 hipStream_t stream) {
+  RpStatus st = RP_OK;
+  if (!with_scan_tile(id, [&](auto c) { st = launch_scan_cfg<decltype(c)>(q, e, D2, wgs, stride, epi, stream); }))
+    return fail(RP_E_INVALID, "no scan tile %d", id);
+  return st;
 }
 
-template <class C, bool PAGED>
-static RpStatus launch_filter_cfg(GemmOperand e, GemmOperand q, int D2, int n_blocks, int stride,
-                                  const EpiSimFilter<C::FP8, PAGED>& epi, hipStream_t stream) {
-  if (n_blocks <= 0) return RP_OK;
+// second-generation filter kernel; fill(epi) sets the epilogue's arguments, whichever of its four types the tile takes
+template <class C, bool PAGED, class Fill>
+static RpStatus launch_filter_cfg(GemmOperand e, GemmOperand q, int D2, int wgs, int stride, Fill&& fill, hipStream_t stream) {
+  if (wgs <= 0) return RP_OK;
   constexpr int LDS = C::RING_BYTES + SIM_FILTER_META_BYTES;
   static LdsAttrOnce attr;
   RP_HIP(attr.ensure((const void*)sim_filter_kernel<C, PAGED>, LDS));
-  const int tiles_q = (epi.B + C::BN - 1) / C::BN;
+  EpiSimFilter<C::FP8, PAGED> epi;
+  fill(epi);
   ProfScope ps(stream, RP_K_SCAN);
-  hipLaunchKernelGGL((sim_filter_kernel<C, PAGED>), dim3(tiles_q * n_blocks), dim3(C::THREADS), LDS, stream, e, q, D2, tiles_q,
-                     stride, epi);
+  hipLaunchKernelGGL((sim_filter_kernel<C, PAGED>), dim3(wgs), dim3(C::THREADS), LDS, stream, e, q, D2, epi.tiles_q, stride,
+                     epi);
   RP_CHECK_LAUNCH();
+  return RP_OK;
+}
+
+// paged (rp_sim_topk_after): the bound joins the pre-test (EpiSimFilter<., PAGED>)
+template <class Fill>
+static RpStatus launch_filter_tile(int id, bool paged, GemmOperand e, GemmOperand q, int D2, int wgs, int stride, Fill&& fill,
+                                   hipStream_t stream) {
+  switch (id) {
+#define RP_TILE(ID, C)                                                                               \
+  case RP_SIM_TILE_##ID:                                                                             \
+    return paged ? launch_filter_cfg<C, true>(e, q, D2, wgs, stride, fill, stream)                   \
+                 : launch_filter_cfg<C, false>(e, q, D2, wgs, stride, fill, stream);
+    RP_TILE(FILTER_NT8, SimCfgFilterNt8)
+    RP_TILE(8FILTER_W8, SimCfg8FilterW8)
+    RP_TILE(8FILTER_TAILW8, SimCfg8FilterTailW8)
+#undef RP_TILE
+    default:
+      return fail(RP_E_INVALID, "no filter tile %d", id);
+  }
+}
+
+// the shape checks of the four rp_sim_topk* entry points and of rp_dbg_sim_plan
+static RpStatus check_sim_shape(bool fp8, int32_t B, int32_t N, int32_t D, int32_t k) {
+  if (fp8)
+    RP_REQUIRE(B > 0 && N > 0 && D > 0 && D % 64 == 0, "B=%d N=%d D=%d (D must be a multiple of 64 for e4m3)", B, N, D);
+  else
+    RP_REQUIRE(B > 0 && N > 0 && D > 0 && D % 32 == 0, "B=%d N=%d D=%d (D must be a multiple of 32)", B, N, D);
+  RP_REQUIRE(k > 0 && k <= SIM_MAX_K, "k=%d out of range (1..%d)", k, SIM_MAX_K);
   return RP_OK;
 }
 
@@ -1172,7 +1346,30 @@ extern "C" size_t rp_sim_topk_workspace_bytes(int32_t B, int32_t N, int32_t D, i
   return plan_sim(B, N, D, k, flags).bytes;
 }
 
-// shared by the bf16 and the e4m3 entry points (q_scale/e_scale NULL = bf16 operands)
+extern "C" RpStatus rp_dbg_sim_plan(int32_t B, int32_t N, int32_t D, int32_t k, int32_t flags, int32_t fp8, int32_t paged,
+                                    int64_t* out) {
+  RP_REQUIRE(out, "null argument");
+  if (RpStatus st = check_sim_shape(fp8 != 0, B, N, D, k)) return st;
+  const SimPlan p = plan_sim(B, N, fp8 ? D / 2 : D, k, flags, fp8 != 0, paged != 0);
+  out[RP_SIM_PLAN_DENSE_ONLY] = p.dense_only;
+  out[RP_SIM_PLAN_NEW_FILTER] = p.new_filter;
+  out[RP_SIM_PLAN_STRIDE] = p.stride;
+  out[RP_SIM_PLAN_SAMPLE_BLOCKS] = p.sample_blocks;
+  out[RP_SIM_PLAN_FILTER_BLOCKS] = p.filter_blocks;
+  out[RP_SIM_PLAN_CAP] = (int64_t)p.cap;
+  out[RP_SIM_PLAN_BYTES] = (int64_t)p.bytes;
+  out[RP_SIM_PLAN_TILE0] = p.tile0;
+  out[RP_SIM_PLAN_WGS0] = p.wgs0;
+  out[RP_SIM_PLAN_TILE1] = p.tile1;
+  out[RP_SIM_PLAN_WGS1] = p.wgs1;
+  out[RP_SIM_PLAN_PAGED_FILTER] = p.paged_filter;
+  out[RP_SIM_PLAN_STAGE0] = p.stage0;
+  out[RP_SIM_PLAN_STAGE1] = p.stage1;
+  return RP_OK;
+}
+
+// shared by the bf16 and the e4m3 entry points (q_scale/e_scale NULL = bf16 operands):
+// check the arguments, plan, pass 0, select, pass 1, gather / select
 static RpStatus sim_topk_impl(const void* Q, const void* E, const float* q_scale, const float* e_scale,
                               const float* after_score, const int32_t* after_id, int32_t B,
                               int32_t N, int32_t D, const int32_t* file_of, const int64_t* end_key,
@@ -1181,20 +1378,17 @@ static RpStatus sim_topk_impl(const void* Q, const void* E, const float* q_scale
                               int32_t* out_count, void* workspace, size_t workspace_bytes, void* stream_) {
   RP_REQUIRE(Q && E && out_scores && out_ids && out_count, "null argument");
   const bool fp8 = q_scale != nullptr;
-  if (fp8)
-    RP_REQUIRE(B > 0 && N > 0 && D > 0 && D % 64 == 0, "B=%d N=%d D=%d (D must be a multiple of 64 for e4m3)", B, N, D);
-  else
-    RP_REQUIRE(B > 0 && N > 0 && D > 0 && D % 32 == 0, "B=%d N=%d D=%d (D must be a multiple of 32)", B, N, D);
-  RP_REQUIRE(k > 0 && k <= SIM_MAX_K, "k=%d out of range (1..%d)", k, SIM_MAX_K);
+  if (RpStatus st = check_sim_shape(fp8, B, N, D, k)) return st;
   if (file_of) RP_REQUIRE(end_key && file_bits_t && own_file && q_key && F > 0, "mask arrays incomplete");
   hipStream_t stream = (hipStream_t)stream_;
   const int D2 = fp8 ? D / 2 : D;  // row length in 2-byte units
-  const SimPlan p = plan_sim(B, N, D2, k, flags, fp8);
+  const SimPlan p = plan_sim(B, N, D2, k, flags, fp8, after_id != nullptr);
   // one size for both operand types, the documented one: the e4m3 plan may need less (the first-generation filter has no
   // private runs), and a workspace between the two sizes used to be accepted by the e4m3 entry points alone
   const size_t need = fp8 ? std::max(p.bytes, plan_sim(B, N, D, k, flags).bytes) : p.bytes;
   if (!workspace || workspace_bytes < need)
     return fail(RP_E_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, need);
+  RP_REQUIRE((after_score == nullptr) == (after_id == nullptr), "after_score and after_id go together");
   char* ws = (char*)workspace;
   uint64_t* dense = (uint64_t*)(ws + p.off_dense);
   uint64_t* cand = (uint64_t*)(ws + p.off_cand);
@@ -1204,7 +1398,6 @@ static RpStatus sim_topk_impl(const void* Q, const void* E, const float* q_scale
 
   GemmOperand qop{(const bf16_t*)Q, D2, B}, eop{(const bf16_t*)E, D2, N};
   EpiSim epi;
-  RP_REQUIRE((after_score == nullptr) == (after_id == nullptr), "after_score and after_id go together");
   epi.q_scale = q_scale;
   epi.e_scale = e_scale;
   epi.after_score = after_score;
@@ -1218,231 +1411,90 @@ static RpStatus sim_topk_impl(const void* Q, const void* E, const float* q_scale
   epi.q_key = q_key;
   epi.B = B;
   epi.id_offset = id_offset;
-  epi.filter = 0;
   epi.dense = dense;
   epi.dense_ld = p.dense_ld;
-  epi.slot_shift = 0;
   epi.thr = thr;
   epi.cand = cand;
   epi.cap = (int)p.cap;
   epi.count = count;
-  epi.smem = nullptr;
-  epi.tile_q0 = 0;
-  epi.bm = p.bm;
   epi.debug_skip = g_scan_no_epilogue;
 
-  RpStatus st;
-  SelectArgs sa;
-  sa.debug = 0;
-  sa.keys = dense;
-  sa.ld = p.dense_ld;
-  sa.counts = nullptr;
-  sa.count_stride = 1;
-  sa.n_fixed = (int)p.dense_ld;
-  sa.cap = (int)p.dense_ld;
-  sa.k = k;
-  sa.out_tau = nullptr;
-  if (p.dense_only) {
-    // single pass: dense keys of every premise tile, then one select
-    if (fp8)
-      st = (p.bm == 256) ? launch_scan_cfg<SimCfg8Q256>(qop, eop, D2, p.tiles_p, 1, epi, stream)
-                         : launch_scan_w<SimCfg8Q128, SimCfg8Q128W8>(qop, eop, D2, p.tiles_p, 1, epi, stream);
-    else if (p.bm == 256)
-      st = launch_scan_cfg<SimCfgQ256>(qop, eop, D2, p.tiles_p, 1, epi, stream);
-    else
-      st = (D2 % 64 == 0) ? launch_scan_w<SimCfgQ128, SimCfgQ128W8>(qop, eop, D2, p.tiles_p, 1, epi, stream)
-                          : launch_scan_w<SimCfgQ128K32, SimCfgQ128K32W8>(qop, eop, D2, p.tiles_p, 1, epi, stream);
-    if (st) return st;
-    sa.out_keys = nullptr;
-    sa.out_ld = 0;
-    sa.out_cnt = nullptr;
-    sa.out_thr = nullptr;
-    sa.out_scores = out_scores;
-    sa.out_ids = out_ids;
-    sa.out_count = out_count;
-    launch_select(sa, B, stream);
+  // pass 0: dense keys of every premise tile (dense-only) or of the sampled blocks
+  if (RpStatus st = launch_scan_tile(p.tile0, qop, eop, D2, p.wgs0, p.dense_only ? 1 : p.stride, epi, stream)) return st;
+  if (p.dense_only) {  // single pass: one select
+    launch_select(select_into_outputs(dense, p.dense_ld, nullptr, k, out_scores, out_ids, out_count), B,
+                  p.stage0 == RP_SIM_STAGE_SELECT_SMALL, stream);
     RP_CHECK_LAUNCH();
     return RP_OK;
   }
-  // pass 0: dense keys of the sampled blocks (4 sub-tiles of 64 rows each), k best of the sample -> bound
-  // (many queries - a shard under the queries of an 8-GPU step: the sample is a quarter of the rows there, MFMA-bound, and
-  // the dense pass's 256-query x 128-row tile runs it faster than the 128 x 64 one - 45 vs 52 us, e4m3 34 vs 44 - once its
-  // tiles fill the chip; with fewer it is slower: 41 vs 29 us at 1024 queries x 32.5 k rows)
-  const int n_sub = p.sample_blocks * (SIM_PB / SimCfgSample::BN);
-  const bool big_sample_tile = ((B + 255) / 256) * p.sample_blocks * (SIM_PB / SimCfgQ256::BN) >= 256;  // fills the chip
-  st = big_sample_tile ? (fp8 ? launch_scan_cfg<SimCfg8Q256>(qop, eop, D2, p.sample_blocks * (SIM_PB / SimCfg8Q256::BN), p.stride, epi, stream)
-                         : (D2 % 64 == 0)
-                             ? launch_scan_cfg<SimCfgSampleBig>(qop, eop, D2, p.sample_blocks * (SIM_PB / SimCfgSampleBig::BN), p.stride, epi, stream)
-                             : launch_scan_cfg<SimCfgQ256>(qop, eop, D2, p.sample_blocks * (SIM_PB / SimCfgQ256::BN), p.stride, epi, stream))
-       : (fp8 && B <= 32 && D2 % 64 == 0 && g_scan_small_tiles) ? launch_scan_cfg<SimCfg8SampleQ32>(qop, eop, D2, n_sub, p.stride, epi, stream)
-       : (fp8 && B <= 32 && D2 % 64 == 32 && D2 > 64 && g_scan_small_tiles)
-           ? launch_scan_cfg<SimCfg8SampleQ32Tail>(qop, eop, D2, n_sub, p.stride, epi, stream)
-       : (fp8 && D2 % 64 == 0) ? launch_scan_w<SimCfg8Sample, SimCfg8SampleK64W8>(qop, eop, D2, n_sub, p.stride, epi, stream)
-       : (fp8 && D2 % 64 == 32 && D2 > 64) ? launch_scan_w<SimCfg8Sample, SimCfg8SampleK64TailW8>(qop, eop, D2, n_sub, p.stride, epi, stream)
-       : fp8 ? launch_scan_cfg<SimCfg8Sample>(qop, eop, D2, n_sub, p.stride, epi, stream)
-       : (g_scan_sample_cfg == 0 && g_scan_small_tiles && B <= 32 && D2 % 64 == 0) ? launch_scan_cfg<SimCfgSampleQ32>(qop, eop, D2, n_sub, p.stride, epi, stream)
-       : (g_scan_sample_cfg == 0 && D2 % 64 == 0)
-           ? launch_scan_w<SimCfgSampleK64, SimCfgSampleK64W8>(qop, eop, D2, n_sub, p.stride, epi, stream)
-           : launch_scan_cfg<SimCfgSample>(qop, eop, D2, n_sub, p.stride, epi, stream);  // (D % 64 != 0: 32-wide K slices)
-  if (st) return st;
-  sa.out_keys = cand;
-  sa.out_ld = p.cap;
-  sa.out_cnt = count;
-  sa.out_thr = thr;
-  sa.out_tau = tau;
-  sa.out_scores = nullptr;
-  sa.out_ids = nullptr;
-  sa.out_count = nullptr;
+  // k best of the sample -> bound
+  SelectArgs sa = select_into_cand(dense, p.dense_ld, k, cand, p.cap, count, thr, tau);
   sa.debug = g_scan_no_epilogue;
-  launch_select(sa, B, stream);
+  launch_select(sa, B, p.stage0 == RP_SIM_STAGE_SELECT_SMALL, stream);
   RP_CHECK_LAUNCH();
   // pass 1: remaining blocks, keep only keys above each query's bound
-  if (p.new_filter) {
-    auto fill = [&](auto& ef) {
-      ef.N = N;
-      ef.B = B;
-      ef.q_scale = q_scale;
-      ef.e_scale = e_scale;
-      ef.tau = tau;
-      ef.slots = (uint2*)(ws + p.off_slots);
-      ef.scnt = (int32_t*)(ws + p.off_scnt);
-      ef.filter_blocks = p.filter_blocks;
-      ef.stride = p.stride;
-      ef.tiles_q = (B + 255) / 256;
-      ef.smem = nullptr;
-      ef.meta_off = 0;
-      ef.p0 = 0;
-      ef.debug_drop_all = g_scan_no_epilogue;
-    };
-    // (bf16 index: the 8-wave tile; the 4-wave forms it replaced stay selectable in probe builds, scan_filter_cfg)
-    if (fp8 && after_id) {  // a later page: the bound joins the pre-test (EpiSimFilter<., PAGED>)
-      EpiSimFilter<1, true> ef;
-      fill(ef);
-      ef.after_score = after_score;
-      ef.after_id = after_id;
-      st = (D2 % 64 == 0) ? launch_filter_cfg<SimCfg8FilterW8, true>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream)
-                          : launch_filter_cfg<SimCfg8FilterTailW8, true>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-    } else if (fp8) {
-      EpiSimFilter<1> ef;
-      fill(ef);
-#ifdef RP_EXPERIMENTS
-      if (g_scan_filter_cfg == 4 && D2 % 64 == 0)
-        st = launch_filter_cfg<SimCfg8Filter, false>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-      else if (g_scan_filter_cfg == 4 && D2 % 64 != 0)
-        st = launch_filter_cfg<SimCfg8FilterTail, false>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-      else
-#endif
-      st = (D2 % 64 == 0) ? launch_filter_cfg<SimCfg8FilterW8, false>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream)
-                          : launch_filter_cfg<SimCfg8FilterTailW8, false>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-    } else if (after_id) {
-      EpiSimFilter<0, true> ef;
-      fill(ef);
-      ef.after_score = after_score;
-      ef.after_id = after_id;
-      st = launch_filter_cfg<SimCfgFilterNt8, true>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-    } else {
-      EpiSimFilter<0> ef;
-      fill(ef);
-#ifdef RP_EXPERIMENTS  // alternatives measured and rejected: only a probe build (RP_EXPERIMENTS=1) carries them
-      if (g_scan_filter_cfg == 1)
-        st = launch_filter_cfg<SimCfgFilterK32, false>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-      else if (g_scan_filter_cfg == 2)
-        st = launch_filter_cfg<SimCfgFilter, false>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-      else if (g_scan_filter_cfg == 4)
-        st = launch_filter_cfg<SimCfgFilterNt, false>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-      else
-#endif
-        st = launch_filter_cfg<SimCfgFilterNt8, false>(eop, qop, D2, p.filter_blocks, p.stride, ef, stream);
-    }
-  } else {
-    epi.filter = 1;
-    const int n_t = p.filter_blocks * (SIM_PB / 128);
-    if (fp8 && B <= 32 && D2 % 64 == 0 && g_scan_small_tiles)
-      st = launch_scan_cfg<SimCfg8Q32>(qop, eop, D2, n_t, p.stride, epi, stream);
-    else if (fp8 && B <= 32 && D2 % 64 == 32 && D2 > 64 && g_scan_small_tiles)
-      st = launch_scan_cfg<SimCfg8Q32Tail>(qop, eop, D2, n_t, p.stride, epi, stream);
-    else if (fp8 && B <= 64 && D2 % 64 == 0 && g_scan_small_tiles)
-      st = launch_scan_cfg<SimCfg8Q64>(qop, eop, D2, n_t, p.stride, epi, stream);
-    else if (fp8 && B <= 64 && D2 % 64 == 32 && D2 > 64 && g_scan_small_tiles)
-      st = launch_scan_cfg<SimCfg8Q64Tail>(qop, eop, D2, n_t, p.stride, epi, stream);
-    else if (fp8)
-      st = (p.bm == 256) ? launch_scan_cfg<SimCfg8Q256>(qop, eop, D2, n_t, p.stride, epi, stream)
-                         : launch_scan_w<SimCfg8Q128, SimCfg8Q128W8>(qop, eop, D2, n_t, p.stride, epi, stream);
-    else if (p.bm == 256)
-      st = launch_scan_cfg<SimCfgQ256>(qop, eop, D2, n_t, p.stride, epi, stream);
-#ifdef RP_EXPERIMENTS
-    else if (B <= 32 && D2 % 64 == 0 && g_scan_filter_cfg == 9)
-      st = launch_scan_cfg<SimCfgQ32S3>(qop, eop, D2, n_t, p.stride, epi, stream);
-    else if (B <= 32 && D2 % 64 == 0 && g_scan_filter_cfg == 10)
-      st = launch_scan_cfg<SimCfgQ32P256>(qop, eop, D2, p.filter_blocks, p.stride, epi, stream);
-#endif
-    else if (B <= 32 && D2 % 64 == 0 && g_scan_small_tiles)
-      st = launch_scan_cfg<SimCfgQ32>(qop, eop, D2, n_t, p.stride, epi, stream);
-    else if (B <= 64 && D2 % 64 == 0 && g_scan_small_tiles)
-      st = launch_scan_cfg<SimCfgQ64>(qop, eop, D2, n_t, p.stride, epi, stream);
-    else
-      st = (D2 % 64 == 0) ? launch_scan_w<SimCfgQ128, SimCfgQ128W8>(qop, eop, D2, n_t, p.stride, epi, stream)
-                          : launch_scan_w<SimCfgQ128K32, SimCfgQ128K32W8>(qop, eop, D2, n_t, p.stride, epi, stream);
-  }
-  if (st) return st;
-  GatherArgs ga;
-  if (p.new_filter) {
-    ga.slots = (const uint2*)(ws + p.off_slots);
-    ga.scnt = (const int32_t*)(ws + p.off_scnt);
-    ga.filter_blocks = p.filter_blocks;
-    ga.tiles_q = (B + 255) / 256;
-    ga.stride = p.stride;
-    ga.N = N;
-    ga.B = B;
-    ga.id_offset = id_offset;
-    ga.file_of = file_of;
-    ga.end_key = end_key;
-    ga.bits_t = file_bits_t;
-    ga.bits_words = (B + 31) / 32;
-    ga.own_file = own_file;
-    ga.q_key = q_key;
-    ga.thr = thr;
-    ga.after_score = after_score;
-    ga.after_id = after_id;
-    ga.cand = cand;
-    ga.cap = p.cap;
-    ga.count = count;
-    ga.debug = g_scan_no_epilogue;
-  }
-  SelectArgs sb;
-  sb.keys = cand;
-  sb.ld = p.cap;
-  sb.counts = count;
-  sb.count_stride = SIM_COUNT_STRIDE;
-  sb.n_fixed = 0;
-  sb.cap = (int)p.cap;
-  sb.k = k;
-  sb.out_keys = nullptr;
-  sb.out_ld = 0;
-  sb.out_cnt = nullptr;
-  sb.out_thr = nullptr;
-  sb.out_tau = nullptr;
-  sb.out_scores = out_scores;
-  sb.out_ids = out_ids;
-  sb.out_count = out_count;
+  const int tiles_q256 = (B + 255) / 256;
+  SelectArgs sb = select_into_outputs(cand, p.cap, count, k, out_scores, out_ids, out_count);
   sb.debug = g_scan_no_epilogue;
-  if (p.new_filter) {  // runs -> predicate -> key list -> select, one kernel
-    ProfScope ps(stream, RP_K_SELECT);
-    // ~k * stride keys lie above the sampled bound, ~3 x that before the accessibility predicate: the smallest shape whose
-    // raw list holds that when many queries share the chip (longer lists stay correct - they spill to the slow path)
-    const int64_t raw_bound = (int64_t)k * p.stride * 4;
-    if (B >= 512 && k <= SELECT_SMALL_MAX_K && raw_bound <= GATHER_ENTRIES_SMALL)
-      hipLaunchKernelGGL((gather_select_kernel<SELECT_THREADS_SMALL, GATHER_ENTRIES_SMALL, SELECT_SMALL_MAX_K>), dim3(B),
-                         dim3(SELECT_THREADS_SMALL), 0, stream, ga, sb);
-    else if (B >= 512 && k <= SELECT_SMALL_MAX_K && raw_bound <= GATHER_ENTRIES_MID)
-      hipLaunchKernelGGL((gather_select_kernel<GATHER_THREADS_MID, GATHER_ENTRIES_MID, SELECT_SMALL_MAX_K>), dim3(B),
-                         dim3(GATHER_THREADS_MID), 0, stream, ga, sb);
-    else
-      hipLaunchKernelGGL((gather_select_kernel<SELECT_THREADS, GATHER_ENTRIES, SIM_MAX_K>), dim3(B), dim3(SELECT_THREADS), 0,
-                         stream, ga, sb);
-  } else {
-    launch_select(sb, B, stream);
+  if (!p.new_filter) {
+    epi.filter = 1;
+    if (RpStatus st = launch_scan_tile(p.tile1, qop, eop, D2, p.wgs1, p.stride, epi, stream)) return st;
+    launch_select(sb, B, p.stage1 == RP_SIM_STAGE_SELECT_SMALL, stream);
+    RP_CHECK_LAUNCH();
+    return RP_OK;
   }
+  auto fill = [&](auto& ef) {
+    ef.N = N;
+    ef.B = B;
+    ef.q_scale = q_scale;
+    ef.e_scale = e_scale;
+    ef.tau = tau;
+    ef.after_score = after_score;
+    ef.after_id = after_id;
+    ef.slots = (uint2*)(ws + p.off_slots);
+    ef.scnt = (int32_t*)(ws + p.off_scnt);
+    ef.filter_blocks = p.filter_blocks;
+    ef.stride = p.stride;
+    ef.tiles_q = tiles_q256;
+    ef.smem = nullptr;
+    ef.meta_off = 0;
+    ef.p0 = 0;
+    ef.debug_drop_all = g_scan_no_epilogue;
+  };
+  if (RpStatus st = launch_filter_tile(p.tile1, p.paged_filter, eop, qop, D2, p.wgs1, p.stride, fill, stream)) return st;
+  // runs -> predicate -> key list -> select, one kernel
+  GatherArgs ga;
+  ga.slots = (const uint2*)(ws + p.off_slots);
+  ga.scnt = (const int32_t*)(ws + p.off_scnt);
+  ga.filter_blocks = p.filter_blocks;
+  ga.tiles_q = tiles_q256;
+  ga.stride = p.stride;
+  ga.N = N;
+  ga.B = B;
+  ga.id_offset = id_offset;
+  ga.file_of = file_of;
+  ga.end_key = end_key;
+  ga.bits_t = file_bits_t;
+  ga.bits_words = (B + 31) / 32;
+  ga.own_file = own_file;
+  ga.q_key = q_key;
+  ga.thr = thr;
+  ga.after_score = after_score;
+  ga.after_id = after_id;
+  ga.cand = cand;
+  ga.cap = p.cap;
+  ga.count = count;
+  ga.debug = g_scan_no_epilogue;
+  ProfScope ps(stream, RP_K_SELECT);
+  if (p.stage1 == RP_SIM_STAGE_GATHER_SMALL)
+    hipLaunchKernelGGL((gather_select_kernel<SELECT_THREADS_SMALL, GATHER_ENTRIES_SMALL, SELECT_SMALL_MAX_K>), dim3(B),
+                       dim3(SELECT_THREADS_SMALL), 0, stream, ga, sb);
+  else if (p.stage1 == RP_SIM_STAGE_GATHER_MID)
+    hipLaunchKernelGGL((gather_select_kernel<GATHER_THREADS_MID, GATHER_ENTRIES_MID, SELECT_SMALL_MAX_K>), dim3(B),
+                       dim3(GATHER_THREADS_MID), 0, stream, ga, sb);
+  else
+    hipLaunchKernelGGL((gather_select_kernel<SELECT_THREADS, GATHER_ENTRIES, SIM_MAX_K>), dim3(B), dim3(SELECT_THREADS), 0,
+                       stream, ga, sb);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }
@@ -1796,23 +1848,8 @@ static RpStatus topk_merge_impl(const float* scores, const int32_t* ids, const i
     hipLaunchKernelGGL(merge_keys_strided_kernel, dim3(B), dim3(256), 0, stream, scores, ids, counts, (size_t)rank_stride, R,
                        k, keys);
   RP_CHECK_LAUNCH();
-  SelectArgs sa;
-  sa.debug = 0;
-  sa.keys = keys;
-  sa.ld = (size_t)R * k;
-  sa.counts = nullptr;
-  sa.count_stride = 1;
-  sa.n_fixed = R * k;
-  sa.cap = R * k;
-  sa.k = k;
-  sa.out_keys = nullptr;
-  sa.out_ld = 0;
-  sa.out_cnt = nullptr;
-  sa.out_thr = nullptr;
-  sa.out_scores = out_scores;
-  sa.out_ids = out_ids;
-  sa.out_count = out_count;
-  launch_select(sa, B, stream);
+  launch_select(select_into_outputs(keys, (size_t)R * k, nullptr, k, out_scores, out_ids, out_count), B,
+                select_small(B, (int64_t)R * k), stream);
   RP_CHECK_LAUNCH();
   return RP_OK;
 }

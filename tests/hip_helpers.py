@@ -1,5 +1,7 @@
 """Thin callers of the C ABI used by the GPU parity tests (raw pointers in, torch tensors as
 containers) + comparison helpers."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -106,6 +108,40 @@ def sim_topk(Q, E, k, masks=None, id_offset=0, flags=0, N=None, retry_dense=True
     torch.cuda.synchronize()
     if retry_dense and bool((out_c < 0).any()):  # the ABI's overflow contract, as every product caller honours it
         return sim_topk(Q, E, k, masks, id_offset, flags | _lib.RP_TOPK_DENSE, N, retry_dense=False)
+    return out_i, out_s, out_c
+
+
+def sim_plan(B, N, D, k, flags=0, fp8=False, paged=False):
+    """rp_dbg_sim_plan as a dict (no GPU call): the fields by name, tiles and stages by name (None: not launched)."""
+    out = (ctypes.c_int64 * len(_lib.SIM_PLAN_FIELDS))()
+    _lib.check(_lib.load().rp_dbg_sim_plan(B, N, D, k, flags, int(fp8), int(paged), out), "rp_dbg_sim_plan")
+    p = dict(zip(_lib.SIM_PLAN_FIELDS, out))
+    for f in ("tile0", "tile1"):
+        p[f] = _lib.SIM_TILES[p[f]] if p[f] >= 0 else None
+    for f in ("stage0", "stage1"):
+        p[f] = _lib.SIM_STAGES[p[f]] if p[f] >= 0 else None
+    return p
+
+
+def sim_topk_after(Q, E, k, after_score, after_id, masks=None, id_offset=0, flags=0, scales=None):
+    """rp_sim_topk_after, or rp_sim_topk_fp8_after with scales = (q_scale, e_scale): the page behind (after_score, after_id)."""
+    lib = _lib.load()
+    (B, D), N = Q.shape, E.shape[0]
+    out_s = torch.empty((B, k), dtype=torch.float32, device=Q.device)
+    out_i = torch.empty((B, k), dtype=torch.int32, device=Q.device)
+    out_c = torch.empty((B,), dtype=torch.int32, device=Q.device)
+    nbytes = lib.rp_sim_topk_workspace_bytes(B, N, D, k, flags)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=Q.device)
+    f, ek, bt, own, qk = masks if masks is not None else (None,) * 5
+    tail = [B, N, D, _lib.ptr(f), _lib.ptr(ek), _lib.ptr(bt), 0 if bt is None else bt.shape[0], _lib.ptr(own), _lib.ptr(qk),
+            id_offset, _lib.ptr(after_score), _lib.ptr(after_id), k, flags, _lib.ptr(out_s), _lib.ptr(out_i), _lib.ptr(out_c),
+            _lib.ptr(ws), nbytes, _lib.current_stream()]
+    if scales is None:
+        _lib.check(lib.rp_sim_topk_after(_lib.ptr(Q), _lib.ptr(E), *tail), "rp_sim_topk_after")
+    else:
+        _lib.check(lib.rp_sim_topk_fp8_after(_lib.ptr(Q), _lib.ptr(scales[0]), _lib.ptr(E), _lib.ptr(scales[1]), *tail),
+                   "rp_sim_topk_fp8_after")
+    torch.cuda.synchronize()
     return out_i, out_s, out_c
 
 

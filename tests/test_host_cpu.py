@@ -155,6 +155,13 @@ def test_retired_gemm_form_options_are_unknown(hip_lib):
         assert b"unknown option " + name in hip_lib.rp_last_error()
 
 
+def test_retired_scan_tile_options_are_unknown(hip_lib):
+    """The probe-only scan tiles left with their options, in product and probe builds alike (docs/HISTORY.md section 20)."""
+    for name in (b"scan_filter_cfg", b"scan_sample_cfg", b"scan_waves"):
+        assert hip_lib.rp_set_option(name, 0) != 0
+        assert b"unknown option " + name in hip_lib.rp_last_error()
+
+
 GEMM_VARIANT_OPTIONS = (b"gemm_variant", b"gemm_variant_all", b"gemm_variant_qkv", b"gemm_variant_wo", b"gemm_variant_o")
 EXPERIMENT_BUILD = os.environ.get("RP_EXPERIMENTS") == "1"  # (reprover_amd/build.py: such a build also carries tiles 27 - 29)
 

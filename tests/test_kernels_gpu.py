@@ -373,12 +373,14 @@ def test_sim_topk_small_query_tiles_are_the_same_bits(gen, fp8, B, N, D, k):
         run = lambda: hh.sim_topk_fp8(Q8, qs, E8, es, k, dm, id_offset=7)  # noqa: E731
     else:
         run = lambda: hh.sim_topk(Q, E, k, dm, id_offset=7)  # noqa: E731
-    a = run()
+    tiles = lambda: tuple(hh.sim_plan(B, N, D, k, 0, fp8)[f] for f in ("tile0", "tile1"))  # noqa: E731
+    a, tiles_a = run(), tiles()
     try:
         _lib.check(lib.rp_set_option(b"scan_small_tiles", 0), "opt")
-        b = run()
+        b, tiles_b = run(), tiles()
     finally:
         _lib.check(lib.rp_set_option(b"scan_small_tiles", 1), "opt")
+    assert (tiles_a != tiles_b) == (B <= 64), (tiles_a, tiles_b)  # the option moved the call onto other tiles - or, at 65, did not
     for x, y in zip(a, b):
         assert torch.equal(x, y)
     if not fp8:
@@ -398,12 +400,13 @@ def test_sim_topk_filter_generations_agree(gen, B, N, D, k):
     lib = _lib.load()
     _lib.check(lib.rp_set_option(b"scan_force_new", 1), "opt")  # batches <= 128 default to the first generation
     try:
-        a = hh.sim_topk(Q, E, k, dm, id_offset=1000)
+        a, new_a = hh.sim_topk(Q, E, k, dm, id_offset=1000), hh.sim_plan(B, N, D, k)["new_filter"]
         _lib.check(lib.rp_set_option(b"scan_impl", 1), "opt")
-        b = hh.sim_topk(Q, E, k, dm, id_offset=1000)
+        b, new_b = hh.sim_topk(Q, E, k, dm, id_offset=1000), hh.sim_plan(B, N, D, k)["new_filter"]
     finally:
         _lib.check(lib.rp_set_option(b"scan_impl", 0), "opt")
         _lib.check(lib.rp_set_option(b"scan_force_new", 0), "opt")
+    assert (new_a, new_b) == (1, 0)  # the two runs did take the two generations
     for x, y in zip(a, b):
         assert torch.equal(x, y)
     hh.check_topk_against_scores(a[0].cpu().numpy() - 1000, a[1].cpu().numpy(), a[2].cpu().numpy(), _scores(Q, E), acc, k,

@@ -72,4 +72,4 @@ for B in Bs:
                       f"E-stream {byts/scan_s/1e9:7.1f} GB/s  MFMA {2.0*B*N*D/scan_s/1e12:6.1f} TFLOP/s  QPS {B/(tot*1e-3):10.0f}  "
                       f"cnt_ok {bool((out_c == k).all())}  [{case}]{' BLOCKED' if bl else ''} chk {int(out_i.sum())}", flush=True)
                 for kv in filter(None, case.split(",")):
-                    _lib.check(lib.rp_set_option(kv.split("=")[0].encode(), {"scan_small_tiles": 1, "scan_waves": 8}.get(kv.split("=")[0], 0)), "opt")
+                    _lib.check(lib.rp_set_option(kv.split("=")[0].encode(), {"scan_small_tiles": 1}.get(kv.split("=")[0], 0)), "opt")
