@@ -535,6 +535,43 @@ RpStatus rp_dbg_wgrad(const void* Y, const void* X, float* out, int32_t T, int32
  * weight-gradient pairs): out0 f32 [splits, ny0, nx0], out1 f32 [splits, ny1, nx1] as rp_dbg_wgrad writes them. */
 RpStatus rp_dbg_wgrad_pair(const void* Y0, const void* X0, float* out0, int32_t ny0, int32_t nx0, const void* Y1,
                            const void* X1, float* out1, int32_t ny1, int32_t nx1, int32_t T, int32_t splits, void* stream);
+/* rp_dbg_wgrad with everything the launch functions take left free (tests/test_train_mfma_kernels_gpu.py): one product, or two
+ * (Y1 != NULL) over the same T token rows in one launch; Y bf16 [T, ldy] with ny live columns, X bf16 [T, ldx] with nx, both
+ * pitches multiples of 8 and the pointers 16-byte aligned; out f32 [splits, ny, nx] per product.  cfg: 0 = 256 x 256 tiles,
+ * 1 = 128 x 128 (one product only), -1 = plan_wgrad's choice; 1 <= splits <= T / 64.  g1 .. dln_part all non-NULL: the
+ * finishing epilogue on product 0 (rows of Y0 in the packed [32 gate | 32 up] order, ny0 % 64 == 0, splits == 1, else
+ * refused): out0 = d wi_0 [ny0 / 2, nx0], g1 = d wi_1, w0 / w1 the masters [ny0 / 2, nx0], ln [nx0], dln_part f32
+ * [ny0 / 32, nx0].  plan_out[2] = the tile configuration and split count that ran.  Everything is checked before the launch;
+ * no output is zeroed first.  Launch only.
+ * rp_dbg_wgrad_plan (no GPU call): out[4] = (cfg, splits) of plan_wgrad(rows0, cols0, nk), then of plan_wgrad_pair(rows0,
+ * cols0, rows1, cols1, nk) (splits 0: separate launches preferred; -1, -1 when rows1 == 0). */
+RpStatus rp_dbg_wgrad_ex(const void* Y0, int32_t ldy0, int32_t ny0, const void* X0, int32_t ldx0, int32_t nx0, float* out0,
+                         const void* Y1, int32_t ldy1, int32_t ny1, const void* X1, int32_t ldx1, int32_t nx1, float* out1,
+                         int32_t T, int32_t cfg, int32_t splits, float* g1, const float* w0, const float* w1, const float* ln,
+                         float* dln_part, int32_t* plan_out, void* stream);
+/* The training attention alone at any max_distance and under the trainer's dropout: forward (att_out bf16 [rows_total, H * 64],
+ * lse_out f32 [H, rows_total], log2 domain), both backward launches (delta_out f32 [H, rows_total], dqkv bf16 [rows_total, 3 * H *
+ * 64]: rows of real tokens written) and the table gradient dtab f32 [2 * maxd + 1, H].  qkv / datt bf16, cu_seqlens int32 [batch + 1]
+ * on the device (0 .. T <= rows_total, no empty sequence), bias_tab f32 [H, 2 * maxd + 1], rows_total % 256 == 0; att: the O the
+ * backward reads for delta (NULL: att_out).  Mask: rp_dbg_dropout_mask(p, seed, site, s0 + i, (h << 20) | j).  Synchronises. */
+RpStatus rp_dbg_attention_train(const void* qkv, const void* att, const void* datt, const int32_t* cu_seqlens, const float* bias_tab,
+                                int32_t batch, int32_t num_heads, int32_t rows_total, int32_t max_distance, float p, uint32_t seed,
+                                uint32_t site, float* lse_out, void* att_out, float* delta_out, void* dqkv, float* dtab, void* stream);
+RpStatus rp_dbg_wgrad_plan(int32_t rows0, int32_t cols0, int32_t rows1, int32_t cols1, int32_t nk, int32_t* out);
+/* One launch_gemm with a training epilogue and its dropout: A bf16 [M, K], W bf16 [N, K] (exactly N rows), M % 256 == 0; the
+ * mask is rp_dbg_dropout_mask(p, seed, site, ..)'s.  mode 0 = the gated-GELU backward over N = d_ff rows (aux0 = gu bf16 [M, ld]
+ * with 2 N packed columns, aux1 = rs [M]; out0 = dzs bf16 [M, ld], out1 = the row dot's slots f32 [ceil(N / 64), M], out2 =
+ * rcoef f32 [M] = rs^2 (sum of the slots) / K; p > 0: dff masked; variant 0 or 26).  mode 1 = the RMSNorm-backward residual (aux0 = x bf16 [M, ld], aux1 = rcoef
+ * [M]; out0 / out1 = the hi / lo planes [M, ld] updated in place; p > 0: also out2 = dxm bf16 [M, ld] = bf16(mask (hi + lo)) of
+ * the planes just stored; variant 0 or 26).  mode 2 = the training forward's FFN-in epilogue over N = 2 d_ff packed rows (aux1 =
+ * rs [M] or NULL; out0 = gu bf16 [M, N], out1 = ff bf16 [M, ld], masked when p > 0; variant -1 = the forward's choice).
+ * mode 3 = the training forward's residual projections (aux0 = the old hi plane bf16 [M, ld], read only; out0 = the new hi
+ * plane, out1 = the lo plane updated in place, out2 = ssp f32 [ceil(N / 64), M] or NULL; p > 0: the projection's output is
+ * masked before it is added; variant -1 = the forward's choice).
+ * plan[6] as rp_dbg_gemm_ex's.  Everything is checked before the launch; no output is zeroed first.  Launch only. */
+RpStatus rp_dbg_train_gemm(int32_t mode, const void* A, const void* W, int32_t M, int32_t N, int32_t K, const void* aux0,
+                           const float* aux1, void* out0, void* out1, void* out2, int32_t ld, float p, uint32_t seed, uint32_t site,
+                           int32_t variant, int32_t* plan, void* stream);
 RpStatus rp_dbg_attention_bwd(const void* qkv, const void* att, const void* datt, const int32_t* cu_seqlens,
                               const float* bias_tab, int32_t batch, int32_t num_heads, int32_t rows_total, void* lse_out,
                               void* att_out, void* dqkv, float* dtab, void* stream);

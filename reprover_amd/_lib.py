@@ -221,6 +221,24 @@ SIGNATURES = {
     "rp_dbg_wgrad": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rp_dbg_wgrad_pair": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    # (tests/test_train_mfma_kernels_gpu.py)
+    "rp_dbg_wgrad_ex": (
+        C.c_int32,
+        [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+         C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p],
+    ),
+    "rp_dbg_attention_train": (
+        C.c_int32,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32,
+         C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "rp_dbg_wgrad_plan": (C.c_int32, [C.c_int32] * 5 + [C.POINTER(C.c_int32)]),
+    "rp_dbg_train_gemm": (
+        C.c_int32,
+        [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_int32, C.c_float, C.c_uint32, C.c_uint32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p],
+    ),
     "rp_dbg_attention_bwd": (
         C.c_int32,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,

@@ -223,10 +223,11 @@ int bwd_variant(int n_rows_w, int K, int Tp) {
 }
 
 RpStatus launch_wgrad(const bf16_t* Y, int ldy, int ny, const bf16_t* X, int ldx, int nx, int Tp, int splits, float* out,
-                      hipStream_t stream, int force_cfg = -1) {
+                      hipStream_t stream, int force_cfg = -1, const WgradFinish* fin = nullptr) {
   RP_REQUIRE(Tp % 64 == 0 && ny % 8 == 0 && nx % 8 == 0 && ny >= 8 && nx >= 8, "wgrad: Tp=%d ny=%d nx=%d", Tp, ny, nx);
   const int cfg = force_cfg >= 0 ? force_cfg : plan_wgrad(ny, nx, Tp / 64).cfg;
-  const WgradOperands a{Y, ldy, ny, X, ldx, nx, out};
+  WgradOperands a{Y, ldy, ny, X, ldx, nx, out};
+  if (fin) a.fin = *fin;  // (rp_dbg_wgrad_ex: the product finishes dWi' on the pair's first product only)
   if (cfg == 1) return launch_wgrad_cfg<WgradCfg<128, 128, 2, 2, 2>>(a, nullptr, Tp / 64, splits, stream);
   return launch_wgrad_cfg<WgradCfg<256, 256, 4, 2, 2>>(a, nullptr, Tp / 64, splits, stream);
 }
@@ -277,6 +278,34 @@ void launch_colsum(const float* part, int rows, int C, float* out, hipStream_t s
 }
 void launch_bias_table(const float* rel_bias, const int32_t* bucket_of, int H, int ntab, float* tab, hipStream_t stream) {
   hipLaunchKernelGGL(bias_table_kernel, dim3((H * ntab + 255) / 256), dim3(256), 0, stream, rel_bias, bucket_of, H, ntab, tab);
+}
+// The training attention's three launches (the trainer and rp_dbg_attention_train): the forward with saved log-sum-exp, the two
+// backward launches of one template (<0>: dQ, delta, the table gradient's partial rows; <1>: dK, dV), and the table gradient.
+void launch_attention_train_fwd(dim3 grid, const bf16_t* qkv, const int4* work, const float* tab, bf16_t* att, int H, int maxd,
+                                float* lse, int ld_stat, const Drop& drop, uint32_t site, hipStream_t stream) {
+  if (drop.thresh)
+    hipLaunchKernelGGL((attention_kernel<true, true>), grid, dim3(256), 0, stream, qkv, work, tab, att, H, maxd, lse, ld_stat, drop, site);
+  else
+    hipLaunchKernelGGL((attention_kernel<true, false>), grid, dim3(256), 0, stream, qkv, work, tab, att, H, maxd, lse, ld_stat, drop, site);
+}
+void launch_attention_bwd(dim3 grid, const bf16_t* qkv, const bf16_t* att, const bf16_t* datt, const float* lse, float* delta,
+                          const int4* work, const float* tab, bf16_t* dqkv, float* dtab_part, int H, int maxd, int ld_stat,
+                          int dbg_flags, const Drop& drop, uint32_t site, hipStream_t stream) {
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, qkv, att, datt, lse, delta, work, tab, dqkv, dtab_part, H, maxd, ld_stat,
+                       dbg_flags, drop, site);
+  };
+  if (drop.thresh) {
+    launch(attn_bwd_kernel<0, true>);
+    launch(attn_bwd_kernel<1, true>);
+  } else {
+    launch(attn_bwd_kernel<0, false>);
+    launch(attn_bwd_kernel<1, false>);
+  }
+}
+void launch_bias_grad(const float* dtab_part, int nrows, int H, int ntab, const int32_t* bucket_of, int nbuckets, float* d_rel_bias,
+                      hipStream_t stream) {
+  hipLaunchKernelGGL(bias_grad_kernel, dim3(H), dim3(256), 0, stream, dtab_part, nrows, H, ntab, bucket_of, nbuckets, d_rel_bias);
 }
 // one repack_layer_kernel launch over up to four matrices: add() in order, then launch (an unused entry starts behind the
 // last tile, so no workgroup selects it)
@@ -357,12 +386,8 @@ RpStatus forward_layers(RpTrainer* tr, const int32_t* ids, const int32_t* cu, in
       return st;
     {
       ProfScope ps(stream, RP_K_ATTENTION);
-      if (drop.thresh)
-        hipLaunchKernelGGL((attention_kernel<true, true>), att_grid, dim3(256), 0, stream, (const bf16_t*)w.qkv[i],
-                           (const int4*)w.work, (const float*)e->bias_tab, w.att[i], H, e->maxd, w.lse[i], Tp, drop, site);
-      else
-        hipLaunchKernelGGL((attention_kernel<true, false>), att_grid, dim3(256), 0, stream, (const bf16_t*)w.qkv[i],
-                           (const int4*)w.work, (const float*)e->bias_tab, w.att[i], H, e->maxd, w.lse[i], Tp, drop, site);
+      launch_attention_train_fwd(att_grid, (const bf16_t*)w.qkv[i], (const int4*)w.work, (const float*)e->bias_tab, w.att[i], H,
+                                 e->maxd, w.lse[i], Tp, drop, site, stream);
     }
     // rows T .. Tp of every saved activation must stay finite: they are K rows of the wgrad GEMMs (against zero dY rows)
     if (Tp > T) RP_HIP(hipMemsetAsync(w.att[i] + (size_t)T * inner, 0, (size_t)(Tp - T) * inner * 2, stream));
@@ -596,18 +621,9 @@ RpStatus backward_layers(RpTrainer* tr, const float* params, const int32_t* ids,
       return st;
     {
       ProfScope ps(stream, RP_K_BWD_ATTENTION);
-      auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, att_grid, dim3(256), 0, stream, (const bf16_t*)w.qkv[i], (const bf16_t*)w.att[i],
-                           (const bf16_t*)w.datt, (const float*)w.lse[i], w.delta, (const int4*)w.work, (const float*)e->bias_tab,
-                           w.dqkv, w.dtab_part, H, e->maxd, Tp, g_train_dbg, drop, site);
-      };
-      if (drop.thresh) {
-        launch(attn_bwd_kernel<0, true>);
-        launch(attn_bwd_kernel<1, true>);
-      } else {
-        launch(attn_bwd_kernel<0, false>);
-        launch(attn_bwd_kernel<1, false>);
-      }
+      launch_attention_bwd(att_grid, (const bf16_t*)w.qkv[i], (const bf16_t*)w.att[i], (const bf16_t*)w.datt, (const float*)w.lse[i],
+                           w.delta, (const int4*)w.work, (const float*)e->bias_tab, w.dqkv, w.dtab_part, H, e->maxd, Tp, g_train_dbg,
+                           drop, site, stream);
       RP_CHECK_LAUNCH();
     }
     {
@@ -640,8 +656,8 @@ RpStatus backward_layers(RpTrainer* tr, const float* params, const int32_t* ids,
   {
     ProfScope ps(stream, RP_K_BWD_OTHER);
     launch_embed_bwd(ids, T, c.vocab_size, (const bf16_t*)w.dxhi, (const bf16_t*)w.dxlo, D, grads + lay.embed(), drop, stream);
-    hipLaunchKernelGGL(bias_grad_kernel, dim3(H), dim3(256), 0, stream, (const float*)w.dtab_part, (int)att_grid.y, H, ntab,
-                       (const int32_t*)tr->bucket_of, c.rel_num_buckets, grads + lay.rel_bias());
+    launch_bias_grad((const float*)w.dtab_part, (int)att_grid.y, H, ntab, (const int32_t*)tr->bucket_of, c.rel_num_buckets,
+                     grads + lay.rel_bias(), stream);
     RP_CHECK_LAUNCH();
   }
   return RP_OK;
@@ -913,6 +929,60 @@ extern "C" RpStatus rp_dbg_wgrad_pair(const void* Y0, const void* X0, float* out
   return launch_wgrad_pair(a, b, T, splits, (hipStream_t)stream_);
 }
 
+// One or two products over the same T token rows with everything launch_wgrad / launch_wgrad_pair take left free: row
+// pitches apart from the widths, the tile configuration forced or planned, the split count, the finishing epilogue on the
+// first product.  Every argument is checked before anything is launched; no output is zeroed first.
+extern "C" RpStatus rp_dbg_wgrad_ex(const void* Y0, int32_t ldy0, int32_t ny0, const void* X0, int32_t ldx0, int32_t nx0,
+                                    float* out0, const void* Y1, int32_t ldy1, int32_t ny1, const void* X1, int32_t ldx1,
+                                    int32_t nx1, float* out1, int32_t T, int32_t cfg, int32_t splits, float* g1, const float* w0,
+                                    const float* w1, const float* ln, float* dln_part, int32_t* plan_out, void* stream_) {
+  RP_REQUIRE(Y0 && X0 && out0 && plan_out, "null argument");
+  RP_REQUIRE(T >= 64 && T % 64 == 0, "T=%d is no positive multiple of 64", T);
+  RP_REQUIRE(splits >= 1 && splits <= T / 64, "splits=%d for %d token tiles", splits, T / 64);
+  RP_REQUIRE(cfg >= -1 && cfg <= 1, "cfg=%d", cfg);
+  auto operand_ok = [](const void* p, int ld, int n) {
+    return n >= 8 && n % 8 == 0 && ld >= n && ld % 8 == 0 && ((uintptr_t)p & 15) == 0;  // 16-byte DMA pieces
+  };
+  RP_REQUIRE(operand_ok(Y0, ldy0, ny0) && operand_ok(X0, ldx0, nx0), "product 0: ny=%d ldy=%d nx=%d ldx=%d", ny0, ldy0, nx0, ldx0);
+  const bool pair = Y1 != nullptr;
+  if (pair) {
+    RP_REQUIRE(X1 && out1, "null argument");
+    RP_REQUIRE(operand_ok(Y1, ldy1, ny1) && operand_ok(X1, ldx1, nx1), "product 1: ny=%d ldy=%d nx=%d ldx=%d", ny1, ldy1, nx1, ldx1);
+    RP_REQUIRE(cfg != 1, "a pair runs on 256 x 256 tiles only");
+  }
+  const bool finish = g1 || w0 || w1 || ln || dln_part;
+  if (finish) RP_REQUIRE(g1 && w0 && w1 && ln && dln_part, "the finishing epilogue: null argument");
+  const WgradFinish fin{1, g1, w0, w1, ln, dln_part};
+  hipStream_t stream = (hipStream_t)stream_;
+  plan_out[0] = pair ? 0 : cfg >= 0 ? cfg : plan_wgrad(ny0, nx0, T / 64).cfg;
+  plan_out[1] = splits;
+  if (!pair)
+    return launch_wgrad((const bf16_t*)Y0, ldy0, ny0, (const bf16_t*)X0, ldx0, nx0, T, splits, out0, stream, cfg,
+                        finish ? &fin : nullptr);
+  WgradOperands a{(const bf16_t*)Y0, ldy0, ny0, (const bf16_t*)X0, ldx0, nx0, out0};
+  if (finish) a.fin = fin;
+  const WgradOperands b{(const bf16_t*)Y1, ldy1, ny1, (const bf16_t*)X1, ldx1, nx1, out1};
+  return launch_wgrad_pair(a, b, T, splits, stream);
+}
+
+// No GPU call.  out[0], out[1] = (cfg, splits) of plan_wgrad(rows0, cols0, nk); out[2], out[3] = those of
+// plan_wgrad_pair(rows0, cols0, rows1, cols1, nk) (splits 0: the model prefers separate launches), -1 when rows1 == 0.
+extern "C" RpStatus rp_dbg_wgrad_plan(int32_t rows0, int32_t cols0, int32_t rows1, int32_t cols1, int32_t nk, int32_t* out) {
+  RP_REQUIRE(out, "null argument");
+  RP_REQUIRE(rows0 >= 1 && cols0 >= 1 && nk >= 1 && rows1 >= 0 && (rows1 == 0 || cols1 >= 1), "rows0=%d cols0=%d rows1=%d cols1=%d nk=%d",
+             rows0, cols0, rows1, cols1, nk);
+  const WgradPlan one = plan_wgrad(rows0, cols0, nk);
+  out[0] = one.cfg;
+  out[1] = one.splits;
+  out[2] = out[3] = -1;
+  if (rows1 > 0) {
+    const WgradPlan two = plan_wgrad_pair(rows0, cols0, rows1, cols1, nk);
+    out[2] = two.cfg;
+    out[3] = two.splits;
+  }
+  return RP_OK;
+}
+
 extern "C" RpStatus rp_dbg_attention_bwd(const void* qkv, const void* att, const void* datt, const int32_t* cu,
                                          const float* bias_tab, int32_t batch, int32_t H, int32_t rows_total, void* lse_out,
                                          void* att_out, void* dqkv, float* dtab /* [H, 257] */, void* stream_) {
@@ -954,6 +1024,62 @@ extern "C" RpStatus rp_dbg_attention_bwd(const void* qkv, const void* att, const
   (void)hipFree(part);
   (void)hipFree(bk);
   if (le != hipSuccess) return fail(RP_E_HIP, "attention backward launch failed: %s", hipGetErrorString(le));
+  return RP_OK;
+}
+
+// The training attention alone, as the trainer launches it: the forward (att_out + lse), both backward launches (delta, dqkv, the
+// table gradient's partial rows) and bias_grad_kernel with identity buckets, at any max_distance and under the trainer's dropout
+// (the mask is rp_dbg_dropout_mask(p, seed, site, row = s0 + i, col = (h << 20) | j)).  att != NULL: the O the backward reads for
+// delta instead of att_out.  Scratch (work list, partial rows, buckets) is allocated here; synchronises.  Everything is checked
+// before anything is launched; no output is zeroed first (rows T .. rows_total of att_out / dqkv / lse / delta are not written).
+extern "C" RpStatus rp_dbg_attention_train(const void* qkv, const void* att, const void* datt, const int32_t* cu, const float* bias_tab,
+                                           int32_t batch, int32_t H, int32_t rows_total, int32_t maxd, float p, uint32_t seed,
+                                           uint32_t site, float* lse_out, void* att_out, float* delta_out, void* dqkv, float* dtab,
+                                           void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RP_REQUIRE(qkv && datt && cu && bias_tab && lse_out && att_out && delta_out && dqkv && dtab, "null argument");
+  RP_REQUIRE(batch >= 1 && H >= 1 && rows_total >= GEMM_M_ALIGN && rows_total % GEMM_M_ALIGN == 0, "batch=%d, H=%d, rows_total=%d", batch,
+             H, rows_total);
+  RP_REQUIRE(maxd >= 1 && 2 * maxd + 1 + 128 <= ATT_TAB_MAX, "max_distance=%d", maxd);  // as rp_encoder_create
+  RP_REQUIRE(p >= 0.f && p < 1.f, "dropout probability %g", (double)p);
+  int T = 0;
+  {
+    std::vector<int32_t> h((size_t)batch + 1);
+    RP_HIP(hipMemcpyAsync(h.data(), cu, h.size() * 4, hipMemcpyDeviceToHost, stream));
+    RP_HIP(hipStreamSynchronize(stream));
+    T = h[batch];
+    RP_REQUIRE(h[0] == 0 && T >= 1 && T <= rows_total, "cu_seqlens runs %d .. %d for rows_total=%d", h[0], T, rows_total);
+    for (int i = 0; i < batch; ++i) RP_REQUIRE(h[i + 1] > h[i], "sequence %d is empty (cu_seqlens %d, %d)", i, h[i], h[i + 1]);
+  }
+  const Drop drop = make_drop(p, seed);
+  const int ntab = 2 * maxd + 1;
+  const dim3 grid(H, T / ATT_Q + batch);
+  const int n_p = T / POOL_CHUNK + batch;
+  int4* work = nullptr;
+  float* part = nullptr;
+  int32_t* bk = nullptr;
+  RP_HIP(hipMalloc((void**)&work, ((size_t)grid.y + n_p) * sizeof(int4)));
+  RP_HIP(hipMalloc((void**)&part, (size_t)grid.y * H * ntab * 4));
+  RP_HIP(hipMalloc((void**)&bk, (size_t)ntab * 4));
+  RP_HIP(hipMemsetAsync(part, 0, (size_t)grid.y * H * ntab * 4, stream));  // (the partial rows accumulate: backward_zero's part)
+  {
+    std::vector<int32_t> ident(ntab);
+    for (int i = 0; i < ntab; ++i) ident[i] = i;  // identity "buckets": the raw table gradient comes back, [ntab, H]
+    RP_HIP(hipMemcpy(bk, ident.data(), (size_t)ntab * 4, hipMemcpyHostToDevice));
+  }
+  launch_worklist(cu, batch, work, (int)grid.y, work + grid.y, n_p, POOL_CHUNK, stream);
+  launch_attention_train_fwd(grid, (const bf16_t*)qkv, (const int4*)work, bias_tab, (bf16_t*)att_out, H, maxd, lse_out, rows_total, drop,
+                             site, stream);
+  const bf16_t* o = att ? (const bf16_t*)att : (const bf16_t*)att_out;
+  launch_attention_bwd(grid, (const bf16_t*)qkv, o, (const bf16_t*)datt, lse_out, delta_out, (const int4*)work, bias_tab, (bf16_t*)dqkv,
+                       part, H, maxd, rows_total, 0, drop, site, stream);
+  launch_bias_grad(part, (int)grid.y, H, ntab, bk, ntab, dtab, stream);
+  const hipError_t le = hipGetLastError();
+  (void)hipStreamSynchronize(stream);
+  (void)hipFree(work);
+  (void)hipFree(part);
+  (void)hipFree(bk);
+  if (le != hipSuccess) return fail(RP_E_HIP, "attention launch failed: %s", hipGetErrorString(le));
   return RP_OK;
 }
 
@@ -1005,6 +1131,90 @@ extern "C" RpStatus rp_dbg_dgrad(const void* A, const void* W, int32_t M, int32_
   return launch_gemm(a, K, M, w, K, N, K,
                      EpiRmsBwdResid{(bf16_t*)out0, (bf16_t*)out0 + (size_t)M * N, N, N, (const bf16_t*)aux0, aux1}, stream,
                      RP_K_BWD_DGRAD, 0, nullptr, variant);
+}
+
+// One launch_gemm with a training epilogue and its dropout (tests/test_train_mfma_kernels_gpu.py).  A bf16 [M, K], W bf16 [N, K]
+// (exactly N rows), M % GEMM_M_ALIGN == 0.  The Drop is rp_trainer_set_dropout's and rp_dbg_dropout_mask's (make_drop), so the mask
+// read back with rp_dbg_dropout_mask(p, seed, site, ..) is the one the launch used.
+//   mode 0: the gated-GELU backward (EpiGegluBwd) over N = d_ff rows of W = Wo2^T.  aux0 = gu bf16 [M, ld] (2 N packed columns live),
+//           aux1 = rs [M]; out0 = dzs bf16 [M, ld], out1 = the row dot's slots f32 [ceil(N / 64), M], out2 = rcoef f32 [M] from
+//           launch_rowdot_finish over those slots with inv_d = 1 / K; p > 0: dff is masked at `site`.  variant 0 or 26.
+//   mode 1: the RMSNorm-backward residual.  aux0 = x bf16 [M, ld], aux1 = rcoef [M]; out0 / out1 = the hi / lo planes [M, ld],
+//           updated in place; p > 0: EpiRmsBwdResidT<true>, out2 = dxm bf16 [M, ld] under the mask of `site` (the trainer's
+//           next_site), p == 0: EpiRmsBwdResid, out2 unused.  variant 0 or 26.
+//   mode 2: the training forward's FFN-in epilogue, N = 2 d_ff packed rows.  aux1 = rs [M] (NULL: no row factor); out0 = gu bf16
+//           [M, N], out1 = ff bf16 [M, ld]; p > 0: EpiGegluTrainT<true> with the mask of `site`, p == 0: <false>.  variant -1:
+//           the forward's own choice (pick_gemm_variant).
+//   mode 3: the training forward's residual projections (EpiResidT<true>).  aux0 = the old hi plane bf16 [M, ld] (read only);
+//           out0 = the new hi plane [M, ld], out1 = the lo plane [M, ld], updated in place; out2 = ssp f32 [ceil(N / 64), M]
+//           or NULL; p > 0: the projection's output is masked at `site` before it is added.  variant -1: the forward's choice.
+// plan[6]: what launch_gemm_cfg launched, as rp_dbg_gemm_ex reports it.  Checked before anything is launched; nothing zeroed.
+extern "C" RpStatus rp_dbg_train_gemm(int32_t mode, const void* A, const void* W, int32_t M, int32_t N, int32_t K, const void* aux0,
+                                      const float* aux1, void* out0, void* out1, void* out2, int32_t ld, float p, uint32_t seed,
+                                      uint32_t site, int32_t variant, int32_t* plan, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RP_REQUIRE(mode >= 0 && mode <= 3, "mode=%d", mode);
+  RP_REQUIRE(A && W && out0 && out1 && plan, "null argument");
+  RP_REQUIRE(M >= GEMM_M_ALIGN && M % GEMM_M_ALIGN == 0 && K >= 32 && K % 32 == 0 && N >= 8 && N % 8 == 0, "M=%d, N=%d, K=%d", M, N, K);
+  RP_REQUIRE(p >= 0.f && p < 1.f, "dropout probability %g", (double)p);
+  const Drop drop = make_drop(p, seed);
+  const bf16_t* a = (const bf16_t*)A;
+  const bf16_t* w = (const bf16_t*)W;
+  auto gemm = [&]() -> RpStatus {
+    if (mode == 0)
+      return launch_gemm(a, K, M, w, K, N, K,
+                         EpiGegluBwd{(const bf16_t*)aux0, (bf16_t*)out0, ld, N, aux1, (float*)out1, (N + 63) / 64, M, drop, site}, stream,
+                         RP_K_BWD_DGRAD, 0, nullptr, variant);
+    if (mode == 1) {
+      if (drop.thresh)
+        return launch_gemm(a, K, M, w, K, N, K,
+                           EpiRmsBwdResidT<true>{(bf16_t*)out0, (bf16_t*)out1, ld, N, (const bf16_t*)aux0, aux1, (bf16_t*)out2, drop, site},
+                           stream, RP_K_BWD_DGRAD, 0, nullptr, variant);
+      return launch_gemm(a, K, M, w, K, N, K, EpiRmsBwdResid{(bf16_t*)out0, (bf16_t*)out1, ld, N, (const bf16_t*)aux0, aux1}, stream,
+                         RP_K_BWD_DGRAD, 0, nullptr, variant);
+    }
+    if (mode == 3)
+      return launch_gemm(a, K, M, w, K, N, K,
+                         EpiResidT<true>{(bf16_t*)out0, (bf16_t*)out1, ld, N, (float*)out2, (N + 63) / 64, M, (const bf16_t*)aux0, drop, site},
+                         stream, RP_K_GEMM_WO, 0, nullptr, variant);
+    const EpiStoreBf16 gu_store{(bf16_t*)out0, N, N, RowScale{aux1}};
+    if (drop.thresh)
+      return launch_gemm(a, K, M, w, K, N, K, EpiGegluTrainT<true>{gu_store, (bf16_t*)out1, ld, N, RowScale{aux1}, drop, site}, stream,
+                         RP_K_GEMM_WI, 0, nullptr, variant);
+    return launch_gemm(a, K, M, w, K, N, K, EpiGegluTrainT<false>{gu_store, (bf16_t*)out1, ld, N, RowScale{aux1}, drop, site}, stream,
+                       RP_K_GEMM_WI, 0, nullptr, variant);
+  };
+  if (mode == 0) {
+    RP_REQUIRE(aux0 && aux1 && out2, "null argument");
+    RP_REQUIRE(N % 64 == 0 && ld >= 2 * N && ld % 8 == 0, "gated GELU backward: N=%d, ld=%d", N, ld);
+    RP_REQUIRE(variant == 0 || variant == 26, "variant=%d", variant);
+  } else if (mode == 1) {
+    RP_REQUIRE(aux0 && aux1, "null argument");
+    RP_REQUIRE(ld >= N && ld % 8 == 0, "ld=%d, N=%d", ld, N);
+    RP_REQUIRE(variant == 0 || variant == 26, "variant=%d", variant);
+    RP_REQUIRE(!drop.thresh || (out2 && site != 0), "the masked form needs dxm and a site");
+  } else if (mode == 3) {
+    RP_REQUIRE(aux0, "null argument");
+    RP_REQUIRE(ld >= N && ld % 8 == 0, "ld=%d, N=%d", ld, N);
+    RP_REQUIRE(variant >= -1, "variant=%d", variant);
+  } else {
+    RP_REQUIRE(N % 64 == 0, "gated GELU: N=%d is not whole 32 / 32 row blocks", N);
+    RP_REQUIRE(ld >= N / 2 && ld % 8 == 0, "ld=%d, N=%d", ld, N);
+    RP_REQUIRE(variant >= -1, "variant=%d", variant);
+  }
+  g_gemm_check_only = true;  // launch_gemm's and launch_gemm_cfg's own requirements first, nothing launched
+  RpStatus st = gemm();
+  g_gemm_check_only = false;
+  if (st) return st;
+  st = gemm();
+  if (mode == 0 && st == RP_OK) {
+    launch_rowdot_finish((const float*)out1, (N + 63) / 64, M, aux1, 1.f / (float)K, (float*)out2, M, stream);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) st = fail(RP_E_HIP, "rowdot_finish launch failed: %s", hipGetErrorString(le));
+  }
+  const GemmLaunchPlan& lp = g_last_gemm_plan;
+  plan[0] = lp.variant, plan[1] = lp.form, plan[2] = lp.tiles_f, plan[3] = lp.tiles_t, plan[4] = lp.n_helpers, plan[5] = lp.full_rows;
+  return st;
 }
 
 // ---- the encoder's pooling head, training row kernels and weight pack / unpack kernels in isolation -------------------------

@@ -264,9 +264,10 @@ def geglu_split(P):
 
 
 def gemm_expected(epi: int, P, S, K: int, x0=None, rs=None, rs_rel: float = 0.0, extra: Optional[float] = None,
-                  exact_acc: bool = False, mutant: Optional[str] = None) -> Tuple[np.ndarray, np.ndarray]:
+                  exact_acc: bool = False, mutant: Optional[str] = None, round_out: bool = True) -> Tuple[np.ndarray, np.ndarray]:
     """-> (ref, bar), float64 [M, n] (GEGLU: [M, n / 2]) from the products' first n columns.  rs: float64 [M] or None;
     ``rs_rel``: the relative error allowed to the kernel's own factor; exact_acc: the integer-operand cases (acc_bar = 0).
+    round_out=False (STORE, GEGLU): the bar of the fp32 value in front of the bf16 rounding (a caller that scales it first).
     Mutants (the CPU test's planted bugs IN THE REFERENCE's place): "resid_overwrites", "geglu_up_row_plus_31",
     "rs_neighbour_row"."""
     e = np.zeros_like(S) if exact_acc else acc_bar(S, K)
@@ -277,7 +278,7 @@ def gemm_expected(epi: int, P, S, K: int, x0=None, rs=None, rs_rel: float = 0.0,
     if epi == EPI_STORE:
         ref = P * r
         pre = r * e + ((U32 + rs_rel) * np.abs(ref) if rs is not None else 0.0)  # (no factor: acc * 1 is exact)
-        return ref, pre + bf16_half_ulp(ref, pre)
+        return ref, pre + (bf16_half_ulp(ref, pre) if round_out else 0.0)
     if epi in (EPI_RESID, EPI_RESID8):
         ref = P if mutant == "resid_overwrites" else x0 + P
         return ref, e + (U32 + (2.0 ** -17 if epi == EPI_RESID else 2.0 ** -16)) * (np.abs(ref) + e)
@@ -292,7 +293,7 @@ def gemm_expected(epi: int, P, S, K: int, x0=None, rs=None, rs_rel: float = 0.0,
     d = np.maximum(np.abs(gelu_new_grad(a0 - e0)), np.abs(gelu_new_grad(a0 + e0)))
     d = np.maximum(d, np.abs(gelu_new_grad(a0)))
     pre = d * np.abs(a1) * e0 + np.abs(gelu_new(a0)) * e1 + 1.2 * e0 * e1 + (FASTMATH_ENC_GEGLU if extra is None else extra)
-    return ref, pre + bf16_half_ulp(ref, pre)
+    return ref, pre + (bf16_half_ulp(ref, pre) if round_out else 0.0)
 
 
 def ssp_reference(x_stored, np_out: int) -> Tuple[np.ndarray, np.ndarray]:
